@@ -7,7 +7,11 @@ environments: uniform-random policy draw -> place the block -> contact interface
 candidates -> (A+1) 64x64 f32 rasters -> bounds/overlap mask -> linear reward  (SURVEY.md §8d).
 `value` counts real environment steps (reset-only lock-steps of an env are not counted).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR writes, after the timed steps, what the last timed lock-step left for a caller (flags, rewards, blocks,
+candidates, a fixed seeded sample of the rasters) as DIR/<name>.npy, at most 64 MB (see dump_outputs()); with the same
+arguments the inputs are the same on every run, so two builds can be compared array for array.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (a
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` child,
@@ -69,6 +73,100 @@ def task_of(args):
         obstacles = [(0.5, 0.0, i * H + H / 2) for i in range(n)]
         label = "bridge_setup(num_stories=%d)" % n
     return names, obstacles, targets, label
+
+
+# ------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240917        # fixes which envs / candidates are sampled; independent of the policy seeds
+
+
+def dump_outputs(genv, out_dir, envs_per_rank, env_id_base=0):
+    """What the last lock-step of the timed path left for a caller, as DIR/<name>.npy (float32 where the buffer is float32
+    or a small integer, float64 for float64 buffers and for 64-bit masks split into two exact uint32 halves).
+
+    env_*   every env of this rank (a fixed seeded sample of 16384 if there are more): flags, reward, counters.
+    blk_* / state_bits / cand_*   a fixed seeded sample of envs (``sample_env``, global env ids), with every raw candidate
+            of each (``cand_env`` = its position in ``sample_env``); the sample size keeps the total under 64 MB.
+    state_raster / cand_raster   f32 images of the first 64 sampled envs and of at most 16 candidates of each of the
+            first 16 (rows listed in ``cand_raster_row``; absent with --no-f32-rasters)."""
+    import numpy as np
+    import torch
+    from bridges_hip.abi import FLAG_NAMES
+
+    E = envs_per_rank
+    g_of = np.concatenate([np.full(g.E, i) for i, g in enumerate(genv.envs)])
+    loc_of = np.concatenate([np.arange(g.E) for g in genv.envs])
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    a_max = max(g.a_max for g in genv.envs)
+    K = genv.envs[0].K
+    res = {}
+
+    def gather(name, rows):
+        """buffer `name` (leading dim E of each group) at env rows `rows` of this rank -> numpy"""
+        parts = []
+        for i, g in enumerate(genv.envs):
+            sel = loc_of[rows][g_of[rows] == i]
+            idx = torch.as_tensor(sel, device=g.device, dtype=torch.long)
+            parts.append((np.nonzero(g_of[rows] == i)[0], g.buf[name][idx].cpu().numpy()))
+        shape = parts[0][1].shape[1:]
+        full = np.empty((len(rows),) + shape, dtype=parts[0][1].dtype)
+        for pos, v in parts:
+            full[pos] = v
+        return full
+
+    def bits(v):
+        v = v.astype(np.int64)
+        return np.stack([(v & 0xFFFFFFFF).astype(np.float64), ((v >> 32) & 0xFFFFFFFF).astype(np.float64)], axis=-1)
+
+    all_rows = np.arange(E) if E <= 16384 else np.sort(rng.choice(E, 16384, replace=False))
+    res["env_id"] = (all_rows + env_id_base).astype(np.float64)
+    flags = gather("step_flags", all_rows)
+    for i, n in enumerate(FLAG_NAMES):
+        res["env_" + n] = (flags[:, i] != 0).astype(np.float32)
+    res["env_flag_bits"] = flags[:, 7].astype(np.float32)
+    for n in ("reward", "lin_reward", "n_blocks", "n_reached", "n_cand", "n_valid", "sel_index", "targets_left", "n_if"):
+        res["env_" + n] = gather(n, all_rows).astype(np.float32 if n != "targets_left" else np.float64)
+    res["env_draw_counter"] = gather("draw_counter", all_rows).astype(np.float64)
+
+    # per sampled env: blocks K*(4*8 + 4 + 1) + state bits 64*16 + interfaces; per candidate row <= 8*(4 + 4) + 4*6 bytes
+    n_heavy = min(E, 1024, max(1, (40 << 20) // (a_max * 56 + K * 48 + 64 * 16)))
+    samp = np.sort(rng.choice(E, n_heavy, replace=False))
+    res["sample_env"] = (samp + env_id_base).astype(np.float64)
+    res["blk_shape"] = gather("blk_shape", samp).astype(np.float32)
+    res["blk_pose"] = gather("blk_pose", samp).astype(np.float64)
+    res["blk_occ"] = gather("blk_occ", samp).astype(np.float32)
+    res["state_bits"] = bits(gather("state_bits", samp))
+    has_f32 = genv.envs[0].buf["state_raster"] is not None
+    if has_f32:
+        res["state_raster"] = gather("state_raster", samp[:64]).astype(np.float32)
+
+    cand = {n: [] for n in ("cand_env", "cand_desc", "cand_pose", "cand_ox", "cand_inb", "cand_mask", "cand_lin", "cand_stable")}
+    rast_rows, rast = [], []
+    for j, r in enumerate(samp):
+        g = genv.envs[g_of[r]]
+        lo, hi = (int(v) for v in g.buf["cand_offset"][loc_of[r]:loc_of[r] + 2].cpu())
+        cand["cand_env"].append(np.full(hi - lo, j, dtype=np.float32))
+        for n in ("cand_desc", "cand_inb", "cand_mask", "cand_lin", "cand_stable"):
+            cand[n].append(g.buf[n][lo:hi].cpu().numpy().astype(np.float32))
+        for n in ("cand_pose", "cand_ox"):
+            cand[n].append(g.buf[n][lo:hi].cpu().numpy().astype(np.float64))
+        if has_f32 and j < 16:
+            m = min(hi - lo, 16)
+            rast_rows.append(np.stack([np.full(m, j), np.arange(m)], axis=1).astype(np.float32))
+            rast.append(g.buf["cand_raster"][lo:lo + m].cpu().numpy().astype(np.float32))
+    for n, v in cand.items():
+        res[n] = np.concatenate(v)
+    if has_f32:
+        res["cand_raster_row"] = np.concatenate(rast_rows)
+        res["cand_raster"] = np.concatenate(rast)
+
+    total = sum(v.nbytes for v in res.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for n, v in res.items():
+        np.save(os.path.join(out_dir, n + ".npy"), v)
+    return {"dir": out_dir, "arrays": len(res), "bytes": total, "sampled_envs": int(n_heavy)}
 
 
 # ------------------------------------------------------------------------- CPU baseline (oracle)
@@ -363,6 +461,8 @@ def parse_args():
                     help="(internal) run only BASELINE configs[3]'s training leg on the ranks of this job and print its JSON")
     ap.add_argument("--sparse-raster-update", action="store_true",
                     help="f32 rasters, but only the row groups that change are stored (reported as its own mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed lock-step (of the last seed) computed as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -502,6 +602,10 @@ def main():
     env = runs[-1]["env"]                              # (side figures of the candidate-stability mode read the last set)
     dt, d, env_steps, dt_all, steps_all = med["dt"], med["d"], med["env_steps"], med["dt_all"], med["steps_all"]
     raster_ms, n_launch, cand_ev, cand_count = med["raster_ms"], med["n_launch"], runs[-1]["cand_ev"], runs[-1]["cand_count"]
+    dumped = None
+    if args.dump_outputs and rank == 0:                # untimed: the env set of the last seed still holds its last lock-step
+        env.sync()
+        dumped = dump_outputs(env, args.dump_outputs, args.envs, env_id_base=rank * args.envs)
 
     def release():
         """Drop every environment set (18.8 GB of raster buffers each) before a side mode allocates its own."""
@@ -607,6 +711,8 @@ def main():
                                   "queued_large_tableaux": int(g0.cand_counters[0])}}
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if use_pg:
             release()
         plain = not (args.no_f32_rasters or args.sparse_raster_update or args.debug or cand_mode or args.bridge_length

@@ -152,8 +152,8 @@ def shape_from_urdf_name(urdf_file, **kw):
 
 # --------------------------------------------------------------------------
 # Mesh route: derive the same table from a URDF + binary STL on disk.  Used by
-# tests (when /root/reference is present) to prove the hard-coded tables above
-# are what the reference's loader would produce.
+# tests (against tests/golden/reference_meshes.json) to prove the hard-coded
+# tables above are what the reference's loader would produce.
 # --------------------------------------------------------------------------
 
 def read_binary_stl(path):

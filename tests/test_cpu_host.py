@@ -368,6 +368,64 @@ def test_bench_starts_its_own_ranks_for_gpus_n(monkeypatch):
     assert seen["env"]["MASTER_ADDR"] == "127.0.0.1"
 
 
+def test_bench_dump_outputs_writes_the_last_lockstep_of_every_group(tmp_path):
+    """bench.py --dump-outputs on a stand-in env set (two groups of CPU buffers in the layout of VecAssemblyGym): one .npy
+    per array, float32 / float64 only, under 64 MB, the same files twice for the same state, and the candidate rows of a
+    sampled env are that env's rows of its own group."""
+    import importlib
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    gen = torch.Generator().manual_seed(3)
+    K, a_max = 15, 40
+
+    def group(n):
+        n_cand = torch.randint(0, a_max + 1, (n,), generator=gen)
+        off = torch.zeros(n + 1, dtype=torch.int32)
+        off[1:] = torch.cumsum(n_cand, 0)
+        C = int(off[-1])
+        buf = dict(step_flags=torch.randint(0, 2, (n, 8), generator=gen, dtype=torch.uint8),
+                   reward=torch.randn(n, generator=gen), lin_reward=torch.randn(n, generator=gen),
+                   n_blocks=torch.randint(0, K, (n,), generator=gen, dtype=torch.int32), n_reached=torch.zeros(n, dtype=torch.int32),
+                   n_cand=n_cand.int(), n_valid=n_cand.int() // 2, sel_index=torch.zeros(n, dtype=torch.int32),
+                   targets_left=torch.ones(n, dtype=torch.int32), n_if=torch.zeros(n, dtype=torch.int32),
+                   draw_counter=torch.arange(n, dtype=torch.int64), blk_shape=torch.zeros((n, K), dtype=torch.int32),
+                   blk_pose=torch.randn((n, K, 4), generator=gen, dtype=torch.float64), blk_occ=torch.zeros((n, K), dtype=torch.uint8),
+                   state_bits=torch.randint(-2**62, 2**62, (n, 64), generator=gen, dtype=torch.int64), cand_offset=off,
+                   cand_desc=torch.randint(0, 9, (C, 4), generator=gen, dtype=torch.int32),
+                   cand_pose=torch.randn((C, 4), generator=gen, dtype=torch.float64), cand_ox=torch.randn(C, generator=gen, dtype=torch.float64),
+                   cand_inb=torch.ones(C, dtype=torch.uint8), cand_mask=torch.randint(0, 2, (C,), generator=gen, dtype=torch.uint8),
+                   cand_lin=torch.randn(C, generator=gen), cand_stable=torch.zeros(C, dtype=torch.uint8),
+                   state_raster=torch.rand((n, 64, 64), generator=gen), cand_raster=torch.rand((C, 64, 64), generator=gen))
+        return types.SimpleNamespace(E=n, K=K, a_max=a_max, device=torch.device("cpu"), buf=buf)
+
+    genv = types.SimpleNamespace(envs=[group(150), group(149)])
+    info = bench.dump_outputs(genv, str(tmp_path / "a"), 299, env_id_base=0)
+    bench.dump_outputs(genv, str(tmp_path / "b"), 299, env_id_base=0)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == info["arrays"] and all(n.endswith(".npy") for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total == info["bytes"] <= 64 << 20
+    ld = lambda n: np.load(tmp_path / "a" / (n + ".npy"))
+    assert np.array_equal(ld("env_reward"), torch.cat([g.buf["reward"] for g in genv.envs]).numpy())
+    samp = ld("sample_env").astype(int)
+    assert len(samp) == 299 and np.array_equal(samp, np.arange(299))
+    cand_env, pose = ld("cand_env").astype(int), ld("cand_pose")
+    for j in (0, 149, 150, 298):                                  # first / last env of each group
+        g, e = genv.envs[samp[j] // 150], samp[j] % 150
+        lo, hi = int(g.buf["cand_offset"][e]), int(g.buf["cand_offset"][e + 1])
+        assert np.array_equal(pose[cand_env == j], g.buf["cand_pose"][lo:hi].numpy())
+    bits = ld("state_bits")
+    want = torch.cat([g.buf["state_bits"] for g in genv.envs]).numpy()
+    assert np.array_equal(bits[..., 0].astype(np.int64) | (bits[..., 1].astype(np.int64) << 32), want)
+    assert ld("state_raster").shape == (64, 64, 64) and ld("cand_raster").shape[0] == len(ld("cand_raster_row"))
+
+
 def test_image_size_rule_and_deferred_losses_without_a_gpu():
     """Host-side pieces that need no device: the image sizes the rasteriser accepts (--image_size, successor_dqn.py:585)
     and the empty DeferredLosses a training call returns before the replay holds a batch."""

@@ -88,21 +88,28 @@ def test_notebook_cell24_25_distances_bit_exact(golden_dir):
         assert env.distance_to_targets() == gold["distance_to_targets"]     # float-exact
 
 
-REF_SHAPES = "/root/reference/assembly_gym/shapes"
+PKG_SHAPES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                          "bridges-with-reinforcement-learning_amd", "assembly_gym", "shapes")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SHAPES), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", sorted(SHAPES))
-def test_shape_tables_match_reference_meshes(name):
+def test_shape_tables_match_reference_meshes(name, golden_dir):
     """The hard-coded outlines are what the reference's loader (merge order of
-    geometry.py:9-21, 2-D face filter of assembly_env.py:50) yields on its files."""
-    verts, faces, depth = shape_from_urdf_file(os.path.join(REF_SHAPES, name + ".urdf"))
+    geometry.py:9-21, 2-D face filter of assembly_env.py:50) yields on its files
+    (stored in reference_meshes.json), and the mesh route reads the same outline
+    from the package's own URDF / STL files."""
+    ref = _load(golden_dir, "reference_meshes.json")[name]
+    verts = [tuple(v) for v in ref["verts"]]
+    faces = [tuple(f) for f in ref["faces"]]
+    depth = ref["depth"]
     s = get_shape(name)
     edges_ref = [(verts[a], verts[b]) for a, b in faces]
     edges_tab = [(s.verts[a], s.verts[b]) for a, b in s.faces]
     assert edges_ref == edges_tab
-    assert [tuple(v) for v in verts] == s.verts and [tuple(f) for f in faces] == s.faces
+    assert verts == s.verts and faces == s.faces
     assert depth == s.depth
+    pv, pf, pd = shape_from_urdf_file(os.path.join(PKG_SHAPES, name + ".urdf"))
+    assert [tuple(v) for v in pv] == verts and [tuple(f) for f in pf] == faces and pd == depth
 
 
 def test_row_run_rasteriser_algorithm_equals_the_per_pixel_test():

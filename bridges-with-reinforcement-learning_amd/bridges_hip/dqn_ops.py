@@ -52,6 +52,25 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
     return q_target, sf_target, argmax_row
 
 
+def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None):
+    """The TD targets of transitions whose next-state rows are the segments ``seg`` of ``next_q`` (td_target's seg_offset).
+    -> (q [B], sf [B, D] or None).  With ``lin``: q = lin + gamma q' of each segment's arg-max row, sf = lin + gamma psi' of
+    that row + the action raster.  lin=None is the single-env reference form: q is the done-masked q' of the arg-max row (lin 0,
+    gamma 1 -- the caller adds its [B, 1] lin_reward by broadcasting) and sf takes lin 0.  ``next_sf``: psi' of every row, or
+    a callable that returns psi' of the arg-max rows from their indices (callers that compute it for those rows only)."""
+    nq = next_q.contiguous().float()
+    zeros = torch.zeros(done.numel(), dtype=torch.float32, device=nq.device) if lin is None else lin
+    q, _, arg = td_target(seg, nq, zeros, done, 1.0 if lin is None else gamma)
+    if next_sf is None:
+        return q, None
+    if callable(next_sf):
+        best = arg.long().clamp_(0, nq.numel() - 1)                       # empty segments are 'done': row unused
+        next_sf = next_sf(best)
+        seg, nq = torch.arange(done.numel() + 1, dtype=torch.int32, device=nq.device), nq[best].contiguous()
+    _, sf, _ = td_target(seg, nq, zeros, done, gamma, next_sf=next_sf, action_raster=action_raster)
+    return q, sf
+
+
 def soft_update_(target, policy, tau):
     """target <- policy * tau + target * (1 - tau) in place (successor_dqn.py:280-288); float32 contiguous tensors."""
     L = abi.require_gpu()

@@ -237,8 +237,8 @@ class FusedSuccessorStep:
             now = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
             if now != (self.lr, self.beta1, self.beta2, self.eps):
                 raise RuntimeError(f"the optimiser's hyper-parameters changed after the fused step adopted them "
-                                   f"({(self.lr, self.beta1, self.beta2, self.eps)} -> {now}): rebuild the step (VecDQN re-captures "
-                                   "its graph when _graph_state is reset)")
+                                   f"({(self.lr, self.beta1, self.beta2, self.eps)} -> {now}): rebuild the step "
+                                   "(robotoddler.training.train_step.release(policy_net): the next call captures it afresh)")
 
     def launch(self, counter, block_all, action_all, binary_all, reward, obstacle, q_target_all, sf_target_all, losses):
         L, rows, px, nf, B = self.L, self.rows, self.px, self.nf, self.batch

@@ -31,6 +31,7 @@ from assembly_gym.envs.gym_env import (AssemblyGym, bridge_setup, horizontal_bri
 from assembly_gym.utils.rendering import render_blocks_2d_bits                            # noqa: E402
 from bridges_hip import dqn_ops, ops                                                      # noqa: E402
 from robotoddler.models.cv import ConvNet, Policy, SuccessorMLP                           # noqa: E402
+from robotoddler.training import train_step as T                                         # noqa: E402
 from robotoddler.utils.actions import filter_actions, generate_actions                    # noqa: E402
 from robotoddler.utils.replay_memory import PrioritizedReplayBuffer, ReplayBuffer          # noqa: E402
 from robotoddler.utils.utils import (convolve_with_gaussian, init_weights, parse_img_size,   # noqa: E402
@@ -125,167 +126,86 @@ def _tagged(t, key):
     return t
 
 
-class _FusedTrainer:
-    """train_policy_net's optimiser steps for a SuccessorMLP on the hand-written step of the vectorised loop
-    (bridges_hip/mlp_ops.py FusedSuccessorStep: forward, both MSE losses, backward and Adam as ~11 launches on the f32
-    matrix cores instead of ~60 library / element-wise ones, no host wait per step).  Same losses as the autograd form:
-    the reference's q target is the [B, B] broadcast  lin_reward[j] + gamma q'[i]  (successor_dqn.py:222 with :435), whose
+def _fused_applies(policy_net, optimizer, loss_parts, scheduler, transitions, batch=None, device=None):
+    """train_policy_net's optimiser steps go through the hand-written SuccessorMLP step (train_step.CapturedTrainStep) when the
+    transitions share one task fingerprint: one reward / obstacle vector per batch.  Same losses as the autograd form: the
+    reference's q target is the [B, B] broadcast  lin_reward[j] + gamma q'[i]  (successor_dqn.py:222 with :435), whose
     mean-squared error against q[i] is  mean_i (q[i] - (mean(lin) + gamma q'[i]))^2 + var(lin)  -- the same gradient as the
     element-wise target mean(lin) + gamma q'[i]; the constant var(lin) is added to the logged loss."""
-
-    def __init__(self, policy_net, optimizer, batch_size, loss_parts):
-        from bridges_hip.mlp_ops import FusedSuccessorStep
-        self.key = (id(optimizer), batch_size, tuple(loss_parts))
-        self.use_q, self.use_sf = 'mse_q_values' in loss_parts, 'mse_block_features' in loss_parts
-        self.step = FusedSuccessorStep(policy_net, batch_size, self.use_q, self.use_sf, optimizer=optimizer)
-        if not self.step.fused_adam:
-            raise ValueError("the optimiser is not a plain Adam over the net's flattened parameters")
-        dev = self.step.flat.device
-        self.counter = torch.zeros((), dtype=torch.int64, device=dev)
-        self.loss1 = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._graphs, self._seen = {}, {}
-
-    def _steps(self, n, *tensors):
-        """n optimiser steps on the n batches in ``tensors`` (block, action, binary, reward, obstacle, q target, sf target,
-        losses).  The first call with a given n queues n x 11 launches; from the second on the sequence is one HIP graph over
-        static copies of the inputs (a launch costs the host ~7 us, a step is ~100 us of GPU work: queued one by one the host
-        and the GPU take about the same time, as a graph the host is free after one launch).  BRIDGES_TRAIN_GRAPH=0: never."""
-        st = self.step
-        self.counter.zero_()
-        g = self._graphs.get(n)
-        if g is None:
-            seen = self._seen[n] = self._seen.get(n, 0) + 1
-            if seen == 1 or os.environ.get("BRIDGES_TRAIN_GRAPH", "1") != "1":
-                for _ in range(n):
-                    st.launch(self.counter, *tensors)
-                return tensors[-1]
-            bufs = [torch.empty_like(t) if t is not None else None for t in tensors]
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for _ in range(n):
-                    st.launch(self.counter, *bufs)
-            g = self._graphs[n] = (graph, bufs)
-        graph, bufs = g
-        for dst, src in zip(bufs[:-1], tensors[:-1]):
-            if dst is not None:
-                dst.copy_(src)
-        bufs[-1].zero_()
-        graph.replay()
-        return bufs[-1].clone()
-
-    @staticmethod
-    def applies(policy_net, optimizer, loss_parts, scheduler, transitions, batch=None, device=None):
-        if scheduler is not None or not isinstance(policy_net, SuccessorMLP) or getattr(policy_net, "_flat_params", None) is None:
+    if scheduler is not None or getattr(policy_net, "_flat_params", None) is None or type(optimizer) is not torch.optim.Adam:
+        return False
+    if not T.fused_step_enabled(policy_net, loss_parts) or not transitions:
+        return False
+    if batch is not None:
+        if not batch.block_features.is_cuda or batch.block_features.dtype != torch.float32:
             return False
-        if not set(loss_parts) <= {'mse_q_values', 'mse_block_features'} or type(optimizer) is not torch.optim.Adam:
-            return False
-        if not transitions:
-            return False
-        if batch is not None:
-            if not batch.block_features.is_cuda or batch.block_features.dtype != torch.float32:
-                return False
-        elif torch.device(device).type != 'cuda' or any(t.block_features.dtype != torch.float32 for t in transitions):
-            return False
-        keys = {getattr(t.reward_features, "_task_key", None) for t in transitions}
-        return len(keys) == 1 and None not in keys and all(getattr(t.obstacle_features, "_task_key", None) in keys for t in transitions)
-
-    @classmethod
-    def of(cls, policy_net, optimizer, batch_size, loss_parts):
-        """The net's trainer for this optimiser / batch size / loss, built on first use; None if the optimiser is not a plain
-        Adam over the flattened parameters."""
-        tr = getattr(policy_net, "_fused_trainer", None)
-        if tr is None or tr.key != (id(optimizer), batch_size, tuple(loss_parts)):
-            try:
-                sync_fused_optimizer(policy_net)
-                tr = policy_net._fused_trainer = cls(policy_net, optimizer, batch_size, loss_parts)
-            except ValueError:
-                return None
-        return tr
-
-    def run_all(self, drawn, target_net, gamma, device):
-        """All optimiser steps of one train_policy_net call: ``drawn`` = the sampled transitions of every step.  The target net
-        does not change inside the call, so the TD targets of all steps come from ONE target forward and ONE segmented argmax
-        over all next-action rows, and the steps are launch sequences that read their batch by a device-side counter
-        (FusedSuccessorStep.launch): per step the host queues 11 launches and nothing else.  A transition drawn several times
-        (the draws are with replacement across the steps; 20 x 32 draws from a buffer of a few hundred) is stacked and
-        evaluated once and its rows are gathered; the rows of a next state are gathered from one copy per transition; the
-        task's reward / obstacle rasters are the same image for every row."""
-        n, st = len(drawn), self.step
-        B, px = st.batch, st.px
-        slot, uniq, which = {}, [], []
-        for b in drawn:
-            for t in b:
-                k = slot.get(id(t))
-                if k is None:
-                    k = slot[id(t)] = len(uniq)
-                    uniq.append(t)
-                which.append(k)
-        cat = lambda field: torch.cat([getattr(t, field) for t in uniq]).to(device=device)
-        num_actions = [max(1, len(t.next_available_actions)) for t in uniq]
-        assert [t.next_actions_features.shape[0] for t in uniq] == num_actions, "a next state's action rows and its action list differ"
-        seg_np = np.zeros(len(uniq) + 1, dtype=np.int32)
-        np.cumsum(num_actions, out=seg_np[1:])
-        owner = np.repeat(np.arange(len(uniq), dtype=np.int64), num_actions)
-        seg, done, owner, which = ops.upload(device, seg_np, np.asarray([t.done for t in uniq], dtype=np.bool_), owner,
-                                             np.asarray(which, dtype=np.int64))
-        rows = int(seg_np[-1])
-        reward, obstacle = uniq[0].reward_features.to(device), uniq[0].obstacle_features.to(device)
-        with torch.no_grad():
-            action_u = cat('action_features')
-            one_row = lambda x: x.shape[0] == 1 or x.stride(0) == 0              # rollout_episode stores expand()ed views
-            if all(one_row(t.next_block_features) and one_row(t.next_binary_features) for t in uniq):
-                nb = torch.cat([t.next_block_features[:1] for t in uniq]).to(device).index_select(0, owner)
-                nbin = torch.cat([t.next_binary_features[:1] for t in uniq]).to(device).index_select(0, owner)
-            else:
-                nb, nbin = cat('next_block_features'), cat('next_binary_features')
-            next_q, next_sf, _ = target_net(nb, nbin, cat('next_actions_features'), reward.expand(rows, -1, -1, -1),
-                                            obstacle.expand(rows, -1, -1, -1))
-            zeros = torch.zeros(len(uniq), dtype=torch.float32, device=device)
-            nq = next_q.contiguous().float()
-            q_sel, _, _ = dqn_ops.td_target(seg, nq, zeros, done, 1.0)
-            sf_target = None
-            if self.use_sf:
-                _, sf_target, _ = dqn_ops.td_target(seg, nq, zeros, done, gamma, next_sf=next_sf[:, 0], action_raster=action_u.squeeze(1))
-                sf_target = sf_target.reshape(len(uniq), px).index_select(0, which)
-            st.check_hyperparameters()
-            q_target = extra = None
-            if self.use_q:
-                lin = cat('lin_reward').reshape(-1).float().index_select(0, which).view(n, B)
-                m = lin.mean(dim=1, keepdim=True)
-                q_target = (m + gamma * q_sel.index_select(0, which).view(n, B)).reshape(-1).contiguous()
-                extra = ((lin - m) ** 2).mean(dim=1)
-            losses = torch.zeros(n, dtype=torch.float32, device=device)
-            losses = self._steps(n, cat('block_features').reshape(len(uniq), px).index_select(0, which),
-                                 action_u.reshape(len(uniq), px).index_select(0, which), cat('binary_features').index_select(0, which),
-                                 reward.reshape(px).contiguous(), obstacle.reshape(px).contiguous(), q_target, sf_target, losses)
-        return losses + extra if extra is not None else losses
-
-    def run(self, batch, q_sel, sf_target, gamma):
-        B = batch.block_features.shape[0]
-        st = self.step
-        st.check_hyperparameters()
-        lin = batch.lin_reward.reshape(-1).float()
-        extra = None
-        q_target = None
-        if self.use_q:
-            m = lin.mean()
-            q_target = (m + gamma * q_sel).contiguous()
-            extra = ((lin - m) ** 2).mean()
-        self.counter.zero_()
-        px = st.px
-        st.launch(self.counter, batch.block_features.reshape(B, px).contiguous(), batch.action_features.reshape(B, px).contiguous(),
-                  batch.binary_features.contiguous(), batch.reward_features[0].reshape(px).contiguous(),
-                  batch.obstacle_features[0].reshape(px).contiguous(), q_target,
-                  sf_target.reshape(B, px).contiguous() if self.use_sf else None, self.loss1)
-        return self.loss1[0] + extra if extra is not None else self.loss1[0].clone()
+    elif torch.device(device).type != 'cuda' or any(t.block_features.dtype != torch.float32 for t in transitions):
+        return False
+    keys = {getattr(t.reward_features, "_task_key", None) for t in transitions}
+    return len(keys) == 1 and None not in keys and all(getattr(t.obstacle_features, "_task_key", None) in keys for t in transitions)
 
 
-def sync_fused_optimizer(policy_net):
-    """Hand Adam's step count back to the torch optimiser (its moments already are the fused step's buffers): call before
-    optimizer.state_dict() / optimizer.step() when train_policy_net may have run on the hand-written step."""
-    tr = getattr(policy_net, "_fused_trainer", None)
-    if tr is not None:
-        tr.step.export_state()
+def _fused_driver(policy_net, optimizer, batch_size, loss_parts, n):
+    """The net's driver of the hand-written step, or None if the optimiser is not a plain Adam over the flattened parameters."""
+    try:
+        return T.CapturedTrainStep.of(policy_net, optimizer, batch_size, loss_parts, n, img=policy_net.img_size, fused=True)
+    except ValueError:
+        return None
+
+
+def _run_fused(tr, drawn, target_net, gamma, device):
+    """The optimiser steps on the batches ``drawn`` (lists of transitions of one task).  The target net does not change inside a
+    train_policy_net call, so the TD targets of all steps come from ONE target forward and ONE segmented argmax over all
+    next-action rows, and the steps are launch sequences that read their batch by a device-side counter: per step the host
+    queues 11 launches and nothing else.  A transition drawn several times (the draws are with replacement across the steps;
+    20 x 32 draws from a buffer of a few hundred) is stacked and evaluated once and its rows are gathered; the rows of a next
+    state are gathered from one copy per transition; the task's reward / obstacle rasters are the same image for every row."""
+    n, B, px = len(drawn), tr.B, tr.img[0] * tr.img[1]
+    slot, uniq, which = {}, [], []
+    for b in drawn:
+        for t in b:
+            k = slot.get(id(t))
+            if k is None:
+                k = slot[id(t)] = len(uniq)
+                uniq.append(t)
+            which.append(k)
+    cat = lambda field: torch.cat([getattr(t, field) for t in uniq]).to(device=device)
+    num_actions = [max(1, len(t.next_available_actions)) for t in uniq]
+    assert [t.next_actions_features.shape[0] for t in uniq] == num_actions, "a next state's action rows and its action list differ"
+    seg_np = np.zeros(len(uniq) + 1, dtype=np.int32)
+    np.cumsum(num_actions, out=seg_np[1:])
+    owner = np.repeat(np.arange(len(uniq), dtype=np.int64), num_actions)
+    seg, done, owner, which = ops.upload(device, seg_np, np.asarray([t.done for t in uniq], dtype=np.bool_), owner,
+                                         np.asarray(which, dtype=np.int64))
+    rows = int(seg_np[-1])
+    reward, obstacle = uniq[0].reward_features.to(device), uniq[0].obstacle_features.to(device)
+    with torch.no_grad():
+        action_u = cat('action_features')
+        one_row = lambda x: x.shape[0] == 1 or x.stride(0) == 0              # rollout_episode stores expand()ed views
+        if all(one_row(t.next_block_features) and one_row(t.next_binary_features) for t in uniq):
+            nb = torch.cat([t.next_block_features[:1] for t in uniq]).to(device).index_select(0, owner)
+            nbin = torch.cat([t.next_binary_features[:1] for t in uniq]).to(device).index_select(0, owner)
+        else:
+            nb, nbin = cat('next_block_features'), cat('next_binary_features')
+        next_q, next_sf, _ = target_net(nb, nbin, cat('next_actions_features'), reward.expand(rows, -1, -1, -1),
+                                        obstacle.expand(rows, -1, -1, -1))
+        q_sel, sf_target = dqn_ops.next_targets(seg, next_q, done, gamma, next_sf=next_sf[:, 0] if tr.use_sf else None,
+                                                action_raster=action_u.squeeze(1))
+        if sf_target is not None:
+            sf_target = sf_target.reshape(len(uniq), px).index_select(0, which)
+        q_target = extra = None
+        if tr.use_q:
+            lin = cat('lin_reward').reshape(-1).float().index_select(0, which).view(n, B)
+            m = lin.mean(dim=1, keepdim=True)
+            q_target = (m + gamma * q_sel.index_select(0, which).view(n, B)).reshape(-1).contiguous()
+            extra = ((lin - m) ** 2).mean(dim=1)
+        losses = tr.run(n, cat('block_features').reshape(len(uniq), px).index_select(0, which),
+                        action_u.reshape(len(uniq), px).index_select(0, which), cat('binary_features').index_select(0, which),
+                        reward.reshape(px).contiguous(), obstacle.reshape(px).contiguous(), q_target, sf_target)
+    return losses + extra if extra is not None else losses.clone()
+
+
+sync_fused_optimizer = T.sync_optimizer      # (this module's name for it: call before optimizer.state_dict() / .step())
 
 
 def train_policy_net(policy_net, target_net, optimizer, replay_buffer, gamma, loss_fct='mse_q_values', scheduler=None,
@@ -303,40 +223,23 @@ def train_policy_net(policy_net, target_net, optimizer, replay_buffer, gamma, lo
     if draw is not None:
         from robotoddler.utils.replay_memory import _stack
         drawn = [draw(batch_size) for _ in range(n_steps)]
-        if batch_size is not None and _FusedTrainer.applies(policy_net, optimizer, loss_fct, scheduler, [t for b in drawn for t in b], device=device):
-            tr = _FusedTrainer.of(policy_net, optimizer, batch_size, loss_fct)
-            if tr is not None:
-                out = []
-                for k in range(0, n_steps, 64):           # (bounds the target pass: 64 steps x 32 transitions x their next actions)
-                    out.append(tr.run_all(drawn[k:k + 64], target_net, gamma, device))
+        if batch_size is not None and _fused_applies(policy_net, optimizer, loss_fct, scheduler, [t for b in drawn for t in b], device=device):
+            tr = _fused_driver(policy_net, optimizer, batch_size, loss_fct, min(n_steps, 64))
+            if tr is not None:                            # (chunks of 64 bound the target pass: 64 steps x 32 transitions x their next actions)
+                out = [_run_fused(tr, drawn[k:k + 64], target_net, gamma, device) for k in range(0, n_steps, 64)]
                 return torch.cat(out).tolist()            # ONE host read for all steps
         steps = ((transitions, _stack(transitions, device)) for transitions in drawn)
     else:
         steps = (replay_buffer.sample(batch_size=batch_size, stack_tensors=True, device=device) for _ in range(n_steps))
     for transitions, batch in steps:
-        fused = _FusedTrainer.applies(policy_net, optimizer, loss_fct, scheduler, transitions, batch)
-        if fused:
-            tr = _FusedTrainer.of(policy_net, optimizer, batch.block_features.shape[0], loss_fct)
-            fused = tr is not None
-        if not fused and getattr(policy_net, "_fused_trainer", None) is not None:
-            sync_fused_optimizer(policy_net)                  # optimizer.step() takes over: it needs the true step count,
-            policy_net._fused_trainer = None                  # and a later fused batch adopts the optimiser's state afresh
-        if fused:
-            with torch.no_grad():
-                next_q, next_sf, _next_bin = target_net(
-                    batch.next_block_features, batch.next_binary_features, batch.next_actions_features,
-                    batch.next_reward_features, batch.next_obstacle_features)
-                num_actions = [max(1, len(a)) for a in batch.next_available_actions]
-                seg, done = ops.upload(next_q.device, np.cumsum([0] + num_actions).astype(np.int32), np.asarray(batch.done, dtype=np.bool_))
-                zeros = torch.zeros(len(num_actions), dtype=torch.float32, device=next_q.device)
-                nq = next_q.contiguous().float()
-                q_sel, _, _ = dqn_ops.td_target(seg, nq, zeros, done, 1.0)
-                sf_target = None
-                if 'mse_block_features' in loss_fct:
-                    _, sf_target, _ = dqn_ops.td_target(seg, nq, zeros, done, gamma, next_sf=next_sf[:, 0],
-                                                        action_raster=batch.action_features.squeeze(1))
-            losses.append(tr.run(batch, q_sel, sf_target, gamma))
+        tr = None
+        if _fused_applies(policy_net, optimizer, loss_fct, scheduler, transitions, batch):
+            tr = _fused_driver(policy_net, optimizer, batch.block_features.shape[0], loss_fct, 1)
+        if tr is not None:                                # a batch of one task: the same step as a call of one batch
+            losses.append(_run_fused(tr, [transitions], target_net, gamma, device))
             continue
+        T.release(policy_net)                             # optimizer.step() takes over: it needs the true step count,
+        #                                                   and a later hand-written step adopts the optimiser's state afresh
         q_values, succ_block_features, succ_binary_features = policy_net(
             batch.block_features, batch.binary_features, batch.action_features, batch.reward_features,
             batch.obstacle_features)
@@ -350,16 +253,11 @@ def train_policy_net(policy_net, target_net, optimizer, replay_buffer, gamma, lo
             use_sf = 'mse_block_features' in loss_fct
             if use_sf and succ_block_features is None:
                 raise ValueError("No successor block features available from the chosen policy net.")
-            # fused HIP op: segmented argmax over the ragged next-action rows, done masking, a + gamma psi'.
-            # lin_reward = 0, gamma_q = 1 makes q_sel the done-masked next q of the selected action; the reward is
-            # added below with torch broadcasting, because the reference adds a [B,1] lin_reward to a [B] vector
-            # (successor_dqn.py:222 with :435) and thereby trains on a [B,B] target -- reproduced as is.
-            zeros = torch.zeros(len(num_actions), dtype=torch.float32, device=next_q.device)
-            q_sel, _, sel_rows = dqn_ops.td_target(seg, next_q.contiguous().float(), zeros, done, 1.0)
-            sf_target = None
-            if use_sf:
-                _, sf_target, _ = dqn_ops.td_target(seg, next_q.contiguous().float(), zeros, done, gamma,
-                                                    next_sf=next_sf[:, 0],
+            # fused HIP op: segmented argmax over the ragged next-action rows, done masking, a + gamma psi'.  q_sel is the
+            # done-masked next q of the selected action; the reward is added below with torch broadcasting, because the
+            # reference adds a [B,1] lin_reward to a [B] vector (successor_dqn.py:222 with :435) and thereby trains on a
+            # [B,B] target -- reproduced as is.
+            q_sel, sf_target = dqn_ops.next_targets(seg, next_q, done, gamma, next_sf=next_sf[:, 0] if use_sf else None,
                                                     action_raster=batch.action_features.squeeze(1))
         loss = 0.
         if 'mse_q_values' in loss_fct:
@@ -695,7 +593,7 @@ def main(argv=None):
         if args['verbose']:
             print(f"episode {i}: {log_info}")
         if args['save_checkpoint'] and i % args['checkpoint_every'] == 0:     # utils.py:54-89 layout
-            sync_fused_optimizer(policy_net)
+            T.sync_optimizer(policy_net)
             save_checkpoint(args['save_checkpoint'], policy_net, target_net, replay_buffer, optimizer, i,
                             {k: (str(v) if not isinstance(v, (int, float, str, bool, type(None))) else v) for k, v in args.items()})
         if i % args['evaluate_every'] == 0:

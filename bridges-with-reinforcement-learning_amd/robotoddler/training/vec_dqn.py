@@ -23,7 +23,6 @@ in one pass (the target net is constant meanwhile); the optimiser steps themselv
 """
 import os
 import time
-import warnings
 
 import numpy as np
 import torch
@@ -33,6 +32,7 @@ from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import VecAssemblyGym
 from robotoddler.training import distributed as D
 from robotoddler.training import records as R
+from robotoddler.training import train_step as T
 
 
 class VecDQN:
@@ -60,7 +60,6 @@ class VecDQN:
         for g in optimizer.param_groups:                # step counter on the device: the train step is graph-captured
             if 'capturable' in g:
                 g['capturable'] = True
-        self._graph_state, self._eager_calls = None, 0
         self._eager_reduce = None                            # dqn_ops.ReduceTables of the eager optimiser steps
         self.episodes_done = 0
         self.env_steps = 0
@@ -313,32 +312,19 @@ class VecDQN:
         use_sf = 'mse_block_features' in self.loss_parts
         if idx.numel() and self._factored(self.target_net):
             # q of every next candidate through the factored forward on the bit-packed rasters; the 8204-wide output
-            # (successor features) is only needed for the arg-max row of each transition
+            # (successor features) is only needed for the arg-max row of each transition: its channel 0 from the first-layer
+            # pre-activations already at hand
             nq, h_pre = self._net_q(self.target_net, renv, idx, row_env, stable_n, return_h=True)
-            nq = nq.contiguous().float()
-            q_target, _, arg = dqn_ops.td_target(seg, nq, lin, done, self.gamma)
-            sf_target = None
-            if use_sf:
-                best = arg.long().clamp_(0, idx.numel() - 1)                       # empty segments are 'done': row unused
-                # channel 0 of the arg-max rows' successor features from the first-layer pre-activations already at hand
-                nsf0 = self.target_net.sf0_from_first_layer(h_pre.index_select(0, best)).contiguous()
-                one_each = torch.arange(E + 1, dtype=torch.int32, device=self.device)
-                _, sf_target, _ = dqn_ops.td_target(one_each, nq[best].contiguous(), lin, done, self.gamma,
-                                                    next_sf=nsf0, action_raster=action_f.squeeze(1))
+            nsf0 = lambda best: self.target_net.sf0_from_first_layer(h_pre.index_select(0, best)).contiguous()
         elif idx.numel():
             nq, nsf, _, inverse = self._forward_rows(self.target_net, renv, idx, row_env, stable_n)
             if use_sf and nsf is None:
                 raise ValueError("No successor block features available from the chosen policy net.")
-            nq = nq.contiguous().float()
-            q_target, _, arg = dqn_ops.td_target(seg, nq, lin, done, self.gamma)
-            sf_target = None
-            if use_sf:
-                # successor features of the arg-max row of every transition only (nsf holds the DISTINCT rows' outputs)
-                best = arg.long().clamp_(0, idx.numel() - 1)                       # empty segments are 'done': row unused
-                nsf0 = nsf[:, 0].index_select(0, best if inverse is None else inverse.index_select(0, best)).reshape(E, -1).contiguous()
-                one_each = torch.arange(E + 1, dtype=torch.int32, device=self.device)
-                _, sf_target, _ = dqn_ops.td_target(one_each, nq[best].contiguous(), lin, done, self.gamma,
-                                                    next_sf=nsf0, action_raster=action_f.squeeze(1))
+            # (nsf holds the DISTINCT rows' outputs)
+            nsf0 = lambda best: nsf[:, 0].index_select(0, best if inverse is None else inverse.index_select(0, best)).reshape(E, -1).contiguous()
+        if idx.numel():
+            q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
+                                                       action_raster=action_f.squeeze(1), lin=lin)
         else:
             q_target = lin
             sf_target = action_f.reshape(E, -1) if use_sf else None
@@ -354,130 +340,32 @@ class VecDQN:
             loss = loss + self.mse(sf[:, 0], sf_target.view_as(sf[:, 0]))
         return loss
 
-    def _capture_train_graph(self, n_max, use_sf):
-        """One optimiser step (batch gather, forward, loss, backward, Adam) as a HIP graph.  The batch is gathered
-        inside the graph from the static arrays of all batches of the lock-step by a device-side step counter, so a
-        train step is exactly one graph launch (eager PyTorch needs ~60 launches of a few microseconds of work each
-        and is bound by their launch latency)."""
-        B, dev = self.B, self.device
-        px = (self.env.img, self.env.img)
-        st = dict(block=torch.zeros((n_max * B, 1, *px), device=dev), binary=torch.zeros((n_max * B, 6), device=dev),
-                  action=torch.zeros((n_max * B, 1, *px), device=dev), q=torch.zeros(n_max * B, device=dev),
-                  sf=torch.zeros((n_max * B, px[0] * px[1]), device=dev) if use_sf else None,
-                  counter=torch.zeros((), dtype=torch.int64, device=dev),
-                  losses=torch.zeros(n_max, device=dev),
-                  lane=torch.arange(B, device=dev), iota=torch.arange(n_max, device=dev), n_max=n_max, use_sf=use_sf)
-        reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1)
-        obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1)
-        st["fused"] = self._fused_step_enabled()
-
-        def body_fused():
-            # forward, losses and backward of the MLP as ~20 hand-written launches on the f32 matrix cores
-            # (bridges_hip/mlp_ops.py, csrc/mlp_kernels.hip) instead of ~60 library / element-wise ones; the gradients land
-            # in the parameters' .grad, the optimiser is torch's fused Adam as before.  Same losses as _loss.
-            n = n_max * B
-            st["step"].launch(st["counter"], st["block"].view(n, -1), st["action"].view(n, -1), st["binary"], st["reward"],
-                              st["obstacle"], st["q"], st["sf"], st["losses"])
-            if not st["step"].fused_adam:                 # else the Adam update is the last launch of the sequence
-                self.opt.step()
-
-        def body():
-            idx = st["lane"] + st["counter"] * B
-            q, sf, _ = self.policy_net(st["block"].index_select(0, idx), st["binary"].index_select(0, idx),
-                                       st["action"].index_select(0, idx), reward, obstacle)
-            # same losses as _loss, but the 131 072-element mean is reduced row-wise and then over the 32 rows: the
-            # multi-workgroup (semaphore) reduction nn.MSELoss launches for it returned garbage on some replays
-            # (negative "MSE", ROCm 7.2 + torch 2.10; eager never) while every single-workgroup reduction was right.
-            # The value is logged through a one-hot of the step counter (pure elementwise arithmetic).
-            loss = 0.
-            if 'mse_q_values' in self.loss_parts:
-                loss = loss + ((q - st["q"].index_select(0, idx)) ** 2).mean()
-            if use_sf:
-                loss = loss + ((sf[:, 0].reshape(B, -1) - st["sf"].index_select(0, idx)) ** 2).mean(dim=1).mean()
-            st["losses"].add_((st["iota"] == st["counter"]).to(torch.float32) * loss.detach())
-            with dqn_ops.deferred_wgrad_reduce(st["reduce"]):          # the conv layers' weight-gradient reductions as one launch
-                loss.backward()
-            if st["adam"] is not None:
-                st["adam"].step()                          # one launch of 1024-element chunks over all parameter tensors
-            else:
-                self.opt.step()
-            st["counter"].add_(1)
-
-        self.policy_net.train()
-        self.opt.zero_grad(set_to_none=True)
-        st["adam"] = None
-        st["reduce"] = dqn_ops.ReduceTables(dev)
-        if not st["fused"]:
-            from bridges_hip.dqn_ops import MultiTensorAdam
-            try:
-                st["adam"] = MultiTensorAdam(self.opt)
-            except ValueError:
-                pass                                       # another optimiser, or one with options the launch does not cover
-        if st["fused"]:
-            from bridges_hip.mlp_ops import FusedSuccessorStep
-            st["step"] = FusedSuccessorStep(self.policy_net, B, 'mse_q_values' in self.loss_parts, use_sf,
-                                            optimizer=self.opt)
-            st["reward"] = self.env.reward_features.reshape(-1).contiguous()
-            st["obstacle"] = self.env.obstacle_raster.reshape(-1).contiguous()
-            # the first layer's input rows of all batches of a call are built by ONE launch before the replays
-            # (train_steps), a replayed step reads batch `counter` of them: one launch per optimiser step less
-            st["step"].allocate_inputs(n_max)
-            st["step"]._prepared = True                  # captured in the form that reads the pre-built rows
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            body_fused() if st["fused"] else body()
-        st["graph"] = graph
-        # all n_max steps of a call as ONE graph as well (the hand-written step only: its launches read the batch counter from
-        # the device, so n_max copies of the sequence are the n_max steps): between two graph launches the GPU idles 8.7 us
-        # (rocprofv3 trace of the loop), inside a graph consecutive kernels follow each other without a gap
-        st["graph_all"] = None
-        if st["fused"] and n_max > 1:
-            graph_all = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph_all):
-                for _ in range(n_max):
-                    body_fused()
-            st["graph_all"] = graph_all
-        return st
-
-    def _fused_step_enabled(self):
-        """The hand-written training step applies to SuccessorMLP with the two MSE losses of the CLI
-        (BRIDGES_FUSED_MLP_STEP=0: the autograd step inside the graph, as before)."""
-        from robotoddler.models.cv import SuccessorMLP
-        return (isinstance(self.policy_net, SuccessorMLP) and os.environ.get("BRIDGES_FUSED_MLP_STEP", "1") != "0"
-                and set(self.loss_parts) <= {'mse_q_values', 'mse_block_features'}
-                and all(p.dtype == torch.float32 for p in self.policy_net.parameters()))
-
-    def _train_graph(self, n_steps, use_sf):
-        """The captured train step, or None (eager).  Default: on for SuccessorMLP, whose step has no multi-workgroup
-        reduction left in it (see _capture_train_graph) and is verified against the eager run at the bench size
-        (tests/test_gpu_vec_dqn.py), and on for ConvNet: its ConvBlocks run forward and backward on the hand-written
-        kernels (deterministic partial-sum reductions, csrc/conv_train_kernels.hip), what is left of the library in its step
-        are single-workgroup reductions over the 32 batch rows, the eager step is bound by the host (1.2 ms of Python and
-        launches for 0.57 ms of GPU work), and the replays run under the on-device restore guard (_guard_restore).  On for
-        the U-Net policy as well: its 3x3 convolutions are the hand-written ones, its transposed and 1x1 convolutions stay with
-        the library but without their bias, whose gradient -- a sum over 131 k elements that torch reduces with the
-        multi-workgroup kernel that once misbehaved inside a replay -- comes from bridges_bias_grad (dqn_ops.conv_bias_train).
-        BRIDGES_TRAIN_GRAPH=0/1 overrides.  The first calls always run eagerly (they initialise the optimiser state and the library workspaces a
-        capture needs)."""
+    def _train_step(self, n_steps):
+        """The policy net's captured-step driver as this loop uses it: two eager calls before the first capture (they
+        initialise the optimiser state and the library workspaces a capture needs), the hand-written step for SuccessorMLP
+        with its first-layer rows built per call, the task maps of the rollout env."""
         from robotoddler.models.cv import ConvNet, Policy, SuccessorMLP
-        default = "1" if isinstance(self.policy_net, (SuccessorMLP, ConvNet, Policy)) else "0"
-        if os.environ.get("BRIDGES_TRAIN_GRAPH", default) != "1":
-            return None
-        st = self._graph_state
-        if st is not None and (st["n_max"] < n_steps or st["use_sf"] != use_sf):
-            self.sync_optimizer_state()
-            st = self._graph_state = None                     # more batches per call than captured for: capture again
-        if st is None:
-            if self._eager_calls < 2:
-                self._eager_calls += 1
-                return None
-            try:
-                st = self._graph_state = self._capture_train_graph(n_steps, use_sf)
-            except RuntimeError as e:                         # same arithmetic either way: keep training eagerly
-                warnings.warn(f"train-step graph capture failed, staying eager: {e}")
-                self._eager_calls = -(1 << 30)
-                return None
-        return st
+        env = self.env
+        return T.CapturedTrainStep.of(self.policy_net, self.opt, self.B, self.loss_parts, n_steps, owner=self, img=(env.img, env.img),
+                                      fused=T.fused_step_enabled(self.policy_net, self.loss_parts),
+                                      graph_default=isinstance(self.policy_net, (SuccessorMLP, ConvNet, Policy)), warmup=2,
+                                      eager_body=False, prepared=True, task=(env.reward_features, env.obstacle_raster))
+
+    @property
+    def _graph_state(self):
+        """This loop's capture on the policy net's driver (n_max, fused, the guard's snapshot), None while it steps eagerly."""
+        drv = getattr(self.policy_net, "_fused_trainer", None)
+        return drv.state if drv is not None and drv.key[3] is self and drv._graphs else None
+
+    # the on-device restore guard of the captured autograd step (train_step.CapturedTrainStep) on this loop's capture
+    def _guard_tensors(self):
+        return self.policy_net._fused_trainer._guard_tensors()
+
+    def _guard_snapshot(self, st):
+        self.policy_net._fused_trainer._guard_snapshot(st)
+
+    def _guard_restore(self, st, losses):
+        self.policy_net._fused_trainer._guard_restore(st, losses)
 
     def train_steps(self, n_steps, defer=False):
         """n_steps optimiser steps on n_steps independently sampled batches; returns the losses (one host sync).
@@ -485,114 +373,40 @@ class VecDQN:
         ``.get()`` waits for that copy only, so the host can queue the next lock-step's acting while the GPU still
         trains (the list form makes the host wait for the last optimiser step before it queues anything)."""
         if len(self.ring) < self.B or n_steps <= 0:
-            return DeferredLosses(None, None, self) if defer else []
+            return DeferredLosses(None, None, None) if defer else []
         B = self.B
         # n_steps independent batches = ONE draw of n_steps * B records: both sampling rules draw with replacement, so
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
         rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
         block_f, binary, action_f, q_target, sf_target = self._targets(rec)
-        use_sf = sf_target is not None
-        st = self._train_graph(n_steps, use_sf)
-        if st is not None:
-            n = n_steps * B
-            if st.get("fused"):
-                st["step"].check_hyperparameters()
-                # the first layer's input rows of all n_steps batches in one launch, straight from the target pass's tensors
-                # (no staging copy of the 13 MB block / action images: a replayed step reads only x_all, q and sf)
-                st["step"].prepare_inputs(n_steps, block_f.reshape(n, -1).contiguous(), action_f.reshape(n, -1).contiguous(),
-                                          binary.contiguous(), st["reward"], st["obstacle"])
-            else:
-                if st["adam"] is not None:
-                    st["adam"].check_hyperparameters()
-                st["block"][:n].copy_(block_f); st["binary"][:n].copy_(binary); st["action"][:n].copy_(action_f)
-                self._guard_snapshot(st)
-            st["q"][:n].copy_(q_target)
-            if use_sf:
-                st["sf"][:n].copy_(sf_target.reshape(n, -1))
-            st["counter"].zero_()
-            st["losses"].zero_()
-            if n_steps == st["n_max"] and st["graph_all"] is not None:
-                st["graph_all"].replay()
-            else:
-                for _ in range(n_steps):
-                    st["graph"].replay()
-            if not st.get("fused"):
-                self._guard_restore(st, st["losses"][:n_steps])
-            if defer:
-                host = torch.empty(n_steps, dtype=torch.float32, pin_memory=True)
-                host.copy_(st["losses"][:n_steps], non_blocking=True)
-                done = torch.cuda.Event()
-                done.record()
-                return DeferredLosses(host, done, self)
-            return self._check_graph_losses(st["losses"][:n_steps].tolist())            # the one host sync of the call
-        reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1)
-        obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1)
-        self.policy_net.train()
-        losses = []
-        for i in range(n_steps):
-            sl = slice(i * B, (i + 1) * B)
-            q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
-            loss = self._loss(q, sf, q_target[sl], sf_target[sl] if use_sf else None)
-            self.opt.zero_grad()
-            if self._eager_reduce is None:
-                self._eager_reduce = dqn_ops.ReduceTables(self.device)
-            with dqn_ops.deferred_wgrad_reduce(self._eager_reduce):
-                loss.backward()
-            self.opt.step()
-            losses.append(loss.detach())
+        drv = self._train_step(n_steps)
+        out = drv.run(n_steps, block_f, action_f, binary, None, None, q_target, sf_target)
+        if out is None:
+            drv = None
+            reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1)
+            obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1)
+            self.policy_net.train()
+            losses = []
+            for i in range(n_steps):
+                sl = slice(i * B, (i + 1) * B)
+                q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
+                loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
+                self.opt.zero_grad()
+                if self._eager_reduce is None:
+                    self._eager_reduce = dqn_ops.ReduceTables(self.device)
+                with dqn_ops.deferred_wgrad_reduce(self._eager_reduce):
+                    loss.backward()
+                self.opt.step()
+                losses.append(loss.detach())
+            out = torch.stack(losses)
         if defer:
             host = torch.empty(n_steps, dtype=torch.float32, pin_memory=True)
-            host.copy_(torch.stack(losses), non_blocking=True)
+            host.copy_(out, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
-            return DeferredLosses(host, done, None)
-        return torch.stack(losses).tolist()
-
-    # The replayed autograd step of the conv nets holds library reductions; one of that kind once returned garbage inside a
-    # replayed graph (see _check_graph_losses).  The host learns of a bad loss one lock-step late (deferred read-back), so the
-    # weights are protected ON THE DEVICE: parameters and Adam state are copied before the replays of a call and put back --
-    # a torch.where on a device flag, no host decision -- when any of the call's losses is negative or not finite.  The
-    # call's optimiser steps are then lost, not applied as garbage; the host switches to the eager step when it sees the loss.
-    def _guard_tensors(self):
-        flat = getattr(self.policy_net, "_flat_params", None)
-        ts = [flat.flat] if flat is not None else [p.data for p in self.policy_net.parameters()]
-        for s in self.opt.state.values():
-            ts += [t for t in s.values() if torch.is_tensor(t) and t.is_cuda]
-        adam = (self._graph_state or {}).get("adam")
-        if adam is not None:
-            ts.append(adam.step_count)
-        return ts
-
-    def _guard_snapshot(self, st):
-        ts = self._guard_tensors()
-        snap = st.get("guard")
-        if snap is None or len(snap) != len(ts) or any(a.shape != b.shape for a, b in zip(snap, ts)):
-            st["guard"] = [t.clone() for t in ts]
-        else:
-            torch._foreach_copy_(snap, ts)
-
-    def _guard_restore(self, st, losses):
-        bad = ~(torch.isfinite(losses).all() & (losses >= 0).all())
-        for t, s in zip(self._guard_tensors(), st["guard"]):
-            torch.where(bad, s, t, out=t)
-
-    def _check_graph_losses(self, losses):
-        """Guard for the anomaly recorded in DESIGN.md: a multi-workgroup reduction inside a replayed graph once returned
-        garbage (a negative "MSE"; ROCm 7.2 + torch 2.10, cause not established).  The graph holds only single-workgroup
-        reductions since, and every replay's loss is checked here: a sum of squares that is negative or not finite
-        means a kernel in the graph misbehaved -- from then on the step runs eagerly."""
-        if not all(np.isfinite(l) and l >= 0.0 for l in losses):
-            warnings.warn(f"train-step graph produced an invalid loss {losses}; switching to the eager step")
-            self.sync_optimizer_state()
-            self._graph_state, self._eager_calls = None, -(1 << 30)
-        return losses
-
-    def sync_optimizer_state(self):
-        """The captured step keeps Adam's step count itself (FusedSuccessorStep.adam_step); hand it back to the torch
-        optimiser before its state is saved or ``optimizer.step()`` takes over again."""
-        st = self._graph_state
-        if st is not None and st.get("fused") and st["step"].fused_adam:
-            st["step"].export_state()
+            return DeferredLosses(host, done, drv)
+        losses = out.tolist()                                # the one host sync of the call
+        return drv.check_losses(losses) if drv is not None else losses
 
     def train_step(self):
         out = self.train_steps(1)
@@ -657,8 +471,8 @@ class VecDQN:
 class DeferredLosses:
     """Losses of one train_steps call on their way to the host (pinned buffer + event)."""
 
-    def __init__(self, host, done, agent):
-        self._host, self._done, self._agent, self._list = host, done, agent, None
+    def __init__(self, host, done, driver):
+        self._host, self._done, self._driver, self._list = host, done, driver, None
 
     def get(self):
         if self._list is None:
@@ -667,8 +481,8 @@ class DeferredLosses:
             else:
                 self._done.synchronize()
                 self._list = self._host.tolist()
-                if self._agent is not None:
-                    self._agent._check_graph_losses(self._list)
+                if self._driver is not None:
+                    self._driver.check_losses(self._list)
         return self._list
 
 
@@ -740,7 +554,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         losses, rec = agent.lockstep(args['num_training_steps'], defer_losses=True)
         it += 1
         if args.get('save_checkpoint') and agent.episodes_done >= next_ckpt:                  # utils.py:54-89 layout
-            agent.sync_optimizer_state()
+            T.sync_optimizer(policy_net)
             if rank == 0:
                 from robotoddler.utils.utils import save_checkpoint
                 save_checkpoint(args['save_checkpoint'], policy_net, target_net, agent.ring, opt, agent.episodes_done,
@@ -768,5 +582,5 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         pending = (info, losses, stats_host, done)
     if pending is not None:
         finish(pending)
-    agent.sync_optimizer_state()       # the captured step counts Adam's steps itself: hand the count back before anyone reads opt.state
+    T.sync_optimizer(policy_net)       # the captured step counts Adam's steps itself: hand the count back before anyone reads opt.state
     return (history, agent) if return_agent else history

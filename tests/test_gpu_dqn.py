@@ -518,12 +518,14 @@ def test_eps_greedy_select_matches_the_segmented_torch_formulation(E, amax, eps,
 @pytest.mark.parametrize("loss_fct,B,size,hidden", [("mse_q_values", 32, (64, 64), [256, 128, 64, 128, 256]),
                                                    ("mse_block_features", 32, (64, 64), [256, 128, 64, 128, 256]),
                                                    ("mse_q_values+mse_block_features", 8, (64, 64), [128, 64, 128])])
-def test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form(loss_fct, B, size, hidden):
+def test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form(loss_fct, B, size, hidden, tasks=1):
     """The single-environment train_policy_net (successor_dqn.py:157-277) takes the hand-written SuccessorMLP step when every
     sampled transition carries the same task fingerprint (rollout_episode tags them): per-step losses -- incl. the [B,B]
     broadcast of the q target, i.e. the var(lin_reward) term -- within 1e-5 of the autograd form on the same batches, the
     weights after three Adam steps within what two correct float32 Adam runs agree to; untagged transitions keep the
-    autograd form; the optimiser's state is the true one after sync_fused_optimizer."""
+    autograd form; the optimiser's state is the true one after sync_fused_optimizer.  tasks=2 (the test below): with two task
+    fingerprints in the buffer the call as a whole does not qualify, but its batches of one task still take the hand-written
+    step, one batch per call."""
     import warnings
     from robotoddler.models.cv import SuccessorMLP
     from robotoddler.training import successor_dqn as S
@@ -533,10 +535,12 @@ def test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form(los
     gamma = 0.8
     trans = synthetic_transitions(3 * B, size, 5)
     reward, obstacle = trans[0].reward_features.to(DEV), trans[0].obstacle_features.to(DEV)
-    key = S._task_key(reward, obstacle)
+    task_maps = [(reward, obstacle), (reward.flip(-1).contiguous(), obstacle.flip(-1).contiguous())]   # 2nd: transitions B.. if tasks == 2
+    keys = [S._task_key(*m) for m in task_maps]
     dev_t = lambda t: t.to(DEV) if torch.is_tensor(t) else t
     shared, plain = [], []
-    for t in trans:
+    for i, t in enumerate(trans):
+        (reward, obstacle), key = task_maps[int(tasks == 2 and i >= B)], keys[int(tasks == 2 and i >= B)]
         n1 = t.next_block_features.shape[0]
         d = {f: dev_t(getattr(t, f)) for f in t._fields}
         d.update(next_reward_features=reward.expand(n1, -1, -1, -1), next_obstacle_features=obstacle.expand(n1, -1, -1, -1))
@@ -545,6 +549,16 @@ def test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form(los
                      next_binary_features=d["next_binary_features"][:1].expand(n1, -1))
         plain.append(Transition(**dict(d, reward_features=reward.clone(), obstacle_features=obstacle.clone())))
         shared.append(Transition(**dict(d, reward_features=S._tagged(reward.clone(), key), obstacle_features=S._tagged(obstacle.clone(), key))))
+
+    class Scripted(ReplayBuffer):
+        """Draws a batch of both tasks (autograd), then one of each task alone (hand-written, one batch per call)."""
+        k = 0
+
+        def draw(self, batch_size=None):
+            lo = [B // 2, 0, B][self.k % 3]
+            self.k += 1
+            return list(self.memory)[lo:lo + batch_size]
+
     torch.manual_seed(1)
     mk = lambda: SuccessorMLP(img_size=size, hidden_dims=hidden).to(DEV)
     nets = {}
@@ -558,12 +572,13 @@ def test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form(los
         tgt.load_state_dict(init)
         S.flatten_nets(pol, tgt)
         opt = torch.optim.Adam(pol.parameters(), lr=1e-3)
-        rb = ReplayBuffer(capacity=1000)
+        rb = ReplayBuffer(capacity=1000) if tasks == 1 else Scripted(capacity=1000)
         rb.push(items)
         random.seed(21)
         losses = S.train_policy_net(pol, tgt, opt, rb, gamma, loss_fct=loss_fct, n_steps=3, batch_size=B, device=DEV)
         nets[name] = (pol, opt, losses, getattr(pol, "_fused_trainer", None), init)
     assert nets["fused"][3] is not None and nets["autograd"][3] is None          # the tagged run took the hand-written step
+    assert tasks == 1 or 1 in nets["fused"][3]._graphs                           # (its second one-batch call: a replay)
     np.testing.assert_allclose(nets["fused"][2], nets["autograd"][2], rtol=2e-5, atol=1e-6)
     for pa, pb in zip(nets["autograd"][0].parameters(), nets["fused"][0].parameters()):
         err = float((pa.detach().double() - pb.detach().double()).norm() / (pa.detach().double().norm() + 1e-30))
@@ -579,9 +594,15 @@ def test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form(los
     assert len(more) == 1 and np.isfinite(more[0]) and {float(st["step"]) for st in nets["fused"][1].state.values()} == {4.0}
 
 
+def test_train_policy_net_per_batch_hand_written_step_follows_the_autograd_form():
+    """Batches of one task in a call whose draws span two tasks: the hand-written step one batch at a time (see above)."""
+    test_train_policy_net_on_the_hand_written_step_follows_the_autograd_form("mse_q_values+mse_block_features", 8, (64, 64),
+                                                                             [128, 64, 128], tasks=2)
+
+
 def test_train_policy_net_graph_of_all_steps_equals_the_queued_launches(monkeypatch):
     """From the second call with the same number of steps on, train_policy_net replays its optimiser steps from one HIP graph
-    (_FusedTrainer._steps): the same launches on copies of the same inputs -- losses and weights bit-identical to the run that
+    (train_step.CapturedTrainStep: one graph per step count): the same launches on copies of the same inputs -- losses and weights bit-identical to the run that
     queues them one by one (BRIDGES_TRAIN_GRAPH=0), over three calls of four steps."""
     import warnings
     from robotoddler.models.cv import SuccessorMLP
@@ -625,3 +646,55 @@ def test_train_policy_net_graph_of_all_steps_equals_the_queued_launches(monkeypa
         out[mode] = (losses, torch.cat([p.detach().flatten() for p in pol.parameters()]).cpu())
     assert len(out["1"][0]) == 12 and out["1"][0] == out["0"][0]
     assert torch.equal(out["1"][1], out["0"][1])
+
+
+def test_one_net_trained_by_both_loops_has_one_driver(monkeypatch):
+    """train_policy_net and then a VecDQN on the same SuccessorMLP and optimiser: the net holds ONE captured-step driver (the
+    loop that takes over hands the previous driver's Adam step count back and builds its own, whose buffers alone hold the
+    optimiser's moments), and after train_step.sync_optimizer the optimiser's step count is the steps of both loops."""
+    import warnings
+    from bridges_hip.shapes import load_urdf
+    from bridges_hip.vec_env import VecAssemblyGym
+    from robotoddler.training import successor_dqn as S
+    from robotoddler.training import train_step as T
+    from robotoddler.training.vec_dqn import VecDQN
+    from robotoddler.utils.replay_memory import ReplayBuffer
+    warnings.filterwarnings("ignore", message="Using a target size")
+    monkeypatch.setenv("BRIDGES_TRAIN_GRAPH", "1")
+    B, size = 16, (64, 64)
+    torch.manual_seed(3)
+    pol, tgt = S.make_nets(vars(S.build_parser().parse_args(["--model", "SuccessorMLP"])), DEV)
+    opt = torch.optim.Adam(pol.parameters(), lr=1e-4)
+    trans = synthetic_transitions(4 * B, size, 13)
+    reward, obstacle = trans[0].reward_features.to(DEV), trans[0].obstacle_features.to(DEV)
+    key = S._task_key(reward, obstacle)
+    items = []
+    for t in trans:
+        n1 = t.next_block_features.shape[0]
+        d = {f: (getattr(t, f).to(DEV) if torch.is_tensor(getattr(t, f)) else getattr(t, f)) for f in t._fields}
+        d.update(next_reward_features=reward.expand(n1, -1, -1, -1), next_obstacle_features=obstacle.expand(n1, -1, -1, -1),
+                 reward_features=S._tagged(reward.clone(), key), obstacle_features=S._tagged(obstacle.clone(), key))
+        items.append(Transition(**d))
+    rb = ReplayBuffer(capacity=1000)
+    rb.push(items)
+    random.seed(4)
+    for _ in range(2):
+        losses = S.train_policy_net(pol, tgt, opt, rb, 0.9, loss_fct="mse_q_values+mse_block_features", n_steps=3, batch_size=B,
+                                    device=DEV)
+        assert len(losses) == 3 and all(np.isfinite(losses))
+    first = pol._fused_trainer
+    assert first is not None and 3 in first._graphs                              # eager call, then a replay
+    H = 0.8
+    env = VecAssemblyGym(64, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(2)],
+                         [(0.5, 0, 2 * H + H / 2)], max_steps=10, seed=5)
+    agent = VecDQN(pol, tgt, opt, env, 10000, B, 0.95, 0.01, "mse_q_values+mse_block_features", seed=1)
+    for _ in range(4):                                                            # two eager calls, two replays of 2 steps
+        losses, _ = agent.lockstep(2)
+        assert len(losses) == 2 and all(np.isfinite(losses))
+    drv = pol._fused_trainer
+    assert drv is not first and drv.step is not None and drv.step.fused_adam and 2 in drv._graphs
+    m = drv.step.m_flat
+    for p in pol.parameters():
+        assert m.data_ptr() <= opt.state[p]["exp_avg"].data_ptr() < m.data_ptr() + 4 * m.numel()
+    T.sync_optimizer(pol)
+    assert {float(st["step"]) for st in opt.state.values()} == {6.0 + 8.0}

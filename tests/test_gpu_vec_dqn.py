@@ -245,7 +245,7 @@ def test_batched_targets_equal_per_batch_targets():
 def test_graph_captured_train_step_equals_eager(model, loss, E, n_steps, locksteps, monkeypatch):
     """The HIP-graph train step (third call onwards) performs the same optimiser steps and logs the same losses as
     eager PyTorch; the 4096-env case is the BASELINE.json configs[2] shape (25 steps of batch 32 per lock-step), the
-    size at which a multi-workgroup reduction inside the graph used to return garbage (VecDQN._capture_train_graph)."""
+    size at which a multi-workgroup reduction inside the graph used to return garbage (train_step.CapturedTrainStep)."""
     from robotoddler.training.successor_dqn import build_parser, make_nets
     from robotoddler.training.vec_dqn import VecDQN
     args = vars(build_parser().parse_args(["--model", model]))

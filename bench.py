@@ -7,7 +7,11 @@ environments: uniform-random policy draw -> place the block -> contact interface
 candidates -> (A+1) 64x64 f32 rasters -> bounds/overlap mask -> linear reward  (SURVEY.md §8d).
 `value` counts real environment steps (reset-only lock-steps of an env are not counted).
 
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, then per seed W warm-up and K timed lock-steps, the dump if asked
+for, the JSON line.  Everything else the bench measures (the CPU baselines, the side modes, the training legs) runs only
+with --full, in the same line as before.
 
 --dump-outputs DIR writes, after the timed steps, what the last timed lock-step left for a caller (flags, rewards, blocks,
 candidates, a fixed seeded sample of the rasters) as DIR/<name>.npy, at most 64 MB (see dump_outputs()); with the same
@@ -21,10 +25,11 @@ by someone else it is simply one of the ranks.
 Envs are independent: each rank owns E envs (weak scaling), there is no data-path collective;
 the only communication is the barrier / max-reduce of the timing contract.
 
-Side numbers (never part of `value`) ride in the same JSON line under `other_modes`, each measured in
-a child process of its own: the two cheaper raster modes, the candidate-stability mask
+With --full, side numbers (never part of `value`) ride in the same JSON line: `cpu_baseline` (N = 1) and, under
+`other_modes`, each measured in a child process of its own: the two cheaper raster modes, the candidate-stability mask
 (`is_action_stable_rbe` over every valid candidate, LPs/s), BASELINE.json's config-5 simulator
-workload (hexagon, bridge span) and training in the loop for configs[1], configs[2] and (one GPU's share of) configs[4].
+workload (hexagon, bridge span) and training in the loop for configs[1], configs[2] and (one GPU's share of) configs[4];
+with a process group (N > 1), BASELINE.json's configs[3] training leg as `other_modes.train_config4`.
 """
 import argparse
 import json
@@ -451,6 +456,8 @@ def parse_args():
                     help="candidate-stability: every lock-step also decides is_action_stable_rbe for every valid candidate")
     ap.add_argument("--snapshots", action="store_true",
                     help="keep the per-env tableau snapshots of the candidate-stability kernel in the simulator modes too (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baselines, side modes, training legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the per-launch HIP events (experiment: their cost)")
     ap.add_argument("--debug", type=int, default=0,
@@ -478,7 +485,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: start one rank per GPU")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "sim":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "sim":
         cpu = cpu_baseline(args)                       # before the GPU is initialised (fork pool)
 
     import torch
@@ -717,16 +724,16 @@ def main():
             release()
         plain = not (args.no_f32_rasters or args.sparse_raster_update or args.debug or cand_mode or args.bridge_length
                      or args.shapes != "trapezoid")
-        if world == 1 and plain and not args.no_other_modes:
+        if args.full and world == 1 and plain and not args.no_other_modes:
             try:
                 release()
                 out["other_modes"] = side_modes(args)
             except Exception as exc:                     # the headline line must survive whatever happens here
                 out["other_modes"] = {"error": repr(exc)[:200]}
-    # BASELINE.json configs[3] on the same N ranks, as a CHILD job with its own process group and a timeout: the
+    # --full: BASELINE.json configs[3] on the same N ranks, as a CHILD job with its own process group and a timeout: the
     # collectives of the training loop have never run on more than one physical GPU from inside this build, and a hang or
     # a crash in there must not cost the headline line.  Every rank of this job leaves its GPU first.
-    want_leg = use_pg and args.mode == "sim" and os.environ.get("BENCH_TRAIN_MODES", "1") != "0"
+    want_leg = args.full and use_pg and args.mode == "sim" and os.environ.get("BENCH_TRAIN_MODES", "1") != "0"
     if use_pg:
         release()
         dist.barrier()

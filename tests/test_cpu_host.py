@@ -368,6 +368,35 @@ def test_bench_starts_its_own_ranks_for_gpus_n(monkeypatch):
     assert seen["env"]["MASTER_ADDR"] == "127.0.0.1"
 
 
+def test_plain_bench_goes_straight_to_the_gpu_and_full_takes_the_cpu_baseline_first(monkeypatch):
+    """`python bench.py --gpus 1` sets up the GPU without measuring the CPU baseline; with --full the baseline comes first,
+    before torch touches the GPU (its worker pool forks)."""
+    import importlib
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    calls = []
+
+    class Reached(Exception):
+        pass
+
+    def stop(name):
+        def f(*a, **kw):
+            calls.append(name)
+            raise Reached(name)
+        return f
+    monkeypatch.setattr(bench, "cpu_baseline", stop("cpu_baseline"))
+    monkeypatch.setattr(torch.cuda, "set_device", stop("set_device"))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    for extra, first in (([], "set_device"), (["--full"], "cpu_baseline")):
+        calls.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", *extra])
+        with pytest.raises(Reached):
+            bench.main()
+        assert calls == [first]
+
+
 def test_bench_dump_outputs_writes_the_last_lockstep_of_every_group(tmp_path):
     """bench.py --dump-outputs on a stand-in env set (two groups of CPU buffers in the layout of VecAssemblyGym): one .npy
     per array, float32 / float64 only, under 64 MB, the same files twice for the same state, and the candidate rows of a

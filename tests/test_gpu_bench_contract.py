@@ -1,4 +1,5 @@
-"""GPU: `python bench.py` prints ONE JSON line with the keys of the measurement contract (driver + judge read them)."""
+"""GPU: `python bench.py` prints ONE JSON line with the keys of the measurement contract (driver + judge read them); with
+--full the same line also carries the CPU baselines and the side modes."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_prints_one_json_line_with_the_contract_keys():
     env = dict(os.environ, BENCH_CPU_WORKERS="2", BENCH_CPU_SECONDS="1", BENCH_NUMPY_STEPS="20", BENCH_TRAIN_MODES="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--envs", "512"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                          "--envs", "512", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -47,13 +48,37 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert "hexagon" in om["config5_hexagon_bridge"]["workload"]
 
 
+def test_plain_bench_runs_the_headline_alone(tmp_path):
+    """Without --full the line carries the headline, its seeds and its roofline, the dump if asked for, and nothing that
+    takes runs of its own: no CPU baseline, no side modes."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                          "--envs", "512", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline", "dump_outputs"):
+        assert key in j, key
+    assert "cpu_baseline" not in j and "other_modes" not in j
+    assert j["n_gpus"] == 1 and j["steps"] == 20 and j["warmup"] == 5 and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["config"]["seeds"] == [0, 1, 2] and sorted(p["seed"] for p in j["config"]["per_seed"]) == [0, 1, 2]
+    vals = sorted(p["value"] for p in j["config"]["per_seed"])
+    assert j["value"] == pytest.approx(vals[1]) and j["value"] > 1e5
+    assert abs(j["ms_per_step"] * j["value"] / 1e3 / (512 * j["config"]["env_step_fraction"]) - 1) < 0.02
+    assert 0 < j["roofline"]["frac"] < 1
+    d = j["dump_outputs"]
+    assert d["arrays"] == len(os.listdir(tmp_path / "dump")) and d["bytes"] > 0
+
+
 def test_bench_launches_its_own_ranks_for_gpus_2():
-    """`python bench.py --gpus 2` with no torchrun environment starts two ranks itself (gloo here: both share the one
+    """`python bench.py --gpus 2 --full` with no torchrun environment starts two ranks itself (gloo here: both share the one
     card of the test box; on a node the same path runs RCCL) and rank 0 prints the one line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(BENCH_DIST_BACKEND="gloo", BENCH_TRAIN_LOCKSTEPS="4", BENCH_TRAIN_WARMUP="4")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
-                          "--envs", "256"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--envs", "256", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -54,11 +54,11 @@ def test_config4_bench_leg_on_a_one_rank_rccl_group():
 
 
 def test_headline_bench_and_its_child_leg_on_a_one_rank_rccl_group():
-    """`bench.py --gpus 1` under torchrun with the forced process group: the N > 1 flow end to end on one GPU -- nccl init with
+    """`bench.py --gpus 1 --full` under torchrun with the forced process group: the N > 1 flow end to end on one GPU -- nccl init with
     device_id, the barriers and the MAX / SUM all-reduces of the timing contract on device tensors, destroy_process_group, then
     the configs[3] leg started by rank 0 as a child torchrun job with its own nccl group -- and ONE JSON line at the end."""
     out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--envs", "512", "--no-other-modes",
-                     "--no-cpu-baseline"],
+                     "--no-cpu-baseline", "--full"],
                     _env(BRIDGES_FORCE_COLLECTIVE="1", BENCH_TRAIN_LOCKSTEPS="3", BENCH_TRAIN_WARMUP="3"))
     assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

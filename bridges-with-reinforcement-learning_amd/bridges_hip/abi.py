@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("BRIDGES_LIB", os.path.join(HERE, "libbridges_hip.so"))      # override: diagnostic builds
+LIB_PATH = os.path.join(HERE, "libbridges_hip.so")
 CSRC_DIR = os.path.join(os.path.dirname(HERE), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
 STAMP_PREFIX = "BRIDGES_SRC_HASH="

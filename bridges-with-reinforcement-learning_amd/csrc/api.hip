@@ -79,9 +79,7 @@ int bridges_env_create(const bridges_task* t, const bridges_env_buffers* buf, br
     if (t->n_targets < 0 || t->n_targets > BRIDGES_MAX_TARGETS) return fail_arg("n_targets");
     if (t->a_max <= 0) return fail_arg("a_max");
     if (t->img_size != 0 && (t->img_size < 2 || t->img_size > BRIDGES_IMG)) return fail_arg("img_size must be 0 (= 64) or 2..64");
-#ifndef BRIDGES_DIAG
-    if (t->debug != 0) return fail_arg("debug switches exist only in a diagnostic build (-DBRIDGES_DIAG, tools/build_diag.sh)");
-#endif
+    if (t->debug != 0) return fail_arg("debug must be 0");
     if (!buf->reward_prefix) return fail_arg("reward_prefix (float64 row prefix sums of reward_map) not given");
     if (buf->lp_ws_stride < (int64_t)BRIDGES_LP_WS_DOUBLES) return fail_arg("lp_ws_stride < BRIDGES_LP_WS_DOUBLES");
     static_assert(BRIDGES_LP_WS_DOUBLES == WARM_WS_DOUBLES, "header and device code disagree on the persistent tableau size");
@@ -234,12 +232,6 @@ int bridges_env_timing_end(bridges_env* env, double* raster_ms_total, int32_t* n
     return BRIDGES_OK;
 }
 
-// Unused dynamic LDS per rasteriser workgroup (4 waves): caps how many of them a CU holds (160 KB of LDS) and so leaves
-// registers / wave slots to the latency-bound task kernels of the other env groups.  0 = no cap: 8 workgroups per CU fill every
-// wave slot (tools/raster_occupancy.sh measures the alternatives).
-#ifndef RASTER_DYN_LDS
-#define RASTER_DYN_LDS 0
-#endif
 static int refresh(bridges_env* env, hipStream_t s, int after_step) {
     const DevCtx& c = env->ctx;
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(SCAN_THREADS), 0, s, c, after_step);
@@ -257,8 +249,10 @@ static int refresh(bridges_env* env, hipStream_t s, int after_step) {
     const bool timed = env->ev_cap > 0 && env->ev_used < env->ev_cap;
     if (env->gate && env->gate->last) HIP_TRY(hipStreamWaitEvent(s, env->gate->last, 0));
     if (timed) HIP_TRY(hipEventRecord(env->ev_start[env->ev_used], s));
-    if (env->max_faces <= 4) hipLaunchKernelGGL(k_raster<4>, dim3((unsigned)rblocks), dim3(256), RASTER_DYN_LDS, s, c);
-    else hipLaunchKernelGGL(k_raster<MAXV>, dim3((unsigned)rblocks), dim3(256), RASTER_DYN_LDS, s, c);
+    // No dynamic LDS, so no cap on the rasteriser's occupancy: 8 workgroups (4 waves each) per CU fill every wave slot.
+    // Capping it to leave room for the other env groups' task kernels cost the headline 5-6 % (profiles/r04_kstep_tail.txt).
+    if (env->max_faces <= 4) hipLaunchKernelGGL(k_raster<4>, dim3((unsigned)rblocks), dim3(256), 0, s, c);
+    else hipLaunchKernelGGL(k_raster<MAXV>, dim3((unsigned)rblocks), dim3(256), 0, s, c);
     LAUNCH_CHECK("k_raster");
     if (timed) { HIP_TRY(hipEventRecord(env->ev_stop[env->ev_used], s)); env->ev_used++; }
     if (env->gate) {
@@ -291,12 +285,8 @@ int bridges_env_refresh(bridges_env* env, void* stream) {
     return refresh(env, (hipStream_t)stream, 0);
 }
 
-#ifndef CS_TAB_SMALL
 #define CS_TAB_SMALL 768     // 6 KiB: with carriers, candidates on up to ~4 placed blocks; 9.5 KB of LDS and <= 128 VGPRs per wave: 16 waves per CU
-#endif
-#ifndef CS_COLS_SMALL
-#define CS_COLS_SMALL 92
-#endif
+#define CS_COLS_SMALL 92     // its columns; the tableau / column / wave variants measured: profiles/r04_cs_variants.txt
 #define CS_TAB_LARGE 4096
 int bridges_env_candidate_stability(bridges_env* env, void* stream) {
     if (!env) return fail_arg("null env");
@@ -495,17 +485,6 @@ int bridges_stability_penalty(const bridges_shape* shapes_dev, int32_t n, int32_
     return stability_launch(shapes_dev, n, K, pose, verts, shape_id, n_blocks, fixed_mask, mu, density, floor_half_width,
                             floor_depth, stable, info, lp_ws, lp_ws_stride, tension_tol, forces, stream);
 }
-
-#ifdef LP_PROFILE
-int bridges_debug_lp_profile(unsigned long long* out8, int reset) {
-    HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_lp_prof), 8 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_lp_prof), z, sizeof(z)));
-    }
-    return BRIDGES_OK;
-}
-#endif
 
 int bridges_soft_update(float* target, const float* policy, int64_t n, float tau, float one_minus_tau, void* stream) {
     if (n < 0) return fail_arg("bridges_soft_update");

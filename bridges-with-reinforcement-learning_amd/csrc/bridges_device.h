@@ -17,14 +17,6 @@
 #define MAXIF BRIDGES_MAX_INTERFACES
 #define IMG BRIDGES_IMG
 
-// Diagnostic switches (bridges_task.debug) exist only in builds made with -DBRIDGES_DIAG (tools/build_diag.sh); the
-// product library compiles every such branch away and bridges_env_create refuses a non-zero debug word.
-#ifdef BRIDGES_DIAG
-#define DIAG(c, bit) (((c).debug & (bit)) != 0)
-#else
-#define DIAG(c, bit) false
-#endif
-
 namespace bridges {
 
 struct Frame2 {            // face frame: centre, tangent (x-axis), outward normal
@@ -151,8 +143,7 @@ struct DevCtx {
     const TaskTable* tt;
     int32_t* h_total;               // mapped host word: total raw candidates of the last scan (sizes the next raster grid)
     int32_t E, K, max_steps, a_max, n_groups, n_ground, n_offsets, n_targets;
-    int32_t debug, env_id_base;     // debug: BRIDGES_DIAG builds only (bit0 skip the LPs, bit1 / bit2 skip the half-plane runs / the f32
-                                    // stores of the rasteriser, bit3 per-env phase stamps, bit4 empty candidate-stability grid)
+    int32_t debug, env_id_base;     // debug: always 0
     int32_t n_shapes, img;            // img: image width = height S <= 64 (64 = the reference's default)
     int32_t group_shape[BRIDGES_MAX_GROUPS];
     int32_t group_face[BRIDGES_MAX_GROUPS];

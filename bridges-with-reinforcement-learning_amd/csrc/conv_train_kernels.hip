@@ -31,12 +31,10 @@ typedef float c3_f32x4 __attribute__((ext_vector_type(4)));
 
 // band rows of a workgroup: 4 on the 16- to 64-pixel layers, the whole image on the 8-pixel ones -- at the CLI's batch of 32 that
 // makes >= 512 workgroups for every layer but the last block's, and with the register cap of two waves per SIMD (C3_MIN_WAVES)
-// two workgroups share a CU, one staging its patch while the other multiplies.  tools/c3_variants.sh (profiles/r04_c3_variants.txt),
+// two workgroups share a CU, one staging its patch while the other multiplies.  profiles/r04_c3_variants.txt,
 // one optimiser step of the U-Net policy: 8 rows / 1 wave 1269 us, 8 / 2 1494 (spills), 4 / 1 1276, 4 / 2 1200.  (16-row bands
 // had left half the chip idle on the 32- and 16-pixel layers.)
-#ifndef C3_BAND_ROWS_WIDE
 #define C3_BAND_ROWS_WIDE 4
-#endif
 __host__ __device__ constexpr int c3_band_rows(int W) { return W >= 16 ? C3_BAND_ROWS_WIDE : 8; }
 // band of the weight-gradient kernel: two operand tiles must fit into 64 KB of static LDS
 __host__ __device__ constexpr int c3_wgrad_rows(int W) { return W >= 64 ? 4 : (W == 32 ? 8 : W); }
@@ -53,9 +51,7 @@ __host__ __device__ constexpr int c3_pad(int raw, int rem) { return ((raw - rem 
 // what it costs (64 -> 128 channels on 8 x 8 images: 8 passes of 16 channels took 39 us, the arithmetic < 2).
 __host__ __device__ constexpr int c3_stage(int W, int CIN_CHUNK) { return CIN_CHUNK < 16 ? CIN_CHUNK : (W <= 16 ? 32 : 16); }
 
-#ifndef C3_MIN_WAVES
 #define C3_MIN_WAVES 2
-#endif
 template <int W, int CIN_CHUNK, int EPI>
 __global__ __launch_bounds__(256, C3_MIN_WAVES) void k_c3(const float* __restrict__ x, const float* __restrict__ in_mask, const float* __restrict__ w,
                                             const float* __restrict__ bias, const float* __restrict__ mask_src, float* __restrict__ out,

@@ -96,7 +96,6 @@ __global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
     const int e = blockIdx.x, lane = threadIdx.x;
     const int K = c.K;
     uint8_t* flags = c.b.step_flags + (size_t)e * 8;
-    const long long ts0 = DIAG(c, 8) ? wall_clock64() : 0;      // debug bit3: per-env phase stamps (tools/kstep_phases.py)
     int32_t* shape_id_g = c.b.blk_shape + (size_t)e * K;
     double* pose_g = c.b.blk_pose + (size_t)e * K * 4;
     double* verts_g = c.b.blk_verts + (size_t)e * K * MAXV * 2;
@@ -209,7 +208,6 @@ __global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
         }
     }
     const int n_reached = c.n_targets - __popc(left);
-    const long long ts1 = DIAG(c, 8) ? wall_clock64() : 0;
 
     // ---- contact interfaces of the new block (assembly_env.py:281-304): its faces against the floor and every
     //      older block's faces, frames computed on the fly from the LDS vertices (same pair order and arithmetic as
@@ -270,21 +268,16 @@ __global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
     // ---- stability with the last block frozen / nothing frozen (gym_env.py:238-245, 325-333) ----
     bool err = false;
     bool st_frozen = true, st_free = true;
-    const long long ts2 = DIAG(c, 8) ? wall_clock64() : 0;
     bool warm_used = false, resolved = false;
-    int lp_diag = 0;
-    if (!DIAG(c, 1)) {
-        AsmView A;                                  // centroids / volumes / contacts from LDS; the block arrays are gone
-        A.pose = nullptr; A.shape_id = nullptr; A.shapes = nullptr; A.n_blocks = nb + 1;
-        A.cand_b = -1; A.cand_pose = nullptr; A.cand_shape = 0; A.cen = Lk.cen; A.vol = Lk.vol; A.n_tens = 0; A.tens_coef = 1.0;
-        A.n_if = n_if; A.n_if0 = n_if < STEP_IF_LDS ? n_if : STEP_IF_LDS;
-        A.if_body0 = Lk.if_body; A.if_geom0 = Lk.if_geom;
-        A.if_body1 = if_body_g + 2 * STEP_IF_LDS; A.if_geom1 = if_geom_g + 8 * STEP_IF_LDS;
-        rbe_both(tab, STEP_TAB_LDS, ws, c.b.lp_ws_stride, S, A, n_if_old, W, c.mu, c.density, lane, &st_frozen, &st_free, &err,
-                 &warm_used, &lp_diag, c.b.lp_snap ? c.b.lp_snap + (size_t)e * c.b.lp_snap_stride : nullptr, &resolved);
-    }
+    AsmView A;                                      // centroids / volumes / contacts from LDS; the block arrays are gone
+    A.pose = nullptr; A.shape_id = nullptr; A.shapes = nullptr; A.n_blocks = nb + 1;
+    A.cand_b = -1; A.cand_pose = nullptr; A.cand_shape = 0; A.cen = Lk.cen; A.vol = Lk.vol; A.n_tens = 0; A.tens_coef = 1.0;
+    A.n_if = n_if; A.n_if0 = n_if < STEP_IF_LDS ? n_if : STEP_IF_LDS;
+    A.if_body0 = Lk.if_body; A.if_geom0 = Lk.if_geom;
+    A.if_body1 = if_body_g + 2 * STEP_IF_LDS; A.if_geom1 = if_geom_g + 8 * STEP_IF_LDS;
+    rbe_both(tab, STEP_TAB_LDS, ws, c.b.lp_ws_stride, S, A, n_if_old, W, c.mu, c.density, lane, &st_frozen, &st_free, &err,
+             &warm_used, c.b.lp_snap ? c.b.lp_snap + (size_t)e * c.b.lp_snap_stride : nullptr, &resolved);
 
-    const long long ts3 = DIAG(c, 8) ? wall_clock64() : 0;
     // ---- reward / termination (gym_env.py:11-22, 141-145) ----
     const bool all_reached = left == 0;
     const bool terminated = !st_frozen || all_reached;
@@ -314,12 +307,6 @@ __global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
     for (int b = 0; b < nb_after; ++b) nfree += __builtin_amdgcn_readlane(nf, b);
     const int nc = c.n_groups * (c.n_ground + nfree * c.n_offsets);     // raw count: k_scan clamps to a_max and flags a truncation
     if (lane == 0) c.b.n_cand[e] = nc;
-    if (DIAG(c, 8) && lane == 0) {               // 100 MHz wall clock: start, after append, after interfaces, after LPs, end
-        const long long ts4 = wall_clock64();
-        double* st = ws + c.b.lp_ws_stride - 8;     // the last 8 doubles of the env's workspace are never used otherwise
-        st[0] = (double)ts0; st[1] = (double)(ts1 - ts0); st[2] = (double)(ts2 - ts1); st[3] = (double)(ts3 - ts2);
-        st[4] = (double)(ts4 - ts3); st[5] = (double)(nb + 1); st[6] = (double)n_if + (warm_used ? 0.5 : 0.0) + 100.0 * (double)lp_diag; st[7] = (double)ts4;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -707,14 +694,13 @@ __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
                 fr0 = a.x; fr1 = a.y; fr2 = b.x; fr3 = b.y;
             }
             const uint64_t occ = c.b.state_bits[(size_t)e * IMG + lane] | obst;
-            uint64_t bits = 0ull;
-            if (!DIAG(c, 2)) bits = (NF == 4 || nv <= 4) ? raster_rows<4>(fr0, fr1, fr2, fr3, c.img, X, Y, lane)
-                                                         : raster_rows6(fr0, fr1, fr2, fr3, c.img, X, Y, lane);
+            const uint64_t bits = (NF == 4 || nv <= 4) ? raster_rows<4>(fr0, fr1, fr2, fr3, c.img, X, Y, lane)
+                                                       : raster_rows6(fr0, fr1, fr2, fr3, c.img, X, Y, lane);
             const bool overlap = __ballot((bits & occ) != 0ull) != 0ull;
             double p_hi, p_lo;
             raster_reward_fetch(bits, c.b.reward_prefix, lane, p_hi, p_lo);
             c.b.cand_bits[ci * IMG + lane] = bits;
-            if (c.b.cand_raster && !DIAG(c, 4))
+            if (c.b.cand_raster)
                 write_f32_image(c.b.cand_raster + ci * IMG * IMG, bits, lane, c.b.cand_raster_nz ? c.b.cand_raster_nz + ci : nullptr);
             const double lin = raster_reward_sum(p_hi, p_lo);
             if (lane == 0) {
@@ -788,12 +774,9 @@ __global__ __launch_bounds__(WAVE) void k_select(DevCtx c, int draw) {
 // a candidate whose tableau does not fit is appended to cand_queue (one atomic per such candidate, they are rare).
 // QUEUE == true: a small persistent grid drains that queue with the full-size LDS tableau and the env workspace
 // lp_ws (one slot per workgroup) behind it; every wave leaves when the queue head passes the count.
-#ifndef CS_NEW_IF
 #define CS_NEW_IF 16
-#endif
-#ifndef CS_WAVES            // waves per SIMD the first pass is compiled for (register cap 512 / CS_WAVES); tools/cs_variants.sh
-#define CS_WAVES 4
-#endif
+#define CS_WAVES 4          // waves per SIMD the first pass is compiled for (register cap 512 / CS_WAVES): 4 waves / 13 spills
+                            // 87.5 M LPs/s against 80.5 M for 3 spill-free waves and less for 5 or 6 (profiles/r04_cs_variants.txt)
 template <int TAB, int MAXCOLS, bool QUEUE>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(QUEUE ? 1 : CS_WAVES, QUEUE ? 2 : CS_WAVES))) void k_candidate_stability(DevCtx c) {
     __shared__ __attribute__((aligned(16))) double tab[TAB];
@@ -817,7 +800,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(QUEUE ? 1 
         } else {
             if (item >= total) return;
             ci = item;
-            if (!c.b.cand_mask[ci] || DIAG(c, 16)) {        // debug bit4: every wave leaves here (cost of the empty grid)
+            if (!c.b.cand_mask[ci]) {
                 if (lane == 0) c.b.cand_stable[ci] = 0;
                 continue;
             }

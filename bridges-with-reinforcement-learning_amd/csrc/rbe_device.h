@@ -12,19 +12,6 @@
 
 namespace bridges {
 
-#ifdef LP_PROFILE   // diagnostic build only (tools/lp_microbench.py --profile): shader cycles per pivot phase
-__device__ unsigned long long g_lp_prof[8];
-#define LP_PROF_DECL long long lp_acc_[6] = {0, 0, 0, 0, 0, 0}
-#define LP_STAMP(var) long long var = clock64()
-#define LP_ACC(slot, a, b) lp_acc_[slot] += (b) - (a)
-#define LP_PROF_FLUSH do { if (lane == 0) for (int k_ = 0; k_ < 6; ++k_) atomicAdd(&g_lp_prof[k_], (unsigned long long)lp_acc_[k_]); } while (0)
-#else
-#define LP_PROF_DECL
-#define LP_STAMP(var)
-#define LP_ACC(slot, a, b)
-#define LP_PROF_FLUSH
-#endif
-
 #define RBE_TOL_PARALLEL 1e-6
 #define RBE_TOL_COPLANAR 1e-6
 #define RBE_AMIN 0.001
@@ -47,9 +34,7 @@ __device__ unsigned long long g_lp_prof[8];
                               // --task mixed --seed 99, lock-step 88, env 797); the check on the original rows accepts 1e-4
 #define LP_S_MAX 1e4          // budget on the total contact force sum_j x_j (oracle/rbe.py S_MAX): equilibria that exist only
                               // through forces of 1e5..1e12 x the block weights along float32 mesh noise are not equilibria
-#ifndef LP_TAB_LDS
 #define LP_TAB_LDS 2048                       // doubles of LDS tableau per wave (16 KiB); larger tableaux live in global memory
-#endif
 #define MAXFACES (1 + MAXK * MAXV)            // floor + K blocks
 #define LP_MAX_COLS (4 * MAXIF)
 #define LP_MAX_CHUNKS ((LP_MAX_COLS + 2 + WAVE - 1) / WAVE)
@@ -339,7 +324,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
     const int nchunk = (n + WAVE - 1) / WAVE;
     const int ncols = n + 1 + ncarr;                   // swept columns: structural, rhs, carriers
     const double progress = 1e-7 * feas;               // 1e-12 at density 1
-    LP_PROF_DECL;
     (void)m_act;                                       // from here on activity is read off the basis
     double w = artificial_sum(T, stride, m, n, basis, lane);
     for (;;) {
@@ -347,7 +331,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
             w = artificial_sum(T, stride, m, n, basis, lane);
             if (w <= feas) break;
         }
-        LP_STAMP(t_a);
         // ---- entering column ----
         int jin = -1;
         if (bland) {
@@ -374,8 +357,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
             w = artificial_sum(T, stride, m, n, basis, lane);
             break;
         }
-        LP_STAMP(t_b);
-        LP_ACC(0, t_a, t_b);
         // ---- ratio test, lanes over rows (m + 2 <= 50 < 64) ----
         double col = (lane <= mc) ? T[lane * stride + jin] : 0.0;  // lane m: budget row, lane m+1: cost entry
         double ratio = 1e300;
@@ -403,8 +384,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
             r = __ffsll((long long)__ballot(tie && col == cmax)) - 1;
         }
         const double ipiv = fast_rcp(readlane_d(col, r));
-        LP_STAMP(t_c);
-        LP_ACC(1, t_b, t_c);
         // ---- stage the entering column, the normalised pivot row and the lists of rows / columns the rank-1
         //      update actually touches (equilibrium tableaux are sparse: typically a fraction of the cells) ----
         S.col[lane] = col;
@@ -424,8 +403,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
             nc += __popcll(cbal);
         }
         wave_sync<IN_LDS>();
-        LP_STAMP(t_d);
-        LP_ACC(2, t_c, t_d);
         // ---- elimination over the touched cells only, 4 independent cells per lane per trip (loads first, then
         //      stores: the cells are distinct, which the compiler cannot prove, so the batching is explicit) ----
         {
@@ -460,9 +437,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
         }
         if (lane == 0) basis[r] = jin;
         wave_sync<IN_LDS>();
-        LP_STAMP(t_e);
-        LP_ACC(3, t_d, t_e);
-        LP_ACC(5, t_a, t_a + 1);       // pivot count
         const double wn = -T[mc * stride + n];
         if (wn < w - progress) { stall = 0; bland = false; }
         else if (++stall > LP_STALL) bland = true;
@@ -470,7 +444,6 @@ __device__ inline double lp_phase1(TP T, int stride, int m, int m_act, int n_gen
         if (++pivots >= LP_MAX_PIVOTS) { *error = true; w = artificial_sum(T, stride, m, n, basis, lane); break; }
     }
     *pivots_out = pivots;
-    LP_PROF_FLUSH;
     return w;
 }
 
@@ -857,7 +830,7 @@ __device__ inline void rbe_both_run(TP T, int stride, int m, int n, LpScratch& S
 // persisting the result there when `keep`.  *warm_used reports which path produced the verdict.
 __device__ inline void rbe_both(double* tab_lds, int lds_cap, double* ws, int64_t ws_cap, LpScratch& S, const AsmView& A, int n_if_old,
                                 const WarmPre& W, double mu, double density, int lane, bool* st_frozen, bool* st_free,
-                                bool* error, bool* warm_used, int* diag = nullptr, double* snap = nullptr, bool* resolved = nullptr) {
+                                bool* error, bool* warm_used, double* snap = nullptr, bool* resolved = nullptr) {
     WarmHdr* hdr = reinterpret_cast<WarmHdr*>(ws);
     double* halves = ws + WARM_HDR_DOUBLES;
     *warm_used = false;
@@ -896,7 +869,6 @@ __device__ inline void rbe_both(double* tab_lds, int lds_cap, double* ws, int64_
         bool marginal = false;
         if (in_lds) rbe_both_run<true>(tab_lds, stride, m, n, S, A, mu, density, lane, warm, st_frozen, st_free, &err, &pivots, snap, &marginal);
         else rbe_both_run<false>(Tg, stride, m, n, S, A, mu, density, lane, warm, st_frozen, st_free, &err, &pivots, snap, &marginal);
-        if (diag) *diag = pivots * 4 + (in_lds ? 0 : 2) + attempt;     // pivots, global-memory tableau, second attempt
         if (!(warm && (err || marginal))) { *error = err; *warm_used = warm; break; }
         if (resolved) *resolved = true;
         warm = false;                                  // the continued tableau failed its check, or reported "unstable" by a

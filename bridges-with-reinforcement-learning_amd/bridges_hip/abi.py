@@ -162,6 +162,85 @@ class EnvBuffers(C.Structure):
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)
 assert [f[0] for f in EnvBuffers._fields_][-10:-7] == ["lp_ws", "lp_ws_stride", "stats"]
 
+# argument types of every entry point that returns an int status (all but the three special symbols below)
+vp, i32, i64, f64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float
+SIGNATURES = {
+    "bridges_env_create": [C.POINTER(Task), C.POINTER(EnvBuffers), C.POINTER(vp)],
+    "bridges_env_destroy": [vp],
+    "bridges_env_reset": [vp, vp],
+    "bridges_env_step": [vp, vp],
+    "bridges_env_select_random": [vp, vp],
+    "bridges_env_lockstep_random": [vp, vp],
+    "bridges_env_refresh": [vp, vp],
+    "bridges_env_candidate_stability": [vp, vp],
+    "bridges_gate_create": [C.POINTER(vp)],
+    "bridges_gate_destroy": [vp],
+    "bridges_env_set_gate": [vp, vp],
+    "bridges_env_timing_begin": [vp, i32],
+    "bridges_env_timing_end": [vp, C.POINTER(C.c_double), C.POINTER(i32)],
+    "bridges_shapes_upload": [C.POINTER(Shape), i32, C.POINTER(vp)],
+    "bridges_shapes_free": [vp],
+    "bridges_place": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_create_block": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_pose_block": [vp, i32, vp, vp, vp, vp],
+    "bridges_face_frames": [vp, i32, vp, vp, vp, vp],
+    "bridges_contains_points": [vp, i32, vp, i32, vp, vp, vp],
+    "bridges_raster": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_raster_sized": [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp],
+    "bridges_render_blocks": [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp],
+    "bridges_bits_or": [i32, vp, vp, vp, vp],
+    "bridges_action_features": [vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_bits_to_f32": [i32, vp, vp, vp],
+    "bridges_bits_linear": [i32, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_sigmoid_dot": [i32, vp, i64, vp, i32, vp, vp],
+    "bridges_bits_dot": [i32, vp, vp, vp, vp, vp, vp],
+    "bridges_head_sigmoid_dot": [i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp],
+    "bridges_linear_backward_log": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, vp, vp, vp],
+    "bridges_mlp_mid_rows": [i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
+    "bridges_mlp_mid_supported": [i32, i32, vp],
+    "bridges_mlp_mid_forward": [i32, i32, vp, vp, vp, vp, vp],
+    "bridges_mlp_mid_backward": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
+    "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_record_state": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_record_result": [i32, vp, vp, vp, vp, vp, vp],
+    "bridges_replay_unpack": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_bits_accumulate": [i32, vp, vp, vp, vp, vp, vp],
+    "bridges_stability": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, i64, vp],
+    "bridges_stability_penalty": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, vp, vp, vp, vp, i64, vp],
+    "bridges_soft_update": [vp, vp, i64, f32, f32, vp],
+    "bridges_bias_relu": [vp, vp, i64, i32, i32, vp],
+    "bridges_bias_relu_pool2": [vp, vp, vp, i64, i32, i32, i32, vp],
+    "bridges_conv3x3_relu_o16": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "bridges_conv3x3_relu_o16_ex": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
+    "bridges_upconv2x2": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "bridges_linear_forward": [i32, i32, i32, vp, vp, vp, i32, vp, vp, i64, vp, vp],
+    "bridges_linear_backward": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp],
+    "bridges_mlp_input": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_mlp_input_batches": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_successor_loss": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_adam_step": [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
+    "bridges_linear_backward_adam": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp, i32, vp],
+    "bridges_conv3x3": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
+    "bridges_conv3x3_wgrad_scratch": [i64, i32, i32, i32, C.POINTER(i64)],
+    "bridges_conv3x3_wgrad": [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp],
+    "bridges_maxpool2": [vp, vp, i64, i32, i32, vp],
+    "bridges_bias_grad": [vp, vp, vp, i64, i64, i32, i32, vp],
+    "bridges_adam_multi": [vp, i32, vp, vp, i32, vp, f64, f64, f64, f64, vp],
+    "bridges_reduce_jobs": [vp, i32, i32, vp],
+    "bridges_upconv2x2_backward_scratch": [i64, i32, i32, i32, i32, C.POINTER(i64)],
+    "bridges_upconv2x2_backward": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, vp],
+    "bridges_conv1x1_o1_forward": [vp, vp, vp, vp, i64, i32, i32, vp],
+    "bridges_conv1x1_o1_backward": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp],
+    "bridges_maxpool2_relu_backward": [vp, vp, vp, i64, i32, i32, vp],
+    "bridges_td_target": [i32, vp, vp, vp, vp, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp],
+}
+
+
+# every symbol include/bridges_hip.h declares
+EXPORTED_SYMBOLS = ("bridges_last_error", "bridges_device_count", "bridges_source_hash", *SIGNATURES)
+
 _lib = None
 
 
@@ -175,7 +254,6 @@ def lib():
             f"{LIB_PATH} not found: build it with `python __graft_entry__.py build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, f64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float
     try:
         L.bridges_source_hash.restype = C.c_char_p
         stamp = L.bridges_source_hash().decode()[len(STAMP_PREFIX):]
@@ -187,97 +265,12 @@ def lib():
                               "rebuild it with `python __graft_entry__.py build`")
     L.bridges_last_error.restype = C.c_char_p
     L.bridges_device_count.restype = C.c_int
-    sigs = {
-        "bridges_env_create": [C.POINTER(Task), C.POINTER(EnvBuffers), C.POINTER(vp)],
-        "bridges_env_destroy": [vp],
-        "bridges_env_reset": [vp, vp],
-        "bridges_env_step": [vp, vp],
-        "bridges_env_select_random": [vp, vp],
-        "bridges_env_lockstep_random": [vp, vp],
-        "bridges_env_refresh": [vp, vp],
-        "bridges_env_candidate_stability": [vp, vp],
-        "bridges_gate_create": [C.POINTER(vp)],
-        "bridges_gate_destroy": [vp],
-        "bridges_env_set_gate": [vp, vp],
-        "bridges_env_timing_begin": [vp, i32],
-        "bridges_env_timing_end": [vp, C.POINTER(C.c_double), C.POINTER(i32)],
-        "bridges_shapes_upload": [C.POINTER(Shape), i32, C.POINTER(vp)],
-        "bridges_shapes_free": [vp],
-        "bridges_place": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_create_block": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_pose_block": [vp, i32, vp, vp, vp, vp],
-        "bridges_face_frames": [vp, i32, vp, vp, vp, vp],
-        "bridges_contains_points": [vp, i32, vp, i32, vp, vp, vp],
-        "bridges_raster": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_raster_sized": [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp],
-        "bridges_render_blocks": [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp],
-        "bridges_bits_or": [i32, vp, vp, vp, vp],
-        "bridges_action_features": [vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_bits_to_f32": [i32, vp, vp, vp],
-        "bridges_bits_linear": [i32, vp, vp, vp, i32, vp, vp, vp, vp],
-        "bridges_sigmoid_dot": [i32, vp, i64, vp, i32, vp, vp],
-        "bridges_bits_dot": [i32, vp, vp, vp, vp, vp, vp],
-        "bridges_head_sigmoid_dot": [i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp],
-        "bridges_linear_backward_log": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, vp, vp, vp],
-        "bridges_mlp_mid_rows": [i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
-        "bridges_mlp_mid_supported": [i32, i32, vp],
-        "bridges_mlp_mid_forward": [i32, i32, vp, vp, vp, vp, vp],
-        "bridges_mlp_mid_backward": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
-        "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_record_state": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_record_result": [i32, vp, vp, vp, vp, vp, vp],
-        "bridges_replay_unpack": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_bits_accumulate": [i32, vp, vp, vp, vp, vp, vp],
-        "bridges_stability": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, i64, vp],
-        "bridges_stability_penalty": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, vp, vp, vp, vp, i64, vp],
-        "bridges_soft_update": [vp, vp, i64, f32, f32, vp],
-        "bridges_bias_relu": [vp, vp, i64, i32, i32, vp],
-        "bridges_bias_relu_pool2": [vp, vp, vp, i64, i32, i32, i32, vp],
-        "bridges_conv3x3_relu_o16": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
-        "bridges_conv3x3_relu_o16_ex": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
-        "bridges_upconv2x2": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
-        "bridges_linear_forward": [i32, i32, i32, vp, vp, vp, i32, vp, vp, i64, vp, vp],
-        "bridges_linear_backward": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp],
-        "bridges_mlp_input": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_mlp_input_batches": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
-        "bridges_successor_loss": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp],
-        "bridges_adam_step": [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
-        "bridges_linear_backward_adam": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp, i32, vp],
-        "bridges_conv3x3": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
-        "bridges_conv3x3_wgrad_scratch": [i64, i32, i32, i32, C.POINTER(i64)],
-        "bridges_conv3x3_wgrad": [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp],
-        "bridges_maxpool2": [vp, vp, i64, i32, i32, vp],
-        "bridges_bias_grad": [vp, vp, vp, i64, i64, i32, i32, vp],
-        "bridges_adam_multi": [vp, i32, vp, vp, i32, vp, f64, f64, f64, f64, vp],
-        "bridges_reduce_jobs": [vp, i32, i32, vp],
-        "bridges_upconv2x2_backward_scratch": [i64, i32, i32, i32, i32, C.POINTER(i64)],
-        "bridges_upconv2x2_backward": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, vp],
-        "bridges_conv1x1_o1_forward": [vp, vp, vp, vp, i64, i32, i32, vp],
-        "bridges_conv1x1_o1_backward": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp],
-        "bridges_maxpool2_relu_backward": [vp, vp, vp, i64, i32, i32, vp],
-        "bridges_td_target": [i32, vp, vp, vp, vp, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp],
-    }
-    for name, argtypes in sigs.items():
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(L, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = (
-    "bridges_last_error", "bridges_device_count", "bridges_source_hash", "bridges_env_create", "bridges_env_destroy",
-    "bridges_env_reset", "bridges_env_step", "bridges_env_select_random", "bridges_env_lockstep_random", "bridges_env_refresh",
-    "bridges_env_candidate_stability",
-    "bridges_gate_create", "bridges_gate_destroy", "bridges_env_set_gate",
-    "bridges_env_timing_begin", "bridges_env_timing_end",
-    "bridges_place", "bridges_create_block", "bridges_pose_block", "bridges_face_frames", "bridges_contains_points", "bridges_raster", "bridges_raster_sized", "bridges_render_blocks", "bridges_action_features", "bridges_bits_or", "bridges_bits_to_f32", "bridges_bits_linear", "bridges_bits_dot", "bridges_bits_accumulate", "bridges_head_sigmoid_dot", "bridges_linear_backward_log", "bridges_mlp_mid_rows", "bridges_mlp_mid_supported", "bridges_mlp_mid_forward", "bridges_mlp_mid_backward", "bridges_eps_greedy_select", "bridges_valid_rows", "bridges_env_groups", "bridges_record_state", "bridges_record_result", "bridges_replay_unpack", "bridges_sigmoid_dot", "bridges_stability", "bridges_stability_penalty",
-    "bridges_shapes_upload", "bridges_shapes_free", "bridges_soft_update", "bridges_td_target", "bridges_bias_relu", "bridges_bias_relu_pool2",
-    "bridges_conv3x3_relu_o16", "bridges_conv3x3_relu_o16_ex", "bridges_conv3x3", "bridges_conv3x3_wgrad_scratch", "bridges_conv3x3_wgrad",
-    "bridges_maxpool2", "bridges_maxpool2_relu_backward", "bridges_bias_grad", "bridges_adam_multi", "bridges_reduce_jobs", "bridges_upconv2x2_backward_scratch", "bridges_upconv2x2_backward", "bridges_conv1x1_o1_forward", "bridges_conv1x1_o1_backward", "bridges_upconv2x2", "bridges_linear_forward", "bridges_linear_backward", "bridges_mlp_input", "bridges_mlp_input_batches", "bridges_successor_loss", "bridges_adam_step", "bridges_linear_backward_adam",
-)
 
 
 def check(rc, what=""):

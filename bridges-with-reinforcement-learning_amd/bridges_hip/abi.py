@@ -173,6 +173,8 @@ SIGNATURES = {
     "bridges_env_lockstep_random": [vp, vp],
     "bridges_env_refresh": [vp, vp],
     "bridges_env_candidate_stability": [vp, vp],
+    "bridges_env_restrict_to_stable": [vp, vp],
+    "bridges_env_rebuild_contacts": [vp, vp],
     "bridges_gate_create": [C.POINTER(vp)],
     "bridges_gate_destroy": [vp],
     "bridges_env_set_gate": [vp, vp],

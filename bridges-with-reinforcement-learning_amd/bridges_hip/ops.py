@@ -510,6 +510,45 @@ def stability_variants(blocks, fixed_sets, mu, density, floor_half_width, floor_
     return out
 
 
+def action_stability(blocks, fixed, candidates, mu, density, floor_half_width, floor_depth):
+    """is_action_stable_rbe (stability.py:122-130) of every candidate placement of ONE assembly in one bridges_stability launch
+    and one copy back: item i is ``blocks`` followed by ``candidates[i]`` (free), the frozen set ``fixed`` (indices into
+    ``blocks``) stays.  ``blocks`` / ``candidates``: objects with ``pose``, ``verts_2d`` and ``geometry`` (assembly_gym Blocks).
+    Returns bool numpy [n]: True = stable; a solver error counts as unstable (stability.py:68)."""
+    L = abi.require_gpu()
+    dev = device()
+    K = abi.MAX_BLOCKS
+    nb, m = len(blocks), len(candidates)
+    if m == 0:
+        return np.zeros(0, dtype=bool)
+    if nb + 1 > K:
+        raise abi.BridgesHipError(f"{nb + 1} blocks > BRIDGES_MAX_BLOCKS ({K})")
+    pose = np.zeros((m, K, 4))
+    verts = np.zeros((m, K, 6, 2))
+    ids = np.zeros((m, K), dtype=np.int32)
+    for i, b in enumerate(blocks):
+        pose[:, i] = b.pose
+        verts[:, i, :len(b.verts_2d)] = b.verts_2d
+        ids[:, i] = REGISTRY.id_of(b.geometry)
+    for j, c in enumerate(candidates):
+        pose[j, nb] = c.pose
+        verts[j, nb, :len(c.verts_2d)] = c.verts_2d
+        ids[j, nb] = REGISTRY.id_of(c.geometry)
+    mask = sum(1 << i for i in fixed if i < nb)
+    tab = REGISTRY.device_table()
+    ws_stride = abi.lp_ws_stride(K)
+    ws = torch.empty((m, ws_stride), dtype=torch.float64, device=dev)
+    stable = torch.zeros(m, dtype=torch.uint8, device=dev)
+    info = torch.zeros((m, 8), dtype=torch.float64, device=dev)
+    a_pose, a_verts, a_ids, a_n, a_mask = upload(dev, pose, verts, ids, np.full(m, nb + 1, dtype=np.int32),
+                                                 np.full(m, mask, dtype=np.int32))
+    abi.check(L.bridges_stability(tab, m, K, _ptr(a_pose), _ptr(a_verts), _ptr(a_ids), _ptr(a_n), _ptr(a_mask),
+                                  float(mu), float(density), float(floor_half_width), float(floor_depth),
+                                  _ptr(stable), _ptr(info), _ptr(ws), ws_stride, _stream()), "bridges_stability")
+    inf, st = download(info, stable)
+    return (st != 0) & (inf[:, 3] == 0)
+
+
 def create_blocks(target_blocks, target_faces, geoms, faces, oxs, oys):
     """AssemblyGym.create_block for n candidate placements in ONE bridges_create_block + ONE bridges_face_frames launch
     and three device-to-host copies (the per-candidate form costs a launch pair and three blocking copies each).

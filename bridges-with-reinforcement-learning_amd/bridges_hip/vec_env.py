@@ -106,7 +106,7 @@ class VecAssemblyGym:
     def __init__(self, num_envs, shapes, obstacles, targets, max_steps=None, mu=0.8, density=1.0, bounds=None,
                  xlim=(-3.0, 7.0), ylim=(0.0, 10.0), x_discr_ground=None, offset_values=(0.0,), seed=0,
                  device="cuda:0", f32_rasters=True, a_max=None, img_size=(64, 64), debug=0, env_id_base=0,
-                 sparse_raster_update=False, candidate_snapshots=True):
+                 sparse_raster_update=False, candidate_snapshots=True, stable_actions_only=False):
         L = abi.require_gpu()
         self.img = check_img_size(img_size)          # S; every image buffer stays a 64x64 canvas, see crop()
         self.L = L
@@ -146,6 +146,9 @@ class VecAssemblyGym:
         self.sparse_raster_update = bool(sparse_raster_update)
         # keep the "last block frozen" tableau of every env for candidate_stability_mask() (123 KB per env)
         self.candidate_snapshots = bool(candidate_snapshots)
+        # the available actions of a state are filter_actions ∩ is_action_stable_rbe: reset / step / refresh narrow the
+        # candidate mask to the stable candidates (restrict_to_stable), so every consumer of cand_mask / n_valid sees only those
+        self.stable_actions_only = bool(stable_actions_only)
         self.grid_x = np.linspace(self.xlim[0], self.xlim[1], self.img)    # rendering.py:108
         self.grid_y = np.linspace(self.ylim[1], self.ylim[0], self.img)
         self._alloc()
@@ -283,6 +286,8 @@ class VecAssemblyGym:
     def reset(self):
         abi.check(self.L.bridges_env_reset(self._env, _stream()), "bridges_env_reset")
         self._contacts_current = True
+        if self.stable_actions_only:
+            self.restrict_to_stable()
         self._cand_version = getattr(self, "_cand_version", 0) + 1
 
     def select_random(self):
@@ -293,6 +298,8 @@ class VecAssemblyGym:
         if sel_index is not None:
             self.buf["sel_index"].copy_(sel_index.to(device=self.device, dtype=torch.int32))
         abi.check(self.L.bridges_env_step(self._env, _stream()), "bridges_env_step")
+        if self.stable_actions_only:
+            self.restrict_to_stable()
         self._cand_version += 1
 
     def timing_begin(self, max_launches):
@@ -307,7 +314,27 @@ class VecAssemblyGym:
     def refresh(self):
         """Recompute the candidate set (enumerate, rasterise, mask) after the host edited the state arrays."""
         abi.check(self.L.bridges_env_refresh(self._env, _stream()), "bridges_env_refresh")
+        if self.stable_actions_only:
+            self.restrict_to_stable()
         self._cand_version += 1
+
+    def restrict_to_stable(self):
+        """Narrow the candidate set to the stable placements (bridges_env_restrict_to_stable): is_action_stable_rbe of every
+        valid candidate (candidate_stability_mask), then cand_mask &= (cand_stable == 1) and n_valid recounted; an env left
+        without a stable candidate is marked no_actions and resets on the next step().  reset() / step() / refresh() call it
+        when the env was created with stable_actions_only=True.  No host synchronisation."""
+        if not self._contacts_current:
+            raise abi.BridgesHipError("candidate stability needs the persistent contact lists of the current states: call "
+                                      "rebuild_contacts() after load_states()")
+        abi.check(self.L.bridges_env_restrict_to_stable(self._env, _stream()), "bridges_env_restrict_to_stable")
+        self._cand_version = getattr(self, "_cand_version", 0) + 1
+
+    def rebuild_contacts(self):
+        """Rebuild the persistent contact list of every env's current block list (bridges_env_rebuild_contacts), as step()
+        would hold it had it placed the blocks one by one, and invalidate the persisted tableaux: after load_states() /
+        load_records() candidate_stability_mask() then decides the loaded states' candidates (from scratch)."""
+        abi.check(self.L.bridges_env_rebuild_contacts(self._env, _stream()), "bridges_env_rebuild_contacts")
+        self._contacts_current = True
 
     def load_states(self, n_blocks, blk_shape, blk_pose, blk_occ):
         """Overwrite the state of every env with caller-supplied block lists (replay re-rasterisation): world
@@ -318,7 +345,7 @@ class VecAssemblyGym:
         self.buf["blk_pose"].copy_(blk_pose)
         self.buf["blk_occ"].copy_(blk_occ)
         self.buf["needs_reset"].zero_()
-        self.buf["n_if"].zero_()                      # interfaces are only needed by step(); replay states never step
+        self.buf["n_if"].zero_()                      # interfaces: rebuild_contacts() (stable_actions_only) or none
         self._contacts_current = False
         flat_shape = self.buf["blk_shape"].reshape(E * K)
         abi.check(self.L.bridges_pose_block(self.table.ptr, E * K, _ptr(flat_shape), _ptr(self.buf["blk_pose"]),
@@ -345,6 +372,8 @@ class VecAssemblyGym:
         nfree = ((faces - popc) * live).sum(dim=1).to(torch.int32)
         n_cand = len(self.groups) * (len(self.x_discr_ground) + nfree * len(self.offset_values))
         self.buf["n_cand"].copy_(n_cand.to(torch.int32))       # raw count: refresh clamps to a_max and flags / counts a truncation
+        if self.stable_actions_only:
+            self.rebuild_contacts()
         self.refresh()
 
     def load_records(self, rec):
@@ -366,7 +395,7 @@ class VecAssemblyGym:
                                                _ptr(b["n_cand"]), _ptr(ranges[0]), _ptr(ranges[1]), _ptr(lin), _ptr(stable_s),
                                                _ptr(done), _ptr(stable_n), _stream()), "bridges_replay_unpack")
         b["needs_reset"].zero_()
-        b["n_if"].zero_()                             # interfaces are only needed by step(); replay states never step
+        b["n_if"].zero_()                             # interfaces: rebuild_contacts() (stable_actions_only) or none
         self._contacts_current = False
         flat_shape = b["blk_shape"].reshape(E * K)
         abi.check(self.L.bridges_pose_block(self.table.ptr, E * K, _ptr(flat_shape), _ptr(b["blk_pose"]), _ptr(b["blk_verts"]),
@@ -378,6 +407,8 @@ class VecAssemblyGym:
         bits_s = torch.empty((E, 64), dtype=torch.int64, device=dev)
         abi.check(self.L.bridges_bits_or(E, _ptr(ranges[1]), _ptr(bits), _ptr(bits_s), _stream()), "bridges_bits_or")
         self._keep = (bits, ranges[0], flat_shape)    # alive until the stream has consumed them
+        if self.stable_actions_only:
+            self.rebuild_contacts()
         self.refresh()
         return bits_s, lin, stable_s, done, stable_n
 
@@ -545,11 +576,14 @@ class VecAssemblyGymGroups:
     def lockstep_random(self):
         """select_random + step for every group, each on its own stream (one C call per group)."""
         fn = self.envs[0].L.bridges_env_lockstep_random
-        for env, sp in zip(self.envs, self._stream_ptrs):
+        for env, st, sp in zip(self.envs, self.streams, self._stream_ptrs):
             rc = fn(env._env, sp)
             env._cand_version += 1
             if rc != 0:
                 abi.check(rc, "bridges_env_lockstep_random")
+            if env.stable_actions_only:
+                with torch.cuda.stream(st):
+                    env.restrict_to_stable()
 
     def lockstep_random_candidates(self, timed=None):
         """lockstep_random, then is_action_stable_rbe for every valid candidate of the new states (candidate_stability_mask),
@@ -563,6 +597,8 @@ class VecAssemblyGymGroups:
                 env._cand_version += 1
                 if rc != 0:
                     abi.check(rc, "bridges_env_lockstep_random")
+                if env.stable_actions_only:
+                    env.restrict_to_stable()
                 if timed is not None:
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record()

@@ -334,6 +334,17 @@ int bridges_env_candidate_stability(bridges_env* env, void* stream) {
                   0, s, c);
 }
 
+int bridges_env_restrict_to_stable(bridges_env* env, void* stream) {
+    if (!env) return fail_arg("null env");
+    if (int rc = bridges_env_candidate_stability(env, stream)) return rc;
+    return launch("k_restrict_stable", k_restrict_stable, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx);
+}
+
+int bridges_env_rebuild_contacts(bridges_env* env, void* stream) {
+    if (!env) return fail_arg("null env");
+    return launch("k_rebuild_contacts", k_rebuild_contacts, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx);
+}
+
 int bridges_env_select_random(bridges_env* env, void* stream) {
     if (!env) return fail_arg("null env");
     return launch("k_select", k_select, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx, 1);

@@ -913,4 +913,72 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(QUEUE ? 1 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Stable actions only (bridges_env_restrict_to_stable), after k_candidate_stability: filter_actions ∩ {is_action_stable_rbe}.
+// One wave per env, the shape of k_select's draw == 0 pass: a valid candidate whose verdict is not 1 (unstable, or a solver
+// error, stability.py:68) leaves cand_mask, n_valid is recounted, and an env left without a candidate is marked as k_select
+// marks one without a valid candidate (the next lock-step is reset-only, successor_dqn.py:409-411).
+__global__ __launch_bounds__(WAVE) void k_restrict_stable(DevCtx c) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const int nc = c.b.n_cand[e];
+    const size_t off = (size_t)c.b.cand_offset[e];
+    int nvalid = 0;
+    for (int a0 = 0; a0 < nc; a0 += WAVE) {
+        const int a = a0 + lane;
+        bool keep = false;
+        if (a < nc && c.b.cand_mask[off + a]) {
+            keep = c.b.cand_stable[off + a] == 1;
+            if (!keep) c.b.cand_mask[off + a] = 0;
+        }
+        nvalid += __popcll(__ballot(keep));
+    }
+    if (lane == 0) {
+        c.b.n_valid[e] = nvalid;
+        if (nvalid == 0) {
+            c.b.needs_reset[e] = 1;
+            c.b.step_flags[(size_t)e * 8 + F_NO_ACTIONS] = 1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The persistent contact list of a state the host wrote (bridges_replay_unpack, load_states), for bridges_env_rebuild_contacts:
+// block after block, the faces of block b against the floor and the faces of every block < b -- the pairs k_step tests when
+// it places block b, in the same order and with the same arithmetic (append_interfaces on frames staged from the vertices;
+// k_step computes them on the fly from the same vertices with the same edge_frame / face_pair_contact_v calls).  One wave
+// per env.  The env's persisted tableaux describe some other assembly: both headers are invalidated, so that k_step and
+// k_candidate_stability take their cold paths on this state.
+__global__ __launch_bounds__(WAVE) void k_rebuild_contacts(DevCtx c) {
+    __shared__ FaceLds F;
+    __shared__ bridges_shape sh_l[8];
+    __shared__ int32_t shape_l[MAXK];
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const int K = c.K;
+    int nb = c.b.n_blocks[e];
+    nb = nb < 0 ? 0 : (nb > K ? K : nb);
+    {
+        const double* src = reinterpret_cast<const double*>(c.tt->shapes);
+        double* dst = reinterpret_cast<double*>(sh_l);
+        const int nd = c.n_shapes * (int)(sizeof(bridges_shape) / 8);
+        for (int i = lane; i < nd; i += WAVE) dst[i] = src[i];
+        if (lane < K) shape_l[lane] = c.b.blk_shape[(size_t)e * K + lane];
+    }
+    __syncthreads();
+    stage_faces(F, 0, 1 + nb * MAXV, c.b.blk_verts + (size_t)e * K * MAXV * 2, shape_l, sh_l, c.floor_hw, lane);
+    __syncthreads();
+    int32_t* if_body_g = c.b.if_body + (size_t)e * MAXIF * 2;
+    double* if_geom_g = c.b.if_geom + (size_t)e * MAXIF * 8;
+    int n_if = 0;
+    bool overflow = false;
+    for (int b = 0; b < nb; ++b)
+        n_if = append_interfaces(F, b, shape_l, sh_l, c.floor_depth, n_if, if_body_g, if_geom_g, lane, &overflow);
+    if (lane == 0) {
+        c.b.n_if[e] = n_if;
+        uint8_t* fl = c.b.step_flags + (size_t)e * 8 + F_LP_ERROR;
+        *fl = (uint8_t)((*fl & ~2u) | (overflow ? 2u : 0u));
+        reinterpret_cast<WarmHdr*>(c.b.lp_ws + (size_t)e * c.b.lp_ws_stride)->magic = 0;
+        if (c.b.lp_snap) reinterpret_cast<WarmHdr*>(c.b.lp_snap + (size_t)e * c.b.lp_snap_stride)->magic = 0;
+    }
+}
+
 }  // namespace bridges

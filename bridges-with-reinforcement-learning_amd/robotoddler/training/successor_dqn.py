@@ -32,7 +32,7 @@ from assembly_gym.utils.rendering import render_blocks_2d_bits                  
 from bridges_hip import dqn_ops, ops                                                      # noqa: E402
 from robotoddler.models.cv import ConvNet, Policy, SuccessorMLP                           # noqa: E402
 from robotoddler.training import train_step as T                                         # noqa: E402
-from robotoddler.utils.actions import filter_actions, generate_actions                    # noqa: E402
+from robotoddler.utils.actions import filter_actions, filter_stable_actions, generate_actions  # noqa: E402
 from robotoddler.utils.replay_memory import PrioritizedReplayBuffer, ReplayBuffer          # noqa: E402
 from robotoddler.utils.utils import (convolve_with_gaussian, init_weights, parse_img_size,   # noqa: E402
                                      save_checkpoint)
@@ -296,7 +296,10 @@ def flatten_nets(*nets):
 
 # ---- rollout (successor_dqn.py:365-475) -------------------------------------------------------------------------
 def rollout_episode(env, policy, policy_net, x_discr_ground, setup_fct, offset_values=[0.], img_size=(64, 64),
-                    xlim=(0, 1), ylim=(0, 1), log_images=False, device=None):
+                    xlim=(0, 1), ylim=(0, 1), log_images=False, device=None, stable_actions_only=False):
+    """stable_actions_only: the available actions of a state are filter_actions ∩ is_action_stable_rbe (one batched
+    stability call per state, filter_stable_actions); everything downstream -- the policy's choice, the no-action
+    termination, the next-state maximum and the transitions' next actions -- sees only those."""
     done, transitions = False, []
     images = [] if log_images else None
     policy_net.eval()
@@ -309,6 +312,10 @@ def rollout_episode(env, policy, policy_net, x_discr_ground, setup_fct, offset_v
     batched = hasattr(env, "create_blocks") and tuple(img_size)[0] == tuple(img_size)[1] <= 64
 
     def candidates(block_f, bits_s):
+        acts, feats = filtered_candidates(block_f, bits_s)
+        return filter_stable_actions(env, acts, feats) if stable_actions_only else (acts, feats)
+
+    def filtered_candidates(block_f, bits_s):
         """generate_actions -> get_action_features -> filter_actions (successor_dqn.py:375-377) of the current state.  With the
         drop-in gym the three are ONE operator call (bridges_action_features: rasters of every candidate, the bounds test of
         collision_on_action and the two overlap tests of filter_actions; tests/test_gpu_api_golden.py shows it equal to the
@@ -496,6 +503,8 @@ def build_parser():
     p.add_argument("--prioritized_replay", action='store_true',
                    help="Sample transitions in proportion to |td_error| + 1e-5 (PrioritizedReplayBuffer, replay_memory.py:45-93).")
     p.add_argument("--shapes", choices=['trapezoid', 'hexagon', 'both'], default='trapezoid')
+    p.add_argument("--stable_actions_only", action='store_true',
+                   help="Restrict every action set to the stable placements (filter_actions ∩ is_action_stable_rbe), in both loops.")
     return p
 
 
@@ -579,7 +588,8 @@ def main(argv=None):
                                    max_steps=args['max_steps'], device=device)
     history = []
     roll = dict(env=env, policy_net=policy_net, setup_fct=setup_fct, x_discr_ground=x_discr_ground, xlim=xlim, ylim=ylim,
-                offset_values=offset_values, img_size=args['image_size'], device=device, log_images=False)
+                offset_values=offset_values, img_size=args['image_size'], device=device, log_images=False,
+                stable_actions_only=args['stable_actions_only'])
     for i in range(first_episode, args['num_episodes'] + 1):
         transitions, images = rollout_episode(policy=eps_greedy.step(), **roll)
         replay_buffer.push(transitions)

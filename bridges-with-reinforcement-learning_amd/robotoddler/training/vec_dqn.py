@@ -37,8 +37,13 @@ from robotoddler.training import train_step as T
 
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
-                 seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False):
+                 seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False):
         self.policy_net, self.target_net, self.opt, self.env = policy_net, target_net, optimizer, env
+        # stable actions only: the rollout env and the replay scratch env narrow every candidate set to the stable placements,
+        # so acting, exploring, the TD target's max over next actions and the done flags all see the same smaller set
+        self.stable_actions_only = bool(stable_actions_only)
+        if self.stable_actions_only != bool(getattr(env, "stable_actions_only", False)):
+            raise ValueError("VecDQN(stable_actions_only=...) must match the rollout env's stable_actions_only")
         self.device = env.device
         self.B, self.gamma, self.tau = batch_size, gamma, tau
         self.loss_parts = loss_function.split('+')
@@ -55,7 +60,8 @@ class VecDQN:
                                          mu=env.mu, density=env.density, bounds=env.bounds, xlim=env.xlim,
                                          ylim=env.ylim, x_discr_ground=env.x_discr_ground,
                                          offset_values=env.offset_values, device=self.device, a_max=env.a_max,
-                                         img_size=(env.img, env.img), f32_rasters=self._replay_f32())
+                                         img_size=(env.img, env.img), f32_rasters=self._replay_f32(),
+                                         stable_actions_only=self.stable_actions_only)
         self.mse = torch.nn.MSELoss()
         for g in optimizer.param_groups:                # step counter on the device: the train step is graph-captured
             if 'capturable' in g:
@@ -282,7 +288,8 @@ class VecDQN:
                                              mu=env.mu, density=env.density, bounds=env.bounds, xlim=env.xlim,
                                              ylim=env.ylim, x_discr_ground=env.x_discr_ground,
                                              offset_values=env.offset_values, device=self.device, a_max=env.a_max,
-                                             img_size=(env.img, env.img), f32_rasters=self._replay_f32())
+                                             img_size=(env.img, env.img), f32_rasters=self._replay_f32(),
+                                             stable_actions_only=self.stable_actions_only)
         return self.replay_env
 
     def _replay_f32(self):
@@ -515,11 +522,12 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     env = VecAssemblyGym(args['num_envs'], geoms, obstacles, targets, max_steps=args['max_steps'],
                          seed=seed * 1000003 + rank, device=device, env_id_base=rank * args['num_envs'],
                          f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net),
-                         img_size=args.get('image_size') or (64, 64))
+                         img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
     opt = torch.optim.Adam(policy_net.parameters(), lr=args['learning_rate'], fused=True)    # one launch for all tensors
     capacity = max(args['replay_buffer_capacity'], 4 * args['num_envs'] * world)
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
-                   args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False))
+                   args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
+                   stable_actions_only=args.get('stable_actions_only', False))
     history, t0, it = [], time.time(), 0
     next_ckpt = args['checkpoint_every']
     if args.get('load_checkpoint'):                      # successor_dqn.py:654-665 + utils.py:31-50 of the reference

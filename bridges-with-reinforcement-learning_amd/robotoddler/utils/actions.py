@@ -42,3 +42,21 @@ def filter_actions(gym_env, available_actions, action_features, block_features, 
     mask = in_bounds & free.cpu()
     kept = [a for a, m in zip(available_actions, mask.tolist()) if m]
     return kept, action_features[mask.to(action_features.device)]
+
+
+def filter_stable_actions(gym_env, available_actions, action_features):
+    """Keep the actions is_action_stable_rbe accepts (assembly_gym/utils/stability.py:122-130 of the reference; a solver error
+    counts as unstable, stability.py:68): the candidate block appended to the assembly (free), the frozen block stays frozen.
+    Every action of the state in ONE batched operator call (ops.action_stability) instead of one solve per action;
+    the blocks come from the gym's candidate cache (create_blocks).  Same return shape as filter_actions."""
+    from bridges_hip import ops
+    n = len(available_actions)
+    if n == 0:
+        return [], action_features[:0]
+    env = gym_env.assembly_env
+    fixed = {i for i, b in enumerate(env.blocks) if b.is_static}
+    stable = ops.action_stability(env.blocks, fixed, gym_env.create_blocks(available_actions), env.mu, env.density,
+                                  env.floor_half_width, env.floor_depth)
+    kept = [a for a, s in zip(available_actions, stable.tolist()) if s]
+    rows = torch.from_numpy(np.flatnonzero(stable)).to(action_features.device)
+    return kept, action_features.index_select(0, rows)

@@ -205,6 +205,17 @@ int bridges_env_refresh(bridges_env* env, void* stream);
  * (free; the last placed block stays frozen, gym_env.py:238-240); its contacts are found against the env's persistent
  * contact list, which must be current (i.e. the state was reached through bridges_env_reset / bridges_env_step). */
 int bridges_env_candidate_stability(bridges_env* env, void* stream);
+/* Stable actions only: bridges_env_candidate_stability, then one wave per env clears cand_mask[ci] where cand_stable[ci] != 1
+ * (a solver error counts as unstable, stability.py:68) and recounts n_valid; an env left without a stable candidate gets
+ * needs_reset and F_NO_ACTIONS, as the candidate refresh marks an env without a valid one.  Call it after
+ * bridges_env_reset / _step / _refresh on the same stream; everything that reads cand_mask / n_valid afterwards sees the
+ * narrowed set.  No host wait. */
+int bridges_env_restrict_to_stable(bridges_env* env, void* stream);
+/* The persistent contact list (n_if, if_body, if_geom) of every env's current block list, rebuilt as bridges_env_step would
+ * hold it had it placed the blocks one by one (same pair order and arithmetic; an overflow sets bit 1 of F_LP_ERROR), for
+ * states the host wrote (bridges_replay_unpack / load_states).  Invalidates the env's persisted tableaux (lp_ws, lp_snap):
+ * bridges_env_candidate_stability then solves the candidates of these states from scratch.  No host wait. */
+int bridges_env_rebuild_contacts(bridges_env* env, void* stream);
 
 /* --- stand-alone operators (same kernels, caller-shaped batches) ------------ */
 /* K1: create_block / align_frames_2d (gym_env.py:204-216, geometry.py:39-50).

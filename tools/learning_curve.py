@@ -23,6 +23,7 @@ ap.add_argument("--loss", default="mse_q_values+mse_block_features")
 ap.add_argument("--lr", type=float, default=1e-4)
 ap.add_argument("--block", type=int, default=100)
 ap.add_argument("--model", default="SuccessorMLP")
+ap.add_argument("--stable_actions_only", action="store_true", help="every action set restricted to the stable placements")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 args = vars(build_parser().parse_args(["--model", a.model, "--loss_function", a.loss]))
@@ -31,9 +32,9 @@ torch.manual_seed(0)
 pol, tgt = make_nets(args, dev)
 env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(a.tower)],
                      [(0.5, 0, a.tower * H + H / 2)], max_steps=a.max_steps, seed=0, device=dev,
-                     f32_rasters=VecDQN.acting_needs_f32_rasters(pol))
+                     f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
-               eps_decay=0.997)
+               eps_decay=0.997, stable_actions_only=a.stable_actions_only)
 t0 = time.time()
 acc = dict(steps=0, reward=0.0, lin=0.0, done=0, solved=0, loss=[])
 for it in range(1, a.locksteps + 1):

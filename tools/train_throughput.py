@@ -27,6 +27,7 @@ ap.add_argument("--miopen_search", action="store_true", help="let MIOpen benchma
 ap.add_argument("--channels_last", action="store_true")
 ap.add_argument("--shapes", default="trapezoid", choices=["trapezoid", "hexagon", "both"])
 ap.add_argument("--bridge_length", type=int, default=0, help="> 0: horizontal_bridge_setup(num_obstacles=N) instead of the tower")
+ap.add_argument("--stable_actions_only", action="store_true", help="every action set restricted to the stable placements")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 if a.miopen_search:
@@ -44,9 +45,10 @@ if a.bridge_length:
 else:
     obstacles, targets = [(0.5, 0., i * H + H / 2) for i in range(a.tower)], [(0.5, 0, a.tower * H + H / 2)]
 env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obstacles, targets, max_steps=a.max_steps, seed=0,
-                     device=dev, f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=False)
+                     device=dev, f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=a.stable_actions_only,
+                     stable_actions_only=a.stable_actions_only)
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
-agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss)
+agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only)
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False

@@ -207,6 +207,7 @@ SIGNATURES = {
     "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_record_state": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_record_result": [i32, vp, vp, vp, vp, vp, vp],
+    "bridges_episode_stats": [i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp],
     "bridges_replay_unpack": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_accumulate": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_stability": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, i64, vp],

@@ -371,6 +371,23 @@ def eps_greedy_select(seg, q, join, u, eps, greedy, idx, cand_offset, rep=None):
     return sel_compact, sel_index, q_sel, explore_w
 
 
+def episode_stats_(out, rec, valid, gpow, n_targets, run, counted, count_first_only=False):
+    """Folds one lock-step's records rec float64 [E, W] / valid bool [E] into the per-episode sums ``out`` float64 [8] in place
+    (bridges_episode_stats): run float32 [E, 2] and counted int32 [E] carry the episodes that span calls, gpow float32 [K] =
+    float32(gamma ** i).  Slots of out: episodes, sum reward, sum lin_reward, sum num_steps, sum stable, sum success, 2 spare."""
+    L = abi.require_gpu()
+    E = valid.numel()
+    assert rec.dtype == torch.float64 and rec.dim() == 2 and rec.shape[0] == E and rec.is_contiguous()
+    assert valid.dtype in (torch.bool, torch.uint8) and valid.is_contiguous()
+    assert run.dtype == torch.float32 and run.shape == (E, 2) and run.is_contiguous()
+    assert counted.dtype == torch.int32 and counted.numel() == E and counted.is_contiguous()
+    assert out.dtype == torch.float64 and out.numel() == 8 and out.is_contiguous()
+    assert gpow.dtype == torch.float32 and gpow.dim() == 1 and gpow.numel() >= 1 and gpow.is_contiguous()
+    abi.check(L.bridges_episode_stats(E, gpow.numel(), _ptr(rec), _ptr(valid), _ptr(gpow), int(n_targets), int(bool(count_first_only)),
+                                      _ptr(run), _ptr(counted), _ptr(out), _stream()), "bridges_episode_stats")
+    return out
+
+
 def bits_dot(bits, img, slot, bits_row=None):
     """out[r] = sum(img[slot[r]] * raster(bits[bits_row[r]])) for bit-packed 64x64 rasters (bridges_bits_dot): img
     [n_slots,64,64] float32, slot [n] int64 -> [n] float32."""

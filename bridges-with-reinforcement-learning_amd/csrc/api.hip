@@ -545,6 +545,15 @@ int bridges_record_result(int32_t E, const float* reward, const float* lin_rewar
                   step_flags, rec, valid);
 }
 
+int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow, int32_t n_targets,
+                          int32_t count_first_only, float* run, int32_t* counted, double* out, void* stream) {
+    if (E < 0 || K < 1 || !gpow || !out || (E > 0 && (!rec || !valid || !run || !counted)))
+        return fail_arg("bridges_episode_stats");
+    if (E == 0) return BRIDGES_OK;
+    return launch("k_episode_stats", k_episode_stats, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec, valid, gpow,
+                  (int)n_targets, (int)(count_first_only != 0), run, counted, out);
+}
+
 int bridges_replay_unpack(int32_t E, int32_t n_rec, int32_t K, const double* rec, const int32_t* shape_faces, int32_t n_shapes,
                           int32_t n_groups, int32_t n_ground, int32_t n_off, int32_t* n_blocks, int32_t* blk_shape,
                           double* blk_pose, uint8_t* blk_occ, int32_t* n_cand, int32_t* ranges_next, int32_t* ranges_prev,

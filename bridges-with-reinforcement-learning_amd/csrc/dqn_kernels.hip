@@ -433,6 +433,65 @@ __global__ __launch_bounds__(256) void k_record_result(int E, const float* __res
     valid[e] = f[0] != 0;
 }
 
+// Per-episode statistics of the vectorised loop: log_episode of the reference (successor_dqn.py:479-499) folded over the
+// lock-step records of every env, before they are gathered (env identity still holds).  Per valid env e, with i = the record's
+// step index (n_blocks of s: every episode starts from the empty assembly and places one block per env-step):
+//   i == 0 restarts run[e];  run[e] += gpow[i] * (reward, lin_reward)  as float32 products and left-to-right float32 sums, no
+//   fused multiply-add (the reference's sum(gamma ** i * t.reward ...) over float32 tensors);  at done the episode's
+//   (1, run, i + 1, stable(s'), reward == n_targets) is added to out unless count_first_only and counted[e] > 0, then counted[e]++.
+// ONE workgroup: thread t walks envs t, t + 256, ...; the partials meet in a fixed-order LDS tree in f64 and thread k adds slot
+// k to out.  No atomics, so two runs on the same inputs give the same bits.
+constexpr int EPISODE_STATS_THREADS = 256;
+constexpr int EPISODE_STATS_SLOTS = 8;        // episodes, sum reward, sum lin_reward, sum num_steps, sum stable, sum success, 2 spare
+
+__global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats(int E, int K, const double* __restrict__ rec,
+                                                                         const uint8_t* __restrict__ valid, const float* __restrict__ gpow,
+                                                                         int n_targets, int count_first_only, float* __restrict__ run,
+                                                                         int32_t* __restrict__ counted, double* __restrict__ out) {
+    __shared__ double part[EPISODE_STATS_SLOTS][EPISODE_STATS_THREADS];
+    const int t = threadIdx.x;
+    double acc[EPISODE_STATS_SLOTS];
+#pragma unroll
+    for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) acc[k] = 0.0;
+    for (int e = t; e < E; e += EPISODE_STATS_THREADS) {
+        if (!valid[e]) continue;
+        const double* r = rec + (size_t)e * BRIDGES_REC_WIDTH;
+        const int i = (int)r[BRIDGES_REC_NB];
+        const int gi = i < 0 ? 0 : (i < K ? i : K - 1);                    // bounds only: a record's step index is < K
+        const float reward = (float)r[BRIDGES_REC_REWARD];                 // float32 values stored exactly as float64
+        const float lin = (float)r[BRIDGES_REC_LIN];
+        float s0 = i == 0 ? 0.f : run[2 * e];
+        float s1 = i == 0 ? 0.f : run[2 * e + 1];
+        s0 = __fadd_rn(s0, __fmul_rn(gpow[gi], reward));
+        s1 = __fadd_rn(s1, __fmul_rn(gpow[gi], lin));
+        run[2 * e] = s0;
+        run[2 * e + 1] = s1;
+        if (r[BRIDGES_REC_DONE] > 0.5) {
+            const int32_t c = counted[e];
+            if (!(count_first_only && c > 0)) {
+                acc[0] += 1.0;
+                acc[1] += (double)s0;
+                acc[2] += (double)s1;
+                acc[3] += (double)(i + 1);
+                acc[4] += r[BRIDGES_REC_STABLE_N] > 0.5 ? 1.0 : 0.0;
+                acc[5] += reward == (float)n_targets ? 1.0 : 0.0;
+            }
+            counted[e] = c + 1;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] = acc[k];
+    __syncthreads();
+    for (int s = EPISODE_STATS_THREADS / 2; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] += part[k][t + s];
+        }
+        __syncthreads();
+    }
+    if (t < EPISODE_STATS_SLOTS) out[t] += part[t][0];
+}
+
 __global__ __launch_bounds__(64) void k_replay_unpack(int E, int n_rec, int K, const double* __restrict__ rec,
                                                       const int32_t* __restrict__ shape_faces, int n_shapes, int n_groups, int n_ground, int n_off,
                                                       int32_t* __restrict__ n_blocks, int32_t* __restrict__ blk_shape,

@@ -73,6 +73,20 @@ def all_gather_records(rec, valid, n_valid=None):
     return out[keep][:, :W]
 
 
+def all_reduce_sum_(t):
+    """Sums ``t`` over the ranks in place (one all_reduce; stream-ordered on RCCL, through host memory under gloo).  A single rank
+    without a forced group issues no collective."""
+    if not active():
+        return t
+    if dist.get_backend() == "gloo" and t.is_cuda:
+        h = t.cpu()
+        dist.all_reduce(h)
+        t.copy_(h)
+    else:
+        dist.all_reduce(t)
+    return t
+
+
 def broadcast_module(module, src=0):
     """Re-synchronise replicated parameters (float atomics in backward can let replicas drift by ulps)."""
     if active():

@@ -505,7 +505,17 @@ def build_parser():
     p.add_argument("--shapes", choices=['trapezoid', 'hexagon', 'both'], default='trapezoid')
     p.add_argument("--stable_actions_only", action='store_true',
                    help="Restrict every action set to the stable placements (filter_actions ∩ is_action_stable_rbe), in both loops.")
+    # the evaluation options of the vectorised loop enter the namespace only when given (argparse.SUPPRESS), so that a plain
+    # parse keeps the keys it always had; their defaults (EVAL_DEFAULTS) apply where run_vectorised reads them
+    p.add_argument("--eval_envs", type=int, default=argparse.SUPPRESS,
+                   help="Vectorised loop: greedy evaluation of one episode in each of N envs every --evaluate_every episodes "
+                        "(default 0: none). The single-env loop evaluates one episode anyway and ignores it.")
+    p.add_argument("--eval_epsilon", type=float, default=argparse.SUPPRESS,
+                   help="Vectorised loop: exploration rate of the evaluation episodes (default 0.0: greedy, as the reference).")
     return p
+
+
+EVAL_DEFAULTS = dict(eval_envs=0, eval_epsilon=0.0)
 
 
 def make_setup_fct(args):

@@ -15,7 +15,12 @@ Semantics follow rollout_episode / train_policy_net / update_target_net of the r
 * uniform replay draws WITH replacement (torch.randint on the device ring; the reference's random.sample draws without:
   a duplicate inside a batch of 32 out of >= 10^4 records has probability ~5e-2 and only repeats a sample);
 * with several ranks every rank trains an identical replica on the identical gathered ring (same sampling seed); extra
-  GPUs add rollout throughput, not optimiser throughput; parameters are re-broadcast every 100 lock-steps.
+  GPUs add rollout throughput, not optimiser throughput; parameters are re-broadcast every 100 lock-steps;
+* log_episode's numbers (successor_dqn.py:479-499) are logged per lock-step as means over the episodes that ended in it on all
+  ranks (EpisodeStats; the reference logs every episode);
+* the evaluation (successor_dqn.py:749-781) runs one greedy episode in each of --eval_envs envs at once and logs their means;
+  --eval_epsilon > 0 (an extension: the reference evaluates greedily only) explores with the training rule on the evaluation's
+  own count images.
 
 How a lock-step is spent: acting through the factored SuccessorMLP forward whose first layer reads
 the bit-packed rasters (bridges_bits_linear); the TD / successor-feature targets of ALL optimiser steps of the lock-step
@@ -32,12 +37,14 @@ from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import VecAssemblyGym
 from robotoddler.training import distributed as D
 from robotoddler.training import records as R
+from robotoddler.training.episode_stats import EpisodeStats
 from robotoddler.training import train_step as T
 
 
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
-                 seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False):
+                 seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
+                 episode_stats=False):
         self.policy_net, self.target_net, self.opt, self.env = policy_net, target_net, optimizer, env
         # stable actions only: the rollout env and the replay scratch env narrow every candidate set to the stable placements,
         # so acting, exploring, the TD target's max over next actions and the done flags all see the same smaller set
@@ -70,6 +77,9 @@ class VecDQN:
         self.episodes_done = 0
         self.env_steps = 0
         self._counts_host = torch.zeros(2, dtype=torch.int64).pin_memory()      # (env-steps, finished episodes) of a lock-step
+        # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
+        self.episode_stats = (EpisodeStats(env.E, env.K, gamma, len(env.targets), self.device) if episode_stats else None)
+        self._eval_state = {}                                # evaluate(): (random stream, EpisodeStats, count images) per env shape
 
     ROW_CHUNK = 2048       # rows per forward call: ONE input shape for the whole run (MIOpen tunes per shape)
     DEDUP_STATES = True    # envs in the same state share one set of candidate rows (tests compare with False)
@@ -244,31 +254,39 @@ class VecDQN:
     # ------------------------------------------------------------------ one lock-step of acting
     @torch.no_grad()
     def act(self, greedy=False):
-        env, E = self.env, self.env.E
+        rec, valid, self._q_sel = self._act_on(self.env, self.step_images, self.explore_gen, self.epsilon, greedy)
+        return rec, valid
+
+    @torch.no_grad()
+    def _act_on(self, env, step_images, explore_gen, epsilon, greedy):
+        """One lock-step of acting on ``env``: epsilon-greedy choice (exploring envs draw from ``explore_gen`` and take the
+        candidate that overlaps least with the count images ``step_images`` [K + 1, S, S], which get the explored rasters
+        added), records, env.step.  -> (rec [E, W], valid [E], q of the chosen rows [E])."""
+        E = env.E
         stable = self._stable_flags(env)
         idx, row_env, seg, rep = self._rows(env, stable)
-        self._q_sel = torch.zeros(E, dtype=torch.float32, device=self.device)
+        q_sel = torch.zeros(E, dtype=torch.float32, device=self.device)
         if idx.numel():
             step_of_row = env.n_blocks[row_env].long()
             q = self._policy_q(env, idx, row_env, stable)
             if self._factored(self.policy_net):
                 # overlap of every candidate with the count image of its episode step, straight from the bit-packed
                 # rasters (exact: integer-valued sums)
-                join = ops.bits_dot(env.cand_bits, self.step_images, step_of_row, bits_row=idx)
+                join = ops.bits_dot(env.cand_bits, step_images, step_of_row, bits_row=idx)
             else:
-                join = (self.step_images[step_of_row] * env.crop(env.cand_raster[idx])).sum(dim=(1, 2))
+                join = (step_images[step_of_row] * env.crop(env.cand_raster[idx])).sum(dim=(1, 2))
             # greedy row = first maximum of q, exploring row = first minimum of the overlap, per env, in ONE launch
             # (bridges_eps_greedy_select; an `if explore.any()` here would make the host wait for the Q pass it has just queued)
-            u = torch.rand(E, generator=self.explore_gen, device=self.device)
-            sel_compact, sel_index, self._q_sel, ex_w = ops.eps_greedy_select(seg, q, join, u, self.epsilon, greedy, idx,
-                                                                              env.cand_offset[:E], rep=rep)
+            u = torch.rand(E, generator=explore_gen, device=self.device)
+            sel_compact, sel_index, q_sel, ex_w = ops.eps_greedy_select(seg, q, join, u, epsilon, greedy, idx, env.cand_offset[:E],
+                                                                        rep=rep)
             # count images of the explored choices; every env takes part with weight 0 or 1, so no host decision
             step_of_env = env.n_blocks.long()
             if env.img == 64:                                     # the set pixels of the chosen rasters, by float atomics
-                ops.bits_accumulate_(self.step_images, env.cand_bits, step_of_env, weight=ex_w, bits_row=sel_compact)
+                ops.bits_accumulate_(step_images, env.cand_bits, step_of_env, weight=ex_w, bits_row=sel_compact)
             else:
                 picked = env.crop(ops.bits_to_f32(env.cand_bits[sel_compact])) * ex_w[:, None, None]
-                self.step_images.index_add_(0, step_of_env, picked)
+                step_images.index_add_(0, step_of_env, picked)
         else:
             sel_compact = torch.zeros(E, dtype=torch.long, device=self.device)
             sel_index = (sel_compact - env.cand_offset[:E].long()).clamp(min=0).to(torch.int32)
@@ -277,7 +295,42 @@ class VecDQN:
         rec = R.pack_state(env, sel_compact)
         env.step(sel_index)
         valid = R.pack_result(env, rec)
-        return rec, valid
+        return rec, valid, q_sel
+
+    # ------------------------------------------------------------------ greedy evaluation (successor_dqn.py:749-781)
+    @torch.no_grad()
+    def evaluate(self, eval_env, epsilon=0.0):
+        """One episode in every env of ``eval_env`` (a VecAssemblyGym of the training task) under the current policy net: greedy
+        (the first maximum of q) for epsilon == 0, else the training rule with the evaluation's own count images and random
+        stream.  Runs exactly eval_env.K lock-steps -- every episode ends by truncation at K at the latest -- and reads the
+        statistics back once.  Touches no training state (rollout env, count images, ring, random streams, epsilon, counters).
+        -> log_episode's keys as means over the N = eval_env.E episodes, plus success_rate and episodes."""
+        if eval_env is self.env:
+            raise ValueError("evaluate() needs an env of its own: the training env's episodes would be cut short")
+        if bool(getattr(eval_env, "stable_actions_only", False)) != self.stable_actions_only:
+            raise ValueError("the evaluation env's stable_actions_only must match the training env's")
+        key = (eval_env.E, eval_env.K, len(eval_env.targets))
+        st = self._eval_state.get(key)
+        if st is None:
+            gen = torch.Generator(device=self.device).manual_seed(0xE7A1 + self.seed * 1000 + self.rank)
+            stats = EpisodeStats(eval_env.E, eval_env.K, self.gamma, len(eval_env.targets), self.device, count_first_only=True,
+                                 across_ranks=False)
+            images = torch.zeros((eval_env.K + 1, eval_env.img, eval_env.img), dtype=torch.float32, device=self.device)
+            st = self._eval_state[key] = (gen, stats, images)
+        gen, stats, images = st
+        stats.reset()
+        images.zero_()
+        eval_env.reset()
+        epsilon = float(epsilon)
+        for _ in range(eval_env.K):
+            rec, valid, _q = self._act_on(eval_env, images, gen, epsilon, epsilon <= 0.0)
+            stats.fold(rec, valid)
+        vals = stats.take().get()                                  # the one wait of the evaluation
+        if vals["episodes"] != eval_env.E:
+            raise RuntimeError(f"evaluation: {vals['episodes']} of {eval_env.E} episodes ended within {eval_env.K} lock-steps "
+                               "(an env whose fresh state has no valid candidate never starts one)")
+        return dict(reward=vals["reward"], lin_reward=vals["lin_reward"], avg_loss=None, num_steps=vals["num_steps"],
+                    stable=vals["stable"], collision=0.0, success_rate=vals["success_rate"], episodes=vals["episodes"])
 
     # ------------------------------------------------------------------ gradient steps on sampled batches
     def _replay_env(self, n_states):
@@ -451,6 +504,8 @@ class VecDQN:
         a DeferredLosses (see train_steps): nothing after the replay push waits for the GPU, so the optimiser steps run
         under the host's queueing of the next lock-step."""
         rec, valid = self.act()
+        if self.episode_stats is not None:
+            self.episode_stats.fold(rec, valid)                # before the all-gather: env identity still holds
         if self.prioritized:
             rec[:, R.O_TD] = self.td_errors(rec).to(rec.dtype)
         # ONE wait per lock-step on this side: the two counts ride to pinned memory in front of the next act's candidate rows,
@@ -496,14 +551,27 @@ class DeferredLosses:
 def lockstep_log_values(info):
     """What one lock-step hands to the aim / wandb sinks, under the reference's names (successor_dqn.py:489-499) where the
     quantity exists per lock-step: reward / lin_reward = mean over the lock-step's transitions (the reference: discounted
-    sum over one episode), avg_loss, num_steps = env-steps of the lock-step on this rank, epsilon; plus the run counters."""
+    sum over one episode), avg_loss, num_steps = env-steps of the lock-step on this rank, epsilon; plus the run counters.
+    Then the per-episode statistics (EpisodeStats): the episodes that ended in the lock-step on all ranks and the means over
+    them of log_episode's discounted reward / lin_reward, episode length and final stability, and the fraction that reached
+    the targets (None when no episode ended)."""
     return dict(reward=info['mean_reward'], lin_reward=info['mean_lin_reward'], avg_loss=info['avg_loss'],
                 num_steps=info['lockstep_env_steps'], epsilon=info['epsilon'], env_steps=info['env_steps'],
-                steps_per_s=info['steps_per_s'])
+                steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
+
+
+# per-lock-step keys of the episode statistics in run_vectorised's info (and lockstep_log_values), in log order
+EPISODE_KEYS = ("episodes_finished", "episode_reward", "episode_lin_reward", "episode_num_steps", "episode_stable", "success_rate")
+
+
+def next_multiple(n, every):
+    """The first multiple of ``every`` above ``n`` finished episodes: the next checkpoint / evaluation threshold of the vectorised
+    loop, from 0 at the start and from the restored episode count on resume."""
+    return (n // every + 1) * every
 
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
-    from robotoddler.training.successor_dqn import make_nets, track_run_sinks
+    from robotoddler.training.successor_dqn import EVAL_DEFAULTS, make_nets, track_run_sinks
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
@@ -527,27 +595,41 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     capacity = max(args['replay_buffer_capacity'], 4 * args['num_envs'] * world)
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
-                   stable_actions_only=args.get('stable_actions_only', False))
+                   stable_actions_only=args.get('stable_actions_only', False), episode_stats=True)
+    # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
+    # training task every --evaluate_every finished episodes
+    eval_envs = args.get('eval_envs', EVAL_DEFAULTS['eval_envs'])
+    eval_epsilon = args.get('eval_epsilon', EVAL_DEFAULTS['eval_epsilon'])
+    eval_env = None
+    if eval_envs > 0 and rank == 0:
+        eval_env = VecAssemblyGym(eval_envs, geoms, obstacles, targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
+                                  device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net),
+                                  img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
     history, t0, it = [], time.time(), 0
-    next_ckpt = args['checkpoint_every']
+    next_ckpt = next_multiple(0, args['checkpoint_every'])
+    next_eval = next_multiple(0, args['evaluate_every'])
     if args.get('load_checkpoint'):                      # successor_dqn.py:654-665 + utils.py:31-50 of the reference
         from robotoddler.utils.utils import load_checkpoint
         path = args['load_checkpoint']
         load_checkpoint(path, policy_net, target_net, agent.ring, opt,
                         devices=dict(policy_net=device, target_net=device, optimizer=device))
         it = agent.load_extra(os.path.join(path, 'agent.pt'))['lockstep']
-        next_ckpt = (agent.episodes_done // args['checkpoint_every'] + 1) * args['checkpoint_every']
+        next_ckpt = next_multiple(agent.episodes_done, args['checkpoint_every'])
+        next_eval = next_multiple(agent.episodes_done, args['evaluate_every'])
         env.reset()                                      # a checkpoint is taken with all environments freshly reset
     steps_at_start, t0 = agent.env_steps, time.time()    # throughput counts what THIS run (resumed or not) has stepped
 
     def finish(entry):
         """Fill in the numbers of a lock-step that were still on their way to the host when its entry was made."""
-        info, deferred, stats_host, done = entry
+        info, deferred, stats_host, done, episodes = entry
         ls = deferred.get()
         info['avg_loss'] = float(np.mean(ls)) if ls else None
         if stats_host is not None:
             done.synchronize()
             info['mean_reward'], info['mean_lin_reward'] = float(stats_host[0]), float(stats_host[1])
+        ep = episodes.get()
+        info.update(episodes_finished=ep['episodes'], episode_reward=ep['reward'], episode_lin_reward=ep['lin_reward'],
+                    episode_num_steps=ep['num_steps'], episode_stable=ep['stable'], success_rate=ep['success_rate'])
         if rank == 0 and (aim_run is not None or wandb_run is not None):
             # one call per lock-step, step = episodes finished so far (the reference's x axis is the episode number)
             track_run_sinks(lockstep_log_values(info), info['episodes'], 'training', aim_run=aim_run, wandb_run=wandb_run)
@@ -568,7 +650,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                 save_checkpoint(args['save_checkpoint'], policy_net, target_net, agent.ring, opt, agent.episodes_done,
                                 {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v)) for k, v in args.items()})
                 agent.save_extra(os.path.join(args['save_checkpoint'], str(agent.episodes_done), 'agent.pt'), lockstep=it)
-            next_ckpt = (agent.episodes_done // args['checkpoint_every'] + 1) * args['checkpoint_every']
+            next_ckpt = next_multiple(agent.episodes_done, args['checkpoint_every'])
             # the single-env reference checkpoints between episodes; the lock-step analogue: every rank starts all its
             # environments afresh, so that a resumed run (fresh environments) continues exactly like this one
             env.reset()
@@ -581,13 +663,23 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
             stats_host.copy_(torch.stack([rec[:, R.O_REWARD].mean(), rec[:, R.O_LIN].mean()]).double(), non_blocking=True)
             done = torch.cuda.Event()
             done.record()
+        episodes = agent.episode_stats.take()             # the episodes that ended in this lock-step, on every rank
         info = dict(lockstep=it, episodes=agent.episodes_done, env_steps=agent.env_steps, avg_loss=None, mean_reward=None,
                     mean_lin_reward=None, epsilon=agent.epsilon, lockstep_env_steps=agent.env_steps - steps_before,
-                    steps_per_s=(agent.env_steps - steps_at_start) * world / max(time.time() - t0, 1e-9))
+                    steps_per_s=(agent.env_steps - steps_at_start) * world / max(time.time() - t0, 1e-9),
+                    **{k: None for k in EPISODE_KEYS})
+        if eval_envs > 0 and agent.episodes_done >= next_eval:
+            if rank == 0:
+                ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)
+                if aim_run is not None or wandb_run is not None:
+                    track_run_sinks(ev, agent.episodes_done, 'evaluation', aim_run=aim_run, wandb_run=wandb_run)
+                if args['verbose']:
+                    print(f"evaluation {agent.episodes_done}: {ev}")
+            next_eval = next_multiple(agent.episodes_done, args['evaluate_every'])
         history.append(info)
         if pending is not None:
             finish(pending)
-        pending = (info, losses, stats_host, done)
+        pending = (info, losses, stats_host, done, episodes)
     if pending is not None:
         finish(pending)
     T.sync_optimizer(policy_net)       # the captured step counts Adam's steps itself: hand the count back before anyone reads opt.state

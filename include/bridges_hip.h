@@ -379,6 +379,14 @@ int bridges_record_state(int32_t E, int32_t K, const int32_t* n_blocks, const in
  * env-step of env e (reset-only lock-steps are not transitions). */
 int bridges_record_result(int32_t E, const float* reward, const float* lin_reward, const uint8_t* step_flags, double* rec,
                           uint8_t* valid, void* stream);
+/* Per-episode statistics (log_episode, successor_dqn.py:479-499) of one lock-step's records rec [E, REC_WIDTH] / valid [E], taken
+ * before the all-gather.  gpow [K] = float32(gamma ** i); run [E, 2] (running discounted reward / lin_reward) and counted [E]
+ * persist between calls.  Per valid env: i = rec[NB]; i == 0 restarts run; run += gpow[i] * (reward, lin_reward) in float32
+ * without fused multiply-add; at REC_DONE, unless count_first_only and counted > 0, out[0..5] += (1, run[0], run[1], i + 1,
+ * REC_STABLE_N, reward == n_targets), then counted++.  out [8] float64 is added to in place (slots 6, 7 spare); one workgroup,
+ * fixed-order reduction (bitwise reproducible), no allocation; E == 0 is a no-op. */
+int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow, int32_t n_targets,
+                          int32_t count_first_only, float* run, int32_t* counted, double* out, void* stream);
 /* Sampled records -> the state arrays of a replay env of E >= n_rec envs (envs >= n_rec repeat record 0): s' = s plus the
  * action block with the occupancy update of gym_env.py:228-232, its RAW candidate count
  * n_groups * (n_ground + free faces * n_off) (generate_actions, actions.py:7-52; bridges_env_refresh clamps it to the env's

@@ -1,5 +1,7 @@
 """Lists the host synchronisations of one pipelined VecDQN lock-step (torch.cuda.set_sync_debug_mode): each one is a
-point where the host stops queueing work until the GPU has caught up.  Usage: python tools/find_syncs.py [--model M]"""
+point where the host stops queueing work until the GPU has caught up.  Usage: python tools/find_syncs.py [--model M]
+[--episode_stats]: with the per-episode statistics on, every lock-step also folds its records and hands the sums to pinned
+memory, as run_vectorised does (the count printed should not change)."""
 import argparse
 import os
 import sys
@@ -13,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")
 ap = argparse.ArgumentParser()
 ap.add_argument("--model", default="SuccessorMLP")
 ap.add_argument("--envs", type=int, default=4096)
+ap.add_argument("--episode_stats", action="store_true", help="VecDQN(episode_stats=True) plus one EpisodeStats.take() per lock-step")
 a = ap.parse_args()
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import VecAssemblyGym
@@ -27,9 +30,17 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i 
                      [(0.5, 0, 4 * H + H / 2)], max_steps=15, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=False)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
-               "mse_block_features")
-for _ in range(5):
+               "mse_block_features", episode_stats=a.episode_stats)
+
+
+def lockstep():
     agent.lockstep(25, defer_losses=True)
+    if agent.episode_stats is not None:
+        agent.episode_stats.take()
+
+
+for _ in range(5):
+    lockstep()
 torch.cuda.synchronize()
 seen = []
 
@@ -43,7 +54,7 @@ def hook(message, category, filename, lineno, file=None, line=None):
 warnings.showwarning = hook
 warnings.simplefilter("always")
 torch.cuda.set_sync_debug_mode("warn")
-agent.lockstep(25, defer_losses=True)
+lockstep()
 torch.cuda.set_sync_debug_mode("default")
 for s in seen:
     print(s)

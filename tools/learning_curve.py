@@ -1,7 +1,9 @@
 """Does the vectorised loop learn?  Trains a Q-network (--model SuccessorMLP | ConvNet | UNet) on tower_height=2 for a fixed
-number of lock-steps and prints the mean sparse reward, linear reward and loss per block of lock-steps (evaluation = the running
-epsilon-greedy rollouts).
-    python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values]"""
+number of lock-steps and prints per block of lock-steps the statistics of the training episodes that ended in it (EpisodeStats:
+log_episode's discounted reward / lin_reward, length, final stability, and success_rate = the fraction that reached the target,
+all under the running epsilon-greedy exploration) and the mean loss; with --eval_envs N also the greedy evaluation of the policy
+at the end of the block (VecDQN.evaluate: one episode in each of N envs, --eval_epsilon 0 = the reference's greedy policy).
+    python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values] [--eval_envs 64]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -9,7 +11,6 @@ import numpy as np
 import torch
 from robotoddler.training.successor_dqn import build_parser, make_nets
 from robotoddler.training.vec_dqn import VecDQN
-from robotoddler.training import records as R
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import VecAssemblyGym
 
@@ -24,6 +25,8 @@ ap.add_argument("--lr", type=float, default=1e-4)
 ap.add_argument("--block", type=int, default=100)
 ap.add_argument("--model", default="SuccessorMLP")
 ap.add_argument("--stable_actions_only", action="store_true", help="every action set restricted to the stable placements")
+ap.add_argument("--eval_envs", type=int, default=0, help="> 0: greedy evaluation over this many envs at the end of every block")
+ap.add_argument("--eval_epsilon", type=float, default=0.0, help="exploration rate of the evaluation episodes")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 args = vars(build_parser().parse_args(["--model", a.model, "--loss_function", a.loss]))
@@ -34,20 +37,26 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i 
                      [(0.5, 0, a.tower * H + H / 2)], max_steps=a.max_steps, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
-               eps_decay=0.997, stable_actions_only=a.stable_actions_only)
+               eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True)
+eval_env = None
+if a.eval_envs > 0:
+    eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(a.tower)],
+                              [(0.5, 0, a.tower * H + H / 2)], max_steps=a.max_steps, seed=1, device=dev,
+                              f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
+r4 = lambda v: None if v is None else round(v, 4)
 t0 = time.time()
-acc = dict(steps=0, reward=0.0, lin=0.0, done=0, solved=0, loss=[])
+deferred = []
 for it in range(1, a.locksteps + 1):
-    losses, rec = agent.lockstep(a.train_steps)
-    acc["steps"] += rec.shape[0]
-    acc["reward"] += float(rec[:, R.O_REWARD].sum()); acc["lin"] += float(rec[:, R.O_LIN].sum())
-    d = rec[:, R.O_DONE] > 0.5
-    acc["done"] += int(d.sum()); acc["solved"] += int((d & (rec[:, R.O_REWARD] > 0.5)).sum())
-    acc["loss"] += losses
+    deferred.append(agent.lockstep(a.train_steps, defer_losses=True)[0])
     if it % a.block == 0:
-        print(json.dumps(dict(lockstep=it, seconds=round(time.time() - t0, 1), epsilon=round(agent.epsilon, 3),
-                              mean_reward=round(acc["reward"] / max(acc["steps"], 1), 4),
-                              mean_lin_reward=round(acc["lin"] / max(acc["steps"], 1), 4),
-                              episodes=acc["done"], solved_fraction=round(acc["solved"] / max(acc["done"], 1), 4),
-                              mean_loss=round(float(np.mean(acc["loss"])), 5) if acc["loss"] else None)), flush=True)
-        acc = dict(steps=0, reward=0.0, lin=0.0, done=0, solved=0, loss=[])
+        ep = agent.episode_stats.take().get()                   # the episodes that ended in the block: one read per block
+        losses = [l for d in deferred for l in d.get()]
+        line = dict(lockstep=it, seconds=round(time.time() - t0, 1), epsilon=round(agent.epsilon, 3), episodes=ep["episodes"],
+                    success_rate=r4(ep["success_rate"]), episode_reward=r4(ep["reward"]), episode_lin_reward=r4(ep["lin_reward"]),
+                    episode_num_steps=r4(ep["num_steps"]), episode_stable=r4(ep["stable"]),
+                    mean_loss=round(float(np.mean(losses)), 5) if losses else None)
+        if eval_env is not None:
+            ev = agent.evaluate(eval_env, a.eval_epsilon)
+            line.update(eval_success_rate=r4(ev["success_rate"]), eval_reward=r4(ev["reward"]), eval_num_steps=r4(ev["num_steps"]))
+        print(json.dumps(line), flush=True)
+        deferred = []

@@ -28,6 +28,8 @@ ap.add_argument("--channels_last", action="store_true")
 ap.add_argument("--shapes", default="trapezoid", choices=["trapezoid", "hexagon", "both"])
 ap.add_argument("--bridge_length", type=int, default=0, help="> 0: horizontal_bridge_setup(num_obstacles=N) instead of the tower")
 ap.add_argument("--stable_actions_only", action="store_true", help="every action set restricted to the stable placements")
+ap.add_argument("--episode_stats", action="store_true",
+                help="per-episode statistics on (one bridges_episode_stats launch per lock-step, read one lock-step late)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 if a.miopen_search:
@@ -48,7 +50,8 @@ env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obs
                      device=dev, f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=a.stable_actions_only,
                      stable_actions_only=a.stable_actions_only)
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
-agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only)
+agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
+               episode_stats=a.episode_stats)
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -61,11 +64,14 @@ torch.cuda.synchronize(); s0 = agent.env_steps; t0 = time.perf_counter()
 pending, per_step, tp = None, [], t0
 for _ in range(a.locksteps):
     deferred, _rec = agent.lockstep(a.train_steps, defer_losses=True)
+    stats = agent.episode_stats.take() if agent.episode_stats is not None else None
     if pending is not None:
-        pending.get()
-    pending = deferred
+        pending[0].get()
+        if pending[1] is not None:
+            pending[1].get()
+    pending = (deferred, stats)
     tn = time.perf_counter(); per_step.append(tn - tp); tp = tn
-losses = pending.get()
+losses = pending[0].get()
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 steps_done = agent.env_steps - s0

@@ -121,11 +121,11 @@ def conv3x3_relu_o16(x, weight, bias, pool=False, x2=None, both=False, proj=None
       x2=tensor        -> the input is torch.cat([x, x2], dim=1) (16 + 16 channels), not materialised;
       proj=(w1, b1)    -> conv2d(it, w1, b1) for a 1x1 convolution w1 [1,16,1,1] to one channel."""
     L = abi.require_gpu()
-    x = x.contiguous()
+    x = _vec4(x)
     n, c_in, H, W = x.shape
     c_in2 = 0
     if x2 is not None:
-        x2 = x2.contiguous()
+        x2 = _vec4(x2)
         assert x2.shape[0] == n and x2.shape[2:] == x.shape[2:]
         c_in2 = x2.shape[1]
     dev = x.device
@@ -319,8 +319,9 @@ def conv3x3_wgrad(g, x, g_mask=None, owner=None):
 
 
 def maxpool2(a):
+    """max_pool2d(a, 2) by bridges_maxpool2: even H, W a multiple of 4 (one thread reads four columns of two rows as float4)."""
     L = abi.require_gpu()
-    a = a.contiguous()
+    a = _vec4(a)
     n, c, H, W = a.shape
     y = torch.empty((n, c, H // 2, W // 2), dtype=torch.float32, device=a.device)
     abi.check(L.bridges_maxpool2(_ptr(a), _ptr(y), n * c, H, W, _stream()), "bridges_maxpool2")
@@ -330,7 +331,7 @@ def maxpool2(a):
 def maxpool2_relu_backward(a, dy):
     """Gradient at the pre-pool activation a = relu(.) from dy at max_pool2d(a, 2) (first maximum takes it, times [a > 0])."""
     L = abi.require_gpu()
-    a, dy = a.contiguous(), dy.contiguous()
+    a, dy = _vec4(a), _vec4(dy)
     n, c, H, W = a.shape
     g = torch.empty_like(a)
     abi.check(L.bridges_maxpool2_relu_backward(_ptr(a), _ptr(dy), _ptr(g), n * c, H, W, _stream()), "bridges_maxpool2_relu_backward")
@@ -344,7 +345,7 @@ class MaxPool2OfReLUFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a):
-        a = a.contiguous()
+        a = _vec4(a)
         ctx.save_for_backward(a)
         return maxpool2(a)
 
@@ -355,7 +356,8 @@ class MaxPool2OfReLUFunction(torch.autograd.Function):
 
 
 def maxpool2_of_relu_applies(a):
-    return a.is_cuda and a.dtype == torch.float32 and a.dim() == 4 and a.shape[2] % 2 == 0 and a.shape[3] % 2 == 0 and torch.is_grad_enabled()
+    """Shapes bridges_maxpool2 / bridges_maxpool2_relu_backward cover: an even height and a width that is a multiple of 4."""
+    return a.is_cuda and a.dtype == torch.float32 and a.dim() == 4 and a.shape[2] % 2 == 0 and a.shape[3] % 4 == 0 and torch.is_grad_enabled()
 
 
 class ConvBlockFunction(torch.autograd.Function):

@@ -225,7 +225,7 @@ def reward_prefix(reward_map):
     bridges_action_features takes the linear reward of a candidate from (build it once per task)."""
     pre = np.zeros((64, 65), dtype=np.float64)
     pre[:, 1:] = np.cumsum(reward_map.detach().cpu().numpy().astype(np.float64).reshape(64, 64), axis=1)
-    return upload(reward_map.device, pre)[0]
+    return upload(device(), pre)[0]                        # the kernel's table: on the GPU whatever device the map is on
 
 
 def action_features(blocks, xlim, ylim, state_bits=None, obstacle_bits=None, reward_map=None, img_size=(64, 64), want_f32=False,

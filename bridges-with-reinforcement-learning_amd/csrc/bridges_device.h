@@ -66,6 +66,14 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     return z ^ (z >> 31);
 }
 
+// ReLU and maximum as torch computes them: a NaN operand stays NaN (fmaxf returns the other operand and `v > 0 ? v : 0`
+// returns 0, which would hide a NaN born in a hidden layer from the loss and from the train-step guard).  For every other
+// operand the results are those of fmaxf(v, 0) / fmaxf(a, b); of equal operands (+0 / -0) the earlier one is kept, as
+// max_pool2d's scan keeps it.
+__device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
+__device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float max4_nan(float a, float b, float c, float d) { return max_nan(max_nan(a, b), max_nan(c, d)); }
+
 __device__ __forceinline__ double shfl_d(double v, int src) { return __shfl(v, src, WAVE); }
 
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {

@@ -121,8 +121,8 @@ __global__ __launch_bounds__(256) void k_conv3x3_o16(const float* __restrict__ x
         for (int c = 0; c < 4; ++c) {
             const f32x4 u = acc[0][c], v = acc[1][c];
             float2 p;
-            p.x = fmaxf(fmaxf(fmaxf(u[0], u[1]), fmaxf(v[0], v[1])) + b, 0.f);
-            p.y = fmaxf(fmaxf(fmaxf(u[2], u[3]), fmaxf(v[2], v[3])) + b, 0.f);
+            p.x = relu_nan(max4_nan(u[0], u[1], v[0], v[1]) + b);
+            p.y = relu_nan(max4_nan(u[2], u[3], v[2], v[3]) + b);
             *reinterpret_cast<float2*>(o + 8 * c + 2 * q) = p;
         }
     }
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_o16(const float* __restrict__ x
             for (int c = 0; c < 4; ++c) {
                 const f32x4 u = acc[r][c];
                 float4 p;
-                p.x = fmaxf(u[0] + b, 0.f); p.y = fmaxf(u[1] + b, 0.f); p.z = fmaxf(u[2] + b, 0.f); p.w = fmaxf(u[3] + b, 0.f);
+                p.x = relu_nan(u[0] + b); p.y = relu_nan(u[1] + b); p.z = relu_nan(u[2] + b); p.w = relu_nan(u[3] + b);
                 *reinterpret_cast<float4*>(o + 16 * c + 4 * q) = p;
             }
         }
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(256) void k_conv3x3_o16(const float* __restrict__ x
             for (int c = 0; c < 4; ++c) {
                 const f32x4 u = acc[r][c];
                 float4 p;
-                p.x = pw * fmaxf(u[0] + b, 0.f); p.y = pw * fmaxf(u[1] + b, 0.f);
-                p.z = pw * fmaxf(u[2] + b, 0.f); p.w = pw * fmaxf(u[3] + b, 0.f);
+                p.x = pw * relu_nan(u[0] + b); p.y = pw * relu_nan(u[1] + b);
+                p.z = pw * relu_nan(u[2] + b); p.w = pw * relu_nan(u[3] + b);
 #pragma unroll
                 for (int m = 1; m < 16; m <<= 1) {               // sum over the 16 lanes of the group (fixed butterfly order)
                     p.x += __shfl_xor(p.x, m); p.y += __shfl_xor(p.y, m); p.z += __shfl_xor(p.z, m); p.w += __shfl_xor(p.w, m);

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256, C3_MIN_WAVES) void k_c3(const float* __restric
         c3_f32x4 u = acc[i];
         float4 p;
         if (EPI == C3_EPI_BIAS_RELU) {
-            p.x = fmaxf(u[0] + b, 0.f); p.y = fmaxf(u[1] + b, 0.f); p.z = fmaxf(u[2] + b, 0.f); p.w = fmaxf(u[3] + b, 0.f);
+            p.x = relu_nan(u[0] + b); p.y = relu_nan(u[1] + b); p.z = relu_nan(u[2] + b); p.w = relu_nan(u[3] + b);
         } else if (EPI == C3_EPI_MASK) {
             const float4 m = *reinterpret_cast<const float4*>(mask_src + o);
             p.x = m.x > 0.f ? u[0] : 0.f; p.y = m.y > 0.f ? u[1] : 0.f; p.z = m.z > 0.f ? u[2] : 0.f; p.w = m.w > 0.f ? u[3] : 0.f;
@@ -574,8 +574,8 @@ __global__ __launch_bounds__(256) void k_maxpool2(const float* __restrict__ a, f
     const float* p = a + (nc * H + 2 * r) * W + 4 * qd;
     const float4 a0 = *reinterpret_cast<const float4*>(p), a1 = *reinterpret_cast<const float4*>(p + W);
     float2 o;
-    o.x = fmaxf(fmaxf(a0.x, a0.y), fmaxf(a1.x, a1.y));
-    o.y = fmaxf(fmaxf(a0.z, a0.w), fmaxf(a1.z, a1.w));
+    o.x = max4_nan(a0.x, a0.y, a1.x, a1.y);
+    o.y = max4_nan(a0.z, a0.w, a1.z, a1.w);
     *reinterpret_cast<float2*>(y + (nc * h2 + r) * (W >> 1) + 2 * qd) = o;
 }
 
@@ -593,13 +593,13 @@ __global__ __launch_bounds__(256) void k_maxpool2_relu_bwd(const float* __restri
     const float2 d = *reinterpret_cast<const float2*>(dy + (nc * h2 + r) * (W >> 1) + 2 * qd);
     float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = make_float4(0.f, 0.f, 0.f, 0.f);
     {
-        const float m = fmaxf(fmaxf(a0.x, a0.y), fmaxf(a1.x, a1.y));
+        const float m = max4_nan(a0.x, a0.y, a1.x, a1.y);
         if (m > 0.f) {
             if (a0.x == m) g0.x = d.x; else if (a0.y == m) g0.y = d.x; else if (a1.x == m) g1.x = d.x; else g1.y = d.x;
         }
     }
     {
-        const float m = fmaxf(fmaxf(a0.z, a0.w), fmaxf(a1.z, a1.w));
+        const float m = max4_nan(a0.z, a0.w, a1.z, a1.w);
         if (m > 0.f) {
             if (a0.z == m) g0.z = d.y; else if (a0.w == m) g0.w = d.y; else if (a1.z == m) g1.z = d.y; else g1.w = d.y;
         }

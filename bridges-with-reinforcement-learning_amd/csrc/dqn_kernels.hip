@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void k_bias_relu(float* __restrict__ x, const 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float b = bias[(i / hw4) % C];
         float4 v = x4[i];
-        v.x = fmaxf(v.x + b, 0.f); v.y = fmaxf(v.y + b, 0.f); v.z = fmaxf(v.z + b, 0.f); v.w = fmaxf(v.w + b, 0.f);
+        v.x = relu_nan(v.x + b); v.y = relu_nan(v.y + b); v.z = relu_nan(v.z + b); v.w = relu_nan(v.w + b);
         x4[i] = v;
     }
 }
@@ -322,8 +322,8 @@ __global__ __launch_bounds__(256) void k_bias_relu_pool2(const float* __restrict
         const float* p = x + (nc * H + 2 * r) * W + 4 * q;
         const float4 a0 = *reinterpret_cast<const float4*>(p), a1 = *reinterpret_cast<const float4*>(p + W);
         float2 o;
-        o.x = fmaxf(fmaxf(fmaxf(a0.x, a0.y), fmaxf(a1.x, a1.y)) + b, 0.f);
-        o.y = fmaxf(fmaxf(fmaxf(a0.z, a0.w), fmaxf(a1.z, a1.w)) + b, 0.f);
+        o.x = relu_nan(max4_nan(a0.x, a0.y, a1.x, a1.y) + b);
+        o.y = relu_nan(max4_nan(a0.z, a0.w, a1.z, a1.w) + b);
         *reinterpret_cast<float2*>(out + (nc * h2 + r) * (W >> 1) + 2 * q) = o;
     }
 }

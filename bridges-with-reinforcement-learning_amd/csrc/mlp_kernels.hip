@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void k_lin_fwd(int K, int N, int kchunk, const
                     part[((size_t)split * rows + m) * N + n] = acc[r];
                 } else {
                     float v = acc[r] + bv;
-                    if (relu) v = v > 0.f ? v : 0.f;
+                    if (relu) v = relu_nan(v);
                     y[(size_t)m * N + n] = v;
                 }
             }
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void k_lin_fwd_finish(int rows, int N, int spl
     const size_t total = (size_t)rows * N;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         float v = split_sum(part + i, total, splits) + bias[i % N];
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (relu) v = relu_nan(v);
         y[i] = v;
     }
 }
@@ -640,7 +640,7 @@ __device__ __forceinline__ void mid_fwd_job(const f4u (&w)[K / 32], float bv, in
         for (int r = 0; r < 16; ++r) {
             float v = ((acc[r] + red[nt & 3][0][r][lane]) + red[nt & 3][1][r][lane]) + red[nt & 3][2][r][lane];
             v += bv;
-            v = v > 0.f ? v : 0.f;
+            v = relu_nan(v);
             const int m = mfma_row(r, lane);
             if (ys) ys[m * (N + MID_PAD) + n] = v;
             if (yg && m < rows_left) yg[(size_t)m * N + n] = v;
@@ -681,7 +681,7 @@ __device__ __forceinline__ void mid_fwd_job_strided(const f4u (&w)[K / 32], floa
         for (int r = 0; r < 16; ++r) {
             float v = ((acc[r] + red[nt & 3][0][r][lane]) + red[nt & 3][1][r][lane]) + red[nt & 3][2][r][lane];
             v += bv;
-            v = v > 0.f ? v : 0.f;
+            v = relu_nan(v);
             const int m = mfma_row(r, lane);
             if (m < rows_left) yg[(size_t)m * y_stride + n] = v;
         }
@@ -762,7 +762,7 @@ __global__ __launch_bounds__(1024) void k_rows2(const float* __restrict__ Wa, co
     ROWS2_FETCH(tile)
     for (; tile < n_tiles; tile += gridDim.x) {
 #pragma unroll
-        for (int j = 0; j < PER; ++j) xa[trow * (DA + MID_PAD) + tcol + j] = (RELU_IN && !(v[j] > 0.f)) ? 0.f : v[j];
+        for (int j = 0; j < PER; ++j) xa[trow * (DA + MID_PAD) + tcol + j] = RELU_IN ? relu_nan(v[j]) : v[j];
         __syncthreads();
         const int next = tile + gridDim.x;
         if (next < n_tiles) ROWS2_FETCH(next)                          // in flight under this tile's layers

@@ -230,6 +230,37 @@ def test_rbe_penalty_variant_against_the_oracle(golden_dir):
         AssemblyEnv(render=False, stability="cra")
 
 
+def test_action_features_takes_a_reward_map_from_the_host_or_the_device():
+    """ops.reward_prefix builds its table on the host and uploads it to the GPU whatever device the map is on: a CPU map and a
+    GPU map give the same bits from bridges_action_features (the table used to follow the map's device, and the kernel was
+    handed a host pointer for a CPU map)."""
+    import torch
+    from assembly_gym.envs.assembly_env import AssemblyEnv
+    from assembly_gym.envs.gym_env import Action, AssemblyGym, bridge_setup, sparse_reward
+    from bridges_hip import ops
+    from oracle.env import OracleGym
+    from oracle.env import bridge_setup as o_bridge_setup
+    from robotoddler.training.successor_dqn import get_task_features
+    lim = dict(xlim=(-3, 7), ylim=(0, 10))
+    env = AssemblyGym(**bridge_setup(num_stories=2), reward_fct=sparse_reward, restrict_2d=True, max_steps=10,
+                      assembly_env=AssemblyEnv(render=False))
+    og = OracleGym(**o_bridge_setup(num_stories=2), max_steps=10, img_size=(64, 64))
+    obs, _ = env.reset()
+    blocks = env.create_blocks([Action(*a) for a in og.candidates()["actions"]])
+    reward, _ = get_task_features(obs, img_size=(64, 64), **lim)
+    on_gpu, on_cpu = reward[0].contiguous(), reward[0].cpu().contiguous()
+    assert on_gpu.is_cuda and not on_cpu.is_cuda
+    for m in (on_gpu, on_cpu):
+        assert ops.reward_prefix(m).is_cuda
+    a = ops.action_features(blocks, lim["xlim"], lim["ylim"], reward_map=on_gpu)
+    b = ops.action_features(blocks, lim["xlim"], lim["ylim"], reward_map=on_cpu)
+    c = ops.action_features(blocks, lim["xlim"], lim["ylim"], prefix=ops.reward_prefix(on_cpu))
+    assert len(blocks) > 0 and float(a[3].abs().sum()) > 0
+    for u, v, w in zip(a, b, c):
+        if u is not None:
+            assert torch.equal(u, v) and torch.equal(u, w)
+
+
 def test_action_features_operator_equals_the_reference_composition():
     """bridges_action_features (rasters + in-bounds / no-overlap mask + linear reward in one call) against what
     the reference composes from get_action_features, filter_actions and sum(action * reward) (successor_dqn.py:84-94,

@@ -1,10 +1,14 @@
 """GPU: the hand-written training passes of the ConvBlock stacks (csrc/conv_train_kernels.hip: conv3x3 forward / input
 gradient / weight gradient on the f32 matrix cores, the pooling pair) against PyTorch float32 (the library's convolutions and
 autograd) -- operator by operator, then a ConvBlock, then whole optimiser steps of ConvNet (robotoddler/models/cv.py:5-73)."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from gpu_helpers import all_predicates_off, hand_written_nodes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -114,19 +118,15 @@ def test_convnet_optimiser_steps_follow_the_library_path():
     losses = [[], []]
     for k, net in enumerate(nets):
         opt = torch.optim.Adam(net.parameters(), lr=1e-3)
-        orig = dqn_ops.conv3x3_supported
-        if k == 1:
-            dqn_ops.conv3x3_supported = lambda *a: False                # the library path (ConvBlock.forward falls back to self.layers)
-        try:
+        with (all_predicates_off() if k == 1 else contextlib.nullcontext()):     # k == 1: the library path, no hand-written kernel
             for _ in range(3):
                 q = net(imgs[0], binary, imgs[1], imgs[2], imgs[3])[0]
+                assert bool(hand_written_nodes(q)) == (k == 0)
                 loss = F.mse_loss(q, target)
                 opt.zero_grad()
                 loss.backward()
                 opt.step()
                 losses[k].append(float(loss))
-        finally:
-            dqn_ops.conv3x3_supported = orig
     np.testing.assert_allclose(losses[0], losses[1], rtol=2e-5)
     for pa, pb in zip(nets[0].parameters(), nets[1].parameters()):
         assert rel(pa.detach(), pb.detach()) < 5e-4
@@ -168,19 +168,15 @@ def test_unet_policy_optimiser_steps_follow_the_library_path():
     losses = [[], []]
     for k, net in enumerate(nets):
         opt = torch.optim.Adam(net.parameters(), lr=1e-4)
-        orig = dqn_ops.conv3x3_supported
-        if k == 1:
-            dqn_ops.conv3x3_supported = lambda *a: False
-        try:
+        with (all_predicates_off() if k == 1 else contextlib.nullcontext()):     # k == 1: the library path, no hand-written kernel
             for _ in range(3):
                 q, sf, _ = net(imgs[0], binary, imgs[1], imgs[2], imgs[3])
+                assert bool(hand_written_nodes(q, sf)) == (k == 0)
                 loss = F.mse_loss(q, q_t) + F.mse_loss(sf[:, 0], sf_t)
                 opt.zero_grad()
                 loss.backward()
                 opt.step()
                 losses[k].append(float(loss))
-        finally:
-            dqn_ops.conv3x3_supported = orig
     np.testing.assert_allclose(losses[0][0], losses[1][0], rtol=1e-5)        # the first loss: forward passes on the same weights
     np.testing.assert_allclose(losses[0], losses[1], rtol=2e-4)              # after one / two Adam updates (losses of O(100))
     for pa, pb in zip(nets[0].parameters(), nets[1].parameters()):

@@ -159,6 +159,23 @@ class EnvBuffers(C.Structure):
         ("cand_ws_stride", C.c_int64), ("lp_snap", C.c_void_p), ("lp_snap_stride", C.c_int64)]
 
 
+# (field name, torch dtype name, shape expression in E, T) -- the device buffers of bridges_task_buffers, in header order
+GAUSS_TAPS = 101
+TASK_BUFFER_FIELDS = [
+    ("env_targets", "float64", "E,T,3"),
+    ("target_bits", "int64", "E,64"),          # uint64 on the device
+    ("reward_map", "float32", "E,64,64"),
+    ("reward_prefix", "float64", "E,64,65"),
+    ("task_episode", "int32", "E"),            # uint32 on the device
+]
+
+
+class TaskBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in TASK_BUFFER_FIELDS] + [
+        ("env_obstacle_bits", C.c_void_p), ("gauss_k", C.c_void_p), ("target_shape", C.c_int32), ("sample", C.c_int32),
+        ("x_range", C.c_double * 2), ("z_range", C.c_double * 2)]
+
+
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)
 assert [f[0] for f in EnvBuffers._fields_][-10:-7] == ["lp_ws", "lp_ws_stride", "stats"]
 
@@ -175,6 +192,8 @@ SIGNATURES = {
     "bridges_env_candidate_stability": [vp, vp],
     "bridges_env_restrict_to_stable": [vp, vp],
     "bridges_env_rebuild_contacts": [vp, vp],
+    "bridges_env_set_task_buffers": [vp, C.POINTER(TaskBuffers)],
+    "bridges_env_load_targets": [vp, vp],
     "bridges_gate_create": [C.POINTER(vp)],
     "bridges_gate_destroy": [vp],
     "bridges_env_set_gate": [vp, vp],

@@ -34,6 +34,15 @@ def _ptr(t):
 _stream = abi.current_stream
 
 
+def gaussian_vector(kernel_size=101, sigma=16):
+    """The normalised float32 vector k of the reference's Gaussian kernel k k^T (utils.py:93-115), built as the reference
+    builds it: torch float32 on the host.  gaussian_reward_map and the device's per-env reward maps (k_task_features) both
+    start from these 101 numbers."""
+    coords = torch.arange(kernel_size) - kernel_size // 2
+    k = torch.exp(-(coords.float() ** 2) / (2 * sigma ** 2))
+    return k / k.sum()
+
+
 def gaussian_reward_map(target_image, kernel_size=101, sigma=16):
     """convolve_with_gaussian(targets raster, 101, 16) of get_task_features (successor_dqn.py:77-82, utils.py:93-115): the
     zero-padded 'same' cross-correlation of the 0/1 target image with the float32 kernel k k^T, k as the reference builds it
@@ -43,9 +52,7 @@ def gaussian_reward_map(target_image, kernel_size=101, sigma=16):
     the same training run ended with different weights after an unrelated process had run convolutions on the box.
     target_image: numpy array [S, S] (the 0/1 targets raster; any weights work); returns float32 [S, S] (within 1e-7 relative
     of the library's float32 sum)."""
-    coords = torch.arange(kernel_size) - kernel_size // 2
-    k = torch.exp(-(coords.float() ** 2) / (2 * sigma ** 2))
-    k = k / k.sum()
+    k = gaussian_vector(kernel_size, sigma)
     k2 = (k.unsqueeze(0) * k.unsqueeze(1)).numpy().astype(np.float64)       # the float32 products, as the reference's kernel
     img = np.asarray(target_image, dtype=np.float64)
     S0, S1 = img.shape
@@ -102,7 +109,53 @@ def check_img_size(img_size):
     return image_size(img_size)
 
 
+class RandomTargets:
+    """``targets=RandomTargets()``: every env draws ``num_targets`` fresh targets whenever it starts an episode, as the
+    reference's tower_setup does per env.reset(**setup_fct()) (assembly_gym/envs/gym_env.py:64-79, successor_dqn.py:371):
+    x ~ U[x_range), z ~ U[z_range), y = 0.  The draw happens on the device, keyed by (seed, global env id, episode, target,
+    axis); its formula is in include/bridges_hip.h (bridges_env_set_task_buffers).  The stream is not numpy's Mersenne
+    Twister; the distribution is the reference's."""
+
+    def __init__(self, num_targets=3, x_range=(-4.0, 4.0), z_range=(0.0, 4.0)):
+        self.num_targets = int(num_targets)
+        self.x_range = (float(x_range[0]), float(x_range[1]))
+        self.z_range = (float(z_range[0]), float(z_range[1]))
+        if not 1 <= self.num_targets <= abi.MAX_TARGETS:
+            raise ValueError(f"num_targets must be 1..{abi.MAX_TARGETS}")
+        if self.x_range[0] > self.x_range[1] or self.z_range[0] > self.z_range[1]:
+            raise ValueError("empty x_range / z_range")
+
+
+def _is_per_env_targets(targets):
+    return isinstance(targets, (torch.Tensor, np.ndarray)) and targets.ndim == 3
+
+
+def _single_task_attribute(name, per_env_name):
+    """An attribute that describes THE task of a fixed-task env.  An env with per-env tasks has no such thing: reading it
+    raises instead of handing one env's map to every row."""
+    key = "_single_task_" + name
+
+    def get(self):
+        if getattr(self, "per_env_tasks", False):
+            raise abi.BridgesHipError(f"this env has per-env tasks: there is no single `{name}`; read `{per_env_name}` "
+                                      "(one entry per env)")
+        return self.__dict__[key]
+
+    def put(self, value):
+        self.__dict__[key] = value
+    return property(get, put)
+
+
 class VecAssemblyGym:
+    """``targets``: a list of (x, y, z) all envs share (the fixed task); a float64 array / tensor [E, T, 3] of per-env targets
+    that stay until set_targets() replaces them; or RandomTargets(): per-env targets redrawn on the device every episode.
+    Per-env tasks add env_targets [E,T,3], target_bits [E,64], reward_maps [E,64,64] (reward_maps_img: its [E,S,S] corner),
+    reward_prefix [E,64,65] and task_episode [E]: 49 KiB per env."""
+
+    reward_map = _single_task_attribute("reward_map", "reward_maps")
+    reward_features = _single_task_attribute("reward_features", "reward_maps_img")
+    _reward_obstacle_flat = _single_task_attribute("_reward_obstacle_flat", "reward_maps_img")
+
     def __init__(self, num_envs, shapes, obstacles, targets, max_steps=None, mu=0.8, density=1.0, bounds=None,
                  xlim=(-3.0, 7.0), ylim=(0.0, 10.0), x_discr_ground=None, offset_values=(0.0,), seed=0,
                  device="cuda:0", f32_rasters=True, a_max=None, img_size=(64, 64), debug=0, env_id_base=0,
@@ -117,7 +170,18 @@ class VecAssemblyGym:
         self.shape_target_faces = [list(getattr(s, "target_faces_2d", range(g.num_faces_2d)))
                                    for s, g in zip(shapes, self.shapes)]
         self.obstacles = [tuple(float(v) for v in o) for o in obstacles]
-        self.targets = [tuple(float(v) for v in t) for t in targets]
+        self.per_env_tasks = False                   # set by _attach_task_buffers
+        self.task_buf = None
+        self.random_targets = None
+        if isinstance(targets, RandomTargets):
+            self.targets, self.n_targets = None, targets.num_targets
+        elif _is_per_env_targets(targets):
+            if tuple(targets.shape[::2]) != (int(num_envs), 3) or not 1 <= targets.shape[1] <= abi.MAX_TARGETS:
+                raise ValueError(f"per-env targets must be [num_envs, 1..{abi.MAX_TARGETS}, 3], got {tuple(targets.shape)}")
+            self.targets, self.n_targets = None, int(targets.shape[1])
+        else:
+            self.targets = [tuple(float(v) for v in t) for t in targets]
+            self.n_targets = len(self.targets)
         self.max_steps = int(max_steps) if max_steps else 0
         self.K = self.max_steps if self.max_steps else abi.MAX_BLOCKS
         if self.K > abi.MAX_BLOCKS:
@@ -154,7 +218,13 @@ class VecAssemblyGym:
         self._alloc()
         self._task_features()
         self._create()
-        self.reset()
+        if isinstance(targets, RandomTargets):
+            self._attach_task_buffers(targets)
+            self.reset()
+        elif self.targets is None:
+            self.set_targets(targets)
+        else:
+            self.reset()
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self):
@@ -209,7 +279,8 @@ class VecAssemblyGym:
             return out
 
         self.buf["obstacle_bits"].copy_(raster_points(self.obstacles))
-        tbits = raster_points(self.targets)
+        tbits = raster_points(self.targets or [])      # per-env tasks: the single-task tables stay empty and unread
+        self.target_bits = tbits                       # [64] raster of the target blocks (per-env tasks: [E,64])
         timg = torch.empty((1, 64, 64), dtype=torch.float32, device=dev)
         abi.check(self.L.bridges_bits_to_f32(1, _ptr(tbits), _ptr(timg), _stream()), "bridges_bits_to_f32")
         S = self.img                                                       # the map of the S x S image, rest of the canvas 0
@@ -238,15 +309,15 @@ class VecAssemblyGym:
         t.n_shapes, t.n_groups = len(self.table_geoms), len(self.groups)
         for i, (si, f) in enumerate(self.groups):
             t.group_shape[i], t.group_face[i] = si, f
-        t.n_ground, t.n_offsets, t.n_targets = len(self.x_discr_ground), len(self.offset_values), len(self.targets)
+        t.n_ground, t.n_offsets, t.n_targets = len(self.x_discr_ground), len(self.offset_values), self.n_targets
         t.mu, t.density = self.mu, self.density
         t.floor_half_width = (self.bounds[1][0] - self.bounds[0][0]) / 2.0      # assembly_env.py:290-296
         t.floor_depth = self.bounds[1][1] - self.bounds[0][1]
         self._create_args = (float(t.floor_half_width), float(t.floor_depth))
         t.xlim[0], t.xlim[1], t.ylim[0], t.ylim[1] = *self.xlim, *self.ylim
-        if len(self.targets) > abi.MAX_TARGETS:
+        if self.n_targets > abi.MAX_TARGETS:
             raise ValueError("too many targets")
-        for i, tg in enumerate(self.targets):
+        for i, tg in enumerate(self.targets or []):
             for k in range(3):
                 t.targets[i][k] = tg[k]
         t.seed = self.seed
@@ -281,6 +352,56 @@ class VecAssemblyGym:
                 self.L.bridges_env_destroy(self._env)
         except Exception:
             pass
+
+    # ------------------------------------------------------------------ per-env tasks
+    def _attach_task_buffers(self, sampler=None):
+        """Allocate (once) and attach the per-env task buffers (bridges_env_set_task_buffers); ``sampler``: a RandomTargets
+        to redraw the targets on the device every episode, None to keep env_targets as they are written."""
+        if self.n_targets < 1:
+            raise ValueError("per-env tasks need at least one target per env")
+        if sampler is not None and sampler.num_targets != self.n_targets:
+            raise ValueError(f"the env was built for {self.n_targets} targets per env, the sampler draws {sampler.num_targets}")
+        if self.task_buf is None:
+            dims = dict(E=self.E, T=self.n_targets)
+            self.task_buf = {name: torch.zeros(tuple(dims[d] if d in dims else int(d) for d in shape.split(",")),
+                                               dtype=getattr(torch, dt), device=self.device)
+                             for name, dt, shape in abi.TASK_BUFFER_FIELDS}
+            self._gauss_k = gaussian_vector().to(self.device)
+            assert self._gauss_k.numel() == abi.GAUSS_TAPS and self._gauss_k.dtype == torch.float32
+        tb = abi.TaskBuffers()
+        for name, _, _ in abi.TASK_BUFFER_FIELDS:
+            setattr(tb, name, self.task_buf[name].data_ptr())
+        tb.env_obstacle_bits = None
+        tb.gauss_k = self._gauss_k.data_ptr()
+        tb.target_shape = len(self.table_geoms) - 1          # cube06 (gym_env.py:277)
+        tb.sample = 1 if sampler is not None else 0
+        if sampler is not None:
+            tb.x_range[0], tb.x_range[1] = sampler.x_range
+            tb.z_range[0], tb.z_range[1] = sampler.z_range
+        abi.check(self.L.bridges_env_set_task_buffers(self._env, C.byref(tb)), "bridges_env_set_task_buffers")
+        self.random_targets = sampler
+        self.per_env_tasks = True
+        self.targets = None
+        b = self.task_buf
+        self.env_targets, self.target_bits, self.task_episode = b["env_targets"], b["target_bits"], b["task_episode"]
+        self.reward_maps, self.reward_prefix = b["reward_map"], b["reward_prefix"]
+        self.reward_maps_img = self.crop(self.reward_maps)
+
+    def set_targets(self, targets, reset=True):
+        """Explicit per-env targets ([E, T, 3] float64, T = the env's number of targets) that stay until set again; a sampler
+        is switched off.  reset=True starts every env on its new task (reset()); reset=False keeps the block lists and
+        target bookkeeping of the current states (a replay env re-creating the task of a loaded state) and only rebuilds
+        the task features and the candidates' linear rewards.  No host wait."""
+        t = torch.as_tensor(targets, dtype=torch.float64).to(self.device)
+        if tuple(t.shape) != (self.E, self.n_targets, 3):
+            raise ValueError(f"targets must be [{self.E}, {self.n_targets}, 3], got {tuple(t.shape)}")
+        self._attach_task_buffers(None)
+        self.env_targets.copy_(t)
+        if reset:
+            self.reset()                                 # rebuilds the task features of every env
+        else:
+            abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
+            self.refresh()
 
     # ------------------------------------------------------------------ lock-step API
     def reset(self):
@@ -535,12 +656,23 @@ class VecAssemblyGymGroups:
         sizes = [base + (1 if g < num_envs % self.G else 0) for g in range(self.G)]
         self.E = int(num_envs)
         self.envs, self.streams, start = [], [], int(env_id_base)
+        # `targets` (VecAssemblyGym's argument after num_envs, shapes, obstacles): a list or RandomTargets() goes to every group as
+        # it is (the draw is keyed by the global env id); a per-env array [E, T, 3] is cut into the groups' slices
+        args, lo = list(args), 0
+        positional = "targets" not in kw
+        targets = args[2] if positional else kw.pop("targets")
         for n in sizes:
             st = torch.cuda.Stream(device=self.device)
+            tg = targets[lo:lo + n] if _is_per_env_targets(targets) else targets
+            if positional:
+                args[2] = tg
+            else:
+                kw["targets"] = tg
             with torch.cuda.stream(st):
                 self.envs.append(VecAssemblyGym(n, *args, device=device, env_id_base=start, **kw))
             self.streams.append(st)
             start += n
+            lo += n
         self._stream_ptrs = [C.c_void_p(st.cuda_stream) for st in self.streams]
         # one raster gate per GPU: the bandwidth-bound rasterisers of the groups run one after another, the
         # latency-bound task kernels of the other groups run beside them
@@ -572,6 +704,16 @@ class VecAssemblyGymGroups:
         for env, st in zip(self.envs, self.streams):
             with torch.cuda.stream(st):
                 env.reset()
+
+    def set_targets(self, targets, reset=True):
+        """VecAssemblyGym.set_targets for all E envs ([E, T, 3]): every group takes its slice, on its own stream."""
+        if int(targets.shape[0]) != self.E:
+            raise ValueError(f"targets must hold {self.E} envs, got {tuple(targets.shape)}")
+        lo = 0
+        for env, st in zip(self.envs, self.streams):
+            with torch.cuda.stream(st):
+                env.set_targets(targets[lo:lo + env.E], reset=reset)
+            lo += env.E
 
     def lockstep_random(self):
         """select_random + step for every group, each on its own stream (one C call per group)."""

@@ -91,6 +91,11 @@ struct bridges_env {
     hipEvent_t* ev_start;
     hipEvent_t* ev_stop;
     int ev_cap, ev_used;
+    // per-env tasks (bridges_env_set_task_buffers): while attached, ctx.b.reward_map / reward_prefix point at the per-env tables
+    bool has_tasks;
+    bridges_task_buffers tasks;
+    const float* fixed_reward_map;         // the fixed task's tables, restored when the buffers are detached
+    const double* fixed_reward_prefix;
 };
 
 // The previous lock-step's candidate count (+3 %, at least one per env), which sizes the grids over candidates.  Those
@@ -180,6 +185,10 @@ int bridges_env_create(const bridges_task* t, const bridges_env_buffers* buf, br
     env->ev_cap = env->ev_used = 0;
     env->gate = nullptr;
     env->raster_done = nullptr;
+    env->has_tasks = false;
+    memset(&env->tasks, 0, sizeof(env->tasks));
+    env->fixed_reward_map = buf->reward_map;
+    env->fixed_reward_prefix = buf->reward_prefix;
     // mapped, coherent host word: k_scan stores the candidate count of the lock-step straight into it (no copy command
     // in the stream); the host reads it as a hint for the next grid, so a late value costs time, never correctness
     e = hipHostMalloc((void**)&env->h_total, sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent);
@@ -286,8 +295,13 @@ static int refresh(bridges_env* env, hipStream_t s, int after_step) {
     if (timed) HIP_TRY(hipEventRecord(env->ev_start[env->ev_used], s));
     // No dynamic LDS, so no cap on the rasteriser's occupancy: 8 workgroups (4 waves each) per CU fill every wave slot.
     // Capping it to leave room for the other env groups' task kernels cost the headline 5-6 % (profiles/r04_kstep_tail.txt).
-    if (int rc = launch("k_raster", env->max_faces <= 4 ? k_raster<4> : k_raster<MAXV>, dim3((unsigned)rblocks), dim3(256), 0, s, c))
+    if (!env->has_tasks) {
+        if (int rc = launch("k_raster", env->max_faces <= 4 ? k_raster<4> : k_raster<MAXV>, dim3((unsigned)rblocks), dim3(256), 0, s, c))
+            return rc;
+    } else if (int rc = launch("k_raster (per-env tables)", env->max_faces <= 4 ? k_raster<4, true> : k_raster<MAXV, true>,
+                               dim3((unsigned)rblocks), dim3(256), 0, s, c)) {
         return rc;
+    }
     if (timed) { HIP_TRY(hipEventRecord(env->ev_stop[env->ev_used], s)); env->ev_used++; }
     if (env->gate) {
         HIP_TRY(hipEventRecord(env->raster_done, s));
@@ -296,16 +310,61 @@ static int refresh(bridges_env* env, hipStream_t s, int after_step) {
     return launch("k_select", k_select, dim3(c.E), dim3(WAVE), 0, s, c, 0);
 }
 
+static int task_features(bridges_env* env, void* stream, int mode) {
+    return launch("k_task_features", k_task_features, dim3(env->ctx.E), dim3(TASK_THREADS), 0, stream, env->ctx, env->tasks, mode);
+}
+
 int bridges_env_reset(bridges_env* env, void* stream) {
     if (!env) return fail_arg("null env");
     if (int rc = launch("k_reset", k_reset, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx)) return rc;
+    if (env->has_tasks)
+        if (int rc = task_features(env, stream, TASK_RESET)) return rc;
     return refresh(env, (hipStream_t)stream, 0);
 }
 
 int bridges_env_step(bridges_env* env, void* stream) {
     if (!env) return fail_arg("null env");
-    if (int rc = launch("k_step", k_step, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx)) return rc;
+    if (!env->has_tasks) {
+        if (int rc = launch("k_step", k_step<>, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx)) return rc;
+    } else {
+        if (int rc = launch("k_step (per-env targets)", k_step<const double*>, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx,
+                            (const double*)env->tasks.env_targets))
+            return rc;
+        // the envs k_step has just reset begin an episode: next task (fixed per-env targets: nothing to do)
+        if (env->tasks.sample)
+            if (int rc = task_features(env, stream, TASK_STEP)) return rc;
+    }
     return refresh(env, (hipStream_t)stream, 1);
+}
+
+int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* tb) {
+    if (!env) return fail_arg("null env");
+    DevCtx& c = env->ctx;
+    if (!tb) {
+        env->has_tasks = false;
+        memset(&env->tasks, 0, sizeof(env->tasks));
+        c.b.reward_map = env->fixed_reward_map;
+        c.b.reward_prefix = env->fixed_reward_prefix;
+        return BRIDGES_OK;
+    }
+    if (!tb->env_targets || !tb->target_bits || !tb->reward_map || !tb->reward_prefix || !tb->task_episode || !tb->gauss_k)
+        return fail_arg("task buffers: env_targets / target_bits / reward_map / reward_prefix / task_episode / gauss_k not given");
+    if (tb->env_obstacle_bits) return fail_arg("task buffers: env_obstacle_bits is reserved (obstacles are shared by all envs)");
+    if (c.n_targets < 1) return fail_arg("task buffers: the task has no targets");
+    if (tb->target_shape < 0 || tb->target_shape >= c.n_shapes) return fail_arg("task buffers: target_shape");
+    if (tb->sample != 0 && tb->sample != 1) return fail_arg("task buffers: sample must be 0 or 1");
+    if (tb->sample && !(tb->x_range[0] <= tb->x_range[1] && tb->z_range[0] <= tb->z_range[1])) return fail_arg("task buffers: x_range / z_range");
+    env->tasks = *tb;
+    env->has_tasks = true;
+    c.b.reward_map = tb->reward_map;
+    c.b.reward_prefix = tb->reward_prefix;
+    return BRIDGES_OK;
+}
+
+int bridges_env_load_targets(bridges_env* env, void* stream) {
+    if (!env) return fail_arg("null env");
+    if (!env->has_tasks) return fail_arg("bridges_env_load_targets: no task buffers attached");
+    return task_features(env, stream, TASK_LOAD);
 }
 
 int bridges_env_refresh(bridges_env* env, void* stream) {

@@ -85,7 +85,17 @@ struct StepKeep {           // what the LP reads of the assembly
 };
 static_assert(sizeof(StepStage) <= STEP_TAB_LDS * sizeof(double), "staging area must fit into the tableau storage");
 
-__global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
+// k_step<>(DevCtx): the fixed task, targets in the kernel arguments.  k_step<const double*>(DevCtx, env_targets): every env
+// tests its own targets (bridges_task_buffers.env_targets[e]: one value per lane, a level-0 load).  One body for both; the
+// optional trailing argument keeps the fixed-task kernel's argument list -- and with it its code, which sits at the register
+// limit -- what it is without the feature.
+__device__ __forceinline__ const double* step_targets() { return nullptr; }
+__device__ __forceinline__ const double* step_targets(const double* p) { return p; }
+template <typename... ENV_TARGETS>
+__global__ __launch_bounds__(WAVE) void k_step(DevCtx c, ENV_TARGETS... env_targets_arg) {
+    constexpr bool PER_ENV = sizeof...(ENV_TARGETS) == 1;
+    const double* env_targets = step_targets(env_targets_arg...);
+    (void)env_targets;
     __shared__ __attribute__((aligned(16))) double tab[STEP_TAB_LDS];
     __shared__ LpScratch S;
     __shared__ StepKeep Lk;
@@ -117,6 +127,10 @@ __global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
     W.magic = hdr_g->magic; W.n_blocks = hdr_g->n_blocks; W.n_if = hdr_g->n_if; W.stride = hdr_g->stride;
     W.half = hdr_g->half; W.m = hdr_g->m;
     W.basis_lane = hdr_g->basis[lane];
+    double tgv = 0.0;                               // PER_ENV: lane 3 t + k holds coordinate k of target t
+    if constexpr (PER_ENV) {
+        if (lane < c.n_targets * 3) tgv = env_targets[(size_t)e * c.n_targets * 3 + lane];
+    }
     {
         const double* src = reinterpret_cast<const double*>(c.tt->shapes);
         double* dst = reinterpret_cast<double*>(L.shapes);
@@ -202,8 +216,14 @@ __global__ __launch_bounds__(WAVE) void k_step(DevCtx c) {
         for (int t = 0; t < c.n_targets; ++t) {
             if (!((left >> t) & 1u)) continue;
             if (skip) { skip = false; continue; }
-            bool in = fabs(c.targets[t][0] - cx) < hx + 1e-6 && fabs(c.targets[t][1]) < hy + 1e-6 &&
-                      fabs(c.targets[t][2] - cz) < hz + 1e-6;
+            bool in;
+            if constexpr (PER_ENV) {
+                const double tx = readlane_d(tgv, 3 * t), ty = readlane_d(tgv, 3 * t + 1), tz = readlane_d(tgv, 3 * t + 2);
+                in = fabs(tx - cx) < hx + 1e-6 && fabs(ty) < hy + 1e-6 && fabs(tz - cz) < hz + 1e-6;
+            } else {
+                in = fabs(c.targets[t][0] - cx) < hx + 1e-6 && fabs(c.targets[t][1]) < hy + 1e-6 &&
+                     fabs(c.targets[t][2] - cz) < hz + 1e-6;
+            }
             if (in) { left &= ~(1u << t); skip = true; }
         }
     }
@@ -668,7 +688,9 @@ __device__ __forceinline__ uint64_t raster_outline(const double* v /*[6,2]*/, in
 // the grid-stride loop makes any count correct.  The row runs (raster_rows) cost ~250 wave instructions per image and
 // hide behind its 16 KiB of stores.
 // NF = 4 when every candidate shape of the task has at most 4 faces (64 VGPRs: 8 waves per SIMD), else MAXV.
-template <int NF>
+// PER_ENV: reward_prefix holds one [64][65] table per env (bridges_task_buffers); the owning env is wave-uniform, so the
+// table's base is scalar arithmetic.
+template <int NF, bool PER_ENV = false>
 __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
@@ -698,7 +720,7 @@ __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
                                                        : raster_rows6(fr0, fr1, fr2, fr3, c.img, X, Y, lane);
             const bool overlap = __ballot((bits & occ) != 0ull) != 0ull;
             double p_hi, p_lo;
-            raster_reward_fetch(bits, c.b.reward_prefix, lane, p_hi, p_lo);
+            raster_reward_fetch(bits, PER_ENV ? c.b.reward_prefix + (size_t)e * (IMG * (IMG + 1)) : c.b.reward_prefix, lane, p_hi, p_lo);
             c.b.cand_bits[ci * IMG + lane] = bits;
             if (c.b.cand_raster)
                 write_f32_image(c.b.cand_raster + ci * IMG * IMG, bits, lane, c.b.cand_raster_nz ? c.b.cand_raster_nz + ci : nullptr);
@@ -713,6 +735,151 @@ __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
                             c.b.state_raster_nz ? c.b.state_raster_nz + e : nullptr);
         }
     }
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// Per-env task features (bridges_task_buffers): tower_setup's draw (assembly_gym/assembly_gym/envs/gym_env.py:64-79) and
+// get_task_features (robotoddler/training/successor_dqn.py:67-85), one workgroup per env.
+//   TASK_LOAD   every env: env_targets were written by the caller; rebuild the features
+//   TASK_RESET  every env: task_episode = 0; with the sampler on, draw the targets of episode 0 first
+//   TASK_STEP   after k_step, sampler on: only the envs k_step has just reset -- finished and auto-reset (F_DONE) or a
+//               reset-only lock-step (!F_VALID) -- take the next episode: task_episode += 1, new targets; the rest leave at once
+// The draw (header comment of bridges_env_set_task_buffers): counter-based, keyed by (seed, global env id, episode, target,
+// axis) through splitmix64 with a salt that separates it from the policy's stream (k_select).
+// The features restate bridges_hip.vec_env.VecAssemblyGym._task_features + gaussian_reward_map operation for operation, so a
+// per-env table is bit-identical to the one a fixed-task env of the same targets gets from the host:
+//   raster   the T cube06 blocks at identity rotation (vertex = target + local vertex) through raster_outline, rows OR-ed;
+//   map      out[y][x] = (float) sum over the set pixels (py, px) of the raster, row-major, of (double)(k[py - y + 50] * k[px - x + 50])
+//            -- the float32 product first (the reference's kernel matrix k k^T is float32), a float64 running sum, taps
+//            outside the 101-wide kernel contribute nothing, one rounding to float32.  Lane x owns column x and walks rows y: every
+//            output pixel is its own sum, so the order is the host's for free;
+//   prefix   [r][x + 1] = [r][x] + (double)map[r][x], left to right (np.cumsum), lane r owns row r.
+// Work: <= 16 T set pixels x 4096 outputs of float64 adds per env that changes task, a chain of dependent adds per output.
+// One workgroup of four waves per env: every wave repeats the (cheap) draw and raster, then wave w takes map rows 16 w ..
+// 16 w + 15, four rows at a time per lane -- four independent sums in flight, one LDS read of k per set pixel for the four.
+// k sits in LDS between zeros (kz), so a tap outside the 101-wide kernel reads 0: the sum takes (double)(0 * k) = +0.0, which
+// changes nothing, exactly what the host adds there.  LDS 51 KB: map and prefix tables are staged so that their 49 KiB leave
+// as contiguous stores.
+enum { TASK_LOAD = 0, TASK_RESET = 1, TASK_STEP = 2 };
+#define TASK_SALT 0x7461736B5F726E67ull     // "task_rng"
+#define TASK_ROW (IMG + 1)
+#define TASK_WAVES 4
+#define TASK_THREADS (TASK_WAVES * WAVE)
+#define TASK_ROWS_IN_FLIGHT 4
+#define TASK_KZ_PAD 16                      // zeros in front of k: tap index py - y + 50 >= -13 on a 64-pixel canvas
+#define TASK_KZ (TASK_KZ_PAD + BRIDGES_GAUSS_TAPS + 16)      // and <= 113
+static_assert(IMG - 1 - BRIDGES_GAUSS_TAPS / 2 <= TASK_KZ_PAD && IMG - 1 + BRIDGES_GAUSS_TAPS / 2 < BRIDGES_GAUSS_TAPS + 16,
+              "every tap index of a 64 x 64 canvas must fall into the padded table");
+static_assert(IMG % (TASK_WAVES * TASK_ROWS_IN_FLIGHT) == 0, "map rows are dealt to the waves in batches");
+__global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridges_task_buffers t, int mode) {
+    __shared__ float kz[TASK_KZ];
+    __shared__ uint64_t tb_l[IMG];
+    __shared__ double tv_l[TASK_WAVES][MAXV * 2];
+    __shared__ float map_l[IMG * TASK_ROW];
+    __shared__ double pre_l[IMG * TASK_ROW];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    const int T = c.n_targets, S = c.img;
+    if (mode == TASK_STEP) {
+        const uint8_t* fl = c.b.step_flags + (size_t)e * 8;
+        if (fl[F_VALID] && !fl[F_DONE]) return;     // mid-episode: the env keeps its task (the whole workgroup leaves)
+    }
+    for (int i = tid; i < TASK_KZ; i += TASK_THREADS) {
+        const int tap = i - TASK_KZ_PAD;
+        kz[i] = (tap >= 0 && tap < BRIDGES_GAUSS_TAPS) ? t.gauss_k[tap] : 0.f;
+    }
+    double* tg = t.env_targets + (size_t)e * T * 3;
+    uint32_t ep = 0u;
+    if (mode == TASK_STEP) ep = t.task_episode[e] + 1u;
+    __syncthreads();                                // every wave has read the episode before it is replaced
+    if (mode != TASK_LOAD && tid == 0) t.task_episode[e] = ep;
+    // ---- targets: lane 3 q + k of every wave holds coordinate k of target q ----
+    double tv = 0.0;
+    if (lane < 3 * T) {
+        if (t.sample && mode != TASK_LOAD) {
+            const int axis = lane % 3;
+            if (axis != 1) {
+                const uint64_t h0 = splitmix64((((c.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(c.env_id_base + e)) ^ TASK_SALT);
+                const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
+                const uint64_t r = splitmix64(h1 ^ (uint64_t)lane);
+                const double u = (double)(r >> 11) * 0x1.0p-53;
+                const double lo = axis == 0 ? t.x_range[0] : t.z_range[0], hi = axis == 0 ? t.x_range[1] : t.z_range[1];
+                const double span = hi - lo;
+                const double step = span * u;
+                tv = lo + step;
+            }
+            if (wv == 0) tg[lane] = tv;
+        } else {
+            tv = tg[lane];
+        }
+    }
+    // ---- raster of the target blocks (every wave, on its own vertex scratch) ----
+    const bridges_shape& cube = c.tt->shapes[t.target_shape];
+    const int nv = cube.nv;
+    uint64_t bits = 0ull;
+    for (int q = 0; q < T; ++q) {
+        const double px = readlane_d(tv, 3 * q), pz = readlane_d(tv, 3 * q + 2);
+        __syncthreads();
+        if (lane < nv) { tv_l[wv][2 * lane] = px + cube.vx[lane]; tv_l[wv][2 * lane + 1] = pz + cube.vz[lane]; }
+        __syncthreads();
+        bits |= raster_outline(tv_l[wv], nv, cube.fa, cube.fb, c.tt->grid_x, c.tt->grid_y, S, lane);
+    }
+    if (wv == 0) {
+        tb_l[lane] = bits;
+        t.target_bits[(size_t)e * IMG + lane] = bits;
+    }
+    __syncthreads();
+    // ---- reward map: lane = column x, wave wv = rows 16 wv .. 16 wv + 15 ----
+    const uint64_t nzrows = __ballot(bits != 0ull);
+    const int half = BRIDGES_GAUSS_TAPS / 2;
+    float* map_g = t.reward_map + (size_t)e * IMG * IMG;
+    for (int b = 0; b < IMG / (TASK_WAVES * TASK_ROWS_IN_FLIGHT); ++b) {
+        const int y0 = (wv * (IMG / TASK_WAVES)) + b * TASK_ROWS_IN_FLIGHT;
+        double acc[TASK_ROWS_IN_FLIGHT];
+#pragma unroll
+        for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) acc[r] = 0.0;
+        uint64_t rows = y0 < S ? nzrows : 0ull;
+        while (rows) {                              // set pixels in row-major order
+            const int py = __builtin_ctzll(rows);
+            rows &= rows - 1ull;
+            float ki[TASK_ROWS_IN_FLIGHT];
+#pragma unroll
+            for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) ki[r] = kz[py - (y0 + r) + half + TASK_KZ_PAD];
+            const uint64_t row = tb_l[py];
+            uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(row >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row);
+            while (m) {
+                const int pxl = __builtin_ctzll(m);
+                m &= m - 1ull;
+                const float kx = kz[pxl - lane + half + TASK_KZ_PAD];
+#pragma unroll
+                for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) {
+                    const float prod = ki[r] * kx;
+                    acc[r] = acc[r] + (double)prod;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) {
+            const int y = y0 + r;
+            const float v = (lane < S && y < S) ? (float)acc[r] : 0.f;
+            map_l[y * TASK_ROW + lane] = v;
+            map_g[y * IMG + lane] = v;
+        }
+    }
+    __syncthreads();
+    // ---- row prefix sums: lane r of wave 0 = row r ----
+    if (wv == 0) {
+        double run = 0.0;
+        pre_l[lane * TASK_ROW] = 0.0;
+        for (int x = 0; x < IMG; ++x) {
+            run = run + (double)map_l[lane * TASK_ROW + x];
+            pre_l[lane * TASK_ROW + x + 1] = run;
+        }
+    }
+    __syncthreads();
+    double* pre_g = t.reward_prefix + (size_t)e * IMG * TASK_ROW;
+    for (int i = tid; i < IMG * TASK_ROW; i += TASK_THREADS) pre_g[i] = pre_l[i];
 }
 
 // ---------------------------------------------------------------------------------------------

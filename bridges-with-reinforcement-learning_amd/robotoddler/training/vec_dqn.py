@@ -45,6 +45,11 @@ class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False):
+        if getattr(env, "per_env_tasks", False):
+            raise ValueError("VecDQN cannot train on a rollout env with per-env tasks (RandomTargets / set_targets): envs in the "
+                             "same state share candidate rows whatever their task (bridges_env_groups keys rows by state "
+                             "alone), the factored SuccessorMLP acting path and the captured train steps hold ONE reward map, "
+                             "and a replay record does not store its task")
         self.policy_net, self.target_net, self.opt, self.env = policy_net, target_net, optimizer, env
         # stable actions only: the rollout env and the replay scratch env narrow every candidate set to the stable placements,
         # so acting, exploring, the TD target's max over next actions and the done flags all see the same smaller set

@@ -55,7 +55,8 @@ typedef struct {
     double gx, gz;                           /* local centroid */
 } bridges_shape;
 
-/* Static description of one vectorised task (all environments share it).
+/* Static description of one vectorised task (all environments share it -- except the targets of an env that has
+ * bridges_task_buffers attached, see bridges_env_set_task_buffers: `targets` is then not read, n_targets still is).
  * Replaces the arguments of AssemblyGym.__init__/reset, AssemblyEnv.__init__
  * (gym_env.py:116-139, 255-289; assembly_env.py:164-199) and the constants of
  * successor_dqn.py:611-616. */
@@ -216,6 +217,42 @@ int bridges_env_restrict_to_stable(bridges_env* env, void* stream);
  * states the host wrote (bridges_replay_unpack / load_states).  Invalidates the env's persisted tableaux (lp_ws, lp_snap):
  * bridges_env_candidate_stability then solves the candidates of these states from scratch.  No host wait. */
 int bridges_env_rebuild_contacts(bridges_env* env, void* stream);
+
+/* --- per-env tasks ------------------------------------------------------------
+ * tower_setup draws three fresh targets each time an episode starts (assembly_gym/assembly_gym/envs/gym_env.py:64-79,
+ * env.reset(**setup_fct()), robotoddler/training/successor_dqn.py:371).  With these buffers attached every env owns its
+ * targets and everything derived from them; without them nothing changes (same launches, same buffers, same bits).
+ * Caller-owned DEVICE buffers, E = n_envs, T = n_targets of the task (a task constant): */
+#define BRIDGES_GAUSS_TAPS 101  /* kernel_size of convolve_with_gaussian (successor_dqn.py:80-82) */
+typedef struct {
+    double* env_targets;       /* [E,T,3] (x, y, z) of every env's targets; y is compared as the fixed task's is */
+    uint64_t* target_bits;     /* [E,64] raster of the env's T cube06 target blocks (get_task_features, successor_dqn.py:73-79) */
+    float* reward_map;         /* [E,64,64] its Gaussian blur: convolve_with_gaussian(raster, 101, 16) of the S x S image */
+    double* reward_prefix;     /* [E,64,65] float64 row prefix sums of reward_map (bridges_env_buffers.reward_prefix, per env) */
+    uint32_t* task_episode;    /* [E] episodes the env has started since bridges_env_reset (the first one is 0) */
+    const uint64_t* env_obstacle_bits;  /* reserved for per-env obstacles: must be NULL, no kernel reads it */
+    const float* gauss_k;      /* [BRIDGES_GAUSS_TAPS] the normalised float32 Gaussian vector k of the reference's kernel k k^T */
+    int32_t target_shape;      /* shape id (in the task's shape table) of a target block: cube06 */
+    int32_t sample;            /* 1: an env draws new targets on the device whenever it starts an episode; 0: env_targets stay */
+    double x_range[2];         /* sampler: x ~ U[x_range), z ~ U[z_range), y = 0 (tower_setup: [-4, 4], [0, 4]) */
+    double z_range[2];
+} bridges_task_buffers;
+/* Attach (or replace) the per-env task buffers; NULL detaches them (the env is a fixed-task env again; call bridges_env_reset).
+ * From here on the reached-test of bridges_env_step reads env_targets[e], the rasteriser takes cand_lin from reward_prefix[e],
+ * and bridges_env_buffers.reward_map / reward_prefix and bridges_task.targets are not read.  Enqueues nothing.
+ * bridges_env_reset then sets task_episode = 0 and rebuilds every env's task features (after drawing the targets of episode
+ * 0 when sample = 1); bridges_env_step does so, when sample = 1, for the envs that begin an episode in that lock-step: task_episode
+ * += 1, new targets.  The step that ends an episode is rewarded against the old targets; the candidates of the fresh state carry
+ * the new task's cand_lin.  With sample = 0 a lock-step launches nothing extra.
+ * The draw is counter-based (splitmix64 as in the synthetic policy, a stream of its own): with gid = env_id_base + e,
+ *   h0 = splitmix64(((seed & 0xFFFFFFFF) << 32 | (uint32)gid) ^ 0x7461736B5F726E67)      ("task_rng")
+ *   h1 = splitmix64(h0 ^ task_episode)
+ *   r  = splitmix64(h1 ^ (3 * t + axis)),   u = (r >> 11) * 2^-53,   value = lo + ((hi - lo) * u)
+ * for target t, axis 0 (x) and 2 (z), every operation rounded to binary64 separately; axis 1 (y) = 0. */
+int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* tb);
+/* The host (or another kernel) has written env_targets: rebuild target_bits, reward_map and reward_prefix of every env.
+ * task_episode and the env states stay; the candidates' cand_lin is stale until bridges_env_reset / _refresh.  No host wait. */
+int bridges_env_load_targets(bridges_env* env, void* stream);
 
 /* --- stand-alone operators (same kernels, caller-shaped batches) ------------ */
 /* K1: create_block / align_frames_2d (gym_env.py:204-216, geometry.py:39-50).

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel stats of the bench modes (run on the MI355X box through gpurun, from the repo root):
-#   tools/profile_modes.sh <tag> [sim] [cand] [hex] [mlp] [mlp_stable] [conv] [conv_all] [unet] [unet_all]     (*_all: every candidate row fed, --no_dedup)
+#   tools/profile_modes.sh <tag> [sim] [cand] [hex] [mlp] [mlp_stable] [conv] [conv_all] [unet] [unet_all] [tasks_fixed] [tasks_random]     (*_all: every candidate row fed, --no_dedup)
 # Writes gpurun_out/prof_<tag>_<mode>/ (trace + stats) and gpurun_out/prof_<tag>_<mode>.json (the bench line).
 set -o pipefail
 tag=$1; shift
@@ -18,6 +18,8 @@ for mode in "$@"; do
     conv_all) args="$root/tools/train_throughput.py --locksteps 4 --warmup 12 --envs 1024 --tower 2 --max_steps 10 --model ConvNet --loss mse_q_values --no_dedup" ;;
     unet) args="$root/tools/train_throughput.py --locksteps 3 --warmup 12 --envs 4096 --max_steps 15 --model UNet --loss mse_q_values+mse_block_features --shapes hexagon --bridge_length 3" ;;
     unet_all) args="$root/tools/train_throughput.py --locksteps 2 --warmup 3 --envs 4096 --max_steps 15 --model UNet --loss mse_q_values+mse_block_features --shapes hexagon --bridge_length 3 --no_dedup" ;;
+    tasks_fixed)  args="$root/tools/random_task_throughput.py --tasks fixed3" ;;       # k_step / k_raster on three shared targets
+    tasks_random) args="$root/tools/random_task_throughput.py --tasks random3" ;;      # + k_task_features, per-env k_step / k_raster
     *) echo "unknown mode $mode"; exit 2 ;;
   esac
   (cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $args) > $out.log 2>&1 || { tail -20 $out.log; exit 1; }

@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""What per-env tasks cost the lock-step simulator: the headline workload's shape (4096 envs as two groups with the raster gate,
+trapezoid, max_steps 15, uniform-random policy, f32 rasters) on three tasks --
+  bridge   the benchmark's bridge_setup(4): one target, four obstacles, shared by all envs (k_step / k_raster);
+  fixed3   three fixed targets, no obstacle, shared by all envs (the same kernels);
+  random3  RandomTargets(): three targets per env, redrawn on the device every episode (the per-env instantiations + k_task_features).
+fixed3 against random3 isolates the feature (same shapes, same max_steps).  Candidates per state differ between tasks, so read
+the time per lock-step together with the candidates per lock-step, not env-steps/s alone.  Prints one JSON line.
+
+  python tools/random_task_throughput.py [--envs 4096] [--groups 2] [--steps 100] [--warmup 20] [--tasks bridge,fixed3,random3]
+"""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
+import torch
+from bridges_hip.shapes import load_urdf
+from bridges_hip.vec_env import RandomTargets, VecAssemblyGymGroups
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=4096)
+ap.add_argument("--groups", type=int, default=2)
+ap.add_argument("--steps", type=int, default=100, help="timed lock-steps (at least 100, as the side modes of bench.py)")
+ap.add_argument("--warmup", type=int, default=20)
+ap.add_argument("--max_steps", type=int, default=15)
+ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--tasks", default="bridge,fixed3,random3")
+a = ap.parse_args()
+if a.steps < 100:
+    sys.exit("--steps must be at least 100")
+
+H = 0.8                                                       # bridge_setup(H=.8, num_stories=4), gym_env.py:36-46
+TASKS = dict(bridge=([(0.5, 0.0, i * H + H / 2) for i in range(4)], [(0.5, 0.0, 4 * H + H / 2)]),
+             fixed3=([], [(0.5, 0.0, 1.2), (-1.5, 0.0, 2.6), (2.5, 0.0, 0.4)]),
+             random3=([], RandomTargets()))
+geoms = [load_urdf("shapes/trapezoid.urdf")]
+out = dict(tool="random_task_throughput", envs=a.envs, groups=a.groups, steps=a.steps, warmup=a.warmup, max_steps=a.max_steps,
+           device=torch.cuda.get_device_name(0), tasks={})
+for name in a.tasks.split(","):
+    obstacles, targets = TASKS[name]
+    env = VecAssemblyGymGroups(a.envs, geoms, obstacles, targets, groups=a.groups, max_steps=a.max_steps, seed=a.seed,
+                               f32_rasters=True, candidate_snapshots=False)
+    for _ in range(a.warmup):
+        env.lockstep_random()
+    env.sync()
+    torch.cuda.synchronize()
+    s0 = env.read_stats()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        env.lockstep_random()
+    env.sync()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    s1 = env.read_stats()
+    d = {k: s1[k] - s0[k] for k in s1}
+    assert d["lp_errors"] == 0 and d["if_overflow"] == 0 and d["cand_overflow"] == 0, d
+    states = a.steps * a.envs                                  # candidate sets produced: one per env and lock-step
+    r = dict(env_steps_per_s=d["env_steps"] / dt, us_per_lockstep=1e6 * dt / a.steps, env_steps=d["env_steps"],
+             reset_only=d["reset_only"], candidates_per_state=d["sum_cand"] / states,
+             candidates_per_lockstep=d["sum_cand"] / a.steps, valid_per_state=d["sum_valid"] / states,
+             blocks_per_state=d["sum_blocks"] / states)
+    if name == "random3":
+        ep = torch.cat([e.task_episode for e in env.envs]).double()
+        r["episodes_per_env"] = float(ep.mean())               # since the reset: warm-up included
+        r["tasks_drawn_per_lockstep"] = float(ep.sum()) / (a.steps + a.warmup)
+    out["tasks"][name] = r
+    del env
+    torch.cuda.empty_cache()
+print(json.dumps(out), flush=True)

@@ -214,8 +214,10 @@ SIGNATURES = {
     "bridges_bits_to_f32": [i32, vp, vp, vp],
     "bridges_bits_linear": [i32, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_sigmoid_dot": [i32, vp, i64, vp, i32, vp, vp],
+    "bridges_sigmoid_dot_rows": [i32, vp, i64, vp, vp, i32, vp, vp],
     "bridges_bits_dot": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_head_sigmoid_dot": [i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp],
+    "bridges_head_sigmoid_dot_rows": [i32, i32, i32, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp],
     "bridges_linear_backward_log": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, vp, vp, vp],
     "bridges_mlp_mid_rows": [i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
     "bridges_mlp_mid_supported": [i32, i32, vp],
@@ -224,6 +226,7 @@ SIGNATURES = {
     "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_env_groups_keyed": [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp],
     "bridges_record_state": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_record_result": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_episode_stats": [i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp],
@@ -241,7 +244,10 @@ SIGNATURES = {
     "bridges_linear_backward": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp],
     "bridges_mlp_input": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_mlp_input_batches": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_mlp_input_rows": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp],
+    "bridges_mlp_input_batches_rows": [i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp],
     "bridges_successor_loss": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_successor_loss_rows": [i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_adam_step": [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
     "bridges_linear_backward_adam": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp, i32, vp],
     "bridges_conv3x3": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],

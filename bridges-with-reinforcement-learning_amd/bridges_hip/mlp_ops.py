@@ -80,6 +80,7 @@ class FusedSuccessorStep:
         self.L = abi.require_gpu()
         self.linears = [m for m in net.mlp.layers if isinstance(m, torch.nn.Linear)]
         self.px = int(net.img_size[0]) * int(net.img_size[1])
+        self.img_shape = (int(net.img_size[0]), int(net.img_size[1]))
         dims = [self.linears[0].in_features] + [lin.out_features for lin in self.linears]
         self.nf = dims[0] - 4 * self.px
         if self.nf < 0 or dims[-1] != 2 * self.px + 2 * self.nf:
@@ -146,15 +147,30 @@ class FusedSuccessorStep:
         self.x_all = torch.zeros((int(n_batches) * self.rows, K), dtype=torch.float32, device=self.linears[0].weight.device)
         self._n_alloc, self._prepared = int(n_batches), False
 
+    def _reward_stride(self, reward, n_rows):
+        """0 for ONE reward map ([px] / [H, W]: the fixed task); px for a map per transition of the per-call arrays (a 2-D
+        [n, px] tensor -- replay of per-env tasks), which must cover the ``n_rows`` transitions the launch can address."""
+        if reward.dim() == 2 and reward.shape[1] == self.px and tuple(reward.shape) != tuple(self.img_shape):
+            assert reward.shape[0] >= n_rows, f"{reward.shape[0]} reward maps for {n_rows} transitions"
+            return self.px
+        assert reward.numel() == self.px
+        return 0
+
     def prepare_inputs(self, n_batches, block_all, action_all, binary_all, reward, obstacle):
-        """Build the input rows of batches 0 .. n_batches - 1 of the per-call arrays in ONE launch (bridges_mlp_input_batches);
-        ``launch`` then reads batch ``counter`` of them."""
+        """Build the input rows of batches 0 .. n_batches - 1 of the per-call arrays in ONE launch (bridges_mlp_input_batches,
+        or _batches_rows when ``reward`` holds a map per transition, [n, px]); ``launch`` then reads batch ``counter`` of them."""
         assert self.x_all is not None and n_batches <= self._n_alloc
         for t in (block_all, action_all, binary_all, reward, obstacle):
             assert t.dtype == torch.float32 and t.is_contiguous()
-        abi.check(self.L.bridges_mlp_input_batches(int(n_batches), self.batch, self.rows, self.px, self.nf, _ptr(block_all),
-                                                   _ptr(action_all), _ptr(binary_all), _ptr(reward), _ptr(obstacle), _ptr(self.x_all),
-                                                   _stream()), "bridges_mlp_input_batches")
+        stride = self._reward_stride(reward, int(n_batches) * self.batch)
+        if stride:
+            abi.check(self.L.bridges_mlp_input_batches_rows(int(n_batches), self.batch, self.rows, self.px, self.nf, _ptr(block_all),
+                                                            _ptr(action_all), _ptr(binary_all), _ptr(reward), stride, _ptr(obstacle),
+                                                            _ptr(self.x_all), _stream()), "bridges_mlp_input_batches_rows")
+        else:
+            abi.check(self.L.bridges_mlp_input_batches(int(n_batches), self.batch, self.rows, self.px, self.nf, _ptr(block_all),
+                                                       _ptr(action_all), _ptr(binary_all), _ptr(reward), _ptr(obstacle), _ptr(self.x_all),
+                                                       _stream()), "bridges_mlp_input_batches")
         self._prepared = True
 
     @staticmethod
@@ -246,10 +262,15 @@ class FusedSuccessorStep:
         for t in (block_all, action_all, binary_all, reward, obstacle):
             assert t.dtype == torch.float32 and t.is_contiguous()
         assert counter.dtype == torch.int64 and losses.dtype == torch.float32
+        # one reward map, or a map per transition ([n, px], n = the rows of block_all): the launches differ in one argument
+        stride = self._reward_stride(reward, block_all.reshape(-1, px).shape[0])
         # the first layer's input: batch `counter` of the pre-built rows of all batches (prepare_inputs), else built here
         pre = self.x_all is not None and self._prepared
         x0, blk = (self.x_all, _ptr(counter)) if pre else (self.acts[0], None)
-        if not pre:
+        if not pre and stride:
+            abi.check(L.bridges_mlp_input_rows(B, rows, px, nf, _ptr(counter), _ptr(block_all), _ptr(action_all), _ptr(binary_all),
+                                               _ptr(reward), stride, _ptr(obstacle), _ptr(self.acts[0]), st), "bridges_mlp_input_rows")
+        elif not pre:
             abi.check(L.bridges_mlp_input(B, rows, px, nf, _ptr(counter), _ptr(block_all), _ptr(action_all), _ptr(binary_all),
                                           _ptr(reward), _ptr(obstacle), _ptr(self.acts[0]), st), "bridges_mlp_input")
         last = len(self.linears) - 1
@@ -267,14 +288,17 @@ class FusedSuccessorStep:
         # layer's backward launch (bridges_linear_backward_log, one thread beside its jobs) -- the loss kernel itself hands
         # nothing between workgroups.  (A net whose head is also its first layer keeps the loss kernel's ticket form.)
         log_in_backward = last >= 1
-        abi.check(L.bridges_successor_loss(B, rows, px, nf, _ptr(self.acts[-1]), _ptr(reward), _ptr(counter),
-                                           _ptr(q_target_all) if self.use_q else None,
-                                           _ptr(sf_target_all) if self.use_sf else None, int(self.use_q), int(self.use_sf),
-                                           _ptr(self.dz[-1]), _ptr(self.loss_rows), _ptr(self.q),
-                                           None if log_in_backward else _ptr(losses), losses.numel(),
-                                           None if log_in_backward else _ptr(counter), None if log_in_backward else _ptr(self.ticket),
-                                           _ptr(self.adam_step) if (self.fused_adam and not log_in_backward) else None, st),
-                  "bridges_successor_loss")
+        loss_tail = (_ptr(q_target_all) if self.use_q else None, _ptr(sf_target_all) if self.use_sf else None, int(self.use_q),
+                     int(self.use_sf), _ptr(self.dz[-1]), _ptr(self.loss_rows), _ptr(self.q),
+                     None if log_in_backward else _ptr(losses), losses.numel(),
+                     None if log_in_backward else _ptr(counter), None if log_in_backward else _ptr(self.ticket),
+                     _ptr(self.adam_step) if (self.fused_adam and not log_in_backward) else None, st)
+        if stride:
+            abi.check(L.bridges_successor_loss_rows(B, rows, px, nf, _ptr(self.acts[-1]), _ptr(reward), stride, _ptr(counter), *loss_tail),
+                      "bridges_successor_loss_rows")
+        else:
+            abi.check(L.bridges_successor_loss(B, rows, px, nf, _ptr(self.acts[-1]), _ptr(reward), _ptr(counter), *loss_tail),
+                      "bridges_successor_loss")
         # the whole optimiser update rides in the LAST backward launch (the first layer's, which has no input gradient):
         # Adam goes into its weight-gradient tiles and extra workgroups of that launch update the other layers, whose
         # gradients are complete and whose weights nothing reads any more.  (Adam launches on a parallel branch of the

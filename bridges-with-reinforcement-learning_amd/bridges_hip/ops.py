@@ -323,19 +323,34 @@ def _head_splits(n_rows, n_tiles, slots=512):
     return best
 
 
-def head_sigmoid_dot(h, Wd, bd, w, splits=None):
+def _row_maps(w, w_row, N, n):
+    """The per-row form of a head's weights: w [M, N] float32 (one map per task), w_row int32 [n] (the map of every row)."""
+    w = w.to(torch.float32).reshape(-1, N).contiguous()
+    assert w_row.dtype == torch.int32 and w_row.numel() == n and w_row.is_contiguous() and w_row.device == w.device
+    assert 1 <= w.shape[0] and w.shape[0] * N < 2 ** 31
+    return w
+
+
+def head_sigmoid_dot(h, Wd, bd, w, splits=None, w_row=None):
     """out[r] = sum_j w[j] * sigmoid(h[r] . Wd[j] + bd[j]) without materialising the [n, N] product (bridges_head_sigmoid_dot):
-    h [n, 256] float32 (rows contiguous), Wd [N, 256], bd [N], w [N]."""
+    h [n, 256] float32 (rows contiguous), Wd [N, 256], bd [N], w [N].  With ``w_row`` (int32 [n]; per-env tasks) w is [M, N], one
+    map per task, and row r is weighed with w[w_row[r]] (bridges_head_sigmoid_dot_rows; entries must lie in [0, M))."""
     L = abi.require_gpu()
     assert h.dtype == torch.float32 and h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == 256
-    Wd, bd, w = Wd.to(torch.float32).contiguous(), bd.to(torch.float32).contiguous(), w.to(torch.float32).reshape(-1).contiguous()
+    Wd, bd = Wd.to(torch.float32).contiguous(), bd.to(torch.float32).contiguous()
     N = Wd.shape[0]
-    assert Wd.shape[1] == 256 and bd.numel() == N and w.numel() == N
     n = h.shape[0]
+    w = w.to(torch.float32).reshape(-1).contiguous() if w_row is None else _row_maps(w, w_row, N, n)
+    assert Wd.shape[1] == 256 and bd.numel() == N and (w_row is not None or w.numel() == N)
     if splits is None:
         splits = _head_splits(n, (N + 31) // 32)
     out = torch.empty(n, dtype=torch.float32, device=h.device)
     part = torch.empty((splits, n), dtype=torch.float32, device=h.device) if splits > 1 else None
+    if w_row is not None:
+        abi.check(L.bridges_head_sigmoid_dot_rows(n, 256, N, _ptr(h), h.stride(0), _ptr(Wd), _ptr(bd), _ptr(w), _ptr(w_row), w.shape[0],
+                                                  _ptr(out), _ptr(part) if part is not None else None, splits, _stream()),
+                  "bridges_head_sigmoid_dot_rows")
+        return out
     abi.check(L.bridges_head_sigmoid_dot(n, 256, N, _ptr(h), h.stride(0), _ptr(Wd), _ptr(bd), _ptr(w), _ptr(out),
                                          _ptr(part) if part is not None else None, splits, _stream()), "bridges_head_sigmoid_dot")
     return out
@@ -422,14 +437,20 @@ def bits_accumulate_(img, bits, slot, weight=None, bits_row=None):
     return img
 
 
-def sigmoid_dot(d, w):
-    """out[r] = sum_j w[j] * sigmoid(d[r, j]) in one pass over ``d`` ([n, k] float32, k % 4 == 0; bridges_sigmoid_dot)."""
+def sigmoid_dot(d, w, w_row=None):
+    """out[r] = sum_j w[j] * sigmoid(d[r, j]) in one pass over ``d`` ([n, k] float32, k % 4 == 0; bridges_sigmoid_dot).  With
+    ``w_row`` (int32 [n]) w is [M, k] and row r is weighed with w[w_row[r]] (bridges_sigmoid_dot_rows)."""
     L = abi.require_gpu()
     assert d.dtype == torch.float32 and d.dim() == 2 and d.stride(1) == 1
-    w = w.to(torch.float32).reshape(-1).contiguous()
     n, k = d.shape
-    assert w.numel() == k
     out = torch.empty(n, dtype=torch.float32, device=d.device)
+    if w_row is not None:
+        w = _row_maps(w, w_row, k, n)
+        abi.check(L.bridges_sigmoid_dot_rows(n, _ptr(d), d.stride(0), _ptr(w), _ptr(w_row), k, _ptr(out), _stream()),
+                  "bridges_sigmoid_dot_rows")
+        return out
+    w = w.to(torch.float32).reshape(-1).contiguous()
+    assert w.numel() == k
     abi.check(L.bridges_sigmoid_dot(n, _ptr(d), d.stride(0), _ptr(w), k, _ptr(out), _stream()), "bridges_sigmoid_dot")
     return out
 

@@ -403,6 +403,18 @@ class VecAssemblyGym:
             abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
             self.refresh()
 
+    def load_targets(self, targets):
+        """Per-env targets ([E, T, 3] or [E, 3 T] float64, already on the device) for a scratch env whose states are about to be
+        loaded (load_records / load_states, whose refresh gives the candidates the new tasks' linear rewards): env_targets and
+        everything derived from them -- target_bits, reward_maps, reward_prefix (bridges_env_load_targets) -- and nothing
+        else; task_episode and the states stay.  One copy, one launch sequence, no host wait."""
+        if not self.per_env_tasks or self.random_targets is not None:
+            raise ValueError("load_targets needs an env with explicit per-env targets (created with an [E, T, 3] array / set_targets)")
+        if targets.numel() != self.env_targets.numel() or targets.dtype != torch.float64:
+            raise ValueError(f"targets must hold {tuple(self.env_targets.shape)} float64 values, got {tuple(targets.shape)} {targets.dtype}")
+        self.env_targets.copy_(targets.reshape(self.env_targets.shape))
+        abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
+
     # ------------------------------------------------------------------ lock-step API
     def reset(self):
         abi.check(self.L.bridges_env_reset(self._env, _stream()), "bridges_env_reset")
@@ -562,11 +574,14 @@ class VecAssemblyGym:
         idx, _ = self.valid_rows()
         return idx, self.buf["cand_stable"][idx] == 1
 
-    def state_groups(self, flag=None):
+    def state_groups(self, flag=None, task=False):
         """rep int32 [E]: the smallest env index that holds exactly this env's state -- block count and the shape, pose bits
         and face occupancy of its blocks, plus the caller's per-env ``flag`` byte (e.g. the 'stable' feature) -- found by a
         64-bit hash and verified word for word (bridges_env_groups; two launches, no wait).  Envs in the same state hold the
-        same candidates in the same order, so valid_rows(rep) lets them share one set of rows."""
+        same candidates in the same order, so valid_rows(rep) lets them share one set of rows.
+        ``task=True`` (an env with per-env tasks): the bit patterns of the env's own targets, env_targets[e], are part of its
+        identity as well (bridges_env_groups_keyed) -- what a network says about a state depends on the task it is asked
+        under, so only envs in the same state AND under the same task share rows."""
         hkey = getattr(self, "_hkey", None)
         if hkey is None:
             hkey = self._hkey = torch.empty(self.E, dtype=torch.int64, device=self.device)
@@ -574,6 +589,15 @@ class VecAssemblyGym:
         if flag is not None:
             flag = flag.to(torch.uint8).contiguous()
         b = self.buf
+        if task:
+            if not self.per_env_tasks:
+                raise ValueError("state_groups(task=True) needs an env with per-env tasks (targets=RandomTargets() / set_targets)")
+            key = self.env_targets
+            assert key.dtype == torch.float64 and key.is_contiguous() and key.shape[0] == self.E
+            abi.check(self.L.bridges_env_groups_keyed(self.E, self.K, _ptr(b["n_blocks"]), _ptr(b["blk_shape"]), _ptr(b["blk_pose"]),
+                                                      _ptr(b["blk_occ"]), _ptr(flag), _ptr(key), key.numel() // self.E, _ptr(hkey),
+                                                      _ptr(rep), _stream()), "bridges_env_groups_keyed")
+            return rep
         abi.check(self.L.bridges_env_groups(self.E, self.K, _ptr(b["n_blocks"]), _ptr(b["blk_shape"]), _ptr(b["blk_pose"]),
                                             _ptr(b["blk_occ"]), _ptr(flag), _ptr(hkey), _ptr(rep), _stream()), "bridges_env_groups")
         return rep

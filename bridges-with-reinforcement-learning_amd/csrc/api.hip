@@ -637,31 +637,64 @@ int bridges_valid_rows(int32_t E, const int32_t* cand_offset, const int32_t* n_c
                   (const int32_t*)seg, rep, seg_lo, seg_hi, idx, row_env);
 }
 
-int bridges_env_groups(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
-                       const uint8_t* blk_occ, const uint8_t* flag, uint64_t* hkey, int32_t* rep, void* stream) {
+int bridges_env_groups_keyed(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
+                             const uint8_t* blk_occ, const uint8_t* flag, const uint64_t* extra, int32_t n_extra, uint64_t* hkey,
+                             int32_t* rep, void* stream) {
     if (E < 1 || K < 1 || K > 64 || !n_blocks || !blk_shape || !blk_pose || !blk_occ || !hkey || !rep) return fail_arg("bridges_env_groups");
+    if (n_extra < 0 || ((extra == nullptr) != (n_extra == 0))) return fail_arg("bridges_env_groups_keyed: extra / n_extra");
     const dim3 grid((unsigned)ceil_div(E, 4));
-    if (int rc = launch("k_env_hash", k_env_hash, grid, dim3(256), 0, stream, E, K, n_blocks, blk_shape, blk_pose, blk_occ, flag, hkey))
+    if (!extra) {
+        if (int rc = launch("k_env_hash", k_env_hash<false>, grid, dim3(256), 0, stream, E, K, n_blocks, blk_shape, blk_pose, blk_occ, flag,
+                            extra, 0, hkey))
+            return rc;
+        return launch("k_env_match", k_env_match<false>, grid, dim3(256), 0, stream, E, K, n_blocks, blk_shape, blk_pose, blk_occ, flag,
+                      extra, 0, (const uint64_t*)hkey, rep);
+    }
+    if (int rc = launch("k_env_hash<keyed>", k_env_hash<true>, grid, dim3(256), 0, stream, E, K, n_blocks, blk_shape, blk_pose, blk_occ,
+                        flag, extra, (int)n_extra, hkey))
         return rc;
-    return launch("k_env_match", k_env_match, grid, dim3(256), 0, stream, E, K, n_blocks, blk_shape, blk_pose, blk_occ, flag,
-                  (const uint64_t*)hkey, rep);
+    return launch("k_env_match<keyed>", k_env_match<true>, grid, dim3(256), 0, stream, E, K, n_blocks, blk_shape, blk_pose, blk_occ, flag,
+                  extra, (int)n_extra, (const uint64_t*)hkey, rep);
 }
 
-int bridges_head_sigmoid_dot(int32_t n_rows, int32_t K, int32_t N, const float* h, int64_t h_stride, const float* Wd,
-                             const float* bd, const float* w, float* out, float* part, int32_t splits, void* stream) {
+int bridges_env_groups(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
+                       const uint8_t* blk_occ, const uint8_t* flag, uint64_t* hkey, int32_t* rep, void* stream) {
+    return bridges_env_groups_keyed(E, K, n_blocks, blk_shape, blk_pose, blk_occ, flag, nullptr, 0, hkey, rep, stream);
+}
+
+// w_row == nullptr: one map w [N] for every row; else w [n_maps, N] and row r takes map w_row[r]
+static int head_sigmoid_dot(int32_t n_rows, int32_t K, int32_t N, const float* h, int64_t h_stride, const float* Wd, const float* bd,
+                            const float* w, const int32_t* w_row, int32_t n_maps, float* out, float* part, int32_t splits,
+                            void* stream) {
     if (n_rows < 0 || N <= 0 || !h || !Wd || !bd || !w || !out || splits < 1 || (splits > 1 && !part))
         return fail_arg("bridges_head_sigmoid_dot");
+    if (w_row && (n_maps < 1 || (int64_t)n_maps * N > INT32_MAX)) return fail_arg("bridges_head_sigmoid_dot_rows: n_maps");
     if (K != HEAD_K) return fail_arg("bridges_head_sigmoid_dot: the hidden width must be 256");
     if ((h_stride & 3) || h_stride < K || !aligned(16, h, Wd)) return fail_arg("bridges_head_sigmoid_dot: rows must be 16-byte aligned");
     if (n_rows == 0) return BRIDGES_OK;
     const int tiles = (N + HEAD_BN - 1) / HEAD_BN;
     const int per = (tiles + splits - 1) / splits;
     const int used = (tiles + per - 1) / per;                             // ranges that hold at least one tile
-    if (int rc = launch("k_head_sigmoid_dot", k_head_sigmoid_dot, dim3((unsigned)ceil_div(n_rows, 128), (unsigned)used), dim3(256), 0,
-                        stream, n_rows, N, h, h_stride, Wd, bd, w, used > 1 ? part : out, per))
+    const dim3 grid((unsigned)ceil_div(n_rows, 128), (unsigned)used);
+    if (int rc = w_row ? launch("k_head_sigmoid_dot<rows>", k_head_sigmoid_dot<true>, grid, dim3(256), 0, stream, n_rows, N, h, h_stride, Wd,
+                                bd, w, w_row, used > 1 ? part : out, per)
+                       : launch("k_head_sigmoid_dot", k_head_sigmoid_dot<false>, grid, dim3(256), 0, stream, n_rows, N, h, h_stride, Wd,
+                                bd, w, w_row, used > 1 ? part : out, per))
         return rc;
     if (used <= 1) return BRIDGES_OK;
     return launch("k_head_sum", k_head_sum, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, stream, n_rows, used, part, out);
+}
+
+int bridges_head_sigmoid_dot(int32_t n_rows, int32_t K, int32_t N, const float* h, int64_t h_stride, const float* Wd,
+                             const float* bd, const float* w, float* out, float* part, int32_t splits, void* stream) {
+    return head_sigmoid_dot(n_rows, K, N, h, h_stride, Wd, bd, w, nullptr, 0, out, part, splits, stream);
+}
+
+int bridges_head_sigmoid_dot_rows(int32_t n_rows, int32_t K, int32_t N, const float* h, int64_t h_stride, const float* Wd,
+                                  const float* bd, const float* w_all, const int32_t* w_row, int32_t n_maps, float* out, float* part,
+                                  int32_t splits, void* stream) {
+    if (!w_row) return fail_arg("bridges_head_sigmoid_dot_rows: w_row");
+    return head_sigmoid_dot(n_rows, K, N, h, h_stride, Wd, bd, w_all, w_row, n_maps, out, part, splits, stream);
 }
 
 int bridges_bits_dot(int32_t n_rows, const uint64_t* bits, const int64_t* bits_row, const float* img, const int64_t* slot,
@@ -685,7 +718,17 @@ int bridges_sigmoid_dot(int32_t n_rows, const float* d, int64_t row_stride, cons
     if (n_rows < 0 || k <= 0 || (k & 3) || (row_stride & 3) || !d || !w || !out) return fail_arg("bridges_sigmoid_dot");
     if (!aligned(16, d, w)) return fail_arg("sigmoid_dot: rows must be 16-byte aligned");
     if (n_rows == 0) return BRIDGES_OK;
-    return launch("k_sigmoid_dot", k_sigmoid_dot, dim3(grid_for_waves(n_rows)), dim3(256), 0, stream, n_rows, d, row_stride, w, k, out);
+    return launch("k_sigmoid_dot", k_sigmoid_dot<false>, dim3(grid_for_waves(n_rows)), dim3(256), 0, stream, n_rows, d, row_stride, w,
+                  (const int32_t*)nullptr, k, out);
+}
+
+int bridges_sigmoid_dot_rows(int32_t n_rows, const float* d, int64_t row_stride, const float* w_all, const int32_t* w_row, int32_t k,
+                             float* out, void* stream) {
+    if (n_rows < 0 || k <= 0 || (k & 3) || (row_stride & 3) || !d || !w_all || !w_row || !out) return fail_arg("bridges_sigmoid_dot_rows");
+    if (!aligned(16, d, w_all)) return fail_arg("sigmoid_dot: rows must be 16-byte aligned");
+    if (n_rows == 0) return BRIDGES_OK;
+    return launch("k_sigmoid_dot<rows>", k_sigmoid_dot<true>, dim3(grid_for_waves(n_rows)), dim3(256), 0, stream, n_rows, d, row_stride,
+                  w_all, w_row, k, out);
 }
 
 int bridges_bias_relu(float* x, const float* bias, int64_t n, int32_t C, int32_t hw, void* stream) {
@@ -877,38 +920,76 @@ int bridges_linear_backward_adam(int32_t rows, int32_t K, int32_t N, const float
                   a_block, (int)a_block_bias, LossLog{});
 }
 
+// reward_stride: 0 = one map [px] for every transition, px = a map per transition of the per-call arrays ([n, px])
+static bool reward_stride_ok(int64_t reward_stride, int32_t px) { return reward_stride == 0 || reward_stride == px; }
+
+int bridges_mlp_input_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, const int64_t* counter, const float* block_all,
+                           const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                           const float* obstacle, float* x, void* stream) {
+    if (batch <= 0 || rows < batch || (rows & 31) || px <= 0 || nf < 0 || !counter || !block_all || !action_all || !reward || !obstacle || !x)
+        return fail_arg("bridges_mlp_input");
+    if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_mlp_input_rows: reward_stride must be 0 or px");
+    const dim3 grid(clamp_grid(ceil_div(rows * (4 * px + nf), 256), 2048));
+    if (reward_stride)
+        return launch("k_mlp_input<rows>", k_mlp_input<true>, grid, dim3(256), 0, stream, batch, rows, px, nf, counter, block_all, action_all,
+                      binary_all, reward, obstacle, x);
+    return launch("k_mlp_input", k_mlp_input<false>, grid, dim3(256), 0, stream, batch, rows, px, nf, counter, block_all, action_all,
+                  binary_all, reward, obstacle, x);
+}
+
 int bridges_mlp_input(int32_t batch, int32_t rows, int32_t px, int32_t nf, const int64_t* counter, const float* block_all,
                       const float* action_all, const float* binary_all, const float* reward, const float* obstacle,
                       float* x, void* stream) {
-    if (batch <= 0 || rows < batch || (rows & 31) || px <= 0 || nf < 0 || !counter || !block_all || !action_all || !reward || !obstacle || !x)
-        return fail_arg("bridges_mlp_input");
-    return launch("k_mlp_input", k_mlp_input, dim3(clamp_grid(ceil_div(rows * (4 * px + nf), 256), 2048)), dim3(256), 0, stream, batch,
-                  rows, px, nf, counter, block_all, action_all, binary_all, reward, obstacle, x);
+    return bridges_mlp_input_rows(batch, rows, px, nf, counter, block_all, action_all, binary_all, reward, 0, obstacle, x, stream);
+}
+
+int bridges_mlp_input_batches_rows(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
+                                   const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                                   const float* obstacle, float* x_all, void* stream) {
+    if (n_batches <= 0 || batch <= 0 || rows < batch || (rows & 31) || px <= 0 || nf < 0 || !block_all || !action_all || !reward || !obstacle || !x_all)
+        return fail_arg("bridges_mlp_input_batches");
+    if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_mlp_input_batches_rows: reward_stride must be 0 or px");
+    const dim3 grid(clamp_grid(ceil_div(rows * (4 * px + nf), 256), 2048), n_batches);
+    if (reward_stride)
+        return launch("k_mlp_input<rows> (all batches)", k_mlp_input<true>, grid, dim3(256), 0, stream, batch, rows, px, nf,
+                      (const int64_t*)nullptr, block_all, action_all, binary_all, reward, obstacle, x_all);
+    return launch("k_mlp_input (all batches)", k_mlp_input<false>, grid, dim3(256), 0, stream, batch, rows, px, nf, (const int64_t*)nullptr,
+                  block_all, action_all, binary_all, reward, obstacle, x_all);
 }
 
 int bridges_mlp_input_batches(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
                               const float* action_all, const float* binary_all, const float* reward, const float* obstacle,
                               float* x_all, void* stream) {
-    if (n_batches <= 0 || batch <= 0 || rows < batch || (rows & 31) || px <= 0 || nf < 0 || !block_all || !action_all || !reward || !obstacle || !x_all)
-        return fail_arg("bridges_mlp_input_batches");
-    return launch("k_mlp_input (all batches)", k_mlp_input, dim3(clamp_grid(ceil_div(rows * (4 * px + nf), 256), 2048), n_batches),
-                  dim3(256), 0, stream, batch, rows, px, nf, (const int64_t*)nullptr, block_all, action_all, binary_all, reward, obstacle,
-                  x_all);
+    return bridges_mlp_input_batches_rows(n_batches, batch, rows, px, nf, block_all, action_all, binary_all, reward, 0, obstacle, x_all,
+                                          stream);
 }
 
 int bridges_successor_loss(int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* y, const float* reward,
                            const int64_t* counter, const float* q_target_all, const float* sf_target_all, int32_t use_q,
                            int32_t use_sf, float* dy, float* loss_rows, float* q_out, float* losses, int32_t n_losses,
                            int64_t* counter_inc, int32_t* ticket, float* adam_step, void* stream) {
+    return bridges_successor_loss_rows(batch, rows, px, nf, y, reward, 0, counter, q_target_all, sf_target_all, use_q, use_sf, dy,
+                                       loss_rows, q_out, losses, n_losses, counter_inc, ticket, adam_step, stream);
+}
+
+int bridges_successor_loss_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* y, const float* reward,
+                                int64_t reward_stride, const int64_t* counter, const float* q_target_all, const float* sf_target_all,
+                                int32_t use_q, int32_t use_sf, float* dy, float* loss_rows, float* q_out, float* losses,
+                                int32_t n_losses, int64_t* counter_inc, int32_t* ticket, float* adam_step, void* stream) {
     if (batch <= 0 || rows < batch || px <= 0 || nf < 0 || !y || !reward || !counter || !dy || !loss_rows || !q_out)
         return fail_arg("bridges_successor_loss");
     if ((use_q && !q_target_all) || (use_sf && !sf_target_all)) return fail_arg("bridges_successor_loss: target missing");
     if (ticket && !counter_inc) return fail_arg("bridges_successor_loss: a ticket needs counter_inc");
     if (adam_step && !ticket) return fail_arg("bridges_successor_loss: adam_step is advanced by the ticket holder");
     // with a ticket word (zero before the first call; the kernel re-arms it) the logging happens inside the loss kernel
-    if (int rc = launch("k_successor_loss", k_successor_loss, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch, px, nf, y, reward, counter,
-                        q_target_all, sf_target_all, use_q, use_sf, dy, loss_rows, q_out, losses, n_losses,
-                        ticket ? counter_inc : (int64_t*)nullptr, ticket, adam_step))
+    if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_successor_loss_rows: reward_stride must be 0 or px");
+    int64_t* const inc = ticket ? counter_inc : (int64_t*)nullptr;
+    if (int rc = reward_stride ? launch("k_successor_loss<rows>", k_successor_loss<true>, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch,
+                                        px, nf, y, reward, counter, q_target_all, sf_target_all, use_q, use_sf, dy, loss_rows, q_out,
+                                        losses, n_losses, inc, ticket, adam_step)
+                               : launch("k_successor_loss", k_successor_loss<false>, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch,
+                                        px, nf, y, reward, counter, q_target_all, sf_target_all, use_q, use_sf, dy, loss_rows, q_out,
+                                        losses, n_losses, inc, ticket, adam_step))
         return rc;
     if (ticket || !losses || !counter_inc) return BRIDGES_OK;
     return launch("k_loss_log", k_loss_log, dim3(1), dim3(64), 0, stream, batch, loss_rows, losses, n_losses, counter_inc);

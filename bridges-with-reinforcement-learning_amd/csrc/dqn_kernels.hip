@@ -258,13 +258,17 @@ __global__ __launch_bounds__(256) void k_bits_accumulate(int n_rows, const uint6
 // Head of the factored acting forward: q[r] = sum_j w[j] * sigmoid(d[r, j])  (cv.py:101-104: softmax over the two successor
 // channels, channel 1, times the reward map, summed over the image) in ONE pass over d instead of sigmoid / mul / sum
 // passes.  One wave per row, 16 B per lane per trip; lane partial sums in f32, the 64 partials added in f64.
+// PER_ROW (per-env tasks): w is [M, k] and row r is weighed with map w_row[r].
+template <bool PER_ROW>
 __global__ __launch_bounds__(256) void k_sigmoid_dot(int n_rows, const float* __restrict__ d, int64_t row_stride,
-                                                     const float* __restrict__ w, int k, float* __restrict__ out) {
+                                                     const float* __restrict__ w_all, const int32_t* __restrict__ w_row, int k,
+                                                     float* __restrict__ out) {
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     const int nwaves = (gridDim.x * blockDim.x) / WAVE;
     for (int r = wave; r < n_rows; r += nwaves) {
         const float* row = d + (size_t)r * row_stride;
+        const float* w = PER_ROW ? w_all + (size_t)w_row[r] * k : w_all;
         float acc = 0.f;
         // four 16-B loads of the row in flight per lane and trip (a 64 x 64 image: four trips), the sigmoid through the
         // hardware reciprocal (1 ulp; a full float32 division is ~10 instructions per pixel and made the pass ALU-heavy)

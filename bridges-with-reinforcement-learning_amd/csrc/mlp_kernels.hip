@@ -418,6 +418,8 @@ __global__ __launch_bounds__(256) void k_lin_dx_finish(int rows, int K, int nspl
 // ---------------------------------------------------------------------------------------------------------------
 // Input rows of one replay batch: x[b] = [block | action | reward | obstacle | binary] (cv.py:100-103) for the batch
 // `*counter` of the static per-call arrays (block_all / action_all [n][px], binary_all [n][nf]); rows >= batch are 0.
+// PER_ROW: every transition was taken under a task of its own -- `reward` is [n][px] and transition src reads its row src.
+template <bool PER_ROW>
 __global__ __launch_bounds__(256) void k_mlp_input(int batch, int rows, int px, int nf, const int64_t* __restrict__ counter,
                                                    const float* __restrict__ block_all, const float* __restrict__ action_all,
                                                    const float* __restrict__ binary_all, const float* __restrict__ reward,
@@ -435,7 +437,7 @@ __global__ __launch_bounds__(256) void k_mlp_input(int batch, int rows, int px, 
             const size_t src = base + b;
             if (c < px) v = block_all[src * px + c];
             else if (c < 2 * px) v = action_all[src * px + (c - px)];
-            else if (c < 3 * px) v = reward[c - 2 * px];
+            else if (c < 3 * px) v = PER_ROW ? reward[src * px + (c - 2 * px)] : reward[c - 2 * px];
             else if (c < 4 * px) v = obstacle[c - 3 * px];
             else v = binary_all[src * nf + (c - 4 * px)];
         }
@@ -470,8 +472,10 @@ __device__ __forceinline__ void loss_log_ticket(int batch, float* loss_rows, flo
 //   q[b]   = sum_j softmax(psi0, psi1)[1][j] * reward[j]            (softmax over the two channels = sigmoid(psi1 - psi0))
 //   loss   = [use_q] mean_b (q - q_t)^2 + [use_sf] mean_b mean_j (psi0 - sf_t)^2
 //   dy     = d loss / d y.  One workgroup per batch row: the q reduction and the gradient that needs it stay together.
+// PER_ROW: `reward` is [n][px], one map per transition of the per-call arrays (row src, as the targets are addressed).
 #define LOSS_THREADS 1024
 #define LOSS_CACHE 4                    // pixels per thread kept in registers between the two passes (64x64 / 1024)
+template <bool PER_ROW>
 __global__ __launch_bounds__(LOSS_THREADS) void k_successor_loss(int batch, int px, int nf, const float* __restrict__ y,
                                                                  const float* __restrict__ reward,
                                                                  const int64_t* __restrict__ counter,
@@ -495,6 +499,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_successor_loss(int batch, int 
     const float* yr = y + (size_t)b * N;
     const size_t src = (size_t)(*counter) * batch + b;
     const float* sft = use_sf ? sf_target_all + src * px : nullptr;
+    if (PER_ROW) reward += src * px;
     // pass 1: q = sum_j sigmoid(psi1 - psi0) * reward, squared error of psi0; f64 sums (their order does not matter then)
     float sig[LOSS_CACHE], rw[LOSS_CACHE], err[LOSS_CACHE];
     double qs = 0.0, ls = 0.0;
@@ -943,13 +948,21 @@ __global__ __launch_bounds__(1024) void k_mid_bwd(MidPtrs p) {
 // A[row = l & 31][k = 8u + 4 (l >> 5) + {0..3}], u < 32) x all N columns in tiles of 32: the tile of Wd (32 x 256) is staged
 // in LDS (row stride 260 floats: conflict-free 16-B reads), double-buffered, the next tile's global loads in flight under
 // this tile's 128 v_mfma_f32_32x32x2_f32; the sigmoid-weighted sum of a tile runs on the vector pipes from the accumulators.
+// PER_ROW (per-env tasks): w is [M, N], one reward map per task, and w_row[r] names the map of row r.  A lane's 16
+// accumulators belong to 16 rows, so it gathers 16 weights per tile -- w[w_row[row(r)]][col], a 128-B segment per half-wave and
+// row -- in the epilogue's place of the one.  Lane l keeps the map offset of slab row l & 31 in one register and a lane reads
+// the offsets of its accumulator rows from their holders (16 ds_bpermute per tile): sixteen offsets held beside the
+// 128-register slab took the kernel past 256 VGPRs, i.e. from two workgroups per CU to one.  Same products, same order: with
+// every w_row naming one map the result is that of the shared-map kernel bit for bit.  Measured: 19.7 against 18.1 us per
+// 1000 rows, whatever the order of the maps.
 #define HEAD_K 256
 #define HEAD_BN 32
 #define HEAD_LDS_STRIDE (HEAD_K + 4)
+template <bool PER_ROW>
 __global__ __launch_bounds__(256) void k_head_sigmoid_dot(int n_rows, int N, const float* __restrict__ h, int64_t h_stride,
                                                           const float* __restrict__ Wd, const float* __restrict__ bd,
-                                                          const float* __restrict__ w, float* __restrict__ out,
-                                                          int tiles_per_split) {
+                                                          const float* __restrict__ w, const int32_t* __restrict__ w_row,
+                                                          float* __restrict__ out, int tiles_per_split) {
     __shared__ __attribute__((aligned(16))) float sB[2][HEAD_BN * HEAD_LDS_STRIDE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = lane & 31, half = lane >> 5;
@@ -979,6 +992,10 @@ __global__ __launch_bounds__(256) void k_head_sigmoid_dot(int n_rows, int N, con
     float qacc[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) qacc[r] = 0.f;
+    // PER_ROW: element offset of the map of slab row (lane & 31) -- one register; the offsets of a lane's 16 accumulator rows
+    // are fetched from the lanes that hold them, tile by tile (rows beyond n: the last row's map)
+    int wofs = 0;
+    if constexpr (PER_ROW) wofs = w_row[my_row] * N;
     // blockIdx.y = a range of column tiles (the launch is cut so that the workgroups fill the CUs evenly); its sums go to
     // out[blockIdx.y * n_rows + r] and k_head_sum adds the ranges up in a fixed order
     const int all_tiles = (N + HEAD_BN - 1) / HEAD_BN;
@@ -1016,9 +1033,22 @@ __global__ __launch_bounds__(256) void k_head_sigmoid_dot(int n_rows, int N, con
             for (int j = 0; j < 4; ++j) b[j] = bn[j];
         }
         const int col = n0 + row;
-        const float wj = col < N ? w[col] : 0.f, bj = col < N ? bd[col] : 0.f;
+        if constexpr (PER_ROW) {
+            // this tile's 16 weights, gathered behind the MFMAs where the read-ahead registers are free (held across them they
+            // took the kernel past 256 VGPRs); the workgroup's other resident partner covers the round trip to L1 / L2
+            const int wc = col < N ? col : N - 1;
+            float wv[16];
+            __builtin_amdgcn_sched_barrier(0);                          // not above the MFMAs: see above
 #pragma unroll
-        for (int r = 0; r < 16; ++r) qacc[r] += wj * __builtin_amdgcn_rcpf(1.f + __expf(-(acc[r] + bj)));
+            for (int r = 0; r < 16; ++r) wv[r] = w[(size_t)(__shfl(wofs, mfma_row(r, lane)) + wc)];
+            const float bj = col < N ? bd[col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) qacc[r] += (col < N ? wv[r] : 0.f) * __builtin_amdgcn_rcpf(1.f + __expf(-(acc[r] + bj)));
+        } else {
+            const float wj = col < N ? w[col] : 0.f, bj = col < N ? bd[col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) qacc[r] += wj * __builtin_amdgcn_rcpf(1.f + __expf(-(acc[r] + bj)));
+        }
         if (t + 1 < n_tiles) HEAD_STORE_TILE(buf ^ 1);
         __syncthreads();
     }

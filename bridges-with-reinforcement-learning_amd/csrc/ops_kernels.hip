@@ -388,14 +388,19 @@ __global__ __launch_bounds__(256) void k_valid_fill(int E, const int32_t* __rest
 //   k_env_hash:  hkey[e] = 64-bit hash of (n_blocks, the live slots' shape / pose bits / occupancy, flag[e])
 //   k_env_match: rep[e] = the smallest env index with the same hash whose state equals env e's WORD FOR WORD (else e itself:
 //                a hash collision only costs the sharing, never correctness).  E^2 / 64 comparisons per wave: 4096 envs, ~10 us.
+// KEYED: an env carries n_extra further 64-bit words (extra [E][n_extra]: the bit patterns of its own task's targets) that
+// are part of its identity -- folded into the hash, compared word for word: envs in the same state under different tasks do
+// not share rows.
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
     return x;
 }
 
+template <bool KEYED>
 __global__ __launch_bounds__(256) void k_env_hash(int E, int K, const int32_t* __restrict__ n_blocks, const int32_t* __restrict__ blk_shape,
                                                   const double* __restrict__ blk_pose, const uint8_t* __restrict__ blk_occ,
-                                                  const uint8_t* __restrict__ flag, uint64_t* __restrict__ hkey) {
+                                                  const uint8_t* __restrict__ flag, const uint64_t* __restrict__ extra, int n_extra,
+                                                  uint64_t* __restrict__ hkey) {
     const int lane = threadIdx.x & 63;
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= E) return;
@@ -408,15 +413,20 @@ __global__ __launch_bounds__(256) void k_env_hash(int E, int K, const int32_t* _
         a = mix64(a ^ p[0]); a = mix64(a ^ p[1]); a = mix64(a ^ p[2]); a = mix64(a ^ p[3]);
         h = mix64(a + (uint64_t)(lane + 1) * 0x9E3779B97F4A7C15ull);
     }
+    if constexpr (KEYED) {                                               // word i of the key, position-dependent like the slots
+        for (int i = lane; i < n_extra; i += 64)
+            h += mix64(mix64(extra[(size_t)e * n_extra + i]) + (uint64_t)(i + 65) * 0x9E3779B97F4A7C15ull);
+    }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) h += __shfl_xor(h, m);
     if (lane == 0) hkey[e] = mix64(h + (uint64_t)nb * 0xD6E8FEB86659FD93ull + (flag ? (uint64_t)flag[e] : 0ull));
 }
 
+template <bool KEYED>
 __global__ __launch_bounds__(256) void k_env_match(int E, int K, const int32_t* __restrict__ n_blocks, const int32_t* __restrict__ blk_shape,
                                                    const double* __restrict__ blk_pose, const uint8_t* __restrict__ blk_occ,
-                                                   const uint8_t* __restrict__ flag, const uint64_t* __restrict__ hkey,
-                                                   int32_t* __restrict__ rep) {
+                                                   const uint8_t* __restrict__ flag, const uint64_t* __restrict__ extra, int n_extra,
+                                                   const uint64_t* __restrict__ hkey, int32_t* __restrict__ rep) {
     const int lane = threadIdx.x & 63;
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= E) return;
@@ -437,6 +447,9 @@ __global__ __launch_bounds__(256) void k_env_match(int E, int K, const int32_t* 
             const uint64_t* pb = reinterpret_cast<const uint64_t*>(blk_pose + b * 4);
             same = blk_shape[a] == blk_shape[b] && blk_occ[a] == blk_occ[b] && pa[0] == pb[0] && pa[1] == pb[1] && pa[2] == pb[2] &&
                    pa[3] == pb[3];
+        }
+        if constexpr (KEYED) {
+            for (int i = lane; i < n_extra; i += 64) same = same && extra[(size_t)e * n_extra + i] == extra[(size_t)r * n_extra + i];
         }
         same = __ballot(!same) == 0ull;
     }

@@ -169,6 +169,18 @@ class SuccessorMLP(nn.Module):
         return torch.stack([const, const + lin.weight[:, 4 * px]])
 
     @torch.no_grad()
+    def first_layer_stable_tables(self, reward_maps, obstacle):
+        """first_layer_stable_table for envs that own their reward maps (per-env tasks): reward_maps [E, px] (or [E, H, W]),
+        obstacle [px] shared -> [E, 2, hidden], row [e, s] = the terms of env e with stable = s (k_bits_linear's ``base`` with
+        base_row = 2 * env + stable).  One [E, px] x [px, hidden] product per call."""
+        px = self.img_size[0] * self.img_size[1]
+        lin = self.first_layer()
+        E = reward_maps.shape[0]
+        const = torch.addmv(lin.bias, lin.weight[:, 3 * px:4 * px], obstacle.reshape(px))
+        per_env = torch.addmm(const, reward_maps.reshape(E, px), lin.weight[:, 2 * px:3 * px].T)
+        return torch.stack([per_env, per_env + lin.weight[:, 4 * px]], dim=1)
+
+    @torch.no_grad()
     def sf0_from_first_layer(self, h_pre):
         """Channel 0 of the successor block features (``forward(...)[1][:, 0]`` flattened to [n, px]) from the
         pre-activation of the first layer: the remaining hidden layers and the first px rows of the output layer -- what the
@@ -204,14 +216,24 @@ class SuccessorMLP(nn.Module):
         return h
 
     @torch.no_grad()
-    def q_from_first_layer(self, h_pre, reward_features, head=None, fused_head=None):
+    def q_from_first_layer(self, h_pre, reward_features, head=None, fused_head=None, reward_rows=None):
         """q from the pre-activation of the first layer ([n, hidden]): the remaining layers and the factored head.
         ``head(d, w) -> sum_j w[j] * sigmoid(d[:, j])`` may be supplied as a fused operator, or -- for a last hidden width of
-        256 -- ``fused_head(h, Wd, bd, w) -> sum_j w[j] * sigmoid(h . Wd[j] + bd[j])``, which never stores the [n, px] product."""
+        256 -- ``fused_head(h, Wd, bd, w) -> sum_j w[j] * sigmoid(h . Wd[j] + bd[j])``, which never stores the [n, px] product.
+        ``reward_rows`` (int32 [n]; per-env tasks): reward_features then holds one map per task ([M, px] or [M, H, W]) and row r
+        is weighed with map reward_rows[r]; the operators get it as their ``w_row`` keyword."""
         lin = [m for m in self.mlp.layers if isinstance(m, nn.Linear)]
         px = self.img_size[0] * self.img_size[1]
         h = self._middle_layers(h_pre, lin)
         Wo, bo = lin[-1].weight, lin[-1].bias
+        if reward_rows is not None:
+            maps = reward_features.reshape(-1, px)
+            if fused_head is not None and h.shape[1] == 256:
+                return fused_head(h, Wo[px:2 * px] - Wo[:px], bo[px:2 * px] - bo[:px], maps, w_row=reward_rows)
+            d = torch.addmm(bo[px:2 * px] - bo[:px], h, (Wo[px:2 * px] - Wo[:px]).T)
+            if head is not None:
+                return head(d, maps, w_row=reward_rows)
+            return (torch.sigmoid(d) * maps.index_select(0, reward_rows.long())).sum(dim=1)
         if fused_head is not None and h.shape[1] == 256:
             return fused_head(h, Wo[px:2 * px] - Wo[:px], bo[px:2 * px] - bo[:px], reward_features.reshape(px))
         d = torch.addmm(bo[px:2 * px] - bo[:px], h, (Wo[px:2 * px] - Wo[:px]).T)

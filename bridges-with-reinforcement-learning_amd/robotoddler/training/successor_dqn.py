@@ -512,10 +512,38 @@ def build_parser():
                         "(default 0: none). The single-env loop evaluates one episode anyway and ignores it.")
     p.add_argument("--eval_epsilon", type=float, default=argparse.SUPPRESS,
                    help="Vectorised loop: exploration rate of the evaluation episodes (default 0.0: greedy, as the reference).")
+    p.add_argument("--random_targets", type=int, default=argparse.SUPPRESS, metavar="T",
+                   help="Vectorised loop, SuccessorMLP: tower_setup(num_targets=T) per env and episode -- every env draws T "
+                        "fresh targets whenever it starts an episode (trapezoid blocks, no obstacles); --eval_envs evaluates on a "
+                        "fixed held-out set of tasks. Not with --tower_height / --bridge_length.")
     return p
 
 
 EVAL_DEFAULTS = dict(eval_envs=0, eval_epsilon=0.0)
+
+
+def check_random_targets(args):
+    """--random_targets T is the vectorised SuccessorMLP loop on per-env random tasks; every other combination is refused in
+    words (SystemExit), before anything touches the GPU."""
+    T = args.get('random_targets')
+    if T is None:
+        return
+    from bridges_hip import abi
+    if not 1 <= T <= abi.MAX_TARGETS:
+        raise SystemExit(f"--random_targets must be 1..{abi.MAX_TARGETS} targets per env")
+    if args.get('tower_height') or args['bridge_length'] != 1:
+        raise SystemExit("--random_targets draws every env's task (tower_setup: random targets, no obstacles): it cannot be "
+                         "combined with --tower_height or --bridge_length, which name one fixed task")
+    if args['num_envs'] <= 1:
+        raise SystemExit("--random_targets needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
+                         "fixed tasks of --tower_height / --bridge_length only")
+    if args['model'] != 'SuccessorMLP':
+        raise SystemExit(f"--random_targets trains --model SuccessorMLP only: {args['model']} takes the reward map as an image "
+                         "channel and its rows are shared by state alone (per-env tasks for the conv nets are not built)")
+    if tuple(args['image_size']) != (64, 64):
+        raise SystemExit("--random_targets needs --image_size 64x64 (the factored acting path of SuccessorMLP)")
+    if args['shapes'] != 'trapezoid':
+        raise SystemExit("--random_targets is tower_setup: --shapes trapezoid")
 
 
 def make_setup_fct(args):
@@ -545,6 +573,7 @@ def main(argv=None):
     args = vars(build_parser().parse_args(argv))
     if args['device'] == 'cpu':
         raise SystemExit("this build has no CPU path: the simulator and the DQN ops are HIP kernels (use --device cuda)")
+    check_random_targets(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

@@ -71,12 +71,18 @@ class CapturedTrainStep:
     captures again; a failed capture (RuntimeError) or an invalid logged loss switches the driver to eager for good."""
 
     def __init__(self, net, optimizer, batch, loss_parts, img, fused, graph_default=True, warmup=1, eager_body=True,
-                 prepared=False, task=None, owner=None):
+                 prepared=False, task=None, owner=None, task_rows=False):
         self.net, self.opt, self.B, self.img = net, optimizer, int(batch), tuple(int(s) for s in img)
         self.key = (optimizer, self.B, tuple(loss_parts), owner)
         self.use_q, self.use_sf = 'mse_q_values' in loss_parts, 'mse_block_features' in loss_parts
         self.fused, self.graph_default, self.warmup, self.eager_body = fused, graph_default, warmup, eager_body
         self.prepared, self.task = prepared, task         # task: the (reward, obstacle) maps of every call (None: per call)
+        # task_rows (per-env tasks; the hand-written step only): every transition has a reward map of its own -- ``run`` takes
+        # them as reward [n * B, px] and copies them into a static [n_max * B, px] buffer the captured launches read with a
+        # row stride, so the graph replays unchanged; task = (None, obstacle): the obstacle map stays shared
+        self.task_rows = bool(task_rows)
+        if self.task_rows and not (fused and task is not None and task[0] is None):
+            raise ValueError("per-transition reward maps need the hand-written step (fused=True) and task=(None, obstacle)")
         self.calls, self.disabled, self.n_max = 0, False, 0
         self.step = self.adam = self.state = None
         self._graphs = {}
@@ -107,7 +113,10 @@ class CapturedTrainStep:
         self.sf = z(N, px) if self.use_sf else None
         self.counter, self.losses = torch.zeros((), dtype=torch.int64, device=dev), z(n)
         self.lane, self.iota = torch.arange(B, device=dev), torch.arange(n, device=dev)
-        self.reward, self.obstacle = (z(px), z(px)) if self.task is None else (t.reshape(-1).contiguous() for t in self.task)
+        if self.task_rows:
+            self.reward, self.obstacle = z(N, px), self.task[1].reshape(-1).contiguous()
+        else:
+            self.reward, self.obstacle = (z(px), z(px)) if self.task is None else (t.reshape(-1).contiguous() for t in self.task)
         self.net.train()
         self.opt.zero_grad(set_to_none=True)
         self.step = self.adam = None
@@ -177,7 +186,8 @@ class CapturedTrainStep:
 
     def run(self, n, block, action, binary, reward, obstacle, q, sf):
         """n optimiser steps on batches 0 .. n-1 of the per-call arrays (rows b * B .. b * B + B - 1 of block / action /
-        binary / q / sf; reward / obstacle: one map for all rows, unused with ``task``) -> the device tensor of the n losses
+        binary / q / sf; reward / obstacle: one map for all rows, unused with ``task`` -- except with ``task_rows``, where
+        reward [n * B, px] holds the map of every transition) -> the device tensor of the n losses
         (a view of the driver's buffer, valid until its next call), or None: the caller steps eagerly."""
         graphs = not self.disabled and graph_enabled(self.graph_default)
         if not graphs or self.calls < self.warmup:
@@ -189,6 +199,8 @@ class CapturedTrainStep:
             self._check_hyperparameters()
             self.counter.zero_()
             self.losses.zero_()
+            if self.task_rows:
+                reward, obstacle = reward.reshape(n * self.B, -1).contiguous(), self.obstacle
             for _ in range(n):
                 self._fused_body(block, action, binary, reward, obstacle, q, sf)
             return self.losses[:n]
@@ -205,6 +217,8 @@ class CapturedTrainStep:
                 self._disable()
                 return self.run(n, block, action, binary, reward, obstacle, q, sf)
         N = n * self.B
+        if self.task_rows:
+            _put(self.reward, reward.reshape(N, -1))       # before the first-layer rows are built from it
         if self.fused and self.prepared:
             # the first layer's input rows of all n batches in one launch, straight from the caller's tensors (no staging
             # copy of the block / action images: a replayed step reads only x_all, q and sf)

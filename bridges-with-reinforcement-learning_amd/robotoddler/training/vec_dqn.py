@@ -34,7 +34,7 @@ import torch
 
 from bridges_hip import dqn_ops, ops
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import VecAssemblyGym
+from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
 from robotoddler.training import distributed as D
 from robotoddler.training import records as R
 from robotoddler.training.episode_stats import EpisodeStats
@@ -44,12 +44,36 @@ from robotoddler.training import train_step as T
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
-                 episode_stats=False):
-        if getattr(env, "per_env_tasks", False):
-            raise ValueError("VecDQN cannot train on a rollout env with per-env tasks (RandomTargets / set_targets): envs in the "
-                             "same state share candidate rows whatever their task (bridges_env_groups keys rows by state "
-                             "alone), the factored SuccessorMLP acting path and the captured train steps hold ONE reward map, "
-                             "and a replay record does not store its task")
+                 episode_stats=False, per_env_tasks=False):
+        """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
+        or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
+        map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
+        and the optimiser step reads a map per transition.  Only the path that is hand-written from acting to Adam takes it:
+        a SuccessorMLP on 64x64 images with the fused optimiser step."""
+        self.per_env_tasks = bool(per_env_tasks)
+        if getattr(env, "per_env_tasks", False) and not self.per_env_tasks:
+            raise ValueError("VecDQN cannot train on a rollout env with per-env tasks (RandomTargets / set_targets) unless it is "
+                             "built with per_env_tasks=True: by default envs in the same state share candidate rows whatever "
+                             "their task (bridges_env_groups keys rows by state alone), the factored SuccessorMLP acting path "
+                             "and the captured train steps hold ONE reward map, and a replay record does not store its task")
+        if self.per_env_tasks:
+            loss_parts = loss_function.split('+')
+            if not getattr(env, "per_env_tasks", False):
+                raise ValueError("VecDQN(per_env_tasks=True) needs a rollout env with per-env tasks "
+                                 "(VecAssemblyGym(targets=RandomTargets()) or set_targets); this env has one fixed task")
+            for name, net in (("policy", policy_net), ("target", target_net)):
+                if not hasattr(net, "q_from_first_layer"):
+                    raise ValueError(f"VecDQN(per_env_tasks=True): the {name} net is a {type(net).__name__}; only SuccessorMLP "
+                                     "weighs its output with a per-row reward map (the conv nets take the map as an image channel)")
+                if tuple(getattr(net, "img_size", (64, 64))) != (64, 64) or env.img != 64:
+                    raise ValueError(f"VecDQN(per_env_tasks=True): the factored acting path is built for 64x64 images, the {name} "
+                                     f"net has {tuple(getattr(net, 'img_size', ()))} and the env {env.img}x{env.img}")
+                if not self._factored(net):
+                    raise ValueError("VecDQN(per_env_tasks=True) needs the factored acting path (VecDQN.FACTORED_ACTING)")
+            if not T.fused_step_enabled(policy_net, loss_parts):
+                raise ValueError("VecDQN(per_env_tasks=True) needs the fused optimiser step (train_step.fused_step_enabled): a "
+                                 "float32 SuccessorMLP, the MSE losses of the CLI and BRIDGES_FUSED_MLP_STEP != 0 -- the "
+                                 "autograd body of the captured step holds one reward map")
         self.policy_net, self.target_net, self.opt, self.env = policy_net, target_net, optimizer, env
         # stable actions only: the rollout env and the replay scratch env narrow every candidate set to the stable placements,
         # so acting, exploring, the TD target's max over next actions and the done flags all see the same smaller set
@@ -60,7 +84,9 @@ class VecDQN:
         self.B, self.gamma, self.tau = batch_size, gamma, tau
         self.loss_parts = loss_function.split('+')
         self.prioritized = bool(prioritized)      # PrioritizedReplayBuffer semantics (replay_memory.py:45-93)
-        self.ring = R.ReplayRing(replay_capacity, self.device)
+        # per-env tasks: a record ends in the T targets (x, y, z) its transition was taken under
+        self.task_width = 3 * env.n_targets if self.per_env_tasks else 0
+        self.ring = R.ReplayRing(replay_capacity, self.device, width=R.RECORD_WIDTH + self.task_width)
         # replay sampling must be identical on every rank (replicated rings) -> shared seed; exploration differs
         self.sample_gen = torch.Generator(device=self.device).manual_seed(1234567 + seed)
         self.explore_gen = torch.Generator(device=self.device).manual_seed(7654321 + seed * 1000 + rank)
@@ -68,12 +94,7 @@ class VecDQN:
         self.epsilon, self.eps_end, self.eps_decay = eps_start, eps_end, eps_decay
         self.step_images = torch.zeros((env.K + 1, env.img, env.img), dtype=torch.float32, device=self.device)
         # scratch env used to rebuild the candidate sets of sampled next states (see _replay_env)
-        self.replay_env = VecAssemblyGym(batch_size, env.shapes, env.obstacles, env.targets, max_steps=env.max_steps,
-                                         mu=env.mu, density=env.density, bounds=env.bounds, xlim=env.xlim,
-                                         ylim=env.ylim, x_discr_ground=env.x_discr_ground,
-                                         offset_values=env.offset_values, device=self.device, a_max=env.a_max,
-                                         img_size=(env.img, env.img), f32_rasters=self._replay_f32(),
-                                         stable_actions_only=self.stable_actions_only)
+        self.replay_env = self._make_replay_env(batch_size)
         self.mse = torch.nn.MSELoss()
         for g in optimizer.param_groups:                # step counter on the device: the train step is graph-captured
             if 'capturable' in g:
@@ -83,7 +104,7 @@ class VecDQN:
         self.env_steps = 0
         self._counts_host = torch.zeros(2, dtype=torch.int64).pin_memory()      # (env-steps, finished episodes) of a lock-step
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
-        self.episode_stats = (EpisodeStats(env.E, env.K, gamma, len(env.targets), self.device) if episode_stats else None)
+        self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device) if episode_stats else None)
         self._eval_state = {}                                # evaluate(): (random stream, EpisodeStats, count images) per env shape
 
     ROW_CHUNK = 2048       # rows per forward call: ONE input shape for the whole run (MIOpen tunes per shape)
@@ -101,7 +122,8 @@ class VecDQN:
         cache = getattr(env, "_dqn_rows", None)
         if cache is not None and cache[0] == env._cand_version:
             return cache[1]
-        rep = env.state_groups(stable) if self.DEDUP_STATES else None
+        # (per-env tasks: the env's own targets are part of the key -- same state, other task, other values)
+        rep = env.state_groups(stable, task=bool(getattr(env, "per_env_tasks", False))) if self.DEDUP_STATES else None
         idx, row_env = env.valid_rows(rep)
         out = (idx, row_env, env.valid_segments(), rep)
         env._dqn_rows = (env._cand_version, out)
@@ -230,6 +252,21 @@ class VecDQN:
         px = 64 * 64
         self.rows_fed = getattr(self, "rows_fed", 0) + idx.numel()
         W1 = net.first_layer().weight
+        if getattr(env, "per_env_tasks", False):
+            # every env owns its reward map: the image-independent part of the first layer is a [E, 2, hidden] table (one
+            # [E, px] x [px, hidden] product per net and call) indexed by 2 * env + stable, and the head weighs row r with the
+            # map of its env (bridges_head_sigmoid_dot_rows / bridges_sigmoid_dot_rows)
+            if not self.per_env_tasks:
+                raise ValueError("an env with per-env tasks needs VecDQN(per_env_tasks=True)")
+            E = env.E
+            maps = env.reward_maps.reshape(E, px)
+            table = net.first_layer_stable_tables(maps, env.obstacle_raster.reshape(-1)).reshape(2 * E, -1)
+            base_row = 2 * torch.arange(E, device=self.device) + stable.long()
+            base = ops.bits_linear(env.state_bits, W1[:, :px].T, base=table, base_row=base_row)
+            h_pre = ops.bits_linear(env.cand_bits, W1[:, px:2 * px].T, bits_row=idx, base=base, base_row=row_env)
+            q = net.q_from_first_layer(h_pre, maps, head=ops.sigmoid_dot, fused_head=ops.head_sigmoid_dot,
+                                       reward_rows=row_env.to(torch.int32))
+            return (q, h_pre) if return_h else q
         # the part of the first layer that does not depend on the images: a two-row table indexed by the env's stable flag
         # (the other binary features are 0, as in the reference without pybullet)
         ro = getattr(env, "_reward_obstacle_flat", None)
@@ -298,9 +335,20 @@ class VecDQN:
         # the record of the lock-step in two launches around the step (bridges_record_state / _result); the torch formulation
         # R.snapshot + R.make_records (~35 launches) is what tests/test_gpu_vec_dqn.py compares them with
         rec = R.pack_state(env, sel_compact)
+        if getattr(env, "per_env_tasks", False):
+            # the task the transition is taken under: the step that ends an episode redraws the env's targets (task_tail)
+            env._task_tail = env.env_targets.reshape(E, -1).clone()
         env.step(sel_index)
         valid = R.pack_result(env, rec)
         return rec, valid, q_sel
+
+    def with_task(self, rec, env=None):
+        """The records of the last act() on ``env`` (default: the rollout env) in the width the ring stores: on per-env tasks
+        the RECORD_WIDTH columns followed by the env's targets as they were BEFORE the step (one device copy; the record
+        kernels, the episode statistics and td_errors address rows of RECORD_WIDTH doubles and see ``rec`` as it is)."""
+        if not self.per_env_tasks:
+            return rec
+        return torch.cat([rec, (env or self.env)._task_tail], dim=1)
 
     # ------------------------------------------------------------------ greedy evaluation (successor_dqn.py:749-781)
     @torch.no_grad()
@@ -309,16 +357,20 @@ class VecDQN:
         (the first maximum of q) for epsilon == 0, else the training rule with the evaluation's own count images and random
         stream.  Runs exactly eval_env.K lock-steps -- every episode ends by truncation at K at the latest -- and reads the
         statistics back once.  Touches no training state (rollout env, count images, ring, random streams, epsilon, counters).
-        -> log_episode's keys as means over the N = eval_env.E episodes, plus success_rate and episodes."""
+        -> log_episode's keys as means over the N = eval_env.E episodes, plus success_rate and episodes.
+        Per-env tasks: reset() sets task_episode to 0, so every evaluation runs on the SAME eval_env.E tasks -- the draws of
+        (the eval env's seed, env, episode 0): a fixed held-out task set, not fresh tasks per evaluation."""
         if eval_env is self.env:
             raise ValueError("evaluate() needs an env of its own: the training env's episodes would be cut short")
         if bool(getattr(eval_env, "stable_actions_only", False)) != self.stable_actions_only:
             raise ValueError("the evaluation env's stable_actions_only must match the training env's")
-        key = (eval_env.E, eval_env.K, len(eval_env.targets))
+        if bool(getattr(eval_env, "per_env_tasks", False)) != self.per_env_tasks:
+            raise ValueError("the evaluation env must have per-env tasks exactly when the agent was built with per_env_tasks=True")
+        key = (eval_env.E, eval_env.K, eval_env.n_targets)
         st = self._eval_state.get(key)
         if st is None:
             gen = torch.Generator(device=self.device).manual_seed(0xE7A1 + self.seed * 1000 + self.rank)
-            stats = EpisodeStats(eval_env.E, eval_env.K, self.gamma, len(eval_env.targets), self.device, count_first_only=True,
+            stats = EpisodeStats(eval_env.E, eval_env.K, self.gamma, eval_env.n_targets, self.device, count_first_only=True,
                                  across_ranks=False)
             images = torch.zeros((eval_env.K + 1, eval_env.img, eval_env.img), dtype=torch.float32, device=self.device)
             st = self._eval_state[key] = (gen, stats, images)
@@ -338,16 +390,22 @@ class VecDQN:
                     stable=vals["stable"], collision=0.0, success_rate=vals["success_rate"], episodes=vals["episodes"])
 
     # ------------------------------------------------------------------ gradient steps on sampled batches
+    def _make_replay_env(self, n_states):
+        """A scratch env of n_states envs of the rollout env's task; on per-env tasks with per-env targets of its own (zeros
+        until _targets writes the sampled records' tasks into them)."""
+        env = self.env
+        targets = (torch.zeros((n_states, env.n_targets, 3), dtype=torch.float64) if self.per_env_tasks else env.targets)
+        return VecAssemblyGym(n_states, env.shapes, env.obstacles, targets, max_steps=env.max_steps,
+                              mu=env.mu, density=env.density, bounds=env.bounds, xlim=env.xlim,
+                              ylim=env.ylim, x_discr_ground=env.x_discr_ground,
+                              offset_values=env.offset_values, device=self.device, a_max=env.a_max,
+                              img_size=(env.img, env.img), f32_rasters=self._replay_f32(),
+                              stable_actions_only=self.stable_actions_only)
+
     def _replay_env(self, n_states):
         """Scratch env that rebuilds the states / candidate sets of sampled transitions (grown on demand)."""
         if self.replay_env.E < n_states:
-            env = self.env
-            self.replay_env = VecAssemblyGym(n_states, env.shapes, env.obstacles, env.targets, max_steps=env.max_steps,
-                                             mu=env.mu, density=env.density, bounds=env.bounds, xlim=env.xlim,
-                                             ylim=env.ylim, x_discr_ground=env.x_discr_ground,
-                                             offset_values=env.offset_values, device=self.device, a_max=env.a_max,
-                                             img_size=(env.img, env.img), f32_rasters=self._replay_f32(),
-                                             stable_actions_only=self.stable_actions_only)
+            self.replay_env = self._make_replay_env(n_states)
         return self.replay_env
 
     def _replay_f32(self):
@@ -360,10 +418,19 @@ class VecDQN:
         """Inputs and TD targets of the transitions in ``rec`` (train_policy_net, successor_dqn.py:178-213).  The
         target net is constant during one train_policy_net call (it is only updated afterwards, :704-708), so the
         targets of all its n_steps batches can be computed in one pass: one state rebuild, one candidate refresh,
-        one target-net forward and one k_td_target launch for n_steps * batch_size transitions."""
+        one target-net forward and one k_td_target launch for n_steps * batch_size transitions.
+        Per-env tasks: the records' tails (their targets) go to the scratch env first, which rebuilds every transition's reward
+        map from them (bridges_env_load_targets; envs beyond n repeat record 0's task, as their states do); a sixth value is
+        returned then, the [n, px] maps of the transitions (a view of the scratch env's reward_maps: valid until the next call)."""
         n = rec.shape[0]
         renv = self._replay_env(n)
         E = renv.E
+        if self.per_env_tasks:
+            if rec.shape[1] != R.RECORD_WIDTH + self.task_width:
+                raise ValueError(f"per-env tasks: records of {R.RECORD_WIDTH + self.task_width} columns expected, got {rec.shape[1]}")
+            tail = rec[:, R.RECORD_WIDTH:]
+            renv.load_targets(tail if n == E else torch.cat([tail, tail[:1].expand(E - n, -1)]))
+            rec = rec[:, :R.RECORD_WIDTH]
         # state s' (= s + action block): candidates, masks, rasters by the same kernels as the rollout; s is the
         # prefix of its block list, so its raster comes out of the same per-block bit rasters.  One launch unpacks the
         # records into the scratch env (envs beyond n repeat record 0 and are sliced off below); R.unpack_states +
@@ -395,7 +462,8 @@ class VecDQN:
             sf_target = action_f.reshape(E, -1) if use_sf else None
         binary = torch.zeros((E, 6), dtype=torch.float32, device=self.device)
         binary[:, 0] = stable_s
-        return block_f[:n], binary[:n], action_f[:n], q_target[:n], (sf_target[:n] if use_sf else None)
+        out = (block_f[:n], binary[:n], action_f[:n], q_target[:n], (sf_target[:n] if use_sf else None))
+        return out + (renv.reward_maps_img[:n].reshape(n, -1),) if self.per_env_tasks else out
 
     def _loss(self, q, sf, q_target, sf_target):
         loss = 0.
@@ -414,7 +482,8 @@ class VecDQN:
         return T.CapturedTrainStep.of(self.policy_net, self.opt, self.B, self.loss_parts, n_steps, owner=self, img=(env.img, env.img),
                                       fused=T.fused_step_enabled(self.policy_net, self.loss_parts),
                                       graph_default=isinstance(self.policy_net, (SuccessorMLP, ConvNet, Policy)), warmup=2,
-                                      eager_body=False, prepared=True, task=(env.reward_features, env.obstacle_raster))
+                                      eager_body=False, prepared=True, task_rows=self.per_env_tasks,
+                                      task=((None if self.per_env_tasks else env.reward_features), env.obstacle_raster))
 
     @property
     def _graph_state(self):
@@ -443,17 +512,21 @@ class VecDQN:
         # n_steps independent batches = ONE draw of n_steps * B records: both sampling rules draw with replacement, so
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
         rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
-        block_f, binary, action_f, q_target, sf_target = self._targets(rec)
+        block_f, binary, action_f, q_target, sf_target, *maps = self._targets(rec)
+        maps = maps[0] if maps else None                     # per-env tasks: the reward map of every transition [n_steps * B, px]
         drv = self._train_step(n_steps)
-        out = drv.run(n_steps, block_f, action_f, binary, None, None, q_target, sf_target)
+        out = drv.run(n_steps, block_f, action_f, binary, maps, None, q_target, sf_target)
         if out is None:
             drv = None
-            reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1)
+            S = self.env.img
+            reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1) if maps is None else None
             obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1)
             self.policy_net.train()
             losses = []
             for i in range(n_steps):
                 sl = slice(i * B, (i + 1) * B)
+                if maps is not None:
+                    reward = maps[sl].reshape(B, 1, S, S)
                 q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
                 loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
                 self.opt.zero_grad()
@@ -523,7 +596,7 @@ class VecDQN:
         arrived.synchronize()                           # passed already unless the rows came out of the env's cache
         n_valid, n_done = int(self._counts_host[0]), int(self._counts_host[1])
         self.env_steps += n_valid
-        allrec = D.all_gather_records(rec, valid, n_valid=n_valid)
+        allrec = D.all_gather_records(self.with_task(rec), valid, n_valid=n_valid)
         self.ring.push(allrec)
         if not D.active():
             self.episodes_done += n_done
@@ -581,7 +654,12 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
     geoms = [load_urdf(f"shapes/{n}.urdf") for n in names]
-    if args.get('tower_height'):
+    random_targets = args.get('random_targets')
+    if random_targets:
+        # tower_setup(num_targets=T) per env and episode (gym_env.py:64-79 of the reference): no obstacles, every env draws
+        # its own targets whenever it starts an episode
+        targets, obstacles = RandomTargets(random_targets), []
+    elif args.get('tower_height'):
         H, N = 0.8, args['tower_height']
         targets = [(0.5, 0, N * H + H / 2)]
         obstacles = [(0.5, 0., i * H + H / 2) for i in range(N)]
@@ -600,14 +678,17 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     capacity = max(args['replay_buffer_capacity'], 4 * args['num_envs'] * world)
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
-                   stable_actions_only=args.get('stable_actions_only', False), episode_stats=True)
+                   stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
+                   per_env_tasks=bool(random_targets))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
-    # training task every --evaluate_every finished episodes
+    # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
+    # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
     eval_envs = args.get('eval_envs', EVAL_DEFAULTS['eval_envs'])
     eval_epsilon = args.get('eval_epsilon', EVAL_DEFAULTS['eval_epsilon'])
     eval_env = None
     if eval_envs > 0 and rank == 0:
-        eval_env = VecAssemblyGym(eval_envs, geoms, obstacles, targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
+        eval_targets = RandomTargets(random_targets) if random_targets else targets
+        eval_env = VecAssemblyGym(eval_envs, geoms, obstacles, eval_targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
                                   device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net),
                                   img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
     history, t0, it = [], time.time(), 0

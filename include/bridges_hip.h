@@ -329,10 +329,20 @@ int bridges_bits_accumulate(int32_t n_rows, const uint64_t* bits, const int64_t*
  * the 256 CUs evenly; the ranges' sums go to part [splits, n] and are added in a fixed order: no atomics, deterministic). */
 int bridges_head_sigmoid_dot(int32_t n_rows, int32_t K, int32_t N, const float* h, int64_t h_stride, const float* Wd,
                              const float* bd, const float* w, float* out, float* part, int32_t splits, void* stream);
+/* The same head with one map PER TASK (per-env tasks: every env owns a reward map): w_all [n_maps, N] row-major, w_row [n_rows]
+ * int32 = the map of row r (its env), out[r] = sum_j w_all[w_row[r]][j] * sigmoid(...).  n_maps * N < 2^31; the entries of
+ * w_row must lie in [0, n_maps) (not checked on the device).  Same kernel, products, split scheme and summation order: with
+ * every w_row naming one map the result equals bridges_head_sigmoid_dot on that map bit for bit. */
+int bridges_head_sigmoid_dot_rows(int32_t n_rows, int32_t K, int32_t N, const float* h, int64_t h_stride, const float* Wd,
+                                  const float* bd, const float* w_all, const int32_t* w_row, int32_t n_maps, float* out, float* part,
+                                  int32_t splits, void* stream);
 /* out[r] = sum_j w[j] * sigmoid(d[r * row_stride + j]), j < k: the q head of SuccessorMLP's factored forward
  * (q = sum(softmax(psi)[:, 1] * reward_map), cv.py:101-104, with psi1 - psi0 = d) in one pass.  k % 4 == 0. */
 int bridges_sigmoid_dot(int32_t n_rows, const float* d, int64_t row_stride, const float* w, int32_t k, float* out,
                         void* stream);
+/* out[r] = sum_j w_all[w_row[r]][j] * sigmoid(d[r * row_stride + j]): w_all [*, k] row-major, w_row [n_rows] int32. */
+int bridges_sigmoid_dot_rows(int32_t n_rows, const float* d, int64_t row_stride, const float* w_all, const int32_t* w_row, int32_t k,
+                             float* out, void* stream);
 /* K2+K3: is_stable_rbe (stability.py:49-71) for n independent assemblies given as
  * padded block lists.  verts [n,K,6,2], shape_id [n,K], n_blocks [n], fixed_mask [n] (bit b = block b
  * is_static)
@@ -365,6 +375,12 @@ int bridges_shapes_free(bridges_shape* dev);
  * the envs of a group share their representative's rows (bridges_valid_rows with rep).  K = block slots per env (<= 64). */
 int bridges_env_groups(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
                        const uint8_t* blk_occ, const uint8_t* flag, uint64_t* hkey, int32_t* rep, void* stream);
+/* The same with n_extra further 64-bit words per env as part of its identity (extra [E, n_extra]; NULL / 0 = none, which is
+ * what bridges_env_groups passes): folded into the hash and compared word for word.  Per-env tasks pass the bit patterns of
+ * env_targets[e] (3 T words): what a network is asked about a state then depends on (state, task). */
+int bridges_env_groups_keyed(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
+                             const uint8_t* blk_occ, const uint8_t* flag, const uint64_t* extra, int32_t n_extra, uint64_t* hkey,
+                             int32_t* rep, void* stream);
 
 /* The rows a Q-network is fed (filter_actions, actions.py:71-82, for every env at once): compact indices of the candidates
  * with cand_mask != 0, env-major in candidate order, their owning env, and seg[e] .. seg[e + 1] = the rows of env e
@@ -528,6 +544,15 @@ int bridges_mlp_input(int32_t batch, int32_t rows, int32_t px, int32_t nf, const
 int bridges_mlp_input_batches(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
                               const float* action_all, const float* binary_all, const float* reward, const float* obstacle,
                               float* x_all, void* stream);
+/* Both with a reward map PER TRANSITION (replay of per-env tasks): reward_stride = 0 is the one map [px] of the entry points
+ * above (which forward here), reward_stride = px makes reward [n, px] and transition row *counter * batch + b read its own row;
+ * any other stride is refused.  The obstacle map stays shared. */
+int bridges_mlp_input_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, const int64_t* counter, const float* block_all,
+                           const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                           const float* obstacle, float* x, void* stream);
+int bridges_mlp_input_batches_rows(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
+                                   const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                                   const float* obstacle, float* x_all, void* stream);
 /* Head + loss + its gradient (cv.py:104-108; successor_dqn.py:215-232): y [rows, 2 px + 2 nf] = (psi0 | psi1 | binary),
  * q = sum_j softmax(psi)[1][j] * reward[j], loss = [use_q] mean (q - q_target)^2 + [use_sf] mean (psi0 - sf_target)^2
  * with the targets of batch *counter (q_target_all [n], sf_target_all [n,px]).  Writes dy [rows, 2 px + 2 nf],
@@ -537,6 +562,11 @@ int bridges_successor_loss(int32_t batch, int32_t rows, int32_t px, int32_t nf, 
                            const int64_t* counter, const float* q_target_all, const float* sf_target_all, int32_t use_q,
                            int32_t use_sf, float* dy, float* loss_rows, float* q_out, float* losses, int32_t n_losses,
                            int64_t* counter_inc, int32_t* ticket, float* adam_step, void* stream);
+/* The same with reward_stride as in bridges_mlp_input_rows: q of transition row src is weighed with reward[src * reward_stride + j]. */
+int bridges_successor_loss_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* y, const float* reward,
+                                int64_t reward_stride, const int64_t* counter, const float* q_target_all, const float* sf_target_all,
+                                int32_t use_q, int32_t use_sf, float* dy, float* loss_rows, float* q_out, float* losses,
+                                int32_t n_losses, int64_t* counter_inc, int32_t* ticket, float* adam_step, void* stream);
 /* `ticket` (device int32, zero before the first call; may be NULL): the logging (losses[*counter_inc] = sum of loss_rows,
  * ++*counter_inc, and ++*adam_step if given) is done inside the loss kernel by the row workgroup that arrives last
  * instead of a second launch; the kernel re-arms the ticket.

@@ -12,7 +12,7 @@ import torch
 from robotoddler.training.successor_dqn import build_parser, make_nets
 from robotoddler.training.vec_dqn import VecDQN
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import VecAssemblyGym
+from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=1024)
@@ -27,21 +27,25 @@ ap.add_argument("--model", default="SuccessorMLP")
 ap.add_argument("--stable_actions_only", action="store_true", help="every action set restricted to the stable placements")
 ap.add_argument("--eval_envs", type=int, default=0, help="> 0: greedy evaluation over this many envs at the end of every block")
 ap.add_argument("--eval_epsilon", type=float, default=0.0, help="exploration rate of the evaluation episodes")
+ap.add_argument("--random_targets", type=int, default=0, metavar="T",
+                help="> 0: per-env random tasks instead of the tower (tower_setup(num_targets=T) per env and episode, no obstacles; "
+                     "SuccessorMLP only); --eval_envs then evaluates on a fixed held-out set of N tasks")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 args = vars(build_parser().parse_args(["--model", a.model, "--loss_function", a.loss]))
 H = 0.8
 torch.manual_seed(0)
 pol, tgt = make_nets(args, dev)
-env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(a.tower)],
-                     [(0.5, 0, a.tower * H + H / 2)], max_steps=a.max_steps, seed=0, device=dev,
+obstacles, targets = [(0.5, 0., i * H + H / 2) for i in range(a.tower)], (lambda: [(0.5, 0, a.tower * H + H / 2)])
+if a.random_targets:
+    obstacles, targets = [], (lambda: RandomTargets(a.random_targets))
+env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, targets(), max_steps=a.max_steps, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
-               eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True)
+               eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets))
 eval_env = None
 if a.eval_envs > 0:
-    eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(a.tower)],
-                              [(0.5, 0, a.tower * H + H / 2)], max_steps=a.max_steps, seed=1, device=dev,
+    eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, targets(), max_steps=a.max_steps, seed=1, device=dev,
                               f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
 r4 = lambda v: None if v is None else round(v, 4)
 t0 = time.time()

@@ -8,7 +8,7 @@ import torch
 from robotoddler.training.successor_dqn import build_parser, make_nets
 from robotoddler.training.vec_dqn import VecDQN
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import VecAssemblyGym
+from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
@@ -30,7 +30,14 @@ ap.add_argument("--bridge_length", type=int, default=0, help="> 0: horizontal_br
 ap.add_argument("--stable_actions_only", action="store_true", help="every action set restricted to the stable placements")
 ap.add_argument("--episode_stats", action="store_true",
                 help="per-episode statistics on (one bridges_episode_stats launch per lock-step, read one lock-step late)")
+ap.add_argument("--random_targets", type=int, default=0, metavar="T",
+                help="> 0: per-env random tasks (tower_setup(num_targets=T) per env and episode, no obstacles; VecDQN(per_env_tasks=True))")
+ap.add_argument("--fixed_targets", type=int, default=0, metavar="T",
+                help="> 0: the fixed-task counterpart of --random_targets T: T targets shared by every env (T = 3: fixed3 of "
+                     "tools/random_task_throughput.py), no obstacles")
 a = ap.parse_args()
+if a.random_targets and a.fixed_targets:
+    ap.error("--random_targets and --fixed_targets are two legs of one comparison: give one")
 dev = torch.device("cuda:0")
 if a.miopen_search:
     torch.backends.cudnn.benchmark = True
@@ -41,7 +48,17 @@ pol, tgt = make_nets(args, dev)
 if a.channels_last:
     pol, tgt = pol.to(memory_format=torch.channels_last), tgt.to(memory_format=torch.channels_last)
 names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[a.shapes]
-if a.bridge_length:
+if a.random_targets:
+    obstacles, targets = [], RandomTargets(a.random_targets)
+elif a.fixed_targets:
+    import numpy as np
+    # the three shared targets tools/random_task_throughput.py calls fixed3; beyond three: one draw of tower_setup's
+    # distribution (x ~ U[-4, 4], z ~ U[0, 4], y = 0)
+    rng = np.random.default_rng(0)
+    fixed3 = [(0.5, 0.0, 1.2), (-1.5, 0.0, 2.6), (2.5, 0.0, 0.4)]
+    obstacles = []
+    targets = (fixed3 + [(float(rng.uniform(-4, 4)), 0.0, float(rng.uniform(0, 4))) for _ in range(a.fixed_targets - 3)])[:a.fixed_targets]
+elif a.bridge_length:
     sq, nn = 0.6, a.bridge_length
     obstacles, targets = [(i * sq, 0.0, sq / 2) for i in range(1, nn + 1)], [(nn * sq + 2.5 * sq, 0.0, sq / 2)]
 else:
@@ -51,7 +68,7 @@ env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obs
                      stable_actions_only=a.stable_actions_only)
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
-               episode_stats=a.episode_stats)
+               episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -93,7 +110,7 @@ for _ in range(n_phase):
     torch.cuda.synchronize(); t1 = time.perf_counter()
     rec, valid = agent.act()
     agent.env_steps += int(valid.sum().item())
-    agent.ring.push(rec[valid])
+    agent.ring.push(agent.with_task(rec)[valid])
     torch.cuda.synchronize(); t2 = time.perf_counter()
     agent.train_steps(a.train_steps)
     agent.update_target()

@@ -170,10 +170,22 @@ TASK_BUFFER_FIELDS = [
 ]
 
 
+# the device buffers of per-env obstacles (shape expression in E, O): env_obstacle_bits sits in the slot the header reserved for
+# it, env_obstacles at the end of the struct
+MAX_OBSTACLES = 4
+OBSTACLE_BUFFER_FIELDS = [
+    ("env_obstacles", "float64", "E,O,3"),
+    ("env_obstacle_bits", "int64", "E,64"),    # uint64 on the device
+]
+
+
 class TaskBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _, _ in TASK_BUFFER_FIELDS] + [
         ("env_obstacle_bits", C.c_void_p), ("gauss_k", C.c_void_p), ("target_shape", C.c_int32), ("sample", C.c_int32),
-        ("x_range", C.c_double * 2), ("z_range", C.c_double * 2)]
+        ("x_range", C.c_double * 2), ("z_range", C.c_double * 2),
+        # per-env obstacles: appended, so the fields above keep their offsets
+        ("env_obstacles", C.c_void_p), ("n_obstacles", C.c_int32), ("sample_obstacles", C.c_int32),
+        ("obs_x_range", (C.c_double * 2) * MAX_OBSTACLES), ("obs_z_range", (C.c_double * 2) * MAX_OBSTACLES)]
 
 
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)

@@ -126,17 +126,40 @@ class RandomTargets:
             raise ValueError("empty x_range / z_range")
 
 
+class RandomObstacles:
+    """``obstacles=RandomObstacles(ranges=[((x0, x1), (z0, z1)), ...])``: every env draws one obstacle per range pair whenever it
+    starts an episode, as the reference's connecting_setup draws its obstacle with its targets per env.reset(**setup_fct())
+    (assembly_gym/envs/gym_env.py:91-99): obstacle o has x ~ U[x0, x1), z ~ U[z0, z1) of ITS pair, y = 0.  The draw happens on the
+    device on the episode counter the targets use, keyed by (seed, global env id, episode, obstacle, axis), a stream of its own;
+    its formula is in include/bridges_hip.h (bridges_env_set_task_buffers)."""
+
+    def __init__(self, ranges):
+        self.ranges = [((float(xr[0]), float(xr[1])), (float(zr[0]), float(zr[1]))) for xr, zr in ranges]
+        if not 1 <= len(self.ranges) <= abi.MAX_OBSTACLES:
+            raise ValueError(f"RandomObstacles takes 1..{abi.MAX_OBSTACLES} range pairs, one per obstacle")
+        for xr, zr in self.ranges:
+            if xr[0] > xr[1] or zr[0] > zr[1]:
+                raise ValueError("empty x range / z range")
+
+    @property
+    def num_obstacles(self):
+        return len(self.ranges)
+
+
 def _is_per_env_targets(targets):
     return isinstance(targets, (torch.Tensor, np.ndarray)) and targets.ndim == 3
 
 
-def _single_task_attribute(name, per_env_name):
-    """An attribute that describes THE task of a fixed-task env.  An env with per-env tasks has no such thing: reading it
-    raises instead of handing one env's map to every row."""
+_is_per_env_obstacles = _is_per_env_targets          # an [E, O, 3] array, as the targets' [E, T, 3]
+
+
+def _single_task_attribute(name, per_env_name, flag="per_env_tasks"):
+    """An attribute that describes THE task of a fixed-task env.  An env with per-env tasks (``flag``: the part of the task
+    the attribute belongs to) has no such thing: reading it raises instead of handing one env's map to every row."""
     key = "_single_task_" + name
 
     def get(self):
-        if getattr(self, "per_env_tasks", False):
+        if getattr(self, flag, False):
             raise abi.BridgesHipError(f"this env has per-env tasks: there is no single `{name}`; read `{per_env_name}` "
                                       "(one entry per env)")
         return self.__dict__[key]
@@ -150,11 +173,17 @@ class VecAssemblyGym:
     """``targets``: a list of (x, y, z) all envs share (the fixed task); a float64 array / tensor [E, T, 3] of per-env targets
     that stay until set_targets() replaces them; or RandomTargets(): per-env targets redrawn on the device every episode.
     Per-env tasks add env_targets [E,T,3], target_bits [E,64], reward_maps [E,64,64] (reward_maps_img: its [E,S,S] corner),
-    reward_prefix [E,64,65] and task_episode [E]: 49 KiB per env."""
+    reward_prefix [E,64,65] and task_episode [E]: 49 KiB per env.
+    ``obstacles``: a list of (x, y, z) all envs share; a float64 array / tensor [E, O, 3] of per-env obstacles that stay until
+    set_obstacles() replaces them; or RandomObstacles(ranges): per-env obstacles redrawn on the device every episode, on the
+    episode counter of the targets.  Per-env obstacles (``per_env_obstacles``) ride on the per-env task buffers -- with one
+    shared target list the targets are replicated into env_targets -- and add env_obstacles [E,O,3], env_obstacle_bits [E,64]
+    and obstacle_rasters ([E,S,S] f32, expanded from the bits when read); the candidate filter tests env e against its own."""
 
     reward_map = _single_task_attribute("reward_map", "reward_maps")
     reward_features = _single_task_attribute("reward_features", "reward_maps_img")
     _reward_obstacle_flat = _single_task_attribute("_reward_obstacle_flat", "reward_maps_img")
+    obstacle_raster = _single_task_attribute("obstacle_raster", "obstacle_rasters", flag="per_env_obstacles")
 
     def __init__(self, num_envs, shapes, obstacles, targets, max_steps=None, mu=0.8, density=1.0, bounds=None,
                  xlim=(-3.0, 7.0), ylim=(0.0, 10.0), x_discr_ground=None, offset_values=(0.0,), seed=0,
@@ -169,10 +198,21 @@ class VecAssemblyGym:
         self.shapes = [s if isinstance(s, ShapeGeometry) else s.geometry for s in shapes]
         self.shape_target_faces = [list(getattr(s, "target_faces_2d", range(g.num_faces_2d)))
                                    for s, g in zip(shapes, self.shapes)]
-        self.obstacles = [tuple(float(v) for v in o) for o in obstacles]
         self.per_env_tasks = False                   # set by _attach_task_buffers
         self.task_buf = None
         self.random_targets = None
+        self.per_env_obstacles = False               # set by _init_obstacles
+        self.obstacle_buf = None
+        self.random_obstacles = None
+        if isinstance(obstacles, RandomObstacles):
+            self.obstacles, self.n_obstacles = [], obstacles.num_obstacles
+        elif _is_per_env_obstacles(obstacles):
+            if tuple(obstacles.shape[::2]) != (int(num_envs), 3) or not 1 <= obstacles.shape[1] <= abi.MAX_OBSTACLES:
+                raise ValueError(f"per-env obstacles must be [num_envs, 1..{abi.MAX_OBSTACLES}, 3], got {tuple(obstacles.shape)}")
+            self.obstacles, self.n_obstacles = [], int(obstacles.shape[1])
+        else:
+            self.obstacles = [tuple(float(v) for v in o) for o in obstacles]
+            self.n_obstacles = 0                     # per-env obstacles of one env; a shared list is not counted here
         if isinstance(targets, RandomTargets):
             self.targets, self.n_targets = None, targets.num_targets
         elif _is_per_env_targets(targets):
@@ -218,11 +258,15 @@ class VecAssemblyGym:
         self._alloc()
         self._task_features()
         self._create()
+        if self.n_obstacles:
+            self._init_obstacles(obstacles)
         if isinstance(targets, RandomTargets):
             self._attach_task_buffers(targets)
             self.reset()
         elif self.targets is None:
             self.set_targets(targets)
+        elif self.per_env_obstacles:
+            self.set_targets(self._replicated_targets())     # one target list under per-env obstacles: every env holds a copy
         else:
             self.reset()
 
@@ -371,7 +415,15 @@ class VecAssemblyGym:
         tb = abi.TaskBuffers()
         for name, _, _ in abi.TASK_BUFFER_FIELDS:
             setattr(tb, name, self.task_buf[name].data_ptr())
-        tb.env_obstacle_bits = None
+        if self.per_env_obstacles:
+            ob, so = self.obstacle_buf, self.random_obstacles
+            tb.env_obstacle_bits, tb.env_obstacles = ob["env_obstacle_bits"].data_ptr(), ob["env_obstacles"].data_ptr()
+            tb.n_obstacles, tb.sample_obstacles = self.n_obstacles, 1 if so is not None else 0
+            for o, (xr, zr) in enumerate(so.ranges if so is not None else []):
+                tb.obs_x_range[o][0], tb.obs_x_range[o][1] = xr
+                tb.obs_z_range[o][0], tb.obs_z_range[o][1] = zr
+        else:
+            tb.env_obstacle_bits = None                      # obstacles stay the shared raster (n_obstacles = 0)
         tb.gauss_k = self._gauss_k.data_ptr()
         tb.target_shape = len(self.table_geoms) - 1          # cube06 (gym_env.py:277)
         tb.sample = 1 if sampler is not None else 0
@@ -413,6 +465,76 @@ class VecAssemblyGym:
         if targets.numel() != self.env_targets.numel() or targets.dtype != torch.float64:
             raise ValueError(f"targets must hold {tuple(self.env_targets.shape)} float64 values, got {tuple(targets.shape)} {targets.dtype}")
         self.env_targets.copy_(targets.reshape(self.env_targets.shape))
+        abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
+
+    # ------------------------------------------------------------------ per-env obstacles
+    def _replicated_targets(self):
+        return torch.tensor(self.targets, dtype=torch.float64).reshape(1, self.n_targets, 3).expand(self.E, -1, -1).contiguous()
+
+    def _init_obstacles(self, obstacles):
+        """Allocate (once) the per-env obstacle buffers; ``obstacles``: a RandomObstacles (the sampler) or an [E, O, 3] array
+        (explicit obstacles, a sampler is switched off).  The next _attach_task_buffers hands them to the library."""
+        sampler = obstacles if isinstance(obstacles, RandomObstacles) else None
+        if sampler is not None:
+            O = sampler.num_obstacles
+        else:
+            obstacles = torch.as_tensor(obstacles, dtype=torch.float64)
+            if obstacles.ndim != 3 or tuple(obstacles.shape[::2]) != (self.E, 3) or not 1 <= obstacles.shape[1] <= abi.MAX_OBSTACLES:
+                raise ValueError(f"obstacles must be [{self.E}, 1..{abi.MAX_OBSTACLES}, 3], got {tuple(obstacles.shape)}")
+            O = int(obstacles.shape[1])
+        if self.obstacle_buf is None:
+            if self.n_targets < 1:
+                raise ValueError("per-env obstacles ride on the per-env task buffers, which need at least one target per env")
+            dims = dict(E=self.E, O=O)
+            self.obstacle_buf = {name: torch.zeros(tuple(dims[d] if d in dims else int(d) for d in shape.split(",")),
+                                                   dtype=getattr(torch, dt), device=self.device)
+                                 for name, dt, shape in abi.OBSTACLE_BUFFER_FIELDS}
+            self.n_obstacles = O
+            self.env_obstacles, self.env_obstacle_bits = self.obstacle_buf["env_obstacles"], self.obstacle_buf["env_obstacle_bits"]
+        elif O != self.n_obstacles:
+            raise ValueError(f"the env was built for {self.n_obstacles} obstacles per env, got {O}")
+        if sampler is None:
+            self.env_obstacles.copy_(obstacles.to(self.device))
+        self.random_obstacles = sampler
+        self.per_env_obstacles = True
+        self.obstacles = []                                  # there is no shared list any more (obstacle_bits is not read)
+
+    @property
+    def obstacle_rasters(self):
+        """[E, S, S] float32: every env's obstacle raster, expanded from env_obstacle_bits when read."""
+        if not self.per_env_obstacles:
+            raise abi.BridgesHipError("this env has one shared obstacle list: read `obstacle_raster`")
+        img = torch.empty((self.E, 64, 64), dtype=torch.float32, device=self.device)
+        abi.check(self.L.bridges_bits_to_f32(self.E, _ptr(self.env_obstacle_bits), _ptr(img), _stream()), "bridges_bits_to_f32")
+        return self.crop(img)
+
+    def set_obstacles(self, obstacles, reset=True):
+        """Explicit per-env obstacles ([E, O, 3] float64, O = the env's number of per-env obstacles; an env with a shared list
+        becomes a per-env one) that stay until set again; an obstacle sampler is switched off, the targets (and their sampler)
+        stay.  reset=True starts every env anew (reset()); reset=False keeps the states and only rebuilds the obstacle rasters
+        and the candidates' masks.  No host wait."""
+        self._init_obstacles(obstacles)
+        if self.per_env_tasks:
+            self._attach_task_buffers(self.random_targets)
+        else:
+            t = self._replicated_targets()
+            self._attach_task_buffers(None)
+            self.env_targets.copy_(t)
+        if reset:
+            self.reset()
+        else:
+            abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
+            self.refresh()
+
+    def load_obstacles(self, obstacles):
+        """Per-env obstacles ([E, O, 3] or [E, 3 O] float64, already on the device) for a scratch env whose states are about to
+        be loaded or refreshed: env_obstacles and env_obstacle_bits (bridges_env_load_targets, which rebuilds the target tables
+        beside them) and nothing else; task_episode and the states stay.  One copy, one launch, no host wait."""
+        if not self.per_env_obstacles or self.random_obstacles is not None:
+            raise ValueError("load_obstacles needs an env with explicit per-env obstacles (created with an [E, O, 3] array / set_obstacles)")
+        if obstacles.numel() != self.env_obstacles.numel() or obstacles.dtype != torch.float64:
+            raise ValueError(f"obstacles must hold {tuple(self.env_obstacles.shape)} float64 values, got {tuple(obstacles.shape)} {obstacles.dtype}")
+        self.env_obstacles.copy_(obstacles.reshape(self.env_obstacles.shape))
         abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
 
     # ------------------------------------------------------------------ lock-step API
@@ -581,7 +703,8 @@ class VecAssemblyGym:
         same candidates in the same order, so valid_rows(rep) lets them share one set of rows.
         ``task=True`` (an env with per-env tasks): the bit patterns of the env's own targets, env_targets[e], are part of its
         identity as well (bridges_env_groups_keyed) -- what a network says about a state depends on the task it is asked
-        under, so only envs in the same state AND under the same task share rows."""
+        under, so only envs in the same state AND under the same task share rows.  Per-env obstacles are part of the task: the
+        bit patterns of env_obstacles[e] follow the targets' in the key."""
         hkey = getattr(self, "_hkey", None)
         if hkey is None:
             hkey = self._hkey = torch.empty(self.E, dtype=torch.int64, device=self.device)
@@ -593,6 +716,8 @@ class VecAssemblyGym:
             if not self.per_env_tasks:
                 raise ValueError("state_groups(task=True) needs an env with per-env tasks (targets=RandomTargets() / set_targets)")
             key = self.env_targets
+            if self.per_env_obstacles:
+                key = torch.cat([key.reshape(self.E, -1), self.env_obstacles.reshape(self.E, -1)], dim=1).contiguous()
             assert key.dtype == torch.float64 and key.is_contiguous() and key.shape[0] == self.E
             abi.check(self.L.bridges_env_groups_keyed(self.E, self.K, _ptr(b["n_blocks"]), _ptr(b["blk_shape"]), _ptr(b["blk_pose"]),
                                                       _ptr(b["blk_occ"]), _ptr(flag), _ptr(key), key.numel() // self.E, _ptr(hkey),
@@ -682,9 +807,12 @@ class VecAssemblyGymGroups:
         self.envs, self.streams, start = [], [], int(env_id_base)
         # `targets` (VecAssemblyGym's argument after num_envs, shapes, obstacles): a list or RandomTargets() goes to every group as
         # it is (the draw is keyed by the global env id); a per-env array [E, T, 3] is cut into the groups' slices
+        # `obstacles` (the argument before it) likewise: a list or RandomObstacles() as it is, an [E, O, 3] array in slices
         args, lo = list(args), 0
         positional = "targets" not in kw
         targets = args[2] if positional else kw.pop("targets")
+        obst_positional = "obstacles" not in kw
+        obstacles = args[1] if obst_positional else kw.pop("obstacles")
         for n in sizes:
             st = torch.cuda.Stream(device=self.device)
             tg = targets[lo:lo + n] if _is_per_env_targets(targets) else targets
@@ -692,6 +820,11 @@ class VecAssemblyGymGroups:
                 args[2] = tg
             else:
                 kw["targets"] = tg
+            ob = obstacles[lo:lo + n] if _is_per_env_obstacles(obstacles) else obstacles
+            if obst_positional:
+                args[1] = ob
+            else:
+                kw["obstacles"] = ob
             with torch.cuda.stream(st):
                 self.envs.append(VecAssemblyGym(n, *args, device=device, env_id_base=start, **kw))
             self.streams.append(st)
@@ -737,6 +870,16 @@ class VecAssemblyGymGroups:
         for env, st in zip(self.envs, self.streams):
             with torch.cuda.stream(st):
                 env.set_targets(targets[lo:lo + env.E], reset=reset)
+            lo += env.E
+
+    def set_obstacles(self, obstacles, reset=True):
+        """VecAssemblyGym.set_obstacles for all E envs ([E, O, 3]): every group takes its slice, on its own stream."""
+        if int(obstacles.shape[0]) != self.E:
+            raise ValueError(f"obstacles must hold {self.E} envs, got {tuple(obstacles.shape)}")
+        lo = 0
+        for env, st in zip(self.envs, self.streams):
+            with torch.cuda.stream(st):
+                env.set_obstacles(obstacles[lo:lo + env.E], reset=reset)
             lo += env.E
 
     def lockstep_random(self):

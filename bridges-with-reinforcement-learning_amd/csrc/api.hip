@@ -298,8 +298,12 @@ static int refresh(bridges_env* env, hipStream_t s, int after_step) {
     if (!env->has_tasks) {
         if (int rc = launch("k_raster", env->max_faces <= 4 ? k_raster<4> : k_raster<MAXV>, dim3((unsigned)rblocks), dim3(256), 0, s, c))
             return rc;
-    } else if (int rc = launch("k_raster (per-env tables)", env->max_faces <= 4 ? k_raster<4, true> : k_raster<MAXV, true>,
-                               dim3((unsigned)rblocks), dim3(256), 0, s, c)) {
+    } else if (env->tasks.n_obstacles == 0) {
+        if (int rc = launch("k_raster (per-env tables)", env->max_faces <= 4 ? k_raster<4, true> : k_raster<MAXV, true>,
+                            dim3((unsigned)rblocks), dim3(256), 0, s, c))
+            return rc;
+    } else if (int rc = launch("k_raster (per-env tables and obstacles)", env->max_faces <= 4 ? k_raster<4, true, const uint64_t*> : k_raster<MAXV, true, const uint64_t*>,
+                               dim3((unsigned)rblocks), dim3(256), 0, s, c, (const uint64_t*)env->tasks.env_obstacle_bits)) {
         return rc;
     }
     if (timed) { HIP_TRY(hipEventRecord(env->ev_stop[env->ev_used], s)); env->ev_used++; }
@@ -330,8 +334,8 @@ int bridges_env_step(bridges_env* env, void* stream) {
         if (int rc = launch("k_step (per-env targets)", k_step<const double*>, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx,
                             (const double*)env->tasks.env_targets))
             return rc;
-        // the envs k_step has just reset begin an episode: next task (fixed per-env targets: nothing to do)
-        if (env->tasks.sample)
+        // the envs k_step has just reset begin an episode: next task (fixed per-env targets and obstacles: nothing to do)
+        if (env->tasks.sample || env->tasks.sample_obstacles)
             if (int rc = task_features(env, stream, TASK_STEP)) return rc;
     }
     return refresh(env, (hipStream_t)stream, 1);
@@ -349,7 +353,17 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
     }
     if (!tb->env_targets || !tb->target_bits || !tb->reward_map || !tb->reward_prefix || !tb->task_episode || !tb->gauss_k)
         return fail_arg("task buffers: env_targets / target_bits / reward_map / reward_prefix / task_episode / gauss_k not given");
-    if (tb->env_obstacle_bits) return fail_arg("task buffers: env_obstacle_bits is reserved (obstacles are shared by all envs)");
+    if (tb->n_obstacles < 0 || tb->n_obstacles > BRIDGES_MAX_OBSTACLES) return fail_arg("task buffers: n_obstacles must be 0..BRIDGES_MAX_OBSTACLES");
+    if (tb->env_obstacle_bits && tb->n_obstacles == 0) return fail_arg("task buffers: env_obstacle_bits given but n_obstacles is 0");
+    if (tb->n_obstacles > 0 && !tb->env_obstacle_bits) return fail_arg("task buffers: n_obstacles > 0 but env_obstacle_bits not given");
+    if (tb->n_obstacles > 0 && !tb->env_obstacles) return fail_arg("task buffers: n_obstacles > 0 but env_obstacles not given");
+    if (tb->n_obstacles == 0 && tb->env_obstacles) return fail_arg("task buffers: env_obstacles given but n_obstacles is 0");
+    if (tb->sample_obstacles != 0 && tb->sample_obstacles != 1) return fail_arg("task buffers: sample_obstacles must be 0 or 1");
+    if (tb->sample_obstacles && tb->n_obstacles == 0) return fail_arg("task buffers: sample_obstacles needs n_obstacles > 0");
+    if (tb->sample_obstacles)
+        for (int o = 0; o < tb->n_obstacles; ++o)
+            if (!(tb->obs_x_range[o][0] <= tb->obs_x_range[o][1] && tb->obs_z_range[o][0] <= tb->obs_z_range[o][1]))
+                return fail_arg("task buffers: obs_x_range / obs_z_range");
     if (c.n_targets < 1) return fail_arg("task buffers: the task has no targets");
     if (tb->target_shape < 0 || tb->target_shape >= c.n_shapes) return fail_arg("task buffers: target_shape");
     if (tb->sample != 0 && tb->sample != 1) return fail_arg("task buffers: sample must be 0 or 1");

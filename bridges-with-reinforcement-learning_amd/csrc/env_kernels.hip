@@ -690,15 +690,25 @@ __device__ __forceinline__ uint64_t raster_outline(const double* v /*[6,2]*/, in
 // NF = 4 when every candidate shape of the task has at most 4 faces (64 VGPRs: 8 waves per SIMD), else MAXV.
 // PER_ENV: reward_prefix holds one [64][65] table per env (bridges_task_buffers); the owning env is wave-uniform, so the
 // table's base is scalar arithmetic.
-template <int NF, bool PER_ENV = false>
-__global__ __launch_bounds__(256) void k_raster(DevCtx c) {
+// k_raster<NF, true, const uint64_t*>(DevCtx, env_obstacle_bits): per-env obstacles (bridges_task_buffers.env_obstacle_bits,
+// [E][64]): the obstacle rows are read per work item beside the state's, from env_obst[e * 64 + lane] (e is wave-uniform: a
+// scalar base again), instead of once per wave from the shared raster.  The source is a compile-time choice, made as k_step
+// makes its own: the optional trailing argument leaves the two instantiations without per-env obstacles their argument list,
+// their hoisted load and their code (compared with the previous build's assembly in docs/MEASUREMENT_LOG.md).
+__device__ __forceinline__ const uint64_t* raster_env_obst() { return nullptr; }
+__device__ __forceinline__ const uint64_t* raster_env_obst(const uint64_t* p) { return p; }
+template <int NF, bool PER_ENV = false, typename... ENV_OBST_ARG>
+__global__ __launch_bounds__(256) void k_raster(DevCtx c, ENV_OBST_ARG... env_obst_arg) {
+    constexpr bool ENV_OBST = sizeof...(ENV_OBST_ARG) == 1;
+    const uint64_t* env_obst = raster_env_obst(env_obst_arg...);
+    (void)env_obst;
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     const int nwaves = (gridDim.x * blockDim.x) / WAVE;
     const int total = c.b.cand_offset[c.E];
     const int items = total + (c.b.state_raster ? c.E : 0);
     const double X = c.tt->grid_x[lane], Y = c.tt->grid_y[lane];
-    const uint64_t obst = c.b.obstacle_bits[lane];
+    const uint64_t obst = ENV_OBST ? 0ull : c.b.obstacle_bits[lane];
     for (int itv = wave; itv < items; itv += nwaves) {
         const int it = __builtin_amdgcn_readfirstlane(itv);       // wave-uniform: metadata comes through scalar loads
         if (it < total) {
@@ -715,7 +725,7 @@ __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
                 const double2 a = p[0], b = p[1];
                 fr0 = a.x; fr1 = a.y; fr2 = b.x; fr3 = b.y;
             }
-            const uint64_t occ = c.b.state_bits[(size_t)e * IMG + lane] | obst;
+            const uint64_t occ = c.b.state_bits[(size_t)e * IMG + lane] | (ENV_OBST ? env_obst[(size_t)e * IMG + lane] : obst);
             const uint64_t bits = (NF == 4 || nv <= 4) ? raster_rows<4>(fr0, fr1, fr2, fr3, c.img, X, Y, lane)
                                                        : raster_rows6(fr0, fr1, fr2, fr3, c.img, X, Y, lane);
             const bool overlap = __ballot((bits & occ) != 0ull) != 0ull;
@@ -743,8 +753,10 @@ __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
 // get_task_features (robotoddler/training/successor_dqn.py:67-85), one workgroup per env.
 //   TASK_LOAD   every env: env_targets were written by the caller; rebuild the features
 //   TASK_RESET  every env: task_episode = 0; with the sampler on, draw the targets of episode 0 first
-//   TASK_STEP   after k_step, sampler on: only the envs k_step has just reset -- finished and auto-reset (F_DONE) or a
-//               reset-only lock-step (!F_VALID) -- take the next episode: task_episode += 1, new targets; the rest leave at once
+//   TASK_STEP   after k_step, a sampler on: only the envs k_step has just reset -- finished and auto-reset (F_DONE) or a
+//               reset-only lock-step (!F_VALID) -- take the next episode: task_episode += 1, new targets and / or new obstacles
+//               (whichever sampler is on; with the obstacle sampler alone the target tables are left as they are); the rest
+//               leave at once
 // The draw (header comment of bridges_env_set_task_buffers): counter-based, keyed by (seed, global env id, episode, target,
 // axis) through splitmix64 with a salt that separates it from the policy's stream (k_select).
 // The features restate bridges_hip.vec_env.VecAssemblyGym._task_features + gaussian_reward_map operation for operation, so a
@@ -763,6 +775,7 @@ __global__ __launch_bounds__(256) void k_raster(DevCtx c) {
 // as contiguous stores.
 enum { TASK_LOAD = 0, TASK_RESET = 1, TASK_STEP = 2 };
 #define TASK_SALT 0x7461736B5F726E67ull     // "task_rng"
+#define OBST_SALT 0x6F6273745F726E67ull     // "obst_rng"
 #define TASK_ROW (IMG + 1)
 #define TASK_WAVES 4
 #define TASK_THREADS (TASK_WAVES * WAVE)
@@ -793,6 +806,50 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
     if (mode == TASK_STEP) ep = t.task_episode[e] + 1u;
     __syncthreads();                                // every wave has read the episode before it is replaced
     if (mode != TASK_LOAD && tid == 0) t.task_episode[e] = ep;
+    const bridges_shape& cube = c.tt->shapes[t.target_shape];
+    const int nv = cube.nv;
+    // ---- per-env obstacles (n_obstacles > 0): lane 3 o + k of every wave holds coordinate k of obstacle o; drawn like the
+    // targets on a stream of its own (OBST_SALT) with one range pair per obstacle, rasterised exactly as the target blocks ----
+    const int O = t.n_obstacles;
+    if (O > 0 && (mode != TASK_STEP || t.sample_obstacles)) {     // fixed obstacles keep their raster over episode boundaries
+        double* og = t.env_obstacles + (size_t)e * O * 3;
+        double ov = 0.0;
+        if (lane < 3 * O) {
+            if (t.sample_obstacles && mode != TASK_LOAD) {
+                const int axis = lane % 3, o = lane / 3;
+                if (axis != 1) {
+                    const uint64_t h0 = splitmix64((((c.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(c.env_id_base + e)) ^ OBST_SALT);
+                    const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
+                    const uint64_t r = splitmix64(h1 ^ (uint64_t)lane);
+                    const double u = (double)(r >> 11) * 0x1.0p-53;
+                    double lo = 0.0, hi = 0.0;
+#pragma unroll
+                    for (int k = 0; k < BRIDGES_MAX_OBSTACLES; ++k)     // selects: the ranges are kernel arguments
+                        if (o == k) {
+                            lo = axis == 0 ? t.obs_x_range[k][0] : t.obs_z_range[k][0];
+                            hi = axis == 0 ? t.obs_x_range[k][1] : t.obs_z_range[k][1];
+                        }
+                    const double span = hi - lo;
+                    const double step = span * u;
+                    ov = lo + step;
+                }
+                if (wv == 0) og[lane] = ov;
+            } else {
+                ov = og[lane];
+            }
+        }
+        uint64_t obits = 0ull;
+        for (int q = 0; q < O; ++q) {
+            const double px = readlane_d(ov, 3 * q), pz = readlane_d(ov, 3 * q + 2);
+            __syncthreads();
+            if (lane < nv) { tv_l[wv][2 * lane] = px + cube.vx[lane]; tv_l[wv][2 * lane + 1] = pz + cube.vz[lane]; }
+            __syncthreads();
+            obits |= raster_outline(tv_l[wv], nv, cube.fa, cube.fb, c.tt->grid_x, c.tt->grid_y, S, lane);
+        }
+        if (wv == 0) t.env_obstacle_bits[(size_t)e * IMG + lane] = obits;
+        // obstacle sampler alone: the env begins an episode under its old targets -- target_bits, map and prefix stay
+        if (mode == TASK_STEP && !t.sample) return;
+    }
     // ---- targets: lane 3 q + k of every wave holds coordinate k of target q ----
     double tv = 0.0;
     if (lane < 3 * T) {
@@ -814,8 +871,6 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
         }
     }
     // ---- raster of the target blocks (every wave, on its own vertex scratch) ----
-    const bridges_shape& cube = c.tt->shapes[t.target_shape];
-    const int nv = cube.nv;
     uint64_t bits = 0ull;
     for (int q = 0; q < T; ++q) {
         const double px = readlane_d(tv, 3 * q), pz = readlane_d(tv, 3 * q + 2);

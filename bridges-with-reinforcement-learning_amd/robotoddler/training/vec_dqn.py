@@ -51,6 +51,10 @@ class VecDQN:
         and the optimiser step reads a map per transition.  Only the path that is hand-written from acting to Adam takes it:
         a SuccessorMLP on 64x64 images with the fused optimiser step."""
         self.per_env_tasks = bool(per_env_tasks)
+        if getattr(env, "per_env_obstacles", False):
+            raise ValueError("VecDQN cannot train on a rollout env with per-env obstacles (RandomObstacles / set_obstacles), with or "
+                             "without per_env_tasks=True: the first layer's image-independent part, the replay record and the "
+                             "captured train steps hold ONE obstacle raster")
         if getattr(env, "per_env_tasks", False) and not self.per_env_tasks:
             raise ValueError("VecDQN cannot train on a rollout env with per-env tasks (RandomTargets / set_targets) unless it is "
                              "built with per_env_tasks=True: by default envs in the same state share candidate rows whatever "

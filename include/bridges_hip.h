@@ -224,18 +224,27 @@ int bridges_env_rebuild_contacts(bridges_env* env, void* stream);
  * targets and everything derived from them; without them nothing changes (same launches, same buffers, same bits).
  * Caller-owned DEVICE buffers, E = n_envs, T = n_targets of the task (a task constant): */
 #define BRIDGES_GAUSS_TAPS 101  /* kernel_size of convolve_with_gaussian (successor_dqn.py:80-82) */
+#define BRIDGES_MAX_OBSTACLES 4 /* per-env obstacles of one env (bridges_task_buffers.n_obstacles) */
 typedef struct {
     double* env_targets;       /* [E,T,3] (x, y, z) of every env's targets; y is compared as the fixed task's is */
     uint64_t* target_bits;     /* [E,64] raster of the env's T cube06 target blocks (get_task_features, successor_dqn.py:73-79) */
     float* reward_map;         /* [E,64,64] its Gaussian blur: convolve_with_gaussian(raster, 101, 16) of the S x S image */
     double* reward_prefix;     /* [E,64,65] float64 row prefix sums of reward_map (bridges_env_buffers.reward_prefix, per env) */
     uint32_t* task_episode;    /* [E] episodes the env has started since bridges_env_reset (the first one is 0) */
-    const uint64_t* env_obstacle_bits;  /* reserved for per-env obstacles: must be NULL, no kernel reads it */
+    uint64_t* env_obstacle_bits;   /* [E,64] or NULL: raster of the env's O cube06 obstacle blocks, written by the library from
+                                      env_obstacles (per-env obstacles, below); NULL with n_obstacles = 0: obstacles stay shared */
     const float* gauss_k;      /* [BRIDGES_GAUSS_TAPS] the normalised float32 Gaussian vector k of the reference's kernel k k^T */
     int32_t target_shape;      /* shape id (in the task's shape table) of a target block: cube06 */
     int32_t sample;            /* 1: an env draws new targets on the device whenever it starts an episode; 0: env_targets stay */
     double x_range[2];         /* sampler: x ~ U[x_range), z ~ U[z_range), y = 0 (tower_setup: [-4, 4], [0, 4]) */
     double z_range[2];
+    /* --- per-env obstacles (connecting_setup draws targets AND obstacles per call, gym_env.py:91-99).  Appended: the fields
+     * above keep their offsets.  All-zero = obstacles stay bridges_env_buffers.obstacle_bits, one raster for all envs. --- */
+    double* env_obstacles;     /* [E,O,3] (x, y, z) of every env's obstacles, O = n_obstacles; NULL when n_obstacles = 0 */
+    int32_t n_obstacles;       /* O: 0 = obstacles stay shared, else 1..BRIDGES_MAX_OBSTACLES (env_obstacle_bits and env_obstacles given) */
+    int32_t sample_obstacles;  /* 1: an env draws new obstacles on the device whenever it starts an episode; 0: env_obstacles stay */
+    double obs_x_range[BRIDGES_MAX_OBSTACLES][2];   /* sampler, per obstacle o: x ~ U[obs_x_range[o]), z ~ U[obs_z_range[o]), y = 0 */
+    double obs_z_range[BRIDGES_MAX_OBSTACLES][2];
 } bridges_task_buffers;
 /* Attach (or replace) the per-env task buffers; NULL detaches them (the env is a fixed-task env again; call bridges_env_reset).
  * From here on the reached-test of bridges_env_step reads env_targets[e], the rasteriser takes cand_lin from reward_prefix[e],
@@ -248,9 +257,22 @@ typedef struct {
  *   h0 = splitmix64(((seed & 0xFFFFFFFF) << 32 | (uint32)gid) ^ 0x7461736B5F726E67)      ("task_rng")
  *   h1 = splitmix64(h0 ^ task_episode)
  *   r  = splitmix64(h1 ^ (3 * t + axis)),   u = (r >> 11) * 2^-53,   value = lo + ((hi - lo) * u)
- * for target t, axis 0 (x) and 2 (z), every operation rounded to binary64 separately; axis 1 (y) = 0. */
+ * for target t, axis 0 (x) and 2 (z), every operation rounded to binary64 separately; axis 1 (y) = 0.
+ * Per-env obstacles (n_obstacles = O > 0, env_obstacle_bits and env_obstacles given; one without the other is refused): every
+ * env owns O cube06 obstacle blocks.  The candidate filter of the rasteriser then tests env e's candidates against
+ * state_bits[e] | env_obstacle_bits[e] and bridges_env_buffers.obstacle_bits is not read; nothing else reads obstacles.
+ * env_obstacle_bits is rebuilt from env_obstacles wherever target_bits is rebuilt from env_targets; with sample_obstacles = 1
+ * the obstacles are drawn first, on the same task_episode counter (targets and obstacles of an episode change together; with
+ * sample = 0 and sample_obstacles = 1 a lock-step still advances task_episode for the envs that begin an episode and redraws
+ * their obstacles, their targets and maps stay).  The obstacle draw is a stream of its own:
+ *   h0 = splitmix64(((seed & 0xFFFFFFFF) << 32 | (uint32)gid) ^ 0x6F6273745F726E67)      ("obst_rng")
+ *   h1 = splitmix64(h0 ^ task_episode)
+ *   r  = splitmix64(h1 ^ (3 * o + axis)),   u = (r >> 11) * 2^-53,   value = lo + ((hi - lo) * u)
+ * for obstacle o with its own ranges obs_x_range[o] / obs_z_range[o], axis 0 (x) and 2 (z), every operation rounded to
+ * binary64 separately; axis 1 (y) = 0. */
 int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* tb);
-/* The host (or another kernel) has written env_targets: rebuild target_bits, reward_map and reward_prefix of every env.
+/* The host (or another kernel) has written env_targets: rebuild target_bits, reward_map and reward_prefix of every env -- and,
+ * with per-env obstacles attached, env_obstacle_bits from env_obstacles.
  * task_episode and the env states stay; the candidates' cand_lin is stale until bridges_env_reset / _refresh.  No host wait. */
 int bridges_env_load_targets(bridges_env* env, void* stream);
 

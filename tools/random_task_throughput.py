@@ -6,15 +6,20 @@ trapezoid, max_steps 15, uniform-random policy, f32 rasters) on three tasks --
   random3  RandomTargets(): three targets per env, redrawn on the device every episode (the per-env instantiations + k_task_features).
 fixed3 against random3 isolates the feature (same shapes, same max_steps).  Candidates per state differ between tasks, so read
 the time per lock-step together with the candidates per lock-step, not env-steps/s alone.  Prints one JSON line.
+--random_obstacles O adds (or, with --tasks, makes available) two more tasks on fixed3's targets --
+  obst_fixed   O fixed obstacles on the floor, shared by all envs (k_step / k_raster, the shared obstacle raster);
+  obst_random  RandomObstacles: O obstacles per env, x ~ U[-3, 3), z ~ U[0.3, 2.5), redrawn on the device every episode (per-env
+               k_step, k_task_features for the obstacle raster alone, k_raster reading env_obstacle_bits per work item).
 
   python tools/random_task_throughput.py [--envs 4096] [--groups 2] [--steps 100] [--warmup 20] [--tasks bridge,fixed3,random3]
+                                         [--random_obstacles O]
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import torch
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomTargets, VecAssemblyGymGroups
+from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGymGroups
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
@@ -23,8 +28,11 @@ ap.add_argument("--steps", type=int, default=100, help="timed lock-steps (at lea
 ap.add_argument("--warmup", type=int, default=20)
 ap.add_argument("--max_steps", type=int, default=15)
 ap.add_argument("--seed", type=int, default=0)
-ap.add_argument("--tasks", default="bridge,fixed3,random3")
+ap.add_argument("--tasks", default=None, help="default: bridge,fixed3,random3 (+ obst_fixed,obst_random with --random_obstacles)")
+ap.add_argument("--random_obstacles", type=int, default=0, metavar="O", help="obstacles per env of the obst_* tasks (1..4)")
 a = ap.parse_args()
+if a.tasks is None:
+    a.tasks = "bridge,fixed3,random3" + (",obst_fixed,obst_random" if a.random_obstacles else "")
 if a.steps < 100:
     sys.exit("--steps must be at least 100")
 
@@ -32,6 +40,10 @@ H = 0.8                                                       # bridge_setup(H=.
 TASKS = dict(bridge=([(0.5, 0.0, i * H + H / 2) for i in range(4)], [(0.5, 0.0, 4 * H + H / 2)]),
              fixed3=([], [(0.5, 0.0, 1.2), (-1.5, 0.0, 2.6), (2.5, 0.0, 0.4)]),
              random3=([], RandomTargets()))
+if a.random_obstacles:
+    O = a.random_obstacles
+    TASKS["obst_fixed"] = ([(-3.0 + 6.0 * (o + 0.5) / O, 0.0, 0.3) for o in range(O)], TASKS["fixed3"][1])
+    TASKS["obst_random"] = (RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * O), TASKS["fixed3"][1])
 geoms = [load_urdf("shapes/trapezoid.urdf")]
 out = dict(tool="random_task_throughput", envs=a.envs, groups=a.groups, steps=a.steps, warmup=a.warmup, max_steps=a.max_steps,
            device=torch.cuda.get_device_name(0), tasks={})
@@ -58,7 +70,7 @@ for name in a.tasks.split(","):
              reset_only=d["reset_only"], candidates_per_state=d["sum_cand"] / states,
              candidates_per_lockstep=d["sum_cand"] / a.steps, valid_per_state=d["sum_valid"] / states,
              blocks_per_state=d["sum_blocks"] / states)
-    if name == "random3":
+    if name in ("random3", "obst_random"):
         ep = torch.cat([e.task_episode for e in env.envs]).double()
         r["episodes_per_env"] = float(ep.mean())               # since the reset: warm-up included
         r["tasks_drawn_per_lockstep"] = float(ep.sum()) / (a.steps + a.warmup)

@@ -225,6 +225,7 @@ SIGNATURES = {
     "bridges_action_features": [vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_to_f32": [i32, vp, vp, vp],
     "bridges_bits_linear": [i32, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_bits_linear2": [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_sigmoid_dot": [i32, vp, i64, vp, i32, vp, vp],
     "bridges_sigmoid_dot_rows": [i32, vp, i64, vp, vp, i32, vp, vp],
     "bridges_bits_dot": [i32, vp, vp, vp, vp, vp, vp],
@@ -258,6 +259,8 @@ SIGNATURES = {
     "bridges_mlp_input_batches": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "bridges_mlp_input_rows": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp],
     "bridges_mlp_input_batches_rows": [i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp],
+    "bridges_mlp_input_task_rows": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp],
+    "bridges_mlp_input_batches_task_rows": [i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp],
     "bridges_successor_loss": [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_successor_loss_rows": [i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_adam_step": [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],

@@ -156,14 +156,29 @@ class FusedSuccessorStep:
         assert reward.numel() == self.px
         return 0
 
+    def _obstacle_bits(self, obstacle, n_rows):
+        """True for an obstacle raster per transition of the per-call arrays, bit-packed (int64 [n, 64] -- replay of per-env
+        obstacles), which must cover the ``n_rows`` transitions the launch can address; False for ONE float map [px]."""
+        if obstacle.dtype == torch.int64:
+            assert obstacle.dim() == 2 and obstacle.shape[1] == 64 and obstacle.is_contiguous(), "obstacle bits must be int64 [n, 64]"
+            assert obstacle.shape[0] >= n_rows, f"{obstacle.shape[0]} obstacle rasters for {n_rows} transitions"
+            return True
+        assert obstacle.dtype == torch.float32 and obstacle.is_contiguous() and obstacle.numel() == self.px
+        return False
+
     def prepare_inputs(self, n_batches, block_all, action_all, binary_all, reward, obstacle):
         """Build the input rows of batches 0 .. n_batches - 1 of the per-call arrays in ONE launch (bridges_mlp_input_batches,
-        or _batches_rows when ``reward`` holds a map per transition, [n, px]); ``launch`` then reads batch ``counter`` of them."""
+        or _batches_rows when ``reward`` holds a map per transition, [n, px], or _batches_task_rows when ``obstacle`` holds a
+        bit-packed raster per transition, int64 [n, 64]); ``launch`` then reads batch ``counter`` of them."""
         assert self.x_all is not None and n_batches <= self._n_alloc
-        for t in (block_all, action_all, binary_all, reward, obstacle):
+        for t in (block_all, action_all, binary_all, reward):
             assert t.dtype == torch.float32 and t.is_contiguous()
         stride = self._reward_stride(reward, int(n_batches) * self.batch)
-        if stride:
+        if self._obstacle_bits(obstacle, int(n_batches) * self.batch):
+            abi.check(self.L.bridges_mlp_input_batches_task_rows(int(n_batches), self.batch, self.rows, self.px, self.nf, _ptr(block_all),
+                                                                 _ptr(action_all), _ptr(binary_all), _ptr(reward), stride, _ptr(obstacle),
+                                                                 _ptr(self.x_all), _stream()), "bridges_mlp_input_batches_task_rows")
+        elif stride:
             abi.check(self.L.bridges_mlp_input_batches_rows(int(n_batches), self.batch, self.rows, self.px, self.nf, _ptr(block_all),
                                                             _ptr(action_all), _ptr(binary_all), _ptr(reward), stride, _ptr(obstacle),
                                                             _ptr(self.x_all), _stream()), "bridges_mlp_input_batches_rows")
@@ -259,15 +274,21 @@ class FusedSuccessorStep:
     def launch(self, counter, block_all, action_all, binary_all, reward, obstacle, q_target_all, sf_target_all, losses):
         L, rows, px, nf, B = self.L, self.rows, self.px, self.nf, self.batch
         st = _stream()
-        for t in (block_all, action_all, binary_all, reward, obstacle):
+        for t in (block_all, action_all, binary_all, reward):
             assert t.dtype == torch.float32 and t.is_contiguous()
         assert counter.dtype == torch.int64 and losses.dtype == torch.float32
         # one reward map, or a map per transition ([n, px], n = the rows of block_all): the launches differ in one argument
         stride = self._reward_stride(reward, block_all.reshape(-1, px).shape[0])
+        # one obstacle map, or a bit-packed raster per transition (int64 [n, 64]): another entry point builds the rows
+        obst_bits = self._obstacle_bits(obstacle, block_all.reshape(-1, px).shape[0])
         # the first layer's input: batch `counter` of the pre-built rows of all batches (prepare_inputs), else built here
         pre = self.x_all is not None and self._prepared
         x0, blk = (self.x_all, _ptr(counter)) if pre else (self.acts[0], None)
-        if not pre and stride:
+        if not pre and obst_bits:
+            abi.check(L.bridges_mlp_input_task_rows(B, rows, px, nf, _ptr(counter), _ptr(block_all), _ptr(action_all), _ptr(binary_all),
+                                                    _ptr(reward), stride, _ptr(obstacle), _ptr(self.acts[0]), st),
+                      "bridges_mlp_input_task_rows")
+        elif not pre and stride:
             abi.check(L.bridges_mlp_input_rows(B, rows, px, nf, _ptr(counter), _ptr(block_all), _ptr(action_all), _ptr(binary_all),
                                                _ptr(reward), stride, _ptr(obstacle), _ptr(self.acts[0]), st), "bridges_mlp_input_rows")
         elif not pre:

@@ -305,6 +305,37 @@ def bits_linear(bits, wt, bits_row=None, base=None, base_row=None):
     return out
 
 
+def bits_linear2(bits_a, wt_a, bits_b, wt_b, bits_row_a=None, bits_row_b=None, base=None, base_row=None):
+    """bits_linear over two bit-packed operands in one launch (bridges_bits_linear2):
+    out[r] = base[base_row[r]] + sum of the rows of ``wt_a`` selected by ``bits_a[bits_row_a[r]]`` + sum of the rows of ``wt_b``
+    selected by ``bits_b[bits_row_b[r]]``, added in that order -- bit for bit
+    ``bits_linear(bits_b, wt_b, bits_row_b, base=bits_linear(bits_a, wt_a, bits_row_a, base, base_row))``.  Returns [n, d] float32;
+    n = the length of a row index that is given, else the rows of ``bits_a``."""
+    L = abi.require_gpu()
+    bits_a, bits_b = bits_a.reshape(-1, 64), bits_b.reshape(-1, 64)
+    assert bits_a.is_contiguous() and bits_a.dtype == torch.int64 and bits_b.is_contiguous() and bits_b.dtype == torch.int64
+    wt_a, wt_b = wt_a.to(torch.float32).contiguous(), wt_b.to(torch.float32).contiguous()
+    assert wt_a.shape[0] == 4096 and wt_a.shape[1] % 4 == 0 and wt_b.shape == wt_a.shape, "wt_a / wt_b must be [4096, d] with d % 4 == 0"
+    d = wt_a.shape[1]
+    n = bits_row_a.numel() if bits_row_a is not None else bits_a.shape[0]
+    if bits_row_a is not None:
+        bits_row_a = bits_row_a.to(torch.int64).contiguous()
+    if bits_row_b is not None:
+        bits_row_b = bits_row_b.to(torch.int64).contiguous()
+        assert bits_row_b.numel() == n
+    else:
+        assert bits_b.shape[0] >= n, f"{bits_b.shape[0]} rasters in bits_b for {n} rows"
+    if base is not None:
+        base = base.to(torch.float32).reshape(-1, d).contiguous()
+        if base_row is not None:
+            base_row = base_row.to(torch.int64).contiguous()
+            assert base_row.numel() == n
+    out = torch.empty((n, d), dtype=torch.float32, device=bits_a.device)
+    abi.check(L.bridges_bits_linear2(n, _ptr(bits_a), _ptr(bits_row_a), _ptr(wt_a), _ptr(bits_b), _ptr(bits_row_b), _ptr(wt_b), d,
+                                     _ptr(base), _ptr(base_row), _ptr(out), _stream()), "bridges_bits_linear2")
+    return out
+
+
 def _head_splits(n_rows, n_tiles, slots=512):
     """Column ranges per 128-row workgroup: enough workgroups that the chip's 2 x 256 resident slots stay evenly filled to the
     end of the launch, few enough that the 128-KB row slab each one loads first stays small against its tiles (measured on

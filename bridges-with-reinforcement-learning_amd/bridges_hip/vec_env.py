@@ -537,6 +537,22 @@ class VecAssemblyGym:
         self.env_obstacles.copy_(obstacles.reshape(self.env_obstacles.shape))
         abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
 
+    def load_task(self, targets, obstacles):
+        """load_targets and load_obstacles in one: both copies, then ONE bridges_env_load_targets, which rebuilds the target
+        tables and the obstacle rasters of every env together (the two methods in a row would run its map work twice).  For a
+        scratch env with explicit per-env targets AND obstacles; task_episode and the states stay.  No host wait."""
+        if not self.per_env_tasks or self.random_targets is not None:
+            raise ValueError("load_task needs an env with explicit per-env targets (created with an [E, T, 3] array / set_targets)")
+        if not self.per_env_obstacles or self.random_obstacles is not None:
+            raise ValueError("load_task needs an env with explicit per-env obstacles (created with an [E, O, 3] array / set_obstacles)")
+        if targets.numel() != self.env_targets.numel() or targets.dtype != torch.float64:
+            raise ValueError(f"targets must hold {tuple(self.env_targets.shape)} float64 values, got {tuple(targets.shape)} {targets.dtype}")
+        if obstacles.numel() != self.env_obstacles.numel() or obstacles.dtype != torch.float64:
+            raise ValueError(f"obstacles must hold {tuple(self.env_obstacles.shape)} float64 values, got {tuple(obstacles.shape)} {obstacles.dtype}")
+        self.env_targets.copy_(targets.reshape(self.env_targets.shape))
+        self.env_obstacles.copy_(obstacles.reshape(self.env_obstacles.shape))
+        abi.check(self.L.bridges_env_load_targets(self._env, _stream()), "bridges_env_load_targets")
+
     # ------------------------------------------------------------------ lock-step API
     def reset(self):
         abi.check(self.L.bridges_env_reset(self._env, _stream()), "bridges_env_reset")

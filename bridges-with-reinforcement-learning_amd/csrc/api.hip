@@ -590,6 +590,16 @@ int bridges_bits_linear(int32_t n_rows, const uint64_t* bits, const int64_t* bit
                   base, base_row, out);
 }
 
+int bridges_bits_linear2(int32_t n_rows, const uint64_t* bits_a, const int64_t* bits_row_a, const float* wt_a, const uint64_t* bits_b,
+                         const int64_t* bits_row_b, const float* wt_b, int32_t d, const float* base, const int64_t* base_row,
+                         float* out, void* stream) {
+    if (n_rows < 0 || d <= 0 || (d & 3) || !bits_a || !wt_a || !bits_b || !wt_b || !out) return fail_arg("bridges_bits_linear2");
+    if (!aligned(16, wt_a, wt_b, out, base)) return fail_arg("bits_linear2: rows must be 16-byte aligned");
+    if (n_rows == 0) return BRIDGES_OK;
+    return launch("k_bits_linear2", k_bits_linear2, dim3(grid_for_waves(n_rows)), dim3(256), 0, stream, n_rows, bits_a, bits_row_a, wt_a,
+                  bits_b, bits_row_b, wt_b, d, base, base_row, out);
+}
+
 int bridges_eps_greedy_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, const float* join,
                               const float* u, float eps, int32_t greedy, const int64_t* idx, const int32_t* cand_offset,
                               const int32_t* rep, int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w, void* stream) {
@@ -976,6 +986,39 @@ int bridges_mlp_input_batches(int32_t n_batches, int32_t batch, int32_t rows, in
                               float* x_all, void* stream) {
     return bridges_mlp_input_batches_rows(n_batches, batch, rows, px, nf, block_all, action_all, binary_all, reward, 0, obstacle, x_all,
                                           stream);
+}
+
+// The _rows forms with an obstacle raster per transition, bit-packed ([n, 64] uint64, one word per image row): px must be 64 * 64.
+static bool obstacle_bits_ok(int32_t px) { return px == IMG * IMG; }
+
+int bridges_mlp_input_task_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, const int64_t* counter, const float* block_all,
+                                const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                                const uint64_t* obstacle_bits, float* x, void* stream) {
+    if (batch <= 0 || rows < batch || (rows & 31) || px <= 0 || nf < 0 || !counter || !block_all || !action_all || !reward || !obstacle_bits || !x)
+        return fail_arg("bridges_mlp_input_task_rows");
+    if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_mlp_input_task_rows: reward_stride must be 0 or px");
+    if (!obstacle_bits_ok(px)) return fail_arg("bridges_mlp_input_task_rows: bit-packed obstacle rasters need px == 4096 (64 x 64)");
+    const dim3 grid(clamp_grid(ceil_div(rows * (4 * px + nf), 256), 2048));
+    if (reward_stride)
+        return launch("k_mlp_input<rows, obstacle bits>", k_mlp_input<true, true>, grid, dim3(256), 0, stream, batch, rows, px, nf, counter,
+                      block_all, action_all, binary_all, reward, obstacle_bits, x);
+    return launch("k_mlp_input<obstacle bits>", k_mlp_input<false, true>, grid, dim3(256), 0, stream, batch, rows, px, nf, counter, block_all,
+                  action_all, binary_all, reward, obstacle_bits, x);
+}
+
+int bridges_mlp_input_batches_task_rows(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
+                                        const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                                        const uint64_t* obstacle_bits, float* x_all, void* stream) {
+    if (n_batches <= 0 || batch <= 0 || rows < batch || (rows & 31) || px <= 0 || nf < 0 || !block_all || !action_all || !reward || !obstacle_bits || !x_all)
+        return fail_arg("bridges_mlp_input_batches_task_rows");
+    if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_mlp_input_batches_task_rows: reward_stride must be 0 or px");
+    if (!obstacle_bits_ok(px)) return fail_arg("bridges_mlp_input_batches_task_rows: bit-packed obstacle rasters need px == 4096 (64 x 64)");
+    const dim3 grid(clamp_grid(ceil_div(rows * (4 * px + nf), 256), 2048), n_batches);
+    if (reward_stride)
+        return launch("k_mlp_input<rows, obstacle bits> (all batches)", k_mlp_input<true, true>, grid, dim3(256), 0, stream, batch, rows, px, nf,
+                      (const int64_t*)nullptr, block_all, action_all, binary_all, reward, obstacle_bits, x_all);
+    return launch("k_mlp_input<obstacle bits> (all batches)", k_mlp_input<false, true>, grid, dim3(256), 0, stream, batch, rows, px, nf,
+                  (const int64_t*)nullptr, block_all, action_all, binary_all, reward, obstacle_bits, x_all);
 }
 
 int bridges_successor_loss(int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* y, const float* reward,

@@ -206,6 +206,60 @@ __global__ __launch_bounds__(256) void k_bits_linear(int n_rows, const uint64_t*
     }
 }
 
+// K8 with two bit-packed operands (per-env obstacles: state raster x W_block + the env's obstacle raster x W_obst):
+//   out[r, :] = base[base_row[r], :] + sum over set pixels p of bits_a[row_a[r]] of wt_a[p, :]
+//                                     + sum over set pixels p of bits_b[row_b[r]] of wt_b[p, :]
+// summed in exactly that order, pixels ascending inside an operand: the float sequence of two chained k_bits_linear launches
+// (the second with the first's output as its base, row r), so the result equals theirs bit for bit -- without the store and
+// reload of the intermediate row and the second launch.  Both row masks stay in the wave (one uint64 per lane each).
+__device__ __forceinline__ void bits_linear_add(float4& acc, uint64_t mine, uint64_t rows_nz, const float* __restrict__ wt, int d,
+                                                int col, bool act) {
+    uint64_t rem = rows_nz;
+    while (rem) {
+        const int rr = __builtin_ctzll(rem);
+        rem &= rem - 1ull;
+        uint64_t m = shfl_u64(mine, rr);                                     // uniform: the mask of image row rr
+        const float* w = wt + (size_t)rr * IMG * d + col;
+        while (m) {
+            const int cc = __builtin_ctzll(m);
+            m &= m - 1ull;
+            if (act) {
+                const float4 v = *reinterpret_cast<const float4*>(w + (size_t)cc * d);
+                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bits_linear2(int n_rows, const uint64_t* __restrict__ bits_a,
+                                                      const int64_t* __restrict__ row_a, const float* __restrict__ wt_a,
+                                                      const uint64_t* __restrict__ bits_b, const int64_t* __restrict__ row_b,
+                                                      const float* __restrict__ wt_b, int d, const float* __restrict__ base,
+                                                      const int64_t* __restrict__ base_row, float* __restrict__ out) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+    const int nwaves = (gridDim.x * blockDim.x) / WAVE;
+    for (int rv = wave; rv < n_rows; rv += nwaves) {
+        const int r = __builtin_amdgcn_readfirstlane(rv);
+        const int64_t src_a = row_a ? row_a[r] : (int64_t)r;
+        const int64_t src_b = row_b ? row_b[r] : (int64_t)r;
+        const uint64_t mine_a = bits_a[(size_t)src_a * IMG + lane];         // image row `lane` of either operand
+        const uint64_t mine_b = bits_b[(size_t)src_b * IMG + lane];
+        const uint64_t nz_a = __ballot(mine_a != 0ull);
+        const uint64_t nz_b = __ballot(mine_b != 0ull);
+        const float* b = base ? base + (size_t)(base_row ? base_row[r] : 0) * d : nullptr;
+        for (int c0 = 0; c0 < d; c0 += 4 * WAVE) {
+            const int col = c0 + 4 * lane;
+            const bool act = col < d;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (b && act) acc = *reinterpret_cast<const float4*>(b + col);
+            bits_linear_add(acc, mine_a, nz_a, wt_a, d, col, act);
+            bits_linear_add(acc, mine_b, nz_b, wt_b, d, col, act);
+            if (act) *reinterpret_cast<float4*>(out + (size_t)r * d + col) = acc;
+        }
+    }
+}
+
 // Count-based exploration of EpsilonGreedy (successor_dqn.py:112-131) on the bit-packed rasters, both directions:
 //   k_bits_dot:        out[r] = sum over the set pixels of bits[bits_row[r]] of img[slot[r]]  (= sum(step_images[step] * a_r))
 //   k_bits_accumulate: img[slot[r]] += weight[r] * raster(bits[bits_row[r]])                  (= step_images[step] += a_sel)

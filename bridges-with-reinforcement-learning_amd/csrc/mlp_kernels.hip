@@ -10,6 +10,7 @@
 // Operand maps (cdna_hip_programming.md, "Fragment layout"): lane l supplies A[row = l & 31][k = l >> 5] and
 // B[k = l >> 5][col = l & 31]; the accumulator register r of lane l is C[row = (r & 3) + 8 (r >> 2) + 4 (l >> 5)]
 // [col = l & 31].  The k order inside a tile is free as long as A and B agree, which lets every lane fetch 16 B.
+#include <type_traits>
 #include "bridges_device.h"
 
 namespace bridges {
@@ -419,11 +420,16 @@ __global__ __launch_bounds__(256) void k_lin_dx_finish(int rows, int K, int nspl
 // Input rows of one replay batch: x[b] = [block | action | reward | obstacle | binary] (cv.py:100-103) for the batch
 // `*counter` of the static per-call arrays (block_all / action_all [n][px], binary_all [n][nf]); rows >= batch are 0.
 // PER_ROW: every transition was taken under a task of its own -- `reward` is [n][px] and transition src reads its row src.
-template <bool PER_ROW>
+// OBST_ROWS: every transition has an obstacle raster of its own as well, kept BIT-PACKED -- `obstacle` is uint64 [n][IMG]
+// (px == IMG * IMG, checked by the entry points) and column 3 px + p of transition src is bit p & 63 of word src * IMG + (p >> 6),
+// the bit order of k_bits_to_f32 / k_bits_linear: 512 B per transition instead of a 16 KiB f32 image, and the 64 consecutive
+// columns of one image row read one word.
+template <bool PER_ROW, bool OBST_ROWS = false>
 __global__ __launch_bounds__(256) void k_mlp_input(int batch, int rows, int px, int nf, const int64_t* __restrict__ counter,
                                                    const float* __restrict__ block_all, const float* __restrict__ action_all,
                                                    const float* __restrict__ binary_all, const float* __restrict__ reward,
-                                                   const float* __restrict__ obstacle, float* __restrict__ x) {
+                                                   typename std::conditional<OBST_ROWS, const uint64_t*, const float*>::type __restrict__ obstacle,
+                                                   float* __restrict__ x) {
     const int K = 4 * px + nf;
     const size_t total = (size_t)rows * K;
     // counter == nullptr: blockIdx.y = the batch, x the [n_batches * rows, K] array of all batches of a train_policy_net call
@@ -438,7 +444,14 @@ __global__ __launch_bounds__(256) void k_mlp_input(int batch, int rows, int px, 
             if (c < px) v = block_all[src * px + c];
             else if (c < 2 * px) v = action_all[src * px + (c - px)];
             else if (c < 3 * px) v = PER_ROW ? reward[src * px + (c - 2 * px)] : reward[c - 2 * px];
-            else if (c < 4 * px) v = obstacle[c - 3 * px];
+            else if (c < 4 * px) {
+                if constexpr (OBST_ROWS) {
+                    const int p = c - 3 * px;
+                    v = (float)((obstacle[src * IMG + (p >> 6)] >> (p & 63)) & 1ull);
+                } else {
+                    v = obstacle[c - 3 * px];
+                }
+            }
             else v = binary_all[src * nf + (c - 4 * px)];
         }
         x[i] = v;

@@ -172,11 +172,12 @@ class SuccessorMLP(nn.Module):
     def first_layer_stable_tables(self, reward_maps, obstacle):
         """first_layer_stable_table for envs that own their reward maps (per-env tasks): reward_maps [E, px] (or [E, H, W]),
         obstacle [px] shared -> [E, 2, hidden], row [e, s] = the terms of env e with stable = s (k_bits_linear's ``base`` with
-        base_row = 2 * env + stable).  One [E, px] x [px, hidden] product per call."""
+        base_row = 2 * env + stable).  One [E, px] x [px, hidden] product per call.  ``obstacle=None`` (per-env obstacles) leaves
+        the obstacle term out -- bias + reward + stable only; the caller adds every env's own (k_bits_linear2's second operand)."""
         px = self.img_size[0] * self.img_size[1]
         lin = self.first_layer()
         E = reward_maps.shape[0]
-        const = torch.addmv(lin.bias, lin.weight[:, 3 * px:4 * px], obstacle.reshape(px))
+        const = lin.bias if obstacle is None else torch.addmv(lin.bias, lin.weight[:, 3 * px:4 * px], obstacle.reshape(px))
         per_env = torch.addmm(const, reward_maps.reshape(E, px), lin.weight[:, 2 * px:3 * px].T)
         return torch.stack([per_env, per_env + lin.weight[:, 4 * px]], dim=1)
 

@@ -516,6 +516,9 @@ def build_parser():
                    help="Vectorised loop, SuccessorMLP: tower_setup(num_targets=T) per env and episode -- every env draws T "
                         "fresh targets whenever it starts an episode (trapezoid blocks, no obstacles); --eval_envs evaluates on a "
                         "fixed held-out set of tasks. Not with --tower_height / --bridge_length.")
+    p.add_argument("--random_obstacles", type=int, default=argparse.SUPPRESS, metavar="O",
+                   help="With --random_targets T only: every env also draws O obstacles (x in [-3, 3), z in [0.3, 2.5)) whenever it "
+                        "starts an episode, as connecting_setup draws obstacles beside its targets; the evaluation env draws its own.")
     return p
 
 
@@ -523,12 +526,17 @@ EVAL_DEFAULTS = dict(eval_envs=0, eval_epsilon=0.0)
 
 
 def check_random_targets(args):
-    """--random_targets T is the vectorised SuccessorMLP loop on per-env random tasks; every other combination is refused in
-    words (SystemExit), before anything touches the GPU."""
-    T = args.get('random_targets')
+    """--random_targets T is the vectorised SuccessorMLP loop on per-env random tasks, --random_obstacles O adds O random
+    obstacles per env to it; every other combination is refused in words (SystemExit), before anything touches the GPU."""
+    T, O = args.get('random_targets'), args.get('random_obstacles')
+    if O is not None and T is None:
+        raise SystemExit("--random_obstacles O is valid only together with --random_targets T: per-env obstacles ride on the "
+                         "per-env task buffers and records of the loop on per-env tasks")
     if T is None:
         return
     from bridges_hip import abi
+    if O is not None and not 1 <= O <= abi.MAX_OBSTACLES:
+        raise SystemExit(f"--random_obstacles must be 1..{abi.MAX_OBSTACLES} obstacles per env")
     if not 1 <= T <= abi.MAX_TARGETS:
         raise SystemExit(f"--random_targets must be 1..{abi.MAX_TARGETS} targets per env")
     if args.get('tower_height') or args['bridge_length'] != 1:
@@ -538,7 +546,8 @@ def check_random_targets(args):
         raise SystemExit("--random_targets needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
                          "fixed tasks of --tower_height / --bridge_length only")
     if args['model'] != 'SuccessorMLP':
-        raise SystemExit(f"--random_targets trains --model SuccessorMLP only: {args['model']} takes the reward map as an image "
+        raise SystemExit(f"--random_targets{' / --random_obstacles' if O is not None else ''} trains --model SuccessorMLP only: "
+                         f"{args['model']} takes the reward map as an image "
                          "channel and its rows are shared by state alone (per-env tasks for the conv nets are not built)")
     if tuple(args['image_size']) != (64, 64):
         raise SystemExit("--random_targets needs --image_size 64x64 (the factored acting path of SuccessorMLP)")

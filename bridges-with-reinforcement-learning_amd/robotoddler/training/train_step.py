@@ -71,7 +71,7 @@ class CapturedTrainStep:
     captures again; a failed capture (RuntimeError) or an invalid logged loss switches the driver to eager for good."""
 
     def __init__(self, net, optimizer, batch, loss_parts, img, fused, graph_default=True, warmup=1, eager_body=True,
-                 prepared=False, task=None, owner=None, task_rows=False):
+                 prepared=False, task=None, owner=None, task_rows=False, obstacle_rows=False):
         self.net, self.opt, self.B, self.img = net, optimizer, int(batch), tuple(int(s) for s in img)
         self.key = (optimizer, self.B, tuple(loss_parts), owner)
         self.use_q, self.use_sf = 'mse_q_values' in loss_parts, 'mse_block_features' in loss_parts
@@ -80,9 +80,16 @@ class CapturedTrainStep:
         # task_rows (per-env tasks; the hand-written step only): every transition has a reward map of its own -- ``run`` takes
         # them as reward [n * B, px] and copies them into a static [n_max * B, px] buffer the captured launches read with a
         # row stride, so the graph replays unchanged; task = (None, obstacle): the obstacle map stays shared
-        self.task_rows = bool(task_rows)
+        # obstacle_rows (per-env obstacles; with task_rows only): every transition has an obstacle raster of its own too --
+        # ``run`` takes them bit-packed as obstacle [n * B, 64] int64 and copies them into a static [n_max * B, 64] buffer the
+        # captured launches read (bridges_mlp_input_task_rows / _batches_task_rows); task = (None, None)
+        self.task_rows, self.obstacle_rows = bool(task_rows), bool(obstacle_rows)
         if self.task_rows and not (fused and task is not None and task[0] is None):
             raise ValueError("per-transition reward maps need the hand-written step (fused=True) and task=(None, obstacle)")
+        if self.obstacle_rows and not (self.task_rows and task[1] is None):
+            raise ValueError("per-transition obstacle rasters need per-transition reward maps (task_rows=True) and task=(None, None)")
+        if self.task_rows and not self.obstacle_rows and task[1] is None:
+            raise ValueError("task=(None, None) needs obstacle_rows=True: without it the obstacle map is the shared task[1]")
         self.calls, self.disabled, self.n_max = 0, False, 0
         self.step = self.adam = self.state = None
         self._graphs = {}
@@ -113,7 +120,9 @@ class CapturedTrainStep:
         self.sf = z(N, px) if self.use_sf else None
         self.counter, self.losses = torch.zeros((), dtype=torch.int64, device=dev), z(n)
         self.lane, self.iota = torch.arange(B, device=dev), torch.arange(n, device=dev)
-        if self.task_rows:
+        if self.obstacle_rows:
+            self.reward, self.obstacle = z(N, px), torch.zeros((N, 64), dtype=torch.int64, device=dev)
+        elif self.task_rows:
             self.reward, self.obstacle = z(N, px), self.task[1].reshape(-1).contiguous()
         else:
             self.reward, self.obstacle = (z(px), z(px)) if self.task is None else (t.reshape(-1).contiguous() for t in self.task)
@@ -187,7 +196,8 @@ class CapturedTrainStep:
     def run(self, n, block, action, binary, reward, obstacle, q, sf):
         """n optimiser steps on batches 0 .. n-1 of the per-call arrays (rows b * B .. b * B + B - 1 of block / action /
         binary / q / sf; reward / obstacle: one map for all rows, unused with ``task`` -- except with ``task_rows``, where
-        reward [n * B, px] holds the map of every transition) -> the device tensor of the n losses
+        reward [n * B, px] holds the map of every transition, and with ``obstacle_rows``, where obstacle [n * B, 64] int64 holds
+        the bit-packed obstacle raster of every transition) -> the device tensor of the n losses
         (a view of the driver's buffer, valid until its next call), or None: the caller steps eagerly."""
         graphs = not self.disabled and graph_enabled(self.graph_default)
         if not graphs or self.calls < self.warmup:
@@ -200,7 +210,8 @@ class CapturedTrainStep:
             self.counter.zero_()
             self.losses.zero_()
             if self.task_rows:
-                reward, obstacle = reward.reshape(n * self.B, -1).contiguous(), self.obstacle
+                reward = reward.reshape(n * self.B, -1).contiguous()
+                obstacle = obstacle.reshape(n * self.B, 64).contiguous() if self.obstacle_rows else self.obstacle
             for _ in range(n):
                 self._fused_body(block, action, binary, reward, obstacle, q, sf)
             return self.losses[:n]
@@ -219,6 +230,8 @@ class CapturedTrainStep:
         N = n * self.B
         if self.task_rows:
             _put(self.reward, reward.reshape(N, -1))       # before the first-layer rows are built from it
+            if self.obstacle_rows:
+                _put(self.obstacle, obstacle.reshape(N, 64))
         if self.fused and self.prepared:
             # the first layer's input rows of all n batches in one launch, straight from the caller's tensors (no staging
             # copy of the block / action images: a replayed step reads only x_all, q and sf)

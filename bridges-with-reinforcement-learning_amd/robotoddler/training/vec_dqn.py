@@ -34,27 +34,43 @@ import torch
 
 from bridges_hip import dqn_ops, ops
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
+from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGym
 from robotoddler.training import distributed as D
 from robotoddler.training import records as R
 from robotoddler.training.episode_stats import EpisodeStats
 from robotoddler.training import train_step as T
 
 
+# --random_obstacles: every obstacle of every env is drawn from x in [-3, 3), z in [0.3, 2.5) at the start of an episode
+OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
+
+
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
-                 episode_stats=False, per_env_tasks=False):
+                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
         and the optimiser step reads a map per transition.  Only the path that is hand-written from acting to Adam takes it:
-        a SuccessorMLP on 64x64 images with the fused optimiser step."""
-        self.per_env_tasks = bool(per_env_tasks)
-        if getattr(env, "per_env_obstacles", False):
-            raise ValueError("VecDQN cannot train on a rollout env with per-env obstacles (RandomObstacles / set_obstacles), with or "
-                             "without per_env_tasks=True: the first layer's image-independent part, the replay record and the "
-                             "captured train steps hold ONE obstacle raster")
+        a SuccessorMLP on 64x64 images with the fused optimiser step.
+        ``per_env_obstacles=True`` (with per_env_tasks=True only): the envs own their obstacles as well
+        (VecAssemblyGym(obstacles=RandomObstacles()) or set_obstacles).  Acting and the target forward add every env's obstacle
+        raster to the first layer as a second bit-packed operand (bridges_bits_linear2), a record ends in the targets AND the
+        obstacles of its transition, replay filters the next states' candidates against them, and the optimiser step reads a
+        bit-packed obstacle raster per transition."""
+        self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
+        if getattr(env, "per_env_obstacles", False) and not self.per_env_obstacles:
+            raise ValueError("VecDQN cannot train on a rollout env with per-env obstacles (RandomObstacles / set_obstacles) unless it "
+                             "is built with per_env_tasks=True AND per_env_obstacles=True: by default the first layer's "
+                             "image-independent part, the replay record and the captured train steps hold ONE obstacle raster")
+        if self.per_env_obstacles:
+            if not self.per_env_tasks:
+                raise ValueError("VecDQN(per_env_obstacles=True) needs per_env_tasks=True: per-env obstacles ride on the per-env task "
+                                 "buffers, the per-env tables and the per-transition records")
+            if not getattr(env, "per_env_obstacles", False):
+                raise ValueError("VecDQN(per_env_obstacles=True) needs a rollout env with per-env obstacles "
+                                 "(VecAssemblyGym(obstacles=RandomObstacles()) or set_obstacles); this env has one shared obstacle list")
         if getattr(env, "per_env_tasks", False) and not self.per_env_tasks:
             raise ValueError("VecDQN cannot train on a rollout env with per-env tasks (RandomTargets / set_targets) unless it is "
                              "built with per_env_tasks=True: by default envs in the same state share candidate rows whatever "
@@ -88,8 +104,11 @@ class VecDQN:
         self.B, self.gamma, self.tau = batch_size, gamma, tau
         self.loss_parts = loss_function.split('+')
         self.prioritized = bool(prioritized)      # PrioritizedReplayBuffer semantics (replay_memory.py:45-93)
-        # per-env tasks: a record ends in the T targets (x, y, z) its transition was taken under
-        self.task_width = 3 * env.n_targets if self.per_env_tasks else 0
+        # per-env tasks: a record ends in the T targets (x, y, z) its transition was taken under, per-env obstacles: followed by
+        # its O obstacles (x, y, z)
+        self.n_task_targets = env.n_targets if self.per_env_tasks else 0
+        self.n_task_obstacles = env.n_obstacles if self.per_env_obstacles else 0
+        self.task_width = 3 * self.n_task_targets + 3 * self.n_task_obstacles
         self.ring = R.ReplayRing(replay_capacity, self.device, width=R.RECORD_WIDTH + self.task_width)
         # replay sampling must be identical on every rank (replicated rings) -> shared seed; exploration differs
         self.sample_gen = torch.Generator(device=self.device).manual_seed(1234567 + seed)
@@ -264,9 +283,18 @@ class VecDQN:
                 raise ValueError("an env with per-env tasks needs VecDQN(per_env_tasks=True)")
             E = env.E
             maps = env.reward_maps.reshape(E, px)
-            table = net.first_layer_stable_tables(maps, env.obstacle_raster.reshape(-1)).reshape(2 * E, -1)
             base_row = 2 * torch.arange(E, device=self.device) + stable.long()
-            base = ops.bits_linear(env.state_bits, W1[:, :px].T, base=table, base_row=base_row)
+            if getattr(env, "per_env_obstacles", False):
+                # every env owns its obstacle raster too: the table leaves the obstacle term out and the env's bit-packed raster
+                # selects its rows of W_obst as the second operand of the same launch (bridges_bits_linear2)
+                if not self.per_env_obstacles:
+                    raise ValueError("an env with per-env obstacles needs VecDQN(per_env_obstacles=True)")
+                table = net.first_layer_stable_tables(maps, None).reshape(2 * E, -1)
+                base = ops.bits_linear2(env.state_bits, W1[:, :px].T, env.env_obstacle_bits, W1[:, 3 * px:4 * px].T, base=table,
+                                        base_row=base_row)
+            else:
+                table = net.first_layer_stable_tables(maps, env.obstacle_raster.reshape(-1)).reshape(2 * E, -1)
+                base = ops.bits_linear(env.state_bits, W1[:, :px].T, base=table, base_row=base_row)
             h_pre = ops.bits_linear(env.cand_bits, W1[:, px:2 * px].T, bits_row=idx, base=base, base_row=row_env)
             q = net.q_from_first_layer(h_pre, maps, head=ops.sigmoid_dot, fused_head=ops.head_sigmoid_dot,
                                        reward_rows=row_env.to(torch.int32))
@@ -341,7 +369,8 @@ class VecDQN:
         rec = R.pack_state(env, sel_compact)
         if getattr(env, "per_env_tasks", False):
             # the task the transition is taken under: the step that ends an episode redraws the env's targets (task_tail)
-            env._task_tail = env.env_targets.reshape(E, -1).clone()
+            env._task_tail = (torch.cat([env.env_targets.reshape(E, -1), env.env_obstacles.reshape(E, -1)], dim=1)
+                              if self.per_env_obstacles else env.env_targets.reshape(E, -1).clone())
         env.step(sel_index)
         valid = R.pack_result(env, rec)
         return rec, valid, q_sel
@@ -349,7 +378,8 @@ class VecDQN:
     def with_task(self, rec, env=None):
         """The records of the last act() on ``env`` (default: the rollout env) in the width the ring stores: on per-env tasks
         the RECORD_WIDTH columns followed by the env's targets as they were BEFORE the step (one device copy; the record
-        kernels, the episode statistics and td_errors address rows of RECORD_WIDTH doubles and see ``rec`` as it is)."""
+        kernels, the episode statistics and td_errors address rows of RECORD_WIDTH doubles and see ``rec`` as it is).  Per-env
+        obstacles: the targets are followed by the env's obstacles, as they were before the step as well."""
         if not self.per_env_tasks:
             return rec
         return torch.cat([rec, (env or self.env)._task_tail], dim=1)
@@ -370,6 +400,9 @@ class VecDQN:
             raise ValueError("the evaluation env's stable_actions_only must match the training env's")
         if bool(getattr(eval_env, "per_env_tasks", False)) != self.per_env_tasks:
             raise ValueError("the evaluation env must have per-env tasks exactly when the agent was built with per_env_tasks=True")
+        if bool(getattr(eval_env, "per_env_obstacles", False)) != self.per_env_obstacles:
+            raise ValueError("the evaluation env must have per-env obstacles exactly when the agent was built with "
+                             "per_env_obstacles=True")
         key = (eval_env.E, eval_env.K, eval_env.n_targets)
         st = self._eval_state.get(key)
         if st is None:
@@ -396,10 +429,11 @@ class VecDQN:
     # ------------------------------------------------------------------ gradient steps on sampled batches
     def _make_replay_env(self, n_states):
         """A scratch env of n_states envs of the rollout env's task; on per-env tasks with per-env targets of its own (zeros
-        until _targets writes the sampled records' tasks into them)."""
+        until _targets writes the sampled records' tasks into them); on per-env obstacles with explicit per-env obstacles too."""
         env = self.env
         targets = (torch.zeros((n_states, env.n_targets, 3), dtype=torch.float64) if self.per_env_tasks else env.targets)
-        return VecAssemblyGym(n_states, env.shapes, env.obstacles, targets, max_steps=env.max_steps,
+        obstacles = (torch.zeros((n_states, env.n_obstacles, 3), dtype=torch.float64) if self.per_env_obstacles else env.obstacles)
+        return VecAssemblyGym(n_states, env.shapes, obstacles, targets, max_steps=env.max_steps,
                               mu=env.mu, density=env.density, bounds=env.bounds, xlim=env.xlim,
                               ylim=env.ylim, x_discr_ground=env.x_discr_ground,
                               offset_values=env.offset_values, device=self.device, a_max=env.a_max,
@@ -425,7 +459,10 @@ class VecDQN:
         one target-net forward and one k_td_target launch for n_steps * batch_size transitions.
         Per-env tasks: the records' tails (their targets) go to the scratch env first, which rebuilds every transition's reward
         map from them (bridges_env_load_targets; envs beyond n repeat record 0's task, as their states do); a sixth value is
-        returned then, the [n, px] maps of the transitions (a view of the scratch env's reward_maps: valid until the next call)."""
+        returned then, the [n, px] maps of the transitions (a view of the scratch env's reward_maps: valid until the next call).
+        Per-env obstacles: the tails' obstacles go in beside the targets (load_task: one bridges_env_load_targets), so the
+        rasteriser filters every next state's candidates against its transition's own obstacles; a seventh value is returned,
+        the bit-packed obstacle rasters of the transitions [n, 64] int64 (a view of the scratch env's env_obstacle_bits)."""
         n = rec.shape[0]
         renv = self._replay_env(n)
         E = renv.E
@@ -433,7 +470,12 @@ class VecDQN:
             if rec.shape[1] != R.RECORD_WIDTH + self.task_width:
                 raise ValueError(f"per-env tasks: records of {R.RECORD_WIDTH + self.task_width} columns expected, got {rec.shape[1]}")
             tail = rec[:, R.RECORD_WIDTH:]
-            renv.load_targets(tail if n == E else torch.cat([tail, tail[:1].expand(E - n, -1)]))
+            tail = tail if n == E else torch.cat([tail, tail[:1].expand(E - n, -1)])
+            if self.per_env_obstacles:
+                nt = 3 * self.n_task_targets
+                renv.load_task(tail[:, :nt].contiguous(), tail[:, nt:].contiguous())
+            else:
+                renv.load_targets(tail)
             rec = rec[:, :R.RECORD_WIDTH]
         # state s' (= s + action block): candidates, masks, rasters by the same kernels as the rollout; s is the
         # prefix of its block list, so its raster comes out of the same per-block bit rasters.  One launch unpacks the
@@ -467,6 +509,8 @@ class VecDQN:
         binary = torch.zeros((E, 6), dtype=torch.float32, device=self.device)
         binary[:, 0] = stable_s
         out = (block_f[:n], binary[:n], action_f[:n], q_target[:n], (sf_target[:n] if use_sf else None))
+        if self.per_env_obstacles:
+            return out + (renv.reward_maps_img[:n].reshape(n, -1), renv.env_obstacle_bits[:n])
         return out + (renv.reward_maps_img[:n].reshape(n, -1),) if self.per_env_tasks else out
 
     def _loss(self, q, sf, q_target, sf_target):
@@ -487,7 +531,9 @@ class VecDQN:
                                       fused=T.fused_step_enabled(self.policy_net, self.loss_parts),
                                       graph_default=isinstance(self.policy_net, (SuccessorMLP, ConvNet, Policy)), warmup=2,
                                       eager_body=False, prepared=True, task_rows=self.per_env_tasks,
-                                      task=((None if self.per_env_tasks else env.reward_features), env.obstacle_raster))
+                                      obstacle_rows=self.per_env_obstacles,
+                                      task=((None if self.per_env_tasks else env.reward_features),
+                                            (None if self.per_env_obstacles else env.obstacle_raster)))
 
     @property
     def _graph_state(self):
@@ -516,21 +562,24 @@ class VecDQN:
         # n_steps independent batches = ONE draw of n_steps * B records: both sampling rules draw with replacement, so
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
         rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
-        block_f, binary, action_f, q_target, sf_target, *maps = self._targets(rec)
-        maps = maps[0] if maps else None                     # per-env tasks: the reward map of every transition [n_steps * B, px]
+        block_f, binary, action_f, q_target, sf_target, *task = self._targets(rec)
+        maps = task[0] if task else None                     # per-env tasks: the reward map of every transition [n_steps * B, px]
+        obst_bits = task[1] if len(task) > 1 else None       # per-env obstacles: its bit-packed obstacle raster [n_steps * B, 64]
         drv = self._train_step(n_steps)
-        out = drv.run(n_steps, block_f, action_f, binary, maps, None, q_target, sf_target)
+        out = drv.run(n_steps, block_f, action_f, binary, maps, obst_bits, q_target, sf_target)
         if out is None:
             drv = None
             S = self.env.img
             reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1) if maps is None else None
-            obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1)
+            obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1) if obst_bits is None else None
             self.policy_net.train()
             losses = []
             for i in range(n_steps):
                 sl = slice(i * B, (i + 1) * B)
                 if maps is not None:
                     reward = maps[sl].reshape(B, 1, S, S)
+                if obst_bits is not None:
+                    obstacle = ops.bits_to_f32(obst_bits[sl]).reshape(B, 1, S, S)
                 q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
                 loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
                 self.opt.zero_grad()
@@ -562,7 +611,8 @@ class VecDQN:
     def save_extra(self, path, **counters):
         torch.save(dict(epsilon=float(self.epsilon), episodes_done=int(self.episodes_done), env_steps=int(self.env_steps),
                         step_images=self.step_images.cpu(), sample_gen=self.sample_gen.get_state().cpu(),
-                        explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()}), path)
+                        explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()},
+                        task_shape=(int(self.n_task_targets), int(self.n_task_obstacles))), path)
 
     def load_extra(self, path):
         """Restores what save_extra wrote.  The file is rank 0's: exact continuation (same exploration draws, same
@@ -571,6 +621,13 @@ class VecDQN:
         env-step count were never saved -- re-seeds its exploration stream from (seed, rank, lock-step) so that the
         ranks keep drawing different uniforms, and starts its local env-step count from rank 0's."""
         blob = torch.load(path, weights_only=True)
+        # (T, O) of the records' tails: the width alone cannot tell T = 3, O = 0 from T = 2, O = 1 (a file written before the
+        # tails held obstacles carries no entry: it holds targets only, whose number the ring's width check has pinned)
+        want = (int(self.n_task_targets), int(self.n_task_obstacles))
+        got = tuple(int(v) for v in blob.get("task_shape", (want[0], 0)))
+        if got != want:
+            raise ValueError(f"{path} was written by a run whose records end in {got[0]} targets and {got[1]} obstacles, this "
+                             f"agent's end in {want[0]} targets and {want[1]} obstacles: the tails do not mean the same task")
         self.epsilon, self.episodes_done, self.env_steps = blob["epsilon"], blob["episodes_done"], blob["env_steps"]
         self.step_images.copy_(blob["step_images"])
         self.sample_gen.set_state(blob["sample_gen"])
@@ -659,10 +716,13 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
     geoms = [load_urdf(f"shapes/{n}.urdf") for n in names]
     random_targets = args.get('random_targets')
+    random_obstacles = args.get('random_obstacles')
     if random_targets:
         # tower_setup(num_targets=T) per env and episode (gym_env.py:64-79 of the reference): no obstacles, every env draws
-        # its own targets whenever it starts an episode
-        targets, obstacles = RandomTargets(random_targets), []
+        # its own targets whenever it starts an episode; --random_obstacles O: and O obstacles beside them, as connecting_setup
+        # draws both at every reset (gym_env.py:91-99)
+        targets = RandomTargets(random_targets)
+        obstacles = RandomObstacles([OBSTACLE_RANGE] * random_obstacles) if random_obstacles else []
     elif args.get('tower_height'):
         H, N = 0.8, args['tower_height']
         targets = [(0.5, 0, N * H + H / 2)]
@@ -683,7 +743,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
-                   per_env_tasks=bool(random_targets))
+                   per_env_tasks=bool(random_targets), per_env_obstacles=bool(random_obstacles))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -692,7 +752,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     eval_env = None
     if eval_envs > 0 and rank == 0:
         eval_targets = RandomTargets(random_targets) if random_targets else targets
-        eval_env = VecAssemblyGym(eval_envs, geoms, obstacles, eval_targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
+        eval_obstacles = RandomObstacles([OBSTACLE_RANGE] * random_obstacles) if random_obstacles else obstacles
+        eval_env = VecAssemblyGym(eval_envs, geoms, eval_obstacles, eval_targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
                                   device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net),
                                   img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
     history, t0, it = [], time.time(), 0

@@ -336,6 +336,15 @@ int bridges_bits_to_f32(int32_t n, const uint64_t* bits, float* img, void* strea
  * ascending p, so the result is deterministic. */
 int bridges_bits_linear(int32_t n_rows, const uint64_t* bits, const int64_t* bits_row, const float* wt, int32_t d,
                         const float* base, const int64_t* base_row, float* out, void* stream);
+/* K8 with TWO bit-packed operands in one launch (per-env obstacles: the state raster on W_block and the env's obstacle raster
+ * on W_obst):  out[r, :] = base term + sum_{p set in bits_a[bits_row_a ? bits_row_a[r] : r]} wt_a[p, :]
+ *                                    + sum_{p set in bits_b[bits_row_b ? bits_row_b[r] : r]} wt_b[p, :]
+ * added in that order (base, a's pixels ascending, b's pixels ascending): the float sequence of bridges_bits_linear on a followed by
+ * bridges_bits_linear on b with the first result as base, so the output equals the chained calls bit for bit.  Arguments as in
+ * bridges_bits_linear (d % 4 == 0, NULL bits_row_* = identity, NULL base = 0; wt_a / wt_b [4096, d]). */
+int bridges_bits_linear2(int32_t n_rows, const uint64_t* bits_a, const int64_t* bits_row_a, const float* wt_a, const uint64_t* bits_b,
+                         const int64_t* bits_row_b, const float* wt_b, int32_t d, const float* base, const int64_t* base_row,
+                         float* out, void* stream);
 /* EpsilonGreedy's count-based exploration (successor_dqn.py:112-131) on bit-packed rasters, for many environments at once:
  * bridges_bits_dot: out[r] = sum(img[slot[r]] * raster(bits[bits_row[r]])) -- the overlap of candidate r with the count image of
  * its episode step (img [n_slots,64,64] f32, slot [n] i64; bits_row NULL = identity);
@@ -575,6 +584,16 @@ int bridges_mlp_input_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, 
 int bridges_mlp_input_batches_rows(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
                                    const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
                                    const float* obstacle, float* x_all, void* stream);
+/* The _rows forms with an obstacle raster PER TRANSITION as well (replay of per-env obstacles), read BIT-PACKED: obstacle_bits
+ * [n, 64] u64, one raster per transition of the per-call arrays in the layout of bridges_bits_to_f32 / bridges_bits_linear --
+ * column 3 px + p of transition row src = bit p & 63 of word src * 64 + (p >> 6): 512 B per transition instead of a 16 KiB f32
+ * image.  px must be 4096 (64 x 64), anything else returns -1; reward / reward_stride as in the _rows forms. */
+int bridges_mlp_input_task_rows(int32_t batch, int32_t rows, int32_t px, int32_t nf, const int64_t* counter, const float* block_all,
+                                const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                                const uint64_t* obstacle_bits, float* x, void* stream);
+int bridges_mlp_input_batches_task_rows(int32_t n_batches, int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* block_all,
+                                        const float* action_all, const float* binary_all, const float* reward, int64_t reward_stride,
+                                        const uint64_t* obstacle_bits, float* x_all, void* stream);
 /* Head + loss + its gradient (cv.py:104-108; successor_dqn.py:215-232): y [rows, 2 px + 2 nf] = (psi0 | psi1 | binary),
  * q = sum_j softmax(psi)[1][j] * reward[j], loss = [use_q] mean (q - q_target)^2 + [use_sf] mean (psi0 - sf_target)^2
  * with the targets of batch *counter (q_target_all [n], sf_target_all [n,px]).  Writes dy [rows, 2 px + 2 nf],

@@ -1,7 +1,8 @@
 """Times one SuccessorMLP optimiser step at batch 32 (BASELINE.json configs[2] shape: 64x64 images, hidden
 256-128-64-128-256) as a replayed HIP graph: the hand-written forward / loss / backward (bridges_hip/mlp_ops.py) + torch's
 fused Adam, against the autograd step + fused Adam.  Under rocprofv3 --kernel-trace the kernel list of either is visible.
-Usage: python tools/mlp_step_bench.py [--autograd] [--replays 400] [--batch 32]"""
+Usage: python tools/mlp_step_bench.py [--autograd] [--replays 400] [--batch 32]
+       python tools/mlp_step_bench.py --obstacle_bits     (times the two kernels of per-env obstacles alone, see obstacle_bits_lines)"""
 import argparse
 import os
 import sys
@@ -12,8 +13,54 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd"))
 
 
+def obstacle_bits_lines(dev, B=32, n_b=25, E=4096, hidden=256, reps=50):
+    """The two kernels of per-env obstacles beside the ones they stand in for, device time per launch: the input rows of 25
+    batches with a reward map per transition and the obstacle as one f32 map (k_mlp_input<rows>) against a bit-packed raster
+    per transition (k_mlp_input<rows, obstacle bits>); the per-env base of the first layer on E state rasters
+    (k_bits_linear) against state + obstacle rasters (k_bits_linear2)."""
+    from bridges_hip import ops
+    from bridges_hip.mlp_ops import FusedSuccessorStep
+    from robotoddler.models.cv import SuccessorMLP
+    px, n = 4096, n_b * B
+    net = SuccessorMLP(img_size=(64, 64), hidden_dims=[hidden, 128, 64, 128, 256]).to(dev)
+    step = FusedSuccessorStep(net, B, True, True)
+    step.allocate_inputs(n_b)
+    block, action = (torch.rand(n, px, device=dev) < 0.05).float(), (torch.rand(n, px, device=dev) < 0.01).float()
+    binary, maps, one = (torch.rand(n, 6, device=dev) < 0.5).float(), torch.rand(n, px, device=dev), (torch.rand(px, device=dev) < 0.03).float()
+
+    def rasters(m, k):                                                  # m rasters of a k x k square each, somewhere on the canvas
+        bits = torch.zeros((m, 64), dtype=torch.int64, device=dev)
+        y, x = torch.randint(0, 64 - k, (m,), device=dev), torch.randint(0, 64 - k, (m,), device=dev)
+        for j in range(k):
+            bits[torch.arange(m, device=dev), y + j] = ((1 << k) - 1) << x
+        return bits
+    obst = rasters(n, 8)
+    state, env_obst = rasters(E, 6), rasters(E, 8)
+    wa, wb = torch.randn(px, hidden, device=dev), torch.randn(px, hidden, device=dev)
+    table, base_row = torch.randn(2 * E, hidden, device=dev), torch.arange(E, device=dev) * 2
+
+    def timed(name, fn):
+        for _ in range(5):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        print(f"{name}: {a.elapsed_time(b) / reps * 1e3:.1f} us per call (host launch path included)", flush=True)
+    timed(f"k_mlp_input<rows> x {n_b} batches, one f32 obstacle map   ", lambda: step.prepare_inputs(n_b, block, action, binary, maps, one))
+    timed(f"k_mlp_input<rows, obstacle bits> x {n_b} batches          ", lambda: step.prepare_inputs(n_b, block, action, binary, maps, obst))
+    timed(f"k_bits_linear  E = {E}, d = {hidden}                      ", lambda: ops.bits_linear(state, wa, base=table, base_row=base_row))
+    timed(f"k_bits_linear2 E = {E}, d = {hidden}                      ", lambda: ops.bits_linear2(state, wa, env_obst, wb, base=table, base_row=base_row))
+    timed(f"k_bits_linear chained twice E = {E}, d = {hidden}         ",
+          lambda: ops.bits_linear(env_obst, wb, base=ops.bits_linear(state, wa, base=table, base_row=base_row), base_row=torch.arange(E, device=dev)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--obstacle_bits", action="store_true",
+                    help="time the two kernels of per-env obstacles (k_bits_linear2, k_mlp_input with obstacle bits) alone and exit")
     ap.add_argument("--autograd", action="store_true")
     ap.add_argument("--replays", type=int, default=400)
     ap.add_argument("--batch", type=int, default=32)
@@ -21,6 +68,9 @@ def main():
     ap.add_argument("--per-step-inputs", action="store_true", help="build the first layer's input rows inside every step (round 2)")
     ap.add_argument("--torch-adam", action="store_true", help="hand-written step + torch's fused Adam launch (the round-2 step)")
     args = ap.parse_args()
+    if args.obstacle_bits:
+        torch.manual_seed(0)
+        return obstacle_bits_lines(torch.device("cuda:0"), B=args.batch)
     from bridges_hip.mlp_ops import FusedSuccessorStep
     from robotoddler.models.cv import SuccessorMLP
     from robotoddler.utils.utils import init_weights

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel stats of the bench modes (run on the MI355X box through gpurun, from the repo root):
-#   tools/profile_modes.sh <tag> [sim] [cand] [hex] [mlp] [mlp_stable] [conv] [conv_all] [unet] [unet_all] [tasks_fixed] [tasks_random] [obst_fixed] [obst_random] [mlp_tasks_fixed] [mlp_tasks_random]     (*_all: every candidate row fed, --no_dedup)
+#   tools/profile_modes.sh <tag> [sim] [cand] [hex] [mlp] [mlp_stable] [conv] [conv_all] [unet] [unet_all] [tasks_fixed] [tasks_random] [obst_fixed] [obst_random] [mlp_tasks_fixed] [mlp_tasks_random] [mlp_obst_fixed] [mlp_obst_random]     (*_all: every candidate row fed, --no_dedup)
 # Writes gpurun_out/prof_<tag>_<mode>/ (trace + stats) and gpurun_out/prof_<tag>_<mode>.json (the bench line).
 set -o pipefail
 tag=$1; shift
@@ -24,6 +24,8 @@ for mode in "$@"; do
     obst_random)  args="$root/tools/random_task_throughput.py --random_obstacles 2 --tasks obst_random" ;;   # RandomObstacles: + k_task_features (obstacle raster), k_raster reading env_obstacle_bits
     mlp_tasks_fixed)  args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --fixed_targets 3" ;;
     mlp_tasks_random) args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --random_targets 3" ;;   # per-row head, keyed groups, k_task_features in replay
+    mlp_obst_fixed)  args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --fixed_targets 3 --fixed_obstacles 2 --no_dedup" ;;
+    mlp_obst_random) args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --random_targets 3 --random_obstacles 2" ;;   # k_bits_linear2, k_mlp_input<rows, obstacle bits>
     *) echo "unknown mode $mode"; exit 2 ;;
   esac
   (cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $args) > $out.log 2>&1 || { tail -20 $out.log; exit 1; }

@@ -8,7 +8,7 @@ import torch
 from robotoddler.training.successor_dqn import build_parser, make_nets
 from robotoddler.training.vec_dqn import VecDQN
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
+from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGym
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
@@ -35,9 +35,19 @@ ap.add_argument("--random_targets", type=int, default=0, metavar="T",
 ap.add_argument("--fixed_targets", type=int, default=0, metavar="T",
                 help="> 0: the fixed-task counterpart of --random_targets T: T targets shared by every env (T = 3: fixed3 of "
                      "tools/random_task_throughput.py), no obstacles")
+ap.add_argument("--random_obstacles", type=int, default=0, metavar="O",
+                help="> 0, with --random_targets: O obstacles per env and episode beside the targets, x ~ U[-3, 3), z ~ U[0.3, 2.5) "
+                     "(VecDQN(per_env_obstacles=True))")
+ap.add_argument("--fixed_obstacles", type=int, default=0, metavar="O",
+                help="> 0, with --fixed_targets: the like-for-like baseline of --random_obstacles O: O fixed obstacles on the floor, "
+                     "shared by all envs (combine with --no_dedup)")
 a = ap.parse_args()
 if a.random_targets and a.fixed_targets:
     ap.error("--random_targets and --fixed_targets are two legs of one comparison: give one")
+if a.random_obstacles and not a.random_targets:
+    ap.error("--random_obstacles rides on --random_targets")
+if a.fixed_obstacles and not a.fixed_targets:
+    ap.error("--fixed_obstacles is the baseline of --random_obstacles: give it with --fixed_targets")
 dev = torch.device("cuda:0")
 if a.miopen_search:
     torch.backends.cudnn.benchmark = True
@@ -49,14 +59,16 @@ if a.channels_last:
     pol, tgt = pol.to(memory_format=torch.channels_last), tgt.to(memory_format=torch.channels_last)
 names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[a.shapes]
 if a.random_targets:
-    obstacles, targets = [], RandomTargets(a.random_targets)
+    targets = RandomTargets(a.random_targets)
+    obstacles = RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles) if a.random_obstacles else []
 elif a.fixed_targets:
     import numpy as np
     # the three shared targets tools/random_task_throughput.py calls fixed3; beyond three: one draw of tower_setup's
     # distribution (x ~ U[-4, 4], z ~ U[0, 4], y = 0)
     rng = np.random.default_rng(0)
     fixed3 = [(0.5, 0.0, 1.2), (-1.5, 0.0, 2.6), (2.5, 0.0, 0.4)]
-    obstacles = []
+    # --fixed_obstacles O: cube06 obstacles resting on the floor (z = half their 0.6 side), spread over the sampler's x range
+    obstacles = [(-2.4 + 4.8 * i / max(a.fixed_obstacles - 1, 1), 0.0, 0.3) for i in range(a.fixed_obstacles)]
     targets = (fixed3 + [(float(rng.uniform(-4, 4)), 0.0, float(rng.uniform(0, 4))) for _ in range(a.fixed_targets - 3)])[:a.fixed_targets]
 elif a.bridge_length:
     sq, nn = 0.6, a.bridge_length
@@ -68,7 +80,8 @@ env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obs
                      stable_actions_only=a.stable_actions_only)
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
-               episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets))
+               episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets),
+               per_env_obstacles=bool(a.random_obstacles))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False

@@ -224,6 +224,7 @@ SIGNATURES = {
     "bridges_bits_or": [i32, vp, vp, vp, vp],
     "bridges_action_features": [vp, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_to_f32": [i32, vp, vp, vp],
+    "bridges_conv_input_rows": [i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp],
     "bridges_bits_linear": [i32, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_bits_linear2": [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_sigmoid_dot": [i32, vp, i64, vp, i32, vp, vp],

@@ -81,6 +81,22 @@ def soft_update_(target, policy, tau):
     return target
 
 
+def stack_channels(block, action, reward, obstacle):
+    """The 4-channel input of the conv nets, cat([block, action, reward, obstacle], dim=1) -- without the copy when the four
+    arguments already ARE that tensor: the consecutive channel views x[:, 0:1] .. x[:, 3:4] of one contiguous [n, 4, H, W]
+    tensor (ops.conv_input writes it in one pass) come back as x itself.  Anything else is concatenated."""
+    views = (block, action, reward, obstacle)
+    if block.dim() == 4 and block.shape[1] == 1:
+        n, _, H, W = block.shape
+        px = H * W
+        base = block.untyped_storage().data_ptr()
+        if all(v.shape == block.shape and v.dtype == block.dtype and v.device == block.device
+               and v.stride() == (4 * px, px, W, 1) and v.untyped_storage().data_ptr() == base
+               and v.storage_offset() == block.storage_offset() + c * px for c, v in enumerate(views)):
+            return block.as_strided((n, 4, H, W), (4 * px, px, W, 1), block.storage_offset())
+    return torch.cat(views, dim=1)
+
+
 def bias_relu_(x, bias):
     """relu(x + bias[c]) in place on the NCHW output ``x`` [n, C, H, W] of a bias-free convolution (one pass)."""
     L = abi.require_gpu()

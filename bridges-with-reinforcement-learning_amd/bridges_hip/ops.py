@@ -336,6 +336,46 @@ def bits_linear2(bits_a, wt_a, bits_b, wt_b, bits_row_a=None, bits_row_b=None, b
     return out
 
 
+def conv_input(block_bits, action_bits, reward, obstacle_bits, block_row=None, action_row=None, reward_row=None, obstacle_row=None,
+               out=None):
+    """The stacked input of the conv Q-networks in one launch (bridges_conv_input_rows): x [n, 4, 64, 64] float32 whose row r is
+    (raster of ``block_bits[block_row[r]]``, raster of ``action_bits[action_row[r]]``, ``reward[reward_row[r]]`` copied bit for
+    bit, raster of ``obstacle_bits[obstacle_row[r]]``) -- cv.py's cat([block, action, reward, obstacle], dim=1) without the f32
+    images of the rasters.  block_bits / action_bits / obstacle_bits [*, 64] int64, reward [*, 64, 64] (or [*, 4096]) float32; a
+    row index that is None is the identity; a 1-row ``reward`` / ``obstacle_bits`` without an index is shared by every row
+    (stride 0).  n = the length of a row index that is given, else the rows of ``block_bits``.  ``out``: a contiguous float32
+    buffer of n * 4 * 64 * 64 elements to write into (e.g. a slice of a static buffer) instead of a new tensor."""
+    L = abi.require_gpu()
+    block_bits, action_bits, obstacle_bits = block_bits.reshape(-1, 64), action_bits.reshape(-1, 64), obstacle_bits.reshape(-1, 64)
+    for b in (block_bits, action_bits, obstacle_bits):
+        assert b.is_contiguous() and b.dtype == torch.int64
+    reward = reward.reshape(-1, 4096)
+    assert reward.is_contiguous() and reward.dtype == torch.float32
+    rows = [r for r in (block_row, action_row, reward_row, obstacle_row) if r is not None]
+    n = rows[0].numel() if rows else block_bits.shape[0]
+    assert all(r.numel() == n for r in rows), "the row indices differ in length"
+    block_row, action_row, reward_row, obstacle_row = (r.to(torch.int64).contiguous() if r is not None else None
+                                                       for r in (block_row, action_row, reward_row, obstacle_row))
+    assert block_row is not None or block_bits.shape[0] >= n, f"{block_bits.shape[0]} rasters in block_bits for {n} rows"
+    assert action_row is not None or action_bits.shape[0] >= n, f"{action_bits.shape[0]} rasters in action_bits for {n} rows"
+    reward_stride = 0 if (reward_row is None and reward.shape[0] == 1) else 4096
+    obstacle_stride = 0 if (obstacle_row is None and obstacle_bits.shape[0] == 1) else 64
+    assert reward_stride == 0 or reward_row is not None or reward.shape[0] >= n, f"{reward.shape[0]} maps in reward for {n} rows"
+    assert obstacle_stride == 0 or obstacle_row is not None or obstacle_bits.shape[0] >= n, \
+        f"{obstacle_bits.shape[0]} rasters in obstacle_bits for {n} rows"
+    if out is None:
+        out = torch.empty((n, 4, 64, 64), dtype=torch.float32, device=block_bits.device)
+    else:
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * 4 * 4096 and out.device == block_bits.device
+        out = out.view(n, 4, 64, 64)
+    if n == 0:
+        return out
+    abi.check(L.bridges_conv_input_rows(n, _ptr(block_bits), _ptr(block_row), _ptr(action_bits), _ptr(action_row), _ptr(reward),
+                                        _ptr(reward_row), reward_stride, _ptr(obstacle_bits), _ptr(obstacle_row), obstacle_stride,
+                                        _ptr(out), _stream()), "bridges_conv_input_rows")
+    return out
+
+
 def _head_splits(n_rows, n_tiles, slots=512):
     """Column ranges per 128-row workgroup: enough workgroups that the chip's 2 x 256 resident slots stay evenly filled to the
     end of the launch, few enough that the 128-KB row slab each one loads first stays small against its tiles (measured on

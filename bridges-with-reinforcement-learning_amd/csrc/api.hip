@@ -530,6 +530,21 @@ int bridges_bits_to_f32(int32_t n, const uint64_t* bits, float* img, void* strea
     return launch("k_bits_to_f32", k_bits_to_f32, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, n, bits, img);
 }
 
+int bridges_conv_input_rows(int32_t n_rows, const uint64_t* block_bits, const int64_t* block_row, const uint64_t* action_bits,
+                            const int64_t* action_row, const float* reward, const int64_t* reward_row, int64_t reward_stride,
+                            const uint64_t* obstacle_bits, const int64_t* obstacle_row, int64_t obstacle_stride, float* x,
+                            void* stream) {
+    if (n_rows < 0 || !block_bits || !action_bits || !reward || !obstacle_bits || !x) return fail_arg("bridges_conv_input_rows");
+    if (reward_stride != 0 && reward_stride != IMG * IMG) return fail_arg("conv_input_rows: reward_stride must be 0 or 4096");
+    if (obstacle_stride != 0 && obstacle_stride != IMG) return fail_arg("conv_input_rows: obstacle_stride must be 0 or 64");
+    if (!aligned(16, reward, x)) return fail_arg("conv_input_rows: reward and x must be 16-byte aligned");
+    if (n_rows == 0) return BRIDGES_OK;
+    // one short-lived wave per (row, channel) image, a workgroup per row, dispatched in row order (the store structure of
+    // k_raster)
+    return launch("k_conv_input", k_conv_input, dim3((unsigned)n_rows), dim3(256), 0, stream, n_rows, block_bits, block_row, action_bits,
+                  action_row, reward, reward_row, reward_stride, obstacle_bits, obstacle_row, obstacle_stride, x);
+}
+
 static int stability_launch(const bridges_shape* shapes_dev, int32_t n, int32_t K, const double* pose, const double* verts,
                             const int32_t* shape_id, const int32_t* n_blocks, const uint32_t* fixed_mask, double mu,
                             double density, double floor_half_width, double floor_depth, uint8_t* stable, double* info,

@@ -237,6 +237,49 @@ __global__ __launch_bounds__(256) void k_bits_to_f32(int n, const uint64_t* bits
         write_f32_image(img + (size_t)it * IMG * IMG, bits[(size_t)it * IMG + lane], lane);
 }
 
+// The stacked input of the conv Q-networks, x [n_rows, 4, 64, 64] f32 in cv.py's channel order (block, action, reward map,
+// obstacle), straight from the bit-packed rasters and a map index.  One short-lived wave per (row, channel) image of 16 KiB
+// -- the store structure of k_raster / k_bits_to_f32: every wave instruction stores a contiguous 1 KiB of float4 -- and the
+// four waves of a workgroup write the four channels of one row, 64 KiB in address order.  The work item is wave-uniform, so
+// the row indices and the source bases are scalar arithmetic.  The map channel is a copy: its sixteen float4 loads per lane
+// are all issued before the first store, and no arithmetic touches the values (NaN payloads, -0.0, denormals pass as bits).
+// A null *_row means row r itself; a stride of 0 means one shared map / raster for every row.
+__global__ __launch_bounds__(256) void k_conv_input(int n_rows, const uint64_t* __restrict__ block_bits,
+                                                    const int64_t* __restrict__ block_row, const uint64_t* __restrict__ action_bits,
+                                                    const int64_t* __restrict__ action_row, const float* __restrict__ reward,
+                                                    const int64_t* __restrict__ reward_row, int64_t reward_stride,
+                                                    const uint64_t* __restrict__ obstacle_bits,
+                                                    const int64_t* __restrict__ obstacle_row, int64_t obstacle_stride,
+                                                    float* __restrict__ x) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    if (item >= (int64_t)n_rows * 4) return;
+    const int64_t r = item >> 2;
+    const int ch = (int)(item & 3);
+    float* dst = x + (size_t)item * (IMG * IMG);
+    if (ch == 2) {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        const f32x4* src = reinterpret_cast<const f32x4*>(reward + (reward_row ? reward_row[r] : r) * reward_stride);
+        f32x4 v[IMG / 4];
+#pragma unroll
+        for (int i = 0; i < IMG / 4; ++i) v[i] = src[i * WAVE + lane];
+        // Left alone the compiler holds the kernel at 64 VGPRs and starts storing after ten loads.  Three empty statements make
+        // every store depend on every load (an asm statement takes at most 15 in-out operands): 16 loads in flight, then 16 stores.
+        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]),
+                          "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]));
+        asm volatile("" : "+v"(v[15]), "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                          "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]));
+        asm volatile("" : "+v"(v[14]) : "v"(v[15]));
+#pragma unroll
+        for (int i = 0; i < IMG / 4; ++i) reinterpret_cast<f32x4*>(dst)[i * WAVE + lane] = v[i];
+        return;
+    }
+    const uint64_t* words = ch == 0   ? block_bits + (block_row ? block_row[r] : r) * IMG
+                            : ch == 1 ? action_bits + (action_row ? action_row[r] : r) * IMG
+                                      : obstacle_bits + (obstacle_row ? obstacle_row[r] : r) * obstacle_stride;
+    write_f32_image(dst, words[lane], lane);
+}
+
 // K2+K3: is_stable_rbe on independent assemblies; fixed_mask bit b = block b is_static.
 __global__ __launch_bounds__(WAVE) void k_stability(const bridges_shape* shapes, int n, int K, const double* pose_all,
                                                     const double* verts_all, const int32_t* shape_all,

@@ -95,7 +95,8 @@ class ConvNet(nn.Module):
             x = torch.cat([block_features, rest[0]], dim=1)
             return self.mlp(self.layers(x).reshape(-1, self.bottleneck_size))
         binary_features, action_features, reward_features, obstacle_features = rest          # cv.py:67-73
-        x = torch.cat([block_features, action_features, reward_features, obstacle_features], dim=1)
+        from bridges_hip import dqn_ops
+        x = dqn_ops.stack_channels(block_features, action_features, reward_features, obstacle_features)
         x = self.layers(x).reshape(-1, self.bottleneck_size)
         x = self.mlp(torch.cat([x, binary_features], dim=1))
         q_values = x[:, 0]
@@ -266,8 +267,8 @@ class UNet(nn.Module):
         self.outconv = nn.Conv2d(16, n_class, kernel_size=1)
 
     def forward(self, block_features, binary_features, action_features, reward_features, obstacle_features):
-        x = torch.cat([block_features, action_features, reward_features, obstacle_features], dim=1)
         from bridges_hip import dqn_ops
+        x = dqn_ops.stack_channels(block_features, action_features, reward_features, obstacle_features)
         cr = _conv_relu if (_fused_inference(x) and x.shape[-1] % 16 == 0) else (
             dqn_ops.conv3x3_relu_train if (torch.is_grad_enabled() and x.is_cuda) else (lambda conv, t: F.relu(conv(t))))
         if _fused_inference(x) and dqn_ops.conv3x3_relu_o16_applies(x, self.e11):

@@ -519,6 +519,10 @@ def build_parser():
     p.add_argument("--random_obstacles", type=int, default=argparse.SUPPRESS, metavar="O",
                    help="With --random_targets T only: every env also draws O obstacles (x in [-3, 3), z in [0.3, 2.5)) whenever it "
                         "starts an episode, as connecting_setup draws obstacles beside its targets; the evaluation env draws its own.")
+    p.add_argument("--task_channels", action='store_true', default=argparse.SUPPRESS,
+                   help="With --random_targets T [--random_obstacles O] and --model ConvNet or UNet at 64x64: train the conv "
+                        "Q-network on the per-env tasks -- every row is fed the reward map and the obstacle raster of its env as "
+                        "image channels, written with its block and action rasters by one kernel (bridges_conv_input_rows).")
     return p
 
 
@@ -527,8 +531,12 @@ EVAL_DEFAULTS = dict(eval_envs=0, eval_epsilon=0.0)
 
 def check_random_targets(args):
     """--random_targets T is the vectorised SuccessorMLP loop on per-env random tasks, --random_obstacles O adds O random
-    obstacles per env to it; every other combination is refused in words (SystemExit), before anything touches the GPU."""
+    obstacles per env to it, --task_channels runs ConvNet / UNet on them instead; every other combination is refused in words (SystemExit), before anything touches the GPU."""
     T, O = args.get('random_targets'), args.get('random_obstacles')
+    conv = bool(args.get('task_channels', False))
+    if conv and T is None:
+        raise SystemExit("--task_channels is valid only together with --random_targets T: it feeds the conv Q-networks the task "
+                         "of every env, and without --random_targets all envs share one task")
     if O is not None and T is None:
         raise SystemExit("--random_obstacles O is valid only together with --random_targets T: per-env obstacles ride on the "
                          "per-env task buffers and records of the loop on per-env tasks")
@@ -543,14 +551,20 @@ def check_random_targets(args):
         raise SystemExit("--random_targets draws every env's task (tower_setup: random targets, no obstacles): it cannot be "
                          "combined with --tower_height or --bridge_length, which name one fixed task")
     if args['num_envs'] <= 1:
-        raise SystemExit("--random_targets needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
-                         "fixed tasks of --tower_height / --bridge_length only")
-    if args['model'] != 'SuccessorMLP':
+        raise SystemExit(f"--random_targets{' / --task_channels' if conv else ''} needs the vectorised loop (--num_envs N, N > 1): "
+                         "the single-env loop trains on the fixed tasks of --tower_height / --bridge_length only")
+    if conv and args['model'] == 'SuccessorMLP':
+        raise SystemExit("--task_channels is for the conv Q-networks (--model ConvNet or UNet): --model SuccessorMLP trains on "
+                         "--random_targets without it")
+    if not conv and args['model'] != 'SuccessorMLP':
         raise SystemExit(f"--random_targets{' / --random_obstacles' if O is not None else ''} trains --model SuccessorMLP only: "
                          f"{args['model']} takes the reward map as an image "
-                         "channel and its rows are shared by state alone (per-env tasks for the conv nets are not built)")
+                         "channel and its rows are shared by state alone (add --task_channels to train ConvNet or UNet on per-env "
+                         "tasks)")
     if tuple(args['image_size']) != (64, 64):
-        raise SystemExit("--random_targets needs --image_size 64x64 (the factored acting path of SuccessorMLP)")
+        raise SystemExit("--random_targets needs --image_size 64x64 (the stacked conv input of --task_channels is built for 64x64)"
+                         if conv else "--random_targets needs --image_size 64x64 (the factored acting path of SuccessorMLP; "
+                                      "--task_channels is built for 64x64 as well)")
     if args['shapes'] != 'trapezoid':
         raise SystemExit("--random_targets is tower_setup: --shapes trapezoid")
 

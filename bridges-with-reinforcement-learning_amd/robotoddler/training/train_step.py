@@ -8,7 +8,7 @@ import warnings
 import numpy as np
 import torch
 
-from bridges_hip import dqn_ops
+from bridges_hip import dqn_ops, ops
 
 
 def graph_enabled(default):
@@ -31,6 +31,16 @@ def fused_step_enabled(net, loss_parts):
     return (isinstance(net, SuccessorMLP) and os.environ.get("BRIDGES_FUSED_MLP_STEP", "1") != "0"
             and set(loss_parts) <= {'mse_q_values', 'mse_block_features'}
             and all(p.dtype == torch.float32 for p in net.parameters()))
+
+
+def conv_task_net(net):
+    """True for the conv Q-networks that take a task as image channels at 64x64: a ConvNet(in_channels=4, img_size=(64, 64)) or
+    the U-Net Policy -- the nets whose input rows ops.conv_input builds."""
+    from robotoddler.models.cv import ConvNet, Policy
+    if isinstance(net, Policy):
+        return True
+    return (isinstance(net, ConvNet) and net.layers[0].layers[0].in_channels == 4
+            and net.bottleneck_size == 128 * (64 // 16) * (64 // 16))
 
 
 def sync_optimizer(policy_net):
@@ -83,9 +93,16 @@ class CapturedTrainStep:
         # obstacle_rows (per-env obstacles; with task_rows only): every transition has an obstacle raster of its own too --
         # ``run`` takes them bit-packed as obstacle [n * B, 64] int64 and copies them into a static [n_max * B, 64] buffer the
         # captured launches read (bridges_mlp_input_task_rows / _batches_task_rows); task = (None, None)
+        # task_rows with the autograd body (fused=False; the conv nets at 64x64 only): ``run`` takes block / action BIT-PACKED
+        # ([n * B, 64] int64 each), and ONE ops.conv_input launch per call writes the stacked rows of all n * B transitions into
+        # the static x_all [n_max * B, 4, 64, 64] -- no f32 block / action images, no staging copies; the captured step takes
+        # batch `counter` of x_all.  task = (None, obstacle_bits [64] int64): the shared obstacle raster, bit-packed as well
         self.task_rows, self.obstacle_rows = bool(task_rows), bool(obstacle_rows)
-        if self.task_rows and not (fused and task is not None and task[0] is None):
-            raise ValueError("per-transition reward maps need the hand-written step (fused=True) and task=(None, obstacle)")
+        self.conv_rows = self.task_rows and not fused and conv_task_net(net) and self.img == (64, 64)
+        if self.task_rows and not ((fused or self.conv_rows) and task is not None and task[0] is None):
+            raise ValueError("per-transition reward maps need the hand-written step (fused=True) -- or, with the autograd body, a "
+                             "conv net that takes the task as image channels (ConvNet(in_channels=4, img_size=(64, 64)) or Policy "
+                             "at 64x64) -- and task=(None, obstacle)")
         if self.obstacle_rows and not (self.task_rows and task[1] is None):
             raise ValueError("per-transition obstacle rasters need per-transition reward maps (task_rows=True) and task=(None, None)")
         if self.task_rows and not self.obstacle_rows and task[1] is None:
@@ -116,11 +133,15 @@ class CapturedTrainStep:
         z = lambda *s: torch.zeros(s, device=dev)
         self._graphs, self.n_max = {}, n
         self.state = dict(n_max=n, fused=self.fused)        # of this build; the guard keeps its snapshot here
-        self.block, self.action, self.binary, self.q = z(N, 1, *S), z(N, 1, *S), z(N, 6), z(N)
+        self.binary, self.q = z(N, 6), z(N)
+        self.block, self.action = (None, None) if self.conv_rows else (z(N, 1, *S), z(N, 1, *S))
+        self.x_all = z(N, 4, *S) if self.conv_rows else None
         self.sf = z(N, px) if self.use_sf else None
         self.counter, self.losses = torch.zeros((), dtype=torch.int64, device=dev), z(n)
         self.lane, self.iota = torch.arange(B, device=dev), torch.arange(n, device=dev)
-        if self.obstacle_rows:
+        if self.conv_rows:                                 # read from the caller's tensors by the one launch of a call
+            self.reward, self.obstacle = None, (None if self.obstacle_rows else self.task[1].reshape(1, 64).contiguous())
+        elif self.obstacle_rows:
             self.reward, self.obstacle = z(N, px), torch.zeros((N, 64), dtype=torch.int64, device=dev)
         elif self.task_rows:
             self.reward, self.obstacle = z(N, px), self.task[1].reshape(-1).contiguous()
@@ -154,10 +175,14 @@ class CapturedTrainStep:
     def _autograd_body(self):
         B, S = self.B, self.img
         idx = self.lane + self.counter * B
-        reward = self.reward.view(1, 1, *S).expand(B, -1, -1, -1)
-        obstacle = self.obstacle.view(1, 1, *S).expand(B, -1, -1, -1)
-        q, sf, _ = self.net(self.block.index_select(0, idx), self.binary.index_select(0, idx), self.action.index_select(0, idx),
-                            reward, obstacle)
+        if self.conv_rows:
+            x = self.x_all.index_select(0, idx)            # the four channel views: the net stacks them back without a copy
+            q, sf, _ = self.net(x[:, 0:1], self.binary.index_select(0, idx), x[:, 1:2], x[:, 2:3], x[:, 3:4])
+        else:
+            reward = self.reward.view(1, 1, *S).expand(B, -1, -1, -1)
+            obstacle = self.obstacle.view(1, 1, *S).expand(B, -1, -1, -1)
+            q, sf, _ = self.net(self.block.index_select(0, idx), self.binary.index_select(0, idx), self.action.index_select(0, idx),
+                                reward, obstacle)
         # the MSE losses, but the 131 072-element mean is reduced row-wise and then over the 32 rows: the multi-workgroup
         # (semaphore) reduction nn.MSELoss launches for it returned garbage on some replays (negative "MSE", ROCm 7.2 + torch
         # 2.10; eager never) while every single-workgroup reduction was right.  The value is logged through a one-hot of the
@@ -197,7 +222,8 @@ class CapturedTrainStep:
         """n optimiser steps on batches 0 .. n-1 of the per-call arrays (rows b * B .. b * B + B - 1 of block / action /
         binary / q / sf; reward / obstacle: one map for all rows, unused with ``task`` -- except with ``task_rows``, where
         reward [n * B, px] holds the map of every transition, and with ``obstacle_rows``, where obstacle [n * B, 64] int64 holds
-        the bit-packed obstacle raster of every transition) -> the device tensor of the n losses
+        the bit-packed obstacle raster of every transition; ``task_rows`` with the autograd body: block / action [n * B, 64]
+        int64 are the bit-packed rasters of every transition too) -> the device tensor of the n losses
         (a view of the driver's buffer, valid until its next call), or None: the caller steps eagerly."""
         graphs = not self.disabled and graph_enabled(self.graph_default)
         if not graphs or self.calls < self.warmup:
@@ -228,11 +254,16 @@ class CapturedTrainStep:
                 self._disable()
                 return self.run(n, block, action, binary, reward, obstacle, q, sf)
         N = n * self.B
-        if self.task_rows:
+        if self.task_rows and not self.conv_rows:
             _put(self.reward, reward.reshape(N, -1))       # before the first-layer rows are built from it
             if self.obstacle_rows:
                 _put(self.obstacle, obstacle.reshape(N, 64))
-        if self.fused and self.prepared:
+        if self.conv_rows:
+            # the stacked rows of all n batches in one launch, straight from the caller's bit rasters and maps
+            ops.conv_input(block, action, reward.reshape(N, -1).contiguous(), obstacle if self.obstacle_rows else self.obstacle,
+                           out=self.x_all[:N])
+            _put(self.binary, binary)
+        elif self.fused and self.prepared:
             # the first layer's input rows of all n batches in one launch, straight from the caller's tensors (no staging
             # copy of the block / action images: a replayed step reads only x_all, q and sf)
             self.step.prepare_inputs(n, block.reshape(N, -1).contiguous(), action.reshape(N, -1).contiguous(),

@@ -48,7 +48,7 @@ OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
-                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False):
+                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -58,8 +58,17 @@ class VecDQN:
         (VecAssemblyGym(obstacles=RandomObstacles()) or set_obstacles).  Acting and the target forward add every env's obstacle
         raster to the first layer as a second bit-packed operand (bridges_bits_linear2), a record ends in the targets AND the
         obstacles of its transition, replay filters the next states' candidates against them, and the optimiser step reads a
-        bit-packed obstacle raster per transition."""
+        bit-packed obstacle raster per transition.
+        ``task_channels=True`` (with per_env_tasks=True only): the conv Q-networks on per-env tasks -- a ConvNet(in_channels=4,
+        img_size=(64, 64)) or the U-Net Policy, which take the task as two image channels.  Every row a net is fed gets the
+        reward map and the obstacle raster of its env (of its transition, in replay) beside its block and action rasters, all
+        four channels written by one launch from the bit-packed rasters and a map index (ops.conv_input); rows are shared by
+        (state, candidate, stable flag, task); the optimiser step is the autograd body on per-transition rows.  Neither the
+        rollout env nor the replay scratch env needs f32 rasters in this mode."""
         self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
+        self.task_channels = bool(task_channels)
+        if self.task_channels:
+            self._check_task_channels(policy_net, target_net, env)
         if getattr(env, "per_env_obstacles", False) and not self.per_env_obstacles:
             raise ValueError("VecDQN cannot train on a rollout env with per-env obstacles (RandomObstacles / set_obstacles) unless it "
                              "is built with per_env_tasks=True AND per_env_obstacles=True: by default the first layer's "
@@ -76,7 +85,7 @@ class VecDQN:
                              "built with per_env_tasks=True: by default envs in the same state share candidate rows whatever "
                              "their task (bridges_env_groups keys rows by state alone), the factored SuccessorMLP acting path "
                              "and the captured train steps hold ONE reward map, and a replay record does not store its task")
-        if self.per_env_tasks:
+        if self.per_env_tasks and not self.task_channels:
             loss_parts = loss_function.split('+')
             if not getattr(env, "per_env_tasks", False):
                 raise ValueError("VecDQN(per_env_tasks=True) needs a rollout env with per-env tasks "
@@ -84,7 +93,8 @@ class VecDQN:
             for name, net in (("policy", policy_net), ("target", target_net)):
                 if not hasattr(net, "q_from_first_layer"):
                     raise ValueError(f"VecDQN(per_env_tasks=True): the {name} net is a {type(net).__name__}; only SuccessorMLP "
-                                     "weighs its output with a per-row reward map (the conv nets take the map as an image channel)")
+                                     "weighs its output with a per-row reward map (the conv nets take the map as an image channel: "
+                                     "build the agent with task_channels=True for them)")
                 if tuple(getattr(net, "img_size", (64, 64))) != (64, 64) or env.img != 64:
                     raise ValueError(f"VecDQN(per_env_tasks=True): the factored acting path is built for 64x64 images, the {name} "
                                      f"net has {tuple(getattr(net, 'img_size', ()))} and the env {env.img}x{env.img}")
@@ -130,6 +140,23 @@ class VecDQN:
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device) if episode_stats else None)
         self._eval_state = {}                                # evaluate(): (random stream, EpisodeStats, count images) per env shape
 
+    def _check_task_channels(self, policy_net, target_net, env):
+        """The conditions of task_channels=True, decided from the arguments alone."""
+        if not self.per_env_tasks:
+            raise ValueError("VecDQN(task_channels=True) needs per_env_tasks=True: the option feeds the conv Q-networks the task of "
+                             "every row, which only an agent on per-env tasks has")
+        if not getattr(env, "per_env_tasks", False):
+            raise ValueError("VecDQN(task_channels=True) needs a rollout env with per-env tasks "
+                             "(VecAssemblyGym(targets=RandomTargets()) or set_targets); this env has one fixed task")
+        for name, net in (("policy", policy_net), ("target", target_net)):
+            if not T.conv_task_net(net):
+                raise ValueError(f"VecDQN(task_channels=True): the {name} net is a {type(net).__name__}; the option is for the conv "
+                                 "Q-networks, ConvNet(in_channels=4, img_size=(64, 64)) or Policy (a SuccessorMLP trains on "
+                                 "per-env tasks without it)")
+        if env.img != 64:
+            raise ValueError(f"VecDQN(task_channels=True): the stacked input is built for 64x64 images (bridges_conv_input_rows), "
+                             f"the env has {env.img}x{env.img}")
+
     ROW_CHUNK = 2048       # rows per forward call: ONE input shape for the whole run (MIOpen tunes per shape)
     DEDUP_STATES = True    # envs in the same state share one set of candidate rows (tests compare with False)
     DEDUP_ROWS = True      # conv nets: feed every distinct (state, candidate, stable flag) input once (tests compare with False)
@@ -167,6 +194,9 @@ class VecDQN:
         candidates.  Rows are keyed by a 64-bit hash of their bit rasters, grouped with torch.unique, and every row is then
         compared WORD FOR WORD with the representative of its group (a hash collision -- probability ~ n^2 / 2^64 -- sends the
         call down the plain path), so feeding only the representatives and copying their outputs is exact.
+        An env with per-env tasks: the map and the obstacle raster of a row are its env's, so the words that determine them --
+        the int64 bit patterns of env_targets[e], and of env_obstacles[e] on per-env obstacles, the words
+        state_groups(task=True) keys on -- are folded into the key and compared as well.
         -> (rep [m]: positions into idx of one row per distinct input, inverse [n]: group of every row) or None."""
         n = idx.numel()
         if not self.DEDUP_ROWS or n < 2:
@@ -178,6 +208,9 @@ class VecDQN:
         cb = env.cand_bits.index_select(0, idx)                                    # [n, 64] int64
         flag = stable_flag.to(torch.int64)
         hs = (env.state_bits * m[0]).sum(dim=1) + flag * 0x51ED270B27B4F3D           # [E]  (int64 arithmetic wraps)
+        task = self._task_words(env)                                                 # [E, w] int64 or None
+        if task is not None:
+            hs = hs * 0x1E3779B97F4A7C15 + (task * self._task_hash_mult(task.shape[1])).sum(dim=1)
         key = hs.index_select(0, row_env) * 0x2545F4914F6CDD1D + (cb * m[1]).sum(dim=1)
         key = key ^ (key >> 29)
         uniq, inverse = torch.unique(key, return_inverse=True)                      # (one wait: the number of groups)
@@ -191,9 +224,29 @@ class VecDQN:
         same = ((cb == cb.index_select(0, r)).all(dim=1)
                 & (env.state_bits.index_select(0, row_env) == env.state_bits.index_select(0, renv)).all(dim=1)
                 & (flag.index_select(0, row_env) == flag.index_select(0, renv)))
+        if task is not None:
+            same = same & (task.index_select(0, row_env) == task.index_select(0, renv)).all(dim=1)
         if not bool(same.all()):
             return None
         return rep, inverse
+
+    @staticmethod
+    def _task_words(env):
+        """[E, 3 T (+ 3 O)] int64: the bit patterns of every env's own targets (and obstacles), None without per-env tasks."""
+        if not getattr(env, "per_env_tasks", False):
+            return None
+        E = env.env_targets.shape[0]
+        words = env.env_targets.reshape(E, -1)
+        if getattr(env, "per_env_obstacles", False):
+            words = torch.cat([words, env.env_obstacles.reshape(E, -1)], dim=1)
+        return words.contiguous().view(torch.int64)
+
+    def _task_hash_mult(self, w):
+        m = getattr(self, "_task_mult", None)
+        if m is None or m.numel() != w:
+            g = torch.Generator().manual_seed(0x7a5c)
+            m = self._task_mult = (torch.randint(-2 ** 62, 2 ** 62, (w,), generator=g, dtype=torch.int64) | 1).to(self.device)
+        return m
 
     def _forward_rows(self, net, env, idx, row_env, stable_flag):
         """net(...) over the candidate rows in chunks of ROW_CHUNK rows; the last chunk is padded with copies of row 0
@@ -222,6 +275,18 @@ class VecDQN:
     # ------------------------------------------------------------------ features of the rows a net is fed
     def _row_features(self, env, idx, row_env, stable_flag):
         n = idx.numel()
+        if self.task_channels:
+            # the conv nets on per-env tasks: all four channels of every row in ONE launch, straight from the bit-packed rasters
+            # and the env's maps (bridges_conv_input_rows); the nets get the channel views and stack them back without a copy
+            if getattr(env, "per_env_obstacles", False):
+                x = ops.conv_input(env.state_bits, env.cand_bits, env.reward_maps, env.env_obstacle_bits, block_row=row_env,
+                                   action_row=idx, reward_row=row_env, obstacle_row=row_env)
+            else:
+                x = ops.conv_input(env.state_bits, env.cand_bits, env.reward_maps, env.obstacle_bits.reshape(1, 64),
+                                   block_row=row_env, action_row=idx, reward_row=row_env)
+            binary = torch.zeros((n, 6), dtype=torch.float32, device=self.device)
+            binary[:, 0] = stable_flag[row_env].float()
+            return x[:, 0:1], binary, x[:, 1:2], x[:, 2:3], x[:, 3:4]
         if env.cand_raster is not None:
             block = env.crop(env.state_raster[row_env]).unsqueeze(1)     # crop: no-op for the 64x64 default
             action = env.crop(env.cand_raster[idx]).unsqueeze(1)
@@ -267,7 +332,7 @@ class VecDQN:
         of every row, from which the successor features of selected rows follow without a second first-layer pass."""
         net.eval()
         if not self._factored(net):
-            if env.cand_raster is None:
+            if env.cand_raster is None and not self.task_channels:
                 raise ValueError("this Q-network acts on f32 rasters: create the rollout env with f32_rasters=True")
             return self._forward_rows(net, env, idx, row_env, stable)[0]
         # the first layer consumes the BIT-PACKED rasters (bridges_bits_linear): a raster times a weight slice is the
@@ -343,7 +408,7 @@ class VecDQN:
         if idx.numel():
             step_of_row = env.n_blocks[row_env].long()
             q = self._policy_q(env, idx, row_env, stable)
-            if self._factored(self.policy_net):
+            if self._factored(self.policy_net) or self.task_channels:
                 # overlap of every candidate with the count image of its episode step, straight from the bit-packed
                 # rasters (exact: integer-valued sums)
                 join = ops.bits_dot(env.cand_bits, step_images, step_of_row, bits_row=idx)
@@ -449,7 +514,7 @@ class VecDQN:
     def _replay_f32(self):
         """The scratch env writes f32 rasters of every raw candidate only for nets that consume them row by row; the
         factored MLP reads the bit rasters and expands the few rows it needs (the arg-max row of each transition)."""
-        return not self._factored(self.target_net)
+        return not (self._factored(self.target_net) or self.task_channels)
 
     @torch.no_grad()
     def _targets(self, rec):
@@ -462,7 +527,10 @@ class VecDQN:
         returned then, the [n, px] maps of the transitions (a view of the scratch env's reward_maps: valid until the next call).
         Per-env obstacles: the tails' obstacles go in beside the targets (load_task: one bridges_env_load_targets), so the
         rasteriser filters every next state's candidates against its transition's own obstacles; a seventh value is returned,
-        the bit-packed obstacle rasters of the transitions [n, 64] int64 (a view of the scratch env's env_obstacle_bits)."""
+        the bit-packed obstacle rasters of the transitions [n, 64] int64 (a view of the scratch env's env_obstacle_bits).
+        task_channels: the target net's rows come from _row_features on the scratch env (one ops.conv_input per chunk), block_f
+        and action_f are None -- no f32 image of a transition is built -- and two more values follow the task's: the bit
+        rasters of s and of the action block, [n, 64] int64 each, from which the train step builds its rows."""
         n = rec.shape[0]
         renv = self._replay_env(n)
         E = renv.E
@@ -482,12 +550,14 @@ class VecDQN:
         # records into the scratch env (envs beyond n repeat record 0 and are sliced off below); R.unpack_states +
         # load_states + prefix_state_bits is the torch formulation the tests compare it with.
         bits_s, lin, stable_s, done_rec, stable_n = renv.load_records(rec.contiguous())
-        block_f = renv.crop(ops.bits_to_f32(bits_s)).unsqueeze(1)
-        action_f = renv.crop(ops.bits_to_f32(renv.state_bits & ~bits_s)).unsqueeze(1)         # s' minus s = the new block
+        use_sf = 'mse_block_features' in self.loss_parts
+        action_bits = renv.state_bits & ~bits_s                                               # s' minus s = the new block
+        block_f = None if self.task_channels else renv.crop(ops.bits_to_f32(bits_s)).unsqueeze(1)
+        # (task_channels: the action raster as f32 only where the successor-feature target adds it)
+        action_f = renv.crop(ops.bits_to_f32(action_bits)).unsqueeze(1) if (use_sf or not self.task_channels) else None
         stable_n = stable_n.bool()
         idx, row_env, seg, _rep = self._rows(renv, stable_n)      # transitions with the same next state share its rows
         done = done_rec.bool() | (renv.n_valid[:E] == 0)
-        use_sf = 'mse_block_features' in self.loss_parts
         if idx.numel() and self._factored(self.target_net):
             # q of every next candidate through the factored forward on the bit-packed rasters; the 8204-wide output
             # (successor features) is only needed for the arg-max row of each transition: its channel 0 from the first-layer
@@ -502,12 +572,15 @@ class VecDQN:
             nsf0 = lambda best: nsf[:, 0].index_select(0, best if inverse is None else inverse.index_select(0, best)).reshape(E, -1).contiguous()
         if idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
-                                                       action_raster=action_f.squeeze(1), lin=lin)
+                                                       action_raster=action_f.squeeze(1) if use_sf else None, lin=lin)
         else:
             q_target = lin
             sf_target = action_f.reshape(E, -1) if use_sf else None
         binary = torch.zeros((E, 6), dtype=torch.float32, device=self.device)
         binary[:, 0] = stable_s
+        if self.task_channels:
+            out = (None, binary[:n], None, q_target[:n], (sf_target[:n] if use_sf else None), renv.reward_maps_img[:n].reshape(n, -1))
+            return out + ((renv.env_obstacle_bits[:n],) if self.per_env_obstacles else ()) + (bits_s[:n], action_bits[:n])
         out = (block_f[:n], binary[:n], action_f[:n], q_target[:n], (sf_target[:n] if use_sf else None))
         if self.per_env_obstacles:
             return out + (renv.reward_maps_img[:n].reshape(n, -1), renv.env_obstacle_bits[:n])
@@ -524,7 +597,8 @@ class VecDQN:
     def _train_step(self, n_steps):
         """The policy net's captured-step driver as this loop uses it: two eager calls before the first capture (they
         initialise the optimiser state and the library workspaces a capture needs), the hand-written step for SuccessorMLP
-        with its first-layer rows built per call, the task maps of the rollout env."""
+        with its first-layer rows built per call, the task maps of the rollout env (task_channels: the conv nets' autograd step
+        on per-transition rows, the shared obstacle raster bit-packed)."""
         from robotoddler.models.cv import ConvNet, Policy, SuccessorMLP
         env = self.env
         return T.CapturedTrainStep.of(self.policy_net, self.opt, self.B, self.loss_parts, n_steps, owner=self, img=(env.img, env.img),
@@ -533,7 +607,8 @@ class VecDQN:
                                       eager_body=False, prepared=True, task_rows=self.per_env_tasks,
                                       obstacle_rows=self.per_env_obstacles,
                                       task=((None if self.per_env_tasks else env.reward_features),
-                                            (None if self.per_env_obstacles else env.obstacle_raster)))
+                                            (None if self.per_env_obstacles else
+                                             (env.obstacle_bits if self.task_channels else env.obstacle_raster))))
 
     @property
     def _graph_state(self):
@@ -563,6 +638,9 @@ class VecDQN:
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
         rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
         block_f, binary, action_f, q_target, sf_target, *task = self._targets(rec)
+        if self.task_channels:                               # the transitions' bit rasters stand in for their f32 images
+            block_f, action_f = task[-2:]
+            task = task[:-2]
         maps = task[0] if task else None                     # per-env tasks: the reward map of every transition [n_steps * B, px]
         obst_bits = task[1] if len(task) > 1 else None       # per-env obstacles: its bit-packed obstacle raster [n_steps * B, 64]
         drv = self._train_step(n_steps)
@@ -570,17 +648,25 @@ class VecDQN:
         if out is None:
             drv = None
             S = self.env.img
-            reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1) if maps is None else None
-            obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1) if obst_bits is None else None
+            if self.task_channels:
+                # the rows of all n_steps * B transitions as the captured step builds them: one launch from bits and maps
+                x = ops.conv_input(block_f, action_f, maps, obst_bits if obst_bits is not None else self.env.obstacle_bits.reshape(1, 64))
+            else:
+                reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1) if maps is None else None
+                obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1) if obst_bits is None else None
             self.policy_net.train()
             losses = []
             for i in range(n_steps):
                 sl = slice(i * B, (i + 1) * B)
-                if maps is not None:
-                    reward = maps[sl].reshape(B, 1, S, S)
-                if obst_bits is not None:
-                    obstacle = ops.bits_to_f32(obst_bits[sl]).reshape(B, 1, S, S)
-                q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
+                if self.task_channels:
+                    xb = x[sl]
+                    q, sf, _ = self.policy_net(xb[:, 0:1], binary[sl], xb[:, 1:2], xb[:, 2:3], xb[:, 3:4])
+                else:
+                    if maps is not None:
+                        reward = maps[sl].reshape(B, 1, S, S)
+                    if obst_bits is not None:
+                        obstacle = ops.bits_to_f32(obst_bits[sl]).reshape(B, 1, S, S)
+                    q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
                 loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
                 self.opt.zero_grad()
                 if self._eager_reduce is None:
@@ -717,6 +803,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     geoms = [load_urdf(f"shapes/{n}.urdf") for n in names]
     random_targets = args.get('random_targets')
     random_obstacles = args.get('random_obstacles')
+    task_channels = bool(args.get('task_channels', False))
     if random_targets:
         # tower_setup(num_targets=T) per env and episode (gym_env.py:64-79 of the reference): no obstacles, every env draws
         # its own targets whenever it starts an episode; --random_obstacles O: and O obstacles beside them, as connecting_setup
@@ -736,14 +823,15 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     policy_net, target_net = make_nets(args, device)
     env = VecAssemblyGym(args['num_envs'], geoms, obstacles, targets, max_steps=args['max_steps'],
                          seed=seed * 1000003 + rank, device=device, env_id_base=rank * args['num_envs'],
-                         f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net),
+                         f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net) and not task_channels,
                          img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
     opt = torch.optim.Adam(policy_net.parameters(), lr=args['learning_rate'], fused=True)    # one launch for all tensors
     capacity = max(args['replay_buffer_capacity'], 4 * args['num_envs'] * world)
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
-                   per_env_tasks=bool(random_targets), per_env_obstacles=bool(random_obstacles))
+                   per_env_tasks=bool(random_targets), per_env_obstacles=bool(random_obstacles),
+                   task_channels=task_channels)
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -754,7 +842,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         eval_targets = RandomTargets(random_targets) if random_targets else targets
         eval_obstacles = RandomObstacles([OBSTACLE_RANGE] * random_obstacles) if random_obstacles else obstacles
         eval_env = VecAssemblyGym(eval_envs, geoms, eval_obstacles, eval_targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
-                                  device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net),
+                                  device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net) and not task_channels,
                                   img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
     history, t0, it = [], time.time(), 0
     next_ckpt = next_multiple(0, args['checkpoint_every'])

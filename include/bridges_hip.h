@@ -328,6 +328,20 @@ int bridges_action_features(const bridges_shape* shapes_dev, int32_t n, const do
 int bridges_bits_or(int32_t n_groups, const int32_t* ranges, const uint64_t* bits, uint64_t* out, void* stream);
 /* bit raster -> f32 image. */
 int bridges_bits_to_f32(int32_t n, const uint64_t* bits, float* img, void* stream);
+/* The stacked input of the conv Q-networks (ConvNet / UNet, cv.py's cat([block, action, reward, obstacle], dim=1)) in one pass:
+ * x [n_rows, 4, 64, 64] f32, contiguous NCHW, row r =
+ *   channel 0: raster(block_bits [*,64] u64 row block_row[r]),  channel 1: raster(action_bits [*,64] u64 row action_row[r])
+ *              -- the bit order of bridges_bits_to_f32 / bridges_bits_linear (pixel (y, x) = bit x of word y), exactly 0.0f / 1.0f;
+ *   channel 2: the 4096 floats at reward + reward_row[r] * reward_stride, copied bit for bit (NaN payloads, -0.0, denormals);
+ *   channel 3: the raster of the 64 words at obstacle_bits + obstacle_row[r] * obstacle_stride.
+ * A NULL *_row = row r itself (the convention of bits_row).  reward_stride must be 0 or 4096, obstacle_stride 0 or 64 (0 = one
+ * shared map / raster for every row); any other stride, n_rows < 0, a NULL data pointer or NULL x returns -1 and launches
+ * nothing; n_rows == 0 succeeds and launches nothing.  reward and x must be 16-byte aligned.  Index values are the caller's
+ * contract, as for bridges_bits_linear. */
+int bridges_conv_input_rows(int32_t n_rows, const uint64_t* block_bits, const int64_t* block_row, const uint64_t* action_bits,
+                            const int64_t* action_row, const float* reward, const int64_t* reward_row, int64_t reward_stride,
+                            const uint64_t* obstacle_bits, const int64_t* obstacle_row, int64_t obstacle_stride, float* x,
+                            void* stream);
 /* K8: linear layer over flattened binary 64x64 rasters, fed with the bit-packed rasters (replaces the product of
  * SuccessorMLP's first layer with the action / block image, robotoddler/models/cv.py:95-97):
  *   out[r, :] = (base ? base[base_row ? base_row[r] : 0, :] : 0) + sum_{p set in bits[bits_row ? bits_row[r] : r]} wt[p, :]

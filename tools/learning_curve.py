@@ -29,13 +29,17 @@ ap.add_argument("--eval_envs", type=int, default=0, help="> 0: greedy evaluation
 ap.add_argument("--eval_epsilon", type=float, default=0.0, help="exploration rate of the evaluation episodes")
 ap.add_argument("--random_targets", type=int, default=0, metavar="T",
                 help="> 0: per-env random tasks instead of the tower (tower_setup(num_targets=T) per env and episode, no obstacles; "
-                     "SuccessorMLP only); --eval_envs then evaluates on a fixed held-out set of N tasks")
+                     "SuccessorMLP, or ConvNet / UNet with --task_channels); --eval_envs then evaluates on a fixed held-out set of N tasks")
 ap.add_argument("--random_obstacles", type=int, default=0, metavar="O",
                 help="> 0, with --random_targets: O obstacles per env and episode beside the targets, x ~ U[-3, 3), z ~ U[0.3, 2.5); "
                      "the evaluation env draws its own")
+ap.add_argument("--task_channels", action="store_true",
+                help="with --random_targets and --model ConvNet | UNet: the conv Q-network on the per-env tasks (VecDQN(task_channels=True))")
 a = ap.parse_args()
 if a.random_obstacles and not a.random_targets:
     ap.error("--random_obstacles rides on --random_targets")
+if a.task_channels and not a.random_targets:
+    ap.error("--task_channels rides on --random_targets")
 dev = torch.device("cuda:0")
 args = vars(build_parser().parse_args(["--model", a.model, "--loss_function", a.loss]))
 H = 0.8
@@ -47,14 +51,15 @@ if a.random_targets:
 if a.random_obstacles:
     obstacles = lambda: RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles)
 env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=0, device=dev,
-                     f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
+                     f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels, stable_actions_only=a.stable_actions_only)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
                eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets),
-               per_env_obstacles=bool(a.random_obstacles))
+               per_env_obstacles=bool(a.random_obstacles), task_channels=a.task_channels)
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
-                              f32_rasters=VecDQN.acting_needs_f32_rasters(pol), stable_actions_only=a.stable_actions_only)
+                              f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels,
+                              stable_actions_only=a.stable_actions_only)
 r4 = lambda v: None if v is None else round(v, 4)
 t0 = time.time()
 deferred = []

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel stats of the bench modes (run on the MI355X box through gpurun, from the repo root):
-#   tools/profile_modes.sh <tag> [sim] [cand] [hex] [mlp] [mlp_stable] [conv] [conv_all] [unet] [unet_all] [tasks_fixed] [tasks_random] [obst_fixed] [obst_random] [mlp_tasks_fixed] [mlp_tasks_random] [mlp_obst_fixed] [mlp_obst_random]     (*_all: every candidate row fed, --no_dedup)
+#   tools/profile_modes.sh <tag> [sim] [cand] [hex] [mlp] [mlp_stable] [conv] [conv_all] [unet] [unet_all] [tasks_fixed] [tasks_random] [obst_fixed] [obst_random] [mlp_tasks_fixed] [mlp_tasks_random] [mlp_obst_fixed] [mlp_obst_random] [conv_tasks_fixed] [conv_tasks_random]     (*_all: every candidate row fed, --no_dedup)
 # Writes gpurun_out/prof_<tag>_<mode>/ (trace + stats) and gpurun_out/prof_<tag>_<mode>.json (the bench line).
 set -o pipefail
 tag=$1; shift
@@ -26,6 +26,8 @@ for mode in "$@"; do
     mlp_tasks_random) args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --random_targets 3" ;;   # per-row head, keyed groups, k_task_features in replay
     mlp_obst_fixed)  args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --fixed_targets 3 --fixed_obstacles 2 --no_dedup" ;;
     mlp_obst_random) args="$root/tools/train_throughput.py --locksteps 6 --warmup 6 --envs 4096 --max_steps 15 --model SuccessorMLP --loss mse_block_features --random_targets 3 --random_obstacles 2" ;;   # k_bits_linear2, k_mlp_input<rows, obstacle bits>
+    conv_tasks_fixed)  args="$root/tools/train_throughput.py --locksteps 4 --warmup 12 --envs 1024 --max_steps 10 --model ConvNet --loss mse_q_values --fixed_targets 3 --no_dedup" ;;
+    conv_tasks_random) args="$root/tools/train_throughput.py --locksteps 4 --warmup 12 --envs 1024 --max_steps 10 --model ConvNet --loss mse_q_values --random_targets 3 --task_channels" ;;   # k_conv_input rows, rows keyed by task, per-transition rows in the captured step
     *) echo "unknown mode $mode"; exit 2 ;;
   esac
   (cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $args) > $out.log 2>&1 || { tail -20 $out.log; exit 1; }

@@ -38,6 +38,9 @@ ap.add_argument("--fixed_targets", type=int, default=0, metavar="T",
 ap.add_argument("--random_obstacles", type=int, default=0, metavar="O",
                 help="> 0, with --random_targets: O obstacles per env and episode beside the targets, x ~ U[-3, 3), z ~ U[0.3, 2.5) "
                      "(VecDQN(per_env_obstacles=True))")
+ap.add_argument("--task_channels", action="store_true",
+                help="with --random_targets and --model ConvNet | UNet: the conv Q-network on the per-env tasks, its rows written by "
+                     "k_conv_input (VecDQN(task_channels=True)); the like-for-like baseline is --fixed_targets T --no_dedup")
 ap.add_argument("--fixed_obstacles", type=int, default=0, metavar="O",
                 help="> 0, with --fixed_targets: the like-for-like baseline of --random_obstacles O: O fixed obstacles on the floor, "
                      "shared by all envs (combine with --no_dedup)")
@@ -46,6 +49,8 @@ if a.random_targets and a.fixed_targets:
     ap.error("--random_targets and --fixed_targets are two legs of one comparison: give one")
 if a.random_obstacles and not a.random_targets:
     ap.error("--random_obstacles rides on --random_targets")
+if a.task_channels and not a.random_targets:
+    ap.error("--task_channels rides on --random_targets")
 if a.fixed_obstacles and not a.fixed_targets:
     ap.error("--fixed_obstacles is the baseline of --random_obstacles: give it with --fixed_targets")
 dev = torch.device("cuda:0")
@@ -76,12 +81,12 @@ elif a.bridge_length:
 else:
     obstacles, targets = [(0.5, 0., i * H + H / 2) for i in range(a.tower)], [(0.5, 0, a.tower * H + H / 2)]
 env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obstacles, targets, max_steps=a.max_steps, seed=0,
-                     device=dev, f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=a.stable_actions_only,
+                     device=dev, f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels, candidate_snapshots=a.stable_actions_only,
                      stable_actions_only=a.stable_actions_only)
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
                episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets),
-               per_env_obstacles=bool(a.random_obstacles))
+               per_env_obstacles=bool(a.random_obstacles), task_channels=a.task_channels)
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -132,7 +137,8 @@ for _ in range(n_phase):
 print(json.dumps(dict(config=vars(a), env_steps_per_s=steps_done / dt,
                       env_steps_per_s_at_median_lockstep=steps_done / a.locksteps / median, ms_median_lockstep=median * 1e3,
                       ms_per_lockstep=dt / a.locksteps * 1e3,
-                      rows_per_lockstep=rows_seen / a.locksteps, rows_fed_fraction=(rows_fed / rows_seen) if rows_seen else None,
+                      rows_per_lockstep=rows_seen / a.locksteps, rows_fed_per_lockstep=rows_fed / a.locksteps,
+                      ms_lockstep_per_1000_fed_rows=(dt * 1e3 / (rows_fed / 1000.0)) if rows_fed else None, rows_fed_fraction=(rows_fed / rows_seen) if rows_seen else None,
                       ms_act=t_act / n_phase * 1e3, ms_targets=t_targets[0] / n_phase * 1e3, ms_train=t_train / n_phase * 1e3,
                       ms_per_train_step=(t_train - t_targets[0]) / n_phase / a.train_steps * 1e3, last_loss=losses[-1] if losses else None,
                       note="env_steps_per_s: pipelined loop (VecDQN.lockstep, deferred loss readback); ms_act / ms_targets / "

@@ -816,7 +816,7 @@ int bridges_linear_forward(int32_t rows, int32_t K, int32_t N, const float* x, c
 static int linear_backward_impl(int32_t rows, int32_t K, int32_t N, const float* dz, const float* a_in, const float* W,
                                 float* dW, float* db, const float* act_below, float* dz_below, float* ws, int64_t ws_floats,
                                 const int64_t* a_block, int32_t a_block_bias, LossLog log, void* stream) {
-    if (rows <= 0 || (rows & 31) || K <= 0 || N <= 0 || !dz || !a_in || !W || !dW || !db) return fail_arg("bridges_linear_backward");
+    if (rows <= 0 || (rows & 31) || K <= 0 || N <= 0 || !dz || !a_in || !W || !dW || !db) return fail_arg("bridges_linear_backward: rows must be a positive multiple of 32");
     const int n_ntiles = ceil_div(N, 32), n_ktiles = ceil_div(K, 32), m_tiles = rows / 32;
     int per_job = ceil_div(n_ntiles * n_ktiles, 1024);           // k tiles per dW job: ~1024 jobs on the big layers
     if (per_job < 4) per_job = 4;                                 // one tile per wave at least

@@ -142,6 +142,7 @@ __global__ __launch_bounds__(256) void k_td_target(int n_trans, const int32_t* _
     }
     const int row = s_idx[0];
     const bool dn = done[i] != 0;
+    const bool no_next = dn || row == 0x7fffffff;       // an empty segment has no next row: nothing of next_sf is read for it
     if (t == 0) {
         float nq = dn ? 0.f : s_val[0];
         q_target[i] = lin_reward[i] + gamma * nq;
@@ -154,12 +155,12 @@ __global__ __launch_bounds__(256) void k_td_target(int n_trans, const int32_t* _
         const int n4 = sf_dim >> 2;
         for (int k = t; k < n4; k += 256) {
             float4 a = reinterpret_cast<const float4*>(ar)[k];
-            float4 s = dn ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(src)[k];
+            float4 s = no_next ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(src)[k];
             float4 o;
             o.x = a.x + gamma * s.x; o.y = a.y + gamma * s.y; o.z = a.z + gamma * s.z; o.w = a.w + gamma * s.w;
             reinterpret_cast<float4*>(dst)[k] = o;
         }
-        for (int k = (n4 << 2) + t; k < sf_dim; k += 256) dst[k] = ar[k] + gamma * (dn ? 0.f : src[k]);
+        for (int k = (n4 << 2) + t; k < sf_dim; k += 256) dst[k] = ar[k] + gamma * (no_next ? 0.f : src[k]);
     }
 }
 

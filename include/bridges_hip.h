@@ -503,7 +503,11 @@ int bridges_soft_update(float* target, const float* policy, int64_t n, float tau
  * per transition i with rows [seg_lo[i], seg_hi[i]) of the target net's output (a prefix-sum array: seg, seg + 1;
  * transitions whose next states are the same state may share a range, bridges_valid_rows with rep):
  *   j* = argmax next_q (first maximum), q_target[i] = lin_reward[i] + gamma * (done ? 0 : next_q[j*]),
- *   sf_target[i,:] = action_raster[i,:] + gamma * (done ? 0 : next_sf[j*,:])   (sf_dim may be 0). */
+ *   sf_target[i,:] = action_raster[i,:] + gamma * (done ? 0 : next_sf[j*,:])   (sf_dim may be 0).
+ * Precondition: a transition that is not done has at least one row (seg_lo[i] < seg_hi[i]); an empty segment belongs to a done
+ * transition, whose next rows are never read.  An empty segment that is NOT done is the caller's error and is marked, not
+ * followed: q_target[i] = lin_reward[i] + gamma * -inf, argmax_row[i] = 0x7fffffff, and its successor-feature part is taken as
+ * zero (sf_target[i,:] = action_raster[i,:]) -- no row of next_sf is read for it. */
 int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
                       int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
                       const uint8_t* done, float gamma, int32_t sf_dim, float* q_target, float* sf_target,

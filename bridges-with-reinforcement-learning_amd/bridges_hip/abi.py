@@ -188,6 +188,17 @@ class TaskBuffers(C.Structure):
         ("obs_x_range", (C.c_double * 2) * MAX_OBSTACLES), ("obs_z_range", (C.c_double * 2) * MAX_OBSTACLES)]
 
 
+# bridges_task_family: one integer n per env and episode names the task (bridges_env_set_task_family)
+FAMILY_NONE, FAMILY_SPAN, FAMILY_TOWER = 0, 1, 2
+PARK_Z = -1000.0                               # BRIDGES_PARK_Z: z of an obstacle slot the drawn task does not use
+EPISODE_STATS_MAX_CLASSES = 8
+
+
+class TaskFamily(C.Structure):
+    _fields_ = [("family", C.c_int32), ("n_lo", C.c_int32), ("n_hi", C.c_int32), ("pad_", C.c_int32),
+                ("size", C.c_double), ("x", C.c_double), ("task_class", C.c_void_p)]
+
+
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)
 assert [f[0] for f in EnvBuffers._fields_][-10:-7] == ["lp_ws", "lp_ws_stride", "stats"]
 
@@ -205,6 +216,7 @@ SIGNATURES = {
     "bridges_env_restrict_to_stable": [vp, vp],
     "bridges_env_rebuild_contacts": [vp, vp],
     "bridges_env_set_task_buffers": [vp, C.POINTER(TaskBuffers)],
+    "bridges_env_set_task_family": [vp, C.POINTER(TaskFamily)],
     "bridges_env_load_targets": [vp, vp],
     "bridges_gate_create": [C.POINTER(vp)],
     "bridges_gate_destroy": [vp],
@@ -244,6 +256,7 @@ SIGNATURES = {
     "bridges_record_state": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_record_result": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_episode_stats": [i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp],
+    "bridges_episode_stats_by_class": [i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
     "bridges_replay_unpack": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_accumulate": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_stability": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, i64, vp],

@@ -474,6 +474,26 @@ def episode_stats_(out, rec, valid, gpow, n_targets, run, counted, count_first_o
     return out
 
 
+def episode_stats_by_class_(out, rec, valid, gpow, n_targets, run, counted, cls, count_first_only=False):
+    """episode_stats_ by class (bridges_episode_stats_by_class): out float64 [n_classes, 8], 1 <= n_classes <= 8, cls int32 [E] =
+    the class every env's episode is played under (a task family's task_class as it was before the step); an ended episode of env
+    e goes into row cls[e], a class outside [0, n_classes) into none.  One class and cls all zero: episode_stats_' bits."""
+    L = abi.require_gpu()
+    E = valid.numel()
+    assert rec.dtype == torch.float64 and rec.dim() == 2 and rec.shape[0] == E and rec.is_contiguous()
+    assert valid.dtype in (torch.bool, torch.uint8) and valid.is_contiguous()
+    assert run.dtype == torch.float32 and run.shape == (E, 2) and run.is_contiguous()
+    assert counted.dtype == torch.int32 and counted.numel() == E and counted.is_contiguous()
+    assert out.dtype == torch.float64 and out.dim() == 2 and out.shape[1] == 8 and out.is_contiguous()
+    assert 1 <= out.shape[0] <= abi.EPISODE_STATS_MAX_CLASSES
+    assert cls.dtype == torch.int32 and cls.numel() == E and cls.is_contiguous()
+    assert gpow.dtype == torch.float32 and gpow.dim() == 1 and gpow.numel() >= 1 and gpow.is_contiguous()
+    abi.check(L.bridges_episode_stats_by_class(E, gpow.numel(), _ptr(rec), _ptr(valid), _ptr(gpow), int(n_targets),
+                                               int(bool(count_first_only)), _ptr(cls), int(out.shape[0]), _ptr(run), _ptr(counted),
+                                               _ptr(out), _stream()), "bridges_episode_stats_by_class")
+    return out
+
+
 def bits_dot(bits, img, slot, bits_row=None):
     """out[r] = sum(img[slot[r]] * raster(bits[bits_row[r]])) for bit-packed 64x64 rasters (bridges_bits_dot): img
     [n_slots,64,64] float32, slot [n] int64 -> [n] float32."""

@@ -146,6 +146,62 @@ class RandomObstacles:
         return len(self.ranges)
 
 
+class RandomBridges:
+    """``targets=RandomBridges(kind, sizes=(lo, hi))``: a task family -- every env draws ONE integer n in [lo, hi] whenever it
+    starts an episode, and its target and obstacles are those of the reference's
+    ``horizontal_bridge_setup(square_size=size, num_obstacles=n)`` (kind "span", gym_env.py:25-42) or
+    ``bridge_setup(H=size, num_stories=n)`` at ``x`` (kind "tower", gym_env.py:46-61).  The env has one target and ``hi``
+    obstacle slots; the slots a drawn task does not use are parked at z = abi.PARK_Z, where they rasterise to nothing.  The
+    draw happens on the device, keyed by (seed, global env id, episode); its formula and the coordinates are in
+    include/bridges_hip.h (bridges_env_set_task_family).  Pass ``obstacles=[]`` (or None, or the same object) beside it."""
+
+    KINDS = dict(span=abi.FAMILY_SPAN, tower=abi.FAMILY_TOWER)
+    DEFAULT_SIZE = dict(span=0.6, tower=0.8)
+
+    def __init__(self, kind="span", sizes=(1, 4), size=None, x=0.5):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be 'span' or 'tower', got {kind!r}")
+        try:
+            lo, hi = sizes
+            ok = int(lo) == lo and int(hi) == hi
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"sizes must be two integers (lo, hi), got {sizes!r}")
+        self.kind, self.lo, self.hi = kind, int(lo), int(hi)
+        if not 0 <= self.lo <= self.hi or not 1 <= self.hi <= abi.MAX_OBSTACLES:
+            raise ValueError(f"sizes must satisfy 0 <= lo <= hi and 1 <= hi <= {abi.MAX_OBSTACLES}, got {sizes!r}")
+        self.size = float(self.DEFAULT_SIZE[kind] if size is None else size)
+        if not self.size > 0:
+            raise ValueError("size must be > 0")
+        self.x = float(x)
+
+    @property
+    def family(self):
+        return self.KINDS[self.kind]
+
+    @property
+    def num_obstacles(self):
+        return self.hi
+
+    @property
+    def n_classes(self):
+        """Rows of per-class statistics: class = n, 0..hi."""
+        return self.hi + 1
+
+    def task(self, n):
+        """-> (targets [(x, y, z)], obstacles [hi x (x, y, z)]) of the task n names, parked slots included: the numbers the
+        device writes (and, for the live ones, the reference's setup functions return)."""
+        s = self.size
+        if self.kind == "span":
+            target = (n * s + 2.5 * s, 0.0, s / 2)
+            live = [((o + 1) * s, 0.0, s / 2) for o in range(n)]
+        else:
+            target = (self.x, 0.0, n * s + s / 2)
+            live = [(self.x, 0.0, o * s + s / 2) for o in range(n)]
+        return [target], live + [(0.0, 0.0, abi.PARK_Z)] * (self.hi - n)
+
+
 def _is_per_env_targets(targets):
     return isinstance(targets, (torch.Tensor, np.ndarray)) and targets.ndim == 3
 
@@ -171,7 +227,9 @@ def _single_task_attribute(name, per_env_name, flag="per_env_tasks"):
 
 class VecAssemblyGym:
     """``targets``: a list of (x, y, z) all envs share (the fixed task); a float64 array / tensor [E, T, 3] of per-env targets
-    that stay until set_targets() replaces them; or RandomTargets(): per-env targets redrawn on the device every episode.
+    that stay until set_targets() replaces them; RandomTargets(): per-env targets redrawn on the device every episode; or
+    RandomBridges(): one target and up to ``hi`` obstacles per env, both named by one integer drawn every episode
+    (``task_family`` the sampler, ``task_class`` int32 [E] the env's current n; random_targets / random_obstacles stay None).
     Per-env tasks add env_targets [E,T,3], target_bits [E,64], reward_maps [E,64,64] (reward_maps_img: its [E,S,S] corner),
     reward_prefix [E,64,65] and task_episode [E]: 49 KiB per env.
     ``obstacles``: a list of (x, y, z) all envs share; a float64 array / tensor [E, O, 3] of per-env obstacles that stay until
@@ -204,7 +262,14 @@ class VecAssemblyGym:
         self.per_env_obstacles = False               # set by _init_obstacles
         self.obstacle_buf = None
         self.random_obstacles = None
-        if isinstance(obstacles, RandomObstacles):
+        self.task_family = None                      # set by _attach_task_family
+        self.task_class = None
+        if isinstance(targets, RandomBridges):
+            if not (obstacles is None or obstacles is targets or (isinstance(obstacles, (list, tuple)) and len(obstacles) == 0)):
+                raise ValueError("RandomBridges draws the obstacles with the target: pass obstacles=[] (or None) beside it")
+            obstacles = []
+            self.obstacles, self.n_obstacles = [], targets.num_obstacles
+        elif isinstance(obstacles, RandomObstacles):
             self.obstacles, self.n_obstacles = [], obstacles.num_obstacles
         elif _is_per_env_obstacles(obstacles):
             if tuple(obstacles.shape[::2]) != (int(num_envs), 3) or not 1 <= obstacles.shape[1] <= abi.MAX_OBSTACLES:
@@ -213,7 +278,9 @@ class VecAssemblyGym:
         else:
             self.obstacles = [tuple(float(v) for v in o) for o in obstacles]
             self.n_obstacles = 0                     # per-env obstacles of one env; a shared list is not counted here
-        if isinstance(targets, RandomTargets):
+        if isinstance(targets, RandomBridges):
+            self.targets, self.n_targets = None, 1
+        elif isinstance(targets, RandomTargets):
             self.targets, self.n_targets = None, targets.num_targets
         elif _is_per_env_targets(targets):
             if tuple(targets.shape[::2]) != (int(num_envs), 3) or not 1 <= targets.shape[1] <= abi.MAX_TARGETS:
@@ -258,6 +325,13 @@ class VecAssemblyGym:
         self._alloc()
         self._task_features()
         self._create()
+        if isinstance(targets, RandomBridges):
+            # explicit per-env buffers of one target and `hi` obstacle slots; the family then writes them on the device
+            self._init_obstacles(torch.zeros((self.E, self.n_obstacles, 3), dtype=torch.float64))
+            self._attach_task_buffers(None)
+            self._attach_task_family(targets)
+            self.reset()
+            return
         if self.n_obstacles:
             self._init_obstacles(obstacles)
         if isinstance(targets, RandomTargets):
@@ -432,12 +506,25 @@ class VecAssemblyGym:
             tb.z_range[0], tb.z_range[1] = sampler.z_range
         abi.check(self.L.bridges_env_set_task_buffers(self._env, C.byref(tb)), "bridges_env_set_task_buffers")
         self.random_targets = sampler
+        self.task_family = None                              # the library drops a family with the buffers it was set on
         self.per_env_tasks = True
         self.targets = None
         b = self.task_buf
         self.env_targets, self.target_bits, self.task_episode = b["env_targets"], b["target_bits"], b["task_episode"]
         self.reward_maps, self.reward_prefix = b["reward_map"], b["reward_prefix"]
         self.reward_maps_img = self.crop(self.reward_maps)
+
+    def _attach_task_family(self, sampler):
+        """Hand a RandomBridges to the library (bridges_env_set_task_family) on the attached per-env task buffers; the next
+        reset() draws episode 0.  Any later _attach_task_buffers (set_targets / set_obstacles) detaches it again."""
+        if self.task_class is None:
+            self.task_class = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+        fam = abi.TaskFamily()
+        fam.family, fam.n_lo, fam.n_hi = sampler.family, sampler.lo, sampler.hi
+        fam.size, fam.x = sampler.size, sampler.x
+        fam.task_class = self.task_class.data_ptr()
+        abi.check(self.L.bridges_env_set_task_family(self._env, C.byref(fam)), "bridges_env_set_task_family")
+        self.task_family = sampler
 
     def set_targets(self, targets, reset=True):
         """Explicit per-env targets ([E, T, 3] float64, T = the env's number of targets) that stay until set again; a sampler

@@ -96,6 +96,8 @@ struct bridges_env {
     bridges_task_buffers tasks;
     const float* fixed_reward_map;         // the fixed task's tables, restored when the buffers are detached
     const double* fixed_reward_prefix;
+    // task family (bridges_env_set_task_family): family.family != BRIDGES_FAMILY_NONE while one is set
+    bridges_task_family family;
 };
 
 // The previous lock-step's candidate count (+3 %, at least one per env), which sizes the grids over candidates.  Those
@@ -187,6 +189,7 @@ int bridges_env_create(const bridges_task* t, const bridges_env_buffers* buf, br
     env->raster_done = nullptr;
     env->has_tasks = false;
     memset(&env->tasks, 0, sizeof(env->tasks));
+    memset(&env->family, 0, sizeof(env->family));
     env->fixed_reward_map = buf->reward_map;
     env->fixed_reward_prefix = buf->reward_prefix;
     // mapped, coherent host word: k_scan stores the candidate count of the lock-step straight into it (no copy command
@@ -315,7 +318,10 @@ static int refresh(bridges_env* env, hipStream_t s, int after_step) {
 }
 
 static int task_features(bridges_env* env, void* stream, int mode) {
-    return launch("k_task_features", k_task_features, dim3(env->ctx.E), dim3(TASK_THREADS), 0, stream, env->ctx, env->tasks, mode);
+    if (env->family.family != BRIDGES_FAMILY_NONE)
+        return launch("k_task_features (task family)", k_task_features<bridges_task_family>, dim3(env->ctx.E), dim3(TASK_THREADS), 0,
+                      stream, env->ctx, env->tasks, mode, env->family);
+    return launch("k_task_features", k_task_features<>, dim3(env->ctx.E), dim3(TASK_THREADS), 0, stream, env->ctx, env->tasks, mode);
 }
 
 int bridges_env_reset(bridges_env* env, void* stream) {
@@ -335,7 +341,7 @@ int bridges_env_step(bridges_env* env, void* stream) {
                             (const double*)env->tasks.env_targets))
             return rc;
         // the envs k_step has just reset begin an episode: next task (fixed per-env targets and obstacles: nothing to do)
-        if (env->tasks.sample || env->tasks.sample_obstacles)
+        if (env->tasks.sample || env->tasks.sample_obstacles || env->family.family != BRIDGES_FAMILY_NONE)
             if (int rc = task_features(env, stream, TASK_STEP)) return rc;
     }
     return refresh(env, (hipStream_t)stream, 1);
@@ -345,6 +351,7 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
     if (!env) return fail_arg("null env");
     DevCtx& c = env->ctx;
     if (!tb) {
+        memset(&env->family, 0, sizeof(env->family));
         env->has_tasks = false;
         memset(&env->tasks, 0, sizeof(env->tasks));
         c.b.reward_map = env->fixed_reward_map;
@@ -369,9 +376,28 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
     if (tb->sample != 0 && tb->sample != 1) return fail_arg("task buffers: sample must be 0 or 1");
     if (tb->sample && !(tb->x_range[0] <= tb->x_range[1] && tb->z_range[0] <= tb->z_range[1])) return fail_arg("task buffers: x_range / z_range");
     env->tasks = *tb;
+    memset(&env->family, 0, sizeof(env->family));      // a family belongs to the buffers it was set on
     env->has_tasks = true;
     c.b.reward_map = tb->reward_map;
     c.b.reward_prefix = tb->reward_prefix;
+    return BRIDGES_OK;
+}
+
+int bridges_env_set_task_family(bridges_env* env, const bridges_task_family* fam) {
+    if (!env) return fail_arg("null env");
+    if (!fam || fam->family == BRIDGES_FAMILY_NONE) {
+        memset(&env->family, 0, sizeof(env->family));
+        return BRIDGES_OK;
+    }
+    if (fam->family != BRIDGES_FAMILY_SPAN && fam->family != BRIDGES_FAMILY_TOWER) return fail_arg("task family: family must be NONE, SPAN or TOWER");
+    if (!env->has_tasks) return fail_arg("task family: no task buffers attached");
+    if (env->ctx.n_targets != 1) return fail_arg("task family: the task must have n_targets == 1");
+    if (fam->n_hi < 1 || fam->n_hi > BRIDGES_MAX_OBSTACLES) return fail_arg("task family: n_hi must be 1..BRIDGES_MAX_OBSTACLES");
+    if (fam->n_lo < 0 || fam->n_lo > fam->n_hi) return fail_arg("task family: 0 <= n_lo <= n_hi");
+    if (env->tasks.n_obstacles != fam->n_hi) return fail_arg("task family: the task buffers must have n_obstacles == n_hi");
+    if (!(fam->size > 0.0)) return fail_arg("task family: size must be > 0");
+    if (!fam->task_class) return fail_arg("task family: task_class not given");
+    env->family = *fam;
     return BRIDGES_OK;
 }
 
@@ -650,6 +676,17 @@ int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t
     if (E == 0) return BRIDGES_OK;
     return launch("k_episode_stats", k_episode_stats, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec, valid, gpow,
                   (int)n_targets, (int)(count_first_only != 0), run, counted, out);
+}
+
+int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow,
+                                   int32_t n_targets, int32_t count_first_only, const int32_t* cls, int32_t n_classes, float* run,
+                                   int32_t* counted, double* out, void* stream) {
+    if (E < 0 || K < 1 || !gpow || !out || (E > 0 && (!rec || !valid || !run || !counted || !cls)))
+        return fail_arg("bridges_episode_stats_by_class");
+    if (n_classes < 1 || n_classes > EPISODE_STATS_MAX_CLASSES) return fail_arg("bridges_episode_stats_by_class: n_classes must be 1..8");
+    if (E == 0) return BRIDGES_OK;
+    return launch("k_episode_stats_by_class", k_episode_stats_by_class, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec,
+                  valid, gpow, (int)n_targets, (int)(count_first_only != 0), cls, (int)n_classes, run, counted, out);
 }
 
 int bridges_replay_unpack(int32_t E, int32_t n_rec, int32_t K, const double* rec, const int32_t* shape_faces, int32_t n_shapes,

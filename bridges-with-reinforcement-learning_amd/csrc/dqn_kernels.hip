@@ -551,6 +551,72 @@ __global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats(int E, 
     if (t < EPISODE_STATS_SLOTS) out[t] += part[t][0];
 }
 
+// The same fold with an ended episode of env e added to row cls[e] of out [n_classes, 8] (per-span / per-height statistics of a
+// task family; cls is the class the episode was played under, snapshotted before the step that redraws it).  A cls outside
+// [0, n_classes) is counted in no row; run and counted advance as ever.  Thread t keeps one partial per (class, slot) in
+// registers -- the class loop is unrolled, a partial takes the add only for its own class, so the order of the adds within a
+// class is k_episode_stats' -- and the classes go through the same LDS tree one after the other: with one class and cls all
+// zero, out, run and counted are k_episode_stats' bit for bit.
+constexpr int EPISODE_STATS_MAX_CLASSES = 8;
+constexpr int EPISODE_STATS_USED = 6;         // slots 6 and 7 stay 0
+
+__global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats_by_class(
+        int E, int K, const double* __restrict__ rec, const uint8_t* __restrict__ valid, const float* __restrict__ gpow, int n_targets,
+        int count_first_only, const int32_t* __restrict__ cls, int n_classes, float* __restrict__ run, int32_t* __restrict__ counted,
+        double* __restrict__ out) {
+    __shared__ double part[EPISODE_STATS_SLOTS][EPISODE_STATS_THREADS];
+    const int t = threadIdx.x;
+    double acc[EPISODE_STATS_MAX_CLASSES][EPISODE_STATS_USED];
+#pragma unroll
+    for (int c = 0; c < EPISODE_STATS_MAX_CLASSES; ++c)
+#pragma unroll
+        for (int k = 0; k < EPISODE_STATS_USED; ++k) acc[c][k] = 0.0;
+    for (int e = t; e < E; e += EPISODE_STATS_THREADS) {
+        if (!valid[e]) continue;
+        const double* r = rec + (size_t)e * BRIDGES_REC_WIDTH;
+        const int i = (int)r[BRIDGES_REC_NB];
+        const int gi = i < 0 ? 0 : (i < K ? i : K - 1);
+        const float reward = (float)r[BRIDGES_REC_REWARD];
+        const float lin = (float)r[BRIDGES_REC_LIN];
+        float s0 = i == 0 ? 0.f : run[2 * e];
+        float s1 = i == 0 ? 0.f : run[2 * e + 1];
+        s0 = __fadd_rn(s0, __fmul_rn(gpow[gi], reward));
+        s1 = __fadd_rn(s1, __fmul_rn(gpow[gi], lin));
+        run[2 * e] = s0;
+        run[2 * e + 1] = s1;
+        if (r[BRIDGES_REC_DONE] > 0.5) {
+            const int32_t cnt = counted[e];
+            if (!(count_first_only && cnt > 0)) {
+                const int ce = cls[e];
+                const double v[EPISODE_STATS_USED] = {1.0, (double)s0, (double)s1, (double)(i + 1),
+                                                      r[BRIDGES_REC_STABLE_N] > 0.5 ? 1.0 : 0.0,
+                                                      reward == (float)n_targets ? 1.0 : 0.0};
+#pragma unroll
+                for (int c = 0; c < EPISODE_STATS_MAX_CLASSES; ++c)
+#pragma unroll
+                    for (int k = 0; k < EPISODE_STATS_USED; ++k) acc[c][k] = ce == c ? acc[c][k] + v[k] : acc[c][k];
+            }
+            counted[e] = cnt + 1;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < EPISODE_STATS_MAX_CLASSES; ++c) {
+        if (c >= n_classes) break;                  // uniform: every thread sees the same n_classes
+#pragma unroll
+        for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] = k < EPISODE_STATS_USED ? acc[c][k < EPISODE_STATS_USED ? k : 0] : 0.0;
+        __syncthreads();
+        for (int s = EPISODE_STATS_THREADS / 2; s > 0; s >>= 1) {
+            if (t < s) {
+#pragma unroll
+                for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] += part[k][t + s];
+            }
+            __syncthreads();
+        }
+        if (t < EPISODE_STATS_SLOTS) out[c * EPISODE_STATS_SLOTS + t] += part[t][0];
+        __syncthreads();                            // the next class reuses the tree
+    }
+}
+
 __global__ __launch_bounds__(64) void k_replay_unpack(int E, int n_rec, int K, const double* __restrict__ rec,
                                                       const int32_t* __restrict__ shape_faces, int n_shapes, int n_groups, int n_ground, int n_off,
                                                       int32_t* __restrict__ n_blocks, int32_t* __restrict__ blk_shape,

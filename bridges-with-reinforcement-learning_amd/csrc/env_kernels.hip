@@ -785,7 +785,19 @@ enum { TASK_LOAD = 0, TASK_RESET = 1, TASK_STEP = 2 };
 static_assert(IMG - 1 - BRIDGES_GAUSS_TAPS / 2 <= TASK_KZ_PAD && IMG - 1 + BRIDGES_GAUSS_TAPS / 2 < BRIDGES_GAUSS_TAPS + 16,
               "every tap index of a 64 x 64 canvas must fall into the padded table");
 static_assert(IMG % (TASK_WAVES * TASK_ROWS_IN_FLIGHT) == 0, "map rows are dealt to the waves in batches");
-__global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridges_task_buffers t, int mode) {
+// Task families (bridges_task_family, header comment of bridges_env_set_task_family): k_task_features<bridges_task_family>
+// draws ONE integer n per env and episode -- a stream of its own (FAMI_SALT), integer arithmetic only -- and writes the target
+// and the obstacles that n names in place of the uniform draws; unused obstacle slots are parked at z = BRIDGES_PARK_Z, where
+// the cube rasterises to nothing.  The optional trailing argument keeps the kernel without a family what it was.
+#define FAMI_SALT 0x66616D695F726E67ull     // "fami_rng"
+__device__ __forceinline__ bridges_task_family task_family() { return bridges_task_family{}; }
+__device__ __forceinline__ bridges_task_family task_family(const bridges_task_family& f) { return f; }
+template <typename... FAMILY>
+__global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridges_task_buffers t, int mode, FAMILY... family_arg) {
+    constexpr bool FAM = sizeof...(FAMILY) == 1;
+    const bridges_task_family fam = task_family(family_arg...);
+    (void)fam;
+    const bool draw_obstacles = FAM ? true : t.sample_obstacles != 0, draw_targets = FAM ? true : t.sample != 0;
     __shared__ float kz[TASK_KZ];
     __shared__ uint64_t tb_l[IMG];
     __shared__ double tv_l[TASK_WAVES][MAXV * 2];
@@ -806,18 +818,39 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
     if (mode == TASK_STEP) ep = t.task_episode[e] + 1u;
     __syncthreads();                                // every wave has read the episode before it is replaced
     if (mode != TASK_LOAD && tid == 0) t.task_episode[e] = ep;
+    int fam_n = 0;                                  // the env's span / height of this episode (every thread draws it)
+    if constexpr (FAM) {
+        if (mode != TASK_LOAD) {
+            const uint64_t h0 = splitmix64((((c.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(c.env_id_base + e)) ^ FAMI_SALT);
+            const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
+            const uint64_t r = splitmix64(h1);
+            fam_n = fam.n_lo + (int)(((r >> 32) * (uint64_t)(fam.n_hi - fam.n_lo + 1)) >> 32);
+            if (tid == 0) fam.task_class[e] = fam_n;
+        }
+    }
     const bridges_shape& cube = c.tt->shapes[t.target_shape];
     const int nv = cube.nv;
     // ---- per-env obstacles (n_obstacles > 0): lane 3 o + k of every wave holds coordinate k of obstacle o; drawn like the
     // targets on a stream of its own (OBST_SALT) with one range pair per obstacle, rasterised exactly as the target blocks ----
     const int O = t.n_obstacles;
-    if (O > 0 && (mode != TASK_STEP || t.sample_obstacles)) {     // fixed obstacles keep their raster over episode boundaries
+    if (O > 0 && (mode != TASK_STEP || draw_obstacles)) {     // fixed obstacles keep their raster over episode boundaries
         double* og = t.env_obstacles + (size_t)e * O * 3;
         double ov = 0.0;
         if (lane < 3 * O) {
-            if (t.sample_obstacles && mode != TASK_LOAD) {
+            if (draw_obstacles && mode != TASK_LOAD) {
                 const int axis = lane % 3, o = lane / 3;
-                if (axis != 1) {
+                if constexpr (FAM) {
+                    const double half = fam.size / 2.0;
+                    if (o >= fam_n) {
+                        ov = axis == 2 ? BRIDGES_PARK_Z : 0.0;
+                    } else if (fam.family == BRIDGES_FAMILY_SPAN) {
+                        const double ox = (double)(o + 1) * fam.size;
+                        ov = axis == 0 ? ox : (axis == 2 ? half : 0.0);
+                    } else {
+                        const double oz = (double)o * fam.size;
+                        ov = axis == 0 ? fam.x : (axis == 2 ? oz + half : 0.0);
+                    }
+                } else if (axis != 1) {
                     const uint64_t h0 = splitmix64((((c.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(c.env_id_base + e)) ^ OBST_SALT);
                     const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
                     const uint64_t r = splitmix64(h1 ^ (uint64_t)lane);
@@ -848,14 +881,22 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
         }
         if (wv == 0) t.env_obstacle_bits[(size_t)e * IMG + lane] = obits;
         // obstacle sampler alone: the env begins an episode under its old targets -- target_bits, map and prefix stay
-        if (mode == TASK_STEP && !t.sample) return;
+        if (mode == TASK_STEP && !draw_targets) return;
     }
     // ---- targets: lane 3 q + k of every wave holds coordinate k of target q ----
     double tv = 0.0;
     if (lane < 3 * T) {
-        if (t.sample && mode != TASK_LOAD) {
+        if (draw_targets && mode != TASK_LOAD) {
             const int axis = lane % 3;
-            if (axis != 1) {
+            if constexpr (FAM) {                    // n_targets == 1: lanes 0..2
+                const double half = fam.size / 2.0, run = (double)fam_n * fam.size;
+                if (fam.family == BRIDGES_FAMILY_SPAN) {
+                    const double lead = 2.5 * fam.size;
+                    tv = axis == 0 ? run + lead : (axis == 2 ? half : 0.0);
+                } else {
+                    tv = axis == 0 ? fam.x : (axis == 2 ? run + half : 0.0);
+                }
+            } else if (axis != 1) {
                 const uint64_t h0 = splitmix64((((c.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(c.env_id_base + e)) ^ TASK_SALT);
                 const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
                 const uint64_t r = splitmix64(h1 ^ (uint64_t)lane);

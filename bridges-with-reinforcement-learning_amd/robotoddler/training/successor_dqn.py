@@ -523,7 +523,23 @@ def build_parser():
                    help="With --random_targets T [--random_obstacles O] and --model ConvNet or UNet at 64x64: train the conv "
                         "Q-network on the per-env tasks -- every row is fed the reward map and the obstacle raster of its env as "
                         "image channels, written with its block and action rasters by one kernel (bridges_conv_input_rows).")
+    p.add_argument("--random_bridge_length", type=parse_size_range, default=argparse.SUPPRESS, metavar="LO:HI",
+                   help="Vectorised loop: horizontal_bridge_setup(num_obstacles=n) per env and episode, n drawn from LO..HI "
+                        "(0 <= LO <= HI <= 4) on the device whenever an env starts an episode; success is logged per n. "
+                        "--model SuccessorMLP, or ConvNet / UNet with --task_channels; any --shapes.")
+    p.add_argument("--random_tower_height", type=parse_size_range, default=argparse.SUPPRESS, metavar="LO:HI",
+                   help="Vectorised loop: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI, as "
+                        "--random_bridge_length draws the span.")
     return p
+
+
+def parse_size_range(text):
+    """'LO:HI' -> (LO, HI), two integers."""
+    try:
+        lo, hi = text.split(":")
+        return int(lo), int(hi)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected LO:HI (two integers), got {text!r}")
 
 
 EVAL_DEFAULTS = dict(eval_envs=0, eval_epsilon=0.0)
@@ -534,6 +550,8 @@ def check_random_targets(args):
     obstacles per env to it, --task_channels runs ConvNet / UNet on them instead; every other combination is refused in words (SystemExit), before anything touches the GPU."""
     T, O = args.get('random_targets'), args.get('random_obstacles')
     conv = bool(args.get('task_channels', False))
+    if args.get('random_bridge_length') is not None or args.get('random_tower_height') is not None:
+        return check_random_bridges(args)
     if conv and T is None:
         raise SystemExit("--task_channels is valid only together with --random_targets T: it feeds the conv Q-networks the task "
                          "of every env, and without --random_targets all envs share one task")
@@ -567,6 +585,39 @@ def check_random_targets(args):
                                       "--task_channels is built for 64x64 as well)")
     if args['shapes'] != 'trapezoid':
         raise SystemExit("--random_targets is tower_setup: --shapes trapezoid")
+
+
+def check_random_bridges(args):
+    """--random_bridge_length LO:HI / --random_tower_height LO:HI: the vectorised loop on a task family (one integer n per env
+    and episode names the bridge span / tower height); what it cannot run is refused in words (SystemExit), before anything
+    touches the GPU."""
+    span, tower = args.get('random_bridge_length'), args.get('random_tower_height')
+    if span is not None and tower is not None:
+        raise SystemExit("--random_bridge_length and --random_tower_height name two task families: give one of them")
+    flag = "--random_bridge_length" if span is not None else "--random_tower_height"
+    lo, hi = span if span is not None else tower
+    if args.get('random_targets') is not None or args.get('random_obstacles') is not None:
+        raise SystemExit(f"{flag} draws the target and the obstacles of every env from one integer: it cannot be combined with "
+                         "--random_targets / --random_obstacles, which draw them independently")
+    if args.get('tower_height') or args['bridge_length'] != 1:
+        raise SystemExit(f"{flag} draws every env's task: it cannot be combined with --tower_height or --bridge_length, which name "
+                         "one fixed task")
+    if args['num_envs'] <= 1:
+        raise SystemExit(f"{flag} needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the fixed tasks "
+                         "of --tower_height / --bridge_length only")
+    if tuple(args['image_size']) != (64, 64):
+        raise SystemExit(f"{flag} needs --image_size 64x64 (the acting paths on per-env tasks are built for 64x64)")
+    from bridges_hip import abi
+    if hi > abi.MAX_OBSTACLES or lo < 0 or lo > hi or hi < 1:
+        raise SystemExit(f"{flag} LO:HI must satisfy 0 <= LO <= HI and 1 <= HI <= {abi.MAX_OBSTACLES} (an env holds at most "
+                         f"{abi.MAX_OBSTACLES} obstacles), got {lo}:{hi}")
+    conv = bool(args.get('task_channels', False))
+    if conv and args['model'] == 'SuccessorMLP':
+        raise SystemExit(f"--task_channels is for the conv Q-networks (--model ConvNet or UNet): --model SuccessorMLP trains on "
+                         f"{flag} without it")
+    if not conv and args['model'] != 'SuccessorMLP':
+        raise SystemExit(f"{flag} with --model {args['model']} needs --task_channels: the conv Q-networks take the task of every "
+                         "env as image channels")
 
 
 def make_setup_fct(args):

@@ -2,6 +2,7 @@
 (vec_dqn.py): which body a step runs, when it is captured as a HIP graph and replayed, how it warms up, when it is switched
 off, and how Adam's step count goes back to the torch optimiser.  One driver per policy net, ``net._fused_trainer``
 (the name of the attribute since the hand-written step was its first body)."""
+import gc
 import os
 import warnings
 
@@ -202,15 +203,26 @@ class CapturedTrainStep:
         self.counter.add_(1)
 
     def _capture(self, m):
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(m):
-                if self.fused:
-                    N = self.n_max * self.B
-                    self._fused_body(self.block.view(N, -1), self.action.view(N, -1), self.binary, self.reward, self.obstacle,
-                                     self.q, self.sf)
-                else:
-                    self._autograd_body()
+        # No garbage collection between capture_begin and capture_end: a dead reference cycle that holds GPU objects (an earlier
+        # agent with its env, its captured graphs and their memory pool) would be destroyed inside the capture, where freeing
+        # device memory is not permitted -- the process aborted there.  torch.cuda.graph no longer collects before it begins a
+        # capture, so collect here, and keep the collector off until the capture has ended.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for _ in range(m):
+                    if self.fused:
+                        N = self.n_max * self.B
+                        self._fused_body(self.block.view(N, -1), self.action.view(N, -1), self.binary, self.reward, self.obstacle,
+                                         self.q, self.sf)
+                    else:
+                        self._autograd_body()
+        finally:
+            if collecting:
+                gc.enable()
         return graph
 
     def _check_hyperparameters(self):

@@ -34,7 +34,7 @@ import torch
 
 from bridges_hip import dqn_ops, ops
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGym
+from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 from robotoddler.training import distributed as D
 from robotoddler.training import records as R
 from robotoddler.training.episode_stats import EpisodeStats
@@ -137,8 +137,16 @@ class VecDQN:
         self.env_steps = 0
         self._counts_host = torch.zeros(2, dtype=torch.int64).pin_memory()      # (env-steps, finished episodes) of a lock-step
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
-        self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device) if episode_stats else None)
+        # (a task family -- RandomBridges -- keeps them per class as well: one row per span / height n = 0..hi)
+        self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
+                              if episode_stats else None)
         self._eval_state = {}                                # evaluate(): (random stream, EpisodeStats, count images) per env shape
+
+    @staticmethod
+    def _n_classes(env):
+        """Rows of the per-class episode statistics: hi + 1 on a task-family env (class = the drawn n), else 1."""
+        family = getattr(env, "task_family", None)
+        return family.n_classes if family is not None else 1
 
     def _check_task_channels(self, policy_net, target_net, env):
         """The conditions of task_channels=True, decided from the arguments alone."""
@@ -436,6 +444,8 @@ class VecDQN:
             # the task the transition is taken under: the step that ends an episode redraws the env's targets (task_tail)
             env._task_tail = (torch.cat([env.env_targets.reshape(E, -1), env.env_obstacles.reshape(E, -1)], dim=1)
                               if self.per_env_obstacles else env.env_targets.reshape(E, -1).clone())
+        if getattr(env, "task_family", None) is not None:
+            env._task_class = env.task_class.clone()            # likewise the class: the step that ends an episode redraws it
         env.step(sel_index)
         valid = R.pack_result(env, rec)
         return rec, valid, q_sel
@@ -456,7 +466,8 @@ class VecDQN:
         (the first maximum of q) for epsilon == 0, else the training rule with the evaluation's own count images and random
         stream.  Runs exactly eval_env.K lock-steps -- every episode ends by truncation at K at the latest -- and reads the
         statistics back once.  Touches no training state (rollout env, count images, ring, random streams, epsilon, counters).
-        -> log_episode's keys as means over the N = eval_env.E episodes, plus success_rate and episodes.
+        -> log_episode's keys as means over the N = eval_env.E episodes, plus success_rate and episodes; on a task-family env
+        (RandomBridges) also success_by_class and episodes_by_class, lists indexed by the drawn n = 0..hi.
         Per-env tasks: reset() sets task_episode to 0, so every evaluation runs on the SAME eval_env.E tasks -- the draws of
         (the eval env's seed, env, episode 0): a fixed held-out task set, not fresh tasks per evaluation."""
         if eval_env is self.env:
@@ -468,12 +479,13 @@ class VecDQN:
         if bool(getattr(eval_env, "per_env_obstacles", False)) != self.per_env_obstacles:
             raise ValueError("the evaluation env must have per-env obstacles exactly when the agent was built with "
                              "per_env_obstacles=True")
-        key = (eval_env.E, eval_env.K, eval_env.n_targets)
+        n_classes = self._n_classes(eval_env)
+        key = (eval_env.E, eval_env.K, eval_env.n_targets, n_classes)
         st = self._eval_state.get(key)
         if st is None:
             gen = torch.Generator(device=self.device).manual_seed(0xE7A1 + self.seed * 1000 + self.rank)
             stats = EpisodeStats(eval_env.E, eval_env.K, self.gamma, eval_env.n_targets, self.device, count_first_only=True,
-                                 across_ranks=False)
+                                 across_ranks=False, n_classes=n_classes)
             images = torch.zeros((eval_env.K + 1, eval_env.img, eval_env.img), dtype=torch.float32, device=self.device)
             st = self._eval_state[key] = (gen, stats, images)
         gen, stats, images = st
@@ -483,13 +495,17 @@ class VecDQN:
         epsilon = float(epsilon)
         for _ in range(eval_env.K):
             rec, valid, _q = self._act_on(eval_env, images, gen, epsilon, epsilon <= 0.0)
-            stats.fold(rec, valid)
+            stats.fold(rec, valid, cls=eval_env._task_class if n_classes > 1 else None)
         vals = stats.take().get()                                  # the one wait of the evaluation
         if vals["episodes"] != eval_env.E:
             raise RuntimeError(f"evaluation: {vals['episodes']} of {eval_env.E} episodes ended within {eval_env.K} lock-steps "
                                "(an env whose fresh state has no valid candidate never starts one)")
-        return dict(reward=vals["reward"], lin_reward=vals["lin_reward"], avg_loss=None, num_steps=vals["num_steps"],
-                    stable=vals["stable"], collision=0.0, success_rate=vals["success_rate"], episodes=vals["episodes"])
+        out = dict(reward=vals["reward"], lin_reward=vals["lin_reward"], avg_loss=None, num_steps=vals["num_steps"],
+                   stable=vals["stable"], collision=0.0, success_rate=vals["success_rate"], episodes=vals["episodes"])
+        if n_classes > 1:                                          # a task family: per span / height n = 0..hi
+            out["success_by_class"] = [c["success_rate"] for c in vals["by_class"]]
+            out["episodes_by_class"] = [c["episodes"] for c in vals["by_class"]]
+        return out
 
     # ------------------------------------------------------------------ gradient steps on sampled batches
     def _make_replay_env(self, n_states):
@@ -730,7 +746,8 @@ class VecDQN:
         under the host's queueing of the next lock-step."""
         rec, valid = self.act()
         if self.episode_stats is not None:
-            self.episode_stats.fold(rec, valid)                # before the all-gather: env identity still holds
+            # before the all-gather: env identity still holds (a task family: under the class of before the step)
+            self.episode_stats.fold(rec, valid, cls=self.env._task_class if self.episode_stats.n_classes > 1 else None)
         if self.prioritized:
             rec[:, R.O_TD] = self.td_errors(rec).to(rec.dtype)
         # ONE wait per lock-step on this side: the two counts ride to pinned memory in front of the next act's candidate rows,
@@ -779,10 +796,16 @@ def lockstep_log_values(info):
     sum over one episode), avg_loss, num_steps = env-steps of the lock-step on this rank, epsilon; plus the run counters.
     Then the per-episode statistics (EpisodeStats): the episodes that ended in the lock-step on all ranks and the means over
     them of log_episode's discounted reward / lin_reward, episode length and final stability, and the fraction that reached
-    the targets (None when no episode ended)."""
-    return dict(reward=info['mean_reward'], lin_reward=info['mean_lin_reward'], avg_loss=info['avg_loss'],
+    the targets (None when no episode ended).  A run on a task family (info['success_by_class']: a list indexed by the drawn
+    n) appends success_rate_n{k}, the success rate of the episodes played on n = k, for the family's n_lo..n_hi."""
+    vals = dict(reward=info['mean_reward'], lin_reward=info['mean_lin_reward'], avg_loss=info['avg_loss'],
                 num_steps=info['lockstep_env_steps'], epsilon=info['epsilon'], env_steps=info['env_steps'],
                 steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
+    by_class = info.get('success_by_class')
+    if by_class is not None:
+        lo = info.get('class_lo', 0)
+        vals.update({f"success_rate_n{k}": v for k, v in enumerate(by_class) if k >= lo})
+    return vals
 
 
 # per-lock-step keys of the episode statistics in run_vectorised's info (and lockstep_log_values), in log order
@@ -804,7 +827,16 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     random_targets = args.get('random_targets')
     random_obstacles = args.get('random_obstacles')
     task_channels = bool(args.get('task_channels', False))
-    if random_targets:
+    family = None                                              # --random_bridge_length / --random_tower_height: (kind, lo, hi)
+    if args.get('random_bridge_length') is not None:
+        family = ("span", *args['random_bridge_length'])
+    elif args.get('random_tower_height') is not None:
+        family = ("tower", *args['random_tower_height'])
+    if family:
+        # horizontal_bridge_setup(num_obstacles=n) / bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI on the
+        # device: one target, up to HI obstacles, both per env
+        targets, obstacles = RandomBridges(family[0], sizes=family[1:]), []
+    elif random_targets:
         # tower_setup(num_targets=T) per env and episode (gym_env.py:64-79 of the reference): no obstacles, every env draws
         # its own targets whenever it starts an episode; --random_obstacles O: and O obstacles beside them, as connecting_setup
         # draws both at every reset (gym_env.py:91-99)
@@ -830,7 +862,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
-                   per_env_tasks=bool(random_targets), per_env_obstacles=bool(random_obstacles),
+                   per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
                    task_channels=task_channels)
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
@@ -839,7 +871,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     eval_epsilon = args.get('eval_epsilon', EVAL_DEFAULTS['eval_epsilon'])
     eval_env = None
     if eval_envs > 0 and rank == 0:
-        eval_targets = RandomTargets(random_targets) if random_targets else targets
+        eval_targets = (RandomBridges(family[0], sizes=family[1:]) if family else
+                        RandomTargets(random_targets) if random_targets else targets)
         eval_obstacles = RandomObstacles([OBSTACLE_RANGE] * random_obstacles) if random_obstacles else obstacles
         eval_env = VecAssemblyGym(eval_envs, geoms, eval_obstacles, eval_targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
                                   device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net) and not task_channels,
@@ -869,6 +902,9 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         ep = episodes.get()
         info.update(episodes_finished=ep['episodes'], episode_reward=ep['reward'], episode_lin_reward=ep['lin_reward'],
                     episode_num_steps=ep['num_steps'], episode_stable=ep['stable'], success_rate=ep['success_rate'])
+        if 'by_class' in ep:
+            info.update(success_by_class=[c['success_rate'] for c in ep['by_class']],
+                        episodes_by_class=[c['episodes'] for c in ep['by_class']], class_lo=family[1])
         if rank == 0 and (aim_run is not None or wandb_run is not None):
             # one call per lock-step, step = episodes finished so far (the reference's x axis is the episode number)
             track_run_sinks(lockstep_log_values(info), info['episodes'], 'training', aim_run=aim_run, wandb_run=wandb_run)
@@ -911,9 +947,13 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)
                 if aim_run is not None or wandb_run is not None:
+                    if family:                               # the sinks take scalars: success_rate_n{k} for the lists by class
+                        by_class = ev['success_by_class']
+                        ev = {k: v for k, v in ev.items() if not k.endswith('_by_class')}
+                        ev.update({f"success_rate_n{k}": v for k, v in enumerate(by_class) if k >= family[1]})
                     track_run_sinks(ev, agent.episodes_done, 'evaluation', aim_run=aim_run, wandb_run=wandb_run)
                 if args['verbose']:
-                    print(f"evaluation {agent.episodes_done}: {ev}")
+                    print(f"evaluation {agent.episodes_done}: {info['evaluation']}")
             next_eval = next_multiple(agent.episodes_done, args['evaluate_every'])
         history.append(info)
         if pending is not None:

@@ -276,6 +276,38 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
  * task_episode and the env states stay; the candidates' cand_lin is stale until bridges_env_reset / _refresh.  No host wait. */
 int bridges_env_load_targets(bridges_env* env, void* stream);
 
+/* --- per-env task families ------------------------------------------------------
+ * horizontal_bridge_setup(num_obstacles = n) and bridge_setup(num_stories = n) are ONE integer n from which the target and all
+ * obstacles follow.  A family draws n per env and episode on the device and writes the task it names into the per-env task
+ * buffers; an env then trains across bridge spans (or tower heights).  An obstacle slot the drawn task does not use is parked
+ * far below the image, where its cube06 rasterises to nothing: every consumer of [E,O,3] obstacle arrays stays as it is. */
+#define BRIDGES_FAMILY_NONE 0
+#define BRIDGES_FAMILY_SPAN 1    /* horizontal_bridge_setup(square_size = size, num_obstacles = n), gym_env.py:25-42 */
+#define BRIDGES_FAMILY_TOWER 2   /* bridge_setup(H = size, num_stories = n) at x, gym_env.py:46-61 */
+#define BRIDGES_PARK_Z (-1000.0) /* z of an obstacle slot the drawn task does not use */
+typedef struct {
+    int32_t family, n_lo, n_hi, pad_;
+    double size, x;              /* x: TOWER only */
+    int32_t* task_class;         /* [E] device: n of the env's current task */
+} bridges_task_family;
+/* Set (or, with NULL or family = BRIDGES_FAMILY_NONE, clear) the task family of an env with per-env task buffers attached.
+ * Refused (BRIDGES_E_ARG) unless the buffers have n_targets = 1 and n_obstacles = n_hi, 0 <= n_lo <= n_hi, 1 <= n_hi <=
+ * BRIDGES_MAX_OBSTACLES, size > 0 and task_class is given.  A later bridges_env_set_task_buffers clears the family.
+ * Enqueues nothing.  With a family set, bridges_env_reset (episode 0) and bridges_env_step for the envs that begin an episode
+ * (task_episode += 1) draw n, write env_targets, env_obstacles and task_class[e] = n and rebuild the task features -- in the
+ * launch that rebuilds them anyway; sample, sample_obstacles and the ranges of the task buffers are not read.
+ * bridges_env_load_targets reads the coordinates as they are written and leaves task_class alone.
+ * The draw is a stream of its own, in integer arithmetic only: with gid = env_id_base + e,
+ *   h0 = splitmix64(((seed & 0xFFFFFFFF) << 32 | (uint32)gid) ^ 0x66616D695F726E67)      ("fami_rng")
+ *   h1 = splitmix64(h0 ^ task_episode)
+ *   r  = splitmix64(h1)
+ *   n  = n_lo + (int)(((r >> 32) * (uint64)(n_hi - n_lo + 1)) >> 32)
+ * Coordinates (binary64, every operation rounded separately, integers converted exactly), y = 0:
+ *   SPAN,  s = size:  target ((n*s) + (2.5*s), 0, s/2);     obstacle slot o < n: ((o+1)*s, 0, s/2)
+ *   TOWER, H = size:  target (x, 0, (n*H) + (H/2));         obstacle slot o < n: (x, 0, (o*H) + (H/2))
+ *   slots o >= n:     (0, 0, BRIDGES_PARK_Z) */
+int bridges_env_set_task_family(bridges_env* env, const bridges_task_family* fam);
+
 /* --- stand-alone operators (same kernels, caller-shaped batches) ------------ */
 /* K1: create_block / align_frames_2d (gym_env.py:204-216, geometry.py:39-50).
  * frame1: [n,6] target frame (c.xz, t.xz, n.xz); shape_id,face: [n]; ox,oy: [n]
@@ -485,6 +517,14 @@ int bridges_record_result(int32_t E, const float* reward, const float* lin_rewar
  * fixed-order reduction (bitwise reproducible), no allocation; E == 0 is a no-op. */
 int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow, int32_t n_targets,
                           int32_t count_first_only, float* run, int32_t* counted, double* out, void* stream);
+/* The same fold by class (the spans / heights of a task family): an ended episode of env e is added to row cls[e] of
+ * out [n_classes, 8], 1 <= n_classes <= 8; cls [E] is the class the episode was played under (bridges_task_family.task_class as
+ * it was BEFORE the step that ended the episode, which redraws it).  A cls[e] outside [0, n_classes) is counted in no row but
+ * still advances run and counted.  One workgroup, one fixed-order reduction per row, no atomics; with n_classes = 1 and cls all
+ * zero, out, run and counted are bridges_episode_stats' bit for bit. */
+int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow,
+                                   int32_t n_targets, int32_t count_first_only, const int32_t* cls, int32_t n_classes, float* run,
+                                   int32_t* counted, double* out /* [n_classes, 8] */, void* stream);
 /* Sampled records -> the state arrays of a replay env of E >= n_rec envs (envs >= n_rec repeat record 0): s' = s plus the
  * action block with the occupancy update of gym_env.py:228-232, its RAW candidate count
  * n_groups * (n_ground + free faces * n_off) (generate_actions, actions.py:7-52; bridges_env_refresh clamps it to the env's

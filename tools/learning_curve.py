@@ -1,4 +1,5 @@
-"""Does the vectorised loop learn?  Trains a Q-network (--model SuccessorMLP | ConvNet | UNet) on tower_height=2 for a fixed
+"""Does the vectorised loop learn?  With --random_bridge_length LO:HI / --random_tower_height LO:HI on a task family, success
+printed per span / height as well.  Trains a Q-network (--model SuccessorMLP | ConvNet | UNet) on tower_height=2 for a fixed
 number of lock-steps and prints per block of lock-steps the statistics of the training episodes that ended in it (EpisodeStats:
 log_episode's discounted reward / lin_reward, length, final stability, and success_rate = the fraction that reached the target,
 all under the running epsilon-greedy exploration) and the mean loss; with --eval_envs N also the greedy evaluation of the policy
@@ -12,7 +13,7 @@ import torch
 from robotoddler.training.successor_dqn import build_parser, make_nets
 from robotoddler.training.vec_dqn import VecDQN
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGym
+from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=1024)
@@ -35,10 +36,23 @@ ap.add_argument("--random_obstacles", type=int, default=0, metavar="O",
                      "the evaluation env draws its own")
 ap.add_argument("--task_channels", action="store_true",
                 help="with --random_targets and --model ConvNet | UNet: the conv Q-network on the per-env tasks (VecDQN(task_channels=True))")
+ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI",
+                help="a task family instead: horizontal_bridge_setup(num_obstacles=n) per env and episode, n drawn from LO..HI "
+                     "(RandomBridges; SuccessorMLP, or ConvNet / UNet with --task_channels)")
+ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
+                help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
 a = ap.parse_args()
+if a.random_bridge_length and a.random_tower_height:
+    ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
+family = None
+if a.random_bridge_length or a.random_tower_height:
+    if a.random_targets or a.random_obstacles:
+        ap.error("a task family draws targets and obstacles from one integer: not with --random_targets / --random_obstacles")
+    lo, hi = (a.random_bridge_length or a.random_tower_height).split(":")
+    family = ("span" if a.random_bridge_length else "tower", int(lo), int(hi))
 if a.random_obstacles and not a.random_targets:
     ap.error("--random_obstacles rides on --random_targets")
-if a.task_channels and not a.random_targets:
+if a.task_channels and not (a.random_targets or family):
     ap.error("--task_channels rides on --random_targets")
 dev = torch.device("cuda:0")
 args = vars(build_parser().parse_args(["--model", a.model, "--loss_function", a.loss]))
@@ -50,11 +64,13 @@ if a.random_targets:
     obstacles, targets = (lambda: []), (lambda: RandomTargets(a.random_targets))
 if a.random_obstacles:
     obstacles = lambda: RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles)
+if family:
+    obstacles, targets = (lambda: []), (lambda: RandomBridges(family[0], sizes=family[1:]))
 env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels, stable_actions_only=a.stable_actions_only)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
-               eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets),
-               per_env_obstacles=bool(a.random_obstacles), task_channels=a.task_channels)
+               eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets or family),
+               per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels)
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
@@ -72,8 +88,13 @@ for it in range(1, a.locksteps + 1):
                     success_rate=r4(ep["success_rate"]), episode_reward=r4(ep["reward"]), episode_lin_reward=r4(ep["lin_reward"]),
                     episode_num_steps=r4(ep["num_steps"]), episode_stable=r4(ep["stable"]),
                     mean_loss=round(float(np.mean(losses)), 5) if losses else None)
+        if family:                                              # success per span / height n = LO..HI, and the episodes behind it
+            line.update(success_by_class={n: r4(c["success_rate"]) for n, c in enumerate(ep["by_class"]) if n >= family[1]},
+                        episodes_by_class={n: c["episodes"] for n, c in enumerate(ep["by_class"]) if n >= family[1]})
         if eval_env is not None:
             ev = agent.evaluate(eval_env, a.eval_epsilon)
             line.update(eval_success_rate=r4(ev["success_rate"]), eval_reward=r4(ev["reward"]), eval_num_steps=r4(ev["num_steps"]))
+            if family:
+                line.update(eval_success_by_class={n: r4(s) for n, s in enumerate(ev["success_by_class"]) if n >= family[1]})
         print(json.dumps(line), flush=True)
         deferred = []

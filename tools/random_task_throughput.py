@@ -11,15 +11,20 @@ the time per lock-step together with the candidates per lock-step, not env-steps
   obst_random  RandomObstacles: O obstacles per env, x ~ U[-3, 3), z ~ U[0.3, 2.5), redrawn on the device every episode (per-env
                k_step, k_task_features for the obstacle raster alone, k_raster reading env_obstacle_bits per work item).
 
+--family span:LO:HI | tower:LO:HI adds (or, with --tasks, makes available) one more task --
+  family       RandomBridges: one target and up to HI obstacles per env, both named by ONE integer n in LO..HI redrawn on the
+               device every episode (the per-env kernels, one k_task_features launch per lock-step that draws n).  Its like-for-like
+               counterpart is --random_targets 1 --random_obstacles HI.
+
   python tools/random_task_throughput.py [--envs 4096] [--groups 2] [--steps 100] [--warmup 20] [--tasks bridge,fixed3,random3]
-                                         [--random_obstacles O]
+                                         [--random_obstacles O] [--random_targets T] [--family span:1:4]
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import torch
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGymGroups
+from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGymGroups
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
@@ -30,9 +35,13 @@ ap.add_argument("--max_steps", type=int, default=15)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--tasks", default=None, help="default: bridge,fixed3,random3 (+ obst_fixed,obst_random with --random_obstacles)")
 ap.add_argument("--random_obstacles", type=int, default=0, metavar="O", help="obstacles per env of the obst_* tasks (1..4)")
+ap.add_argument("--random_targets", type=int, default=0, metavar="T",
+                help="> 0: task `uniform` = RandomTargets(T) beside RandomObstacles of --random_obstacles O: the independent samplers")
+ap.add_argument("--family", default=None, metavar="KIND:LO:HI", help="task `family` = RandomBridges(KIND, sizes=(LO, HI)), KIND span | tower")
 a = ap.parse_args()
 if a.tasks is None:
-    a.tasks = "bridge,fixed3,random3" + (",obst_fixed,obst_random" if a.random_obstacles else "")
+    a.tasks = ("family" + (",uniform" if a.random_targets else "") if a.family else
+               "bridge,fixed3,random3" + (",obst_fixed,obst_random" if a.random_obstacles else ""))
 if a.steps < 100:
     sys.exit("--steps must be at least 100")
 
@@ -44,6 +53,12 @@ if a.random_obstacles:
     O = a.random_obstacles
     TASKS["obst_fixed"] = ([(-3.0 + 6.0 * (o + 0.5) / O, 0.0, 0.3) for o in range(O)], TASKS["fixed3"][1])
     TASKS["obst_random"] = (RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * O), TASKS["fixed3"][1])
+if a.random_targets:
+    TASKS["uniform"] = (RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles) if a.random_obstacles else [],
+                        RandomTargets(a.random_targets))
+if a.family:
+    kind, lo, hi = a.family.split(":")
+    TASKS["family"] = ([], RandomBridges(kind, sizes=(int(lo), int(hi))))
 geoms = [load_urdf("shapes/trapezoid.urdf")]
 out = dict(tool="random_task_throughput", envs=a.envs, groups=a.groups, steps=a.steps, warmup=a.warmup, max_steps=a.max_steps,
            device=torch.cuda.get_device_name(0), tasks={})
@@ -70,10 +85,13 @@ for name in a.tasks.split(","):
              reset_only=d["reset_only"], candidates_per_state=d["sum_cand"] / states,
              candidates_per_lockstep=d["sum_cand"] / a.steps, valid_per_state=d["sum_valid"] / states,
              blocks_per_state=d["sum_blocks"] / states)
-    if name in ("random3", "obst_random"):
+    if name in ("random3", "obst_random", "uniform", "family"):
         ep = torch.cat([e.task_episode for e in env.envs]).double()
         r["episodes_per_env"] = float(ep.mean())               # since the reset: warm-up included
         r["tasks_drawn_per_lockstep"] = float(ep.sum()) / (a.steps + a.warmup)
+    if name == "family":
+        cls = torch.cat([e.task_class for e in env.envs])
+        r["envs_by_class"] = torch.bincount(cls, minlength=int(hi) + 1).tolist()      # the tasks held at the end of the run
     out["tasks"][name] = r
     del env
     torch.cuda.empty_cache()

@@ -8,7 +8,7 @@ import torch
 from robotoddler.training.successor_dqn import build_parser, make_nets
 from robotoddler.training.vec_dqn import VecDQN
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGym
+from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
@@ -44,12 +44,25 @@ ap.add_argument("--task_channels", action="store_true",
 ap.add_argument("--fixed_obstacles", type=int, default=0, metavar="O",
                 help="> 0, with --fixed_targets: the like-for-like baseline of --random_obstacles O: O fixed obstacles on the floor, "
                      "shared by all envs (combine with --no_dedup)")
+ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI",
+                help="a task family instead: horizontal_bridge_setup(num_obstacles=n) per env and episode, n drawn from LO..HI "
+                     "(RandomBridges; SuccessorMLP, or ConvNet / UNet with --task_channels)")
+ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
+                help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
 a = ap.parse_args()
+if a.random_bridge_length and a.random_tower_height:
+    ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
+family = None
+if a.random_bridge_length or a.random_tower_height:
+    if a.random_targets or a.random_obstacles:
+        ap.error("a task family draws targets and obstacles from one integer: not with --random_targets / --random_obstacles")
+    lo, hi = (a.random_bridge_length or a.random_tower_height).split(":")
+    family = ("span" if a.random_bridge_length else "tower", int(lo), int(hi))
 if a.random_targets and a.fixed_targets:
     ap.error("--random_targets and --fixed_targets are two legs of one comparison: give one")
 if a.random_obstacles and not a.random_targets:
     ap.error("--random_obstacles rides on --random_targets")
-if a.task_channels and not a.random_targets:
+if a.task_channels and not (a.random_targets or family):
     ap.error("--task_channels rides on --random_targets")
 if a.fixed_obstacles and not a.fixed_targets:
     ap.error("--fixed_obstacles is the baseline of --random_obstacles: give it with --fixed_targets")
@@ -63,7 +76,9 @@ pol, tgt = make_nets(args, dev)
 if a.channels_last:
     pol, tgt = pol.to(memory_format=torch.channels_last), tgt.to(memory_format=torch.channels_last)
 names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[a.shapes]
-if a.random_targets:
+if family:
+    obstacles, targets = [], RandomBridges(family[0], sizes=family[1:])
+elif a.random_targets:
     targets = RandomTargets(a.random_targets)
     obstacles = RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles) if a.random_obstacles else []
 elif a.fixed_targets:
@@ -85,8 +100,8 @@ env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obs
                      stable_actions_only=a.stable_actions_only)
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
-               episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets),
-               per_env_obstacles=bool(a.random_obstacles), task_channels=a.task_channels)
+               episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets or family),
+               per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels)
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False

@@ -192,6 +192,9 @@ class TaskBuffers(C.Structure):
 FAMILY_NONE, FAMILY_SPAN, FAMILY_TOWER = 0, 1, 2
 PARK_Z = -1000.0                               # BRIDGES_PARK_Z: z of an obstacle slot the drawn task does not use
 EPISODE_STATS_MAX_CLASSES = 8
+FAMILY_MAX_CLASSES = 8                         # classes of a threshold table (bridges_family_thresholds)
+FAMILY_MAX_WEIGHT = 1 << 20                    # largest weight of a class
+FAMILY_FAIL_SCALE = 65536                      # bridges_family_curriculum: w = w_min + round(fail * 65536)
 
 
 class TaskFamily(C.Structure):
@@ -217,6 +220,7 @@ SIGNATURES = {
     "bridges_env_rebuild_contacts": [vp, vp],
     "bridges_env_set_task_buffers": [vp, C.POINTER(TaskBuffers)],
     "bridges_env_set_task_family": [vp, C.POINTER(TaskFamily)],
+    "bridges_env_set_family_thresholds": [vp, vp],
     "bridges_env_load_targets": [vp, vp],
     "bridges_gate_create": [C.POINTER(vp)],
     "bridges_gate_destroy": [vp],
@@ -257,6 +261,9 @@ SIGNATURES = {
     "bridges_record_result": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_episode_stats": [i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp],
     "bridges_episode_stats_by_class": [i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
+    "bridges_family_thresholds": [vp, i32, vp, vp],
+    "bridges_family_draw": [C.c_uint64, i32, i32, vp, i32, i32, vp, vp, vp],
+    "bridges_family_curriculum": [vp, i32, vp, i32, i32, f64, C.c_uint32, i32, vp, vp, vp],
     "bridges_replay_unpack": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_accumulate": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_stability": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, i64, vp],

@@ -494,6 +494,50 @@ def episode_stats_by_class_(out, rec, valid, gpow, n_targets, run, counted, cls,
     return out
 
 
+def family_thresholds_(thr, w):
+    """thr int64 [C-1] <- the threshold table of the weights w int32 [C] (both on the device; the bits are the header's uint64 /
+    uint32 -- a weight is <= 2^20, a threshold <= 2^32), 1 <= C <= 8 (bridges_family_thresholds).  A weight above 2^20 counts as
+    2^20 and a zero sum gives the table of equal weights: neither is knowable here without a host wait."""
+    L = abi.require_gpu()
+    C_ = w.numel()
+    assert w.dtype == torch.int32 and w.dim() == 1 and w.is_contiguous() and 1 <= C_ <= abi.FAMILY_MAX_CLASSES
+    assert thr.dtype == torch.int64 and thr.dim() == 1 and thr.numel() == C_ - 1 and thr.is_contiguous()
+    abi.check(L.bridges_family_thresholds(_ptr(w), C_, _ptr(thr) if C_ > 1 else None, _stream()), "bridges_family_thresholds")
+    return thr
+
+
+def family_draw(seed, env_id_base, episode, n_lo, n_hi, thr=None):
+    """-> int32 [E]: the class env env_id_base + i draws in its episode episode[i] (int32 [E], the bits of the env's uint32
+    task_episode) from n_lo..n_hi, uniformly or -- thr int64 [n_hi - n_lo] -- by the threshold table (bridges_family_draw)."""
+    L = abi.require_gpu()
+    E = episode.numel()
+    assert episode.dtype == torch.int32 and episode.dim() == 1 and episode.is_contiguous()
+    C_ = int(n_hi) - int(n_lo) + 1
+    if thr is not None:
+        assert thr.dtype == torch.int64 and thr.dim() == 1 and thr.numel() == C_ - 1 and thr.is_contiguous()
+        assert thr.device == episode.device
+    out = torch.empty(E, dtype=torch.int32, device=episode.device)
+    abi.check(L.bridges_family_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base), E, _ptr(episode), int(n_lo), int(n_hi),
+                                    _ptr(thr) if thr is not None and C_ > 1 else None, _ptr(out), _stream()), "bridges_family_draw")
+    return out
+
+
+def family_curriculum_(sums, state, n_lo, n_hi, beta, w_min, min_episodes, w, thr):
+    """One curriculum update in place (bridges_family_curriculum): sums float64 [n_classes, 8] (episode_stats_by_class_'s rows;
+    consumed rows are zeroed), state float64 [n_classes, 2] = (ema, seen), w int32 [C] and thr int64 [C-1] the new weights and
+    table of the classes n_lo..n_hi."""
+    L = abi.require_gpu()
+    C_ = int(n_hi) - int(n_lo) + 1
+    assert sums.dtype == torch.float64 and sums.dim() == 2 and sums.shape[1] == 8 and sums.is_contiguous()
+    assert state.dtype == torch.float64 and state.shape == (sums.shape[0], 2) and state.is_contiguous()
+    assert w.dtype == torch.int32 and w.dim() == 1 and w.numel() == C_ and w.is_contiguous()
+    assert thr.dtype == torch.int64 and thr.dim() == 1 and thr.numel() == C_ - 1 and thr.is_contiguous()
+    abi.check(L.bridges_family_curriculum(_ptr(sums), int(sums.shape[0]), _ptr(state), int(n_lo), int(n_hi), float(beta), int(w_min),
+                                          int(min_episodes), _ptr(w), _ptr(thr) if C_ > 1 else None, _stream()),
+              "bridges_family_curriculum")
+    return w, thr
+
+
 def bits_dot(bits, img, slot, bits_row=None):
     """out[r] = sum(img[slot[r]] * raster(bits[bits_row[r]])) for bit-packed 64x64 rasters (bridges_bits_dot): img
     [n_slots,64,64] float32, slot [n] int64 -> [n] float32."""

@@ -153,12 +153,15 @@ class RandomBridges:
     ``bridge_setup(H=size, num_stories=n)`` at ``x`` (kind "tower", gym_env.py:46-61).  The env has one target and ``hi``
     obstacle slots; the slots a drawn task does not use are parked at z = abi.PARK_Z, where they rasterise to nothing.  The
     draw happens on the device, keyed by (seed, global env id, episode); its formula and the coordinates are in
-    include/bridges_hip.h (bridges_env_set_task_family).  Pass ``obstacles=[]`` (or None, or the same object) beside it."""
+    include/bridges_hip.h (bridges_env_set_task_family).  Pass ``obstacles=[]`` (or None, or the same object) beside it.
+    ``weights``: hi - lo + 1 non-negative integers, each <= 2^20, not all zero -- class lo + k is drawn with probability
+    weights[k] / sum(weights) through a threshold table (bridges_env_set_family_thresholds); None is the uniform draw, and
+    equal weights give the uniform draw's classes draw for draw."""
 
     KINDS = dict(span=abi.FAMILY_SPAN, tower=abi.FAMILY_TOWER)
     DEFAULT_SIZE = dict(span=0.6, tower=0.8)
 
-    def __init__(self, kind="span", sizes=(1, 4), size=None, x=0.5):
+    def __init__(self, kind="span", sizes=(1, 4), size=None, x=0.5, weights=None):
         if kind not in self.KINDS:
             raise ValueError(f"kind must be 'span' or 'tower', got {kind!r}")
         try:
@@ -175,6 +178,7 @@ class RandomBridges:
         if not self.size > 0:
             raise ValueError("size must be > 0")
         self.x = float(x)
+        self.weights = None if weights is None else check_family_weights(weights, self.hi - self.lo + 1)
 
     @property
     def family(self):
@@ -200,6 +204,36 @@ class RandomBridges:
             target = (self.x, 0.0, n * s + s / 2)
             live = [(self.x, 0.0, o * s + s / 2) for o in range(n)]
         return [target], live + [(0.0, 0.0, abi.PARK_Z)] * (self.hi - n)
+
+
+def check_family_weights(weights, n):
+    """-> the weights of a family of n classes as a tuple of ints; ValueError unless they are n non-negative integers, each at
+    most 2^20 (abi.FAMILY_MAX_WEIGHT), with a sum > 0."""
+    try:
+        ws = list(weights)
+        ok = all(int(w) == w for w in ws)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"weights must be a sequence of integers, got {weights!r}")
+    ws = tuple(int(w) for w in ws)
+    if len(ws) != n:
+        raise ValueError(f"weights must hold one weight per class (hi - lo + 1 = {n}), got {len(ws)}")
+    if any(w < 0 or w > abi.FAMILY_MAX_WEIGHT for w in ws):
+        raise ValueError(f"weights must satisfy 0 <= w <= {abi.FAMILY_MAX_WEIGHT}, got {weights!r}")
+    if sum(ws) == 0:
+        raise ValueError("weights must not all be zero")
+    return ws
+
+
+def family_thresholds(weights):
+    """The threshold table of a weighted class draw as Python ints: thr[k] = ceil((w[0] + .. + w[k]) * 2^32 / sum(w)),
+    k = 0..C-2 -- what bridges_family_thresholds writes on the device."""
+    total, cum, out = sum(weights), 0, []
+    for w in weights[:-1]:
+        cum += w
+        out.append(-((-cum << 32) // total))
+    return out
 
 
 def _is_per_env_targets(targets):
@@ -264,6 +298,8 @@ class VecAssemblyGym:
         self.random_obstacles = None
         self.task_family = None                      # set by _attach_task_family
         self.task_class = None
+        self.family_weights = None                   # set by set_family_weights: int32 [C], int64 [C-1] on the device
+        self.family_thresholds = None
         if isinstance(targets, RandomBridges):
             if not (obstacles is None or obstacles is targets or (isinstance(obstacles, (list, tuple)) and len(obstacles) == 0)):
                 raise ValueError("RandomBridges draws the obstacles with the target: pass obstacles=[] (or None) beside it")
@@ -330,6 +366,8 @@ class VecAssemblyGym:
             self._init_obstacles(torch.zeros((self.E, self.n_obstacles, 3), dtype=torch.float64))
             self._attach_task_buffers(None)
             self._attach_task_family(targets)
+            if targets.weights is not None:
+                self.set_family_weights(targets.weights)
             self.reset()
             return
         if self.n_obstacles:
@@ -507,6 +545,7 @@ class VecAssemblyGym:
         abi.check(self.L.bridges_env_set_task_buffers(self._env, C.byref(tb)), "bridges_env_set_task_buffers")
         self.random_targets = sampler
         self.task_family = None                              # the library drops a family with the buffers it was set on
+        self.family_weights = self.family_thresholds = None  # and the family's threshold table with it
         self.per_env_tasks = True
         self.targets = None
         b = self.task_buf
@@ -525,6 +564,31 @@ class VecAssemblyGym:
         fam.task_class = self.task_class.data_ptr()
         abi.check(self.L.bridges_env_set_task_family(self._env, C.byref(fam)), "bridges_env_set_task_family")
         self.task_family = sampler
+        self.family_weights = self.family_thresholds = None
+
+    def set_family_weights(self, weights):
+        """Weights of the family's classes lo..hi (RandomBridges(weights=...) documents them), or None for the uniform draw.
+        Takes effect from the next episode each env starts; resets nothing and waits for nothing.  The table is built on the
+        device (ops.family_thresholds_) into ``family_thresholds`` (int64 [C-1]: the bits of the library's uint64) from
+        ``family_weights`` (int32 [C]); both tensors stay the same objects over later calls, and a kernel that rewrites
+        family_thresholds in the env's stream (ops.family_curriculum_) changes the draws of the lock-steps after it."""
+        if self.task_family is None:
+            raise ValueError("set_family_weights needs a task family (targets=RandomBridges(...))")
+        if weights is None:
+            abi.check(self.L.bridges_env_set_family_thresholds(self._env, None), "bridges_env_set_family_thresholds")
+            self.family_weights = self.family_thresholds = None
+            return
+        n = self.task_family.hi - self.task_family.lo + 1
+        ws = check_family_weights(weights, n)
+        if self.family_weights is None:
+            self.family_weights = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.family_thresholds = torch.zeros(n - 1, dtype=torch.int64, device=self.device)
+        self.family_weights.copy_(torch.tensor(ws, dtype=torch.int32))
+        from .ops import family_thresholds_
+        family_thresholds_(self.family_thresholds, self.family_weights)
+        if n > 1:                                            # one class: no table, the draw is lo either way
+            abi.check(self.L.bridges_env_set_family_thresholds(self._env, self.family_thresholds.data_ptr()),
+                      "bridges_env_set_family_thresholds")
 
     def set_targets(self, targets, reset=True):
         """Explicit per-env targets ([E, T, 3] float64, T = the env's number of targets) that stay until set again; a sampler
@@ -974,6 +1038,12 @@ class VecAssemblyGymGroups:
             with torch.cuda.stream(st):
                 env.set_targets(targets[lo:lo + env.E], reset=reset)
             lo += env.E
+
+    def set_family_weights(self, weights):
+        """VecAssemblyGym.set_family_weights for every group, on its own stream (every group keeps a table of its own)."""
+        for env, st in zip(self.envs, self.streams):
+            with torch.cuda.stream(st):
+                env.set_family_weights(weights)
 
     def set_obstacles(self, obstacles, reset=True):
         """VecAssemblyGym.set_obstacles for all E envs ([E, O, 3]): every group takes its slice, on its own stream."""

@@ -98,7 +98,14 @@ struct bridges_env {
     const double* fixed_reward_prefix;
     // task family (bridges_env_set_task_family): family.family != BRIDGES_FAMILY_NONE while one is set
     bridges_task_family family;
+    // its threshold table (bridges_env_set_family_thresholds): caller-owned device memory, NULL = the uniform draw
+    const uint64_t* family_thr;
 };
+
+static void clear_family(bridges_env* env) {
+    memset(&env->family, 0, sizeof(env->family));
+    env->family_thr = nullptr;
+}
 
 // The previous lock-step's candidate count (+3 %, at least one per env), which sizes the grids over candidates.  Those
 // kernels grid-stride, so a stale or low estimate costs time, never correctness.
@@ -189,7 +196,7 @@ int bridges_env_create(const bridges_task* t, const bridges_env_buffers* buf, br
     env->raster_done = nullptr;
     env->has_tasks = false;
     memset(&env->tasks, 0, sizeof(env->tasks));
-    memset(&env->family, 0, sizeof(env->family));
+    clear_family(env);
     env->fixed_reward_map = buf->reward_map;
     env->fixed_reward_prefix = buf->reward_prefix;
     // mapped, coherent host word: k_scan stores the candidate count of the lock-step straight into it (no copy command
@@ -318,6 +325,9 @@ static int refresh(bridges_env* env, hipStream_t s, int after_step) {
 }
 
 static int task_features(bridges_env* env, void* stream, int mode) {
+    if (env->family.family != BRIDGES_FAMILY_NONE && env->family_thr)
+        return launch("k_task_features (weighted task family)", k_task_features<bridges_task_family, const uint64_t*>, dim3(env->ctx.E),
+                      dim3(TASK_THREADS), 0, stream, env->ctx, env->tasks, mode, env->family, env->family_thr);
     if (env->family.family != BRIDGES_FAMILY_NONE)
         return launch("k_task_features (task family)", k_task_features<bridges_task_family>, dim3(env->ctx.E), dim3(TASK_THREADS), 0,
                       stream, env->ctx, env->tasks, mode, env->family);
@@ -351,7 +361,7 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
     if (!env) return fail_arg("null env");
     DevCtx& c = env->ctx;
     if (!tb) {
-        memset(&env->family, 0, sizeof(env->family));
+        clear_family(env);
         env->has_tasks = false;
         memset(&env->tasks, 0, sizeof(env->tasks));
         c.b.reward_map = env->fixed_reward_map;
@@ -376,7 +386,7 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
     if (tb->sample != 0 && tb->sample != 1) return fail_arg("task buffers: sample must be 0 or 1");
     if (tb->sample && !(tb->x_range[0] <= tb->x_range[1] && tb->z_range[0] <= tb->z_range[1])) return fail_arg("task buffers: x_range / z_range");
     env->tasks = *tb;
-    memset(&env->family, 0, sizeof(env->family));      // a family belongs to the buffers it was set on
+    clear_family(env);      // a family belongs to the buffers it was set on
     env->has_tasks = true;
     c.b.reward_map = tb->reward_map;
     c.b.reward_prefix = tb->reward_prefix;
@@ -386,7 +396,7 @@ int bridges_env_set_task_buffers(bridges_env* env, const bridges_task_buffers* t
 int bridges_env_set_task_family(bridges_env* env, const bridges_task_family* fam) {
     if (!env) return fail_arg("null env");
     if (!fam || fam->family == BRIDGES_FAMILY_NONE) {
-        memset(&env->family, 0, sizeof(env->family));
+        clear_family(env);
         return BRIDGES_OK;
     }
     if (fam->family != BRIDGES_FAMILY_SPAN && fam->family != BRIDGES_FAMILY_TOWER) return fail_arg("task family: family must be NONE, SPAN or TOWER");
@@ -398,6 +408,14 @@ int bridges_env_set_task_family(bridges_env* env, const bridges_task_family* fam
     if (!(fam->size > 0.0)) return fail_arg("task family: size must be > 0");
     if (!fam->task_class) return fail_arg("task family: task_class not given");
     env->family = *fam;
+    env->family_thr = nullptr;                         // a table belongs to the family it was set on
+    return BRIDGES_OK;
+}
+
+int bridges_env_set_family_thresholds(bridges_env* env, const uint64_t* thr_dev) {
+    if (!env) return fail_arg("null env");
+    if (env->family.family == BRIDGES_FAMILY_NONE) return fail_arg("family thresholds: no task family set");
+    env->family_thr = thr_dev;
     return BRIDGES_OK;
 }
 
@@ -687,6 +705,35 @@ int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, cons
     if (E == 0) return BRIDGES_OK;
     return launch("k_episode_stats_by_class", k_episode_stats_by_class, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec,
                   valid, gpow, (int)n_targets, (int)(count_first_only != 0), cls, (int)n_classes, run, counted, out);
+}
+
+int bridges_family_thresholds(const uint32_t* w_dev, int32_t C, uint64_t* thr_dev, void* stream) {
+    if (C < 1 || C > FAMILY_MAX_CLASSES) return fail_arg("bridges_family_thresholds: C must be 1..8");
+    if (!w_dev || (C > 1 && !thr_dev)) return fail_arg("bridges_family_thresholds");
+    if (C == 1) return BRIDGES_OK;                     // one class: the table has no entry
+    return launch("k_family_thresholds", k_family_thresholds, dim3(1), dim3(WAVE), 0, stream, w_dev, (int)C, thr_dev);
+}
+
+int bridges_family_draw(uint64_t seed, int32_t env_id_base, int32_t E, const uint32_t* episode, int32_t n_lo, int32_t n_hi,
+                        const uint64_t* thr, int32_t* n_out, void* stream) {
+    if (E < 0 || (E > 0 && (!episode || !n_out))) return fail_arg("bridges_family_draw");
+    if (n_lo < 0 || n_lo > n_hi || n_hi - n_lo + 1 > FAMILY_MAX_CLASSES) return fail_arg("bridges_family_draw: 0 <= n_lo <= n_hi, at most 8 classes");
+    if (E == 0) return BRIDGES_OK;
+    return launch("k_family_draw", k_family_draw, dim3((E + FAMILY_DRAW_THREADS - 1) / FAMILY_DRAW_THREADS), dim3(FAMILY_DRAW_THREADS), 0,
+                  stream, seed, (int)env_id_base, (int)E, episode, (int)n_lo, (int)n_hi, thr, n_out);
+}
+
+int bridges_family_curriculum(double* sums, int32_t n_classes, double* state, int32_t n_lo, int32_t n_hi, double beta, uint32_t w_min,
+                              int32_t min_episodes, uint32_t* w, uint64_t* thr, void* stream) {
+    if (!sums || !state || !w) return fail_arg("bridges_family_curriculum");
+    if (n_classes < 1 || n_classes > EPISODE_STATS_MAX_CLASSES) return fail_arg("bridges_family_curriculum: n_classes must be 1..8");
+    if (n_lo < 0 || n_lo > n_hi || n_hi >= n_classes) return fail_arg("bridges_family_curriculum: 0 <= n_lo <= n_hi < n_classes");
+    if (n_hi > n_lo && !thr) return fail_arg("bridges_family_curriculum: thr not given");
+    if (!(beta >= 0.0 && beta <= 1.0)) return fail_arg("bridges_family_curriculum: beta must be in [0, 1]");
+    if (w_min < 1 || w_min > FAMILY_MAX_WEIGHT - 65536u) return fail_arg("bridges_family_curriculum: w_min must be 1..2^20 - 2^16");
+    if (min_episodes < 1) return fail_arg("bridges_family_curriculum: min_episodes must be >= 1");
+    return launch("k_family_curriculum", k_family_curriculum, dim3(1), dim3(WAVE), 0, stream, sums, state, (int)n_lo, (int)n_hi, beta,
+                  w_min, (int)min_episodes, w, thr);
 }
 
 int bridges_replay_unpack(int32_t E, int32_t n_rec, int32_t K, const double* rec, const int32_t* shape_faces, int32_t n_shapes,

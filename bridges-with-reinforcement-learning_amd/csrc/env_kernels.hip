@@ -790,13 +790,38 @@ static_assert(IMG % (TASK_WAVES * TASK_ROWS_IN_FLIGHT) == 0, "map rows are dealt
 // and the obstacles that n names in place of the uniform draws; unused obstacle slots are parked at z = BRIDGES_PARK_Z, where
 // the cube rasterises to nothing.  The optional trailing argument keeps the kernel without a family what it was.
 #define FAMI_SALT 0x66616D695F726E67ull     // "fami_rng"
+// The class draw of a family, in one place (k_task_features<bridges_task_family...> and the stand-alone k_family_draw): the word
+// r of (seed, global env id, episode) on the family's stream, u = r >> 32, and
+//   thr == nullptr:  n = n_lo + ((u * C) >> 32)                         C = n_hi - n_lo + 1  (the uniform draw)
+//   thr [C - 1]:     n = n_lo + #{k in 0..C-2 : u >= thr[k]}            (weighted: header comment of
+//                                                                        bridges_env_set_family_thresholds)
+// Integer arithmetic only.  thr is read with plain loads at every draw: a kernel earlier in the stream may have rewritten it.
+__device__ __forceinline__ int family_class(uint64_t seed, uint32_t gid, uint32_t ep, int n_lo, int n_hi, const uint64_t* thr) {
+    const uint64_t h0 = splitmix64((((seed & 0xFFFFFFFFull) << 32) | gid) ^ FAMI_SALT);
+    const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
+    const uint64_t r = splitmix64(h1);
+    const uint64_t u = r >> 32;
+    const int C = n_hi - n_lo + 1;
+    if (!thr) return n_lo + (int)((u * (uint64_t)C) >> 32);
+    int n = n_lo;
+    for (int k = 0; k < C - 1; ++k) n += u >= thr[k] ? 1 : 0;
+    return n;
+}
 __device__ __forceinline__ bridges_task_family task_family() { return bridges_task_family{}; }
 __device__ __forceinline__ bridges_task_family task_family(const bridges_task_family& f) { return f; }
+__device__ __forceinline__ bridges_task_family task_family(const bridges_task_family& f, const uint64_t*) { return f; }
+__device__ __forceinline__ const uint64_t* task_thresholds() { return nullptr; }
+__device__ __forceinline__ const uint64_t* task_thresholds(const bridges_task_family&) { return nullptr; }
+__device__ __forceinline__ const uint64_t* task_thresholds(const bridges_task_family&, const uint64_t* thr) { return thr; }
+// FAMILY... is empty (no family), <bridges_task_family> (the uniform draw) or <bridges_task_family, const uint64_t*> (a threshold
+// table attached: the weighted draw); the first two are the kernels they were before the third existed.
 template <typename... FAMILY>
 __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridges_task_buffers t, int mode, FAMILY... family_arg) {
-    constexpr bool FAM = sizeof...(FAMILY) == 1;
+    constexpr bool FAM = sizeof...(FAMILY) >= 1;
     const bridges_task_family fam = task_family(family_arg...);
+    const uint64_t* const fam_thr = task_thresholds(family_arg...);
     (void)fam;
+    (void)fam_thr;
     const bool draw_obstacles = FAM ? true : t.sample_obstacles != 0, draw_targets = FAM ? true : t.sample != 0;
     __shared__ float kz[TASK_KZ];
     __shared__ uint64_t tb_l[IMG];
@@ -821,10 +846,7 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
     int fam_n = 0;                                  // the env's span / height of this episode (every thread draws it)
     if constexpr (FAM) {
         if (mode != TASK_LOAD) {
-            const uint64_t h0 = splitmix64((((c.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(c.env_id_base + e)) ^ FAMI_SALT);
-            const uint64_t h1 = splitmix64(h0 ^ (uint64_t)ep);
-            const uint64_t r = splitmix64(h1);
-            fam_n = fam.n_lo + (int)(((r >> 32) * (uint64_t)(fam.n_hi - fam.n_lo + 1)) >> 32);
+            fam_n = family_class(c.seed, (uint32_t)(c.env_id_base + e), ep, fam.n_lo, fam.n_hi, fam_thr);
             if (tid == 0) fam.task_class[e] = fam_n;
         }
     }
@@ -976,6 +998,79 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
     __syncthreads();
     double* pre_g = t.reward_prefix + (size_t)e * IMG * TASK_ROW;
     for (int i = tid; i < IMG * TASK_ROW; i += TASK_THREADS) pre_g[i] = pre_l[i];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Weighted families and the curriculum (header comments of bridges_family_thresholds / _draw / _curriculum).
+// The stand-alone class draw: thread i draws the class of env env_id_base + i in its episode episode[i].
+constexpr int FAMILY_MAX_CLASSES = 8;
+constexpr uint32_t FAMILY_MAX_WEIGHT = 1u << 20;
+constexpr int FAMILY_DRAW_THREADS = 256;
+__global__ __launch_bounds__(FAMILY_DRAW_THREADS) void k_family_draw(uint64_t seed, int env_id_base, int E,
+                                                                     const uint32_t* __restrict__ episode, int n_lo, int n_hi,
+                                                                     const uint64_t* thr, int32_t* __restrict__ n_out) {
+    const int i = blockIdx.x * FAMILY_DRAW_THREADS + threadIdx.x;
+    if (i >= E) return;
+    n_out[i] = family_class(seed, (uint32_t)(env_id_base + i), episode[i], n_lo, n_hi, thr);
+}
+
+// thr[k] = ceil((w[0] + .. + w[k]) * 2^32 / sum(w)), k = 0..C-2, in exact integer arithmetic: a weight is at most 2^20 (a larger
+// one is taken as 2^20) and C <= 8, so a partial sum is < 2^24 and its product with 2^32 < 2^56.  sum(w) == 0 cannot be refused
+// from inside the stream: the table of equal weights is written instead.  One thread: seven 64-bit divisions.
+__device__ void family_thresholds_from_weights(const uint32_t* w, int C, uint64_t* thr) {
+    uint64_t sum = 0;
+    for (int k = 0; k < C; ++k) sum += w[k] < FAMILY_MAX_WEIGHT ? w[k] : FAMILY_MAX_WEIGHT;
+    const bool equal = sum == 0;
+    if (equal) sum = (uint64_t)C;
+    uint64_t cum = 0;
+    for (int k = 0; k < C - 1; ++k) {
+        cum += equal ? 1u : (w[k] < FAMILY_MAX_WEIGHT ? w[k] : FAMILY_MAX_WEIGHT);
+        thr[k] = ((cum << 32) + sum - 1) / sum;
+    }
+}
+
+__global__ __launch_bounds__(WAVE) void k_family_thresholds(const uint32_t* w, int C, uint64_t* thr) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) family_thresholds_from_weights(w, C, thr);
+}
+
+// The curriculum update.  ONE workgroup of one wave; lane k < C owns class n = n_lo + k: row n of sums [n_classes, 8] (the
+// layout of k_episode_stats_by_class: slot 0 = episodes, slot 5 = successes) and row n of state [n_classes, 2] = (ema, seen).
+//   e = sums[n][0];  e >= min_episodes:  rate = sums[n][5] / e;  ema = seen ? ema + beta * (rate - ema) : rate  (every operation
+//   rounded to binary64 on its own);  seen = 1;  the row of sums is zeroed.  A row below min_episodes stays and accumulates.
+//   fail = seen ? min(max(1 - ema, 0), 1) : 1;   w[k] = w_min + (uint32)(fail * 65536.0 + 0.5)
+// Then lane 0 builds thr from w (family_thresholds_from_weights).  Rows outside [n_lo, n_hi] are neither read nor written.
+// Fixed order, no atomics, no allocation.
+__global__ __launch_bounds__(WAVE) void k_family_curriculum(double* __restrict__ sums, double* __restrict__ state, int n_lo, int n_hi,
+                                                           double beta, uint32_t w_min, int min_episodes, uint32_t* __restrict__ w,
+                                                           uint64_t* __restrict__ thr) {
+    __shared__ uint32_t w_l[FAMILY_MAX_CLASSES];
+    const int k = threadIdx.x, C = n_hi - n_lo + 1;
+    if (k < C) {
+        double* row = sums + (size_t)(n_lo + k) * 8;
+        double* st = state + (size_t)(n_lo + k) * 2;
+        double ema = st[0];
+        bool seen = st[1] != 0.0;
+        const double e = row[0];
+        if (e >= (double)min_episodes) {
+            const double rate = __ddiv_rn(row[5], e);
+            ema = seen ? __dadd_rn(ema, __dmul_rn(beta, __dsub_rn(rate, ema))) : rate;
+            seen = true;
+            st[0] = ema;
+            st[1] = 1.0;
+            for (int s = 0; s < 8; ++s) row[s] = 0.0;
+        }
+        double fail = 1.0;
+        if (seen) {
+            fail = __dsub_rn(1.0, ema);
+            fail = fail > 0.0 ? fail : 0.0;
+            fail = fail < 1.0 ? fail : 1.0;
+        }
+        const uint32_t wk = w_min + (uint32_t)__dadd_rn(__dmul_rn(fail, 65536.0), 0.5);
+        w_l[k] = wk;
+        w[k] = wk;
+    }
+    __syncthreads();
+    if (k == 0) family_thresholds_from_weights(w_l, C, thr);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -530,7 +530,34 @@ def build_parser():
     p.add_argument("--random_tower_height", type=parse_size_range, default=argparse.SUPPRESS, metavar="LO:HI",
                    help="Vectorised loop: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI, as "
                         "--random_bridge_length draws the span.")
+    add_curriculum_arguments(p)
     return p
+
+
+def add_curriculum_arguments(p):
+    """--family_weights and --curriculum*: how a task family (--random_bridge_length / --random_tower_height) draws its classes;
+    shared with the tools that take the family options."""
+    p.add_argument("--family_weights", type=parse_family_weights, default=argparse.SUPPRESS, metavar="W,W,...",
+                   help="With --random_bridge_length / --random_tower_height LO:HI: HI - LO + 1 non-negative integer weights "
+                        "(each <= 2^20, not all zero); n = LO + k is drawn with probability W[k] / sum(W) instead of uniformly. "
+                        "The evaluation envs stay uniform.")
+    p.add_argument("--curriculum", action="store_true", default=argparse.SUPPRESS,
+                   help="With --random_bridge_length / --random_tower_height: adapt the weights on the device -- every "
+                        "--curriculum_every lock-steps the weight of n becomes floor + the failure rate of the training episodes "
+                        "played on n (an exponential moving average), so episodes move to the spans / heights the policy fails on.")
+    p.add_argument("--curriculum_every", type=int, default=argparse.SUPPRESS, help="Lock-steps between curriculum updates (10).")
+    p.add_argument("--curriculum_beta", type=float, default=argparse.SUPPRESS,
+                   help="Weight of the newest success rate in the moving average, 0..1 (0.25).")
+    p.add_argument("--curriculum_floor", type=float, default=argparse.SUPPRESS,
+                   help="Share of the weight scale every n keeps whatever its success, 0..1 (0.1): no n is starved.")
+
+
+def parse_family_weights(text):
+    """'W,W,...' -> (W, W, ...), integers."""
+    try:
+        return tuple(int(w) for w in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected W,W,... (integers), got {text!r}")
 
 
 def parse_size_range(text):
@@ -552,6 +579,7 @@ def check_random_targets(args):
     conv = bool(args.get('task_channels', False))
     if args.get('random_bridge_length') is not None or args.get('random_tower_height') is not None:
         return check_random_bridges(args)
+    check_curriculum(args, None)
     if conv and T is None:
         raise SystemExit("--task_channels is valid only together with --random_targets T: it feeds the conv Q-networks the task "
                          "of every env, and without --random_targets all envs share one task")
@@ -618,6 +646,39 @@ def check_random_bridges(args):
     if not conv and args['model'] != 'SuccessorMLP':
         raise SystemExit(f"{flag} with --model {args['model']} needs --task_channels: the conv Q-networks take the task of every "
                          "env as image channels")
+    check_curriculum(args, (lo, hi))
+
+
+CURRICULUM_OPTIONS = ("curriculum_every", "curriculum_beta", "curriculum_floor")
+
+
+def check_curriculum(args, sizes):
+    """--family_weights / --curriculum*: ``sizes`` is the (LO, HI) of an accepted --random_bridge_length / --random_tower_height
+    (which has checked --num_envs > 1 already), None without one; refusals in words (SystemExit) as everywhere here."""
+    weights, on = args.get('family_weights'), bool(args.get('curriculum'))
+    given = [f"--{k}" for k in CURRICULUM_OPTIONS if args.get(k) is not None]
+    if sizes is None:
+        asked = (["--family_weights"] if weights is not None else []) + (["--curriculum"] if on else []) + given
+        if asked:
+            raise SystemExit(f"{asked[0]} weighs the classes of a task family: it needs --random_bridge_length LO:HI or "
+                             "--random_tower_height LO:HI (and the vectorised loop, --num_envs N, N > 1)")
+        return
+    if given and not on:
+        raise SystemExit(f"{given[0]} is a setting of --curriculum: give --curriculum as well")
+    if on and weights is not None:
+        raise SystemExit("--curriculum adapts the weights itself: it cannot be combined with the fixed --family_weights")
+    if weights is not None:
+        from bridges_hip.vec_env import check_family_weights
+        try:
+            check_family_weights(weights, sizes[1] - sizes[0] + 1)
+        except ValueError as e:
+            raise SystemExit(f"--family_weights: {e}")
+    if on:
+        from robotoddler.training.vec_dqn import curriculum_from_args
+        try:
+            curriculum_from_args(args)
+        except ValueError as e:
+            raise SystemExit(f"--{e}".replace("--curriculum: ", "--curriculum_"))
 
 
 def make_setup_fct(args):

@@ -37,6 +37,7 @@ from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 from robotoddler.training import distributed as D
 from robotoddler.training import records as R
+from robotoddler.training.curriculum import Curriculum, CurriculumRun
 from robotoddler.training.episode_stats import EpisodeStats
 from robotoddler.training import train_step as T
 
@@ -48,7 +49,7 @@ OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
-                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False):
+                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -64,7 +65,9 @@ class VecDQN:
         reward map and the obstacle raster of its env (of its transition, in replay) beside its block and action rasters, all
         four channels written by one launch from the bit-packed rasters and a map index (ops.conv_input); rows are shared by
         (state, candidate, stable flag, task); the optimiser step is the autograd body on per-transition rows.  Neither the
-        rollout env nor the replay scratch env needs f32 rasters in this mode."""
+        rollout env nor the replay scratch env needs f32 rasters in this mode.
+        ``curriculum=Curriculum(...)`` (a rollout env on a task family only): the weights of the family's classes follow the
+        failure rate per class on the device (robotoddler.training.curriculum); evaluation envs are not touched."""
         self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
         self.task_channels = bool(task_channels)
         if self.task_channels:
@@ -141,6 +144,9 @@ class VecDQN:
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
                               if episode_stats else None)
         self._eval_state = {}                                # evaluate(): (random stream, EpisodeStats, count images) per env shape
+        # the curriculum keeps an accumulator of its own: whether and when the logging statistics above are taken is not its business
+        self.curriculum = CurriculumRun(curriculum, env, gamma) if curriculum is not None else None
+        self.curriculum_weights_host = None                  # pinned copy of the weights as of the last lock-step
 
     @staticmethod
     def _n_classes(env):
@@ -711,10 +717,13 @@ class VecDQN:
 
     # ------------------------------------------------------------------ checkpoint of what the nets / ring do not hold
     def save_extra(self, path, **counters):
-        torch.save(dict(epsilon=float(self.epsilon), episodes_done=int(self.episodes_done), env_steps=int(self.env_steps),
-                        step_images=self.step_images.cpu(), sample_gen=self.sample_gen.get_state().cpu(),
-                        explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()},
-                        task_shape=(int(self.n_task_targets), int(self.n_task_obstacles))), path)
+        blob = dict(epsilon=float(self.epsilon), episodes_done=int(self.episodes_done), env_steps=int(self.env_steps),
+                    step_images=self.step_images.cpu(), sample_gen=self.sample_gen.get_state().cpu(),
+                    explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()},
+                    task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)))
+        if getattr(self, "curriculum", None) is not None:    # one more key: (ema, seen), weights, sums and accumulator
+            blob["curriculum"] = self.curriculum.state_dict()
+        torch.save(blob, path)
 
     def load_extra(self, path):
         """Restores what save_extra wrote.  The file is rank 0's: exact continuation (same exploration draws, same
@@ -737,6 +746,8 @@ class VecDQN:
             self.explore_gen.set_state(blob["explore_gen"])
         else:
             self.explore_gen.manual_seed(7654321 + self.seed * 1000 + self.rank + 7919 * (int(blob["counters"].get("lockstep", 0)) + 1))
+        if getattr(self, "curriculum", None) is not None and "curriculum" in blob:     # continue with the same table
+            self.curriculum.load_state_dict(blob["curriculum"])
         return blob["counters"]
 
     # ------------------------------------------------------------------ driver
@@ -748,6 +759,10 @@ class VecDQN:
         if self.episode_stats is not None:
             # before the all-gather: env identity still holds (a task family: under the class of before the step)
             self.episode_stats.fold(rec, valid, cls=self.env._task_class if self.episode_stats.n_classes > 1 else None)
+        if self.curriculum is not None:
+            # every `every` lock-steps this launches the update as well: the draws of the next lock-step's step read its table
+            self.curriculum.fold(rec, valid, self.env._task_class)
+            self.curriculum_weights_host = self.curriculum.weights_to_host()
         if self.prioritized:
             rec[:, R.O_TD] = self.td_errors(rec).to(rec.dtype)
         # ONE wait per lock-step on this side: the two counts ride to pinned memory in front of the next act's candidate rows,
@@ -797,7 +812,8 @@ def lockstep_log_values(info):
     Then the per-episode statistics (EpisodeStats): the episodes that ended in the lock-step on all ranks and the means over
     them of log_episode's discounted reward / lin_reward, episode length and final stability, and the fraction that reached
     the targets (None when no episode ended).  A run on a task family (info['success_by_class']: a list indexed by the drawn
-    n) appends success_rate_n{k}, the success rate of the episodes played on n = k, for the family's n_lo..n_hi."""
+    n) appends success_rate_n{k}, the success rate of the episodes played on n = k, for the family's n_lo..n_hi; a run with a
+    curriculum (info['curriculum_weights']: the weights of n_lo..n_hi) appends curriculum_weight_n{n}."""
     vals = dict(reward=info['mean_reward'], lin_reward=info['mean_lin_reward'], avg_loss=info['avg_loss'],
                 num_steps=info['lockstep_env_steps'], epsilon=info['epsilon'], env_steps=info['env_steps'],
                 steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
@@ -805,11 +821,24 @@ def lockstep_log_values(info):
     if by_class is not None:
         lo = info.get('class_lo', 0)
         vals.update({f"success_rate_n{k}": v for k, v in enumerate(by_class) if k >= lo})
+    weights = info.get('curriculum_weights')
+    if weights is not None:                                  # the curriculum's weight of every class n = class_lo + k
+        vals.update({f"curriculum_weight_n{info.get('class_lo', 0) + k}": w for k, w in enumerate(weights)})
     return vals
 
 
 # per-lock-step keys of the episode statistics in run_vectorised's info (and lockstep_log_values), in log order
 EPISODE_KEYS = ("episodes_finished", "episode_reward", "episode_lin_reward", "episode_num_steps", "episode_stable", "success_rate")
+
+
+def curriculum_from_args(args):
+    """--curriculum [--curriculum_every N --curriculum_beta B --curriculum_floor F] -> Curriculum, or None without --curriculum."""
+    if not args.get('curriculum'):
+        return None
+    defaults = Curriculum()
+    return Curriculum(beta=args.get('curriculum_beta', defaults.beta), floor=args.get('curriculum_floor', defaults.floor),
+                      every=args.get('curriculum_every', defaults.every),
+                      min_episodes=args.get('curriculum_min_episodes', defaults.min_episodes))
 
 
 def next_multiple(n, every):
@@ -835,7 +864,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     if family:
         # horizontal_bridge_setup(num_obstacles=n) / bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI on the
         # device: one target, up to HI obstacles, both per env
-        targets, obstacles = RandomBridges(family[0], sizes=family[1:]), []
+        # --family_weights: fixed weights of the classes LO..HI (the evaluation env below stays uniform)
+        targets, obstacles = RandomBridges(family[0], sizes=family[1:], weights=args.get('family_weights')), []
     elif random_targets:
         # tower_setup(num_targets=T) per env and episode (gym_env.py:64-79 of the reference): no obstacles, every env draws
         # its own targets whenever it starts an episode; --random_obstacles O: and O obstacles beside them, as connecting_setup
@@ -863,7 +893,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
                    per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
-                   task_channels=task_channels)
+                   task_channels=task_channels, curriculum=curriculum_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -893,7 +923,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
 
     def finish(entry):
         """Fill in the numbers of a lock-step that were still on their way to the host when its entry was made."""
-        info, deferred, stats_host, done, episodes = entry
+        info, deferred, stats_host, done, episodes, weights_host = entry
         ls = deferred.get()
         info['avg_loss'] = float(np.mean(ls)) if ls else None
         if stats_host is not None:
@@ -905,6 +935,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         if 'by_class' in ep:
             info.update(success_by_class=[c['success_rate'] for c in ep['by_class']],
                         episodes_by_class=[c['episodes'] for c in ep['by_class']], class_lo=family[1])
+        if weights_host is not None:                         # copied in front of the losses and the statistics waited for above
+            info.update(curriculum_weights=weights_host.tolist(), class_lo=family[1])
         if rank == 0 and (aim_run is not None or wandb_run is not None):
             # one call per lock-step, step = episodes finished so far (the reference's x axis is the episode number)
             track_run_sinks(lockstep_log_values(info), info['episodes'], 'training', aim_run=aim_run, wandb_run=wandb_run)
@@ -958,7 +990,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         history.append(info)
         if pending is not None:
             finish(pending)
-        pending = (info, losses, stats_host, done, episodes)
+        pending = (info, losses, stats_host, done, episodes, agent.curriculum_weights_host)
     if pending is not None:
         finish(pending)
     T.sync_optimizer(policy_net)       # the captured step counts Adam's steps itself: hand the count back before anyone reads opt.state

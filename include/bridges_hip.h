@@ -308,6 +308,22 @@ typedef struct {
  *   slots o >= n:     (0, 0, BRIDGES_PARK_Z) */
 int bridges_env_set_task_family(bridges_env* env, const bridges_task_family* fam);
 
+/* --- weighted families and the curriculum ----------------------------------------
+ * A family may carry a threshold table thr: uint64 [C - 1] in device memory, C = n_hi - n_lo + 1.  The draw then uses the
+ * family's word r exactly as above (same stream, same salt, same (seed, gid, task_episode)) and, with u = r >> 32,
+ *   n = n_lo + #{ k in 0..C-2 : u >= thr[k] }
+ * in place of the last line of the uniform draw.  The table of non-negative integer weights w[0..C-1], each <= 2^20, sum > 0:
+ *   thr[k] = ceil((w[0] + .. + w[k]) * 2^32 / sum(w))         exact integer arithmetic (the numerator is < 2^56)
+ * Class n_lo + k is drawn for thr[k-1] <= u < thr[k] (thr[-1] = 0, thr[C-1] = 2^32): a zero-weight class has an empty interval
+ * and is never drawn; a trailing zero weight gives thr = 2^32, above every u.  Equal weights give thr[k] =
+ * ceil((k+1) * 2^32 / C), and  u >= ceil(j * 2^32 / C)  <=>  u * C >= j * 2^32  <=>  (u * C) >> 32 >= j:  the uniform draw, for every u.
+ *
+ * Attach (or, with NULL, detach) a table.  Refused (BRIDGES_E_ARG) without a family set; cleared wherever the family is
+ * cleared (bridges_env_set_task_family, bridges_env_set_task_buffers).  Enqueues nothing and reads nothing: the buffer stays
+ * the caller's, every draw reads it afresh, so a kernel may rewrite it in-stream and the next lock-step's draw sees the new
+ * values.  With no table attached the env launches the kernel it launched before tables existed. */
+int bridges_env_set_family_thresholds(bridges_env* env, const uint64_t* thr_dev /* [C-1] or NULL */);
+
 /* --- stand-alone operators (same kernels, caller-shaped batches) ------------ */
 /* K1: create_block / align_frames_2d (gym_env.py:204-216, geometry.py:39-50).
  * frame1: [n,6] target frame (c.xz, t.xz, n.xz); shape_id,face: [n]; ox,oy: [n]
@@ -525,6 +541,29 @@ int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t
 int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow,
                                    int32_t n_targets, int32_t count_first_only, const int32_t* cls, int32_t n_classes, float* run,
                                    int32_t* counted, double* out /* [n_classes, 8] */, void* stream);
+/* Task-family operators (bridges_env_set_family_thresholds has the formulas).
+ * bridges_family_thresholds: thr_dev [C-1] from the weights w_dev [C] on the device, 1 <= C <= 8 (C == 1: nothing to write,
+ * nothing is enqueued).  The weights live in device memory, so neither their sum nor their size is knowable here without a
+ * host wait: a weight above 2^20 is taken as 2^20, and sum(w) == 0 writes the table of equal weights.  (A caller that holds
+ * the weights on the host -- bridges_hip.vec_env.RandomBridges(weights=...) -- refuses both before anything is enqueued.) */
+int bridges_family_thresholds(const uint32_t* w_dev, int32_t C, uint64_t* thr_dev, void* stream);
+/* The class draw of a family on caller-shaped batches: n_out[i] = the class env env_id_base + i draws in its episode
+ * episode[i] under (seed, n_lo, n_hi) and the table thr [n_hi - n_lo] (NULL: the uniform draw) -- the function
+ * bridges_env_reset / _step run inside their task kernel.  0 <= n_lo <= n_hi, at most 8 classes. */
+int bridges_family_draw(uint64_t seed, int32_t env_id_base, int32_t E, const uint32_t* episode /* [E] */, int32_t n_lo, int32_t n_hi,
+                        const uint64_t* thr /* or NULL */, int32_t* n_out /* [E] */, void* stream);
+/* Curriculum update: move the draw towards the classes the policy fails on.  sums [n_classes, 8] float64 has the layout of
+ * bridges_episode_stats_by_class (row = class n, slot 0 = episodes, slot 5 = successes), state [n_classes, 2] float64 =
+ * (ema, seen); rows outside [n_lo, n_hi] are neither read nor written.  For n in n_lo..n_hi, e = sums[n][0]:
+ *   e >= min_episodes:  rate = sums[n][5] / e;  ema = seen ? ema + beta * (rate - ema) : rate;  seen = 1;  sums[n][:] = 0
+ *                       (binary64, every operation rounded separately, no contraction)
+ *   e <  min_episodes:  the row stays and keeps accumulating
+ *   fail = seen ? min(max(1 - ema, 0), 1) : 1;      w[n - n_lo] = w_min + (uint32)(fail * 65536.0 + 0.5)
+ * and thr [n_hi - n_lo] from w as bridges_family_thresholds builds it.  1 <= w_min <= 2^20 - 2^16 keeps every class drawable
+ * and every weight <= 2^20; 0 <= beta <= 1; min_episodes >= 1; 0 <= n_lo <= n_hi < n_classes <= 8.  One workgroup, fixed order,
+ * no atomics, no allocation, no host wait. */
+int bridges_family_curriculum(double* sums, int32_t n_classes, double* state, int32_t n_lo, int32_t n_hi, double beta, uint32_t w_min,
+                              int32_t min_episodes, uint32_t* w /* [C] */, uint64_t* thr /* [C-1] */, void* stream);
 /* Sampled records -> the state arrays of a replay env of E >= n_rec envs (envs >= n_rec repeat record 0): s' = s plus the
  * action block with the occupancy update of gym_env.py:228-232, its RAW candidate count
  * n_groups * (n_ground + free faces * n_off) (generate_actions, actions.py:7-52; bridges_env_refresh clamps it to the env's

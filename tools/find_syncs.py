@@ -1,7 +1,9 @@
 """Lists the host synchronisations of one pipelined VecDQN lock-step (torch.cuda.set_sync_debug_mode): each one is a
 point where the host stops queueing work until the GPU has caught up.  Usage: python tools/find_syncs.py [--model M]
 [--episode_stats]: with the per-episode statistics on, every lock-step also folds its records and hands the sums to pinned
-memory, as run_vectorised does (the count printed should not change)."""
+memory, as run_vectorised does (the count printed should not change).  --random_bridge_length LO:HI runs the lock-step on a task
+family (RandomBridges), --curriculum [--curriculum_every N ...] with its curriculum on as well: with --curriculum_every 1 the listed
+lock-step holds the fold AND the update, and the count should be that of the same line without --curriculum."""
 import argparse
 import os
 import sys
@@ -16,21 +18,28 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--model", default="SuccessorMLP")
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--episode_stats", action="store_true", help="VecDQN(episode_stats=True) plus one EpisodeStats.take() per lock-step")
-a = ap.parse_args()
+ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI", help="a task family (RandomBridges) instead of the fixed tower")
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import VecAssemblyGym
-from robotoddler.training.successor_dqn import build_parser, make_nets
-from robotoddler.training.vec_dqn import VecDQN
+from bridges_hip.vec_env import RandomBridges, VecAssemblyGym
+from robotoddler.training.successor_dqn import add_curriculum_arguments, build_parser, check_curriculum, make_nets
+from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
+add_curriculum_arguments(ap)
+a = ap.parse_args()
+sizes = tuple(int(v) for v in a.random_bridge_length.split(":")) if a.random_bridge_length else None
+check_curriculum(vars(a), sizes)
 
 dev = torch.device("cuda:0")
 args = vars(build_parser().parse_args(["--model", a.model]))
 pol, tgt = make_nets(args, dev)
 H = 0.8
-env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(4)],
-                     [(0.5, 0, 4 * H + H / 2)], max_steps=15, seed=0, device=dev,
+obstacles, targets = [(0.5, 0., i * H + H / 2) for i in range(4)], [(0.5, 0, 4 * H + H / 2)]
+if sizes:
+    obstacles, targets = [], RandomBridges("span", sizes=sizes, weights=vars(a).get("family_weights"))
+env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, targets, max_steps=15, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=False)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
-               "mse_block_features", episode_stats=a.episode_stats)
+               "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes), per_env_obstacles=bool(sizes),
+               curriculum=curriculum_from_args(vars(a)))
 
 
 def lockstep():

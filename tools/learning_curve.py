@@ -10,8 +10,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import numpy as np
 import torch
-from robotoddler.training.successor_dqn import build_parser, make_nets
-from robotoddler.training.vec_dqn import VecDQN
+from robotoddler.training.successor_dqn import add_curriculum_arguments, build_parser, check_curriculum, make_nets
+from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
@@ -41,6 +41,7 @@ ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI",
                      "(RandomBridges; SuccessorMLP, or ConvNet / UNet with --task_channels)")
 ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
                 help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
+add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -50,6 +51,7 @@ if a.random_bridge_length or a.random_tower_height:
         ap.error("a task family draws targets and obstacles from one integer: not with --random_targets / --random_obstacles")
     lo, hi = (a.random_bridge_length or a.random_tower_height).split(":")
     family = ("span" if a.random_bridge_length else "tower", int(lo), int(hi))
+check_curriculum(vars(a), family[1:] if family else None)
 if a.random_obstacles and not a.random_targets:
     ap.error("--random_obstacles rides on --random_targets")
 if a.task_channels and not (a.random_targets or family):
@@ -64,13 +66,16 @@ if a.random_targets:
     obstacles, targets = (lambda: []), (lambda: RandomTargets(a.random_targets))
 if a.random_obstacles:
     obstacles = lambda: RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles)
-if family:
+train_targets = targets
+if family:                                                      # the weights are the training env's: evaluation stays uniform
     obstacles, targets = (lambda: []), (lambda: RandomBridges(family[0], sizes=family[1:]))
-env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=0, device=dev,
+    train_targets = lambda: RandomBridges(family[0], sizes=family[1:], weights=vars(a).get("family_weights"))
+env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), train_targets(), max_steps=a.max_steps, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels, stable_actions_only=a.stable_actions_only)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
                eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets or family),
-               per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels)
+               per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
+               curriculum=curriculum_from_args(vars(a)))
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
@@ -91,6 +96,8 @@ for it in range(1, a.locksteps + 1):
         if family:                                              # success per span / height n = LO..HI, and the episodes behind it
             line.update(success_by_class={n: r4(c["success_rate"]) for n, c in enumerate(ep["by_class"]) if n >= family[1]},
                         episodes_by_class={n: c["episodes"] for n, c in enumerate(ep["by_class"]) if n >= family[1]})
+            if env.family_weights is not None:                  # the weights the next block draws under (one read per block)
+                line.update(weights_by_class={family[1] + k: w for k, w in enumerate(env.family_weights.tolist())})
         if eval_env is not None:
             ev = agent.evaluate(eval_env, a.eval_epsilon)
             line.update(eval_success_rate=r4(ev["success_rate"]), eval_reward=r4(ev["reward"]), eval_num_steps=r4(ev["num_steps"]))

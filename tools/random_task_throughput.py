@@ -38,7 +38,17 @@ ap.add_argument("--random_obstacles", type=int, default=0, metavar="O", help="ob
 ap.add_argument("--random_targets", type=int, default=0, metavar="T",
                 help="> 0: task `uniform` = RandomTargets(T) beside RandomObstacles of --random_obstacles O: the independent samplers")
 ap.add_argument("--family", default=None, metavar="KIND:LO:HI", help="task `family` = RandomBridges(KIND, sizes=(LO, HI)), KIND span | tower")
+ap.add_argument("--family_weights", default=None, metavar="W,W,...",
+                help="with --family: HI - LO + 1 integer weights of the classes LO..HI (the weighted draw: a threshold table read by "
+                     "the task kernel); equal weights draw the classes of the uniform draw")
+ap.add_argument("--curriculum", action="store_true",
+                help="refused here: the curriculum follows a policy's success per class, and this tool steps a uniform-random "
+                     "policy without records (tools/train_throughput.py and tools/learning_curve.py run it)")
 a = ap.parse_args()
+if a.curriculum:
+    ap.error("--curriculum needs the training loop: use tools/train_throughput.py or tools/learning_curve.py")
+if a.family_weights and not a.family:
+    ap.error("--family_weights weighs the classes of --family KIND:LO:HI")
 if a.tasks is None:
     a.tasks = ("family" + (",uniform" if a.random_targets else "") if a.family else
                "bridge,fixed3,random3" + (",obst_fixed,obst_random" if a.random_obstacles else ""))
@@ -58,10 +68,11 @@ if a.random_targets:
                         RandomTargets(a.random_targets))
 if a.family:
     kind, lo, hi = a.family.split(":")
-    TASKS["family"] = ([], RandomBridges(kind, sizes=(int(lo), int(hi))))
+    weights = [int(w) for w in a.family_weights.split(",")] if a.family_weights else None
+    TASKS["family"] = ([], RandomBridges(kind, sizes=(int(lo), int(hi)), weights=weights))
 geoms = [load_urdf("shapes/trapezoid.urdf")]
 out = dict(tool="random_task_throughput", envs=a.envs, groups=a.groups, steps=a.steps, warmup=a.warmup, max_steps=a.max_steps,
-           device=torch.cuda.get_device_name(0), tasks={})
+           device=torch.cuda.get_device_name(0), family_weights=a.family_weights, tasks={})
 for name in a.tasks.split(","):
     obstacles, targets = TASKS[name]
     env = VecAssemblyGymGroups(a.envs, geoms, obstacles, targets, groups=a.groups, max_steps=a.max_steps, seed=a.seed,

@@ -5,8 +5,8 @@ if "--miopen_search" not in sys.argv:
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import torch
-from robotoddler.training.successor_dqn import build_parser, make_nets
-from robotoddler.training.vec_dqn import VecDQN
+from robotoddler.training.successor_dqn import add_curriculum_arguments, build_parser, check_curriculum, make_nets
+from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
@@ -49,6 +49,7 @@ ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI",
                      "(RandomBridges; SuccessorMLP, or ConvNet / UNet with --task_channels)")
 ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
                 help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
+add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -58,6 +59,7 @@ if a.random_bridge_length or a.random_tower_height:
         ap.error("a task family draws targets and obstacles from one integer: not with --random_targets / --random_obstacles")
     lo, hi = (a.random_bridge_length or a.random_tower_height).split(":")
     family = ("span" if a.random_bridge_length else "tower", int(lo), int(hi))
+check_curriculum(vars(a), family[1:] if family else None)
 if a.random_targets and a.fixed_targets:
     ap.error("--random_targets and --fixed_targets are two legs of one comparison: give one")
 if a.random_obstacles and not a.random_targets:
@@ -77,7 +79,7 @@ if a.channels_last:
     pol, tgt = pol.to(memory_format=torch.channels_last), tgt.to(memory_format=torch.channels_last)
 names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[a.shapes]
 if family:
-    obstacles, targets = [], RandomBridges(family[0], sizes=family[1:])
+    obstacles, targets = [], RandomBridges(family[0], sizes=family[1:], weights=vars(a).get("family_weights"))
 elif a.random_targets:
     targets = RandomTargets(a.random_targets)
     obstacles = RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * a.random_obstacles) if a.random_obstacles else []
@@ -101,7 +103,8 @@ env = VecAssemblyGym(a.envs, [load_urdf(f"shapes/{n}.urdf") for n in names], obs
 opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
                episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets or family),
-               per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels)
+               per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
+               curriculum=curriculum_from_args(vars(a)))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -149,7 +152,8 @@ for _ in range(n_phase):
     agent.update_target()
     torch.cuda.synchronize(); t3 = time.perf_counter()
     t_act += t2 - t1; t_train += t3 - t2
-print(json.dumps(dict(config=vars(a), env_steps_per_s=steps_done / dt,
+print(json.dumps(dict(config=vars(a), family_weights=env.family_weights.tolist() if getattr(env, "family_weights", None) is not None else None,
+                      env_steps_per_s=steps_done / dt,
                       env_steps_per_s_at_median_lockstep=steps_done / a.locksteps / median, ms_median_lockstep=median * 1e3,
                       ms_per_lockstep=dt / a.locksteps * 1e3,
                       rows_per_lockstep=rows_seen / a.locksteps, rows_fed_per_lockstep=rows_fed / a.locksteps,

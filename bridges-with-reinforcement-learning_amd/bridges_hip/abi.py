@@ -195,6 +195,7 @@ EPISODE_STATS_MAX_CLASSES = 8
 FAMILY_MAX_CLASSES = 8                         # classes of a threshold table (bridges_family_thresholds)
 FAMILY_MAX_WEIGHT = 1 << 20                    # largest weight of a class
 FAMILY_FAIL_SCALE = 65536                      # bridges_family_curriculum: w = w_min + round(fail * 65536)
+NSTEP_MAX = 8                                  # BRIDGES_NSTEP_MAX: the longest horizon of an n-step record
 
 
 class TaskFamily(C.Structure):
@@ -299,6 +300,9 @@ SIGNATURES = {
     "bridges_conv1x1_o1_backward": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp],
     "bridges_maxpool2_relu_backward": [vp, vp, vp, i64, i32, i32, vp],
     "bridges_td_target": [i32, vp, vp, vp, vp, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp],
+    "bridges_td_target_rows": [i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_nstep_fold": [i32, i32, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_bits_discounted_sum": [i32, vp, i64, vp, vp, f32, vp, vp, vp],
 }
 
 

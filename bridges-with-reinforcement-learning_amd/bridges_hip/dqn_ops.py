@@ -15,13 +15,15 @@ def _ptr(t):
 _stream = abi.current_stream
 
 
-def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_raster=None):
+def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_raster=None, discount=None):
     """Target construction of train_policy_net (successor_dqn.py:197-213, 222, 230) in one kernel.
 
     seg_offset int32 [B+1]: rows [seg_offset[i], seg_offset[i+1]) of next_q / next_sf belong to transition i; or a pair
     (lo, hi) of int32 [B] tensors with the rows [lo[i], hi[i]) (transitions whose next states are the same state share rows).
     next_q f32 [R]; next_sf f32 [R, D] view (row stride may exceed D, e.g. psi[:, 0] of a [R,2,64,64] tensor);
     action_raster f32 [B, D]; lin_reward f32 [B]; done uint8/bool [B].
+    ``discount`` f32 [B]: a discount per transition in place of ``gamma`` (n-step returns: gamma^h of the transition's horizon;
+    bridges_td_target_rows).  None is bridges_td_target with the scalar.
     Returns (q_target [B], sf_target [B, D] or None, argmax_row int32 [B])."""
     L = abi.require_gpu()
     dev = next_q.device
@@ -46,29 +48,59 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
         action_raster = action_raster.to(torch.float32).reshape(B, D).contiguous()
         sf_target = torch.empty((B, D), dtype=torch.float32, device=dev)
         sf_dim = D
+    if discount is not None:
+        discount = discount.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+        assert discount.numel() == B
+        abi.check(L.bridges_td_target_rows(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(next_q), _ptr(next_sf), stride, _ptr(action_raster),
+                                           _ptr(lin_reward), _ptr(done_u8), _ptr(discount), sf_dim, _ptr(q_target), _ptr(sf_target),
+                                           _ptr(argmax_row), _stream()), "bridges_td_target_rows")
+        return q_target, sf_target, argmax_row
     abi.check(L.bridges_td_target(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(next_q), _ptr(next_sf), stride, _ptr(action_raster),
                                   _ptr(lin_reward), _ptr(done_u8), float(gamma), sf_dim, _ptr(q_target), _ptr(sf_target),
                                   _ptr(argmax_row), _stream()), "bridges_td_target")
     return q_target, sf_target, argmax_row
 
 
-def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None):
+def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None):
     """The TD targets of transitions whose next-state rows are the segments ``seg`` of ``next_q`` (td_target's seg_offset).
     -> (q [B], sf [B, D] or None).  With ``lin``: q = lin + gamma q' of each segment's arg-max row, sf = lin + gamma psi' of
     that row + the action raster.  lin=None is the single-env reference form: q is the done-masked q' of the arg-max row (lin 0,
     gamma 1 -- the caller adds its [B, 1] lin_reward by broadcasting) and sf takes lin 0.  ``next_sf``: psi' of every row, or
-    a callable that returns psi' of the arg-max rows from their indices (callers that compute it for those rows only)."""
+    a callable that returns psi' of the arg-max rows from their indices (callers that compute it for those rows only).
+    ``discount`` f32 [B] (with ``lin``): a discount per transition in place of gamma, in both targets (td_target's)."""
     nq = next_q.contiguous().float()
     zeros = torch.zeros(done.numel(), dtype=torch.float32, device=nq.device) if lin is None else lin
-    q, _, arg = td_target(seg, nq, zeros, done, 1.0 if lin is None else gamma)
+    if discount is not None and lin is None:
+        raise ValueError("next_targets(discount=...) is the vectorised form: it needs lin")
+    q, _, arg = td_target(seg, nq, zeros, done, 1.0 if lin is None else gamma, discount=discount)
     if next_sf is None:
         return q, None
     if callable(next_sf):
         best = arg.long().clamp_(0, nq.numel() - 1)                       # empty segments are 'done': row unused
         next_sf = next_sf(best)
         seg, nq = torch.arange(done.numel() + 1, dtype=torch.int32, device=nq.device), nq[best].contiguous()
-    _, sf, _ = td_target(seg, nq, zeros, done, gamma, next_sf=next_sf, action_raster=action_raster)
+    _, sf, _ = td_target(seg, nq, zeros, done, gamma, next_sf=next_sf, action_raster=action_raster, discount=discount)
     return q, sf
+
+
+def nstep_fold(rec, valid, gamma, n, count, acc, disc, stable_s, td):
+    """The n-step fold of one lock-step's one-step records (bridges_nstep_fold): rec [E, W] float64 (W >= RECORD_WIDTH: the record
+    and its task tail), valid [E] bool / uint8; the window state count [E] int32 and acc, disc, stable_s, td [E, n] float64 is
+    updated in place.  -> (out [E * n, W + 1] float64, out_valid [E * n] bool): env e's emitted h-step records are the rows
+    e * n ..., oldest first, marked in out_valid; the content of the other rows is unspecified.  No host wait."""
+    L = abi.require_gpu()
+    E, W = rec.shape
+    assert rec.dtype == torch.float64 and rec.is_contiguous() and valid.numel() == E
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == E
+    for t in (acc, disc, stable_s, td):
+        assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (E, n)
+    valid = valid.contiguous()
+    valid_u8 = valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)
+    out = torch.empty((E * n, W + 1), dtype=torch.float64, device=rec.device)
+    out_valid = torch.empty(E * n, dtype=torch.bool, device=rec.device)
+    abi.check(L.bridges_nstep_fold(E, W, int(n), _ptr(rec), _ptr(valid_u8), float(gamma), _ptr(count), _ptr(acc), _ptr(disc),
+                                   _ptr(stable_s), _ptr(td), _ptr(out), _ptr(out_valid), _stream()), "bridges_nstep_fold")
+    return out, out_valid
 
 
 def soft_update_(target, policy, tau):

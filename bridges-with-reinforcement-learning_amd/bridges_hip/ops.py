@@ -281,6 +281,26 @@ def bits_to_f32(bits):
     return img
 
 
+def bits_discounted_sum(bits, first, h, gamma, want_sum=True):
+    """The discounted sum of consecutive block rasters (bridges_bits_discounted_sum): bits [R, 64] int64, first [B] int64 and
+    h [B] int32 (1..abi.NSTEP_MAX) -> (sum [B, 64, 64] float32, disc [B] float32) with
+    sum[i] = sum_{k < h[i]} d_k * image(bits[first[i] + k]) and disc[i] = d_{h[i]}, d_0 = 1, d_{k+1} = d_k * gamma in float32;
+    h = 1 everywhere gives bits_to_f32(bits[first]) bit for bit.  want_sum=False: (None, disc)."""
+    L = abi.require_gpu()
+    bits = bits.reshape(-1, 64)
+    assert bits.is_contiguous() and bits.dtype == torch.int64
+    first = first.to(torch.int64).contiguous()
+    h = h.to(torch.int32).contiguous()
+    B = first.numel()
+    assert h.numel() == B
+    img = torch.empty((B, 64, 64), dtype=torch.float32, device=bits.device) if want_sum else None
+    disc = torch.empty(B, dtype=torch.float32, device=bits.device)
+    if B:
+        abi.check(L.bridges_bits_discounted_sum(B, _ptr(bits), bits.shape[0], _ptr(first), _ptr(h), float(gamma), _ptr(img), _ptr(disc),
+                                                _stream()), "bridges_bits_discounted_sum")
+    return img, disc
+
+
 def bits_linear(bits, wt, bits_row=None, base=None, base_row=None):
     """out[r] = base[base_row[r]] + sum of the rows of ``wt`` ([4096, d], pixel-major) selected by the set pixels of the
     bit-packed raster ``bits[bits_row[r]]`` ([*,64] int64): a linear layer applied to flattened binary images without

@@ -640,6 +640,42 @@ int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg
                   next_sf_row_stride, action_raster, lin_reward, done, gamma, sf_dim, q_target, sf_target, argmax_row);
 }
 
+int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
+                           int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
+                           const uint8_t* done, const float* discount, int32_t sf_dim, float* q_target, float* sf_target,
+                           int32_t* argmax_row, void* stream) {
+    if (n_trans < 0 || sf_dim < 0 || (n_trans > 0 && (!seg_lo || !seg_hi || !discount))) return fail_arg("bridges_td_target_rows");
+    if (n_trans == 0) return BRIDGES_OK;
+    if (sf_dim > 0 && ((next_sf_row_stride & 3) || (sf_dim & 3) || !aligned(16, next_sf, action_raster, sf_target)))
+        return fail_arg("td_target_rows: sf rows must be 16-byte aligned");
+    return launch("k_td_target_rows", k_td_target_rows, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi, next_q, next_sf,
+                  next_sf_row_stride, action_raster, lin_reward, done, discount, sf_dim, q_target, sf_target, argmax_row);
+}
+
+int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
+                       double* acc, double* disc, double* stable_s, double* td, double* out, uint8_t* out_valid, void* stream) {
+    if (E < 0 || n < 1 || n > BRIDGES_NSTEP_MAX) return fail_arg("bridges_nstep_fold: n must be 1..BRIDGES_NSTEP_MAX");
+    if (W < BRIDGES_REC_WIDTH) return fail_arg("bridges_nstep_fold: a record has at least BRIDGES_REC_WIDTH columns");
+    if (!rec || !valid || !count || !acc || !disc || !stable_s || !td || !out || !out_valid) return fail_arg("bridges_nstep_fold");
+    if (!aligned(8, rec, acc, disc, stable_s, td, out) || !aligned(4, count))
+        return fail_arg("bridges_nstep_fold: misaligned pointer");
+    if (E == 0) return BRIDGES_OK;
+    // one wave per env, four envs per workgroup
+    return launch("k_nstep_fold", k_nstep_fold, dim3((unsigned)ceil_div(E, 4)), dim3(256), 0, stream, (int)E, (int)W, (int)n, rec, valid,
+                  gamma, count, acc, disc, stable_s, td, out, out_valid);
+}
+
+int bridges_bits_discounted_sum(int32_t n, const uint64_t* bits, int64_t n_rows, const int64_t* first, const int32_t* h, float gamma,
+                                float* sum, float* disc, void* stream) {
+    if (n < 0 || n_rows < 0 || (n > 0 && (!bits || !first || !h || !disc))) return fail_arg("bridges_bits_discounted_sum");
+    if (!aligned(16, sum) || !aligned(8, bits, first) || !aligned(4, h, disc))
+        return fail_arg("bits_discounted_sum: misaligned pointer (sum: 16 bytes)");
+    if (n == 0) return BRIDGES_OK;
+    // one short-lived wave per transition, dispatched in transition order (the store structure of k_raster)
+    return launch("k_bits_discounted_sum", k_bits_discounted_sum, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, (int)n, bits,
+                  n_rows, first, h, gamma, sum, disc);
+}
+
 int bridges_bits_linear(int32_t n_rows, const uint64_t* bits, const int64_t* bits_row, const float* wt, int32_t d,
                         const float* base, const int64_t* base_row, float* out, void* stream) {
     if (n_rows < 0 || d <= 0 || (d & 3) || !bits || !wt || !out) return fail_arg("bridges_bits_linear");

@@ -164,6 +164,146 @@ __global__ __launch_bounds__(256) void k_td_target(int n_trans, const int32_t* _
     }
 }
 
+// k_td_target with a discount PER TRANSITION (n-step returns: discount[i] = gamma^h of transition i's horizon):
+//   q_target[i] = lin_reward[i] + discount[i] * q',  sf_target[i,:] = action_raster[i,:] + discount[i] * psi'.
+// Everything else is k_td_target's, statement for statement -- the first-maximum rule, the empty-segment and done rules, both
+// segment forms, the strided next_sf, argmax_row -- so a discount filled with gamma gives k_td_target's outputs bit for bit.
+__global__ __launch_bounds__(256) void k_td_target_rows(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
+                                                        const float* __restrict__ next_q, const float* __restrict__ next_sf,
+                                                        int64_t sf_row_stride, const float* __restrict__ action_raster,
+                                                        const float* __restrict__ lin_reward, const uint8_t* __restrict__ done,
+                                                        const float* __restrict__ discount, int sf_dim, float* __restrict__ q_target,
+                                                        float* __restrict__ sf_target, int32_t* __restrict__ argmax_row) {
+    __shared__ float s_val[256];
+    __shared__ int s_idx[256];
+    const int i = blockIdx.x, t = threadIdx.x;
+    const int lo = seg_lo[i], hi = seg_hi[i];
+    const float gamma = discount[i];
+    float best = -INFINITY;
+    int bidx = 0x7fffffff;
+    for (int j = lo + t; j < hi; j += 256) {
+        float v = next_q[j];
+        if (v > best || (v == best && j < bidx) || bidx == 0x7fffffff) { best = v; bidx = j; }   // NaN-free inputs
+    }
+    s_val[t] = best; s_idx[t] = bidx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            float v = s_val[t + o]; int k = s_idx[t + o];
+            if (k != 0x7fffffff && (s_idx[t] == 0x7fffffff || v > s_val[t] || (v == s_val[t] && k < s_idx[t]))) {
+                s_val[t] = v; s_idx[t] = k;
+            }
+        }
+        __syncthreads();
+    }
+    const int row = s_idx[0];
+    const bool dn = done[i] != 0;
+    const bool no_next = dn || row == 0x7fffffff;       // an empty segment has no next row: nothing of next_sf is read for it
+    if (t == 0) {
+        float nq = dn ? 0.f : s_val[0];
+        q_target[i] = lin_reward[i] + gamma * nq;
+        argmax_row[i] = row;
+    }
+    if (sf_dim > 0) {
+        const float* src = next_sf + (int64_t)row * sf_row_stride;
+        const float* ar = action_raster + (int64_t)i * sf_dim;
+        float* dst = sf_target + (int64_t)i * sf_dim;
+        const int n4 = sf_dim >> 2;
+        for (int k = t; k < n4; k += 256) {
+            float4 a = reinterpret_cast<const float4*>(ar)[k];
+            float4 s = no_next ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(src)[k];
+            float4 o;
+            o.x = a.x + gamma * s.x; o.y = a.y + gamma * s.y; o.z = a.z + gamma * s.z; o.w = a.w + gamma * s.w;
+            reinterpret_cast<float4*>(dst)[k] = o;
+        }
+        for (int k = (n4 << 2) + t; k < sf_dim; k += 256) dst[k] = ar[k] + gamma * (no_next ? 0.f : src[k]);
+    }
+}
+
+// The n-step fold of one lock-step's one-step records (robotoddler/training/vec_dqn.py, DESIGN.md "n-step returns"): every env
+// keeps a window of up to n pending starts -- the return accumulated so far, the discount of the next reward, and the start's
+// stable(s) flag and priority -- and per valid transition
+//   1. a start is appended (acc 0, disc 1, the record's STABLE_S and TD),
+//   2. every pending start j takes the reward: acc_j += disc_j * lin, disc_j *= gamma            (float64),
+//   3. a done record emits every pending start, oldest first, with horizon h_j = count - j, and empties the window; otherwise a
+//      full window (count == n) emits its oldest start with h = n and shifts the rest down.
+// An emitted row is the CURRENT record (block list, action, DONE, STABLE_N, REWARD, task tail: the last step's) with LIN = acc_j,
+// STABLE_S and TD = the start's, and h_j in the new last column W.  Env e's rows are out[e * n ...], oldest first; out_valid marks
+// them, the rest of the env's n rows is not written.  An env without a valid transition keeps its window and emits nothing.
+// One wave per env, four envs per workgroup: the window update is wave-uniform (every lane holds the window in registers, lane 0
+// writes it back), the lanes stride the columns of the row copies (8-byte accesses, consecutive lanes on consecutive doubles).
+// No atomics, no count: the caller sums out_valid.
+__global__ __launch_bounds__(256) void k_nstep_fold(int E, int W, int n, const double* __restrict__ rec, const uint8_t* __restrict__ valid,
+                                                    double gamma, int32_t* __restrict__ count, double* __restrict__ acc,
+                                                    double* __restrict__ disc, double* __restrict__ stable_s, double* __restrict__ td,
+                                                    double* __restrict__ out, uint8_t* __restrict__ out_valid) {
+    constexpr int N = BRIDGES_NSTEP_MAX;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int e = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    if (e >= E) return;
+    const double* row = rec + (size_t)e * W;
+    int n_emit = 0, c = 0;
+    double a[N], d[N], ss[N], pr[N];
+    if (valid[e]) {
+        c = count[e];
+        c = c < 0 ? 0 : (c > n - 1 ? n - 1 : c);            // the invariant of the window: at most n - 1 starts are pending here
+        const double lin = row[BRIDGES_REC_LIN], r_ss = row[BRIDGES_REC_STABLE_S], r_td = row[BRIDGES_REC_TD];
+        const bool dn = row[BRIDGES_REC_DONE] > 0.5;
+        const size_t w0 = (size_t)e * n;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const bool live = j < c;
+            a[j] = live ? acc[w0 + j] : 0.0;
+            d[j] = live ? disc[w0 + j] : 1.0;
+            ss[j] = live ? stable_s[w0 + j] : r_ss;         // slot c is the appended start; the slots above it are never read
+            pr[j] = live ? td[w0 + j] : r_td;
+        }
+        c += 1;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            if (j < c) {
+                a[j] += d[j] * lin;
+                d[j] *= gamma;
+            }
+        }
+        n_emit = dn ? c : (c == n ? 1 : 0);
+        // the window after the emissions: empty, shifted down by one, or as it is
+        const int keep = dn ? 0 : c - n_emit;
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                if (j < keep) {
+                    const int s = (j + 1 < N) ? j + 1 : j;
+                    acc[w0 + j] = n_emit ? a[s] : a[j];
+                    disc[w0 + j] = n_emit ? d[s] : d[j];
+                    stable_s[w0 + j] = n_emit ? ss[s] : ss[j];
+                    td[w0 + j] = n_emit ? pr[s] : pr[j];
+                }
+            }
+            count[e] = keep;
+        }
+    }
+    if (lane < n) out_valid[(size_t)e * n + lane] = lane < n_emit;
+    if (n_emit == 0) return;
+    const int Wo = W + 1;
+    double* dst = out + (size_t)e * n * Wo;
+    for (int c0 = 0; c0 < Wo; c0 += WAVE) {
+        const int col = c0 + lane;
+        const double v = col < W ? row[col] : 0.0;
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+            if (r < n_emit && col < Wo) {
+                double o = v;
+                if (col == BRIDGES_REC_LIN) o = a[r];
+                if (col == BRIDGES_REC_STABLE_S) o = ss[r];
+                if (col == BRIDGES_REC_TD) o = pr[r];
+                if (col == W) o = (double)(c - r);
+                dst[(size_t)r * Wo + col] = o;
+            }
+        }
+    }
+}
+
 // K8: first layer of an MLP that consumes flattened binary 64x64 rasters, fed with the bit-packed rasters themselves
 // (cv.py:95-97 concatenates block / action / reward / obstacle images and multiplies by W1; a block covers ~35 of the
 // 4096 pixels, so the product with its raster is the sum of ~35 rows of the transposed weight slice):

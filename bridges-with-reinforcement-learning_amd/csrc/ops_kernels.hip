@@ -280,6 +280,71 @@ __global__ __launch_bounds__(256) void k_conv_input(int n_rows, const uint64_t* 
     write_f32_image(dst, words[lane], lane);
 }
 
+// The discounted sum of h consecutive block rasters per transition (the action part of an h-step successor-feature target):
+//   sum[i] = sum_{k < h[i]} d_k * image(bits[first[i] + k]),  disc[i] = d_{h[i]},  d_0 = 1, d_{k+1} = d_k * gamma in float32
+// in the bit-to-pixel order of k_bits_to_f32; the terms are added in ascending k from the k = 0 image, so h = 1 writes exactly
+// the 0.0f / 1.0f of k_bits_to_f32.  One short-lived wave per transition, the store structure of k_bits_to_f32 / k_conv_input:
+// every wave instruction stores a contiguous 1 KiB of float4, and the (at most 8) words a lane needs are all loaded before its
+// first store.  first / h are wave-uniform; h is clamped to 0..BRIDGES_NSTEP_MAX and the rows to the n_rows of the table, so a
+// bad index reads nothing outside it.  sum may be null: only disc is written then.
+__global__ __launch_bounds__(256) void k_bits_discounted_sum(int n, const uint64_t* __restrict__ bits, int64_t n_rows,
+                                                             const int64_t* __restrict__ first, const int32_t* __restrict__ h,
+                                                             float gamma, float* __restrict__ sum, float* __restrict__ disc) {
+    constexpr int N = BRIDGES_NSTEP_MAX;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t it = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    if (it >= n) return;
+    int64_t f = first[it];
+    int hh = h[it];
+    f = f < 0 ? 0 : (f > n_rows ? n_rows : f);
+    hh = hh < 0 ? 0 : (hh > N ? N : hh);
+    if ((int64_t)hh > n_rows - f) hh = (int)(n_rows - f);
+    uint64_t w[N];
+    float d[N + 1];
+    d[0] = 1.f;
+    uint64_t any = 0ull;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        w[k] = k < hh ? bits[(size_t)(f + k) * IMG + lane] : 0ull;
+        any |= w[k];
+        d[k + 1] = d[k] * gamma;
+    }
+    if (lane == 0) {
+        float dh = d[0];
+#pragma unroll
+        for (int k = 1; k <= N; ++k) dh = k == hh ? d[k] : dh;
+        disc[it] = dh;
+    }
+    if (!sum) return;
+    float* img = sum + (size_t)it * IMG * IMG;
+    const int sub = lane >> 4, col4 = (lane & 15) * 4;
+    const uint64_t nonzero_rows = __ballot(any != 0ull);           // most of a raster is empty rows
+#pragma unroll
+    for (int r0 = 0; r0 < IMG; r0 += 4) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if ((nonzero_rows >> r0) & 0xFull) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                if (k < hh) {
+                    const uint32_t nib = (uint32_t)(shfl_u64(w[k], r0 + sub) >> col4) & 0xFu;
+                    if (k == 0) {
+                        v.x = (nib & 1u) ? 1.f : 0.f;
+                        v.y = (nib & 2u) ? 1.f : 0.f;
+                        v.z = (nib & 4u) ? 1.f : 0.f;
+                        v.w = (nib & 8u) ? 1.f : 0.f;
+                    } else {
+                        v.x += (nib & 1u) ? d[k] : 0.f;
+                        v.y += (nib & 2u) ? d[k] : 0.f;
+                        v.z += (nib & 4u) ? d[k] : 0.f;
+                        v.w += (nib & 8u) ? d[k] : 0.f;
+                    }
+                }
+            }
+        }
+        *reinterpret_cast<float4*>(img + (size_t)(r0 + sub) * IMG + col4) = v;
+    }
+}
+
 // K2+K3: is_stable_rbe on independent assemblies; fixed_mask bit b = block b is_static.
 __global__ __launch_bounds__(WAVE) void k_stability(const bridges_shape* shapes, int n, int K, const double* pose_all,
                                                     const double* verts_all, const int32_t* shape_all,

@@ -73,6 +73,24 @@ def all_gather_records(rec, valid, n_valid=None):
     return out[keep][:, :W]
 
 
+def all_gather_rows(rec, valid):
+    """rec [E, W] float64, valid [E] bool -> (rows [world * E, W], valid [world * E] bool): the rows of every rank, rank-major and
+    UNCOMPACTED, with their validity -- what the n-step fold runs on, so that every rank folds the same rows into the same
+    windows.  The payload is all_gather_records': the rows with the validity in-band.  Without a process group: (rec, valid)."""
+    if not active():
+        return rec, valid
+    world = dist.get_world_size()
+    E, W = rec.shape
+    payload = torch.cat([rec, valid.to(rec.dtype).unsqueeze(1)], dim=1).contiguous()     # validity travels in-band
+    dev = rec.device
+    if dist.get_backend() == "gloo" and payload.is_cuda:        # rehearsal mode: gloo moves host memory
+        payload = payload.cpu()
+    out = torch.empty((world * E, W + 1), dtype=rec.dtype, device=payload.device)
+    dist.all_gather_into_tensor(out, payload)
+    out = out.to(dev)
+    return out[:, :W].contiguous(), out[:, W] > 0.5
+
+
 def all_reduce_sum_(t):
     """Sums ``t`` over the ranks in place (one all_reduce; stream-ordered on RCCL, through host memory under gloo).  A single rank
     without a forced group issues no collective."""

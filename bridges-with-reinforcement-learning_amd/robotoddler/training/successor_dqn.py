@@ -531,7 +531,32 @@ def build_parser():
                    help="Vectorised loop: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI, as "
                         "--random_bridge_length draws the span.")
     add_curriculum_arguments(p)
+    add_n_step_argument(p)
     return p
+
+
+def add_n_step_argument(p):
+    """--n_step: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--n_step", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="Vectorised loop: train on N-step returns, 1 <= N <= 8 and N <= --max_steps (default 1: the one-step target). "
+                        "Every env folds its last N transitions on the device; the replay ring then holds h-step records (h = N, "
+                        "shorter at the end of an episode) and the mean_lin_reward / lin_reward of the log is the mean h-step "
+                        "return G = sum_k gamma^k lin_reward_k of the rows pushed in the lock-step, not the mean one-step reward.")
+
+
+def check_n_step(args):
+    """--n_step N: refused in words (SystemExit) where the loop cannot run it, before anything touches the GPU."""
+    n = args.get('n_step')
+    if n is None:
+        return
+    from bridges_hip import abi
+    if not 1 <= n <= abi.NSTEP_MAX:
+        raise SystemExit(f"--n_step must be 1..{abi.NSTEP_MAX} (the window of an env holds at most {abi.NSTEP_MAX} transitions)")
+    if n > 1 and args['num_envs'] <= 1:
+        raise SystemExit("--n_step N > 1 needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
+                         "reference's one-step target")
+    if n > args['max_steps']:
+        raise SystemExit(f"--n_step {n} is above --max_steps {args['max_steps']}: no episode has that many transitions")
 
 
 def add_curriculum_arguments(p):
@@ -709,6 +734,7 @@ def main(argv=None):
     if args['device'] == 'cpu':
         raise SystemExit("this build has no CPU path: the simulator and the DQN ops are HIP kernels (use --device cuda)")
     check_random_targets(args)
+    check_n_step(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

@@ -9,6 +9,8 @@ Semantics follow rollout_episode / train_policy_net / update_target_net of the r
   start and the chosen rasters added afterwards;
 * the TD target is the elementwise  lin_reward + gamma * q'  (the single-env reference path trains on a [B,B]
   broadcast of it because its lin_reward is [B,1]; that quirk is reproduced only in the single-env loop);
+  with n_step = n > 1 (an extension: the reference has no multi-step target) it is  G + gamma^h * q',  G the h-step return of
+  the transition's window, h = n or what the end of the episode leaves (DESIGN.md section 7, "n-step returns");
 * "done" of a transition = terminated | truncated | no next action (successor_dqn.py:393, 409-411);
 * epsilon decays once per LOCK-STEP (the reference: once per episode, successor_dqn.py:702 -- with thousands of envs
   hundreds of episodes end per lock-step and a per-episode decay would reach the floor within a dozen lock-steps);
@@ -32,7 +34,7 @@ import time
 import numpy as np
 import torch
 
-from bridges_hip import dqn_ops, ops
+from bridges_hip import abi, dqn_ops, ops
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 from robotoddler.training import distributed as D
@@ -49,7 +51,8 @@ OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
 class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
-                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None):
+                 episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
+                 n_step=1):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -67,7 +70,19 @@ class VecDQN:
         (state, candidate, stable flag, task); the optimiser step is the autograd body on per-transition rows.  Neither the
         rollout env nor the replay scratch env needs f32 rasters in this mode.
         ``curriculum=Curriculum(...)`` (a rollout env on a task family only): the weights of the family's classes follow the
-        failure rate per class on the device (robotoddler.training.curriculum); evaluation envs are not touched."""
+        failure rate per class on the device (robotoddler.training.curriculum); evaluation envs are not touched.
+        ``n_step=n`` (1..8, at most the env's max_steps): train on n-step returns.  Every env keeps a window of its last n
+        transitions on the device (bridges_nstep_fold); a lock-step pushes, per env, the h-step record of the oldest start once
+        the window is full (h = n) and of every pending start when the episode ends (h = n .. 1).  A ring row is the record of
+        the window's LAST step with the h-step return in O_LIN, the start's stable flag and priority in O_STABLE_S / O_TD and h
+        in a new last column; _targets rebuilds the start state as a prefix of the row's block list and discounts the
+        bootstrap by gamma^h ("n-step returns").  n_step=1 is the one-step loop: no column, no launch of this."""
+        self.n_step = int(n_step)
+        if not 1 <= self.n_step <= abi.NSTEP_MAX:
+            raise ValueError(f"VecDQN(n_step={n_step}): the window holds 1..{abi.NSTEP_MAX} transitions per env (BRIDGES_NSTEP_MAX)")
+        if self.n_step > 1 and self.n_step > int(env.max_steps):
+            raise ValueError(f"VecDQN(n_step={n_step}): an episode of this env has at most max_steps = {env.max_steps} transitions, "
+                             "no window would ever fill")
         self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
         self.task_channels = bool(task_channels)
         if self.task_channels:
@@ -122,7 +137,9 @@ class VecDQN:
         self.n_task_targets = env.n_targets if self.per_env_tasks else 0
         self.n_task_obstacles = env.n_obstacles if self.per_env_obstacles else 0
         self.task_width = 3 * self.n_task_targets + 3 * self.n_task_obstacles
-        self.ring = R.ReplayRing(replay_capacity, self.device, width=R.RECORD_WIDTH + self.task_width)
+        # n-step returns: one more column, the horizon h of the row
+        self.ring = R.ReplayRing(replay_capacity, self.device, width=R.RECORD_WIDTH + self.task_width + (self.n_step > 1))
+        self._window = None                                  # the n-step windows of the envs of all ranks, made by the first fold
         # replay sampling must be identical on every rank (replicated rings) -> shared seed; exploration differs
         self.sample_gen = torch.Generator(device=self.device).manual_seed(1234567 + seed)
         self.explore_gen = torch.Generator(device=self.device).manual_seed(7654321 + seed * 1000 + rank)
@@ -138,7 +155,8 @@ class VecDQN:
         self._eager_reduce = None                            # dqn_ops.ReduceTables of the eager optimiser steps
         self.episodes_done = 0
         self.env_steps = 0
-        self._counts_host = torch.zeros(2, dtype=torch.int64).pin_memory()      # (env-steps, finished episodes) of a lock-step
+        # (env-steps, finished episodes) of a lock-step; n-step returns on one rank: and the emitted rows
+        self._counts_host = torch.zeros(3 if self.n_step > 1 else 2, dtype=torch.int64).pin_memory()
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
         # (a task family -- RandomBridges -- keeps them per class as well: one row per span / height n = 0..hi)
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
@@ -556,6 +574,11 @@ class VecDQN:
         n = rec.shape[0]
         renv = self._replay_env(n)
         E = renv.E
+        horizon = None
+        if self.n_step > 1:                                  # an h-step row: the record of the window's last step, then its tail, then h
+            if rec.shape[1] != self.ring.width:
+                raise ValueError(f"n-step returns: records of {self.ring.width} columns expected, got {rec.shape[1]}")
+            horizon, rec = rec[:, -1], rec[:, :-1]
         if self.per_env_tasks:
             if rec.shape[1] != R.RECORD_WIDTH + self.task_width:
                 raise ValueError(f"per-env tasks: records of {R.RECORD_WIDTH + self.task_width} columns expected, got {rec.shape[1]}")
@@ -573,10 +596,28 @@ class VecDQN:
         # load_states + prefix_state_bits is the torch formulation the tests compare it with.
         bits_s, lin, stable_s, done_rec, stable_n = renv.load_records(rec.contiguous())
         use_sf = 'mse_block_features' in self.loss_parts
-        action_bits = renv.state_bits & ~bits_s                                               # s' minus s = the new block
+        discount = sf_action = None
+        if horizon is None:
+            action_bits = renv.state_bits & ~bits_s                                           # s' minus s = the new block
+        else:
+            # the scratch env holds s_{t+h} and G came out as lin, the start's stable flag as stable_s; the start state s_t is the
+            # first O_NB - (h - 1) blocks of the row's block list, a_t the block after them, and the successor-feature target
+            # takes the discounted sum of the h blocks placed since (bridges_bits_discounted_sum) in place of a_t's raster
+            h = horizon.to(torch.int32)
+            nb_t = rec[:, R.O_NB].to(torch.int32) - (h - 1)
+            if n < E:                                        # envs beyond n repeat record 0, as load_records loads them
+                h, nb_t = torch.cat([h, h[:1].expand(E - n)]), torch.cat([nb_t, nb_t[:1].expand(E - n)])
+            bits_s = renv.prefix_state_bits(nb_t)
+            action_bits = renv.prefix_state_bits(nb_t + 1) & ~bits_s
+            first = torch.arange(E, dtype=torch.int64, device=self.device) * renv.K + nb_t
+            asum, discount = ops.bits_discounted_sum(renv._keep[0], first, h, self.gamma, want_sum=use_sf)
+            sf_action = renv.crop(asum).unsqueeze(1) if use_sf else None
         block_f = None if self.task_channels else renv.crop(ops.bits_to_f32(bits_s)).unsqueeze(1)
         # (task_channels: the action raster as f32 only where the successor-feature target adds it)
-        action_f = renv.crop(ops.bits_to_f32(action_bits)).unsqueeze(1) if (use_sf or not self.task_channels) else None
+        action_f = (renv.crop(ops.bits_to_f32(action_bits)).unsqueeze(1)
+                    if ((use_sf and horizon is None) or not self.task_channels) else None)
+        if horizon is None:
+            sf_action = action_f
         stable_n = stable_n.bool()
         idx, row_env, seg, _rep = self._rows(renv, stable_n)      # transitions with the same next state share its rows
         done = done_rec.bool() | (renv.n_valid[:E] == 0)
@@ -594,10 +635,11 @@ class VecDQN:
             nsf0 = lambda best: nsf[:, 0].index_select(0, best if inverse is None else inverse.index_select(0, best)).reshape(E, -1).contiguous()
         if idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
-                                                       action_raster=action_f.squeeze(1) if use_sf else None, lin=lin)
+                                                       action_raster=sf_action.squeeze(1) if use_sf else None, lin=lin,
+                                                       discount=discount)
         else:
             q_target = lin
-            sf_target = action_f.reshape(E, -1) if use_sf else None
+            sf_target = sf_action.reshape(E, -1) if use_sf else None
         binary = torch.zeros((E, 6), dtype=torch.float32, device=self.device)
         binary[:, 0] = stable_s
         if self.task_channels:
@@ -720,7 +762,7 @@ class VecDQN:
         blob = dict(epsilon=float(self.epsilon), episodes_done=int(self.episodes_done), env_steps=int(self.env_steps),
                     step_images=self.step_images.cpu(), sample_gen=self.sample_gen.get_state().cpu(),
                     explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()},
-                    task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)))
+                    task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)), n_step=int(getattr(self, "n_step", 1)))
         if getattr(self, "curriculum", None) is not None:    # one more key: (ema, seen), weights, sums and accumulator
             blob["curriculum"] = self.curriculum.state_dict()
         torch.save(blob, path)
@@ -739,6 +781,12 @@ class VecDQN:
         if got != want:
             raise ValueError(f"{path} was written by a run whose records end in {got[0]} targets and {got[1]} obstacles, this "
                              f"agent's end in {want[0]} targets and {want[1]} obstacles: the tails do not mean the same task")
+        # (a file written before the loop had n-step returns carries no entry: its rows are one-step records)
+        got_n = int(blob.get("n_step", 1))
+        want_n = int(getattr(self, "n_step", 1))
+        if got_n != want_n:
+            raise ValueError(f"{path} was written by a run with n_step = {got_n}, this agent folds n_step = {want_n}: the rows "
+                             "of the ring do not mean the same returns")
         self.epsilon, self.episodes_done, self.env_steps = blob["epsilon"], blob["episodes_done"], blob["env_steps"]
         self.step_images.copy_(blob["step_images"])
         self.sample_gen.set_state(blob["sample_gen"])
@@ -751,10 +799,27 @@ class VecDQN:
         return blob["counters"]
 
     # ------------------------------------------------------------------ driver
+    def reset_window(self):
+        """Empty the n-step window of every env (n_step > 1; a no-op otherwise).  Called wherever env.reset() abandons the
+        running episodes -- after a checkpoint is written and on resume -- so that no start of an abandoned episode is folded
+        into the next one; the pending starts (up to n - 1 transitions per env) are dropped, they never reach the ring."""
+        if self._window is not None:
+            self._window[0].zero_()
+
+    def _fold(self, rec, valid):
+        """One lock-step's one-step rows (of all ranks) through the n-step windows -> (out [rows * n, W + 1], out_valid)."""
+        if self._window is None:
+            rows, n = rec.shape[0], self.n_step
+            self._window = (torch.zeros(rows, dtype=torch.int32, device=self.device),
+                            *(torch.zeros((rows, n), dtype=torch.float64, device=self.device) for _ in range(4)))
+        return dqn_ops.nstep_fold(rec.contiguous(), valid, self.gamma, self.n_step, *self._window)
+
     def lockstep(self, n_train_steps, defer_losses=False):
         """act -> all-gather -> replay push -> n optimiser steps -> soft update.  defer_losses=True returns the losses as
         a DeferredLosses (see train_steps): nothing after the replay push waits for the GPU, so the optimiser steps run
-        under the host's queueing of the next lock-step."""
+        under the host's queueing of the next lock-step.
+        n_step > 1: act -> gather -> fold -> push; the statistics, the curriculum and td_errors see the one-step records (a start's
+        priority is its one-step TD error), the ring and the caller get the emitted h-step rows."""
         rec, valid = self.act()
         if self.episode_stats is not None:
             # before the all-gather: env identity still holds (a task family: under the class of before the step)
@@ -768,17 +833,38 @@ class VecDQN:
         # ONE wait per lock-step on this side: the two counts ride to pinned memory in front of the next act's candidate rows,
         # whose row count the host has to wait for anyway (bridges_valid_rows)
         done_rec = valid & (rec[:, R.O_DONE] > 0.5)
-        self._counts_host.copy_(torch.stack([valid.sum(), done_rec.sum()]), non_blocking=True)
+        counts = [valid.sum(), done_rec.sum()]
+        folded = None
+        if self.n_step > 1 and not D.active():
+            # one rank: the fold runs here, and the number of emitted rows rides with the two counts -- no wait of its own
+            folded = self._fold(self.with_task(rec), valid)
+            counts.append(folded[1].sum())
+        elif self.n_step > 1:
+            counts.append(torch.zeros_like(counts[0]))
+        self._counts_host.copy_(torch.stack(counts), non_blocking=True)
         arrived = torch.cuda.Event()
         arrived.record()
         self._rows(self.env, self._stable_flags(self.env))
         arrived.synchronize()                           # passed already unless the rows came out of the env's cache
         n_valid, n_done = int(self._counts_host[0]), int(self._counts_host[1])
         self.env_steps += n_valid
-        allrec = D.all_gather_records(self.with_task(rec), valid, n_valid=n_valid)
+        if self.n_step > 1:
+            if folded is None:
+                # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
+                # windows and pushes the same rows; the collective carries what it carries for n_step = 1
+                out, out_valid = self._fold(*D.all_gather_rows(self.with_task(rec), valid))
+                allrec = out[out_valid]
+            else:
+                out, out_valid = folded
+                allrec = out.index_select(0, torch.nonzero_static(out_valid, size=int(self._counts_host[2])).squeeze(1))
+        else:
+            allrec = D.all_gather_records(self.with_task(rec), valid, n_valid=n_valid)
         self.ring.push(allrec)
         if not D.active():
             self.episodes_done += n_done
+        elif self.n_step > 1:
+            # a finished episode emits up to n done rows: the one of its last transition has h = 1
+            self.episodes_done += int(((allrec[:, R.O_DONE] > 0.5) & (allrec[:, -1] == 1.0)).sum().item())
         else:
             self.episodes_done += int((allrec[:, R.O_DONE] > 0.5).sum().item())
         losses = self.train_steps(n_train_steps, defer=defer_losses)
@@ -893,7 +979,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
                    per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
-                   task_channels=task_channels, curriculum=curriculum_from_args(args))
+                   task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -919,6 +1005,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         next_ckpt = next_multiple(agent.episodes_done, args['checkpoint_every'])
         next_eval = next_multiple(agent.episodes_done, args['evaluate_every'])
         env.reset()                                      # a checkpoint is taken with all environments freshly reset
+        agent.reset_window()
     steps_at_start, t0 = agent.env_steps, time.time()    # throughput counts what THIS run (resumed or not) has stepped
 
     def finish(entry):
@@ -959,8 +1046,10 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                 agent.save_extra(os.path.join(args['save_checkpoint'], str(agent.episodes_done), 'agent.pt'), lockstep=it)
             next_ckpt = next_multiple(agent.episodes_done, args['checkpoint_every'])
             # the single-env reference checkpoints between episodes; the lock-step analogue: every rank starts all its
-            # environments afresh, so that a resumed run (fresh environments) continues exactly like this one
+            # environments afresh, so that a resumed run (fresh environments) continues exactly like this one (n-step returns:
+            # the pending starts of the abandoned episodes are dropped with them)
             env.reset()
+            agent.reset_window()
         if it % 100 == 0:
             D.broadcast_module(policy_net)
             D.broadcast_module(target_net)

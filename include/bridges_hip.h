@@ -591,6 +591,42 @@ int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg
                       int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
                       const uint8_t* done, float gamma, int32_t sf_dim, float* q_target, float* sf_target,
                       int32_t* argmax_row, void* stream);
+/* bridges_td_target with a discount PER TRANSITION, discount [n_trans] f32, in place of the scalar gamma (n-step returns: the
+ * discount of transition i is gamma^h of its horizon):
+ *   q_target[i] = lin_reward[i] + discount[i] * (done ? 0 : next_q[j*]),
+ *   sf_target[i,:] = action_raster[i,:] + discount[i] * (done ? 0 : next_sf[j*,:]).
+ * The first-maximum rule, the empty-segment and done rules, both segment forms, the strided next_sf and argmax_row are those of
+ * bridges_td_target; a discount filled with gamma gives its outputs bit for bit. */
+int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
+                           int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
+                           const uint8_t* done, const float* discount, int32_t sf_dim, float* q_target, float* sf_target,
+                           int32_t* argmax_row, void* stream);
+
+/* --- n-step returns of the vectorised loop ------------------------------------------------------------------------
+ * The fold of one lock-step's one-step records rec [E, W] f64 (W >= BRIDGES_REC_WIDTH: the record plus its task tail) / valid [E]
+ * into h-step records.  Per-env window state that persists between calls: count [E] i32 (pending starts, 0 .. n - 1) and
+ * acc, disc, stable_s, td [E, n] f64.  Per env with a valid transition, in this order:
+ *   1. a pending start is appended: acc = 0, disc = 1, the record's STABLE_S and TD;
+ *   2. every pending start j: acc_j += disc_j * rec[LIN], disc_j *= gamma (float64);
+ *   3. rec[DONE] set: every pending start is emitted, oldest first, with horizon h_j = count - j, and the window is emptied;
+ *      else count == n: the oldest start is emitted with h = n and the rest shifts down.
+ * An env with valid = 0 keeps its window (it is empty then: the transition before a reset-only lock-step was done).
+ * out [E * n, W + 1] f64, out_valid [E * n] u8: env e's emissions are rows e * n ..., oldest first, out_valid = 1; the other rows
+ * of its block have out_valid = 0 and unspecified content.  An emitted row is rec[e] with LIN = acc_j (the h-step return),
+ * STABLE_S and TD = the start's, and h_j in column W; block list, action, DONE, STABLE_N, REWARD and the tail stay the last
+ * step's, so the start state is the first rec[NB] - (h - 1) blocks of the row's block list and the start action the block after.
+ * n outside 1..BRIDGES_NSTEP_MAX, W < BRIDGES_REC_WIDTH, a NULL or misaligned pointer return -1 and launch nothing. */
+#define BRIDGES_NSTEP_MAX 8
+int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
+                       double* acc, double* disc, double* stable_s, double* td, double* out, uint8_t* out_valid, void* stream);
+/* The discounted sum of consecutive block rasters (the action part of an h-step successor-feature target): bits [n_rows, 64] u64,
+ * per transition i a first row first[i] (i64) and a count h[i] (i32, 1..BRIDGES_NSTEP_MAX) ->
+ *   sum [n, 64, 64] f32:  sum[i] = sum_{k < h[i]} d_k * image(bits[first[i] + k]),    disc [n] f32:  disc[i] = d_{h[i]},
+ * d_0 = 1, d_{k+1} = d_k * gamma in float32 (both outputs from the same sequence), the terms added in ascending k; the
+ * bit-to-pixel order is bridges_bits_to_f32's and h = 1 gives its image bit for bit.  sum may be NULL (disc only).
+ * h is clamped to 0..BRIDGES_NSTEP_MAX and first[i] + k to the n_rows of the table: nothing outside bits is read. */
+int bridges_bits_discounted_sum(int32_t n, const uint64_t* bits, int64_t n_rows, const int64_t* first, const int32_t* h, float gamma,
+                                float* sum, float* disc, void* stream);
 
 /* Inference epilogues of the conv Q-networks (robotoddler/models/cv.py:5-17, 41-73, 108-170: Conv2d -> ReLU
  * [-> MaxPool2d(2)]), one pass instead of torch's three; bit-identical to relu(conv + bias) / maxpool(relu(conv + bias)).

@@ -5,7 +5,7 @@ if "--miopen_search" not in sys.argv:
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import torch
-from robotoddler.training.successor_dqn import add_curriculum_arguments, build_parser, check_curriculum, make_nets
+from robotoddler.training.successor_dqn import add_curriculum_arguments, add_n_step_argument, build_parser, check_curriculum, make_nets
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
@@ -50,6 +50,7 @@ ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI",
 ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
                 help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
 add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
+add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_step=N))
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -104,7 +105,7 @@ opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
                episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
-               curriculum=curriculum_from_args(vars(a)))
+               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -146,7 +147,11 @@ for _ in range(n_phase):
     torch.cuda.synchronize(); t1 = time.perf_counter()
     rec, valid = agent.act()
     agent.env_steps += int(valid.sum().item())
-    agent.ring.push(agent.with_task(rec)[valid])
+    if agent.n_step > 1:                                         # the h-step rows the fold emits, as lockstep pushes them
+        out, out_valid = agent._fold(agent.with_task(rec), valid)
+        agent.ring.push(out[out_valid])
+    else:
+        agent.ring.push(agent.with_task(rec)[valid])
     torch.cuda.synchronize(); t2 = time.perf_counter()
     agent.train_steps(a.train_steps)
     agent.update_target()

@@ -301,6 +301,7 @@ SIGNATURES = {
     "bridges_maxpool2_relu_backward": [vp, vp, vp, i64, i32, i32, vp],
     "bridges_td_target": [i32, vp, vp, vp, vp, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp],
     "bridges_td_target_rows": [i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_td_target_select": [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp],
     "bridges_nstep_fold": [i32, i32, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_discounted_sum": [i32, vp, i64, vp, vp, f32, vp, vp, vp],
 }

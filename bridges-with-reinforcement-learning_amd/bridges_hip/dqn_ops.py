@@ -15,7 +15,7 @@ def _ptr(t):
 _stream = abi.current_stream
 
 
-def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_raster=None, discount=None):
+def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_raster=None, discount=None, select_q=None):
     """Target construction of train_policy_net (successor_dqn.py:197-213, 222, 230) in one kernel.
 
     seg_offset int32 [B+1]: rows [seg_offset[i], seg_offset[i+1]) of next_q / next_sf belong to transition i; or a pair
@@ -24,6 +24,10 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
     action_raster f32 [B, D]; lin_reward f32 [B]; done uint8/bool [B].
     ``discount`` f32 [B]: a discount per transition in place of ``gamma`` (n-step returns: gamma^h of the transition's horizon;
     bridges_td_target_rows).  None is bridges_td_target with the scalar.
+    ``select_q`` f32 [R], contiguous, a value for every row of next_q (double Q-learning: the policy net's q): the row of a
+    transition is the first maximum of select_q over its segment and its value is next_q's at that row
+    (bridges_td_target_select, with or without ``discount``; next_sf rows need not be 16-byte aligned there).  None is the plain
+    target: the two entry points above, called as ever.
     Returns (q_target [B], sf_target [B, D] or None, argmax_row int32 [B])."""
     L = abi.require_gpu()
     dev = next_q.device
@@ -51,6 +55,14 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
     if discount is not None:
         discount = discount.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
         assert discount.numel() == B
+    if select_q is not None:
+        assert select_q.dtype == torch.float32 and select_q.is_contiguous() and select_q.device == dev
+        assert select_q.numel() == next_q.numel()
+        abi.check(L.bridges_td_target_select(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(select_q), _ptr(next_q), _ptr(next_sf), stride,
+                                             _ptr(action_raster), _ptr(lin_reward), _ptr(done_u8), _ptr(discount), float(gamma), sf_dim,
+                                             _ptr(q_target), _ptr(sf_target), _ptr(argmax_row), _stream()), "bridges_td_target_select")
+        return q_target, sf_target, argmax_row
+    if discount is not None:
         abi.check(L.bridges_td_target_rows(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(next_q), _ptr(next_sf), stride, _ptr(action_raster),
                                            _ptr(lin_reward), _ptr(done_u8), _ptr(discount), sf_dim, _ptr(q_target), _ptr(sf_target),
                                            _ptr(argmax_row), _stream()), "bridges_td_target_rows")
@@ -61,25 +73,35 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
     return q_target, sf_target, argmax_row
 
 
-def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None):
+def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None, select_q=None):
     """The TD targets of transitions whose next-state rows are the segments ``seg`` of ``next_q`` (td_target's seg_offset).
     -> (q [B], sf [B, D] or None).  With ``lin``: q = lin + gamma q' of each segment's arg-max row, sf = lin + gamma psi' of
     that row + the action raster.  lin=None is the single-env reference form: q is the done-masked q' of the arg-max row (lin 0,
     gamma 1 -- the caller adds its [B, 1] lin_reward by broadcasting) and sf takes lin 0.  ``next_sf``: psi' of every row, or
     a callable that returns psi' of the arg-max rows from their indices (callers that compute it for those rows only).
-    ``discount`` f32 [B] (with ``lin``): a discount per transition in place of gamma, in both targets (td_target's)."""
+    ``discount`` f32 [B] (with ``lin``): a discount per transition in place of gamma, in both targets (td_target's).
+    ``select_q`` f32 [R] (with ``lin``): double Q-learning -- the arg-max row of a segment is select_q's first maximum, the values
+    are next_q's and next_sf's at that row (td_target's).  It goes to the call that finds the rows; the second call of the
+    callable-next_sf form has one row per segment and nothing to select (with psi' of every row it selects again)."""
     nq = next_q.contiguous().float()
     zeros = torch.zeros(done.numel(), dtype=torch.float32, device=nq.device) if lin is None else lin
     if discount is not None and lin is None:
         raise ValueError("next_targets(discount=...) is the vectorised form: it needs lin")
-    q, _, arg = td_target(seg, nq, zeros, done, 1.0 if lin is None else gamma, discount=discount)
+    if select_q is not None and lin is None:
+        raise ValueError("next_targets(select_q=...) is the vectorised form: it needs lin")
+    if select_q is not None:
+        select_q = select_q.contiguous().float()
+    q, _, arg = td_target(seg, nq, zeros, done, 1.0 if lin is None else gamma, discount=discount, select_q=select_q)
     if next_sf is None:
         return q, None
     if callable(next_sf):
         best = arg.long().clamp_(0, nq.numel() - 1)                       # empty segments are 'done': row unused
         next_sf = next_sf(best)
         seg, nq = torch.arange(done.numel() + 1, dtype=torch.int32, device=nq.device), nq[best].contiguous()
-    _, sf, _ = td_target(seg, nq, zeros, done, gamma, next_sf=next_sf, action_raster=action_raster, discount=discount)
+        select_q = None                                                   # one row per segment: nothing left to select
+    # (select_q with psi' of every row: the same selection again)
+    _, sf, _ = td_target(seg, nq, zeros, done, gamma, next_sf=next_sf, action_raster=action_raster, discount=discount,
+                         select_q=select_q)
     return q, sf
 
 

@@ -652,6 +652,28 @@ int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t
                   next_sf_row_stride, action_raster, lin_reward, done, discount, sf_dim, q_target, sf_target, argmax_row);
 }
 
+int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                             const float* next_sf, int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
+                             const uint8_t* done, const float* discount, float gamma, int32_t sf_dim, float* q_target,
+                             float* sf_target, int32_t* argmax_row, void* stream) {
+    if (n_trans < 0 || sf_dim < 0) return fail_arg("bridges_td_target_select: negative count");
+    if (n_trans == 0) return BRIDGES_OK;
+    if (!seg_lo || !seg_hi || !select_q || !next_q || !lin_reward || !done || !q_target || !argmax_row)
+        return fail_arg("bridges_td_target_select: null pointer");
+    if (sf_dim > 0 && (!next_sf || !action_raster || !sf_target || next_sf_row_stride < 0))
+        return fail_arg("bridges_td_target_select: sf_dim > 0 needs next_sf, action_raster and sf_target");
+    if (!aligned(4, seg_lo, seg_hi, select_q, next_q, next_sf, action_raster, lin_reward, discount, q_target, sf_target, argmax_row))
+        return fail_arg("bridges_td_target_select: misaligned pointer");
+    // (sf rows that are not 16-byte aligned, or an sf_dim that is no multiple of 4, take the kernel's element-wise epilogue)
+    if (discount)
+        return launch("k_td_target_select<rows>", k_td_target_select<true>, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi,
+                      select_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done, discount, gamma, sf_dim, q_target,
+                      sf_target, argmax_row);
+    return launch("k_td_target_select", k_td_target_select<false>, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi,
+                  select_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done, (const float*)nullptr, gamma, sf_dim,
+                  q_target, sf_target, argmax_row);
+}
+
 int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
                        double* acc, double* disc, double* stable_s, double* td, double* out, uint8_t* out_valid, void* stream) {
     if (E < 0 || n < 1 || n > BRIDGES_NSTEP_MAX) return fail_arg("bridges_nstep_fold: n must be 1..BRIDGES_NSTEP_MAX");

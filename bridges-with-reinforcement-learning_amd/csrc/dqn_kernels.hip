@@ -220,6 +220,83 @@ __global__ __launch_bounds__(256) void k_td_target_rows(int n_trans, const int32
     }
 }
 
+// (value, row) pairs of the segmented arg-max: b replaces a when b holds a row and a holds none, or b's value is greater, or the
+// values are equal and b's row is lower.  "Greater value, then lower row" is a TOTAL order on pairs with distinct rows (a pair
+// without a row is below all of them), so the maximum of a set of pairs does not depend on the order in which they are combined.
+__device__ __forceinline__ void td_take_better(float& av, int& ak, float bv, int bk) {
+    if (bk != 0x7fffffff && (ak == 0x7fffffff || bv > av || (bv == av && bk < ak))) { av = bv; ak = bk; }
+}
+
+// Double Q-learning target: k_td_target / k_td_target_rows with the row SELECTED by one value vector and VALUED by another,
+//   row = first maximum of select_q over [seg_lo[i], seg_hi[i])  (ties to the lowest row; all -inf: the first row),
+//   q_target[i] = lin_reward[i] + d_i * (done ? 0 : next_q[row]),  sf_target[i,:] = action_raster[i,:] + d_i * next_sf[row,:],
+// d_i = discount[i] (PER_ROW) or the scalar gamma.  The empty-segment and done rules, both segment forms, the strided next_sf and
+// argmax_row are k_td_target's and the epilogue is its arithmetic statement for statement, so select_q == next_q gives the
+// outputs of k_td_target (scalar) and k_td_target_rows (PER_ROW) bit for bit.
+// Reduction for wave64: every thread strides the segment, a wave reduces its 64 pairs by __shfl_down (offsets 32 .. 1; a lane
+// whose partner lies beyond the wave gets its own pair back, which changes nothing), the four wave results pass through LDS
+// behind ONE barrier and every thread combines the four.  Because the order of pairs is total (td_take_better) the result is the
+// one of k_td_target's LDS tree, whatever the shape of the reduction.
+// The successor-feature row goes 16 B per lane when sf_dim and the row stride are multiples of 4 floats and the three bases are
+// 16-byte aligned, element by element otherwise (sf_dim = 6): the same float operations per element either way.
+template <bool PER_ROW>
+__global__ __launch_bounds__(256) void k_td_target_select(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
+                                                          const float* __restrict__ select_q, const float* __restrict__ next_q,
+                                                          const float* __restrict__ next_sf, int64_t sf_row_stride,
+                                                          const float* __restrict__ action_raster, const float* __restrict__ lin_reward,
+                                                          const uint8_t* __restrict__ done, const float* __restrict__ discount,
+                                                          float gamma_scalar, int sf_dim, float* __restrict__ q_target,
+                                                          float* __restrict__ sf_target, int32_t* __restrict__ argmax_row) {
+    __shared__ float s_val[4];
+    __shared__ int s_idx[4];
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (i >= n_trans) return;                            // (uniform per workgroup: the grid is n_trans)
+    const int lo = seg_lo[i], hi = seg_hi[i];
+    float gamma = gamma_scalar;
+    if constexpr (PER_ROW) gamma = discount[i];
+    float best = -INFINITY;
+    int bidx = 0x7fffffff;
+    for (int j = lo + t; j < hi; j += 256) {
+        float v = select_q[j];
+        if (v > best || (v == best && j < bidx) || bidx == 0x7fffffff) { best = v; bidx = j; }   // NaN-free inputs
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const float v = __shfl_down(best, o, WAVE);
+        const int k = __shfl_down(bidx, o, WAVE);
+        td_take_better(best, bidx, v, k);
+    }
+    if ((t & (WAVE - 1)) == 0) { s_val[t / WAVE] = best; s_idx[t / WAVE] = bidx; }
+    __syncthreads();
+    best = s_val[0]; bidx = s_idx[0];
+#pragma unroll
+    for (int w = 1; w < 256 / WAVE; ++w) td_take_better(best, bidx, s_val[w], s_idx[w]);
+    const int row = bidx;
+    const bool dn = done[i] != 0;
+    const bool no_next = dn || row == 0x7fffffff;       // an empty segment has no next row: nothing of next_q / next_sf is read for it
+    if (t == 0) {
+        float nq = dn ? 0.f : (row == 0x7fffffff ? -INFINITY : next_q[row]);
+        q_target[i] = lin_reward[i] + gamma * nq;
+        argmax_row[i] = row;
+    }
+    if (sf_dim > 0) {
+        const float* src = next_sf + (int64_t)(no_next ? 0 : row) * sf_row_stride;
+        const float* ar = action_raster + (int64_t)i * sf_dim;
+        float* dst = sf_target + (int64_t)i * sf_dim;
+        const bool vec = (((int64_t)sf_dim | sf_row_stride) & 3) == 0 &&
+                         ((((uintptr_t)next_sf) | ((uintptr_t)action_raster) | ((uintptr_t)sf_target)) & 15) == 0;
+        const int n4 = vec ? sf_dim >> 2 : 0;
+        for (int k = t; k < n4; k += 256) {
+            float4 a = reinterpret_cast<const float4*>(ar)[k];
+            float4 s = no_next ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(src)[k];
+            float4 o;
+            o.x = a.x + gamma * s.x; o.y = a.y + gamma * s.y; o.z = a.z + gamma * s.z; o.w = a.w + gamma * s.w;
+            reinterpret_cast<float4*>(dst)[k] = o;
+        }
+        for (int k = (n4 << 2) + t; k < sf_dim; k += 256) dst[k] = ar[k] + gamma * (no_next ? 0.f : src[k]);
+    }
+}
+
 // The n-step fold of one lock-step's one-step records (robotoddler/training/vec_dqn.py, DESIGN.md "n-step returns"): every env
 // keeps a window of up to n pending starts -- the return accumulated so far, the discount of the next reward, and the start's
 // stable(s) flag and priority -- and per valid transition

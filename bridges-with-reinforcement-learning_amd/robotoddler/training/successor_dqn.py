@@ -532,6 +532,7 @@ def build_parser():
                         "--random_bridge_length draws the span.")
     add_curriculum_arguments(p)
     add_n_step_argument(p)
+    add_double_q_argument(p)
     return p
 
 
@@ -557,6 +558,22 @@ def check_n_step(args):
                          "reference's one-step target")
     if n > args['max_steps']:
         raise SystemExit(f"--n_step {n} is above --max_steps {args['max_steps']}: no episode has that many transitions")
+
+
+def add_double_q_argument(p):
+    """--double_q: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--double_q", action="store_true", default=argparse.SUPPRESS,
+                   help="Vectorised loop: double Q-learning targets -- the policy net chooses the next action, the target net "
+                        "values it: q = G + gamma^h q_target(s', argmax_a' q_policy(s', a')), and the successor-feature target "
+                        "takes the target net's features of that action. One more forward over the next-state rows per "
+                        "lock-step. Composes with --n_step and --prioritized_replay.")
+
+
+def check_double_q(args):
+    """--double_q: refused in words (SystemExit) where the loop cannot run it, before anything touches the GPU."""
+    if args.get('double_q') and args['num_envs'] <= 1:
+        raise SystemExit("--double_q needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
+                         "reference's target, where the target net both chooses and values the next action")
 
 
 def add_curriculum_arguments(p):
@@ -735,6 +752,7 @@ def main(argv=None):
         raise SystemExit("this build has no CPU path: the simulator and the DQN ops are HIP kernels (use --device cuda)")
     check_random_targets(args)
     check_n_step(args)
+    check_double_q(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

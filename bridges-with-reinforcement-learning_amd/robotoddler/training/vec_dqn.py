@@ -52,7 +52,7 @@ class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
-                 n_step=1):
+                 n_step=1, double_q=False):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -76,7 +76,17 @@ class VecDQN:
         the window is full (h = n) and of every pending start when the episode ends (h = n .. 1).  A ring row is the record of
         the window's LAST step with the h-step return in O_LIN, the start's stable flag and priority in O_STABLE_S / O_TD and h
         in a new last column; _targets rebuilds the start state as a prefix of the row's block list and discounts the
-        bootstrap by gamma^h ("n-step returns").  n_step=1 is the one-step loop: no column, no launch of this."""
+        bootstrap by gamma^h ("n-step returns").  n_step=1 is the one-step loop: no column, no launch of this.
+        ``double_q=True``: double Q-learning targets (an extension: the reference keeps the form as a commented alternative).
+        _targets runs the POLICY net over the candidate rows of the sampled next states as well, and the row of a transition is
+        the first maximum of the policy net's q while its value and successor features stay the target net's
+        (bridges_td_target_select): q = G + gamma^h q_target_net(s', argmax_a' q_policy_net(s', a')).  The selection uses the
+        policy net as it stands when _targets runs, once per lock-step for all n_steps batches -- the approximation the loop
+        already makes by sharing one target pass between them.  It composes with n_step, prioritized, stable_actions_only, the
+        curriculum, per-env tasks / obstacles, task_channels and several ranks (the targets are computed after the gather);
+        td_errors stays the reference's formula.  The ring stores transitions, not targets, so a checkpoint can be resumed with
+        the option switched ("Double Q-learning").  False is the loop as it was: no launch of this."""
+        self.double_q = bool(double_q)
         self.n_step = int(n_step)
         if not 1 <= self.n_step <= abi.NSTEP_MAX:
             raise ValueError(f"VecDQN(n_step={n_step}): the window holds 1..{abi.NSTEP_MAX} transitions per env (BRIDGES_NSTEP_MAX)")
@@ -193,6 +203,8 @@ class VecDQN:
     DEDUP_STATES = True    # envs in the same state share one set of candidate rows (tests compare with False)
     DEDUP_ROWS = True      # conv nets: feed every distinct (state, candidate, stable flag) input once (tests compare with False)
     TRACK_ROWS = False     # tools: count the valid rows of every Q pass (rows_seen) beside the rows actually fed (rows_fed)
+    #                        (double_q=True: rows_fed counts BOTH passes over the next-state rows, the target net's and the policy net's)
+    _COMPUTE = object()    # _forward_rows(groups=...): "find the distinct rows yourself"
 
     def _rows(self, env, stable):
         """The candidate rows a Q pass over ``env`` is fed: (idx, row_env, (seg_lo, seg_hi), rep).  Thousands of envs of one task
@@ -280,12 +292,15 @@ class VecDQN:
             m = self._task_mult = (torch.randint(-2 ** 62, 2 ** 62, (w,), generator=g, dtype=torch.int64) | 1).to(self.device)
         return m
 
-    def _forward_rows(self, net, env, idx, row_env, stable_flag):
+    def _forward_rows(self, net, env, idx, row_env, stable_flag, groups=_COMPUTE):
         """net(...) over the candidate rows in chunks of ROW_CHUNK rows; the last chunk is padded with copies of row 0
         (sliced off again), so the convolution / GEMM shapes never change from lock-step to lock-step.  Rows with identical
         inputs are fed once (_distinct_rows).  -> (q [n], successor block features of the DISTINCT rows or None, successor
-        binary features of the distinct rows or None, inverse [n] = the distinct row of every row (None: every row is fed))."""
-        groups = self._distinct_rows(env, idx, row_env, stable_flag)
+        binary features of the distinct rows or None, inverse [n] = the distinct row of every row (None: every row is fed)).
+        ``groups``: what _distinct_rows returned for these very rows, for a caller that feeds them to two nets (the hashing and
+        torch.unique then run once)."""
+        if groups is VecDQN._COMPUTE:
+            groups = self._distinct_rows(env, idx, row_env, stable_flag)
         inverse = None
         if groups is not None:
             rep, inverse = groups
@@ -359,14 +374,15 @@ class VecDQN:
         return self._net_q(self.policy_net, env, idx, row_env, stable)
 
     @torch.no_grad()
-    def _net_q(self, net, env, idx, row_env, stable, return_h=False):
+    def _net_q(self, net, env, idx, row_env, stable, return_h=False, groups=_COMPUTE):
         """q of ``net`` for the candidate rows; with return_h (factored nets only) also the first layer's pre-activation
-        of every row, from which the successor features of selected rows follow without a second first-layer pass."""
+        of every row, from which the successor features of selected rows follow without a second first-layer pass.
+        ``groups`` (nets fed through _forward_rows only): the distinct rows, found by the caller."""
         net.eval()
         if not self._factored(net):
             if env.cand_raster is None and not self.task_channels:
                 raise ValueError("this Q-network acts on f32 rasters: create the rollout env with f32_rasters=True")
-            return self._forward_rows(net, env, idx, row_env, stable)[0]
+            return self._forward_rows(net, env, idx, row_env, stable, groups=groups)[0]
         # the first layer consumes the BIT-PACKED rasters (bridges_bits_linear): a raster times a weight slice is the
         # sum of the ~35 weight rows of its set pixels, so neither f32 images nor a [n, 4096] GEMM
         px = 64 * 64
@@ -562,6 +578,8 @@ class VecDQN:
         target net is constant during one train_policy_net call (it is only updated afterwards, :704-708), so the
         targets of all its n_steps batches can be computed in one pass: one state rebuild, one candidate refresh,
         one target-net forward and one k_td_target launch for n_steps * batch_size transitions.
+        double_q: a second forward, the policy net's as it stands now, over the same rows behind the first, and the target launch
+        selects every transition's row by its q (k_td_target_select); the conv nets' distinct rows are found once for both.
         Per-env tasks: the records' tails (their targets) go to the scratch env first, which rebuilds every transition's reward
         map from them (bridges_env_load_targets; envs beyond n repeat record 0's task, as their states do); a sixth value is
         returned then, the [n, px] maps of the transitions (a view of the scratch env's reward_maps: valid until the next call).
@@ -621,14 +639,20 @@ class VecDQN:
         stable_n = stable_n.bool()
         idx, row_env, seg, _rep = self._rows(renv, stable_n)      # transitions with the same next state share its rows
         done = done_rec.bool() | (renv.n_valid[:E] == 0)
+        select_q, double_q = None, self.double_q
         if idx.numel() and self._factored(self.target_net):
             # q of every next candidate through the factored forward on the bit-packed rasters; the 8204-wide output
             # (successor features) is only needed for the arg-max row of each transition: its channel 0 from the first-layer
             # pre-activations already at hand
             nq, h_pre = self._net_q(self.target_net, renv, idx, row_env, stable_n, return_h=True)
             nsf0 = lambda best: self.target_net.sf0_from_first_layer(h_pre.index_select(0, best)).contiguous()
+            if double_q:                                # (h_pre stays the target net's: the selected row's psi' is its)
+                select_q = self._net_q(self.policy_net, renv, idx, row_env, stable_n)
         elif idx.numel():
-            nq, nsf, _, inverse = self._forward_rows(self.target_net, renv, idx, row_env, stable_n)
+            groups = self._distinct_rows(renv, idx, row_env, stable_n)
+            nq, nsf, _, inverse = self._forward_rows(self.target_net, renv, idx, row_env, stable_n, groups=groups)
+            if double_q:
+                select_q = self._net_q(self.policy_net, renv, idx, row_env, stable_n, groups=groups)
             if use_sf and nsf is None:
                 raise ValueError("No successor block features available from the chosen policy net.")
             # (nsf holds the DISTINCT rows' outputs)
@@ -636,7 +660,7 @@ class VecDQN:
         if idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
                                                        action_raster=sf_action.squeeze(1) if use_sf else None, lin=lin,
-                                                       discount=discount)
+                                                       discount=discount, select_q=select_q)
         else:
             q_target = lin
             sf_target = sf_action.reshape(E, -1) if use_sf else None
@@ -979,7 +1003,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
                    per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
-                   task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1))
+                   task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1),
+                   double_q=bool(args.get('double_q', False)))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)

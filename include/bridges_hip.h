@@ -601,6 +601,25 @@ int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t
                            int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
                            const uint8_t* done, const float* discount, int32_t sf_dim, float* q_target, float* sf_target,
                            int32_t* argmax_row, void* stream);
+/* Double Q-learning: the target with the next row SELECTED by one value vector and VALUED by another.  select_q [R] f32 holds a
+ * value for the same rows as next_q (the policy net's q where next_q is the target net's):
+ *   j* = the first maximum of select_q over [seg_lo[i], seg_hi[i]) (ties go to the lowest row; NaN-free inputs; a segment that is
+ *        all -inf yields its first row),
+ *   q_target[i] = lin_reward[i] + d_i * (done ? 0 : next_q[j*]),
+ *   sf_target[i,:] = action_raster[i,:] + d_i * (done ? 0 : next_sf[j*,:]),   argmax_row[i] = j*,
+ * d_i = discount[i] when discount is not NULL (the per-transition form of bridges_td_target_rows), else the scalar gamma.
+ * next_sf is strided (next_sf_row_stride floats between rows); sf_dim may be 0, and need not be a multiple of 4 -- rows that are
+ * not 16-byte aligned are handled element by element.  An empty segment is what bridges_td_target states: argmax_row[i] =
+ * 0x7fffffff, q_target[i] = lin_reward[i] + d_i * (done ? 0 : -inf), sf_target[i,:] = action_raster[i,:], and nothing of next_q or
+ * next_sf is read for it.  With select_q == next_q (the same pointer or equal values) every output equals bridges_td_target's
+ * (discount NULL) and bridges_td_target_rows' (discount given) bit for bit.
+ * Returns -1 and launches nothing for: n_trans < 0 or sf_dim < 0; with n_trans > 0 a NULL seg_lo, seg_hi, select_q, next_q,
+ * lin_reward, done, q_target or argmax_row; sf_dim > 0 with a NULL next_sf, action_raster or sf_target or a negative row stride;
+ * a float / int32 pointer that is not 4-byte aligned.  n_trans == 0 returns 0 and launches nothing. */
+int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                             const float* next_sf, int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
+                             const uint8_t* done, const float* discount, float gamma, int32_t sf_dim, float* q_target,
+                             float* sf_target, int32_t* argmax_row, void* stream);
 
 /* --- n-step returns of the vectorised loop ------------------------------------------------------------------------
  * The fold of one lock-step's one-step records rec [E, W] f64 (W >= BRIDGES_REC_WIDTH: the record plus its task tail) / valid [E]

@@ -4,13 +4,17 @@ number of lock-steps and prints per block of lock-steps the statistics of the tr
 log_episode's discounted reward / lin_reward, length, final stability, and success_rate = the fraction that reached the target,
 all under the running epsilon-greedy exploration) and the mean loss; with --eval_envs N also the greedy evaluation of the policy
 at the end of the block (VecDQN.evaluate: one episode in each of N envs, --eval_epsilon 0 = the reference's greedy policy).
+With --eval_envs the line also holds eval_q_first, the mean over the evaluation envs of the policy net's q of the row chosen in
+the FIRST step of the episode: the net's own forecast of eval_lin_reward, the discounted lin_reward the same episodes then
+realise -- their difference is the over-estimation that --double_q is meant to reduce.
     python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values] [--eval_envs 64]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import numpy as np
 import torch
-from robotoddler.training.successor_dqn import add_curriculum_arguments, add_n_step_argument, build_parser, check_curriculum, make_nets
+from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument, build_parser,
+                                                check_curriculum, make_nets)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
@@ -43,6 +47,7 @@ ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
                 help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
 add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
 add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_step=N))
+add_double_q_argument(ap)                # --double_q: double Q-learning targets (VecDQN(double_q=True))
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -76,13 +81,32 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), 
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True), env, 200000, 32, 0.95, 0.01, a.loss,
                eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
-               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1))
+               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False))
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
                               f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels,
                               stable_actions_only=a.stable_actions_only)
 r4 = lambda v: None if v is None else round(v, 4)
+
+
+def evaluate_with_first_q(agent, eval_env, epsilon):
+    """agent.evaluate plus the mean q of the rows chosen in the episodes' first step (read after the evaluation's own wait)."""
+    act_on, first = agent._act_on, []
+
+    def recording(*args, **kw):
+        out = act_on(*args, **kw)
+        if not first:
+            first.append(out[2].mean())
+        return out
+    agent._act_on = recording
+    try:
+        ev = agent.evaluate(eval_env, epsilon)
+    finally:
+        del agent._act_on
+    return ev, float(first[0])
+
+
 t0 = time.time()
 deferred = []
 for it in range(1, a.locksteps + 1):
@@ -100,8 +124,9 @@ for it in range(1, a.locksteps + 1):
             if env.family_weights is not None:                  # the weights the next block draws under (one read per block)
                 line.update(weights_by_class={family[1] + k: w for k, w in enumerate(env.family_weights.tolist())})
         if eval_env is not None:
-            ev = agent.evaluate(eval_env, a.eval_epsilon)
-            line.update(eval_success_rate=r4(ev["success_rate"]), eval_reward=r4(ev["reward"]), eval_num_steps=r4(ev["num_steps"]))
+            ev, q_first = evaluate_with_first_q(agent, eval_env, a.eval_epsilon)
+            line.update(eval_success_rate=r4(ev["success_rate"]), eval_reward=r4(ev["reward"]), eval_num_steps=r4(ev["num_steps"]),
+                        eval_lin_reward=r4(ev["lin_reward"]), eval_q_first=r4(q_first))
             if family:
                 line.update(eval_success_by_class={n: r4(s) for n, s in enumerate(ev["success_by_class"]) if n >= family[1]})
         print(json.dumps(line), flush=True)

@@ -2,7 +2,8 @@
 256-128-64-128-256) as a replayed HIP graph: the hand-written forward / loss / backward (bridges_hip/mlp_ops.py) + torch's
 fused Adam, against the autograd step + fused Adam.  Under rocprofv3 --kernel-trace the kernel list of either is visible.
 Usage: python tools/mlp_step_bench.py [--autograd] [--replays 400] [--batch 32]
-       python tools/mlp_step_bench.py --obstacle_bits     (times the two kernels of per-env obstacles alone, see obstacle_bits_lines)"""
+       python tools/mlp_step_bench.py --obstacle_bits     (times the two kernels of per-env obstacles alone, see obstacle_bits_lines)
+       python tools/mlp_step_bench.py --td_select         (times the double-Q target kernel against bridges_td_target, see td_select_lines)"""
 import argparse
 import os
 import sys
@@ -57,8 +58,80 @@ def obstacle_bits_lines(dev, B=32, n_b=25, E=4096, hidden=256, reps=50):
           lambda: ops.bits_linear(env_obst, wb, base=ops.bits_linear(state, wa, base=table, base_row=base_row), base_row=torch.arange(E, device=dev)))
 
 
+def td_select_lines(dev, B=32, n_b=25, rounds=15, per_graph=20):
+    """k_td_target_select (dqn_ops.td_target(select_q=...)) beside k_td_target (the same call without select_q) on the same
+    segments, device time per launch.  Shapes: n_b * B transitions whose segments are the candidate sets of a tower-4 rollout
+    (an env of n_b * B envs after 6 lock-steps of random actions), and the same number of transitions on 700-row segments
+    (the longest of the conformance probe, tests/mlp_conformance.td_probe), eight distinct ones shared as (lo, hi) pairs; each
+    with sf_dim = 0 (the launch the loop makes: rows only, the successor features follow for the selected rows) and with
+    sf_dim = 4096.  A launch is timed as 1 / per_graph of a replayed HIP graph of per_graph launches, between HIP events; the two
+    kernels ALTERNATE for `rounds` rounds and the line gives the median and the range over the rounds of each -- the range of
+    bridges_td_target, unchanged since before this kernel existed, is the run-to-run spread to hold the difference against."""
+    import statistics
+    from bridges_hip import dqn_ops
+    from bridges_hip.shapes import load_urdf
+    from bridges_hip.vec_env import VecAssemblyGym
+    n, H = n_b * B, 0.8
+    env = VecAssemblyGym(n, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(4)], [(0.5, 0, 4 * H + H / 2)],
+                         max_steps=15, seed=0, device=dev, f32_rasters=False, candidate_snapshots=False)
+    for _ in range(6):
+        env.select_random()
+        env.step()
+    counts = env.n_valid[:n].to(torch.int32)
+    hi = torch.cumsum(counts, 0).to(torch.int32)
+    rollout = (hi - counts, hi)
+    lo8 = 700 * (torch.arange(n, device=dev, dtype=torch.int32) % 8)
+    longest = (lo8, lo8 + 700)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, (lo, hi) in (("tower-4 rollout segments", rollout), ("700-row segments", longest)):
+        R = int(hi.max())
+        lens = (hi - lo).float()
+        print(f"{name}: {n} transitions, {R} rows, segment length mean {float(lens.mean()):.1f} max {int(lens.max())}", flush=True)
+        next_q, select_q = torch.randn(R, device=dev, generator=g), torch.randn(R, device=dev, generator=g)
+        lin, done = torch.randn(n, device=dev, generator=g), (torch.rand(n, device=dev, generator=g) < 0.1).to(torch.uint8)
+        for sf_dim in (0, 4096):
+            if sf_dim and R * sf_dim * 4 > (2 << 30):
+                print(f"  sf_dim {sf_dim}: skipped, next_sf would hold {R * sf_dim * 4 / 2 ** 30:.1f} GiB", flush=True)
+                continue
+            kw = {}
+            if sf_dim:
+                kw = dict(next_sf=torch.randn(R, sf_dim, device=dev, generator=g), action_raster=torch.rand(n, sf_dim, device=dev, generator=g))
+            calls = dict(td_target=lambda: dqn_ops.td_target((lo, hi), next_q, lin, done, 0.95, **kw),
+                         td_target_select=lambda: dqn_ops.td_target((lo, hi), next_q, lin, done, 0.95, select_q=select_q, **kw))
+            graphs = {}
+            for k, fn in calls.items():
+                fn()
+                st = torch.cuda.Stream()
+                st.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(st):
+                    fn()
+                torch.cuda.current_stream().wait_stream(st)
+                graphs[k] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[k]):
+                    for _ in range(per_graph):
+                        fn()
+                for _ in range(3):
+                    graphs[k].replay()
+            torch.cuda.synchronize()
+            times = {k: [] for k in calls}
+            for _ in range(rounds):
+                for k in calls:                                         # alternate: both see the same minutes of the machine
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(5):
+                        graphs[k].replay()
+                    b.record()
+                    torch.cuda.synchronize()
+                    times[k].append(a.elapsed_time(b) / (5 * per_graph) * 1e3)
+            for k, t in times.items():
+                print(f"  sf_dim {sf_dim:4d} {k:17s}: median {statistics.median(t):7.2f} us  min {min(t):7.2f}  max {max(t):7.2f} "
+                      f"per launch over {rounds} rounds", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--td_select", action="store_true",
+                    help="time the double-Q target kernel (k_td_target_select) against bridges_td_target at the same shapes and exit")
     ap.add_argument("--obstacle_bits", action="store_true",
                     help="time the two kernels of per-env obstacles (k_bits_linear2, k_mlp_input with obstacle bits) alone and exit")
     ap.add_argument("--autograd", action="store_true")
@@ -71,6 +144,9 @@ def main():
     if args.obstacle_bits:
         torch.manual_seed(0)
         return obstacle_bits_lines(torch.device("cuda:0"), B=args.batch)
+    if args.td_select:
+        torch.manual_seed(0)
+        return td_select_lines(torch.device("cuda:0"), B=args.batch)
     from bridges_hip.mlp_ops import FusedSuccessorStep
     from robotoddler.models.cv import SuccessorMLP
     from robotoddler.utils.utils import init_weights

@@ -5,7 +5,8 @@ if "--miopen_search" not in sys.argv:
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import torch
-from robotoddler.training.successor_dqn import add_curriculum_arguments, add_n_step_argument, build_parser, check_curriculum, make_nets
+from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument, build_parser,
+                                                check_curriculum, make_nets)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
@@ -51,6 +52,7 @@ ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
                 help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
 add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
 add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_step=N))
+add_double_q_argument(ap)                # --double_q: double Q-learning targets (VecDQN(double_q=True)); rows_fed counts both passes
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -105,7 +107,7 @@ opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
                episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
-               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1))
+               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -161,6 +163,10 @@ print(json.dumps(dict(config=vars(a), family_weights=env.family_weights.tolist()
                       env_steps_per_s=steps_done / dt,
                       env_steps_per_s_at_median_lockstep=steps_done / a.locksteps / median, ms_median_lockstep=median * 1e3,
                       ms_per_lockstep=dt / a.locksteps * 1e3,
+                      # host time between consecutive lock-steps, sorted: min, 10 / 25 / 75 / 90 % points, max (the host runs ahead
+                      # of the GPU and waits one lock-step late, so single lock-steps can read far below and above the mean)
+                      ms_lockstep_points=[round(per_step[min(len(per_step) - 1, int(f * len(per_step)))] * 1e3, 2)
+                                          for f in (0.0, 0.1, 0.25, 0.75, 0.9, 1.0)],
                       rows_per_lockstep=rows_seen / a.locksteps, rows_fed_per_lockstep=rows_fed / a.locksteps,
                       ms_lockstep_per_1000_fed_rows=(dt * 1e3 / (rows_fed / 1000.0)) if rows_fed else None, rows_fed_fraction=(rows_fed / rows_seen) if rows_seen else None,
                       ms_act=t_act / n_phase * 1e3, ms_targets=t_targets[0] / n_phase * 1e3, ms_train=t_train / n_phase * 1e3,

@@ -562,13 +562,13 @@ int bridges_action_features(const bridges_shape* shapes_dev, int32_t n, const do
 }
 
 int bridges_bits_or(int32_t n_groups, const int32_t* ranges, const uint64_t* bits, uint64_t* out, void* stream) {
-    if (n_groups < 0) return fail_arg("bridges_bits_or");
+    if (n_groups < 0 || (n_groups > 0 && (!ranges || !bits || !out))) return fail_arg("bridges_bits_or");
     if (n_groups == 0) return BRIDGES_OK;
     return launch("k_bits_or", k_bits_or, dim3(n_groups), dim3(WAVE), 0, stream, n_groups, ranges, bits, out);
 }
 
 int bridges_bits_to_f32(int32_t n, const uint64_t* bits, float* img, void* stream) {
-    if (n < 0) return fail_arg("bridges_bits_to_f32");
+    if (n < 0 || (n > 0 && (!bits || !img))) return fail_arg("bridges_bits_to_f32");
     if (n == 0) return BRIDGES_OK;
     // one short-lived wave per image, dispatched in image order (the store structure of k_raster)
     return launch("k_bits_to_f32", k_bits_to_f32, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, n, bits, img);

@@ -372,9 +372,10 @@ int bridges_action_features(const bridges_shape* shapes_dev, int32_t n, const do
                             const double* grid_x, const double* grid_y, int32_t size, double xlim0, double xlim1, double ylim0,
                             double ylim1, const uint64_t* state_bits, const uint64_t* obstacle_bits, const double* reward_prefix,
                             uint64_t* bits, float* img, uint8_t* mask, float* lin_reward, void* stream);
-/* OR-reduce groups of bit rasters: out[g] = OR bits[ranges[g][0] .. ranges[g][1]);  ranges int32 [n_groups,2]. */
+/* OR-reduce groups of bit rasters: out[g] = OR bits[ranges[g][0] .. ranges[g][1]);  ranges int32 [n_groups,2]; an empty range
+ * gives 64 zero words.  A NULL pointer with n_groups > 0 returns -1 and launches nothing. */
 int bridges_bits_or(int32_t n_groups, const int32_t* ranges, const uint64_t* bits, uint64_t* out, void* stream);
-/* bit raster -> f32 image. */
+/* bit raster -> f32 image.  A NULL pointer with n > 0 returns -1 and launches nothing. */
 int bridges_bits_to_f32(int32_t n, const uint64_t* bits, float* img, void* stream);
 /* The stacked input of the conv Q-networks (ConvNet / UNet, cv.py's cat([block, action, reward, obstacle], dim=1)) in one pass:
  * x [n_rows, 4, 64, 64] f32, contiguous NCHW, row r =

@@ -304,6 +304,9 @@ SIGNATURES = {
     "bridges_td_target_select": [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp],
     "bridges_nstep_fold": [i32, i32, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_discounted_sum": [i32, vp, i64, vp, vp, f32, vp, vp, vp],
+    "bridges_priority_sample_scratch": [i64, C.POINTER(i64)],
+    "bridges_priority_sample": [i64, i32, i32, vp, f64, i64, vp, vp, vp, i64, vp],
+    "bridges_priority_update": [i64, i32, i32, vp, i64, vp, vp, vp, vp],
 }
 
 

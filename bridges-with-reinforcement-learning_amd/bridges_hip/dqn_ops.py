@@ -125,6 +125,46 @@ def nstep_fold(rec, valid, gamma, n, count, acc, disc, stable_s, td):
     return out, out_valid
 
 
+def priority_sample_scratch(n_rec):
+    """Doubles of scratch bridges_priority_sample needs for a ring of up to ``n_rec`` live rows (no GPU needed)."""
+    need = C.c_int64(0)
+    abi.check(abi.lib().bridges_priority_sample_scratch(int(n_rec), C.byref(need)), "bridges_priority_sample_scratch")
+    return need.value
+
+
+def priority_sample(rec, n_rec, col, alpha, u, scratch):
+    """The inverse-CDF draw over column ``col`` of the first ``n_rec`` rows of rec [*, W] float64 (bridges_priority_sample):
+    mass pow(clamp(priority, 0, 1e30) + 1e-5, alpha), u [n] float64 in [0, 1) -> idx [n] int64, the first row whose inclusive
+    prefix sum exceeds u * total (searchsorted(right=True), clamped to n_rec - 1).  ``scratch``: float64, at least
+    priority_sample_scratch(n_rec) elements, overwritten.  Three launches, no host wait, the same idx for the same inputs."""
+    L = abi.require_gpu()
+    assert rec.dtype == torch.float64 and rec.dim() == 2 and rec.is_contiguous()
+    assert u.dtype == torch.float64 and u.is_contiguous() and u.device == rec.device
+    assert scratch.dtype == torch.float64 and scratch.is_contiguous() and scratch.device == rec.device
+    if not 0 <= int(n_rec) <= rec.shape[0]:
+        raise ValueError(f"priority_sample: n_rec = {n_rec} of a buffer of {rec.shape[0]} rows")
+    idx = torch.empty(u.numel(), dtype=torch.int64, device=rec.device)
+    abi.check(L.bridges_priority_sample(int(n_rec), rec.shape[1], int(col), _ptr(rec), float(alpha), u.numel(), _ptr(u), _ptr(idx),
+                                        _ptr(scratch), scratch.numel(), _stream()), "bridges_priority_sample")
+    return idx
+
+
+def priority_update_(rec, n_rec, col, idx, q_sa, q_target):
+    """rec[idx[j], col] = |q_sa[j] - q_target[j]| in place (bridges_priority_update): idx [n] int64, q_sa and q_target [n]
+    float32.  A row named several times takes its last draw's value; an index outside [0, n_rec) writes nothing."""
+    L = abi.require_gpu()
+    assert rec.dtype == torch.float64 and rec.dim() == 2 and rec.is_contiguous()
+    if not 0 <= int(n_rec) <= rec.shape[0]:
+        raise ValueError(f"priority_update_: n_rec = {n_rec} of a buffer of {rec.shape[0]} rows")
+    n = idx.numel()
+    assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.device == rec.device
+    for t in (q_sa, q_target):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == rec.device
+    abi.check(L.bridges_priority_update(int(n_rec), rec.shape[1], int(col), _ptr(rec), n, _ptr(idx), _ptr(q_sa), _ptr(q_target),
+                                        _stream()), "bridges_priority_update")
+    return rec
+
+
 def soft_update_(target, policy, tau):
     """target <- policy * tau + target * (1 - tau) in place (successor_dqn.py:280-288); float32 contiguous tensors."""
     L = abi.require_gpu()

@@ -12,6 +12,7 @@
 #include "mlp_kernels.hip"
 #include "conv_kernels.hip"
 #include "conv_train_kernels.hip"
+#include "replay_kernels.hip"
 
 using namespace bridges;
 
@@ -685,6 +686,52 @@ int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const
     // one wave per env, four envs per workgroup
     return launch("k_nstep_fold", k_nstep_fold, dim3((unsigned)ceil_div(E, 4)), dim3(256), 0, stream, (int)E, (int)W, (int)n, rec, valid,
                   gamma, count, acc, disc, stable_s, td, out, out_valid);
+}
+
+int bridges_priority_sample_scratch(int64_t n_rec, int64_t* doubles) {
+    if (!doubles || n_rec < 0 || n_rec > BRIDGES_PRIORITY_MAX_ROWS) return fail_arg("bridges_priority_sample_scratch");
+    const int64_t chunks = ceil_div(n_rec, PRIO_CHUNK);
+    *doubles = chunks * PRIO_CHUNK + 2 * chunks;          // the masses of whole chunks, the chunk sums, their prefix sums
+    return BRIDGES_OK;
+}
+
+int bridges_priority_sample(int64_t n_rec, int32_t W, int32_t col, const double* rec, double alpha, int64_t n_draws, const double* u,
+                            int64_t* idx, double* scratch, int64_t scratch_doubles, void* stream) {
+    if (n_draws < 0) return fail_arg("bridges_priority_sample: negative count");
+    if (n_draws == 0) return BRIDGES_OK;
+    if (n_rec <= 0 || n_rec > BRIDGES_PRIORITY_MAX_ROWS) return fail_arg("bridges_priority_sample: n_rec must be 1..BRIDGES_PRIORITY_MAX_ROWS");
+    if (col < 0 || W <= col) return fail_arg("bridges_priority_sample: the column lies outside the record");
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail_arg("bridges_priority_sample: alpha must lie in [0, 1]");
+    if (!rec || !u || !idx || !scratch) return fail_arg("bridges_priority_sample: null pointer");
+    if (!aligned(8, rec, u, idx, scratch)) return fail_arg("bridges_priority_sample: misaligned pointer");
+    int64_t need = 0;
+    if (int rc = bridges_priority_sample_scratch(n_rec, &need)) return rc;
+    if (scratch_doubles < need) return fail_arg("bridges_priority_sample: scratch too small (bridges_priority_sample_scratch)");
+    const int chunks = (int)ceil_div(n_rec, PRIO_CHUNK);
+    double* mass = scratch;
+    double* chunk_sum = mass + (int64_t)chunks * PRIO_CHUNK;
+    double* chunk_cdf = chunk_sum + chunks;
+    const int mode = alpha == 0.0 ? 0 : (alpha == 1.0 ? 1 : 2);
+    if (int rc = launch("k_priority_mass", k_priority_mass, dim3((unsigned)chunks), dim3(PRIO_CHUNK), 0, stream, n_rec, (int)W, (int)col, rec,
+                        alpha, mode, mass, chunk_sum))
+        return rc;
+    if (int rc = launch("k_priority_scan", k_priority_scan, dim3(1), dim3(256), 0, stream, chunks, (const double*)chunk_sum, chunk_cdf))
+        return rc;
+    // one wave per draw, four draws per workgroup
+    return launch("k_priority_draw", k_priority_draw, dim3((unsigned)ceil_div(n_draws, 4)), dim3(256), 0, stream, n_rec, chunks,
+                  (const double*)mass, (const double*)chunk_cdf, n_draws, u, idx);
+}
+
+int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, int64_t n, const int64_t* idx, const float* q_sa,
+                            const float* q_target, void* stream) {
+    if (n < 0 || n_rec < 0) return fail_arg("bridges_priority_update: negative count");
+    if (col < 0 || W <= col) return fail_arg("bridges_priority_update: the column lies outside the record");
+    if (n == 0) return BRIDGES_OK;
+    if (n > BRIDGES_PRIORITY_MAX_UPDATES) return fail_arg("bridges_priority_update: n > BRIDGES_PRIORITY_MAX_UPDATES");
+    if (!rec || !idx || !q_sa || !q_target) return fail_arg("bridges_priority_update: null pointer");
+    if (!aligned(8, rec, idx) || !aligned(4, q_sa, q_target)) return fail_arg("bridges_priority_update: misaligned pointer");
+    return launch("k_priority_update", k_priority_update, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, n_rec, (int)W, (int)col,
+                  rec, n, idx, q_sa, q_target);
 }
 
 int bridges_bits_discounted_sum(int32_t n, const uint64_t* bits, int64_t n_rows, const int64_t* first, const int32_t* h, float gamma,

@@ -533,7 +533,48 @@ def build_parser():
     add_curriculum_arguments(p)
     add_n_step_argument(p)
     add_double_q_argument(p)
+    add_priority_arguments(p)
     return p
+
+
+def add_priority_arguments(p, prioritized_flag=False):
+    """--priority_alpha / --priority_refresh: shared with the tools that train through the vectorised loop
+    (``prioritized_flag``: and --prioritized_replay itself, for a parser that has none)."""
+    if prioritized_flag:
+        p.add_argument("--prioritized_replay", action="store_true",
+                       help="replay in proportion to td_error + 1e-5 (VecDQN(prioritized=True))")
+    p.add_argument("--priority_alpha", type=float, default=argparse.SUPPRESS, metavar="A",
+                   help="Vectorised loop with --prioritized_replay: replay a transition with probability proportional to "
+                        "(td_error + 1e-5)^A, 0 <= A <= 1 (default 1: the reference's rule; 0: uniform), drawn by the sampler "
+                        "kernel on the device.")
+    p.add_argument("--priority_refresh", action="store_true", default=argparse.SUPPRESS,
+                   help="Vectorised loop with --prioritized_replay, one rank: after every lock-step's target pass write "
+                        "|q(s,a) - q_target| of the sampled transitions back as their priorities (rows keep the rollout's TD error "
+                        "until they are first sampled). One more policy-net forward over the sampled rows per lock-step.")
+
+
+def check_priority(args):
+    """--priority_alpha / --priority_refresh: refused in words (SystemExit) where the loop cannot run them, before anything
+    touches the GPU."""
+    given = [f"--{k}" for k in ('priority_alpha', 'priority_refresh') if k in args]
+    if not given:
+        return
+    if args['num_envs'] <= 1:
+        raise SystemExit(f"{' / '.join(given)} need the vectorised loop (--num_envs N, N > 1): the single-env loop samples through "
+                         "the reference's PrioritizedReplayBuffer")
+    if not args.get('prioritized_replay'):
+        raise SystemExit(f"{' / '.join(given)} shape the prioritised draw: they need --prioritized_replay")
+    a = args.get('priority_alpha', 1.0)
+    if not 0.0 <= a <= 1.0:
+        raise SystemExit(f"--priority_alpha must lie in [0, 1] (0: uniform, 1: proportional to td_error + 1e-5), not {a}")
+
+
+def priority_from_args(args):
+    """The prioritised-replay arguments of VecDQN from parsed options (a tool's: every lock-step there is vectorised);
+    --priority_alpha / --priority_refresh without --prioritized_replay is refused as check_priority refuses it."""
+    check_priority(dict(args, num_envs=2))
+    return dict(prioritized=bool(args.get('prioritized_replay', False)), priority_alpha=args.get('priority_alpha', 1.0),
+                priority_refresh=bool(args.get('priority_refresh', False)))
 
 
 def add_n_step_argument(p):
@@ -753,6 +794,7 @@ def main(argv=None):
     check_random_targets(args)
     check_n_step(args)
     check_double_q(args)
+    check_priority(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

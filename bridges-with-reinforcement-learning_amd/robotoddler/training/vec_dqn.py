@@ -16,6 +16,9 @@ Semantics follow rollout_episode / train_policy_net / update_target_net of the r
   hundreds of episodes end per lock-step and a per-episode decay would reach the floor within a dozen lock-steps);
 * uniform replay draws WITH replacement (torch.randint on the device ring; the reference's random.sample draws without:
   a duplicate inside a batch of 32 out of >= 10^4 records has probability ~5e-2 and only repeats a sample);
+* prioritised replay draws in proportion to td_error + 1e-5, the rollout's TD error (PrioritizedReplayBuffer); priority_alpha /
+  priority_refresh (extensions: the reference has neither) add Schaul et al.'s exponent and write |q(s,a) - q_target| of the
+  sampled transitions back as their priorities, both on the device (DESIGN.md section 7, "Prioritised replay on the device");
 * with several ranks every rank trains an identical replica on the identical gathered ring (same sampling seed); extra
   GPUs add rollout throughput, not optimiser throughput; parameters are re-broadcast every 100 lock-steps;
 * log_episode's numbers (successor_dqn.py:479-499) are logged per lock-step as means over the episodes that ended in it on all
@@ -52,7 +55,7 @@ class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
-                 n_step=1, double_q=False):
+                 n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -85,7 +88,27 @@ class VecDQN:
         already makes by sharing one target pass between them.  It composes with n_step, prioritized, stable_actions_only, the
         curriculum, per-env tasks / obstacles, task_channels and several ranks (the targets are computed after the gather);
         td_errors stays the reference's formula.  The ring stores transitions, not targets, so a checkpoint can be resumed with
-        the option switched ("Double Q-learning").  False is the loop as it was: no launch of this."""
+        the option switched ("Double Q-learning").  False is the loop as it was: no launch of this.
+        ``priority_alpha=a`` (0..1, with prioritized=True only): a transition is replayed with probability proportional to
+        (td_error + 1e-5)^a -- Schaul et al.'s exponent; 1 is the reference's rule, 0 the uniform draw -- through the sampler
+        kernel (ReplayRing.sample_prioritized).  ``priority_refresh=True`` (with prioritized=True only, one rank): after _targets
+        the policy net as it stands then values (s_t, a_t) of all n_steps * B sampled transitions, and |q(s_t, a_t) - q_target| is
+        written back to the sampled rows (ReplayRing.update_priorities); rows keep the rollout's td_errors until they are first
+        sampled.  Neither option changes the record, the ring or a checkpoint, so a run may be resumed with other settings; with
+        priority_alpha=1.0 and priority_refresh=False the loop samples through ReplayRing.sample as it always did (DESIGN.md,
+        "Prioritised replay on the device")."""
+        self.priority_alpha, self.priority_refresh = float(priority_alpha), bool(priority_refresh)
+        if not 0.0 <= self.priority_alpha <= 1.0:            # (a NaN fails both comparisons)
+            raise ValueError(f"VecDQN(priority_alpha={priority_alpha}): the exponent of the priorities lies in [0, 1] "
+                             "(0: uniform, 1: proportional to td_error + 1e-5)")
+        if not prioritized and (self.priority_refresh or self.priority_alpha != 1.0):
+            raise ValueError("VecDQN(priority_alpha=..., priority_refresh=...) shape the prioritised draw: they need prioritized=True "
+                             "(a uniform loop stores no priorities: O_TD of its records is 0)")
+        if self.priority_refresh and D.active():
+            raise ValueError("VecDQN(priority_refresh=True) runs on one rank only: the replica nets drift between the parameter "
+                             "broadcasts, so every rank would write other priorities and the rings would stop being replicas "
+                             "(priority_alpha alone is allowed: the sampler is deterministic on identical rings)")
+        self._transitions = None                             # priority_refresh: what _targets leaves for _transition_q
         self.double_q = bool(double_q)
         self.n_step = int(n_step)
         if not 1 <= self.n_step <= abi.NSTEP_MAX:
@@ -666,6 +689,8 @@ class VecDQN:
             sf_target = sf_action.reshape(E, -1) if use_sf else None
         binary = torch.zeros((E, 6), dtype=torch.float32, device=self.device)
         binary[:, 0] = stable_s
+        if self.priority_refresh:                            # (s_t, a_t) of every transition, for _transition_q
+            self._transitions = (renv, bits_s, action_bits, stable_s, block_f, action_f)
         if self.task_channels:
             out = (None, binary[:n], None, q_target[:n], (sf_target[:n] if use_sf else None), renv.reward_maps_img[:n].reshape(n, -1))
             return out + ((renv.env_obstacle_bits[:n],) if self.per_env_obstacles else ()) + (bits_s[:n], action_bits[:n])
@@ -673,6 +698,27 @@ class VecDQN:
         if self.per_env_obstacles:
             return out + (renv.reward_maps_img[:n].reshape(n, -1), renv.env_obstacle_bits[:n])
         return out + (renv.reward_maps_img[:n].reshape(n, -1),) if self.per_env_tasks else out
+
+    @torch.no_grad()
+    def _transition_q(self, n):
+        """q(s_t, a_t) of the POLICY net as it stands now for the n transitions the last _targets call was given (priority_refresh),
+        through the forwards acting uses (_net_q): the transitions stand in for an env whose state e is s_t of transition e and
+        whose only candidate row is a_t (_TransitionRows over the scratch env, which still holds their tasks).  The factored
+        SuccessorMLP reads the bit rasters (bridges_bits_linear; per-env tasks: the scratch env's reward maps and the
+        [E, 2, hidden] tables, per-env obstacles: bridges_bits_linear2), the conv nets run the module forward in eval() over the
+        f32 images _targets built, in ROW_CHUNK chunks padded as _forward_rows pads, or with task_channels over one
+        ops.conv_input per chunk.  Every row is fed: looking for equal rows would cost a host wait.  -> q [n] float32."""
+        renv, bits_s, action_bits, stable_s, block_f, action_f = self._transitions
+        view = getattr(renv, "_transition_rows", None)
+        if view is None:
+            view = renv._transition_rows = _TransitionRows(renv)
+        view.state_bits, view.cand_bits = bits_s, action_bits
+        factored = self._factored(self.policy_net)
+        view.state_raster = block_f.squeeze(1) if (block_f is not None and not factored) else None
+        view.cand_raster = action_f.squeeze(1) if (action_f is not None and not factored and not self.task_channels) else None
+        rows = torch.arange(renv.E, dtype=torch.int64, device=self.device)
+        q = self._net_q(self.policy_net, view, rows, rows, stable_s.bool(), groups=None)
+        return q[:n].contiguous().float()
 
     def _loss(self, q, sf, q_target, sf_target):
         loss = 0.
@@ -724,8 +770,18 @@ class VecDQN:
         B = self.B
         # n_steps independent batches = ONE draw of n_steps * B records: both sampling rules draw with replacement, so
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
-        rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
+        drawn = None
+        if self.priority_refresh or self.priority_alpha != 1.0:
+            # the sampler kernel: the exponent, and the ring rows of the draws for the refresh
+            rec, drawn = self.ring.sample_prioritized(n_steps * B, self.sample_gen, self.priority_alpha)
+        else:
+            rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
         block_f, binary, action_f, q_target, sf_target, *task = self._targets(rec)
+        if self.priority_refresh:
+            # |q(s_t, a_t) - q_target| of the policy net as it stands now, back to the sampled rows in one launch (once per
+            # lock-step for all n_steps batches, the approximation double_q makes); q_target is what _targets returned, whatever
+            # the loss parts are
+            self.ring.update_priorities(drawn, self._transition_q(n_steps * B), q_target)
         if self.task_channels:                               # the transitions' bit rasters stand in for their f32 images
             block_f, action_f = task[-2:]
             task = task[:-2]
@@ -897,6 +953,23 @@ class VecDQN:
         return losses, allrec
 
 
+class _TransitionRows:
+    """The transitions of a _targets call as the env a Q pass reads (VecDQN._transition_q): state e = s_t of transition e
+    (state_bits / state_raster), its one candidate row e = a_t (cand_bits / cand_raster); the images are cropped already.  The
+    task -- reward maps, obstacle rasters, the flags -- is the scratch env's, which every other attribute is read from."""
+
+    def __init__(self, env):
+        self._env = env
+        self.state_bits = self.cand_bits = self.state_raster = self.cand_raster = None
+
+    def __getattr__(self, name):                             # (only what the instance itself does not hold)
+        return getattr(self._env, name)
+
+    @staticmethod
+    def crop(x):
+        return x
+
+
 class DeferredLosses:
     """Losses of one train_steps call on their way to the host (pinned buffer + event)."""
 
@@ -1004,7 +1077,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
                    per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
                    task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1),
-                   double_q=bool(args.get('double_q', False)))
+                   double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
+                   priority_refresh=bool(args.get('priority_refresh', False)))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)

@@ -648,6 +648,36 @@ int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const
 int bridges_bits_discounted_sum(int32_t n, const uint64_t* bits, int64_t n_rows, const int64_t* first, const int32_t* h, float gamma,
                                 float* sum, float* disc, void* stream);
 
+/* --- prioritised replay of the vectorised loop --------------------------------------------------------------------
+ * The inverse-CDF draw over one column of the replay ring.  rec [n_rec, W] f64 holds the live rows (their order is irrelevant),
+ * col the priority column (BRIDGES_REC_TD), u [n_draws] f64 uniforms in [0, 1):
+ *   m_i = pow(fmin(fmax(rec[i, col], 0), 1e30) + 1e-5, alpha)     (alpha == 1: the sum itself, no pow; alpha == 0: m_i = 1),
+ *   idx[j] = the first k with m_0 + .. + m_k > u[j] * (m_0 + .. + m_{n_rec-1}), clamped to n_rec - 1
+ * -- torch.searchsorted(cumsum(m), u * sum(m), right=True).clamp(max = n_rec - 1).  A NaN or negative priority counts as 0 and
+ * one above 1e30 as 1e30 (fmax / fmin return the operand that is not NaN), so the total is finite and positive whatever a
+ * diverged step wrote.  The sums are float64 in a fixed order of the kernels' own (256-row chunks summed by a tree, the chunk
+ * sums scanned serially, the masses inside a chunk scanned by a wave): against the exactly rounded prefix sums idx[j] may differ
+ * where u[j] * total lies within ~n_rec * 2^-52 * total of a boundary, and nowhere else.  No floating-point atomics: the same
+ * inputs give the same idx bit for bit on every call and every device.  Three launches (masses + chunk sums, scan, draws), no
+ * host wait; rec is only read.  scratch: bridges_priority_sample_scratch(n_rec) doubles, caller-owned, overwritten.
+ * u[j] outside [0, 1) or NaN is not an error: every idx[j] lies in [0, n_rec).
+ * Returns -1 and launches nothing for: n_draws < 0; with n_draws > 0: n_rec <= 0 or n_rec > BRIDGES_PRIORITY_MAX_ROWS; col < 0 or
+ * W <= col; alpha outside [0, 1] or NaN; a NULL rec, u, idx or scratch; a pointer that is not 8-byte aligned; scratch_doubles
+ * below the sizing call's answer.  n_draws == 0 returns 0 and launches nothing. */
+#define BRIDGES_PRIORITY_MAX_ROWS (1ll << 30)
+#define BRIDGES_PRIORITY_MAX_UPDATES (1ll << 20)
+int bridges_priority_sample_scratch(int64_t n_rec, int64_t* doubles);
+int bridges_priority_sample(int64_t n_rec, int32_t W, int32_t col, const double* rec, double alpha, int64_t n_draws, const double* u,
+                            int64_t* idx, double* scratch, int64_t scratch_doubles, void* stream);
+/* The refresh of sampled rows: rec[idx[j], col] = (double)fabsf(q_sa[j] - q_target[j]) for j < n (idx i64, q_sa and q_target f32).
+ * A row named by several j takes the value of the LAST of them (the highest j); every row is written by one thread, so equal
+ * inputs give equal rings.  An idx[j] outside [0, n_rec) writes nothing; no column but col and no row that idx does not name is
+ * written.  One launch; the work grows with n^2 / 2 (n = n_steps * batch_size, hundreds), n <= BRIDGES_PRIORITY_MAX_UPDATES.
+ * Returns -1 and launches nothing for: n < 0 or n_rec < 0; col < 0 or W <= col; with n > 0 a NULL rec, idx, q_sa or q_target, an
+ * rec / idx that is not 8-byte or a q_sa / q_target that is not 4-byte aligned.  n == 0 returns 0 and launches nothing. */
+int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, int64_t n, const int64_t* idx, const float* q_sa,
+                            const float* q_target, void* stream);
+
 /* Inference epilogues of the conv Q-networks (robotoddler/models/cv.py:5-17, 41-73, 108-170: Conv2d -> ReLU
  * [-> MaxPool2d(2)]), one pass instead of torch's three; bit-identical to relu(conv + bias) / maxpool(relu(conv + bias)).
  * x [n, C, hw] f32 contiguous NCHW output of a bias-free convolution, updated in place (hw % 4 == 0). */

@@ -5,7 +5,9 @@ memory, as run_vectorised does (the count printed should not change).  --random_
 family (RandomBridges), --curriculum [--curriculum_every N ...] with its curriculum on as well: with --curriculum_every 1 the listed
 lock-step holds the fold AND the update, and the count should be that of the same line without --curriculum.  --n_step N runs the
 lock-step with n-step returns (the fold and the compaction of its rows): the count should be that of the same line without it.
---double_q runs it with double Q-learning targets (a second forward over the next-state rows): the count should not change either."""
+--double_q runs it with double Q-learning targets (a second forward over the next-state rows): the count should not change either.
+--prioritized_replay [--priority_alpha A] [--priority_refresh] runs it on prioritised replay; the sampler kernel and the refresh add
+launches, and the count should be that of plain --prioritized_replay."""
 import argparse
 import os
 import sys
@@ -23,12 +25,13 @@ ap.add_argument("--episode_stats", action="store_true", help="VecDQN(episode_sta
 ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI", help="a task family (RandomBridges) instead of the fixed tower")
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, VecAssemblyGym
-from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument, build_parser,
-                                                check_curriculum, make_nets)
+from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
+                                                add_priority_arguments, build_parser, check_curriculum, make_nets, priority_from_args)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 add_curriculum_arguments(ap)
 add_n_step_argument(ap)
 add_double_q_argument(ap)
+add_priority_arguments(ap, prioritized_flag=True)
 a = ap.parse_args()
 sizes = tuple(int(v) for v in a.random_bridge_length.split(":")) if a.random_bridge_length else None
 check_curriculum(vars(a), sizes)
@@ -44,7 +47,8 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, ta
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=False)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
                "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes), per_env_obstacles=bool(sizes),
-               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False))
+               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
+               **priority_from_args(vars(a)))
 
 
 def lockstep():

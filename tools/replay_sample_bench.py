@@ -1,0 +1,61 @@
+"""The prioritised draw on the device against the torch formulation it stands beside, on identical rings in one process:
+ReplayRing.sample_prioritized (bridges_priority_sample: masses + chunk sums, scan, one search per draw -- three launches -- and the
+gather) beside ReplayRing.sample(prioritized=True) (a strided column read, cumsum over the live ring, rand, a multiply,
+searchsorted, clamp and the gather).  Both draw their uniforms with the same torch.rand call, which is inside both timings.  HIP
+events around single calls, both sides alternating, warm-up first; prints one JSON line per ring size with the medians and the
+spread (min, max, inter-quartile range).
+    python tools/replay_sample_bench.py [--rows 16384 131072] [--width 111] [--draws 800] [--alpha 1.0] [--reps 40]
+The kernel path reads one 64-byte sector per 8 W-byte row (the priority column is strided by the record layout), writes and reads
+8 bytes of mass per row, and touches ~13 chunk prefix sums and 2 KiB of masses per draw."""
+import argparse, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
+import numpy as np
+import torch
+from robotoddler.training import records as R
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", type=int, nargs="+", default=[16384, 131072], help="live rows of the ring (one JSON line each)")
+ap.add_argument("--width", type=int, default=R.RECORD_WIDTH)
+ap.add_argument("--draws", type=int, default=800)
+ap.add_argument("--alpha", type=float, default=1.0, help="the kernel path's exponent (the torch formulation has none: alpha = 1)")
+ap.add_argument("--reps", type=int, default=40)
+ap.add_argument("--warmup", type=int, default=10)
+a = ap.parse_args()
+assert a.reps >= 20
+dev = torch.device("cuda:0")
+for rows in a.rows:
+    g = torch.Generator().manual_seed(rows)
+    ring = R.ReplayRing(rows, dev, width=a.width)
+    rec = torch.randn((rows, a.width), generator=g, dtype=torch.float64)
+    rec[:, R.O_TD] = torch.empty(rows, dtype=torch.float64).exponential_(1.0, generator=g)     # TD errors: non-negative, no outlier
+    ring.push(rec.to(dev))
+    gk, gf = (torch.Generator(device=dev).manual_seed(7) for _ in range(2))
+    kernel = lambda: ring.sample_prioritized(a.draws, gk, a.alpha)[0]
+    formulation = lambda: ring.sample(a.draws, gf, prioritized=True)
+    if a.alpha == 1.0:                                   # the same stream, the same distribution: the same records but for near-ties
+        same = (kernel() == formulation()).all(dim=1).float().mean().item()
+        assert same > 0.99, same
+    for _ in range(a.warmup):
+        kernel(); formulation()
+    torch.cuda.synchronize()
+    times = dict(kernel=[], formulation=[])
+    for _ in range(a.reps):
+        for name, fn in (("kernel", kernel), ("formulation", formulation)):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            out = fn()
+            stop.record()
+            stop.synchronize()
+            times[name].append(start.elapsed_time(stop) * 1e3)              # us
+            del out
+    summary = {}
+    for name, t in times.items():
+        t = np.array(t)
+        q1, med, q3 = np.percentile(t, [25, 50, 75])
+        summary[name] = dict(median_us=float(med), min_us=float(t.min()), max_us=float(t.max()), iqr_us=float(q3 - q1), calls=len(t))
+    k, f = summary["kernel"], summary["formulation"]
+    print(json.dumps(dict(config=dict(vars(a), rows=rows), **summary, ratio_of_medians=f["median_us"] / k["median_us"],
+                          faster_by_more_than_the_formulations_spread=bool(f["median_us"] - k["median_us"] > f["max_us"] - f["min_us"]),
+                          note="HIP events around single calls (rand, the draw and the gather; host launch gaps included), both sides "
+                               "alternating in one process; spread = max - min of the timed calls")), flush=True)

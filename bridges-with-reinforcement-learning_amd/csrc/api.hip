@@ -629,6 +629,17 @@ int bridges_soft_update(float* target, const float* policy, int64_t n, float tau
                   policy, n, tau, one_minus_tau);
 }
 
+// The one launch behind the three TD-target entry points (their checks differ, the kernel does not): per-row discounts when
+// `discount` is given, the scalar gamma otherwise.
+static int td_target_launch(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                            const float* next_sf, int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
+                            const uint8_t* done, const float* discount, float gamma, int32_t sf_dim, float* q_target,
+                            float* sf_target, int32_t* argmax_row, void* stream) {
+    return launch(discount ? "k_td_target<rows>" : "k_td_target", discount ? k_td_target<true> : k_td_target<false>, dim3(n_trans),
+                  dim3(256), 0, stream, n_trans, seg_lo, seg_hi, select_q, next_q, next_sf, next_sf_row_stride, action_raster,
+                  lin_reward, done, discount, gamma, sf_dim, q_target, sf_target, argmax_row);
+}
+
 int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
                       int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
                       const uint8_t* done, float gamma, int32_t sf_dim, float* q_target, float* sf_target,
@@ -637,8 +648,8 @@ int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg
     if (n_trans == 0) return BRIDGES_OK;
     if (sf_dim > 0 && ((next_sf_row_stride & 3) || (sf_dim & 3) || !aligned(16, next_sf, action_raster, sf_target)))
         return fail_arg("td_target: sf rows must be 16-byte aligned");
-    return launch("k_td_target", k_td_target, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi, next_q, next_sf,
-                  next_sf_row_stride, action_raster, lin_reward, done, gamma, sf_dim, q_target, sf_target, argmax_row);
+    return td_target_launch(n_trans, seg_lo, seg_hi, next_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done,
+                            nullptr, gamma, sf_dim, q_target, sf_target, argmax_row, stream);
 }
 
 int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
@@ -649,8 +660,8 @@ int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t
     if (n_trans == 0) return BRIDGES_OK;
     if (sf_dim > 0 && ((next_sf_row_stride & 3) || (sf_dim & 3) || !aligned(16, next_sf, action_raster, sf_target)))
         return fail_arg("td_target_rows: sf rows must be 16-byte aligned");
-    return launch("k_td_target_rows", k_td_target_rows, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi, next_q, next_sf,
-                  next_sf_row_stride, action_raster, lin_reward, done, discount, sf_dim, q_target, sf_target, argmax_row);
+    return td_target_launch(n_trans, seg_lo, seg_hi, next_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done,
+                            discount, 0.f, sf_dim, q_target, sf_target, argmax_row, stream);
 }
 
 int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
@@ -666,13 +677,8 @@ int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32
     if (!aligned(4, seg_lo, seg_hi, select_q, next_q, next_sf, action_raster, lin_reward, discount, q_target, sf_target, argmax_row))
         return fail_arg("bridges_td_target_select: misaligned pointer");
     // (sf rows that are not 16-byte aligned, or an sf_dim that is no multiple of 4, take the kernel's element-wise epilogue)
-    if (discount)
-        return launch("k_td_target_select<rows>", k_td_target_select<true>, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi,
-                      select_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done, discount, gamma, sf_dim, q_target,
-                      sf_target, argmax_row);
-    return launch("k_td_target_select", k_td_target_select<false>, dim3(n_trans), dim3(256), 0, stream, n_trans, seg_lo, seg_hi,
-                  select_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done, (const float*)nullptr, gamma, sf_dim,
-                  q_target, sf_target, argmax_row);
+    return td_target_launch(n_trans, seg_lo, seg_hi, select_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done,
+                            discount, gamma, sf_dim, q_target, sf_target, argmax_row, stream);
 }
 
 int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
@@ -797,8 +803,8 @@ int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t
     if (E < 0 || K < 1 || !gpow || !out || (E > 0 && (!rec || !valid || !run || !counted)))
         return fail_arg("bridges_episode_stats");
     if (E == 0) return BRIDGES_OK;
-    return launch("k_episode_stats", k_episode_stats, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec, valid, gpow,
-                  (int)n_targets, (int)(count_first_only != 0), run, counted, out);
+    return launch("k_episode_stats<1>", k_episode_stats<1>, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec, valid, gpow,
+                  (int)n_targets, (int)(count_first_only != 0), (const int32_t*)nullptr, 1, run, counted, out);
 }
 
 int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow,
@@ -808,8 +814,8 @@ int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, cons
         return fail_arg("bridges_episode_stats_by_class");
     if (n_classes < 1 || n_classes > EPISODE_STATS_MAX_CLASSES) return fail_arg("bridges_episode_stats_by_class: n_classes must be 1..8");
     if (E == 0) return BRIDGES_OK;
-    return launch("k_episode_stats_by_class", k_episode_stats_by_class, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream, E, K, rec,
-                  valid, gpow, (int)n_targets, (int)(count_first_only != 0), cls, (int)n_classes, run, counted, out);
+    return launch("k_episode_stats<8>", k_episode_stats<EPISODE_STATS_MAX_CLASSES>, dim3(1), dim3(EPISODE_STATS_THREADS), 0, stream,
+                  E, K, rec, valid, gpow, (int)n_targets, (int)(count_first_only != 0), cls, (int)n_classes, run, counted, out);
 }
 
 int bridges_family_thresholds(const uint32_t* w_dev, int32_t C, uint64_t* thr_dev, void* stream) {

@@ -136,6 +136,33 @@ __device__ __forceinline__ int wave_min_i(int v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// One Adam step (torch.optim.Adam, amsgrad = False, weight_decay = 0, maximize = False), the operation order of torch's fused
+// kernel:
+//   m = m + (g - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;
+//   p = p - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+// Every coefficient is formed in float64 from the optimiser's float64 hyper-parameters and rounded once (1 - 0.999f is off by
+// 5e-5 relative, which would show in v); t = the number of THIS update.  The kernels that update parameters do it through this
+// struct (the tile site of k_lin_bwd<true>, mlp_kernels.hip, states the same update on loose floats), so they agree bit for bit.
+struct Adam {
+    float step_size, bc2_sqrt, w1, w2, beta2, eps;
+    __device__ __forceinline__ Adam(double lr, double beta1_d, double beta2_d, double eps_d, double t) {
+        step_size = (float)(lr / (1.0 - pow(beta1_d, t)));
+        bc2_sqrt = (float)sqrt(1.0 - pow(beta2_d, t));
+        w1 = (float)(1.0 - beta1_d); w2 = (float)(1.0 - beta2_d); beta2 = (float)beta2_d; eps = (float)eps_d;
+    }
+    __device__ __forceinline__ void apply(float& p, float g, float& m, float& v) const {
+        m = m + (g - m) * w1;
+        v = beta2 * v + w2 * g * g;
+        p = p - step_size * m / (sqrtf(v) / bc2_sqrt + eps);
+    }
+    __device__ __forceinline__ void apply(float4& p, const float4& g, float4& m, float4& v) const {
+        apply(p.x, g.x, m.x, v.x);
+        apply(p.y, g.y, m.y, v.y);
+        apply(p.z, g.z, m.z, v.z);
+        apply(p.w, g.w, m.w, v.w);
+    }
+};
+
 // Small constant tables of a task, resident in device memory.
 struct TaskTable {
     bridges_shape shapes[8];

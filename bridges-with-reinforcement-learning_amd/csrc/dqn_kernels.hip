@@ -23,49 +23,31 @@ __global__ __launch_bounds__(256) void k_soft_update(float* __restrict__ target,
         target[i] = policy[i] * tau + target[i] * omt;
 }
 
-// One Adam step (torch.optim.Adam, amsgrad = False, weight_decay = 0, maximize = False; the optimiser of
-// successor_dqn.py:640) over ONE flat float32 buffer of parameters / gradients / moments, 16 B per lane:
-//   m = m + (g - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;
-//   p = p - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
-// (the operation order of torch's fused kernel).  t = *step, a device float the caller has ALREADY incremented for this
-// step (the fused SuccessorMLP step does it in its loss kernel); the bias corrections are formed in float64.
+// One Adam step (struct Adam, bridges_device.h; the optimiser of successor_dqn.py:640) over ONE flat float32 buffer of
+// parameters / gradients / moments, 16 B per lane.  t = *step, a device float the caller has ALREADY incremented for this step
+// (the fused SuccessorMLP step does it in its loss kernel).
 // 7 x 4 B of traffic per parameter (torch's multi-tensor launch moves the same bytes at ~3.9 TB/s: 46 us for the 6.4 M
 // parameters of SuccessorMLP; this launch streams them in one grid).
 __global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, const float* __restrict__ step, double lr,
                                                    double beta1_d, double beta2_d, double eps_d) {
-    // every coefficient is formed in float64 from the optimiser's float64 hyper-parameters and rounded once (1 - 0.999f is
-    // off by 5e-5 relative, which would show in v)
-    const double t = (double)*step;
-    const float step_size = (float)(lr / (1.0 - pow(beta1_d, t)));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2_d, t));
-    const float w1 = (float)(1.0 - beta1_d), w2 = (float)(1.0 - beta2_d), beta2 = (float)beta2_d, eps = (float)eps_d;
+    const Adam adam(lr, beta1_d, beta2_d, eps_d, (double)*step);
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     float4* p4 = reinterpret_cast<float4*>(p);
     const float4* g4 = reinterpret_cast<const float4*>(g);
     float4* m4 = reinterpret_cast<float4*>(m);
     float4* v4 = reinterpret_cast<float4*>(v);
-#define ADAM_ONE(P, G, M, V)                                         \
-    do {                                                             \
-        M = M + (G - M) * w1;                                        \
-        V = beta2 * V + w2 * G * G;                                  \
-        P = P - step_size * M / (sqrtf(V) / bc2_sqrt + eps);         \
-    } while (0)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-        ADAM_ONE(pp.x, gg.x, mm.x, vv.x);
-        ADAM_ONE(pp.y, gg.y, mm.y, vv.y);
-        ADAM_ONE(pp.z, gg.z, mm.z, vv.z);
-        ADAM_ONE(pp.w, gg.w, mm.w, vv.w);
+        adam.apply(pp, gg, mm, vv);
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         float pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-        ADAM_ONE(pp, gg, mm, vv);
+        adam.apply(pp, gg, mm, vv);
         p[i] = pp; m[i] = mm; v[i] = vv;
     }
-#undef ADAM_ONE
 }
 
 // The same update over MANY tensors in one launch (the conv Q-networks: 34-60 parameter tensors of 16 .. 295 k elements, each
@@ -80,143 +62,21 @@ __global__ __launch_bounds__(256) void k_adam_multi(const bridges_adam_slot* __r
     const bridges_adam_slot s = slots[chunk_slot[blockIdx.x]];
     const int64_t base = (int64_t)chunk_off[blockIdx.x] * 1024;
     const double t = (double)*step + 1.0;
-    const float step_size = (float)(lr / (1.0 - pow(beta1_d, t)));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2_d, t));
-    const float w1 = (float)(1.0 - beta1_d), w2 = (float)(1.0 - beta2_d), beta2 = (float)beta2_d, eps = (float)eps_d;
+    const Adam adam(lr, beta1_d, beta2_d, eps_d, t);
     if (base == 0 && threadIdx.x == 0 && s.step) *s.step = (float)t;
-#define ADAM_ONE(P, G, M, V)                                         \
-    do {                                                             \
-        M = M + (G - M) * w1;                                        \
-        V = beta2 * V + w2 * G * G;                                  \
-        P = P - step_size * M / (sqrtf(V) / bc2_sqrt + eps);         \
-    } while (0)
     const int64_t i = base + 4 * (int64_t)threadIdx.x;
     const bool vec = ((((uintptr_t)s.p) | ((uintptr_t)s.g) | ((uintptr_t)s.m) | ((uintptr_t)s.v)) & 15) == 0;
     if (vec && i + 3 < s.n) {
         float4 pp = *reinterpret_cast<float4*>(s.p + i), gg = *reinterpret_cast<const float4*>(s.g + i);
         float4 mm = *reinterpret_cast<float4*>(s.m + i), vv = *reinterpret_cast<float4*>(s.v + i);
-        ADAM_ONE(pp.x, gg.x, mm.x, vv.x);
-        ADAM_ONE(pp.y, gg.y, mm.y, vv.y);
-        ADAM_ONE(pp.z, gg.z, mm.z, vv.z);
-        ADAM_ONE(pp.w, gg.w, mm.w, vv.w);
+        adam.apply(pp, gg, mm, vv);
         *reinterpret_cast<float4*>(s.p + i) = pp; *reinterpret_cast<float4*>(s.m + i) = mm; *reinterpret_cast<float4*>(s.v + i) = vv;
     } else {
         for (int64_t j = i; j < i + 4 && j < s.n; ++j) {
             float pp = s.p[j], gg = s.g[j], mm = s.m[j], vv = s.v[j];
-            ADAM_ONE(pp, gg, mm, vv);
+            adam.apply(pp, gg, mm, vv);
             s.p[j] = pp; s.m[j] = mm; s.v[j] = vv;
         }
-    }
-#undef ADAM_ONE
-}
-
-// train_policy_net target construction (successor_dqn.py:197-213, 222, 230).  One workgroup per transition:
-// segmented first-argmax over its next-action rows, then the q target and (optionally) the successor-feature
-// target row, 16 B per lane.
-__global__ __launch_bounds__(256) void k_td_target(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
-                                                   const float* __restrict__ next_q, const float* __restrict__ next_sf,
-                                                   int64_t sf_row_stride, const float* __restrict__ action_raster,
-                                                   const float* __restrict__ lin_reward, const uint8_t* __restrict__ done,
-                                                   float gamma, int sf_dim, float* __restrict__ q_target,
-                                                   float* __restrict__ sf_target, int32_t* __restrict__ argmax_row) {
-    __shared__ float s_val[256];
-    __shared__ int s_idx[256];
-    const int i = blockIdx.x, t = threadIdx.x;
-    const int lo = seg_lo[i], hi = seg_hi[i];
-    float best = -INFINITY;
-    int bidx = 0x7fffffff;
-    for (int j = lo + t; j < hi; j += 256) {
-        float v = next_q[j];
-        if (v > best || (v == best && j < bidx) || bidx == 0x7fffffff) { best = v; bidx = j; }   // NaN-free inputs
-    }
-    s_val[t] = best; s_idx[t] = bidx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            float v = s_val[t + o]; int k = s_idx[t + o];
-            if (k != 0x7fffffff && (s_idx[t] == 0x7fffffff || v > s_val[t] || (v == s_val[t] && k < s_idx[t]))) {
-                s_val[t] = v; s_idx[t] = k;
-            }
-        }
-        __syncthreads();
-    }
-    const int row = s_idx[0];
-    const bool dn = done[i] != 0;
-    const bool no_next = dn || row == 0x7fffffff;       // an empty segment has no next row: nothing of next_sf is read for it
-    if (t == 0) {
-        float nq = dn ? 0.f : s_val[0];
-        q_target[i] = lin_reward[i] + gamma * nq;
-        argmax_row[i] = row;
-    }
-    if (sf_dim > 0) {
-        const float* src = next_sf + (int64_t)row * sf_row_stride;
-        const float* ar = action_raster + (int64_t)i * sf_dim;
-        float* dst = sf_target + (int64_t)i * sf_dim;
-        const int n4 = sf_dim >> 2;
-        for (int k = t; k < n4; k += 256) {
-            float4 a = reinterpret_cast<const float4*>(ar)[k];
-            float4 s = no_next ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(src)[k];
-            float4 o;
-            o.x = a.x + gamma * s.x; o.y = a.y + gamma * s.y; o.z = a.z + gamma * s.z; o.w = a.w + gamma * s.w;
-            reinterpret_cast<float4*>(dst)[k] = o;
-        }
-        for (int k = (n4 << 2) + t; k < sf_dim; k += 256) dst[k] = ar[k] + gamma * (no_next ? 0.f : src[k]);
-    }
-}
-
-// k_td_target with a discount PER TRANSITION (n-step returns: discount[i] = gamma^h of transition i's horizon):
-//   q_target[i] = lin_reward[i] + discount[i] * q',  sf_target[i,:] = action_raster[i,:] + discount[i] * psi'.
-// Everything else is k_td_target's, statement for statement -- the first-maximum rule, the empty-segment and done rules, both
-// segment forms, the strided next_sf, argmax_row -- so a discount filled with gamma gives k_td_target's outputs bit for bit.
-__global__ __launch_bounds__(256) void k_td_target_rows(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
-                                                        const float* __restrict__ next_q, const float* __restrict__ next_sf,
-                                                        int64_t sf_row_stride, const float* __restrict__ action_raster,
-                                                        const float* __restrict__ lin_reward, const uint8_t* __restrict__ done,
-                                                        const float* __restrict__ discount, int sf_dim, float* __restrict__ q_target,
-                                                        float* __restrict__ sf_target, int32_t* __restrict__ argmax_row) {
-    __shared__ float s_val[256];
-    __shared__ int s_idx[256];
-    const int i = blockIdx.x, t = threadIdx.x;
-    const int lo = seg_lo[i], hi = seg_hi[i];
-    const float gamma = discount[i];
-    float best = -INFINITY;
-    int bidx = 0x7fffffff;
-    for (int j = lo + t; j < hi; j += 256) {
-        float v = next_q[j];
-        if (v > best || (v == best && j < bidx) || bidx == 0x7fffffff) { best = v; bidx = j; }   // NaN-free inputs
-    }
-    s_val[t] = best; s_idx[t] = bidx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            float v = s_val[t + o]; int k = s_idx[t + o];
-            if (k != 0x7fffffff && (s_idx[t] == 0x7fffffff || v > s_val[t] || (v == s_val[t] && k < s_idx[t]))) {
-                s_val[t] = v; s_idx[t] = k;
-            }
-        }
-        __syncthreads();
-    }
-    const int row = s_idx[0];
-    const bool dn = done[i] != 0;
-    const bool no_next = dn || row == 0x7fffffff;       // an empty segment has no next row: nothing of next_sf is read for it
-    if (t == 0) {
-        float nq = dn ? 0.f : s_val[0];
-        q_target[i] = lin_reward[i] + gamma * nq;
-        argmax_row[i] = row;
-    }
-    if (sf_dim > 0) {
-        const float* src = next_sf + (int64_t)row * sf_row_stride;
-        const float* ar = action_raster + (int64_t)i * sf_dim;
-        float* dst = sf_target + (int64_t)i * sf_dim;
-        const int n4 = sf_dim >> 2;
-        for (int k = t; k < n4; k += 256) {
-            float4 a = reinterpret_cast<const float4*>(ar)[k];
-            float4 s = no_next ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(src)[k];
-            float4 o;
-            o.x = a.x + gamma * s.x; o.y = a.y + gamma * s.y; o.z = a.z + gamma * s.z; o.w = a.w + gamma * s.w;
-            reinterpret_cast<float4*>(dst)[k] = o;
-        }
-        for (int k = (n4 << 2) + t; k < sf_dim; k += 256) dst[k] = ar[k] + gamma * (no_next ? 0.f : src[k]);
     }
 }
 
@@ -227,26 +87,27 @@ __device__ __forceinline__ void td_take_better(float& av, int& ak, float bv, int
     if (bk != 0x7fffffff && (ak == 0x7fffffff || bv > av || (bv == av && bk < ak))) { av = bv; ak = bk; }
 }
 
-// Double Q-learning target: k_td_target / k_td_target_rows with the row SELECTED by one value vector and VALUED by another,
+// train_policy_net target construction (successor_dqn.py:197-213, 222, 230), one workgroup per transition: the row is SELECTED
+// by one value vector and VALUED by another (double Q-learning; the plain target passes next_q for both),
 //   row = first maximum of select_q over [seg_lo[i], seg_hi[i])  (ties to the lowest row; all -inf: the first row),
 //   q_target[i] = lin_reward[i] + d_i * (done ? 0 : next_q[row]),  sf_target[i,:] = action_raster[i,:] + d_i * next_sf[row,:],
-// d_i = discount[i] (PER_ROW) or the scalar gamma.  The empty-segment and done rules, both segment forms, the strided next_sf and
-// argmax_row are k_td_target's and the epilogue is its arithmetic statement for statement, so select_q == next_q gives the
-// outputs of k_td_target (scalar) and k_td_target_rows (PER_ROW) bit for bit.
+// d_i = discount[i] (PER_ROW; n-step returns: gamma^h of transition i's horizon) or the scalar gamma.  An empty segment has no
+// row (argmax_row 0x7fffffff, q' = -inf, psi' = 0) and a done transition takes q' = 0, psi' = 0.  Every entry point that forms
+// a target launches this kernel, so select_q == next_q and a discount filled with gamma give the same bits by construction.
 // Reduction for wave64: every thread strides the segment, a wave reduces its 64 pairs by __shfl_down (offsets 32 .. 1; a lane
 // whose partner lies beyond the wave gets its own pair back, which changes nothing), the four wave results pass through LDS
-// behind ONE barrier and every thread combines the four.  Because the order of pairs is total (td_take_better) the result is the
-// one of k_td_target's LDS tree, whatever the shape of the reduction.
+// behind ONE barrier and every thread combines the four.  Because the order of pairs is total (td_take_better) the result does
+// not depend on the shape of the reduction.
 // The successor-feature row goes 16 B per lane when sf_dim and the row stride are multiples of 4 floats and the three bases are
 // 16-byte aligned, element by element otherwise (sf_dim = 6): the same float operations per element either way.
 template <bool PER_ROW>
-__global__ __launch_bounds__(256) void k_td_target_select(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
-                                                          const float* __restrict__ select_q, const float* __restrict__ next_q,
-                                                          const float* __restrict__ next_sf, int64_t sf_row_stride,
-                                                          const float* __restrict__ action_raster, const float* __restrict__ lin_reward,
-                                                          const uint8_t* __restrict__ done, const float* __restrict__ discount,
-                                                          float gamma_scalar, int sf_dim, float* __restrict__ q_target,
-                                                          float* __restrict__ sf_target, int32_t* __restrict__ argmax_row) {
+__global__ __launch_bounds__(256) void k_td_target(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
+                                                   const float* __restrict__ select_q, const float* __restrict__ next_q,
+                                                   const float* __restrict__ next_sf, int64_t sf_row_stride,
+                                                   const float* __restrict__ action_raster, const float* __restrict__ lin_reward,
+                                                   const uint8_t* __restrict__ done, const float* __restrict__ discount,
+                                                   float gamma_scalar, int sf_dim, float* __restrict__ q_target,
+                                                   float* __restrict__ sf_target, int32_t* __restrict__ argmax_row) {
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     const int i = blockIdx.x, t = threadIdx.x;
@@ -381,6 +242,27 @@ __global__ __launch_bounds__(256) void k_nstep_fold(int E, int W, int n, const d
     }
 }
 
+// acc += the rows of wt at the set pixels of one bit-packed raster, ascending p (lane l holds image row l in `mine`, rows_nz is
+// the ballot of the non-empty rows): the walk of both first-layer kernels below.
+__device__ __forceinline__ void bits_linear_add(float4& acc, uint64_t mine, uint64_t rows_nz, const float* __restrict__ wt, int d,
+                                                int col, bool act) {
+    uint64_t rem = rows_nz;
+    while (rem) {
+        const int rr = __builtin_ctzll(rem);
+        rem &= rem - 1ull;
+        uint64_t m = shfl_u64(mine, rr);                                     // uniform: the mask of image row rr
+        const float* w = wt + (size_t)rr * IMG * d + col;
+        while (m) {
+            const int cc = __builtin_ctzll(m);
+            m &= m - 1ull;
+            if (act) {
+                const float4 v = *reinterpret_cast<const float4*>(w + (size_t)cc * d);
+                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            }
+        }
+    }
+}
+
 // K8: first layer of an MLP that consumes flattened binary 64x64 rasters, fed with the bit-packed rasters themselves
 // (cv.py:95-97 concatenates block / action / reward / obstacle images and multiplies by W1; a block covers ~35 of the
 // 4096 pixels, so the product with its raster is the sum of ~35 rows of the transposed weight slice):
@@ -404,21 +286,7 @@ __global__ __launch_bounds__(256) void k_bits_linear(int n_rows, const uint64_t*
             const bool act = col < d;
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
             if (b && act) acc = *reinterpret_cast<const float4*>(b + col);
-            uint64_t rem = rows_nz;
-            while (rem) {
-                const int rr = __builtin_ctzll(rem);
-                rem &= rem - 1ull;
-                uint64_t m = shfl_u64(mine, rr);                             // uniform: the mask of image row rr
-                const float* w = wt + (size_t)rr * IMG * d + col;
-                while (m) {
-                    const int cc = __builtin_ctzll(m);
-                    m &= m - 1ull;
-                    if (act) {
-                        const float4 v = *reinterpret_cast<const float4*>(w + (size_t)cc * d);
-                        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-                    }
-                }
-            }
+            bits_linear_add(acc, mine, rows_nz, wt, d, col, act);
             if (act) *reinterpret_cast<float4*>(out + (size_t)r * d + col) = acc;
         }
     }
@@ -430,25 +298,6 @@ __global__ __launch_bounds__(256) void k_bits_linear(int n_rows, const uint64_t*
 // summed in exactly that order, pixels ascending inside an operand: the float sequence of two chained k_bits_linear launches
 // (the second with the first's output as its base, row r), so the result equals theirs bit for bit -- without the store and
 // reload of the intermediate row and the second launch.  Both row masks stay in the wave (one uint64 per lane each).
-__device__ __forceinline__ void bits_linear_add(float4& acc, uint64_t mine, uint64_t rows_nz, const float* __restrict__ wt, int d,
-                                                int col, bool act) {
-    uint64_t rem = rows_nz;
-    while (rem) {
-        const int rr = __builtin_ctzll(rem);
-        rem &= rem - 1ull;
-        uint64_t m = shfl_u64(mine, rr);                                     // uniform: the mask of image row rr
-        const float* w = wt + (size_t)rr * IMG * d + col;
-        while (m) {
-            const int cc = __builtin_ctzll(m);
-            m &= m - 1ull;
-            if (act) {
-                const float4 v = *reinterpret_cast<const float4*>(w + (size_t)cc * d);
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_bits_linear2(int n_rows, const uint64_t* __restrict__ bits_a,
                                                       const int64_t* __restrict__ row_a, const float* __restrict__ wt_a,
                                                       const uint64_t* __restrict__ bits_b, const int64_t* __restrict__ row_b,
@@ -714,21 +563,32 @@ __global__ __launch_bounds__(256) void k_record_result(int E, const float* __res
 // step index (n_blocks of s: every episode starts from the empty assembly and places one block per env-step):
 //   i == 0 restarts run[e];  run[e] += gpow[i] * (reward, lin_reward)  as float32 products and left-to-right float32 sums, no
 //   fused multiply-add (the reference's sum(gamma ** i * t.reward ...) over float32 tensors);  at done the episode's
-//   (1, run, i + 1, stable(s'), reward == n_targets) is added to out unless count_first_only and counted[e] > 0, then counted[e]++.
-// ONE workgroup: thread t walks envs t, t + 256, ...; the partials meet in a fixed-order LDS tree in f64 and thread k adds slot
-// k to out.  No atomics, so two runs on the same inputs give the same bits.
+//   (1, run, i + 1, stable(s'), reward == n_targets) is added to row cls[e] of out [n_classes, 8] unless count_first_only and
+//   counted[e] > 0, then counted[e]++.
+// cls is the class the episode was played under (per-span / per-height statistics of a task family), snapshotted before the step
+// that redraws it; a cls outside [0, n_classes) is counted in no row, run and counted advance as ever.  MAX_CLASSES = 1 is the
+// fold without classes: the class is the constant 0, cls is not read and out is one row.
+// ONE workgroup: thread t walks envs t, t + 256, ... and keeps one partial per (class, slot) in registers -- the class loop is
+// unrolled, a partial takes the add only for its own class, so the order of the adds within a class does not depend on
+// MAX_CLASSES; the classes go one after the other through a fixed-order LDS tree in f64 and thread k adds slot k to out.  No
+// atomics, so two runs on the same inputs give the same bits, and one class with cls all zero gives the bits of MAX_CLASSES = 1.
 constexpr int EPISODE_STATS_THREADS = 256;
 constexpr int EPISODE_STATS_SLOTS = 8;        // episodes, sum reward, sum lin_reward, sum num_steps, sum stable, sum success, 2 spare
+constexpr int EPISODE_STATS_USED = 6;         // slots 6 and 7 stay 0
+constexpr int EPISODE_STATS_MAX_CLASSES = 8;
 
-__global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats(int E, int K, const double* __restrict__ rec,
-                                                                         const uint8_t* __restrict__ valid, const float* __restrict__ gpow,
-                                                                         int n_targets, int count_first_only, float* __restrict__ run,
-                                                                         int32_t* __restrict__ counted, double* __restrict__ out) {
+template <int MAX_CLASSES>
+__global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats(
+        int E, int K, const double* __restrict__ rec, const uint8_t* __restrict__ valid, const float* __restrict__ gpow, int n_targets,
+        int count_first_only, const int32_t* __restrict__ cls, int n_classes, float* __restrict__ run, int32_t* __restrict__ counted,
+        double* __restrict__ out) {
     __shared__ double part[EPISODE_STATS_SLOTS][EPISODE_STATS_THREADS];
     const int t = threadIdx.x;
-    double acc[EPISODE_STATS_SLOTS];
+    double acc[MAX_CLASSES][EPISODE_STATS_USED];
 #pragma unroll
-    for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) acc[k] = 0.0;
+    for (int c = 0; c < MAX_CLASSES; ++c)
+#pragma unroll
+        for (int k = 0; k < EPISODE_STATS_USED; ++k) acc[c][k] = 0.0;
     for (int e = t; e < E; e += EPISODE_STATS_THREADS) {
         if (!valid[e]) continue;
         const double* r = rec + (size_t)e * BRIDGES_REC_WIDTH;
@@ -743,73 +603,14 @@ __global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats(int E, 
         run[2 * e] = s0;
         run[2 * e + 1] = s1;
         if (r[BRIDGES_REC_DONE] > 0.5) {
-            const int32_t c = counted[e];
-            if (!(count_first_only && c > 0)) {
-                acc[0] += 1.0;
-                acc[1] += (double)s0;
-                acc[2] += (double)s1;
-                acc[3] += (double)(i + 1);
-                acc[4] += r[BRIDGES_REC_STABLE_N] > 0.5 ? 1.0 : 0.0;
-                acc[5] += reward == (float)n_targets ? 1.0 : 0.0;
-            }
-            counted[e] = c + 1;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] = acc[k];
-    __syncthreads();
-    for (int s = EPISODE_STATS_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] += part[k][t + s];
-        }
-        __syncthreads();
-    }
-    if (t < EPISODE_STATS_SLOTS) out[t] += part[t][0];
-}
-
-// The same fold with an ended episode of env e added to row cls[e] of out [n_classes, 8] (per-span / per-height statistics of a
-// task family; cls is the class the episode was played under, snapshotted before the step that redraws it).  A cls outside
-// [0, n_classes) is counted in no row; run and counted advance as ever.  Thread t keeps one partial per (class, slot) in
-// registers -- the class loop is unrolled, a partial takes the add only for its own class, so the order of the adds within a
-// class is k_episode_stats' -- and the classes go through the same LDS tree one after the other: with one class and cls all
-// zero, out, run and counted are k_episode_stats' bit for bit.
-constexpr int EPISODE_STATS_MAX_CLASSES = 8;
-constexpr int EPISODE_STATS_USED = 6;         // slots 6 and 7 stay 0
-
-__global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats_by_class(
-        int E, int K, const double* __restrict__ rec, const uint8_t* __restrict__ valid, const float* __restrict__ gpow, int n_targets,
-        int count_first_only, const int32_t* __restrict__ cls, int n_classes, float* __restrict__ run, int32_t* __restrict__ counted,
-        double* __restrict__ out) {
-    __shared__ double part[EPISODE_STATS_SLOTS][EPISODE_STATS_THREADS];
-    const int t = threadIdx.x;
-    double acc[EPISODE_STATS_MAX_CLASSES][EPISODE_STATS_USED];
-#pragma unroll
-    for (int c = 0; c < EPISODE_STATS_MAX_CLASSES; ++c)
-#pragma unroll
-        for (int k = 0; k < EPISODE_STATS_USED; ++k) acc[c][k] = 0.0;
-    for (int e = t; e < E; e += EPISODE_STATS_THREADS) {
-        if (!valid[e]) continue;
-        const double* r = rec + (size_t)e * BRIDGES_REC_WIDTH;
-        const int i = (int)r[BRIDGES_REC_NB];
-        const int gi = i < 0 ? 0 : (i < K ? i : K - 1);
-        const float reward = (float)r[BRIDGES_REC_REWARD];
-        const float lin = (float)r[BRIDGES_REC_LIN];
-        float s0 = i == 0 ? 0.f : run[2 * e];
-        float s1 = i == 0 ? 0.f : run[2 * e + 1];
-        s0 = __fadd_rn(s0, __fmul_rn(gpow[gi], reward));
-        s1 = __fadd_rn(s1, __fmul_rn(gpow[gi], lin));
-        run[2 * e] = s0;
-        run[2 * e + 1] = s1;
-        if (r[BRIDGES_REC_DONE] > 0.5) {
             const int32_t cnt = counted[e];
             if (!(count_first_only && cnt > 0)) {
-                const int ce = cls[e];
+                const int ce = MAX_CLASSES > 1 ? cls[e] : 0;
                 const double v[EPISODE_STATS_USED] = {1.0, (double)s0, (double)s1, (double)(i + 1),
                                                       r[BRIDGES_REC_STABLE_N] > 0.5 ? 1.0 : 0.0,
                                                       reward == (float)n_targets ? 1.0 : 0.0};
 #pragma unroll
-                for (int c = 0; c < EPISODE_STATS_MAX_CLASSES; ++c)
+                for (int c = 0; c < MAX_CLASSES; ++c)
 #pragma unroll
                     for (int k = 0; k < EPISODE_STATS_USED; ++k) acc[c][k] = ce == c ? acc[c][k] + v[k] : acc[c][k];
             }
@@ -817,8 +618,8 @@ __global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats_by_clas
         }
     }
 #pragma unroll
-    for (int c = 0; c < EPISODE_STATS_MAX_CLASSES; ++c) {
-        if (c >= n_classes) break;                  // uniform: every thread sees the same n_classes
+    for (int c = 0; c < MAX_CLASSES; ++c) {
+        if (MAX_CLASSES > 1 && c >= n_classes) break;   // uniform: every thread sees the same n_classes
 #pragma unroll
         for (int k = 0; k < EPISODE_STATS_SLOTS; ++k) part[k][t] = k < EPISODE_STATS_USED ? acc[c][k < EPISODE_STATS_USED ? k : 0] : 0.0;
         __syncthreads();

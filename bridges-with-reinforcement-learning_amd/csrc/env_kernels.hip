@@ -1034,7 +1034,7 @@ __global__ __launch_bounds__(WAVE) void k_family_thresholds(const uint32_t* w, i
 }
 
 // The curriculum update.  ONE workgroup of one wave; lane k < C owns class n = n_lo + k: row n of sums [n_classes, 8] (the
-// layout of k_episode_stats_by_class: slot 0 = episodes, slot 5 = successes) and row n of state [n_classes, 2] = (ema, seen).
+// layout of k_episode_stats: slot 0 = episodes, slot 5 = successes) and row n of state [n_classes, 2] = (ema, seen).
 //   e = sums[n][0];  e >= min_episodes:  rate = sums[n][5] / e;  ema = seen ? ema + beta * (rate - ema) : rate  (every operation
 //   rounded to binary64 on its own);  seen = 1;  the row of sums is zeroed.  A row below min_episodes stays and accumulates.
 //   fail = seen ? min(max(1 - ema, 0), 1) : 1;   w[k] = w_min + (uint32)(fail * 65536.0 + 0.5)

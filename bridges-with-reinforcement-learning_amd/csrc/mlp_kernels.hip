@@ -151,8 +151,8 @@ __global__ __launch_bounds__(256) void k_lin_fwd_finish(int rows, int N, int spl
 // Adam folded into the weight-gradient jobs of a layer WITHOUT an input gradient (the first layer: nothing in the step
 // reads its weights after the forward pass, so they may change in place): the 32x32 gradient tile in the accumulators
 // goes straight into m, v and W -- the gradient never exists in memory (for SuccessorMLP's first layer that is 16.8 MB
-// not written and not read again, and 4.2 M of the 6.4 M parameters out of the separate Adam launch).  Same arithmetic as
-// k_adam_flat (dqn_kernels.hip).
+// not written and not read again, and 4.2 M of the 6.4 M parameters out of the separate Adam launch).  The update is struct
+// Adam's (bridges_device.h), as in k_adam_flat.
 struct AdamFold {
     float* W; float* bias; float* mW; float* vW; float* mb; float* vb;
     const float* step;                  // device float: number of THIS update (already incremented)
@@ -162,6 +162,8 @@ struct AdamFold {
     // any more, so the whole optimiser update rides in the last launch of the step
     float* rest_p; const float* rest_g; float* rest_m; float* rest_v; long long rest_n;
 };
+// k_lin_bwd<true> sits at its register limit (two waves per SIMD): with struct Adam at its tile site the compiler spills, so that
+// one site keeps its coefficients as loose floats and this statement of Adam::apply.
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float step_size, float bc2_sqrt, float beta2,
                                          float w1, float w2, float eps) {
     m = m + (g - m) * w1;
@@ -331,10 +333,7 @@ __global__ __launch_bounds__(ADAM ? 512 : 256) __attribute__((amdgpu_waves_per_e
     }
     job -= n_dw_jobs;
     if constexpr (ADAM) {                                          // flat Adam over the other layers' range
-        const double t = (double)*ad.step;
-        const float step_size = (float)(ad.lr / (1.0 - pow(ad.beta1, t)));
-        const float bc2_sqrt = (float)sqrt(1.0 - pow(ad.beta2, t));
-        const float w1 = (float)(1.0 - ad.beta1), w2 = (float)(1.0 - ad.beta2), b2 = (float)ad.beta2, eps = (float)ad.eps;
+        const Adam adam(ad.lr, ad.beta1, ad.beta2, ad.eps, (double)*ad.step);
         const long long n4 = ad.rest_n >> 2;                       // the range is padded to whole float4s
         const long long stride = (long long)(gridDim.x - n_dw_jobs) * blockDim.x;
         float4* p4 = reinterpret_cast<float4*>(ad.rest_p);
@@ -343,10 +342,7 @@ __global__ __launch_bounds__(ADAM ? 512 : 256) __attribute__((amdgpu_waves_per_e
         float4* v4 = reinterpret_cast<float4*>(ad.rest_v);
         for (long long i = (long long)job * blockDim.x + threadIdx.x; i < n4; i += stride) {
             float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-            adam_one(pp.x, gg.x, mm.x, vv.x, step_size, bc2_sqrt, b2, w1, w2, eps);
-            adam_one(pp.y, gg.y, mm.y, vv.y, step_size, bc2_sqrt, b2, w1, w2, eps);
-            adam_one(pp.z, gg.z, mm.z, vv.z, step_size, bc2_sqrt, b2, w1, w2, eps);
-            adam_one(pp.w, gg.w, mm.w, vv.w, step_size, bc2_sqrt, b2, w1, w2, eps);
+            adam.apply(pp, gg, mm, vv);
             p4[i] = pp; m4[i] = mm; v4[i] = vv;
         }
         return;
@@ -896,10 +892,7 @@ __global__ __launch_bounds__(1024) void k_mid_bwd(MidPtrs p) {
             // latency is the launch's critical path; the riders have ~18 us for ~12 us of streaming)
             __builtin_amdgcn_s_sleep(127);
             __builtin_amdgcn_s_sleep(127);
-            const double t = (double)*p.step;
-            const float step_size = (float)(p.lr / (1.0 - pow(p.beta1, t)));
-            const float bc2_sqrt = (float)sqrt(1.0 - pow(p.beta2, t));
-            const float w1 = (float)(1.0 - p.beta1), w2 = (float)(1.0 - p.beta2), b2 = (float)p.beta2, eps = (float)p.eps;
+            const Adam adam(p.lr, p.beta1, p.beta2, p.eps, (double)*p.step);
             const long long n4 = p.rest_n >> 2;
             const long long stride = (long long)(gridDim.x - D0 / 32) * blockDim.x;
             float4* p4 = reinterpret_cast<float4*>(p.rest_p);
@@ -908,10 +901,7 @@ __global__ __launch_bounds__(1024) void k_mid_bwd(MidPtrs p) {
             float4* v4 = reinterpret_cast<float4*>(p.rest_v);
             for (long long i = (long long)(blockIdx.x - D0 / 32) * blockDim.x + threadIdx.x; i < n4; i += stride) {
                 float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-                adam_one(pp.x, gg.x, mm.x, vv.x, step_size, bc2_sqrt, b2, w1, w2, eps);
-                adam_one(pp.y, gg.y, mm.y, vv.y, step_size, bc2_sqrt, b2, w1, w2, eps);
-                adam_one(pp.z, gg.z, mm.z, vv.z, step_size, bc2_sqrt, b2, w1, w2, eps);
-                adam_one(pp.w, gg.w, mm.w, vv.w, step_size, bc2_sqrt, b2, w1, w2, eps);
+                adam.apply(pp, gg, mm, vv);
                 p4[i] = pp; m4[i] = mm; v4[i] = vv;
             }
         }

@@ -538,7 +538,8 @@ int bridges_episode_stats(int32_t E, int32_t K, const double* rec, const uint8_t
  * out [n_classes, 8], 1 <= n_classes <= 8; cls [E] is the class the episode was played under (bridges_task_family.task_class as
  * it was BEFORE the step that ended the episode, which redraws it).  A cls[e] outside [0, n_classes) is counted in no row but
  * still advances run and counted.  One workgroup, one fixed-order reduction per row, no atomics; with n_classes = 1 and cls all
- * zero, out, run and counted are bridges_episode_stats' bit for bit. */
+ * zero, out, run and counted are bridges_episode_stats' bit for bit (both launch one kernel template: bridges_episode_stats is
+ * its instance without classes). */
 int bridges_episode_stats_by_class(int32_t E, int32_t K, const double* rec, const uint8_t* valid, const float* gpow,
                                    int32_t n_targets, int32_t count_first_only, const int32_t* cls, int32_t n_classes, float* run,
                                    int32_t* counted, double* out /* [n_classes, 8] */, void* stream);
@@ -587,7 +588,9 @@ int bridges_soft_update(float* target, const float* policy, int64_t n, float tau
  * Precondition: a transition that is not done has at least one row (seg_lo[i] < seg_hi[i]); an empty segment belongs to a done
  * transition, whose next rows are never read.  An empty segment that is NOT done is the caller's error and is marked, not
  * followed: q_target[i] = lin_reward[i] + gamma * -inf, argmax_row[i] = 0x7fffffff, and its successor-feature part is taken as
- * zero (sf_target[i,:] = action_raster[i,:]) -- no row of next_sf is read for it. */
+ * zero (sf_target[i,:] = action_raster[i,:]) -- no row of next_sf is read for it.
+ * sf_dim > 0 needs sf_dim and next_sf_row_stride to be multiples of 4 and next_sf, action_raster, sf_target 16-byte aligned (-1
+ * otherwise).  This is bridges_td_target_select with select_q = next_q behind these stricter checks: one kernel serves both. */
 int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
                       int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
                       const uint8_t* done, float gamma, int32_t sf_dim, float* q_target, float* sf_target,
@@ -597,7 +600,8 @@ int bridges_td_target(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg
  *   q_target[i] = lin_reward[i] + discount[i] * (done ? 0 : next_q[j*]),
  *   sf_target[i,:] = action_raster[i,:] + discount[i] * (done ? 0 : next_sf[j*,:]).
  * The first-maximum rule, the empty-segment and done rules, both segment forms, the strided next_sf and argmax_row are those of
- * bridges_td_target; a discount filled with gamma gives its outputs bit for bit. */
+ * bridges_td_target, and so are the alignment rules; a discount filled with gamma gives its outputs bit for bit (the same
+ * kernel, bridges_td_target_select's with select_q = next_q). */
 int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* next_q, const float* next_sf,
                            int64_t next_sf_row_stride, const float* action_raster, const float* lin_reward,
                            const uint8_t* done, const float* discount, int32_t sf_dim, float* q_target, float* sf_target,
@@ -613,7 +617,7 @@ int bridges_td_target_rows(int32_t n_trans, const int32_t* seg_lo, const int32_t
  * not 16-byte aligned are handled element by element.  An empty segment is what bridges_td_target states: argmax_row[i] =
  * 0x7fffffff, q_target[i] = lin_reward[i] + d_i * (done ? 0 : -inf), sf_target[i,:] = action_raster[i,:], and nothing of next_q or
  * next_sf is read for it.  With select_q == next_q (the same pointer or equal values) every output equals bridges_td_target's
- * (discount NULL) and bridges_td_target_rows' (discount given) bit for bit.
+ * (discount NULL) and bridges_td_target_rows' (discount given) bit for bit: the three entry points launch one kernel.
  * Returns -1 and launches nothing for: n_trans < 0 or sf_dim < 0; with n_trans > 0 a NULL seg_lo, seg_hi, select_q, next_q,
  * lin_reward, done, q_target or argmax_row; sf_dim > 0 with a NULL next_sf, action_raster or sf_target or a negative row stride;
  * a float / int32 pointer that is not 4-byte aligned.  n_trans == 0 returns 0 and launches nothing. */

@@ -406,7 +406,7 @@ def twin_adam_tail_not_updated(p, g, m, v, t, hyper=ADAM_HYPER):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# TD target: k_td_target, one workgroup of 256 threads per transition (row j of a segment sits in thread (j - lo) % 256)
+# TD target: k_td_target<PER_ROW>, one workgroup of 256 threads per transition (row j of a segment sits in thread (j - lo) % 256)
 
 TD_LENGTHS = (1, 255, 256, 257, 513, 700)      # below, at and above one stride of the 256 threads; two and three strides
 TD_SF_DIMS = (0, 4, 64, 4096)

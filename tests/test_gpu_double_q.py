@@ -74,6 +74,7 @@ def test_kernel_on_the_probe(sf_dim, strided, form):
 @pytest.mark.parametrize("form", ["scalar", "rows"])
 @pytest.mark.parametrize("sf_dim", [0, 4, 64, 4096])
 def test_select_q_equal_to_next_q_is_the_plain_target_bit_for_bit(sf_dim, form):
+    # both sides launch one kernel (k_td_target<PER_ROW>) now; the independent evidence is test_gpu_twin_kernels_golden.py
     for strided in (True, False):
         pr = Q.select_probe(sf_dim, DEV, strided=strided)
         d = GAMMA if form == "scalar" else row_discounts(len(pr["lo"]), GAMMA).to(DEV)

@@ -259,6 +259,7 @@ def test_episode_stats_by_class_against_the_restatement(count_first_only):
     assert vals["episodes"] == sum(len(e) for e in ref.episodes) and [c["episodes"] for c in vals["by_class"]] == [len(e) for e in ref.episodes]
     assert vals["by_class"][3]["success_rate"] is None and float(st.out_by_class.abs().sum()) == 0.0
     # one class, cls all zero: bridges_episode_stats bit for bit
+    # (both sides are k_episode_stats<MAX_CLASSES> now; the independent evidence is test_gpu_twin_kernels_golden.py)
     from bridges_hip import ops
     one = EpisodeStats(E, K, gamma, n_targets, dev, count_first_only=count_first_only)
     out1, run1 = torch.zeros((1, 8), dtype=torch.float64, device=dev), torch.zeros((E, 2), dtype=torch.float32, device=dev)

@@ -3,7 +3,7 @@
 fused Adam, against the autograd step + fused Adam.  Under rocprofv3 --kernel-trace the kernel list of either is visible.
 Usage: python tools/mlp_step_bench.py [--autograd] [--replays 400] [--batch 32]
        python tools/mlp_step_bench.py --obstacle_bits     (times the two kernels of per-env obstacles alone, see obstacle_bits_lines)
-       python tools/mlp_step_bench.py --td_select         (times the double-Q target kernel against bridges_td_target, see td_select_lines)"""
+       python tools/mlp_step_bench.py --td_select         (times bridges_td_target and bridges_td_target_select, see td_select_lines)"""
 import argparse
 import os
 import sys
@@ -59,14 +59,16 @@ def obstacle_bits_lines(dev, B=32, n_b=25, E=4096, hidden=256, reps=50):
 
 
 def td_select_lines(dev, B=32, n_b=25, rounds=15, per_graph=20):
-    """k_td_target_select (dqn_ops.td_target(select_q=...)) beside k_td_target (the same call without select_q) on the same
-    segments, device time per launch.  Shapes: n_b * B transitions whose segments are the candidate sets of a tower-4 rollout
+    """bridges_td_target_select (dqn_ops.td_target(select_q=...)) beside bridges_td_target (the same call without select_q) on
+    the same segments, device time per launch.  BOTH COLUMNS TIME ONE KERNEL, k_td_target<false> (the plain entry point passes
+    next_q as select_q): the tool serves to compare a tree with its parent -- run it in both checkouts, alternating, and hold
+    a column against the same column of the other -- and the difference between its own two columns is its noise.  Shapes: n_b * B transitions whose segments are the candidate sets of a tower-4 rollout
     (an env of n_b * B envs after 6 lock-steps of random actions), and the same number of transitions on 700-row segments
     (the longest of the conformance probe, tests/mlp_conformance.td_probe), eight distinct ones shared as (lo, hi) pairs; each
     with sf_dim = 0 (the launch the loop makes: rows only, the successor features follow for the selected rows) and with
     sf_dim = 4096.  A launch is timed as 1 / per_graph of a replayed HIP graph of per_graph launches, between HIP events; the two
-    kernels ALTERNATE for `rounds` rounds and the line gives the median and the range over the rounds of each -- the range of
-    bridges_td_target, unchanged since before this kernel existed, is the run-to-run spread to hold the difference against."""
+    calls ALTERNATE for `rounds` rounds and the line gives the median and the range over the rounds of each -- the range is the
+    run-to-run spread to hold a difference between two trees against."""
     import statistics
     from bridges_hip import dqn_ops
     from bridges_hip.shapes import load_urdf
@@ -131,7 +133,7 @@ def td_select_lines(dev, B=32, n_b=25, rounds=15, per_graph=20):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--td_select", action="store_true",
-                    help="time the double-Q target kernel (k_td_target_select) against bridges_td_target at the same shapes and exit")
+                    help="time bridges_td_target and bridges_td_target_select (one kernel, k_td_target) at the same shapes and exit")
     ap.add_argument("--obstacle_bits", action="store_true",
                     help="time the two kernels of per-env obstacles (k_bits_linear2, k_mlp_input with obstacle bits) alone and exit")
     ap.add_argument("--autograd", action="store_true")

@@ -26,6 +26,10 @@ static int fail_arg(const char* what) {
     snprintf(g_err, sizeof(g_err), "bad argument: %s", what);
     return BRIDGES_E_ARG;
 }
+static int fail_arg(const char* who, const char* what) {
+    snprintf(g_err, sizeof(g_err), "bad argument: %s: %s", who, what);
+    return BRIDGES_E_ARG;
+}
 #define HIP_TRY(x)                                        \
     do {                                                  \
         hipError_t e_ = (x);                              \
@@ -489,6 +493,7 @@ int bridges_place(const bridges_shape* shapes_dev, int32_t n, const double* fram
                   const int32_t* face, const double* ox, const double* oy, double* pose, double* verts, void* stream) {
     if (n < 0 || !shapes_dev) return fail_arg("bridges_place");
     if (n == 0) return BRIDGES_OK;
+    if (!frame1 || !shape_id || !face || !ox || !oy || !pose || !verts) return fail_arg("bridges_place: NULL array with n > 0");
     return launch("k_place", k_place, dim3(ceil_div(n, 256)), dim3(256), 0, stream, shapes_dev, n, frame1, shape_id, face, ox, oy,
                   pose, verts);
 }
@@ -499,6 +504,9 @@ int bridges_create_block(const bridges_shape* shapes_dev, int32_t n, const doubl
                          double* target_frame_out, void* stream) {
     if (n < 0 || !shapes_dev) return fail_arg("bridges_create_block");
     if (n == 0) return BRIDGES_OK;
+    // target_verts / target_shape are read only for items with target_face >= 0, which the host cannot see
+    if (!target_face || !shape_id || !face || !ox || !oy || !pose || !verts)
+        return fail_arg("bridges_create_block: NULL array with n > 0");
     return launch("k_create_block", k_create_block, dim3(ceil_div(n, 256)), dim3(256), 0, stream, shapes_dev, n, target_verts,
                   target_shape, target_face, shape_id, face, ox, oy, pose, verts, target_frame_out);
 }
@@ -507,6 +515,7 @@ int bridges_pose_block(const bridges_shape* shapes_dev, int32_t n, const int32_t
                        double* verts, void* stream) {
     if (n < 0 || !shapes_dev) return fail_arg("bridges_pose_block");
     if (n == 0) return BRIDGES_OK;
+    if (!shape_id || !pose || !verts) return fail_arg("bridges_pose_block: NULL array with n > 0");
     return launch("k_pose_block", k_pose_block, dim3(ceil_div(n, 256)), dim3(256), 0, stream, shapes_dev, n, shape_id, pose, verts);
 }
 
@@ -514,6 +523,7 @@ int bridges_face_frames(const bridges_shape* shapes_dev, int32_t n, const int32_
                         double* frames, void* stream) {
     if (n < 0 || !shapes_dev) return fail_arg("bridges_face_frames");
     if (n == 0) return BRIDGES_OK;
+    if (!shape_id || !verts || !frames) return fail_arg("bridges_face_frames: NULL array with n > 0");
     return launch("k_face_frames", k_face_frames, dim3(ceil_div(n, 256)), dim3(256), 0, stream, shapes_dev, n, shape_id, verts, frames);
 }
 
@@ -521,6 +531,8 @@ int bridges_contains_points(const bridges_shape* shapes_dev, int32_t shape_id, c
                             const double* points, uint8_t* inside, void* stream) {
     if (n < 0 || !shapes_dev) return fail_arg("bridges_contains_points");
     if (n == 0) return BRIDGES_OK;
+    if (shape_id < 0) return fail_arg("bridges_contains_points: shape_id < 0");
+    if (!verts || !points || !inside) return fail_arg("bridges_contains_points: NULL array with n > 0");
     return launch("k_contains_points", k_contains_points, dim3(ceil_div(n, 256)), dim3(256), 0, stream, shapes_dev, shape_id, verts,
                   n, points, inside);
 }
@@ -534,19 +546,26 @@ int bridges_render_blocks(const bridges_shape* shapes_dev, int32_t n, const doub
                   shape_id, grid_x, W, grid_y, H, out);
 }
 
-int bridges_raster_sized(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
-                         const double* grid_x, const double* grid_y, int32_t size, uint64_t* bits, float* img,
-                         void* stream) {
-    if (n < 0 || !shapes_dev) return fail_arg("bridges_raster");
-    if (size < 2 || size > IMG) return fail_arg("bridges_raster: image size must be 2..64");
+// bridges_raster_sized and bridges_raster; `who` is the entry point an argument error names
+static int raster_sized(const char* who, const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
+                        const double* grid_x, const double* grid_y, int32_t size, uint64_t* bits, float* img, void* stream) {
+    if (n < 0 || !shapes_dev) return fail_arg(who);
+    if (size < 2 || size > IMG) return fail_arg(who, "image size must be 2..64");
     if (n == 0) return BRIDGES_OK;
+    if (!verts || !shape_id || !grid_x || !grid_y) return fail_arg(who, "NULL array with n > 0");     // bits / img: either may be NULL
     return launch("k_raster_generic", k_raster_generic, dim3(grid_for_waves(n)), dim3(256), 0, stream, shapes_dev, n, verts, shape_id,
                   grid_x, grid_y, (int)size, bits, img);
 }
 
+int bridges_raster_sized(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
+                         const double* grid_x, const double* grid_y, int32_t size, uint64_t* bits, float* img,
+                         void* stream) {
+    return raster_sized("bridges_raster_sized", shapes_dev, n, verts, shape_id, grid_x, grid_y, size, bits, img, stream);
+}
+
 int bridges_raster(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
                    const double* grid_x, const double* grid_y, uint64_t* bits, float* img, void* stream) {
-    return bridges_raster_sized(shapes_dev, n, verts, shape_id, grid_x, grid_y, IMG, bits, img, stream);
+    return raster_sized("bridges_raster", shapes_dev, n, verts, shape_id, grid_x, grid_y, IMG, bits, img, stream);
 }
 
 int bridges_action_features(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,

@@ -327,29 +327,34 @@ int bridges_env_set_family_thresholds(bridges_env* env, const uint64_t* thr_dev 
 /* --- stand-alone operators (same kernels, caller-shaped batches) ------------ */
 /* K1: create_block / align_frames_2d (gym_env.py:204-216, geometry.py:39-50).
  * frame1: [n,6] target frame (c.xz, t.xz, n.xz); shape_id,face: [n]; ox,oy: [n]
- * -> pose [n,4], verts [n,6,2]. */
+ * -> pose [n,4], verts [n,6,2].  A NULL array with n > 0 returns -1 and launches nothing. */
 int bridges_place(const bridges_shape* shapes_dev, int32_t n, const double* frame1, const int32_t* shape_id,
                   const int32_t* face, const double* ox, const double* oy, double* pose, double* verts,
                   void* stream);
 /* K1 as AssemblyGym.create_block (gym_env.py:204-216): target = floor (target_face[i] < 0) or face target_face[i]
- * of a posed block (target_verts [n,6,2], target_shape [n]).  target_frame_out [n,6] may be NULL. */
+ * of a posed block (target_verts [n,6,2], target_shape [n]; read only for items with target_face[i] >= 0, so they may be
+ * NULL when every target is the floor).  target_frame_out [n,6] may be NULL.  A NULL target_face, shape_id, face, ox, oy, pose or
+ * verts with n > 0 returns -1 and launches nothing. */
 int bridges_create_block(const bridges_shape* shapes_dev, int32_t n, const double* target_verts,
                          const int32_t* target_shape, const int32_t* target_face, const int32_t* shape_id,
                          const int32_t* face, const double* ox, const double* oy, double* pose, double* verts,
                          double* target_frame_out, void* stream);
-/* Block.__init__ (assembly_env.py:146-153): world vertices of shapes posed by (x, z, cos, sin). */
+/* Block.__init__ (assembly_env.py:146-153): world vertices of shapes posed by (x, z, cos, sin): shape_id [n], pose [n,4] ->
+ * verts [n,6,2] (slots >= nv are 0).  A NULL array with n > 0 returns -1 and launches nothing. */
 int bridges_pose_block(const bridges_shape* shapes_dev, int32_t n, const int32_t* shape_id, const double* pose,
                        double* verts, void* stream);
-/* Shape.get_face_frame_2d on posed blocks (assembly_env.py:118-124): frames [n,6,6] = centre.xz, x-axis.xz, normal.xz. */
+/* Shape.get_face_frame_2d on posed blocks (assembly_env.py:118-124): frames [n,6,6] = centre.xz, x-axis.xz, normal.xz (slots
+ * >= nv are 0).  A NULL array with n > 0 returns -1 and launches nothing. */
 int bridges_face_frames(const bridges_shape* shapes_dev, int32_t n, const int32_t* shape_id, const double* verts,
                         double* frames, void* stream);
 /* Shape.contains_2d (assembly_env.py:126-137) of ONE posed block for n arbitrary points (x, z):
- * verts [6,2], points [n,2] f64 -> inside [n] u8. */
+ * verts [6,2], points [n,2] f64 -> inside [n] u8.  A NULL array with n > 0, or shape_id < 0, returns -1 and launches nothing. */
 int bridges_contains_points(const bridges_shape* shapes_dev, int32_t shape_id, const double* verts, int32_t n,
                             const double* points, uint8_t* inside, void* stream);
 /* K4: render_blocks_2d (rendering.py:105-113) of n posed outlines, one image each.
  * verts [n,6,2] world vertices in shape-vertex order, shape_id [n], grid_x/grid_y [64] DEVICE
- * -> bits [n,64] and/or f32 [n,64,64] (either may be NULL). */
+ * -> bits [n,64] and/or f32 [n,64,64] (either may be NULL).  A NULL verts, shape_id, grid_x or grid_y with n > 0 returns -1 and
+ * launches nothing. */
 int bridges_raster(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
                    const double* grid_x, const double* grid_y, uint64_t* bits, float* img, void* stream);
 /* render_blocks_2d (rendering.py:105-113) at any image size (the reference's default is 512 x 512): the UNION of n posed
@@ -358,7 +363,8 @@ int bridges_raster(const bridges_shape* shapes_dev, int32_t n, const double* ver
 int bridges_render_blocks(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
                           const double* grid_x, int32_t W, const double* grid_y, int32_t H, uint8_t* out, void* stream);
 /* The same for S x S images, 2 <= S <= 64 (render_blocks_2d's img_size argument, rendering.py:105): grid_x/grid_y
- * hold S values; the outputs keep the 64-word / 64x64 layout, the image is the top-left S x S corner, the rest 0. */
+ * hold S values; the outputs keep the 64-word / 64x64 layout, the image is the top-left S x S corner, the rest 0.  A NULL verts,
+ * shape_id, grid_x or grid_y with n > 0 returns -1 and launches nothing. */
 int bridges_raster_sized(const bridges_shape* shapes_dev, int32_t n, const double* verts, const int32_t* shape_id,
                          const double* grid_x, const double* grid_y, int32_t size, uint64_t* bits, float* img,
                          void* stream);

@@ -448,7 +448,13 @@ int bridges_sigmoid_dot_rows(int32_t n_rows, const float* d, int64_t row_stride,
  * is_static)
  * -> stable [n] u8, info [n,8] f64 (phase-1 objective, n_interfaces, pivots, error, shader cycles spent in
  *    interface detection, shader cycles spent in the LP, 0, 0).
- * lp_ws: [n, lp_ws_stride] doubles, lp_ws_stride >= 9*MAX_INTERFACES + (3K+2)*(4*MAX_INTERFACES+3). */
+ * lp_ws: [n, lp_ws_stride] doubles, lp_ws_stride >= 9*MAX_INTERFACES + (3K+2)*(4*MAX_INTERFACES+3).
+ * On return row e of lp_ws begins with the contact list found for assembly e (the rest of the row is the tableau overflow
+ * area, scratch): 8*MAX_INTERFACES doubles of if_geom (p_lo.xz, p_hi.xz, n.xz, t.xz per interface, the layout of
+ * bridges_env_buffers.if_geom), then MAX_INTERFACES int32 pairs (body A with -1 for the floor, body B), i.e. another
+ * MAX_INTERFACES doubles.  Interfaces are ordered by (body B, body A, face of A, face of B); only the first info[1] entries
+ * are valid, and when more than MAX_INTERFACES contacts exist the first MAX_INTERFACES are kept and info[3] is set.
+ * bridges_stability_penalty leaves the same list. */
 int bridges_stability(const bridges_shape* shapes_dev, int32_t n, int32_t K, const double* pose,
                       const double* verts, const int32_t* shape_id, const int32_t* n_blocks,
                       const uint32_t* fixed_mask, double mu, double density, double floor_half_width,

@@ -307,6 +307,8 @@ SIGNATURES = {
     "bridges_priority_sample_scratch": [i64, C.POINTER(i64)],
     "bridges_priority_sample": [i64, i32, i32, vp, f64, i64, vp, vp, vp, i64, vp],
     "bridges_priority_update": [i64, i32, i32, vp, i64, vp, vp, vp, vp],
+    "bridges_priority_weights": [i64, i64, i64, vp, f64, vp, i64, vp, vp],
+    "bridges_successor_loss_weighted": [i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
 }
 
 

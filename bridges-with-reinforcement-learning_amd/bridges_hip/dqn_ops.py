@@ -165,6 +165,20 @@ def priority_update_(rec, n_rec, col, idx, q_sa, q_target):
     return rec
 
 
+def priority_weights(idx, n_rec, batch, beta, scratch):
+    """The importance-sampling weights of the draws ``idx`` [n] int64 (bridges_priority_weights): ``scratch`` as priority_sample
+    left it for the same ``n_rec`` (its masses are read, nothing is written).  Every ``batch`` consecutive draws are normalised
+    by their own maximum: weight = pow(min mass of the batch / mass, beta) -> [n] float32, the largest of every batch exactly 1;
+    an index outside [0, n_rec) gets 0.  One launch, no host wait, the same bits on every call."""
+    L = abi.require_gpu()
+    assert idx.dtype == torch.int64 and idx.is_contiguous()
+    assert scratch.dtype == torch.float64 and scratch.is_contiguous() and scratch.device == idx.device
+    weight = torch.empty(idx.numel(), dtype=torch.float32, device=idx.device)
+    abi.check(L.bridges_priority_weights(int(n_rec), idx.numel(), int(batch), _ptr(idx), float(beta), _ptr(scratch), scratch.numel(),
+                                         _ptr(weight), _stream()), "bridges_priority_weights")
+    return weight
+
+
 def soft_update_(target, policy, tau):
     """target <- policy * tau + target * (1 - tau) in place (successor_dqn.py:280-288); float32 contiguous tensors."""
     L = abi.require_gpu()

@@ -271,7 +271,10 @@ class FusedSuccessorStep:
                                    f"({(self.lr, self.beta1, self.beta2, self.eps)} -> {now}): rebuild the step "
                                    "(robotoddler.training.train_step.release(policy_net): the next call captures it afresh)")
 
-    def launch(self, counter, block_all, action_all, binary_all, reward, obstacle, q_target_all, sf_target_all, losses):
+    def launch(self, counter, block_all, action_all, binary_all, reward, obstacle, q_target_all, sf_target_all, losses,
+               weight_all=None):
+        """``weight_all`` [n] float32 (None: the unweighted step, the call sequence it always was): an importance-sampling weight
+        per transition of the per-call arrays, addressed as the targets are; the loss launch is bridges_successor_loss_weighted."""
         L, rows, px, nf, B = self.L, self.rows, self.px, self.nf, self.batch
         st = _stream()
         for t in (block_all, action_all, binary_all, reward):
@@ -314,7 +317,12 @@ class FusedSuccessorStep:
                      None if log_in_backward else _ptr(losses), losses.numel(),
                      None if log_in_backward else _ptr(counter), None if log_in_backward else _ptr(self.ticket),
                      _ptr(self.adam_step) if (self.fused_adam and not log_in_backward) else None, st)
-        if stride:
+        if weight_all is not None:
+            assert weight_all.dtype == torch.float32 and weight_all.is_contiguous()
+            assert weight_all.numel() >= block_all.reshape(-1, px).shape[0], "one weight per transition of the per-call arrays"
+            abi.check(L.bridges_successor_loss_weighted(B, rows, px, nf, _ptr(self.acts[-1]), _ptr(reward), stride, _ptr(counter),
+                                                        *loss_tail[:-1], _ptr(weight_all), st), "bridges_successor_loss_weighted")
+        elif stride:
             abi.check(L.bridges_successor_loss_rows(B, rows, px, nf, _ptr(self.acts[-1]), _ptr(reward), stride, _ptr(counter), *loss_tail),
                       "bridges_successor_loss_rows")
         else:

@@ -759,6 +759,25 @@ int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, 
                   rec, n, idx, q_sa, q_target);
 }
 
+int bridges_priority_weights(int64_t n_rec, int64_t n_draws, int64_t batch, const int64_t* idx, double beta, const double* scratch,
+                             int64_t scratch_doubles, float* weight, void* stream) {
+    if (n_draws < 0) return fail_arg("bridges_priority_weights: negative count");
+    if (n_draws == 0) return BRIDGES_OK;
+    if (n_rec <= 0 || n_rec > BRIDGES_PRIORITY_MAX_ROWS) return fail_arg("bridges_priority_weights: n_rec must be 1..BRIDGES_PRIORITY_MAX_ROWS");
+    if (batch <= 0 || batch > INT32_MAX || n_draws % batch != 0) return fail_arg("bridges_priority_weights: n_draws must be a multiple of batch >= 1");
+    if (n_draws / batch > INT32_MAX) return fail_arg("bridges_priority_weights: more batches than a grid holds");
+    if (!(beta >= 0.0 && beta <= 1.0)) return fail_arg("bridges_priority_weights: beta must lie in [0, 1]");
+    if (!idx || !scratch || !weight) return fail_arg("bridges_priority_weights: null pointer");
+    if (!aligned(8, idx, scratch) || !aligned(4, weight)) return fail_arg("bridges_priority_weights: misaligned pointer");
+    int64_t need = 0;
+    if (int rc = bridges_priority_sample_scratch(n_rec, &need)) return rc;
+    if (scratch_doubles < need) return fail_arg("bridges_priority_weights: scratch too small (bridges_priority_sample_scratch)");
+    const int mode = beta == 0.0 ? 0 : (beta == 1.0 ? 1 : 2);
+    // one workgroup per batch; the masses are the first chunks * PRIO_CHUNK doubles of the sampler's scratch
+    return launch("k_priority_weights", k_priority_weights, dim3((unsigned)(n_draws / batch)), dim3(256), 0, stream, n_rec, (int)batch, idx,
+                  scratch, beta, mode, weight);
+}
+
 int bridges_bits_discounted_sum(int32_t n, const uint64_t* bits, int64_t n_rows, const int64_t* first, const int32_t* h, float gamma,
                                 float* sum, float* disc, void* stream) {
     if (n < 0 || n_rows < 0 || (n > 0 && (!bits || !first || !h || !disc))) return fail_arg("bridges_bits_discounted_sum");
@@ -1270,12 +1289,36 @@ int bridges_successor_loss_rows(int32_t batch, int32_t rows, int32_t px, int32_t
     // with a ticket word (zero before the first call; the kernel re-arms it) the logging happens inside the loss kernel
     if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_successor_loss_rows: reward_stride must be 0 or px");
     int64_t* const inc = ticket ? counter_inc : (int64_t*)nullptr;
-    if (int rc = reward_stride ? launch("k_successor_loss<rows>", k_successor_loss<true>, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch,
+    if (int rc = reward_stride ? launch("k_successor_loss<rows>", k_successor_loss<true, false>, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch,
                                         px, nf, y, reward, counter, q_target_all, sf_target_all, use_q, use_sf, dy, loss_rows, q_out,
-                                        losses, n_losses, inc, ticket, adam_step)
-                               : launch("k_successor_loss", k_successor_loss<false>, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch,
+                                        losses, n_losses, inc, ticket, adam_step, (const float*)nullptr)
+                               : launch("k_successor_loss", k_successor_loss<false, false>, dim3(rows), dim3(LOSS_THREADS), 0, stream, batch,
                                         px, nf, y, reward, counter, q_target_all, sf_target_all, use_q, use_sf, dy, loss_rows, q_out,
-                                        losses, n_losses, inc, ticket, adam_step))
+                                        losses, n_losses, inc, ticket, adam_step, (const float*)nullptr))
+        return rc;
+    if (ticket || !losses || !counter_inc) return BRIDGES_OK;
+    return launch("k_loss_log", k_loss_log, dim3(1), dim3(64), 0, stream, batch, loss_rows, losses, n_losses, counter_inc);
+}
+
+int bridges_successor_loss_weighted(int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* y, const float* reward,
+                                    int64_t reward_stride, const int64_t* counter, const float* q_target_all,
+                                    const float* sf_target_all, int32_t use_q, int32_t use_sf, float* dy, float* loss_rows,
+                                    float* q_out, float* losses, int32_t n_losses, int64_t* counter_inc, int32_t* ticket,
+                                    float* adam_step, const float* weight_all, void* stream) {
+    if (batch <= 0 || rows < batch || px <= 0 || nf < 0 || !y || !reward || !counter || !dy || !loss_rows || !q_out)
+        return fail_arg("bridges_successor_loss_weighted");
+    if (!weight_all) return fail_arg("bridges_successor_loss_weighted: weight missing");
+    if ((use_q && !q_target_all) || (use_sf && !sf_target_all)) return fail_arg("bridges_successor_loss_weighted: target missing");
+    if (ticket && !counter_inc) return fail_arg("bridges_successor_loss_weighted: a ticket needs counter_inc");
+    if (adam_step && !ticket) return fail_arg("bridges_successor_loss_weighted: adam_step is advanced by the ticket holder");
+    if (!reward_stride_ok(reward_stride, px)) return fail_arg("bridges_successor_loss_weighted: reward_stride must be 0 or px");
+    int64_t* const inc = ticket ? counter_inc : (int64_t*)nullptr;
+    if (int rc = reward_stride ? launch("k_successor_loss<rows, weighted>", k_successor_loss<true, true>, dim3(rows), dim3(LOSS_THREADS), 0,
+                                        stream, batch, px, nf, y, reward, counter, q_target_all, sf_target_all, use_q, use_sf, dy,
+                                        loss_rows, q_out, losses, n_losses, inc, ticket, adam_step, weight_all)
+                               : launch("k_successor_loss<weighted>", k_successor_loss<false, true>, dim3(rows), dim3(LOSS_THREADS), 0,
+                                        stream, batch, px, nf, y, reward, counter, q_target_all, sf_target_all, use_q, use_sf, dy,
+                                        loss_rows, q_out, losses, n_losses, inc, ticket, adam_step, weight_all))
         return rc;
     if (ticket || !losses || !counter_inc) return BRIDGES_OK;
     return launch("k_loss_log", k_loss_log, dim3(1), dim3(64), 0, stream, batch, loss_rows, losses, n_losses, counter_inc);

@@ -482,9 +482,12 @@ __device__ __forceinline__ void loss_log_ticket(int batch, float* loss_rows, flo
 //   loss   = [use_q] mean_b (q - q_t)^2 + [use_sf] mean_b mean_j (psi0 - sf_t)^2
 //   dy     = d loss / d y.  One workgroup per batch row: the q reduction and the gradient that needs it stay together.
 // PER_ROW: `reward` is [n][px], one map per transition of the per-call arrays (row src, as the targets are addressed).
+// WEIGHTED: weight_all [n], one importance-sampling weight per transition (row src likewise; bridges_priority_weights): row b's
+// share of the loss and its two finished gradient coefficients, dq and csf, are each multiplied by w_b once -- w == 1 gives the
+// bits of the unweighted kernel --, q_out stays the unweighted q and rows b >= batch are untouched by it.
 #define LOSS_THREADS 1024
 #define LOSS_CACHE 4                    // pixels per thread kept in registers between the two passes (64x64 / 1024)
-template <bool PER_ROW>
+template <bool PER_ROW, bool WEIGHTED>
 __global__ __launch_bounds__(LOSS_THREADS) void k_successor_loss(int batch, int px, int nf, const float* __restrict__ y,
                                                                  const float* __restrict__ reward,
                                                                  const int64_t* __restrict__ counter,
@@ -494,7 +497,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_successor_loss(int batch, int 
                                                                  float* __restrict__ loss_rows, float* __restrict__ q_out,
                                                                  float* __restrict__ losses, int n_losses,
                                                                  int64_t* __restrict__ counter_inc, int32_t* __restrict__ ticket,
-                                                                 float* __restrict__ adam_step) {
+                                                                 float* __restrict__ adam_step,
+                                                                 const float* __restrict__ weight_all) {
     __shared__ double s_q[LOSS_THREADS / 64], s_l[LOSS_THREADS / 64];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int N = 2 * px + 2 * nf;
@@ -539,8 +543,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_successor_loss(int batch, int 
     for (int w = 0; w < LOSS_THREADS / 64; ++w) { qd += s_q[w]; ld += s_l[w]; }
     const float q = (float)qd, lsf = (float)ld;
     const float inv_b = 1.f / (float)batch;
-    const float dq = use_q ? 2.f * (q - q_target_all[src]) * inv_b : 0.f;
-    const float csf = 2.f * inv_b / (float)px;
+    float dq = use_q ? 2.f * (q - q_target_all[src]) * inv_b : 0.f;
+    float csf = 2.f * inv_b / (float)px;
+    if constexpr (WEIGHTED) { const float w = weight_all[src]; dq *= w; csf *= w; }
     // pass 2: d loss / d psi
 #pragma unroll
     for (int i = 0; i < LOSS_CACHE; ++i) {
@@ -563,6 +568,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_successor_loss(int batch, int 
         float l = 0.f;
         if (use_q) { const float d = q - q_target_all[src]; l += d * d * inv_b; }
         if (use_sf) l += lsf * inv_b / (float)px;
+        if constexpr (WEIGHTED) l *= weight_all[src];
         __hip_atomic_store(&loss_rows[b], l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // write-through: read by the last arriver
         q_out[b] = q;
     }

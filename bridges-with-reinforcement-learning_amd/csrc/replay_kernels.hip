@@ -1,5 +1,6 @@
 // K8: prioritised replay on the device (robotoddler/training/records.py, ReplayRing.sample_prioritized / update_priorities):
-// the inverse-CDF draw over the priority column of the ring and the write-back of refreshed priorities.
+// the inverse-CDF draw over the priority column of the ring, the write-back of refreshed priorities and the importance-sampling
+// weights of the draws (ReplayRing.sample_weights).
 #include "bridges_device.h"
 
 namespace bridges {
@@ -115,6 +116,38 @@ __global__ __launch_bounds__(256) void k_priority_update(int64_t n_rec, int W, i
         __syncthreads();
     }
     if (last) rec[mine * W + col] = (double)fabsf(q_sa[j] - q_target[j]);
+}
+
+// The importance-sampling weights of the draws (ReplayRing.sample_weights): w_j = (n_rec * m_idx[j] / total)^(-beta), every batch
+// of `batch` consecutive draws divided by its own maximum -- n_rec and total cancel: w_j = pow(min_k m_idx[k] / m_idx[j], beta), k
+// over the batch of j.  `mass` is what k_priority_mass left in the sampler's scratch: the distribution the draws were made from,
+// whatever k_priority_update has written to the record column since.  One workgroup per batch, thread t takes draws t, t + 256, ..;
+// the minimum is a DPP tree per wave and the four wave results through LDS (a minimum has no order: the same bits on every call,
+// no atomics).  float64 throughout, one rounding to float32.  mode 0: beta == 0 (all ones), 1: beta == 1 (the quotient), 2: pow --
+// prio_mass's switch.  An index outside [0, n_rec) takes weight 0 and no part in the minimum (k_priority_update's stance).
+__global__ __launch_bounds__(256) void k_priority_weights(int64_t n_rec, int batch, const int64_t* __restrict__ idx,
+                                                          const double* __restrict__ mass, double beta, int mode,
+                                                          float* __restrict__ weight) {
+    __shared__ double wave_part[256 / WAVE];
+    const int64_t base = (int64_t)blockIdx.x * batch;
+    double lo = INFINITY;                                // masses are finite and positive: never NaN
+    for (int k = threadIdx.x; k < batch; k += 256) {
+        const int64_t i = idx[base + k];
+        if (i >= 0 && i < n_rec) lo = fmin(lo, mass[i]);
+    }
+    lo = wave_min_d(lo);                                 // every thread is back here: all 64 lanes of the wave take part
+    if ((threadIdx.x & (WAVE - 1)) == 0) wave_part[threadIdx.x / WAVE] = lo;
+    __syncthreads();
+    lo = fmin(fmin(wave_part[0], wave_part[1]), fmin(wave_part[2], wave_part[3]));
+    for (int k = threadIdx.x; k < batch; k += 256) {
+        const int64_t i = idx[base + k];
+        float w = 0.f;
+        if (i >= 0 && i < n_rec) {
+            const double r = lo / mass[i];               // in (0, 1]; exactly 1 for the row(s) that hold the minimum
+            w = mode == 0 ? 1.f : (float)(mode == 1 ? r : pow(r, beta));
+        }
+        weight[base + k] = w;
+    }
 }
 
 }  // namespace bridges

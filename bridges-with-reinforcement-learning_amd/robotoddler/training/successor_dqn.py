@@ -551,12 +551,19 @@ def add_priority_arguments(p, prioritized_flag=False):
                    help="Vectorised loop with --prioritized_replay, one rank: after every lock-step's target pass write "
                         "|q(s,a) - q_target| of the sampled transitions back as their priorities (rows keep the rollout's TD error "
                         "until they are first sampled). One more policy-net forward over the sampled rows per lock-step.")
+    p.add_argument("--priority_beta", type=float, default=argparse.SUPPRESS, metavar="B",
+                   help="Vectorised loop with --prioritized_replay: importance-sampling weights (N P(i))^(-B), 0 <= B <= 1, each batch "
+                        "divided by its own maximum, computed on the device and multiplied into the loss of every sampled "
+                        "transition (default: no weights).")
+    p.add_argument("--priority_beta_anneal", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="With --priority_beta: raise the exponent linearly from B to 1 over the first N lock-steps that train "
+                        "(default 0: constant).")
 
 
 def check_priority(args):
-    """--priority_alpha / --priority_refresh: refused in words (SystemExit) where the loop cannot run them, before anything
-    touches the GPU."""
-    given = [f"--{k}" for k in ('priority_alpha', 'priority_refresh') if k in args]
+    """--priority_alpha / --priority_refresh / --priority_beta / --priority_beta_anneal: refused in words (SystemExit) where the
+    loop cannot run them, before anything touches the GPU."""
+    given = [f"--{k}" for k in ('priority_alpha', 'priority_refresh', 'priority_beta', 'priority_beta_anneal') if k in args]
     if not given:
         return
     if args['num_envs'] <= 1:
@@ -567,14 +574,22 @@ def check_priority(args):
     a = args.get('priority_alpha', 1.0)
     if not 0.0 <= a <= 1.0:
         raise SystemExit(f"--priority_alpha must lie in [0, 1] (0: uniform, 1: proportional to td_error + 1e-5), not {a}")
+    if 'priority_beta' in args and not 0.0 <= args['priority_beta'] <= 1.0:
+        raise SystemExit(f"--priority_beta must lie in [0, 1] (0: all weights 1, 1: the full correction), not {args['priority_beta']}")
+    if 'priority_beta_anneal' in args and ('priority_beta' not in args or args['priority_beta_anneal'] < 0):
+        raise SystemExit("--priority_beta_anneal N (N >= 0) anneals --priority_beta: give --priority_beta as well")
 
 
 def priority_from_args(args):
     """The prioritised-replay arguments of VecDQN from parsed options (a tool's: every lock-step there is vectorised);
-    --priority_alpha / --priority_refresh without --prioritized_replay is refused as check_priority refuses it."""
+    --priority_alpha / --priority_refresh / --priority_beta without --prioritized_replay is refused as check_priority refuses
+    it.  The keys of the weights are there only when --priority_beta was given."""
     check_priority(dict(args, num_envs=2))
-    return dict(prioritized=bool(args.get('prioritized_replay', False)), priority_alpha=args.get('priority_alpha', 1.0),
-                priority_refresh=bool(args.get('priority_refresh', False)))
+    out = dict(prioritized=bool(args.get('prioritized_replay', False)), priority_alpha=args.get('priority_alpha', 1.0),
+               priority_refresh=bool(args.get('priority_refresh', False)))
+    if 'priority_beta' in args:
+        out.update(priority_beta=args['priority_beta'], priority_beta_anneal=args.get('priority_beta_anneal', 0))
+    return out
 
 
 def add_n_step_argument(p):

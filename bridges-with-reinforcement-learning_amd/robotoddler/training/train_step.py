@@ -82,9 +82,14 @@ class CapturedTrainStep:
     captures again; a failed capture (RuntimeError) or an invalid logged loss switches the driver to eager for good."""
 
     def __init__(self, net, optimizer, batch, loss_parts, img, fused, graph_default=True, warmup=1, eager_body=True,
-                 prepared=False, task=None, owner=None, task_rows=False, obstacle_rows=False):
+                 prepared=False, task=None, owner=None, task_rows=False, obstacle_rows=False, weights=False):
         self.net, self.opt, self.B, self.img = net, optimizer, int(batch), tuple(int(s) for s in img)
-        self.key = (optimizer, self.B, tuple(loss_parts), owner)
+        # weights (importance-sampling weights of prioritised replay): ``run`` takes weights [n * B] float32 and copies them into
+        # the static w [n_max * B]; the hand-written step scales row b's loss share and gradient coefficients by w_b
+        # (bridges_successor_loss_weighted), the autograd body its per-row terms before the reduction over the batch rows.  Part
+        # of the key: a net is never replayed with a graph captured for the other form
+        self.weights = bool(weights)
+        self.key = (optimizer, self.B, tuple(loss_parts), owner, self.weights)
         self.use_q, self.use_sf = 'mse_q_values' in loss_parts, 'mse_block_features' in loss_parts
         self.fused, self.graph_default, self.warmup, self.eager_body = fused, graph_default, warmup, eager_body
         self.prepared, self.task = prepared, task         # task: the (reward, obstacle) maps of every call (None: per call)
@@ -118,7 +123,7 @@ class CapturedTrainStep:
         its state back: one driver per net, so no two hand-written steps adopt the same Adam state.  A driver with an eager
         body builds it here (for n batches): ValueError if the hand-written step does not take the optimiser over."""
         drv = getattr(net, "_fused_trainer", None)
-        if drv is None or drv.key != (optimizer, int(batch), tuple(loss_parts), owner):
+        if drv is None or drv.key != (optimizer, int(batch), tuple(loss_parts), owner, bool(config.get("weights", False))):
             release(net)
             drv = cls(net, optimizer, batch, loss_parts, owner=owner, **config)
             if drv.eager_body:
@@ -138,6 +143,8 @@ class CapturedTrainStep:
         self.block, self.action = (None, None) if self.conv_rows else (z(N, 1, *S), z(N, 1, *S))
         self.x_all = z(N, 4, *S) if self.conv_rows else None
         self.sf = z(N, px) if self.use_sf else None
+        if self.weights:
+            self.w = z(N)
         self.counter, self.losses = torch.zeros((), dtype=torch.int64, device=dev), z(n)
         self.lane, self.iota = torch.arange(B, device=dev), torch.arange(n, device=dev)
         if self.conv_rows:                                 # read from the caller's tensors by the one launch of a call
@@ -168,8 +175,11 @@ class CapturedTrainStep:
             except ValueError:
                 pass                                       # another optimiser, or one with options the launch does not cover
 
-    def _fused_body(self, block, action, binary, reward, obstacle, q, sf):
-        self.step.launch(self.counter, block, action, binary, reward, obstacle, q, sf, self.losses)
+    def _fused_body(self, block, action, binary, reward, obstacle, q, sf, w=None):
+        if w is not None:
+            self.step.launch(self.counter, block, action, binary, reward, obstacle, q, sf, self.losses, weight_all=w)
+        else:
+            self.step.launch(self.counter, block, action, binary, reward, obstacle, q, sf, self.losses)
         if not self.step.fused_adam:                       # else the Adam update is the last launch of the sequence
             self.opt.step()
 
@@ -189,10 +199,17 @@ class CapturedTrainStep:
         # 2.10; eager never) while every single-workgroup reduction was right.  The value is logged through a one-hot of the
         # step counter (pure elementwise arithmetic).
         loss = 0.
-        if self.use_q:
-            loss = loss + ((q - self.q.index_select(0, idx)) ** 2).mean()
-        if self.use_sf:
-            loss = loss + ((sf[:, 0].reshape(B, -1) - self.sf.index_select(0, idx)) ** 2).mean(dim=1).mean()
+        if self.weights:                                   # every row's term times its weight, before the reduction over the rows
+            w = self.w.index_select(0, idx)
+            if self.use_q:
+                loss = loss + (w * (q - self.q.index_select(0, idx)) ** 2).mean()
+            if self.use_sf:
+                loss = loss + (w * ((sf[:, 0].reshape(B, -1) - self.sf.index_select(0, idx)) ** 2).mean(dim=1)).mean()
+        else:
+            if self.use_q:
+                loss = loss + ((q - self.q.index_select(0, idx)) ** 2).mean()
+            if self.use_sf:
+                loss = loss + ((sf[:, 0].reshape(B, -1) - self.sf.index_select(0, idx)) ** 2).mean(dim=1).mean()
         self.losses.add_((self.iota == self.counter).to(torch.float32) * loss.detach())
         with dqn_ops.deferred_wgrad_reduce(self.reduce):   # the conv layers' weight-gradient reductions as one launch
             loss.backward()
@@ -217,7 +234,7 @@ class CapturedTrainStep:
                     if self.fused:
                         N = self.n_max * self.B
                         self._fused_body(self.block.view(N, -1), self.action.view(N, -1), self.binary, self.reward, self.obstacle,
-                                         self.q, self.sf)
+                                         self.q, self.sf, self.w if self.weights else None)
                     else:
                         self._autograd_body()
         finally:
@@ -230,13 +247,16 @@ class CapturedTrainStep:
         if body is not None:
             body.check_hyperparameters()
 
-    def run(self, n, block, action, binary, reward, obstacle, q, sf):
+    def run(self, n, block, action, binary, reward, obstacle, q, sf, weights=None):
         """n optimiser steps on batches 0 .. n-1 of the per-call arrays (rows b * B .. b * B + B - 1 of block / action /
         binary / q / sf; reward / obstacle: one map for all rows, unused with ``task`` -- except with ``task_rows``, where
         reward [n * B, px] holds the map of every transition, and with ``obstacle_rows``, where obstacle [n * B, 64] int64 holds
         the bit-packed obstacle raster of every transition; ``task_rows`` with the autograd body: block / action [n * B, 64]
-        int64 are the bit-packed rasters of every transition too) -> the device tensor of the n losses
+        int64 are the bit-packed rasters of every transition too; a driver built with ``weights=True``: weights [n * B] float32,
+        the importance-sampling weight of every transition) -> the device tensor of the n losses
         (a view of the driver's buffer, valid until its next call), or None: the caller steps eagerly."""
+        if self.weights != (weights is not None):
+            raise ValueError("CapturedTrainStep.run: weights are given exactly to a driver built with weights=True")
         graphs = not self.disabled and graph_enabled(self.graph_default)
         if not graphs or self.calls < self.warmup:
             self.calls += graphs
@@ -250,8 +270,10 @@ class CapturedTrainStep:
             if self.task_rows:
                 reward = reward.reshape(n * self.B, -1).contiguous()
                 obstacle = obstacle.reshape(n * self.B, 64).contiguous() if self.obstacle_rows else self.obstacle
+            if self.weights:
+                weights = weights.reshape(-1).contiguous()
             for _ in range(n):
-                self._fused_body(block, action, binary, reward, obstacle, q, sf)
+                self._fused_body(block, action, binary, reward, obstacle, q, sf, weights)
             return self.losses[:n]
         if n > self.n_max:                                 # the first capture, or more batches than the buffers hold
             self._build(n)
@@ -264,7 +286,7 @@ class CapturedTrainStep:
             except RuntimeError as e:                      # same arithmetic either way: keep training eagerly
                 warnings.warn(f"train-step graph capture failed, staying eager: {e}")
                 self._disable()
-                return self.run(n, block, action, binary, reward, obstacle, q, sf)
+                return self.run(n, block, action, binary, reward, obstacle, q, sf, weights)
         N = n * self.B
         if self.task_rows and not self.conv_rows:
             _put(self.reward, reward.reshape(N, -1))       # before the first-layer rows are built from it
@@ -290,6 +312,8 @@ class CapturedTrainStep:
             _put(self.q, q)
         if sf is not None:
             _put(self.sf, sf)
+        if self.weights:
+            _put(self.w, weights.reshape(-1))
         self.counter.zero_()
         self.losses.zero_()
         for _ in range(n // m):

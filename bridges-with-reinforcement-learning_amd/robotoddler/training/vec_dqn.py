@@ -19,6 +19,7 @@ Semantics follow rollout_episode / train_policy_net / update_target_net of the r
 * prioritised replay draws in proportion to td_error + 1e-5, the rollout's TD error (PrioritizedReplayBuffer); priority_alpha /
   priority_refresh (extensions: the reference has neither) add Schaul et al.'s exponent and write |q(s,a) - q_target| of the
   sampled transitions back as their priorities, both on the device (DESIGN.md section 7, "Prioritised replay on the device");
+  priority_beta (an extension likewise) multiplies the loss terms of every sampled transition with its importance-sampling weight;
 * with several ranks every rank trains an identical replica on the identical gathered ring (same sampling seed); extra
   GPUs add rollout throughput, not optimiser throughput; parameters are re-broadcast every 100 lock-steps;
 * log_episode's numbers (successor_dqn.py:479-499) are logged per lock-step as means over the episodes that ended in it on all
@@ -55,7 +56,7 @@ class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
-                 n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False):
+                 n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -96,8 +97,28 @@ class VecDQN:
         written back to the sampled rows (ReplayRing.update_priorities); rows keep the rollout's td_errors until they are first
         sampled.  Neither option changes the record, the ring or a checkpoint, so a run may be resumed with other settings; with
         priority_alpha=1.0 and priority_refresh=False the loop samples through ReplayRing.sample as it always did (DESIGN.md,
-        "Prioritised replay on the device")."""
+        "Prioritised replay on the device").
+        ``priority_beta=b`` (0..1, with prioritized=True only; None, the default: no weights anywhere): Schaul et al.'s
+        importance-sampling correction.  Every sampled transition gets the weight (N P(i))^(-b), each batch divided by its own
+        maximum (ReplayRing.sample_weights, computed on the device from the masses the draw was made from), and the optimiser step
+        multiplies the transition's loss terms by it.  The loop then always samples through the sampler kernel, at
+        priority_alpha=1 without refresh too.  ``priority_beta_anneal=n`` (> 0): the exponent rises linearly from b to 1 over the
+        first n train_steps calls that trained (0: constant); the count is checkpointed.  Several ranks are allowed: the weights
+        are a deterministic function of identical rings."""
         self.priority_alpha, self.priority_refresh = float(priority_alpha), bool(priority_refresh)
+        self.priority_beta = None if priority_beta is None else float(priority_beta)
+        self.priority_beta_anneal = int(priority_beta_anneal)
+        self.priority_beta_calls = 0                         # train_steps calls that trained so far: the annealing clock
+        if self.priority_beta is not None and not 0.0 <= self.priority_beta <= 1.0:      # (a NaN fails both comparisons)
+            raise ValueError(f"VecDQN(priority_beta={priority_beta}): the exponent of the importance-sampling weights lies in "
+                             "[0, 1] (0: all weights 1, 1: the full correction)")
+        if self.priority_beta_anneal < 0:
+            raise ValueError(f"VecDQN(priority_beta_anneal={priority_beta_anneal}): a number of train_steps calls, >= 0")
+        if not prioritized and (self.priority_beta is not None or self.priority_beta_anneal):
+            raise ValueError("VecDQN(priority_beta=..., priority_beta_anneal=...) correct the prioritised draw: they need "
+                             "prioritized=True (a uniform draw has nothing to correct)")
+        if self.priority_beta is None and self.priority_beta_anneal:
+            raise ValueError("VecDQN(priority_beta_anneal=...) anneals priority_beta: give priority_beta as well")
         if not 0.0 <= self.priority_alpha <= 1.0:            # (a NaN fails both comparisons)
             raise ValueError(f"VecDQN(priority_alpha={priority_alpha}): the exponent of the priorities lies in [0, 1] "
                              "(0: uniform, 1: proportional to td_error + 1e-5)")
@@ -720,7 +741,23 @@ class VecDQN:
         q = self._net_q(self.policy_net, view, rows, rows, stable_s.bool(), groups=None)
         return q[:n].contiguous().float()
 
-    def _loss(self, q, sf, q_target, sf_target):
+    def beta_now(self):
+        """The exponent of the importance-sampling weights of the next train_steps call that trains:
+        min(1, beta0 + (1 - beta0) * k / anneal), k = the calls that trained so far (anneal == 0: beta0).  Host arithmetic on a
+        scalar launch argument: the weights launch lies outside the captured graph."""
+        b0, n = self.priority_beta, self.priority_beta_anneal
+        return b0 if n == 0 else min(1.0, b0 + (1.0 - b0) * self.priority_beta_calls / n)
+
+    def _loss(self, q, sf, q_target, sf_target, w=None):
+        """``w`` [B] (importance-sampling weights): every row's term times its weight before the mean over the rows -- the
+        formulas of the captured autograd body (train_step.CapturedTrainStep._autograd_body)."""
+        if w is not None:
+            loss = 0.
+            if 'mse_q_values' in self.loss_parts:
+                loss = loss + (w * (q - q_target) ** 2).mean()
+            if sf_target is not None:
+                loss = loss + (w * ((sf[:, 0] - sf_target.view_as(sf[:, 0])) ** 2).reshape(w.shape[0], -1).mean(dim=1)).mean()
+            return loss
         loss = 0.
         if 'mse_q_values' in self.loss_parts:
             loss = loss + self.mse(q, q_target)
@@ -739,7 +776,7 @@ class VecDQN:
                                       fused=T.fused_step_enabled(self.policy_net, self.loss_parts),
                                       graph_default=isinstance(self.policy_net, (SuccessorMLP, ConvNet, Policy)), warmup=2,
                                       eager_body=False, prepared=True, task_rows=self.per_env_tasks,
-                                      obstacle_rows=self.per_env_obstacles,
+                                      obstacle_rows=self.per_env_obstacles, weights=self.priority_beta is not None,
                                       task=((None if self.per_env_tasks else env.reward_features),
                                             (None if self.per_env_obstacles else
                                              (env.obstacle_bits if self.task_channels else env.obstacle_raster))))
@@ -770,8 +807,14 @@ class VecDQN:
         B = self.B
         # n_steps independent batches = ONE draw of n_steps * B records: both sampling rules draw with replacement, so
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
-        drawn = None
-        if self.priority_refresh or self.priority_alpha != 1.0:
+        drawn = weights = None
+        if self.priority_beta is not None:
+            # importance-sampling weights: always the sampler kernel (they need the draws' rows and the masses), and the weights
+            # directly behind the draw -- they describe the distribution it was made from, before any refresh
+            rec, drawn = self.ring.sample_prioritized(n_steps * B, self.sample_gen, self.priority_alpha)
+            weights = self.ring.sample_weights(drawn, B, self.beta_now())
+            self.priority_beta_calls += 1
+        elif self.priority_refresh or self.priority_alpha != 1.0:
             # the sampler kernel: the exponent, and the ring rows of the draws for the refresh
             rec, drawn = self.ring.sample_prioritized(n_steps * B, self.sample_gen, self.priority_alpha)
         else:
@@ -788,7 +831,10 @@ class VecDQN:
         maps = task[0] if task else None                     # per-env tasks: the reward map of every transition [n_steps * B, px]
         obst_bits = task[1] if len(task) > 1 else None       # per-env obstacles: its bit-packed obstacle raster [n_steps * B, 64]
         drv = self._train_step(n_steps)
-        out = drv.run(n_steps, block_f, action_f, binary, maps, obst_bits, q_target, sf_target)
+        if weights is not None:
+            out = drv.run(n_steps, block_f, action_f, binary, maps, obst_bits, q_target, sf_target, weights=weights)
+        else:
+            out = drv.run(n_steps, block_f, action_f, binary, maps, obst_bits, q_target, sf_target)
         if out is None:
             drv = None
             S = self.env.img
@@ -811,7 +857,10 @@ class VecDQN:
                     if obst_bits is not None:
                         obstacle = ops.bits_to_f32(obst_bits[sl]).reshape(B, 1, S, S)
                     q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
-                loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
+                if weights is not None:
+                    loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None, weights[sl])
+                else:
+                    loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
                 self.opt.zero_grad()
                 if self._eager_reduce is None:
                     self._eager_reduce = dqn_ops.ReduceTables(self.device)
@@ -845,6 +894,8 @@ class VecDQN:
                     task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)), n_step=int(getattr(self, "n_step", 1)))
         if getattr(self, "curriculum", None) is not None:    # one more key: (ema, seen), weights, sums and accumulator
             blob["curriculum"] = self.curriculum.state_dict()
+        if getattr(self, "priority_beta", None) is not None:  # one more key: the annealing clock of the weights' exponent
+            blob["priority_beta_calls"] = int(self.priority_beta_calls)
         torch.save(blob, path)
 
     def load_extra(self, path):
@@ -876,6 +927,8 @@ class VecDQN:
             self.explore_gen.manual_seed(7654321 + self.seed * 1000 + self.rank + 7919 * (int(blob["counters"].get("lockstep", 0)) + 1))
         if getattr(self, "curriculum", None) is not None and "curriculum" in blob:     # continue with the same table
             self.curriculum.load_state_dict(blob["curriculum"])
+        if getattr(self, "priority_beta", None) is not None:  # (a file of a run without the option carries no entry: 0)
+            self.priority_beta_calls = int(blob.get("priority_beta_calls", 0))
         return blob["counters"]
 
     # ------------------------------------------------------------------ driver
@@ -1078,7 +1131,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
                    task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1),
                    double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
-                   priority_refresh=bool(args.get('priority_refresh', False)))
+                   priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
+                   priority_beta_anneal=args.get('priority_beta_anneal', 0))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)

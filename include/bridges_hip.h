@@ -693,6 +693,20 @@ int bridges_priority_sample(int64_t n_rec, int32_t W, int32_t col, const double*
  * rec / idx that is not 8-byte or a q_sa / q_target that is not 4-byte aligned.  n == 0 returns 0 and launches nothing. */
 int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, int64_t n, const int64_t* idx, const float* q_sa,
                             const float* q_target, void* stream);
+/* The importance-sampling weights of the draws (Schaul et al.'s beta): idx [n_draws] i64 as bridges_priority_sample returned it,
+ * scratch as THAT call left it for the same n_rec (its first ceil(n_rec / 256) * 256 doubles are the masses m_i; only read here),
+ * weight [n_draws] f32.  w_j = (n_rec * m_idx[j] / total)^(-beta); every `batch` consecutive draws are one optimiser step and are
+ * divided by their own maximum, so the largest weight of a batch is exactly 1 and n_rec and total cancel:
+ *   weight[j] = (float)pow(min_k m_idx[k] / m_idx[j], beta),   k over the batch of j
+ * in float64, rounded once (beta == 0: 1.0f, no pow; beta == 1: the quotient, no pow).  The masses are those the draws were made
+ * from, not the record column: a bridges_priority_update in between does not change the weights, the next
+ * bridges_priority_sample on the same scratch does.  An idx[j] outside [0, n_rec) gets weight 0 and takes no part in the minimum.
+ * One launch, one workgroup per batch, no atomics: the same bits on every call.
+ * Returns -1 and launches nothing for: n_draws < 0; with n_draws > 0: n_rec <= 0 or n_rec > BRIDGES_PRIORITY_MAX_ROWS; batch <= 0
+ * or n_draws % batch != 0; beta outside [0, 1] or NaN; a NULL idx, scratch or weight; an idx / scratch that is not 8-byte or a
+ * weight that is not 4-byte aligned; scratch_doubles below the sizing call's answer.  n_draws == 0 returns 0, launches nothing. */
+int bridges_priority_weights(int64_t n_rec, int64_t n_draws, int64_t batch, const int64_t* idx, double beta, const double* scratch,
+                             int64_t scratch_doubles, float* weight, void* stream);
 
 /* Inference epilogues of the conv Q-networks (robotoddler/models/cv.py:5-17, 41-73, 108-170: Conv2d -> ReLU
  * [-> MaxPool2d(2)]), one pass instead of torch's three; bit-identical to relu(conv + bias) / maxpool(relu(conv + bias)).
@@ -807,6 +821,18 @@ int bridges_successor_loss_rows(int32_t batch, int32_t rows, int32_t px, int32_t
                                 int64_t reward_stride, const int64_t* counter, const float* q_target_all, const float* sf_target_all,
                                 int32_t use_q, int32_t use_sf, float* dy, float* loss_rows, float* q_out, float* losses,
                                 int32_t n_losses, int64_t* counter_inc, int32_t* ticket, float* adam_step, void* stream);
+/* The _rows form with an importance-sampling weight per transition: weight_all [n] f32 (bridges_priority_weights), addressed as the
+ * targets are (row *counter * batch + b).  loss = [use_q] mean_b w_b (q - q_target)^2 + [use_sf] mean_b w_b mean_j (psi0 - sf_target)^2:
+ * loss_rows[b] is w_b times the row's unweighted share, the two gradient coefficients of row b (2 (q - q_target) / batch and
+ * 2 / (batch px)) are each multiplied by w_b once before they meet the per-pixel factors, q_out stays the unweighted q, rows
+ * b >= batch stay zero.  With every w_b == 1.0f the outputs are the bits of bridges_successor_loss / _rows.  reward_stride 0 or px
+ * as there; ticket, losses, counter_inc and adam_step as there (the logged loss is the in-order f32 sum of the weighted rows,
+ * also through bridges_linear_backward_log).  A NULL weight_all returns -1. */
+int bridges_successor_loss_weighted(int32_t batch, int32_t rows, int32_t px, int32_t nf, const float* y, const float* reward,
+                                    int64_t reward_stride, const int64_t* counter, const float* q_target_all,
+                                    const float* sf_target_all, int32_t use_q, int32_t use_sf, float* dy, float* loss_rows,
+                                    float* q_out, float* losses, int32_t n_losses, int64_t* counter_inc, int32_t* ticket,
+                                    float* adam_step, const float* weight_all, void* stream);
 /* `ticket` (device int32, zero before the first call; may be NULL): the logging (losses[*counter_inc] = sum of loss_rows,
  * ++*counter_inc, and ++*adam_step if given) is done inside the loss kernel by the row workgroup that arrives last
  * instead of a second launch; the kernel re-arms the ticket.

@@ -7,7 +7,8 @@ lock-step holds the fold AND the update, and the count should be that of the sam
 lock-step with n-step returns (the fold and the compaction of its rows): the count should be that of the same line without it.
 --double_q runs it with double Q-learning targets (a second forward over the next-state rows): the count should not change either.
 --prioritized_replay [--priority_alpha A] [--priority_refresh] runs it on prioritised replay; the sampler kernel and the refresh add
-launches, and the count should be that of plain --prioritized_replay."""
+launches, and the count should be that of plain --prioritized_replay; --priority_beta B [--priority_beta_anneal N] adds the
+importance-sampling weights (one more launch, no wait)."""
 import argparse
 import os
 import sys

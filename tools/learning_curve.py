@@ -48,7 +48,7 @@ ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
 add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
 add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_step=N))
 add_double_q_argument(ap)                # --double_q: double Q-learning targets (VecDQN(double_q=True))
-add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh]
+add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")

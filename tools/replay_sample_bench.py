@@ -6,7 +6,11 @@ events around single calls, both sides alternating, warm-up first; prints one JS
 spread (min, max, inter-quartile range).
     python tools/replay_sample_bench.py [--rows 16384 131072] [--width 111] [--draws 800] [--alpha 1.0] [--reps 40]
 The kernel path reads one 64-byte sector per 8 W-byte row (the priority column is strided by the record layout), writes and reads
-8 bytes of mass per row, and touches ~13 chunk prefix sums and 2 KiB of masses per draw."""
+8 bytes of mass per row, and touches ~13 chunk prefix sums and 2 KiB of masses per draw.
+    python tools/replay_sample_bench.py --beta 0.4 [--batch 32] [...]
+times the importance-sampling weights of one draw instead: ReplayRing.sample_weights (bridges_priority_weights: one launch, one
+workgroup per batch) beside the torch formulation of the same numbers (gather of the masses, pow, per-batch amin, divide, cast),
+in the same manner; the draw itself is made once, outside the timings."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -19,6 +23,8 @@ ap.add_argument("--rows", type=int, nargs="+", default=[16384, 131072], help="li
 ap.add_argument("--width", type=int, default=R.RECORD_WIDTH)
 ap.add_argument("--draws", type=int, default=800)
 ap.add_argument("--alpha", type=float, default=1.0, help="the kernel path's exponent (the torch formulation has none: alpha = 1)")
+ap.add_argument("--beta", type=float, default=None, help="time the weights kernel against its torch formulation at this exponent")
+ap.add_argument("--batch", type=int, default=32, help="--beta: draws per optimiser step (each batch is normalised by its own maximum)")
 ap.add_argument("--reps", type=int, default=40)
 ap.add_argument("--warmup", type=int, default=10)
 a = ap.parse_args()
@@ -33,7 +39,16 @@ for rows in a.rows:
     gk, gf = (torch.Generator(device=dev).manual_seed(7) for _ in range(2))
     kernel = lambda: ring.sample_prioritized(a.draws, gk, a.alpha)[0]
     formulation = lambda: ring.sample(a.draws, gf, prioritized=True)
-    if a.alpha == 1.0:                                   # the same stream, the same distribution: the same records but for near-ties
+    if a.beta is not None:
+        _, idx = ring.sample_prioritized(a.draws, gk, a.alpha)
+        mass = ring._priority_scratch[:rows]                 # what the draw was made from
+        kernel = lambda: ring.sample_weights(idx, a.batch, a.beta)
+
+        def formulation():
+            r = mass.index_select(0, idx).view(-1, a.batch)
+            return (r.amin(dim=1, keepdim=True) / r).pow(a.beta).reshape(-1).float()
+        assert torch.allclose(kernel(), formulation(), rtol=1e-6, atol=0.0)
+    elif a.alpha == 1.0:                                 # the same stream, the same distribution: the same records but for near-ties
         same = (kernel() == formulation()).all(dim=1).float().mean().item()
         assert same > 0.99, same
     for _ in range(a.warmup):
@@ -57,5 +72,6 @@ for rows in a.rows:
     k, f = summary["kernel"], summary["formulation"]
     print(json.dumps(dict(config=dict(vars(a), rows=rows), **summary, ratio_of_medians=f["median_us"] / k["median_us"],
                           faster_by_more_than_the_formulations_spread=bool(f["median_us"] - k["median_us"] > f["max_us"] - f["min_us"]),
-                          note="HIP events around single calls (rand, the draw and the gather; host launch gaps included), both sides "
+                          note="HIP events around single calls (" + ("the weights of one draw" if a.beta is not None else "rand, the draw and the gather")
+                               + "; host launch gaps included), both sides "
                                "alternating in one process; spread = max - min of the timed calls")), flush=True)

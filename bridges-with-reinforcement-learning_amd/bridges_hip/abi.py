@@ -255,6 +255,7 @@ SIGNATURES = {
     "bridges_mlp_mid_forward": [i32, i32, vp, vp, vp, vp, vp],
     "bridges_mlp_mid_backward": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
     "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_boltzmann_select": [i32, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups_keyed": [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp],

@@ -477,6 +477,37 @@ def eps_greedy_select(seg, q, join, u, eps, greedy, idx, cand_offset, rep=None):
     return sel_compact, sel_index, q_sel, explore_w
 
 
+def boltzmann_select(seg, q, u, temperature, greedy, idx, cand_offset, rep=None):
+    """Boltzmann exploration for every env in one launch (bridges_boltzmann_select): env e draws one of its rows with probability
+    proportional to exp(q / temperature) by the inverse CDF at u[e] (the rule stands in include/bridges_hip.h; float64 on the
+    device).  seg, q, u, idx, cand_offset and rep as for eps_greedy_select; temperature > 0 and finite (the library refuses any
+    other, and an empty q).
+    -> (sel_compact int64 [E], sel_index int32 [E], q_sel float32 [E], explore_w float32 [E] = 1 where the drawn row is not the
+    first maximum, p_sel float32 [E] = the probability the drawn row had)."""
+    L = abi.require_gpu()
+    if isinstance(seg, (tuple, list)):
+        seg_lo, seg_hi = seg
+        E = seg_lo.numel()
+    else:
+        E = seg.numel() - 1
+        seg_lo, seg_hi = seg[:E], seg[1:]
+    n = q.numel()
+    assert seg_lo.dtype == torch.int32 and seg_hi.dtype == torch.int32 and seg_lo.is_contiguous() and seg_hi.is_contiguous()
+    assert seg_hi.numel() == E and idx.dtype == torch.int64 and cand_offset.dtype == torch.int32
+    assert rep is None or (rep.dtype == torch.int32 and rep.numel() == E and rep.is_contiguous())
+    q, u = q.to(torch.float32).contiguous(), u.to(torch.float32).contiguous()
+    idx, cand_offset = idx.contiguous(), cand_offset.contiguous()
+    assert idx.numel() == n and u.numel() == E and cand_offset.numel() >= E
+    dev = q.device
+    sel_compact = torch.empty(E, dtype=torch.int64, device=dev)
+    sel_index = torch.empty(E, dtype=torch.int32, device=dev)
+    q_sel, explore_w, p_sel = (torch.empty(E, dtype=torch.float32, device=dev) for _ in range(3))
+    abi.check(L.bridges_boltzmann_select(E, n, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), _ptr(u), float(temperature), int(bool(greedy)),
+                                         _ptr(idx), _ptr(cand_offset), _ptr(rep), _ptr(sel_compact), _ptr(sel_index), _ptr(q_sel),
+                                         _ptr(explore_w), _ptr(p_sel), _stream()), "bridges_boltzmann_select")
+    return sel_compact, sel_index, q_sel, explore_w, p_sel
+
+
 def episode_stats_(out, rec, valid, gpow, n_targets, run, counted, count_first_only=False):
     """Folds one lock-step's records rec float64 [E, W] / valid bool [E] into the per-episode sums ``out`` float64 [8] in place
     (bridges_episode_stats): run float32 [E, 2] and counted int32 [E] carry the episodes that span calls, gpow float32 [K] =

@@ -817,6 +817,21 @@ int bridges_eps_greedy_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, 
                   seg_hi, q, join, u, eps, (int)greedy, idx, cand_offset, rep, sel_compact, sel_index, q_sel, explore_w);
 }
 
+int bridges_boltzmann_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, const float* u,
+                             float temperature, int32_t greedy, const int64_t* idx, const int32_t* cand_offset, const int32_t* rep,
+                             int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w, float* p_sel, void* stream) {
+    if (E < 0) return fail_arg("bridges_boltzmann_select: negative count");
+    if (E == 0) return BRIDGES_OK;
+    if (n_rows < 1) return fail_arg("bridges_boltzmann_select: n_rows must be >= 1");
+    if (!(temperature > 0.f && temperature < INFINITY))                           // (a NaN fails the comparison)
+        return fail_arg("bridges_boltzmann_select: the temperature must be finite and > 0");
+    if (!seg_lo || !seg_hi || !q || !u || !idx || !cand_offset || !sel_compact || !sel_index || !q_sel || !explore_w || !p_sel)
+        return fail_arg("bridges_boltzmann_select: null pointer");
+    // one wave per env, four envs per workgroup
+    return launch("k_boltzmann_select", k_boltzmann_select, dim3((unsigned)ceil_div(E, 4)), dim3(256), 0, stream, E, n_rows, seg_lo,
+                  seg_hi, q, u, temperature, (int)greedy, idx, cand_offset, rep, sel_compact, sel_index, q_sel, explore_w, p_sel);
+}
+
 int bridges_record_state(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
                          const uint8_t* blk_occ, const uint8_t* step_flags, const int64_t* sel_row, const int32_t* cand_desc,
                          const double* cand_pose, double* rec, void* stream) {

@@ -503,6 +503,119 @@ __global__ __launch_bounds__(256) void k_eps_greedy_select(int E, int n_rows, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Boltzmann exploration (the reference's Softmax policy, successor_dqn.py:138-154, made to run) for every env of the vectorised
+// loop in one launch: env e draws row j of its rows lo .. hi - 1 of the Q pass with probability proportional to
+//   w_j = exp((q_j - m) / T),  m = the largest q of the env that is neither NaN nor -inf (such rows weigh 0; m = +inf: the +inf
+//   rows weigh 1, all others 0),
+// by the inverse CDF: c_j = w_lo + .. + w_j in row order, the row is the first with c_j > u[e] * total (strict; none, by rounding:
+// the last row with w_j > 0).  No eligible row: row lo with p_sel 0.  The rule in full stands in include/bridges_hip.h.
+// One wave per env, three passes over its rows: the maximum (lane-strided, DPP tree), the total (64 rows at a time, DPP tree per
+// chunk, chunks added in order) and the search (64 rows at a time, shuffle scan as in k_priority_draw, a running carry from chunk
+// to chunk; it stops at the first chunk that holds the row).  float64 throughout: (q - m) / T reaches -745 before a weight
+// underflows, and a float32 prefix sum over hundreds of rows would move draws near a boundary to the neighbouring row; p_sel is
+// rounded to float32 once.  No atomics, no LDS, a fixed order of additions: the same bits on every call.  lo and hi are made
+// scalar, so every lane runs every chunk and reaches every cross-lane step.  greedy != 0: the row of
+// k_eps_greedy_select(greedy = 1), by its very loop.
+//   sel_compact / sel_index / q_sel as k_eps_greedy_select writes them; explore_w[e] = 1.0 if the env has rows and the drawn row
+//   is not the first maximum among its eligible rows, else 0.0; p_sel[e] = w_row / total (greedy: 1; no rows, no eligible row: 0).
+__device__ __forceinline__ double boltzmann_weight(float qv, double m, double T) {
+    if (!(qv == qv) || qv == -INFINITY) return 0.0;
+    if (m == (double)INFINITY) return qv == INFINITY ? 1.0 : 0.0;
+    return exp(((double)qv - m) / T);
+}
+
+__global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, const int32_t* __restrict__ seg_lo,
+                                                          const int32_t* __restrict__ seg_hi, const float* __restrict__ q,
+                                                          const float* __restrict__ u, float temperature, int greedy,
+                                                          const int64_t* __restrict__ idx, const int32_t* __restrict__ cand_offset,
+                                                          const int32_t* __restrict__ rep, int64_t* __restrict__ sel_compact,
+                                                          int32_t* __restrict__ sel_index, float* __restrict__ q_sel,
+                                                          float* __restrict__ explore_w, float* __restrict__ p_sel) {
+    constexpr int NONE = 0x7fffffff;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int e = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    if (e >= E) return;                                  // wave-uniform: e is the same in all 64 lanes
+    const int lo = __builtin_amdgcn_readfirstlane(seg_lo[e]), hi = __builtin_amdgcn_readfirstlane(seg_hi[e]);
+    const bool has = hi > lo;
+    int row = NONE, first_max = NONE;
+    double p = 0.0;
+    if (greedy) {
+        // k_eps_greedy_select's search, operand for operand (it decides what a NaN row does to the choice)
+        float best = -INFINITY;
+        int bi = NONE;
+        for (int j = lo + lane; j < hi; j += 64) {
+            const float v = q[j];
+            if (bi == NONE || v > best || (v == best && j < bi)) { best = v; bi = j; }
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const float v = __shfl_xor(best, m);
+            const int k = __shfl_xor(bi, m);
+            if (k != NONE && (bi == NONE || v > best || (v == best && k < bi))) { best = v; bi = k; }
+        }
+        row = first_max = bi;
+        p = has ? 1.0 : 0.0;
+    } else if (has) {
+        const double T = (double)temperature;
+        // pass 1: the largest eligible q (-inf: no row is eligible)
+        double mx = -INFINITY;
+        for (int j = lo + lane; j < hi; j += 64) {
+            const float v = q[j];
+            if (v == v && (double)v > mx) mx = (double)v;
+        }
+        const double m = wave_max_d(mx);
+        if (m == -(double)INFINITY) {
+            row = first_max = lo;
+        } else {
+            // pass 2: the total, and the first row that holds the maximum
+            double total = 0.0;
+            int fm = NONE;
+            for (int base = lo; base < hi; base += 64) {
+                const int j = base + lane;
+                const float v = j < hi ? q[j] : -INFINITY;
+                if (fm == NONE && (double)v == m) fm = j;
+                total += wave_sum_d(boltzmann_weight(v, m, T));
+            }
+            first_max = wave_min_i(fm);
+            // pass 3: the first row whose prefix exceeds the target
+            const double target = (double)u[e] * total;
+            double carry = 0.0;
+            int last_pos = -1;                            // this lane's last row of positive weight
+            int found = NONE;
+            for (int base = lo; base < hi; base += 64) {
+                const int j = base + lane;
+                const double w = boltzmann_weight(j < hi ? q[j] : -INFINITY, m, T);
+                double incl = w;                          // inclusive scan of the chunk's weights
+#pragma unroll
+                for (int s = 1; s < WAVE; s <<= 1) {
+                    const double up = __shfl_up(incl, s, WAVE);
+                    if (lane >= s) incl += up;
+                }
+                if (w > 0.0) last_pos = j;
+                found = wave_min_i((j < hi && carry + incl > target) ? j : NONE);
+                if (found != NONE) break;                 // wave-uniform: wave_min_i returns a scalar
+                carry += readlane_d(incl, WAVE - 1);
+            }
+            if (found == NONE) found = -wave_min_i(-last_pos);        // rounding left none: the last row that weighs anything
+            row = found;
+            p = boltzmann_weight(q[row], m, T) / total;
+        }
+    }
+    if (lane == 0) {
+        const bool explored = has && !greedy && row != first_max;
+        if (!has) row = 0;
+        if (row > n_rows - 1) row = n_rows - 1;
+        const int64_t c = idx[row];
+        sel_compact[e] = c;
+        const int64_t rel = c - (int64_t)cand_offset[rep ? rep[e] : e];
+        sel_index[e] = rel > 0 ? (int32_t)rel : 0;
+        q_sel[e] = has ? q[row] : 0.f;
+        explore_w[e] = explored ? 1.f : 0.f;
+        p_sel[e] = (float)p;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Transition records of the vectorised loop (robotoddler/training/records.py: one float64 row per transition, the
 // compact form of the reference's Transition, successor_dqn.py:27-44; layout BRIDGES_REC_* of the header).  The torch
 // formulation of these three steps was ~95 slice / cast / index launches of a few microseconds per lock-step.

@@ -109,6 +109,55 @@ class EpsilonGreedy:
         return sel
 
 
+def check_temperature_schedule(temp_start, temp_end, decay, who="Softmax"):
+    """0 < temp_end <= temp_start, 0 < decay <= 1, all three finite (a NaN fails every comparison)."""
+    if not (0.0 < temp_end <= temp_start < float("inf")):
+        raise ValueError(f"{who}: the temperature falls from temp_start to temp_end, 0 < temp_end <= temp_start < inf, "
+                         f"not from {temp_start} to {temp_end}")
+    if not 0.0 < decay <= 1.0:
+        raise ValueError(f"{who}: the decay of the temperature lies in (0, 1], not {decay}")
+
+
+def boltzmann_row(q_values, u, temp):
+    """The row a Boltzmann draw takes (the rule of bridges_boltzmann_select, include/bridges_hip.h, in float64 on the host):
+    weights exp((q - m) / temp) with m the largest q that is neither NaN nor -inf (such rows weigh 0; m = +inf: the +inf rows weigh 1),
+    prefix sums in row order, the first row whose prefix exceeds u * total -- none, by rounding: the last row that weighs anything;
+    no eligible row: row 0."""
+    q = np.asarray(q_values, dtype=np.float64).reshape(-1)
+    elig = ~np.isnan(q) & (q != -np.inf)
+    if not elig.any():
+        return 0
+    m = q[elig].max()
+    w = np.zeros_like(q)
+    if m == np.inf:
+        w[q == np.inf] = 1.0
+    else:
+        with np.errstate(under="ignore"):
+            w[elig] = np.exp((q[elig] - m) / float(temp))
+    c = np.add.accumulate(w)
+    hit = c > float(u) * c[-1]
+    return int(np.argmax(hit)) if hit.any() else int(np.flatnonzero(w > 0)[-1])
+
+
+class Softmax:
+    """Boltzmann exploration with an annealed temperature (successor_dqn.py:138-154 of the reference, whose sketch cannot run: it
+    never sets temp_end and draws a probability where it means an index).  Row j is taken with probability proportional to
+    exp(q_j / temp); the uniform draw comes from ``random``, the stream EpsilonGreedy uses, so --seed covers it."""
+
+    def __init__(self, temp_start=1, temp_end=0.1, decay=0.99, episode=0):
+        check_temperature_schedule(temp_start, temp_end, decay)
+        self.temp = (temp_start - temp_end) * (decay ** episode) + temp_end
+        self.temp_start, self.temp_end, self.decay = temp_start, temp_end, decay
+
+    def step(self):
+        self.temp = (self.temp - self.temp_end) * self.decay + self.temp_end
+        return self
+
+    def __call__(self, q_values, *args, **kwargs):
+        q = q_values.detach().float().cpu().numpy() if torch.is_tensor(q_values) else q_values
+        return boltzmann_row(q, random.random(), self.temp)
+
+
 # ---- training (successor_dqn.py:157-288) ------------------------------------------------------------------------
 def _task_key(*tensors):
     """Fingerprint of an episode's task features (reward map, obstacle raster): transitions whose tensors carry the same key
@@ -466,6 +515,8 @@ def log_episode(episode, transitions, losses, gamma, context='training', policy=
     }
     if policy is not None and hasattr(policy, 'epsilon'):
         info['epsilon'] = policy.epsilon
+    if policy is not None and hasattr(policy, 'temp'):       # a Softmax policy
+        info['temperature'] = policy.temp
     track_run_sinks(info, episode, context, aim_run=aim_run, wandb_run=wandb_run)
     return info, None
 
@@ -534,7 +585,53 @@ def build_parser():
     add_n_step_argument(p)
     add_double_q_argument(p)
     add_priority_arguments(p)
+    add_exploration_arguments(p)
     return p
+
+
+EXPLORATIONS = ("epsilon_greedy", "boltzmann")
+# the schedules' defaults: the vectorised loop anneals per lock-step (as its epsilon), the single-env loop per episode
+TEMP_DEFAULTS = dict(temp_start=1.0, temp_end=0.1, temp_decay=0.999)
+
+
+def add_exploration_arguments(p):
+    """--exploration / --temp_start / --temp_end / --temp_decay: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--exploration", choices=EXPLORATIONS, default=argparse.SUPPRESS,
+                   help="How the agent explores, in both loops (default epsilon_greedy: the count-based rule of the reference). "
+                        "boltzmann: every env draws its candidate with probability proportional to exp(q / temperature), on the "
+                        "device in the vectorised loop (bridges_boltzmann_select), with the Softmax policy in the single-env loop; "
+                        "the temperature falls as t <- (t - temp_end) * temp_decay + temp_end per lock-step (per episode in the "
+                        "single-env loop). Evaluation stays greedy.")
+    p.add_argument("--temp_start", type=float, default=argparse.SUPPRESS, help="With --exploration boltzmann: first temperature (1.0).")
+    p.add_argument("--temp_end", type=float, default=argparse.SUPPRESS, help="With --exploration boltzmann: last temperature (0.1).")
+    p.add_argument("--temp_decay", type=float, default=argparse.SUPPRESS,
+                   help="With --exploration boltzmann: decay of the temperature per lock-step / episode (0.999).")
+
+
+def check_exploration(args):
+    """--exploration / --temp_*: refused in words (SystemExit) before anything touches the GPU."""
+    given = [f"--{k}" for k in TEMP_DEFAULTS if k in args]
+    boltzmann = args.get('exploration', EXPLORATIONS[0]) == "boltzmann"
+    if given and not boltzmann:
+        raise SystemExit(f"{' / '.join(given)} shape the temperature of Boltzmann exploration: they need --exploration boltzmann")
+    if boltzmann:
+        t = {k: args.get(k, v) for k, v in TEMP_DEFAULTS.items()}
+        try:
+            check_temperature_schedule(t['temp_start'], t['temp_end'], t['temp_decay'], who="--temp_start / --temp_end / --temp_decay")
+        except ValueError as e:
+            raise SystemExit(str(e)) from e
+        if args.get('eval_epsilon', 0.0) > 0:
+            raise SystemExit("--eval_epsilon > 0 explores with the epsilon-greedy rule: not with --exploration boltzmann, whose "
+                             "evaluation is greedy")
+
+
+def exploration_from_args(args):
+    """The exploration arguments of VecDQN from parsed options (the temp_* keys only with --exploration boltzmann); refuses what
+    check_exploration refuses."""
+    check_exploration(args)
+    if args.get('exploration', EXPLORATIONS[0]) != "boltzmann":
+        return {}
+    return dict(exploration="boltzmann", **{k: args.get(k, v) for k, v in TEMP_DEFAULTS.items()})
 
 
 def add_priority_arguments(p, prioritized_flag=False):
@@ -810,6 +907,7 @@ def main(argv=None):
     check_n_step(args)
     check_double_q(args)
     check_priority(args)
+    check_exploration(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
@@ -846,7 +944,13 @@ def main(argv=None):
                                                 target_net=target_net, device=device)
     else:
         replay_buffer = ReplayBuffer(capacity=args['replay_buffer_capacity'])
-    eps_greedy = EpsilonGreedy(eps_start=0.5, gamma=0.999, eps_end=0.05, episode=0, max_steps=args['max_steps'], device=device)
+    temps = exploration_from_args(args)                   # --exploration boltzmann: the Softmax policy in EpsilonGreedy's place
+
+    def make_policy(episode):
+        if temps:
+            return Softmax(temp_start=temps['temp_start'], temp_end=temps['temp_end'], decay=temps['temp_decay'], episode=episode)
+        return EpsilonGreedy(eps_start=0.5, gamma=0.999, eps_end=0.05, episode=episode, max_steps=args['max_steps'], device=device)
+    eps_greedy = make_policy(0)
     greedy = lambda q, *a, **k: torch.argmax(q)
     setup_fct = make_setup_fct(args)
     env = AssemblyGym(reward_fct=sparse_reward, max_steps=args['max_steps'], restrict_2d=True,
@@ -859,8 +963,7 @@ def main(argv=None):
                                devices=dict(policy_net=device, target_net=device, optimizer=device))
         optimizer_to(optimizer, device)
         first_episode = int(meta['episode']) + 1
-        eps_greedy = EpsilonGreedy(eps_start=0.5, gamma=0.999, eps_end=0.05, episode=int(meta['episode']),
-                                   max_steps=args['max_steps'], device=device)
+        eps_greedy = make_policy(int(meta['episode']))
     history = []
     roll = dict(env=env, policy_net=policy_net, setup_fct=setup_fct, x_discr_ground=x_discr_ground, xlim=xlim, ylim=ylim,
                 offset_values=offset_values, img_size=args['image_size'], device=device, log_images=False,

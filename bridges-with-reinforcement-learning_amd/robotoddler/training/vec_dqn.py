@@ -7,6 +7,9 @@ Semantics follow rollout_episode / train_policy_net / update_target_net of the r
 * epsilon-greedy draws one uniform per env; exploring envs take the candidate whose raster overlaps least with the
   per-episode-step count images (successor_dqn.py:112-132), all envs scored against the images of the lock-step
   start and the chosen rasters added afterwards;
+* exploration="boltzmann" (an extension: the reference's Softmax policy, successor_dqn.py:138-154, cannot run) draws every env's
+  candidate from softmax(q / temperature) on the device instead, the temperature annealed per lock-step (DESIGN.md section 7,
+  "Boltzmann exploration");
 * the TD target is the elementwise  lin_reward + gamma * q'  (the single-env reference path trains on a [B,B]
   broadcast of it because its lin_reward is [B,1]; that quirk is reproduced only in the single-env loop);
   with n_step = n > 1 (an extension: the reference has no multi-step target) it is  G + gamma^h * q',  G the h-step return of
@@ -56,7 +59,8 @@ class VecDQN:
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
-                 n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0):
+                 n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0,
+                 exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -104,7 +108,28 @@ class VecDQN:
         multiplies the transition's loss terms by it.  The loop then always samples through the sampler kernel, at
         priority_alpha=1 without refresh too.  ``priority_beta_anneal=n`` (> 0): the exponent rises linearly from b to 1 over the
         first n train_steps calls that trained (0: constant); the count is checkpointed.  Several ranks are allowed: the weights
-        are a deterministic function of identical rings."""
+        are a deterministic function of identical rings.
+        ``exploration="boltzmann"`` (an extension: the reference sketches a Softmax policy that cannot run): every env draws its
+        candidate with probability proportional to exp(q / temperature) in one launch on the device (bridges_boltzmann_select, the
+        rule in include/bridges_hip.h) with the uniform draw epsilon-greedy would have compared with epsilon.  The overlap with the
+        count images is not computed and the images stay as they are (two launches fewer per acting lock-step).  The temperature
+        starts at ``temp_start`` (1.0) and follows t <- (t - temp_end) * temp_decay + temp_end per lock-step (``temp_end`` 0.1,
+        ``temp_decay`` 0.999: the reference's form, per lock-step as epsilon's); epsilon is left alone.  It is a function of the
+        lock-step count alone, so ranks agree; it is checkpointed.  act(greedy=True) and evaluate() stay greedy.  The temp_*
+        arguments are refused without the option.  "epsilon_greedy" is the loop as it was: no launch of this."""
+        self.exploration = str(exploration)
+        if self.exploration not in ("epsilon_greedy", "boltzmann"):
+            raise ValueError(f"VecDQN(exploration={exploration!r}): one of 'epsilon_greedy', 'boltzmann'")
+        if self.exploration != "boltzmann" and (temp_start, temp_end, temp_decay) != (1.0, 0.1, 0.999):
+            raise ValueError("VecDQN(temp_start=..., temp_end=..., temp_decay=...) shape the temperature of Boltzmann exploration: "
+                             "they need exploration='boltzmann' (epsilon-greedy has no temperature)")
+        self.temp_start, self.temp_end, self.temp_decay = float(temp_start), float(temp_end), float(temp_decay)
+        if self.exploration == "boltzmann":
+            from robotoddler.training.successor_dqn import check_temperature_schedule
+            check_temperature_schedule(self.temp_start, self.temp_end, self.temp_decay, who="VecDQN(exploration='boltzmann')")
+        self.temperature = self.temp_start
+        self.explored_fraction = None                        # Boltzmann: the share of the last lock-step's valid envs off the arg-max
+        self._ex_w = None
         self.priority_alpha, self.priority_refresh = float(priority_alpha), bool(priority_refresh)
         self.priority_beta = None if priority_beta is None else float(priority_beta)
         self.priority_beta_anneal = int(priority_beta_anneal)
@@ -210,7 +235,8 @@ class VecDQN:
         self.episodes_done = 0
         self.env_steps = 0
         # (env-steps, finished episodes) of a lock-step; n-step returns on one rank: and the emitted rows
-        self._counts_host = torch.zeros(3 if self.n_step > 1 else 2, dtype=torch.int64).pin_memory()
+        # Boltzmann exploration: and, last, the envs whose draw left the first maximum
+        self._counts_host = torch.zeros((3 if self.n_step > 1 else 2) + (self.exploration == "boltzmann"), dtype=torch.int64).pin_memory()
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
         # (a task family -- RandomBridges -- keeps them per class as well: one row per span / height n = 0..hi)
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
@@ -492,12 +518,21 @@ class VecDQN:
     def _act_on(self, env, step_images, explore_gen, epsilon, greedy):
         """One lock-step of acting on ``env``: epsilon-greedy choice (exploring envs draw from ``explore_gen`` and take the
         candidate that overlaps least with the count images ``step_images`` [K + 1, S, S], which get the explored rasters
-        added), records, env.step.  -> (rec [E, W], valid [E], q of the chosen rows [E])."""
+        added; exploration="boltzmann": a draw from softmax(q / temperature) per env, ``epsilon`` and the count images unused),
+        records, env.step.  -> (rec [E, W], valid [E], q of the chosen rows [E])."""
         E = env.E
         stable = self._stable_flags(env)
         idx, row_env, seg, rep = self._rows(env, stable)
         q_sel = torch.zeros(E, dtype=torch.float32, device=self.device)
-        if idx.numel():
+        if idx.numel() and getattr(self, "exploration", "epsilon_greedy") == "boltzmann":
+            # every env draws its row from softmax(q / temperature) with its own uniform, in ONE launch (bridges_boltzmann_select;
+            # greedy: the first maximum, as below); no overlap with the count images is computed and none is added to them.  Envs
+            # in the same state still share their representative's rows, but stop acting alike sooner than under a greedy choice
+            q = self._policy_q(env, idx, row_env, stable)
+            u = torch.rand(E, generator=explore_gen, device=self.device)
+            sel_compact, sel_index, q_sel, self._ex_w, _p = ops.boltzmann_select(seg, q, u, self.temperature, greedy, idx,
+                                                                                 env.cand_offset[:E], rep=rep)
+        elif idx.numel():
             step_of_row = env.n_blocks[row_env].long()
             q = self._policy_q(env, idx, row_env, stable)
             if self._factored(self.policy_net) or self.task_channels:
@@ -521,6 +556,7 @@ class VecDQN:
         else:
             sel_compact = torch.zeros(E, dtype=torch.long, device=self.device)
             sel_index = (sel_compact - env.cand_offset[:E].long()).clamp(min=0).to(torch.int32)
+            self._ex_w = None                                     # (Boltzmann: no env drew anything)
         # the record of the lock-step in two launches around the step (bridges_record_state / _result); the torch formulation
         # R.snapshot + R.make_records (~35 launches) is what tests/test_gpu_vec_dqn.py compares them with
         rec = R.pack_state(env, sel_compact)
@@ -556,6 +592,9 @@ class VecDQN:
         (the eval env's seed, env, episode 0): a fixed held-out task set, not fresh tasks per evaluation."""
         if eval_env is self.env:
             raise ValueError("evaluate() needs an env of its own: the training env's episodes would be cut short")
+        if float(epsilon) > 0.0 and getattr(self, "exploration", "epsilon_greedy") == "boltzmann":
+            raise ValueError("evaluate(epsilon > 0) explores with the epsilon-greedy rule on count images; an agent built with "
+                             "exploration='boltzmann' evaluates greedily only (epsilon=0)")
         if bool(getattr(eval_env, "stable_actions_only", False)) != self.stable_actions_only:
             raise ValueError("the evaluation env's stable_actions_only must match the training env's")
         if bool(getattr(eval_env, "per_env_tasks", False)) != self.per_env_tasks:
@@ -896,6 +935,8 @@ class VecDQN:
             blob["curriculum"] = self.curriculum.state_dict()
         if getattr(self, "priority_beta", None) is not None:  # one more key: the annealing clock of the weights' exponent
             blob["priority_beta_calls"] = int(self.priority_beta_calls)
+        if getattr(self, "exploration", "epsilon_greedy") == "boltzmann":      # one more key: where the schedule stands
+            blob["temperature"] = float(self.temperature)
         torch.save(blob, path)
 
     def load_extra(self, path):
@@ -929,6 +970,8 @@ class VecDQN:
             self.curriculum.load_state_dict(blob["curriculum"])
         if getattr(self, "priority_beta", None) is not None:  # (a file of a run without the option carries no entry: 0)
             self.priority_beta_calls = int(blob.get("priority_beta_calls", 0))
+        if getattr(self, "exploration", "epsilon_greedy") == "boltzmann":      # (a file of a run without the option: temp_start)
+            self.temperature = float(blob.get("temperature", self.temp_start))
         return blob["counters"]
 
     # ------------------------------------------------------------------ driver
@@ -974,6 +1017,9 @@ class VecDQN:
             counts.append(folded[1].sum())
         elif self.n_step > 1:
             counts.append(torch.zeros_like(counts[0]))
+        boltzmann = self.exploration == "boltzmann"
+        if boltzmann:                                   # the envs that left the arg-max ride with the counts: no wait of their own
+            counts.append((self._ex_w * valid).sum().to(torch.int64) if self._ex_w is not None else torch.zeros_like(counts[0]))
         self._counts_host.copy_(torch.stack(counts), non_blocking=True)
         arrived = torch.cuda.Event()
         arrived.record()
@@ -981,6 +1027,8 @@ class VecDQN:
         arrived.synchronize()                           # passed already unless the rows came out of the env's cache
         n_valid, n_done = int(self._counts_host[0]), int(self._counts_host[1])
         self.env_steps += n_valid
+        if boltzmann:
+            self.explored_fraction = int(self._counts_host[-1]) / n_valid if n_valid else None
         if self.n_step > 1:
             if folded is None:
                 # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
@@ -1002,7 +1050,10 @@ class VecDQN:
             self.episodes_done += int((allrec[:, R.O_DONE] > 0.5).sum().item())
         losses = self.train_steps(n_train_steps, defer=defer_losses)
         self.update_target()
-        self.epsilon = (self.epsilon - self.eps_end) * self.eps_decay + self.eps_end
+        if boltzmann:                                   # (epsilon is left alone: nothing reads it in this mode)
+            self.temperature = (self.temperature - self.temp_end) * self.temp_decay + self.temp_end
+        else:
+            self.epsilon = (self.epsilon - self.eps_end) * self.eps_decay + self.eps_end
         return losses, allrec
 
 
@@ -1053,6 +1104,8 @@ def lockstep_log_values(info):
     vals = dict(reward=info['mean_reward'], lin_reward=info['mean_lin_reward'], avg_loss=info['avg_loss'],
                 num_steps=info['lockstep_env_steps'], epsilon=info['epsilon'], env_steps=info['env_steps'],
                 steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
+    if 'temperature' in info:                                # Boltzmann exploration only
+        vals.update(temperature=info['temperature'], explored_fraction=info.get('explored_fraction'))
     by_class = info.get('success_by_class')
     if by_class is not None:
         lo = info.get('class_lo', 0)
@@ -1084,7 +1137,7 @@ def next_multiple(n, every):
 
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
-    from robotoddler.training.successor_dqn import EVAL_DEFAULTS, make_nets, track_run_sinks
+    from robotoddler.training.successor_dqn import EVAL_DEFAULTS, exploration_from_args, make_nets, track_run_sinks
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
@@ -1132,7 +1185,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1),
                    double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
                    priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
-                   priority_beta_anneal=args.get('priority_beta_anneal', 0))
+                   priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -1217,6 +1270,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                     mean_lin_reward=None, epsilon=agent.epsilon, lockstep_env_steps=agent.env_steps - steps_before,
                     steps_per_s=(agent.env_steps - steps_at_start) * world / max(time.time() - t0, 1e-9),
                     **{k: None for k in EPISODE_KEYS})
+        if agent.exploration == "boltzmann":                 # (the temperature the NEXT lock-step draws at, as epsilon above)
+            info.update(temperature=agent.temperature, explored_fraction=agent.explored_fraction)
         if eval_envs > 0 and agent.episodes_done >= next_eval:
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)

@@ -508,6 +508,28 @@ int bridges_eps_greedy_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, 
                               const float* u, float eps, int32_t greedy, const int64_t* idx, const int32_t* cand_offset,
                               const int32_t* rep, int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w, void* stream);
 
+/* Boltzmann exploration for every env at once: env e draws one of its rows lo = seg_lo[e] .. hi - 1 = seg_hi[e] - 1 of q / idx
+ * (as for bridges_eps_greedy_select; rep may be NULL) with probability proportional to exp(q / temperature).  The rule, in
+ * float64, with T = (double)temperature > 0 and the uniform draw u[e] in [0, 1):
+ *   - a row is ELIGIBLE if its q is neither NaN nor -inf; m = the largest eligible q;
+ *   - weights: w_j = exp(((double)q_j - m) / T) for an eligible row, 0 for any other; if m is +inf: 1 for the +inf rows, else 0;
+ *   - c_j = w_lo + .. + w_j in row order, total = c_{hi-1}, target = (double)u[e] * total;
+ *   - the row is the first j with c_j > target (strict); if rounding leaves none, the last row with w_j > 0;
+ *   - p_sel[e] = w_row / total, rounded to float32 once;
+ *   - no row eligible: row lo, p_sel 0, explore_w 0;  no rows (hi <= lo): row 0, q_sel 0, p_sel 0, explore_w 0;
+ *   - explore_w[e] = 1 if the env has rows and the row is not the first maximum among its eligible rows, else 0;
+ *   - greedy != 0: the row, sel_* and q_sel of bridges_eps_greedy_select(greedy = 1) on the same q, p_sel 1 (0 without rows),
+ *     explore_w 0.
+ * sel_compact[e] = idx[row], sel_index[e] = max(sel_compact - cand_offset[rep ? rep[e] : e], 0), q_sel[e] = q[row]; the row is
+ * clamped to n_rows - 1.  T -> 0 draws uniformly among the exact ties of the maximum, T -> inf uniformly among the eligible rows,
+ * and q / T far above 709 cannot overflow (the exponent is never positive).  Envs that share rows draw each with their own u[e].
+ * The order of every sum is fixed: the same inputs give the same bits.  The device's prefix sums are added in another order than
+ * c_j above (a scan per 64 rows), so a target within a few ulp of a c_j may fall to the neighbouring row.
+ * E == 0: nothing to do.  Refused: n_rows < 1, a temperature that is not finite or not > 0, a NULL array (rep excepted). */
+int bridges_boltzmann_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, const float* u,
+                             float temperature, int32_t greedy, const int64_t* idx, const int32_t* cand_offset, const int32_t* rep,
+                             int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w, float* p_sel, void* stream);
+
 /* --- transition records of the vectorised loop ------------------------------------------------------------------
  * One float64 row per transition: the compact form of the reference's Transition (successor_dqn.py:27-44) -- the block
  * list of s, the placed block and the scalars; rasters and candidate sets are re-generated when a record is sampled.

@@ -1,0 +1,95 @@
+"""The Boltzmann selection of a lock-step on the device against what it replaces and against a torch formulation, on identical
+inputs in one process and at the loop's launch shape (one wave per env over its rows of the Q pass):
+  boltzmann    ops.boltzmann_select (bridges_boltzmann_select: one launch)
+  eps_greedy   what epsilon-greedy acting launches in its place: ops.bits_dot (the overlap of every row with the count image of
+               its step), ops.eps_greedy_select and ops.bits_accumulate_ (the count images of the explored choices)
+  torch        the segmented softmax draw in torch: segment maxima by scatter_reduce, exp in float64, one cumsum over all rows,
+               per-env targets, searchsorted, clamp, the gathers
+HIP events around single calls, the three legs alternating, warm-up first; one JSON line per shape with medians and spread.
+    python tools/boltzmann_select_bench.py [--envs 1024 4096] [--rows_per_env 40] [--temperature 1.0] [--reps 40]"""
+import argparse, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
+import numpy as np
+import torch
+from bridges_hip import ops
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, nargs="+", default=[1024, 4096], help="envs of the lock-step (one JSON line each)")
+ap.add_argument("--rows_per_env", type=int, default=40, help="mean rows of an env; the lengths are drawn from 1 .. 2 * this")
+ap.add_argument("--temperature", type=float, default=1.0)
+ap.add_argument("--steps", type=int, default=10, help="count images (episode steps)")
+ap.add_argument("--reps", type=int, default=40)
+ap.add_argument("--warmup", type=int, default=10)
+a = ap.parse_args()
+assert a.reps >= 20
+dev = torch.device("cuda:0")
+for E in a.envs:
+    g = torch.Generator().manual_seed(E)
+    lengths = torch.randint(1, 2 * a.rows_per_env + 1, (E,), generator=g)
+    seg = torch.cat([torch.zeros(1, dtype=torch.int64), lengths.cumsum(0)]).to(torch.int32).to(dev)
+    n = int(seg[-1])
+    lo, hi = seg[:-1].long(), seg[1:].long()
+    row_env = torch.repeat_interleave(torch.arange(E), lengths).to(dev)
+    q = torch.randn(n, generator=g).to(dev)
+    u = torch.rand(E, generator=g).to(dev)
+    idx = torch.arange(n, device=dev)
+    cand_offset = seg[:-1].contiguous()
+    cand_bits = torch.randint(-2 ** 62, 2 ** 62, (n, 64), generator=g, dtype=torch.int64).to(dev)
+    images = torch.zeros((a.steps + 1, 64, 64), device=dev)
+    step_of_env = torch.randint(0, a.steps, (E,), generator=g).to(dev)
+    step_of_row = step_of_env[row_env]
+    T = a.temperature
+
+    def boltzmann():
+        return ops.boltzmann_select(seg, q, u, T, False, idx, cand_offset)
+
+    def eps_greedy():
+        join = ops.bits_dot(cand_bits, images, step_of_row, bits_row=idx)
+        out = ops.eps_greedy_select(seg, q, join, u, 0.5, False, idx, cand_offset)
+        ops.bits_accumulate_(images, cand_bits, step_of_env, weight=out[3], bits_row=out[0])
+        return out
+
+    def formulation():
+        m = torch.full((E,), -torch.inf, device=dev).scatter_reduce_(0, row_env, q, reduce="amax")
+        w = torch.exp((q.double() - m.double()[row_env]) / T)
+        c = torch.cumsum(w, 0)
+        before = torch.where(lo > 0, c[(lo - 1).clamp(min=0)], torch.zeros_like(c[:1]))
+        target = before + u.double() * (c[hi - 1] - before)
+        row = torch.minimum(torch.maximum(torch.searchsorted(c, target, right=True), lo), hi - 1)
+        sel = idx[row]
+        first_max = torch.full((E,), n, dtype=torch.int64, device=dev).scatter_reduce_(
+            0, row_env, torch.where(q == m[row_env], idx, n), reduce="amin")
+        return sel, (sel - cand_offset).to(torch.int32), q[row], (row != first_max).float(), (w[row] / (c[hi - 1] - before)).float()
+    k, f = boltzmann(), formulation()
+    same = (k[0] == f[0]).float().mean().item()          # one global cumsum is another order of additions: near-ties may differ
+    assert same > 0.999, same
+    legs = (("boltzmann", boltzmann), ("eps_greedy", eps_greedy), ("torch", formulation))
+    for _ in range(a.warmup):
+        for _name, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in legs}
+    for _ in range(a.reps):
+        for name, fn in legs:
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            out = fn()
+            stop.record()
+            stop.synchronize()
+            times[name].append(start.elapsed_time(stop) * 1e3)              # us
+            del out
+    summary = {}
+    for name, t in times.items():
+        t = np.array(t)
+        q1, med, q3 = np.percentile(t, [25, 50, 75])
+        summary[name] = dict(median_us=float(med), min_us=float(t.min()), max_us=float(t.max()), iqr_us=float(q3 - q1), calls=len(t))
+    b = summary["boltzmann"]
+    print(json.dumps(dict(config=dict(vars(a), envs=E, rows=n), same_rows_as_torch=same, **summary,
+                          eps_greedy_over_boltzmann=summary["eps_greedy"]["median_us"] / b["median_us"],
+                          torch_over_boltzmann=summary["torch"]["median_us"] / b["median_us"],
+                          inside_the_spread={name: bool(abs(summary[name]["median_us"] - b["median_us"])
+                                                        <= max(summary[name]["max_us"] - summary[name]["min_us"], b["max_us"] - b["min_us"]))
+                                             for name in ("eps_greedy", "torch")},
+                          note="HIP events around single calls (host launch gaps included), the legs alternating in one process; "
+                               "spread = max - min of the timed calls")), flush=True)

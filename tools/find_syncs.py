@@ -27,12 +27,14 @@ ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI", help="a
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, VecAssemblyGym
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
-                                                add_priority_arguments, build_parser, check_curriculum, make_nets, priority_from_args)
+                                                add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
+                                                exploration_from_args, make_nets, priority_from_args)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 add_curriculum_arguments(ap)
 add_n_step_argument(ap)
 add_double_q_argument(ap)
 add_priority_arguments(ap, prioritized_flag=True)
+add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 a = ap.parse_args()
 sizes = tuple(int(v) for v in a.random_bridge_length.split(":")) if a.random_bridge_length else None
 check_curriculum(vars(a), sizes)
@@ -49,7 +51,7 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, ta
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
                "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes), per_env_obstacles=bool(sizes),
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)))
+               **priority_from_args(vars(a)), **exploration_from_args(vars(a)))
 
 
 def lockstep():

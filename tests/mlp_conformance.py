@@ -1,4 +1,5 @@
-"""Conformance of the SuccessorMLP step kernels (csrc/mlp_kernels.hip) and the scalar-ish DQN kernels (csrc/dqn_kernels.hip):
+"""Conformance of the SuccessorMLP step kernels (csrc/mlp_kernels.hip, the middle-layer stack included) and the scalar-ish DQN
+kernels (csrc/dqn_kernels.hip):
 shape tables, probe data, float64 references with their error bounds, the acceptance rule and deliberately defective twins.
 Test infrastructure, not a test module: nothing here needs a GPU -- every function takes the device -- so
 tests/test_cpu_mlp_conformance_refs.py checks on the CPU that the references accept a clean float32 evaluation and reject every
@@ -518,3 +519,239 @@ def td_conform(name, got, lib, ref, ref_rows, shape=None):
     conform(name + ".q", got[0], lib[0], *ref["q"], shape)
     if ref["sf"] is not None:
         conform(name + ".sf", got[1], lib[1], *ref["sf"], shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The middle stack: k_mid_fwd / k_mid_bwd<256,128,64,128,256> (one launch each way for the step's four middle Linear + ReLU
+# layers, the backward launch with "rider" workgroups that apply another layer's Adam update) and k_rows2<256,128,64,true> /
+# k_rows2<64,128,256,false> (the same stack for many rows, two layers a launch, the hidden activation in LDS only).
+
+MID_DIMS = (256, 128, 64, 128, 256)
+MID_ROWS_N = (1, 31, 32, 33, 63, 8193, 16389)   # partial / full / one-past tiles; 8193: the first row of a second grid round;
+                                                # 16389: a third round, so the prefetch of `next` is live in the second
+MID_ROWS_STRIDES = ((256, 256), (260, 257), (320, 300), (256, 300), (320, 256))      # (x_stride, y_stride) in floats
+MID_ROWS_STRIDED_N = (1, 31, 32, 8193)          # the rows the strided pairs run at: the three smallest and one large
+MID_REST_N = (0, 4, 4100, 16388, 4 * (249 * 4096) + 4)       # the riders' Adam range, see rider_plan
+
+
+def T(K):
+    """The term count of a layer's product as lin_forward_ref counts it."""
+    return K + ceil_div(K, 64) + 4
+
+
+def rows_plan(n_rows):
+    """(workgroups, grid rounds) of either launch of bridges_mlp_mid_rows (csrc/api.hip: a workgroup per 32-row tile, the grid
+    clamped to 256, the kernel strides over the tiles)."""
+    tiles = ceil_div(n_rows, 32)
+    grid = min(max(tiles, 1), 256)
+    return grid, ceil_div(tiles, grid)
+
+
+def rider_plan(rest_n):
+    """(rider workgroups, stride rounds, float4 groups in the last round) of bridges_mlp_mid_backward's Adam range
+    (csrc/api.hip: a rider per 4096 float4 groups, at most 248; k_mid_bwd: a rider's 1024 threads stride over the groups)."""
+    n4 = rest_n >> 2
+    riders = min(ceil_div(n4, 4096), 248)
+    if riders == 0:
+        return 0, 0, 0
+    stride = riders * 1024
+    return riders, ceil_div(n4, stride), n4 - (ceil_div(n4, stride) - 1) * stride
+
+
+def mid_probe(device, seed=0):
+    """The stack's probe data, layer l from lin_probe(32, D[l], D[l + 1]) (so every layer carries the edge ramps and scaled
+    first / last rows): W [4], b [4], x = the forward's acts[0], acts [5] = the BACKWARD's activations (mask_like: positives,
+    +0, -0.0 and negatives; acts[l] is both the mask of dz[l] and the A operand of dW[l]), dz4 [32, 256]."""
+    D = MID_DIMS
+    prs = [lin_probe(32, D[l], D[l + 1], device, seed) for l in range(4)]
+    g = torch.Generator().manual_seed(1000003 * seed + 4)
+    acts = [pr["act"] for pr in prs] + [mask_like(g, 32, D[4]).to(device)]
+    return dict(W=[pr["w"] for pr in prs], b=[pr["b"] for pr in prs], x=prs[0]["x"], acts=acts, dz4=prs[3]["dz"])
+
+
+def rows_probe(n, device, seed=0, nan_row=None):
+    """x [n, 256]: the pre-activation in front of the stack for n rows -- dense noise (about half negative), ramps in the first
+    and last 8 columns, -0.0 sprinkled in, first and last row scaled, and (``nan_row``) one row of NaN."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * n + 13)
+    x = dense(g, n, MID_DIMS[0])
+    edge_ramps_(x, 1.0, -2.0)
+    x[torch.rand(n, MID_DIMS[0], generator=g) < 0.05] = -0.0
+    x[0] *= 2.0
+    x[-1] *= 0.5
+    if nan_row is not None:
+        x[nan_row] = math.nan
+    return x.contiguous().to(device)
+
+
+def mid_forward_lib(W, b, x, relu_in=False):
+    """Plain float32 torch -> [acts[1], .., acts[4]]."""
+    a, out = (F.relu(x) if relu_in else x), []
+    for w_, b_ in zip(W, b):
+        a = F.relu(F.linear(a, w_, b_))
+        out.append(a)
+    return out
+
+
+def mid_forward_conform(name, x, outs, W, b, shape=None):
+    """k_mid_fwd writes every activation, so each link is judged as ONE layer: outs[l] against lin_forward_ref on the stack's
+    OWN input of that layer (x, outs[0], ..), the library figure F.linear + relu on the same input."""
+    ins = [x] + list(outs[:-1])
+    for l, (a, y) in enumerate(zip(ins, outs)):
+        ref, bound = lin_forward_ref(a, W[l], b[l], True)
+        conform(f"{name}.acts{l + 1}", y, lin_forward_lib(a, W[l], b[l], True), ref, bound, shape)
+
+
+def chain2_ref(x, Wa, ba, Wb, bb, relu_in):
+    """One k_rows2 launch: y = relu(h Wb^T + bb), h = relu(x' Wa^T + ba), x' = relu(x) if relu_in -> (float64 y, bound).  h never
+    leaves LDS, so its error is carried through the second layer (ReLU is 1-Lipschitz):
+      B1 = dot_bound(T(DA), |x'| |Wa|^T + |ba|);  B2 = dot_bound(T(DB), |h| |Wb|^T + |bb|) + B1 |Wb|^T."""
+    xd, Wa, ba, Wb, bb = (t.double() for t in (x, Wa, ba, Wb, bb))
+    if relu_in:
+        xd = xd.clamp_min(0)
+    h = (xd @ Wa.T + ba).clamp_min(0)
+    B1 = dot_bound(T(Wa.shape[1]), xd.abs() @ Wa.abs().T + ba.abs())
+    y = (h @ Wb.T + bb).clamp_min(0)
+    return y, dot_bound(T(Wb.shape[1]), h.abs() @ Wb.abs().T + bb.abs()) + B1 @ Wb.abs().T
+
+
+def rows_lib(W, b, x):
+    """bridges_mlp_mid_rows in plain float32 torch -> (mid [n, 64], y [n, 256])."""
+    a = mid_forward_lib(W, b, x, relu_in=True)
+    return a[1], a[3]
+
+
+def rows_conform(name, x, mid, y, W, b, shape=None, keep=None):
+    """The first launch judged on ``mid`` from x, the second on ``y`` from the given ``mid`` (the kernel's own), each against
+    chain2_ref; ``keep``: a row mask (the rows without a NaN, which conform would count as outside)."""
+    sel = (lambda t: t) if keep is None else (lambda t: t[keep])
+    ref, bound = chain2_ref(x, W[0], b[0], W[1], b[1], True)
+    lb = F.relu(F.linear(F.relu(F.linear(F.relu(x), W[0], b[0])), W[1], b[1]))
+    conform(f"{name}.mid", sel(mid), sel(lb), sel(ref), sel(bound), shape)
+    ref, bound = chain2_ref(mid, W[2], b[2], W[3], b[3], False)
+    lb = F.relu(F.linear(F.relu(F.linear(mid, W[2], b[2])), W[3], b[3]))
+    conform(f"{name}.y", sel(y), sel(lb), sel(ref), sel(bound), shape)
+
+
+def mid_backward_ref(W, acts, dz4):
+    """k_mid_bwd in float64 with the allowance carried down the chain -> {dW0..3, db0..3, dz0: (reference, bound)}.  The masks
+    come from the given acts, so no float32 / float64 decision can differ.  z_4 = dz4, B_4 = 0; for l = 3 .. 0:
+      dW[l] = z_{l+1}^T acts[l]        bound dot_bound(32, |z_{l+1}|^T |acts[l]|) + B_{l+1}^T |acts[l]|
+      db[l] = sum over rows of z_{l+1} bound dot_bound(32, sum |z_{l+1}|) + sum B_{l+1}
+      z_l   = (z_{l+1} W[l]) [acts[l] > 0]
+      B_l   = (dot_bound(T(D[l+1]), |z_{l+1}| |W[l]|) + B_{l+1} |W[l]|) [acts[l] > 0]
+    z_0 is dz[0]; where a mask is off the bound is zero and the result must be exactly 0."""
+    z, B, out = dz4.double(), torch.zeros_like(dz4, dtype=torch.float64), {}
+    for l in (3, 2, 1, 0):
+        a, w = acts[l].double(), W[l].double()
+        out[f"dW{l}"] = (z.T @ a, dot_bound(32, z.abs().T @ a.abs()) + B.T @ a.abs())
+        out[f"db{l}"] = (z.sum(0), dot_bound(32, z.abs().sum(0)) + B.sum(0))
+        on = (acts[l] > 0).double()
+        z, B = (z @ w) * on, (dot_bound(T(w.shape[0]), z.abs() @ w.abs()) + B @ w.abs()) * on
+    out["dz0"] = (z, B)
+    return out
+
+
+def mid_backward_lib(W, acts, dz4):
+    """The same chain in plain float32 torch; masks by torch.where, so a non-finite gradient under a dead unit gives 0 as
+    autograd's ReLU backward does."""
+    z, out = dz4, {}
+    for l in (3, 2, 1, 0):
+        out[f"dW{l}"], out[f"db{l}"] = z.T @ acts[l], z.sum(0)
+        z = torch.where(acts[l] > 0, z @ W[l], torch.zeros_like(acts[l]))
+    out["dz0"] = z
+    return out
+
+
+MID_BWD_KEYS = tuple(f"{k}{l}" for l in (3, 2, 1, 0) for k in ("dW", "db")) + ("dz0",)
+
+
+def mid_backward_conform(name, got, W, acts, dz4, shape=None):
+    refs, lb = mid_backward_ref(W, acts, dz4), mid_backward_lib(W, acts, dz4)
+    for k in MID_BWD_KEYS:
+        conform(f"{name}.{k}", got[k], lb[k], *refs[k], shape)
+
+
+# defective twins of the stack (float32, plain torch)
+def twin_mid_fwd_quarter_left_out(W, b, x, relu_in=False):
+    """Layer 1 (128 -> 64) without the third of its four K quarters (a wave's partial sum never added)."""
+    a = mid_forward_lib(W[:1], b[:1], x, relu_in)
+    keep = [k for k in range(W[1].shape[1]) if not 64 <= k < 96]
+    h = F.relu(F.linear(a[0][:, keep], W[1][:, keep], b[1]))
+    return a + [h] + mid_forward_lib(W[2:], b[2:], h)
+
+
+def twin_mid_fwd_last_tile_without_bias(W, b, x, relu_in=False):
+    """Columns 224 .. 255 of the last layer without their bias."""
+    b3 = b[3].clone()
+    b3[-32:] = 0.0
+    return mid_forward_lib(W, b[:3] + [b3], x, relu_in)
+
+
+def twin_mid_fwd_bf16_operands(W, b, x, relu_in=False):
+    """Layer 2 (64 -> 128) with both operands rounded to bfloat16 (a matrix-core instruction of the wrong type)."""
+    a = mid_forward_lib(W[:2], b[:2], x, relu_in)
+    h = F.relu(F.linear(a[1].bfloat16().float(), W[2].bfloat16().float(), b[2]))
+    return a + [h] + mid_forward_lib(W[3:], b[3:], h)
+
+
+def rows_from(fwd):
+    """A forward twin as a twin of bridges_mlp_mid_rows."""
+    def fn(W, b, x):
+        a = fwd(W, b, x, True)
+        return a[1], a[3]
+    return fn
+
+
+def twin_rows_relu_in_forgotten(W, b, x):
+    a = mid_forward_lib(W, b, x, relu_in=False)
+    return a[1], a[3]
+
+
+def twin_rows_last_tile_from_row_n_minus_1(W, b, x):
+    """Every row of a partial last tile computed from row n - 1 (the clamp of the fetch applied to all of the tile's rows)."""
+    n = x.shape[0]
+    x2 = x.clone()
+    if n % 32:
+        x2[n - n % 32:] = x[n - 1]
+    return rows_lib(W, b, x2)
+
+
+def twin_mid_bwd_inner_mask_ge_zero(W, acts, dz4):
+    """The mask of dz[2] taken as acts[2] >= 0: +0 and -0.0 pass."""
+    z, out = dz4, {}
+    for l in (3, 2, 1, 0):
+        out[f"dW{l}"], out[f"db{l}"] = z.T @ acts[l], z.sum(0)
+        z = torch.where((acts[l] >= 0) if l == 2 else (acts[l] > 0), z @ W[l], torch.zeros_like(acts[l]))
+    out["dz0"] = z
+    return out
+
+
+def twin_mid_bwd_dw_from_unmasked_gradient(W, acts, dz4):
+    """dW[l], l < 3, formed from the product before its mask."""
+    out = mid_backward_lib(W, acts, dz4)
+    z = dz4
+    for l in (3, 2, 1):
+        raw = z @ W[l]
+        out[f"dW{l - 1}"] = raw.T @ acts[l - 1]
+        z = torch.where(acts[l] > 0, raw, torch.zeros_like(raw))
+    return out
+
+
+def twin_mid_bwd_db_even_rows_only(W, acts, dz4):
+    """db summed over rows 0, 2, .., 30: the half-wave that holds the odd rows never joins (a lost cross-half shuffle)."""
+    out = mid_backward_lib(W, acts, dz4)
+    z = dz4
+    for l in (3, 2, 1, 0):
+        out[f"db{l}"] = z[0::2].sum(0)
+        z = torch.where(acts[l] > 0, z @ W[l], torch.zeros_like(acts[l]))
+    return out
+
+
+def twin_rider_first_round_only(p, g, m, v, t, hyper=ADAM_HYPER):
+    """Each rider thread updates its first float4 group only: the range beyond the first stride round keeps its old values."""
+    out = adam_lib(p, g, m, v, t, hyper)
+    riders = rider_plan(p.numel())[0]
+    done = min(4 * riders * 1024, p.numel())
+    for k, old in (("p", p), ("m", m), ("v", v)):
+        out[k] = torch.cat([out[k][:done], old[done:]])
+    return out

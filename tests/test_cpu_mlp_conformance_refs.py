@@ -4,7 +4,8 @@
   yardstick): the references and bounds alone stay inside the conditions the GPU tests put on the kernels.
 * Every defective twin -- a float32 evaluation wrong in one way a kernel could be -- is rejected at every row where its defect
   applies, and applies to at least one row: the evidence that tests/test_gpu_mlp_conformance.py would notice such a kernel.
-* The tables reach the branches they are there for (the split counts csrc/api.hip would choose)."""
+* The tables reach the branches they are there for (the split counts, grid rounds and rider counts csrc/api.hip would choose).
+* The middle stack (k_mid_fwd, k_mid_bwd with its riders, k_rows2) has the same three kinds of test at the end of the module."""
 import pytest
 import torch
 
@@ -138,3 +139,112 @@ def test_float32_td_target_passes_and_the_last_maximum_is_rejected(sf_dim):
     assert rows[:7] == [0, rows[1], rows[2], lo[3] + 200, lo[4] + 44, lo[5] + 5, lo[6]] and rows[7] == M.NO_ROW
     assert rows[8] == lo[3] + 200 and rows[9] == lo[5] + 5 + 256          # the shared ranges: the second starts behind lo + 5
     assert [h - l for l, h in zip(lo, pr["hi"])][:6] == list(M.TD_LENGTHS)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the middle stack: k_mid_fwd, k_mid_bwd with its riders, k_rows2
+
+MID_SEEDS = (0, 1)
+ROWS_CPU_N = tuple(n for n in M.MID_ROWS_N if n <= 8193)       # 16389 adds a grid round, not a numerical case: left to the GPU
+
+
+def mid_forward_conform_all(seed, fwd):
+    pr = M.mid_probe(CPU, seed)
+    M.mid_forward_conform("mid_fwd", pr["x"], fwd(pr["W"], pr["b"], pr["x"]), pr["W"], pr["b"], seed)
+
+
+def rows_conform_all(n, fn):
+    pr = M.mid_probe(CPU)
+    x = M.rows_probe(n, CPU)
+    mid, y = fn(pr["W"], pr["b"], x)
+    M.rows_conform("mid_rows", x, mid, y, pr["W"], pr["b"], n)
+
+
+def mid_backward_conform_all(seed, bwd):
+    pr = M.mid_probe(CPU, seed)
+    M.mid_backward_conform("mid_bwd", bwd(pr["W"], pr["acts"], pr["dz4"]), pr["W"], pr["acts"], pr["dz4"], seed)
+
+
+def rider_conform_all(n, t, fn):
+    p, g, m, v = M.adam_probe(n, CPU, seed=3)
+    refs, got, lib = M.adam_ref(p, g, m, v, t), fn(p, g, m, v, t), M.adam_lib(p, g, m, v, t)
+    for k in ("p", "m", "v"):
+        M.conform(f"rider.{k}", got[k], lib[k], *refs[k], (n, t))
+
+
+@pytest.mark.parametrize("seed", MID_SEEDS)
+def test_float32_middle_stack_passes(seed):
+    mid_forward_conform_all(seed, M.mid_forward_lib)
+    mid_backward_conform_all(seed, M.mid_backward_lib)
+
+
+@pytest.mark.parametrize("n", ROWS_CPU_N)
+def test_float32_two_layer_chains_pass(n):
+    rows_conform_all(n, M.rows_lib)
+
+
+@pytest.mark.parametrize("t", M.ADAM_STEPS)
+def test_float32_rider_adam_passes_and_a_single_stride_round_is_rejected(t):
+    hit = []
+    for n in M.MID_REST_N:
+        if n:
+            rider_conform_all(n, t, M.adam_lib)
+        if M.rider_plan(n)[1] > 1:
+            hit.append(n)
+            assert rejected(rider_conform_all, n, t, M.twin_rider_first_round_only), (n, t)
+    assert len(hit) >= 3
+
+
+MID_FWD_TWINS = {"quarter_left_out": M.twin_mid_fwd_quarter_left_out, "last_tile_without_bias": M.twin_mid_fwd_last_tile_without_bias,
+                 "bf16_operands": M.twin_mid_fwd_bf16_operands}
+MID_BWD_TWINS = {"inner_mask_ge_zero": M.twin_mid_bwd_inner_mask_ge_zero, "dw_from_unmasked_gradient": M.twin_mid_bwd_dw_from_unmasked_gradient,
+                 "db_even_rows_only": M.twin_mid_bwd_db_even_rows_only}
+MID_ROWS_TWINS = {          # name -> (twin, applies(n))
+    "relu_in_forgotten": (M.twin_rows_relu_in_forgotten, lambda n: True),
+    "last_tile_from_row_n_minus_1": (M.twin_rows_last_tile_from_row_n_minus_1, lambda n: n % 32 >= 2),
+    **{k: (M.rows_from(f), lambda n: True) for k, f in MID_FWD_TWINS.items()},
+}
+
+
+@pytest.mark.parametrize("twin", sorted(MID_FWD_TWINS))
+def test_defective_forward_stack_twins_are_rejected(twin):
+    for seed in MID_SEEDS:
+        assert rejected(mid_forward_conform_all, seed, MID_FWD_TWINS[twin]), (twin, seed)
+
+
+@pytest.mark.parametrize("twin", sorted(MID_BWD_TWINS))
+def test_defective_backward_stack_twins_are_rejected(twin):
+    for seed in MID_SEEDS:
+        assert rejected(mid_backward_conform_all, seed, MID_BWD_TWINS[twin]), (twin, seed)
+
+
+@pytest.mark.parametrize("twin", sorted(MID_ROWS_TWINS))
+def test_defective_two_layer_chain_twins_are_rejected(twin):
+    fn, applies = MID_ROWS_TWINS[twin]
+    hit = [n for n in ROWS_CPU_N if n < 8193 and applies(n)]
+    assert hit, twin
+    for n in hit:
+        assert rejected(rows_conform_all, n, fn), (twin, n)
+    for n in [n for n in ROWS_CPU_N if not applies(n)][:2]:                # where the defect does not apply the twin IS the operator
+        rows_conform_all(n, fn)
+
+
+def test_middle_stack_tables_reach_their_branches():
+    """From the launch arithmetic of csrc/api.hip (M.rows_plan, M.rider_plan)."""
+    plans = {n: M.rows_plan(n) for n in M.MID_ROWS_N}
+    assert plans[1] == (1, 1) and plans[32] == (1, 1) and plans[33] == (2, 1) and plans[63] == (2, 1)
+    assert plans[8193] == (256, 2) and 8193 == 256 * 32 + 1               # 257 tiles on the clamped grid: one row in round two
+    assert plans[16389] == (256, 3)                                        # a second round with a `next` to prefetch
+    assert any(M.ceil_div(n, 32) > 256 for n in M.MID_ROWS_N)
+    assert {n % 32 for n in M.MID_ROWS_N} >= {0, 1, 31} and any(n % 32 >= 2 and n > 8192 for n in M.MID_ROWS_N)
+    assert set(M.MID_ROWS_STRIDED_N) <= set(M.MID_ROWS_N) and max(M.MID_ROWS_STRIDED_N) > 8192
+    assert {s[0] for s in M.MID_ROWS_STRIDES} == {256, 260, 320} and {s[1] for s in M.MID_ROWS_STRIDES} == {256, 257, 300}
+    assert all(s[0] % 4 == 0 for s in M.MID_ROWS_STRIDES)
+    riders = {n: M.rider_plan(n) for n in M.MID_REST_N}
+    assert riders[0] == (0, 0, 0) and riders[4] == (1, 1, 1)
+    assert riders[4100] == (1, 2, 1)                                       # one rider, a ragged second round
+    assert riders[16388] == (2, 3, 1)                                      # two riders, three rounds, the last ragged
+    big = max(M.MID_REST_N)
+    assert M.ceil_div(big >> 2, 4096) > 248 and riders[big][0] == 248 and riders[big][1] > 4 and riders[big][2] < 248 * 1024
+    assert all(n % 4 == 0 for n in M.MID_REST_N)
+    assert [M.T(K) for K in (256, 128, 64)] == [264, 134, 69]

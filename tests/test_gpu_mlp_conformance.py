@@ -1,9 +1,9 @@
-"""GPU: conformance of the SuccessorMLP step kernels (csrc/mlp_kernels.hip: k_lin_fwd, k_lin_bwd, k_successor_loss and the
-folded Adam update) and of the scalar-ish DQN kernels (csrc/dqn_kernels.hip: k_td_target, k_adam_flat, k_adam_multi,
-k_soft_update) at the entry points of include/bridges_hip.h.
+"""GPU: conformance of the SuccessorMLP step kernels (csrc/mlp_kernels.hip: k_lin_fwd, k_lin_bwd, k_successor_loss, the folded
+Adam update, and the middle stack's k_mid_fwd, k_mid_bwd with its Adam riders and k_rows2) and of the scalar-ish DQN kernels
+(csrc/dqn_kernels.hip: k_td_target, k_adam_flat, k_adam_multi, k_soft_update) at the entry points of include/bridges_hip.h.
 
 Tables, probe data, float64 references, bounds and the acceptance rule come from tests/mlp_conformance.py (checked without a GPU
-by tests/test_cpu_mlp_conformance_refs.py, which also shows that a kernel wrong in one of seven ways would be rejected):
+by tests/test_cpu_mlp_conformance_refs.py, which also shows that a kernel wrong in one of sixteen ways would be rejected):
 
 * every element inside the first-order float32 bound around the float64 result, exact zeros where the kernel must write them;
 * q_kernel <= FACTOR * q_library, the library being torch's float32 result on the same inputs (``Q ...`` lines are printed;
@@ -86,6 +86,8 @@ def poisoned_blocks(t, block, n_blocks=3):
 
 @pytest.mark.parametrize("shape", M.LIN_SHAPES)
 def test_linear_forward_inside_the_bound(shape):
+    """k_lin_fwd, and behind a split-K launch k_lin_fwd_finish, at bridges_linear_forward against lin_forward_ref's float64 result:
+    with the full workspace, without one (one split) and with room for two splits; x_block addressing; repeats bit for bit."""
     rows, K, N = shape
     pr = M.lin_probe(rows, K, N, DEV)
     x, w, b = pr["x"], pr["w"], pr["b"]
@@ -109,6 +111,9 @@ def test_linear_forward_inside_the_bound(shape):
 
 @pytest.mark.parametrize("shape", M.LIN_SHAPES)
 def test_linear_backward_inside_the_bound(shape):
+    """k_lin_bwd<false>, and behind a split-N launch k_lin_dx_finish, at bridges_linear_backward against lin_backward_ref's float64
+    dW, db and masked dx: with and without a mask, with a workspace that cuts the split count, without an input gradient, and
+    through a_block addressing; repeats bit for bit."""
     rows, K, N = shape
     pr = M.lin_probe(rows, K, N, DEV)
     x, w, dz, act = pr["x"], pr["w"], pr["dz"], pr["act"]
@@ -134,22 +139,23 @@ def test_linear_backward_inside_the_bound(shape):
         assert all(torch.equal(got[k], first[k]) for k in got), (blk, bias)
 
 
-def test_linear_refusals_name_their_reason_and_leave_the_output_alone():
+def refused(rc, reason):
+    """A non-zero status, ``reason`` in bridges_last_error() and in what abi.check raises."""
     from bridges_hip import abi
+    assert rc != 0
+    msg = lib().bridges_last_error().decode()
+    assert reason in msg, msg
+    with pytest.raises(abi.BridgesHipError, match=reason):
+        abi.check(rc, "entry point")
+
+
+def test_linear_refusals_name_their_reason_and_leave_the_output_alone():
     L = lib()
     pr = M.lin_probe(64, 70, 33, DEV)
     x, w, b, dz, act = (pr[k] for k in ("x", "w", "b", "dz", "act"))
     y = torch.full((64, 33), SENTINEL, device=DEV)
     dW, db, dx = torch.full((33, 70), SENTINEL, device=DEV), torch.full((33,), SENTINEL, device=DEV), torch.full((64, 70), SENTINEL, device=DEV)
     ws = workspace()
-
-    def refused(rc, reason):
-        assert rc != 0
-        msg = L.bridges_last_error().decode()
-        assert reason in msg, msg
-        with pytest.raises(abi.BridgesHipError, match=reason):
-            abi.check(rc, "entry point")
-
     refused(L.bridges_linear_forward(48, 70, 33, ptr(x), ptr(w), ptr(b), 0, ptr(y), ptr(ws), ws.numel(), None, stream()), "multiple of 32")
     refused(L.bridges_linear_backward(48, 70, 33, ptr(dz), ptr(x), ptr(w), ptr(dW), ptr(db), ptr(act), ptr(dx), ptr(ws), ws.numel(), None, 0,
                                       stream()), "multiple of 32")
@@ -225,6 +231,8 @@ def row_order_sum(loss_rows, batch):
 
 @pytest.mark.parametrize("shape", M.LOSS_SHAPES)
 def test_successor_loss_inside_the_bound(shape):
+    """k_successor_loss<PER_ROW> at bridges_successor_loss / _rows against loss_ref's float64 q, per-row loss and gradient, at two
+    positions of the per-call arrays; exact zeros in padding rows and behind column 2 px."""
     batch, px, nf, use_q, use_sf, per_row = shape
     pr = M.loss_probe(batch, px, nf, per_row, DEV)
     for c in (0, 2):                                                                    # addressing into the per-call arrays
@@ -412,3 +420,241 @@ def test_soft_update_bitwise_below_two_float4(n):
     td = t.to(DEV)
     dqn_ops.soft_update_(td, p.to(DEV), 0.01)
     assert torch.equal(td.cpu(), ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the middle stack, straight through the C ABI: host pointer tables as mlp_ops builds them, outputs full of SENTINEL
+
+MID_DIMS_C = (C.c_int32 * 5)(*M.MID_DIMS)
+F_MID, B_MID, R_MID = "bridges_mlp_mid_forward", "bridges_mlp_mid_backward", "bridges_mlp_mid_rows"
+
+
+def table(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+def fresh(*shape):
+    return torch.full(shape, SENTINEL, device=DEV)
+
+
+def untouched(*tensors):
+    return all(bool((t == SENTINEL).all()) for t in tensors)
+
+
+def same_bits(a, b):
+    """Equal bit for bit (so +0 differs from -0.0); a NaN equals any NaN: its payload is no value of the operator."""
+    na, nb = torch.isnan(a), torch.isnan(b)
+    bits = lambda t, n: torch.where(n, torch.zeros_like(t), t).contiguous().view(torch.int32)
+    return a.shape == b.shape and torch.equal(na, nb) and torch.equal(bits(a, na), bits(b, nb))
+
+
+def off4(t):
+    """A copy of t that starts 4 bytes into an allocation."""
+    buf = fresh(t.numel() + 4)
+    view = buf[1:1 + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def mid_forward(W, b, x):
+    acts = [x.clone()] + [fresh(32, d) for d in M.MID_DIMS[1:]]
+    call(F_MID, 32, 4, MID_DIMS_C, table(W), table(b), table(acts), stream())
+    return acts
+
+
+def mid_backward(W, acts, dz4, rest=(None, None, None, None), rest_n=0, step=None, hyper=M.ADAM_HYPER):
+    """-> ({dW0..3, db0..3, dz0}, the dz table's five tensors)."""
+    D = M.MID_DIMS
+    dW, db = [fresh(D[l + 1], D[l]) for l in range(4)], [fresh(D[l + 1]) for l in range(4)]
+    dz = [fresh(32, d) for d in D[:4]] + [dz4]
+    call(B_MID, 32, 4, MID_DIMS_C, table(W), table(dW), table(db), table(acts), table(dz), *[ptr(r) for r in rest], rest_n, ptr(step),
+         *hyper, stream())
+    out = {f"dW{l}": dW[l] for l in range(4)}
+    out.update({f"db{l}": db[l] for l in range(4)}, dz0=dz[0])
+    return out, dz
+
+
+def test_mid_forward_inside_the_bound_and_equal_to_the_layer_launches():
+    """k_mid_fwd<256,128,64,128,256> at bridges_mlp_mid_forward on the lin_probe stack: every element of acts[1..4] within the
+    one-layer float64 bound of lin_forward_ref on the kernel's own acts[l], q_kernel <= FACTOR q_library; acts[l + 1] bit for bit
+    what bridges_linear_forward gives on acts[l] (the header's claim); a second call repeats; acts[0] is not written; a NaN in
+    one input row makes that row NaN in all four outputs, leaves the 31 others bit-identical and matches the library's pattern."""
+    pr = M.mid_probe(DEV)
+    W, b, x = pr["W"], pr["b"], pr["x"]
+    acts = mid_forward(W, b, x)
+    M.mid_forward_conform("mid_fwd", acts[0], acts[1:], W, b)
+    for l in range(4):
+        assert same_bits(acts[l + 1], forward(acts[l], W[l], b[l], True)), l
+    again = mid_forward(W, b, x)
+    assert all(same_bits(p, q) for p, q in zip(again, acts)) and torch.equal(acts[0], x)
+    xn = x.clone()
+    xn[5, 17] = math.nan
+    got, lb = mid_forward(W, b, xn), M.mid_forward_lib(W, b, xn)
+    others = torch.arange(32, device=DEV) != 5
+    for l in range(4):
+        assert bool(torch.isnan(got[l + 1][5]).all()) and same_bits(got[l + 1][others], acts[l + 1][others]), l
+        assert torch.equal(torch.isnan(got[l + 1]), torch.isnan(lb[l])), l
+
+
+def test_mid_backward_inside_the_propagated_bounds_and_equal_to_the_layer_launches():
+    """k_mid_bwd<256,128,64,128,256> at bridges_mlp_mid_backward, no riders, activations that are masks with +0, -0.0 and
+    negatives: dz[0], dW[0..3] and db[0..3] within the bounds mid_backward_ref carries down the chain, q_kernel <= FACTOR
+    q_library; dz[0] exactly 0 wherever acts[0] is not positive; bit for bit four chained bridges_linear_backward calls; dz[1..3]
+    keep their sentinel, acts, W and dz[4] are not written; a second call repeats; with a NaN and an Inf in dz[4] every output
+    is non-finite exactly where the library chain's is."""
+    pr = M.mid_probe(DEV)
+    W, acts, dz4 = pr["W"], pr["acts"], pr["dz4"]
+    keep = [t.clone() for t in W + acts + [dz4]]
+    a0 = acts[0]
+    assert all(bool(c.any()) for c in ((a0 == 0) & ~torch.signbit(a0), (a0 == 0) & torch.signbit(a0), a0 < 0, a0 > 0))
+    got, dz = mid_backward(W, acts, dz4)
+    M.mid_backward_conform("mid_bwd", got, W, acts, dz4)
+    assert bool((got["dz0"][~(a0 > 0)] == 0).all())
+    z = dz4
+    for l in (3, 2, 1, 0):
+        one = backward(z, acts[l], W[l], acts[l])
+        assert same_bits(one["dW"], got[f"dW{l}"]) and same_bits(one["db"], got[f"db{l}"]), l
+        z = one["dx"]
+    assert same_bits(z, got["dz0"])
+    assert untouched(*dz[1:4]) and all(torch.equal(p, q) for p, q in zip(W + acts + [dz4], keep))
+    again, _ = mid_backward(W, acts, dz4)
+    assert all(same_bits(again[k], got[k]) for k in M.MID_BWD_KEYS)
+    dzn = dz4.clone()
+    dzn[3, 40], dzn[20, 200] = math.nan, math.inf
+    gotn, dzs = mid_backward(W, acts, dzn)
+    lb = M.mid_backward_lib(W, acts, dzn)
+    for k in M.MID_BWD_KEYS:
+        fin = torch.isfinite(lb[k])
+        assert not bool(fin.all()), k
+        assert torch.equal(torch.isfinite(gotn[k]), fin), (k, int((~torch.isfinite(gotn[k])).sum()), int((~fin).sum()))
+    assert untouched(*dzs[1:4])
+
+
+@pytest.mark.parametrize("t", M.ADAM_STEPS)
+def test_mid_backward_riders_equal_the_flat_adam(t):
+    """The rider workgroups of k_mid_bwd for every range of MID_REST_N (none, one float4, one ragged rider, two riders over three
+    stride rounds, more than the cap of 248 over five): parameters and both moments bit for bit what bridges_adam_step gives on
+    copies (one Adam struct) and within adam_ref's float64 bound; the chain's outputs bit for bit those of the call
+    without riders; the gradient, *step and the four floats behind the range are not written."""
+    pr = M.mid_probe(DEV)
+    clean, _ = mid_backward(pr["W"], pr["acts"], pr["dz4"])
+    step, pool = torch.full((), float(t), device=DEV), {}
+    for rest_n in M.MID_REST_N:
+        inputs = tuple(x[:rest_n] for x in M.adam_probe(max(rest_n, 4), DEV, seed=3))
+        bufs = [torch.cat([x, fresh(4)]) for x in inputs]
+        want = [x.clone() for x in bufs]
+        call("bridges_adam_step", *[ptr(x) for x in want], rest_n, ptr(step), *M.ADAM_HYPER, stream())
+        got, _ = mid_backward(pr["W"], pr["acts"], pr["dz4"], rest=bufs, rest_n=rest_n, step=step)
+        for k, a, w in zip("pgmv", bufs, want):
+            assert torch.equal(a, w), (rest_n, t, k, float((a.double() - w.double()).abs().max()))
+        assert torch.equal(bufs[1][:rest_n], inputs[1]) and float(step) == t and untouched(*[x[rest_n:] for x in bufs]), rest_n
+        assert all(same_bits(got[k], clean[k]) for k in M.MID_BWD_KEYS), rest_n
+        if rest_n:
+            adam_conform("mid_bwd.rider", dict(p=bufs[0][:rest_n], m=bufs[2][:rest_n], v=bufs[3][:rest_n]), inputs, t, (rest_n, t), pool)
+    adam_pool_conform("mid_bwd.rider", pool, (M.MID_REST_N, t))
+
+
+@pytest.mark.parametrize("n", M.MID_ROWS_N)
+def test_mid_rows_inside_the_chain_bounds_and_equal_to_the_layer_launches(n):
+    """k_rows2<256,128,64,true> and k_rows2<64,128,256,false> at bridges_mlp_mid_rows: ``mid`` (the first launch) and ``y`` (the
+    second, from the kernel's own mid) within chain2_ref's propagated float64 bounds, q_kernel <= FACTOR q_library; both bit for
+    bit bridges_linear_forward layer by layer on relu(x) in zero-padded rows.  The input holds negatives, -0.0 and (n >= 31) a
+    row of NaN, which comes out as NaN.  Rows >= n of y and of mid (allocated to the next multiple of 32 plus a tile) and the
+    columns of y between 256 and y_stride keep their sentinel; the columns of x beyond 256 hold NaN and are never read: every
+    strided call gives the contiguous result.  n = 8193 and 16389 take a workgroup through a second and a third tile."""
+    pr = M.mid_probe(DEV)
+    W, b = pr["W"], pr["b"]
+    nan_row = n - 2 if n >= 31 else None
+    x = M.rows_probe(n, DEV, nan_row=nan_row)
+    assert bool((x < 0).any()) and bool(((x == 0) & torch.signbit(x)).any())
+    rows = M.rows_of(n)
+
+    def run(xs, ys):
+        xb = torch.full((n, xs), math.nan, device=DEV)
+        xb[:, :256] = x
+        yb, mb = fresh(rows + 32, ys), fresh(rows + 32, 64)
+        call(R_MID, n, 4, MID_DIMS_C, table(W), table(b), ptr(xb), xs, ptr(yb), ys, ptr(mb), stream())
+        assert untouched(yb[n:], yb[:n, 256:], mb[n:]) and same_bits(xb[:, :256], x), (xs, ys)
+        return yb[:n, :256].contiguous(), mb[:n].clone()
+
+    y, mid = run(256, 256)
+    keep = torch.ones(n, dtype=torch.bool, device=DEV)
+    if nan_row is not None:
+        keep[nan_row] = False
+        assert bool(torch.isnan(y[nan_row]).all()) and bool(torch.isnan(mid[nan_row]).all())
+    assert bool(torch.isfinite(y[keep]).all()) and bool(torch.isfinite(mid[keep]).all())
+    M.rows_conform("mid_rows", x, mid, y, W, b, n, keep)
+    a = torch.zeros((rows, 256), device=DEV)
+    a[:n] = torch.relu(x)
+    for l in range(4):
+        a = forward(a, W[l], b[l], True)
+        assert l != 1 or same_bits(mid, a[:n])
+    assert same_bits(y, a[:n])
+    for xs, ys in (M.MID_ROWS_STRIDES if n in M.MID_ROWS_STRIDED_N else M.MID_ROWS_STRIDES[:1]):       # (the first: a repeat)
+        y2, mid2 = run(xs, ys)
+        assert same_bits(y2, y) and same_bits(mid2, mid), (xs, ys)
+
+
+def test_mid_stack_refusals_name_the_entry_point_and_leave_the_outputs_alone():
+    """What csrc/api.hip refuses on the host, before any launch: rows != 32, another layer count or width, no bias table, a W[l],
+    acts[l] or dz[4] that starts 4 bytes into an allocation; an Adam range that is no multiple of 4, has no step or a misaligned
+    buffer, beta1 = 1, lr = NaN; for the many-rows call a stride below the width, an x stride that is no multiple of 4, no
+    scratch, a misaligned x, n_rows < 0.  n_rows = 0 is BRIDGES_OK and writes nothing.  bridges_mlp_mid_supported is 1 for
+    (32, 4, MID_DIMS) alone."""
+    L = lib()
+    pr = M.mid_probe(DEV)
+    W, b, acts, dz4, D = pr["W"], pr["b"], pr["acts"], pr["dz4"], M.MID_DIMS
+    facts = [pr["x"]] + [fresh(32, d) for d in D[1:]]
+    dW, db = [fresh(D[l + 1], D[l]) for l in range(4)], [fresh(D[l + 1]) for l in range(4)]
+    dz = [fresh(32, d) for d in D[:4]] + [dz4]
+    rest, step = [fresh(8) for _ in range(4)], torch.ones((), device=DEV)
+    rest_off, out_off = fresh(12)[1:9], off4(facts[4])
+    bad_dims, swapped = (C.c_int32 * 5)(256, 128, 32, 128, 256), (C.c_int32 * 5)(128, 256, 64, 128, 256)
+    swap = lambda seq, l, t: [t if i == l else s for i, s in enumerate(seq)]
+
+    def fwd(rows=32, nl=4, dims=MID_DIMS_C, W_=W, b_=b, acts_=facts):
+        return L.bridges_mlp_mid_forward(rows, nl, dims, table(W_), table(b_) if b_ is not None else None, table(acts_), stream())
+
+    def bwd(rows=32, nl=4, dims=MID_DIMS_C, W_=W, acts_=acts, dz_=dz, rest_=rest, rest_n=0, step_=step, hyper=M.ADAM_HYPER):
+        return L.bridges_mlp_mid_backward(rows, nl, dims, table(W_), table(dW), table(db), table(acts_), table(dz_), *[ptr(r) for r in rest_],
+                                          rest_n, ptr(step_), *hyper, stream())
+
+    for fn, who in ((fwd, F_MID), (bwd, B_MID)):
+        refused(fn(rows=64), who)
+        refused(fn(nl=3), who)
+        refused(fn(dims=bad_dims), who)
+        for l in (0, 2):
+            refused(fn(W_=swap(W, l, off4(W[l]))), who)
+    refused(fwd(b_=None), F_MID)
+    refused(fwd(acts_=swap(facts, 0, off4(facts[0]))), F_MID)
+    refused(fwd(acts_=swap(facts, 4, out_off)), F_MID)
+    refused(bwd(acts_=swap(acts, 1, off4(acts[1]))), B_MID)
+    refused(bwd(dz_=swap(dz, 4, off4(dz4))), B_MID)
+    lr, b1, b2, eps = M.ADAM_HYPER
+    refused(bwd(rest_n=6), B_MID)
+    refused(bwd(rest_n=4, step_=None), B_MID)
+    refused(bwd(rest_n=4, rest_=swap(rest, 2, rest_off)), B_MID)
+    refused(bwd(rest_n=4, hyper=(lr, 1.0, b2, eps)), B_MID)
+    refused(bwd(rest_n=4, hyper=(math.nan, b1, b2, eps)), B_MID)
+
+    x = M.rows_probe(33, DEV)
+    xw = torch.zeros((33, 260), device=DEV)
+    yb, mb = fresh(96, 256), fresh(96, 64)
+
+    def rows_call(n=33, x_=x, xs=256, ys=256, mid_=mb):
+        return L.bridges_mlp_mid_rows(n, 4, MID_DIMS_C, table(W), table(b), ptr(x_), xs, ptr(yb), ys, ptr(mid_), stream())
+
+    refused(rows_call(xs=252), R_MID)
+    refused(rows_call(x_=xw, xs=258), R_MID)
+    refused(rows_call(ys=255), R_MID)
+    refused(rows_call(mid_=None), R_MID)
+    refused(rows_call(x_=off4(x)), R_MID)
+    refused(rows_call(n=-1), R_MID)
+    assert rows_call(n=0) == 0
+    torch.cuda.synchronize()
+    assert untouched(*facts[1:], out_off, *dW, *db, *dz[:4], *rest, rest_off, yb, mb) and float(step) == 1.0
+
+    S = L.bridges_mlp_mid_supported
+    assert S(32, 4, MID_DIMS_C) == 1
+    assert [S(64, 4, MID_DIMS_C), S(0, 4, MID_DIMS_C), S(31, 4, MID_DIMS_C), S(32, 3, MID_DIMS_C), S(32, 5, MID_DIMS_C), S(32, 4, bad_dims),
+            S(32, 4, swapped), S(32, 4, None)] == [0] * 8

@@ -269,7 +269,9 @@ def test_middle_layer_stack_equals_the_per_layer_launches(hidden, with_adam, mon
 @pytest.mark.parametrize("n", [1, 32, 45, 1000, 8209])
 def test_middle_stack_for_many_rows_equals_the_layer_by_layer_forward(n):
     """bridges_mlp_mid_rows (the acting forward's middle layers, two launches) against bridges_linear_forward layer by layer on
-    the same rows: bit for bit (same tiles, same order), and within 1e-5 of the float64 product; rows beyond n untouched."""
+    the same rows: bit for bit (same tiles, same order), and within 1e-5 of the float64 product.  The wrapper allocates the
+    output here; that rows beyond n, the gaps of a strided y and the scratch behind row n are never written is checked on
+    sentinel-filled buffers by tests/test_gpu_mlp_conformance.py::test_mid_rows_inside_the_chain_bounds_and_equal_to_the_layer_launches."""
     from bridges_hip import mlp_ops
     net = make_net(seed=11)
     lin = [m for m in net.mlp.layers if isinstance(m, torch.nn.Linear)]

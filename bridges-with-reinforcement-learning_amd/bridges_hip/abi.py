@@ -309,6 +309,9 @@ SIGNATURES = {
     "bridges_priority_sample": [i64, i32, i32, vp, f64, i64, vp, vp, vp, i64, vp],
     "bridges_priority_update": [i64, i32, i32, vp, i64, vp, vp, vp, vp],
     "bridges_priority_weights": [i64, i64, i64, vp, f64, vp, i64, vp, vp],
+    "bridges_hindsight_relabel_scratch": [i32, i32, C.POINTER(i64)],
+    "bridges_hindsight_relabel": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp,
+                                  i64, vp],
     "bridges_successor_loss_weighted": [i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
 }
 

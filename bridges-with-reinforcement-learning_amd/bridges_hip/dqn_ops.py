@@ -179,6 +179,53 @@ def priority_weights(idx, n_rec, batch, beta, scratch):
     return weight
 
 
+def hindsight_relabel_scratch(E, G):
+    """Bytes of scratch bridges_hindsight_relabel needs for E envs and G slots (no GPU needed)."""
+    need = C.c_int64(0)
+    abi.check(abi.lib().bridges_hindsight_relabel_scratch(int(E), int(G), C.byref(need)), "bridges_hindsight_relabel_scratch")
+    return need.value
+
+
+def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, count=None, scratch=None):
+    """Hindsight relabelling of the episodes that ended in this lock-step (bridges_hindsight_relabel, "final" strategy): buf
+    [E, K, W] float64 the buffered records of every env's running episode (a record and its task tail, the env's T targets
+    first), flags [E, K, 8] uint8 their step_flags, length [E] int32, ended [E] bool / uint8, episode [E] the task_episode of
+    the buffered episodes (int32 / uint32 bits).  ``env``: the VecAssemblyGym with per-env tasks the episodes were rolled out
+    in -- its seed, env_id_base, shape table, pixel grid, image size and Gaussian vector key the draw and shape the reward maps.
+    -> (out [E * K * G, W] float64, count [1] int32 on the device): the first count rows of out are the relabelled rows, env
+    ascending, then slot, then step; the rest of out is not written.  ``out`` / ``count`` / ``scratch`` (uint8,
+    hindsight_relabel_scratch(E, G) bytes) may be passed to reuse buffers.  Three launches, no host wait, the same bits on every
+    call."""
+    L = abi.require_gpu()
+    E, K, W = buf.shape
+    G = int(G)
+    if not getattr(env, "per_env_tasks", False):
+        raise ValueError("hindsight_relabel needs an env with per-env tasks (targets=RandomTargets() / set_targets)")
+    T = int(env.n_targets)
+    dev = buf.device
+    assert buf.dtype == torch.float64 and buf.is_contiguous()
+    assert flags.dtype == torch.uint8 and flags.is_contiguous() and tuple(flags.shape) == (E, K, 8)
+    assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() == E
+    assert episode.dtype in (torch.int32, torch.uint32) and episode.is_contiguous() and episode.numel() == E
+    ended = ended.contiguous()
+    ended_u8 = ended.view(torch.uint8) if ended.dtype == torch.bool else ended.to(torch.uint8)
+    assert ended_u8.numel() == E
+    if out is None:
+        out = torch.empty((E * K * max(G, 1), W), dtype=torch.float64, device=dev)
+    if count is None:
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= E * K * G * W
+    assert count.dtype == torch.int32 and count.numel() >= 1
+    if scratch is None:
+        scratch = torch.empty(max(4 * E * max(G, 1), 4), dtype=torch.uint8, device=dev)
+    abi.check(L.bridges_hindsight_relabel(E, K, W, T, G, _ptr(buf), _ptr(flags), _ptr(length), _ptr(ended_u8), _ptr(episode),
+                                          int(env.seed) & (2 ** 64 - 1), int(env.env_id_base), env.table.ptr, len(env.table_geoms),
+                                          len(env.table_geoms) - 1, _ptr(env.grid_x_dev), _ptr(env.grid_y_dev), int(env.img),
+                                          env._gauss_k.data_ptr(), _ptr(out), _ptr(count), _ptr(scratch), scratch.numel(), _stream()),
+              "bridges_hindsight_relabel")
+    return out, count
+
+
 def soft_update_(target, policy, tau):
     """target <- policy * tau + target * (1 - tau) in place (successor_dqn.py:280-288); float32 contiguous tensors."""
     L = abi.require_gpu()

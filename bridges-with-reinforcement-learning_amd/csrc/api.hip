@@ -13,6 +13,7 @@
 #include "conv_kernels.hip"
 #include "conv_train_kernels.hip"
 #include "replay_kernels.hip"
+#include "hindsight_kernels.hip"
 
 using namespace bridges;
 
@@ -745,6 +746,46 @@ int bridges_priority_sample(int64_t n_rec, int32_t W, int32_t col, const double*
     // one wave per draw, four draws per workgroup
     return launch("k_priority_draw", k_priority_draw, dim3((unsigned)ceil_div(n_draws, 4)), dim3(256), 0, stream, n_rec, chunks,
                   (const double*)mass, (const double*)chunk_cdf, n_draws, u, idx);
+}
+
+int bridges_hindsight_relabel_scratch(int32_t E, int32_t G, int64_t* bytes) {
+    if (!bytes || E < 0 || G < 1 || G > HIND_MAX_GOALS) return fail_arg("bridges_hindsight_relabel_scratch");
+    *bytes = (int64_t)sizeof(int32_t) * (E > 0 ? (int64_t)E * G : 1);         // the rows of every (env, slot), then their offsets
+    return BRIDGES_OK;
+}
+
+int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                              const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
+                              const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
+                              const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
+                              int64_t scratch_bytes, void* stream) {
+    if (E < 0) return fail_arg("bridges_hindsight_relabel: negative count");
+    if (G < 1 || G > HIND_MAX_GOALS) return fail_arg("bridges_hindsight_relabel: G must be 1..4");
+    if (K < 1 || K > BRIDGES_MAX_BLOCKS) return fail_arg("bridges_hindsight_relabel: K must be 1..BRIDGES_MAX_BLOCKS");
+    if (T < 1 || T > BRIDGES_MAX_TARGETS) return fail_arg("bridges_hindsight_relabel: T must be 1..BRIDGES_MAX_TARGETS");
+    if (W < BRIDGES_REC_WIDTH + 3 * T) return fail_arg("bridges_hindsight_relabel: a record ends in its 3 T target values");
+    if (n_shapes < 1 || n_shapes > 8 || target_shape < 0 || target_shape >= n_shapes) return fail_arg("bridges_hindsight_relabel: shape table");
+    if (img < 1 || img > IMG) return fail_arg("bridges_hindsight_relabel: img must be 1..64");
+    if ((int64_t)E * G * K > INT32_MAX) return fail_arg("bridges_hindsight_relabel: more rows than an int32 counts");
+    if (!buf || !flags || !len || !ended || !episode || !shapes_dev || !grid_x || !grid_y || !gauss_k || !out || !count || !scratch)
+        return fail_arg("bridges_hindsight_relabel: null pointer");
+    if (!aligned(8, buf, shapes_dev, grid_x, grid_y, out) || !aligned(4, len, episode, gauss_k, count, scratch))
+        return fail_arg("bridges_hindsight_relabel: misaligned pointer");
+    int64_t need = 0;
+    if (int rc = bridges_hindsight_relabel_scratch(E, G, &need)) return rc;
+    if (scratch_bytes < need) return fail_arg("bridges_hindsight_relabel: scratch too small (bridges_hindsight_relabel_scratch)");
+    if (E == 0) return BRIDGES_OK;
+    HindArgs a;
+    a.buf = buf; a.flags = flags; a.len = len; a.ended = ended; a.episode = episode; a.shapes = shapes_dev; a.grid_x = grid_x;
+    a.grid_y = grid_y; a.gauss_k = gauss_k; a.seed = seed; a.E = E; a.K = K; a.W = W; a.T = T; a.G = G; a.env_id_base = env_id_base;
+    a.n_shapes = n_shapes; a.target_shape = target_shape; a.img = img;
+    int32_t* cnt = (int32_t*)scratch;
+    const int items = E * G;
+    // one wave per (env, slot), four per workgroup
+    if (int rc = launch("k_hindsight_count", k_hindsight_count, dim3((unsigned)ceil_div(items, 4)), dim3(256), 0, stream, a, cnt)) return rc;
+    if (int rc = launch("k_hindsight_scan", k_hindsight_scan, dim3(1), dim3(HIND_SCAN_THREADS), 0, stream, items, cnt, count)) return rc;
+    return launch("k_hindsight_rows", k_hindsight_rows, dim3((unsigned)items), dim3(TASK_THREADS), 0, stream, a, (const int32_t*)cnt,
+                  (const int32_t*)count, out);
 }
 
 int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, int64_t n, const int64_t* idx, const float* q_sa,

@@ -813,6 +813,63 @@ __device__ __forceinline__ bridges_task_family task_family(const bridges_task_fa
 __device__ __forceinline__ const uint64_t* task_thresholds() { return nullptr; }
 __device__ __forceinline__ const uint64_t* task_thresholds(const bridges_task_family&) { return nullptr; }
 __device__ __forceinline__ const uint64_t* task_thresholds(const bridges_task_family&, const uint64_t* thr) { return thr; }
+// The reward map of a target raster and its row prefix sums, into LDS (the arithmetic above): every thread of the four waves
+// calls it with its wave's copy of the raster rows `bits` (row r in lane r) after wave 0 has put them into tb_l and the
+// workgroup has met.  STORE_MAP: the map goes to map_g [64][64] as well.  Returns with map_l and pre_l complete and visible.
+// k_task_features and the hindsight relabelling (hindsight_kernels.hip) share it, so a relabelled task's tables are an env's.
+template <bool STORE_MAP>
+__device__ __forceinline__ void task_map_prefix(const uint64_t bits, const uint64_t* tb_l, const float* kz, float* map_l, double* pre_l,
+                                                const int S, const int lane, const int wv, float* map_g) {
+    // ---- reward map: lane = column x, wave wv = rows 16 wv .. 16 wv + 15 ----
+    const uint64_t nzrows = __ballot(bits != 0ull);
+    const int half = BRIDGES_GAUSS_TAPS / 2;
+    for (int b = 0; b < IMG / (TASK_WAVES * TASK_ROWS_IN_FLIGHT); ++b) {
+        const int y0 = (wv * (IMG / TASK_WAVES)) + b * TASK_ROWS_IN_FLIGHT;
+        double acc[TASK_ROWS_IN_FLIGHT];
+#pragma unroll
+        for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) acc[r] = 0.0;
+        uint64_t rows = y0 < S ? nzrows : 0ull;
+        while (rows) {                              // set pixels in row-major order
+            const int py = __builtin_ctzll(rows);
+            rows &= rows - 1ull;
+            float ki[TASK_ROWS_IN_FLIGHT];
+#pragma unroll
+            for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) ki[r] = kz[py - (y0 + r) + half + TASK_KZ_PAD];
+            const uint64_t row = tb_l[py];
+            uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(row >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row);
+            while (m) {
+                const int pxl = __builtin_ctzll(m);
+                m &= m - 1ull;
+                const float kx = kz[pxl - lane + half + TASK_KZ_PAD];
+#pragma unroll
+                for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) {
+                    const float prod = ki[r] * kx;
+                    acc[r] = acc[r] + (double)prod;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) {
+            const int y = y0 + r;
+            const float v = (lane < S && y < S) ? (float)acc[r] : 0.f;
+            map_l[y * TASK_ROW + lane] = v;
+            if constexpr (STORE_MAP) map_g[y * IMG + lane] = v;
+        }
+    }
+    __syncthreads();
+    // ---- row prefix sums: lane r of wave 0 = row r ----
+    if (wv == 0) {
+        double run = 0.0;
+        pre_l[lane * TASK_ROW] = 0.0;
+        for (int x = 0; x < IMG; ++x) {
+            run = run + (double)map_l[lane * TASK_ROW + x];
+            pre_l[lane * TASK_ROW + x + 1] = run;
+        }
+    }
+    __syncthreads();
+}
+
 // FAMILY... is empty (no family), <bridges_task_family> (the uniform draw) or <bridges_task_family, const uint64_t*> (a threshold
 // table attached: the weighted draw); the first two are the kernels they were before the third existed.
 template <typename... FAMILY>
@@ -947,55 +1004,7 @@ __global__ __launch_bounds__(TASK_THREADS) void k_task_features(DevCtx c, bridge
         t.target_bits[(size_t)e * IMG + lane] = bits;
     }
     __syncthreads();
-    // ---- reward map: lane = column x, wave wv = rows 16 wv .. 16 wv + 15 ----
-    const uint64_t nzrows = __ballot(bits != 0ull);
-    const int half = BRIDGES_GAUSS_TAPS / 2;
-    float* map_g = t.reward_map + (size_t)e * IMG * IMG;
-    for (int b = 0; b < IMG / (TASK_WAVES * TASK_ROWS_IN_FLIGHT); ++b) {
-        const int y0 = (wv * (IMG / TASK_WAVES)) + b * TASK_ROWS_IN_FLIGHT;
-        double acc[TASK_ROWS_IN_FLIGHT];
-#pragma unroll
-        for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) acc[r] = 0.0;
-        uint64_t rows = y0 < S ? nzrows : 0ull;
-        while (rows) {                              // set pixels in row-major order
-            const int py = __builtin_ctzll(rows);
-            rows &= rows - 1ull;
-            float ki[TASK_ROWS_IN_FLIGHT];
-#pragma unroll
-            for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) ki[r] = kz[py - (y0 + r) + half + TASK_KZ_PAD];
-            const uint64_t row = tb_l[py];
-            uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(row >> 32)) << 32) |
-                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row);
-            while (m) {
-                const int pxl = __builtin_ctzll(m);
-                m &= m - 1ull;
-                const float kx = kz[pxl - lane + half + TASK_KZ_PAD];
-#pragma unroll
-                for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) {
-                    const float prod = ki[r] * kx;
-                    acc[r] = acc[r] + (double)prod;
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < TASK_ROWS_IN_FLIGHT; ++r) {
-            const int y = y0 + r;
-            const float v = (lane < S && y < S) ? (float)acc[r] : 0.f;
-            map_l[y * TASK_ROW + lane] = v;
-            map_g[y * IMG + lane] = v;
-        }
-    }
-    __syncthreads();
-    // ---- row prefix sums: lane r of wave 0 = row r ----
-    if (wv == 0) {
-        double run = 0.0;
-        pre_l[lane * TASK_ROW] = 0.0;
-        for (int x = 0; x < IMG; ++x) {
-            run = run + (double)map_l[lane * TASK_ROW + x];
-            pre_l[lane * TASK_ROW + x + 1] = run;
-        }
-    }
-    __syncthreads();
+    task_map_prefix<true>(bits, tb_l, kz, map_l, pre_l, S, lane, wv, t.reward_map + (size_t)e * IMG * IMG);
     double* pre_g = t.reward_prefix + (size_t)e * IMG * TASK_ROW;
     for (int i = tid; i < IMG * TASK_ROW; i += TASK_THREADS) pre_g[i] = pre_l[i];
 }

@@ -1,0 +1,253 @@
+// Hindsight goal relabelling of finished episodes (strategy "final", header comment of bridges_hindsight_relabel): every
+// episode that ended in this lock-step is written a second time, G times, under T targets that its own final structure reached --
+// the centres of the bounding boxes of blocks drawn from it -- with the reward, the linear reward and the done flag the
+// environment would have recorded had the same placements been made under those targets.  Nothing of the simulator runs again:
+// the stability verdicts are the rollout's (the step_flags kept beside every buffered record), the reached-test is k_step's on
+// vertices rebuilt from the recorded poses, and the linear reward comes from the row runs of the block's raster on the float64
+// row prefix sums of the hindsight task's reward map, built by the device code of k_task_features (task_map_prefix).
+//
+// Three launches, no atomics:
+//   k_hindsight_count   one wave per (env, slot): draws the goals and walks the reached-test alone -> rows of the slot
+//   k_hindsight_scan    one workgroup: exclusive prefix sum of the counts in place (as k_scan), the total -> *count
+//   k_hindsight_rows    four waves per (env, slot) with rows: the goals again (same draw, same bits), the raster of the T target
+//                       cubes, map and prefix tables in LDS (51 KB, as k_task_features: three workgroups per CU), then wave 0 walks
+//                       the episode and stores row offset[slot] + t.  The order of the output is (env, slot, t) by construction.
+// The work per finished (env, slot) is that of one k_task_features workgroup -- which the lock-step runs for every finished env
+// anyway -- plus K rasters of ~250 wave instructions; envs in mid-episode leave at once.
+#include "bridges_device.h"
+// (device code of env_kernels.hip -- raster_rows_nv, raster_reward_fetch, task_map_prefix -- is in scope: api.hip includes it first)
+
+namespace bridges {
+
+#define HIND_SALT 0x68696E645F726E67ull     // "hind_rng"
+#define HIND_MAX_GOALS 4
+#define HIND_SCAN_THREADS 256
+
+struct HindArgs {
+    const double* buf;              // [E, K, W] the buffered records of every env's running episode
+    const uint8_t* flags;           // [E, K, 8] step_flags of the step of each record
+    const int32_t* len;             // [E] records in the buffer
+    const uint8_t* ended;           // [E] the episode ended in this lock-step
+    const uint32_t* episode;        // [E] task_episode of the episode in the buffer
+    const bridges_shape* shapes;    // the task's shape table
+    const double* grid_x;           // [img] pixel centres
+    const double* grid_y;
+    const float* gauss_k;           // [BRIDGES_GAUSS_TAPS]
+    uint64_t seed;
+    int32_t E, K, W, T, G, env_id_base, n_shapes, target_shape, img;
+};
+
+// Lane v < nv: world vertex v of the block that record `row` placed (pos + R(c, s) * local vertex: k_pose_block's and
+// k_enumerate's expression, on the recorded pose -- the rollout's bits).  Returns the (clamped) shape id.
+__device__ __forceinline__ int hind_block_verts(const HindArgs& a, const double* row, int lane, double& vx, double& vz) {
+    int sh = (int)row[BRIDGES_REC_ASHAPE];
+    sh = sh < 0 ? 0 : (sh < a.n_shapes ? sh : a.n_shapes - 1);
+    const bridges_shape& s = a.shapes[sh];
+    const double px = row[BRIDGES_REC_APOSE], pz = row[BRIDGES_REC_APOSE + 1], cs = row[BRIDGES_REC_APOSE + 2], sn = row[BRIDGES_REC_APOSE + 3];
+    vx = 0.0; vz = 0.0;
+    if (lane < s.nv) {
+        double rx, rz;
+        rot2(s.vx[lane], s.vz[lane], cs, sn, rx, rz);
+        vx = px + rx; vz = pz + rz;
+    }
+    return sh;
+}
+
+// Axis-aligned bounding box of a block's vertices as k_step's reached-test takes it.
+struct HindBox { double cx, cz, hx, hz; };
+__device__ __forceinline__ HindBox hind_box(double vx, double vz, bool hasv) {
+    const double x0 = wave_min_d(hasv ? vx : 1e300), x1 = wave_max_d(hasv ? vx : -1e300);
+    const double z0 = wave_min_d(hasv ? vz : 1e300), z1 = wave_max_d(hasv ? vz : -1e300);
+    HindBox b;
+    b.cx = (x0 + x1) * 0.5; b.cz = (z0 + z1) * 0.5; b.hx = (x1 - x0) * 0.5; b.hz = (z1 - z0) * 0.5;
+    return b;
+}
+
+// The hindsight targets of slot g of env e's episode of m records: lane 3 q + k holds coordinate k of target q (y = 0), as
+// k_step keeps its per-env targets.  Returns m' (the eligible blocks); with m' == 0 there are no targets.
+// The choice: idx = 0 .. m' - 1, for i < min(T, m'): j = i + ((u * (m' - i)) >> 32), u = r >> 32, swap(idx[i], idx[j]) with
+//   h0 = splitmix64(((seed & 0xFFFFFFFF) << 32 | gid) ^ HIND_SALT);  h1 = splitmix64(h0 ^ episode);  h2 = splitmix64(h1 ^ g);
+//   r = splitmix64(h2 ^ i);   target q is the box centre of block idx[q mod m'].  Lane i holds idx[i]; integer arithmetic only.
+__device__ __forceinline__ int hind_goals(const HindArgs& a, int e, int g, int m, int lane, double& tgv) {
+    const double* rows = a.buf + (size_t)e * a.K * a.W;
+    tgv = 0.0;
+    int mp = m;
+    if (m > 0 && !(rows[(size_t)(m - 1) * a.W + BRIDGES_REC_STABLE_N] > 0.5)) mp = m - 1;     // a collapsed last block is no goal
+    if (mp <= 0) return 0;
+    const uint64_t h0 = splitmix64((((a.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(a.env_id_base + e)) ^ HIND_SALT);
+    const uint64_t h1 = splitmix64(h0 ^ (uint64_t)a.episode[e]);
+    const uint64_t h2 = splitmix64(h1 ^ (uint64_t)g);
+    int idx = lane;
+    const int nd = a.T < mp ? a.T : mp;
+    for (int i = 0; i < nd; ++i) {
+        const uint64_t u = splitmix64(h2 ^ (uint64_t)i) >> 32;
+        const int j = __builtin_amdgcn_readfirstlane(i + (int)((u * (uint64_t)(mp - i)) >> 32));
+        const int vi = __builtin_amdgcn_readlane(idx, i), vj = __builtin_amdgcn_readlane(idx, j);
+        idx = lane == i ? vj : (lane == j ? vi : idx);
+    }
+    for (int q = 0; q < a.T; ++q) {
+        const int b = __builtin_amdgcn_readlane(idx, q % mp);
+        double vx, vz;
+        const int sh = hind_block_verts(a, rows + (size_t)b * a.W, lane, vx, vz);
+        const HindBox bx = hind_box(vx, vz, lane < a.shapes[sh].nv);
+        tgv = lane == 3 * q ? bx.cx : (lane == 3 * q + 2 ? bx.cz : tgv);
+    }
+    return mp;
+}
+
+// k_step's reached-test of one placed block against the open targets `left`, literally: the target after a reached one is
+// skipped (env_kernels.hip, "targets"), ty = 0.
+__device__ __forceinline__ uint32_t hind_reach(const HindArgs& a, uint32_t left, double tgv, const HindBox& b, double depth) {
+    const double hy = depth * 0.5;
+    bool skip = false;
+    for (int t = 0; t < a.T; ++t) {
+        if (!((left >> t) & 1u)) continue;
+        if (skip) { skip = false; continue; }
+        const double tx = readlane_d(tgv, 3 * t), ty = readlane_d(tgv, 3 * t + 1), tz = readlane_d(tgv, 3 * t + 2);
+        const bool in = fabs(tx - b.cx) < b.hx + 1e-6 && fabs(ty) < hy + 1e-6 && fabs(tz - b.cz) < b.hz + 1e-6;
+        if (in) { left &= ~(1u << t); skip = true; }
+    }
+    return left;
+}
+
+__device__ __forceinline__ int hind_len(const HindArgs& a, int e) {
+    if (!a.ended[e]) return 0;
+    const int m = a.len[e];
+    return m < 0 ? 0 : (m > a.K ? a.K : m);
+}
+
+__global__ __launch_bounds__(256) void k_hindsight_count(HindArgs a, int32_t* __restrict__ cnt) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int item = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE));
+    if (item >= a.E * a.G) return;
+    const int e = item / a.G, g = item % a.G;
+    const int m = hind_len(a, e);
+    double tgv;
+    int n = 0;
+    if (m > 0 && hind_goals(a, e, g, m, lane, tgv) > 0) {
+        const double* rows = a.buf + (size_t)e * a.K * a.W;
+        uint32_t left = (1u << a.T) - 1u;
+        for (int t = 0; t < m; ++t) {
+            double vx, vz;
+            const int sh = hind_block_verts(a, rows + (size_t)t * a.W, lane, vx, vz);
+            left = hind_reach(a, left, tgv, hind_box(vx, vz, lane < a.shapes[sh].nv), a.shapes[sh].depth);
+            n = t + 1;
+            if (left == 0u) break;                  // the episode is over under the new targets: later transitions do not exist
+        }
+    }
+    if (lane == 0) cnt[item] = n;
+}
+
+// Exclusive prefix sum in place (cnt[i] <- rows in front of slot i), the total -> *total.  One workgroup, as k_scan.
+__global__ __launch_bounds__(HIND_SCAN_THREADS) void k_hindsight_scan(int n, int32_t* __restrict__ cnt, int32_t* __restrict__ total) {
+    __shared__ int wave_tot[HIND_SCAN_THREADS / WAVE];
+    __shared__ int carry_s;
+    const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += HIND_SCAN_THREADS) {
+        const int i = base + t;
+        const int v = i < n ? cnt[i] : 0;
+        int incl = v;
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int up = __shfl_up(incl, o, WAVE);
+            if (lane >= o) incl += up;
+        }
+        if (lane == WAVE - 1) wave_tot[wv] = incl;
+        __syncthreads();
+        int wbase = 0;
+        for (int k = 0; k < wv; ++k) wbase += wave_tot[k];
+        const int carry = carry_s;
+        if (i < n) cnt[i] = carry + wbase + incl - v;
+        __syncthreads();
+        if (t == HIND_SCAN_THREADS - 1) carry_s = carry + wbase + incl;
+        __syncthreads();
+    }
+    if (t == 0) *total = carry_s;
+}
+
+// Raster of a convex outline whose world vertex v sits in lane v: raster_outline's frames (edge_frame on the same vertices) and
+// its row runs, without the trip through memory.
+__device__ __forceinline__ uint64_t hind_raster(double vx, double vz, const bridges_shape& s, const HindArgs& a, int lane) {
+    const int f = lane < s.nv ? lane : 0;
+    const int ia = s.fa[f], ib = s.fb[f];
+    const double ax = shfl_d(vx, ia), az = shfl_d(vz, ia), bx = shfl_d(vx, ib), bz = shfl_d(vz, ib);
+    double cx = 0.0, cz = 0.0, nx = 0.0, nz = 0.0;
+    if (lane < s.nv) {
+        const Frame2 fr = edge_frame(ax, az, bx, bz);
+        cx = fr.cx; cz = fr.cz; nx = fr.nx; nz = fr.nz;
+    }
+    const int gi = lane < a.img ? lane : a.img - 1;
+    return raster_rows_nv(cx, cz, nx, nz, s.nv, a.img, a.grid_x[gi], a.grid_y[gi], lane);
+}
+
+__global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows(HindArgs a, const int32_t* __restrict__ off, const int32_t* __restrict__ total,
+                                                                double* __restrict__ out) {
+    __shared__ float kz[TASK_KZ];
+    __shared__ uint64_t tb_l[IMG];
+    __shared__ float map_l[IMG * TASK_ROW];
+    __shared__ double pre_l[IMG * TASK_ROW];
+    const int item = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    const int e = item / a.G, g = item % a.G;
+    const int m = hind_len(a, e);
+    if (m == 0) return;                             // mid-episode (the whole workgroup leaves)
+    const int first = off[item];
+    const int n = (item + 1 < a.E * a.G ? off[item + 1] : *total) - first;
+    if (n <= 0) return;                             // no eligible block
+    for (int i = tid; i < TASK_KZ; i += TASK_THREADS) {
+        const int tap = i - TASK_KZ_PAD;
+        kz[i] = (tap >= 0 && tap < BRIDGES_GAUSS_TAPS) ? a.gauss_k[tap] : 0.f;
+    }
+    double tgv;
+    hind_goals(a, e, g, m, lane, tgv);
+    // raster of the T target cubes at identity rotation (vertex = target + local vertex: k_task_features), every wave
+    const bridges_shape& cube = a.shapes[a.target_shape];
+    uint64_t bits = 0ull;
+    for (int q = 0; q < a.T; ++q) {
+        const double px = readlane_d(tgv, 3 * q), pz = readlane_d(tgv, 3 * q + 2);
+        const int v = lane < cube.nv ? lane : 0;
+        bits |= hind_raster(px + cube.vx[v], pz + cube.vz[v], cube, a, lane);
+    }
+    if (wv == 0) tb_l[lane] = bits;
+    __syncthreads();
+    task_map_prefix<false>(bits, tb_l, kz, map_l, pre_l, a.img, lane, wv, nullptr);
+    if (wv != 0) return;
+    // ---- wave 0: the episode under the hindsight targets ----
+    const double* rows = a.buf + (size_t)e * a.K * a.W;
+    const uint8_t* fl = a.flags + (size_t)e * a.K * 8;
+    uint32_t left = (1u << a.T) - 1u;
+    for (int t = 0; t < n; ++t) {
+        const double* row = rows + (size_t)t * a.W;
+        double vx, vz;
+        const int sh = hind_block_verts(a, row, lane, vx, vz);
+        const bridges_shape& s = a.shapes[sh];
+        left = hind_reach(a, left, tgv, hind_box(vx, vz, lane < s.nv), s.depth);
+        const uint64_t rb = hind_raster(vx, vz, s, a, lane);
+        double p_hi, p_lo;
+        raster_reward_fetch(rb, pre_l, lane, p_hi, p_lo);
+        const float base = (float)raster_reward_sum(p_hi, p_lo);                 // k_raster's cand_lin
+        const bool st_frozen = fl[t * 8 + F_STABLE_FROZEN], st_free = fl[t * 8 + F_STABLE_UNFROZEN];
+        const bool truncated = fl[t * 8 + F_TRUNCATED], no_actions = fl[t * 8 + F_NO_ACTIONS];
+        const int n_reached = a.T - __popc(left);
+        const bool all_reached = left == 0u;
+        const float reward = !st_frozen ? -1.f : (all_reached ? (float)n_reached : (float)(-1 + n_reached));
+        const float lin = st_free ? base : (st_frozen ? base / 100.f : 0.f);
+        const bool done = !st_frozen || all_reached || truncated || no_actions;
+        double* o = out + (size_t)(first + t) * a.W;
+        for (int c0 = 0; c0 < a.W; c0 += WAVE) {    // (every lane stays for the shuffle)
+            const int c = c0 + lane;
+            double v = c < a.W ? row[c] : 0.0;
+            if (c == BRIDGES_REC_REWARD) v = (double)reward;
+            if (c == BRIDGES_REC_LIN) v = (double)lin;
+            if (c == BRIDGES_REC_DONE) v = done ? 1.0 : 0.0;
+            const int k = c - BRIDGES_REC_WIDTH;
+            const bool tail = k >= 0 && k < 3 * a.T;
+            const double tk = shfl_d(tgv, tail ? k : 0);
+            if (tail) v = tk;
+            if (c < a.W) o[c] = v;
+        }
+    }
+}
+
+}  // namespace bridges

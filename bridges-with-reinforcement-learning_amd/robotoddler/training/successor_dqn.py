@@ -586,6 +586,7 @@ def build_parser():
     add_double_q_argument(p)
     add_priority_arguments(p)
     add_exploration_arguments(p)
+    add_hindsight_arguments(p)
     return p
 
 
@@ -727,6 +728,44 @@ def check_double_q(args):
     if args.get('double_q') and args['num_envs'] <= 1:
         raise SystemExit("--double_q needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
                          "reference's target, where the target net both chooses and values the next action")
+
+
+def add_hindsight_arguments(p):
+    """--hindsight / --hindsight_goals: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--hindsight", choices=("final",), default=argparse.SUPPRESS,
+                   help="With --random_targets T only: hindsight goal relabelling -- every episode that ends is stored a second "
+                        "time under T targets its own final structure reached (the centres of the bounding boxes of blocks drawn "
+                        "from it), with the rewards the env would have given under them. The log gains hindsight_rows.")
+    p.add_argument("--hindsight_goals", type=int, default=argparse.SUPPRESS, metavar="G",
+                   help="With --hindsight final: relabelled copies of every finished episode, 1..4 (1).")
+
+
+def check_hindsight(args):
+    """--hindsight / --hindsight_goals: refused in words (SystemExit) where the loop cannot run them, before anything touches the GPU."""
+    if 'hindsight' not in args:
+        if 'hindsight_goals' in args:
+            raise SystemExit("--hindsight_goals counts the relabelled copies of an episode: it needs --hindsight final")
+        return
+    if not 1 <= args.get('hindsight_goals', 1) <= 4:
+        raise SystemExit("--hindsight_goals must be 1..4")
+    if not args.get('random_targets'):
+        raise SystemExit("--hindsight final needs --random_targets T (and with it --num_envs N, N > 1): only a record that ends "
+                         "in its own targets can be given others")
+    if args.get('random_bridge_length') is not None or args.get('random_tower_height') is not None or args.get('curriculum'):
+        raise SystemExit("--hindsight final does not run on a task family (--random_bridge_length / --random_tower_height) or "
+                         "with --curriculum: a family's task is its class, and a box centre names none")
+    if args.get('n_step', 1) > 1:
+        raise SystemExit("--hindsight final needs --n_step 1: an h-step row's return would have to be folded again under the new targets")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--hindsight final runs on one rank only: the relabelled rows are not part of the all-gather")
+
+
+def hindsight_from_args(args):
+    """The hindsight arguments of VecDQN from parsed options; refuses what check_hindsight refuses."""
+    check_hindsight(args)
+    if 'hindsight' not in args:
+        return {}
+    return dict(hindsight=args['hindsight'], hindsight_goals=args.get('hindsight_goals', 1))
 
 
 def add_curriculum_arguments(p):
@@ -908,6 +947,7 @@ def main(argv=None):
     check_double_q(args)
     check_priority(args)
     check_exploration(args)
+    check_hindsight(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

@@ -60,7 +60,7 @@ class VecDQN:
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
                  n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0,
-                 exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999):
+                 exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -116,7 +116,16 @@ class VecDQN:
         starts at ``temp_start`` (1.0) and follows t <- (t - temp_end) * temp_decay + temp_end per lock-step (``temp_end`` 0.1,
         ``temp_decay`` 0.999: the reference's form, per lock-step as epsilon's); epsilon is left alone.  It is a function of the
         lock-step count alone, so ranks agree; it is checkpointed.  act(greedy=True) and evaluate() stay greedy.  The temp_*
-        arguments are refused without the option.  "epsilon_greedy" is the loop as it was: no launch of this."""
+        arguments are refused without the option.  "epsilon_greedy" is the loop as it was: no launch of this.
+        ``hindsight="final"`` (with per_env_tasks=True only, one-step returns, one rank; an extension: hindsight experience replay,
+        Andrychowicz et al., strategy "final"): every episode that ends is pushed a second time, ``hindsight_goals`` = G times
+        (1..4), under T targets its own final structure reached -- the centres of the bounding boxes of blocks drawn from it on a
+        stream of its own -- with the reward, linear reward and done flag the env would have recorded under those targets
+        (bridges_hindsight_relabel, the rule in include/bridges_hip.h; DESIGN.md, "Hindsight relabelling").  The loop keeps every
+        env's running episode on the device (records.HindsightBuffer); the relabelled rows follow the lock-step's own records
+        into the ring, their number rides to the host with the lock-step's counts: no wait of its own.  The training step does
+        not change.  It composes with per-env obstacles, task_channels, double_q, prioritised replay (a relabelled row carries
+        the priority of the transition it restates) and Boltzmann exploration.  None is the loop as it was: no launch of this."""
         self.exploration = str(exploration)
         if self.exploration not in ("epsilon_greedy", "boltzmann"):
             raise ValueError(f"VecDQN(exploration={exploration!r}): one of 'epsilon_greedy', 'boltzmann'")
@@ -164,6 +173,22 @@ class VecDQN:
                              "no window would ever fill")
         self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
         self.task_channels = bool(task_channels)
+        self.hindsight, self.hindsight_goals = hindsight, int(hindsight_goals)
+        if self.hindsight not in (None, "final"):
+            raise ValueError(f"VecDQN(hindsight={hindsight!r}): None or 'final'")
+        if self.hindsight is None and self.hindsight_goals != 1:
+            raise ValueError("VecDQN(hindsight_goals=...) counts the relabelled copies of an episode: it needs hindsight='final'")
+        if self.hindsight is not None:
+            if not 1 <= self.hindsight_goals <= 4:
+                raise ValueError(f"VecDQN(hindsight_goals={hindsight_goals}): an episode is relabelled 1..4 times")
+            if not self.per_env_tasks:
+                raise ValueError("VecDQN(hindsight='final') needs per_env_tasks=True: only a record that ends in its own targets can be given others")
+            if getattr(env, "task_family", None) is not None or curriculum is not None:
+                raise ValueError("VecDQN(hindsight='final') does not run on a task family (RandomBridges) or under a curriculum: a family's task is its class, and a box centre names none")
+            if self.n_step > 1:
+                raise ValueError("VecDQN(hindsight='final') needs n_step=1: an h-step row's return would have to be folded again under the new targets")
+            if D.active():
+                raise ValueError("VecDQN(hindsight='final') runs on one rank only: the relabelled rows are not part of the all-gather")
         if self.task_channels:
             self._check_task_channels(policy_net, target_net, env)
         if getattr(env, "per_env_obstacles", False) and not self.per_env_obstacles:
@@ -219,6 +244,10 @@ class VecDQN:
         # n-step returns: one more column, the horizon h of the row
         self.ring = R.ReplayRing(replay_capacity, self.device, width=R.RECORD_WIDTH + self.task_width + (self.n_step > 1))
         self._window = None                                  # the n-step windows of the envs of all ranks, made by the first fold
+        # hindsight relabelling: the running episode of every env, in the ring's width
+        self.hindsight_buffer = (R.HindsightBuffer(env.E, self.ring.width, self.device, goals=self.hindsight_goals, n_blocks=env.K)
+                                 if self.hindsight is not None else None)
+        self.hindsight_rows = 0                              # relabelled rows the last lock-step pushed
         # replay sampling must be identical on every rank (replicated rings) -> shared seed; exploration differs
         self.sample_gen = torch.Generator(device=self.device).manual_seed(1234567 + seed)
         self.explore_gen = torch.Generator(device=self.device).manual_seed(7654321 + seed * 1000 + rank)
@@ -236,7 +265,9 @@ class VecDQN:
         self.env_steps = 0
         # (env-steps, finished episodes) of a lock-step; n-step returns on one rank: and the emitted rows
         # Boltzmann exploration: and, last, the envs whose draw left the first maximum
-        self._counts_host = torch.zeros((3 if self.n_step > 1 else 2) + (self.exploration == "boltzmann"), dtype=torch.int64).pin_memory()
+        # hindsight relabelling: and, after those, the relabelled rows
+        self._counts_host = torch.zeros((3 if self.n_step > 1 else 2) + (self.exploration == "boltzmann") + (self.hindsight is not None),
+                                        dtype=torch.int64).pin_memory()
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
         # (a task family -- RandomBridges -- keeps them per class as well: one row per span / height n = 0..hi)
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
@@ -566,6 +597,8 @@ class VecDQN:
                               if self.per_env_obstacles else env.env_targets.reshape(E, -1).clone())
         if getattr(env, "task_family", None) is not None:
             env._task_class = env.task_class.clone()            # likewise the class: the step that ends an episode redraws it
+        if getattr(self, "hindsight", None) is not None and env is self.env:
+            env._task_episode = env.task_episode.clone()        # and the episode counter, which keys the hindsight draw
         env.step(sel_index)
         valid = R.pack_result(env, rec)
         return rec, valid, q_sel
@@ -937,6 +970,9 @@ class VecDQN:
             blob["priority_beta_calls"] = int(self.priority_beta_calls)
         if getattr(self, "exploration", "epsilon_greedy") == "boltzmann":      # one more key: where the schedule stands
             blob["temperature"] = float(self.temperature)
+        if getattr(self, "hindsight", None) is not None:      # two more keys: the setting and the running episodes
+            blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
+            blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
         torch.save(blob, path)
 
     def load_extra(self, path):
@@ -959,6 +995,14 @@ class VecDQN:
         if got_n != want_n:
             raise ValueError(f"{path} was written by a run with n_step = {got_n}, this agent folds n_step = {want_n}: the rows "
                              "of the ring do not mean the same returns")
+        # (a file of a run without hindsight relabelling carries no entry)
+        got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
+        want_h = (str(self.hindsight), int(self.hindsight_goals)) if getattr(self, "hindsight", None) is not None else None
+        if got_h != want_h:
+            raise ValueError(f"{path} was written by a run with (hindsight, hindsight_goals) = {got_h}, this agent has {want_h}: the "
+                             "ring does not hold the same mix of rolled-out and relabelled rows")
+        if want_h is not None:
+            self.hindsight_buffer.load_state_dict(blob["hindsight_buffer"])
         self.epsilon, self.episodes_done, self.env_steps = blob["epsilon"], blob["episodes_done"], blob["env_steps"]
         self.step_images.copy_(blob["step_images"])
         self.sample_gen.set_state(blob["sample_gen"])
@@ -981,6 +1025,8 @@ class VecDQN:
         into the next one; the pending starts (up to n - 1 transitions per env) are dropped, they never reach the ring."""
         if self._window is not None:
             self._window[0].zero_()
+        if getattr(self, "hindsight_buffer", None) is not None:      # hindsight relabelling: the running episodes go with them
+            self.hindsight_buffer.clear()
 
     def _fold(self, rec, valid):
         """One lock-step's one-step rows (of all ranks) through the n-step windows -> (out [rows * n, W + 1], out_valid)."""
@@ -1020,6 +1066,14 @@ class VecDQN:
         boltzmann = self.exploration == "boltzmann"
         if boltzmann:                                   # the envs that left the arg-max ride with the counts: no wait of their own
             counts.append((self._ex_w * valid).sum().to(torch.int64) if self._ex_w is not None else torch.zeros_like(counts[0]))
+        hind = None
+        if self.hindsight is not None:
+            # the lock-step joins every env's running episode; the episodes that end are relabelled at once (three launches) and
+            # the number of rows that came out rides with the counts: no wait of its own
+            hb = self.hindsight_buffer
+            hb.write(self.with_task(rec), self.env.step_flags, valid, self.env._task_episode)
+            hind = hb.relabel(self.env, done_rec)
+            counts.append(hind[1][0].to(torch.int64))
         self._counts_host.copy_(torch.stack(counts), non_blocking=True)
         arrived = torch.cuda.Event()
         arrived.record()
@@ -1028,7 +1082,7 @@ class VecDQN:
         n_valid, n_done = int(self._counts_host[0]), int(self._counts_host[1])
         self.env_steps += n_valid
         if boltzmann:
-            self.explored_fraction = int(self._counts_host[-1]) / n_valid if n_valid else None
+            self.explored_fraction = int(self._counts_host[-1 - (hind is not None)]) / n_valid if n_valid else None
         if self.n_step > 1:
             if folded is None:
                 # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
@@ -1041,6 +1095,9 @@ class VecDQN:
         else:
             allrec = D.all_gather_records(self.with_task(rec), valid, n_valid=n_valid)
         self.ring.push(allrec)
+        if hind is not None:                            # behind the lock-step's own records
+            self.hindsight_rows = int(self._counts_host[-1])
+            self.ring.push(hind[0][:self.hindsight_rows])
         if not D.active():
             self.episodes_done += n_done
         elif self.n_step > 1:
@@ -1106,6 +1163,8 @@ def lockstep_log_values(info):
                 steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
     if 'temperature' in info:                                # Boltzmann exploration only
         vals.update(temperature=info['temperature'], explored_fraction=info.get('explored_fraction'))
+    if 'hindsight_rows' in info:                             # hindsight relabelling only
+        vals.update(hindsight_rows=info['hindsight_rows'])
     by_class = info.get('success_by_class')
     if by_class is not None:
         lo = info.get('class_lo', 0)
@@ -1137,7 +1196,7 @@ def next_multiple(n, every):
 
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
-    from robotoddler.training.successor_dqn import EVAL_DEFAULTS, exploration_from_args, make_nets, track_run_sinks
+    from robotoddler.training.successor_dqn import EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets, track_run_sinks
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
@@ -1185,7 +1244,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1),
                    double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
                    priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
-                   priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args))
+                   priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args),
+                   **hindsight_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -1272,6 +1332,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                     **{k: None for k in EPISODE_KEYS})
         if agent.exploration == "boltzmann":                 # (the temperature the NEXT lock-step draws at, as epsilon above)
             info.update(temperature=agent.temperature, explored_fraction=agent.explored_fraction)
+        if agent.hindsight is not None:                      # the relabelled rows this lock-step pushed behind its own records
+            info.update(hindsight_rows=agent.hindsight_rows)
         if eval_envs > 0 and agent.episodes_done >= next_eval:
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)

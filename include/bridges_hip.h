@@ -730,6 +730,39 @@ int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, 
 int bridges_priority_weights(int64_t n_rec, int64_t n_draws, int64_t batch, const int64_t* idx, double beta, const double* scratch,
                              int64_t scratch_doubles, float* weight, void* stream);
 
+/* --- hindsight goal relabelling of the vectorised loop on per-env tasks ("final" strategy) ---------------------------
+ * Every episode that ended in this lock-step is written again, G times, under T targets its own final structure reached.
+ * Inputs (device): buf [E, K, W] f64, the records of every env's running episode in step order (W >= BRIDGES_REC_WIDTH + 3 T: a
+ * record and its task tail, the T targets first); flags [E, K, 8] u8, the step_flags of the step of each record; len [E] i32,
+ * the records held (m); ended [E] u8, set where the record len - 1 has BRIDGES_REC_DONE; episode [E] u32, task_episode of the
+ * buffered episode.  shapes_dev (bridges_shapes_upload), target_shape (cube06), grid_x / grid_y [img], img and gauss_k
+ * [BRIDGES_GAUSS_TAPS] are the env's.  Per ended env e and slot g < G:
+ *   eligible blocks: all m, but the last when its step was not frozen-stable (BRIDGES_REC_STABLE_N == 0): m'; m' == 0: no rows.
+ *   choice: idx = 0 .. m' - 1; for i < min(T, m'): swap(idx[i], idx[j]), j = i + ((u * (m' - i)) >> 32), u = r >> 32,
+ *     h0 = splitmix64(((seed & 0xFFFFFFFF) << 32 | (uint32)(env_id_base + e)) ^ 0x68696E645F726E67)      ("hind_rng")
+ *     h1 = splitmix64(h0 ^ episode[e]);  h2 = splitmix64(h1 ^ g);  r = splitmix64(h2 ^ i)      -- integer arithmetic only
+ *   target q = (cx, 0, cz), the centre of the axis-aligned bounding box of block idx[q mod m'], taken over the block's world
+ *     vertices (rebuilt from the recorded shape id and pose as bridges_pose_block does) exactly as bridges_env_step's
+ *     reached-test takes its box: cx = (x0 + x1) * 0.5.
+ *   rows t = 0, 1, ..: record t with REWARD, LIN, DONE and the 3 T target values of the tail replaced by what bridges_env_step
+ *     records under the new targets: its reached-test (the target after a reached one is skipped), its sparse reward,
+ *     LIN = free-stable ? base : (frozen-stable ? base / 100 : 0) with base the rasteriser's float cand_lin of the block on the
+ *     new targets' reward map (the arithmetic of the per-env task features), DONE = !frozen-stable | all targets reached |
+ *     truncated | no_actions, the four flags read from flags[e, t].  The walk stops after the first t at which all targets are
+ *     reached.  Every other column (TD, the obstacle values of the tail) is copied.
+ * out [E * K * G, W] f64: the rows compacted to the front, env ascending, then g, then t; *count (device i32) their number; rows
+ * beyond it are not written.  Three launches (count, scan, rows), no atomics, no host wait: the same bits on every call.
+ * scratch: bridges_hindsight_relabel_scratch(E, G) bytes, caller-owned, overwritten.
+ * Returns -1 and launches nothing for: E < 0; G outside 1..4; K outside 1..BRIDGES_MAX_BLOCKS; T outside 1..BRIDGES_MAX_TARGETS;
+ * W < BRIDGES_REC_WIDTH + 3 T; a shape table of no or more than 8 shapes or a target_shape outside it; img outside 1..64; a NULL
+ * or misaligned pointer; scratch_bytes below the sizing call's answer.  E == 0 returns 0 and launches nothing. */
+int bridges_hindsight_relabel_scratch(int32_t E, int32_t G, int64_t* bytes);
+int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                              const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
+                              const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
+                              const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
+                              int64_t scratch_bytes, void* stream);
+
 /* Inference epilogues of the conv Q-networks (robotoddler/models/cv.py:5-17, 41-73, 108-170: Conv2d -> ReLU
  * [-> MaxPool2d(2)]), one pass instead of torch's three; bit-identical to relu(conv + bias) / maxpool(relu(conv + bias)).
  * x [n, C, hw] f32 contiguous NCHW output of a bias-free convolution, updated in place (hw % 4 == 0). */

@@ -24,17 +24,21 @@ ap.add_argument("--model", default="SuccessorMLP")
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--episode_stats", action="store_true", help="VecDQN(episode_stats=True) plus one EpisodeStats.take() per lock-step")
 ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI", help="a task family (RandomBridges) instead of the fixed tower")
+ap.add_argument("--random_targets", type=int, default=0, metavar="T",
+                help="> 0: per-env random tasks (RandomTargets(T), no obstacles; VecDQN(per_env_tasks=True)) instead of the fixed tower")
 from bridges_hip.shapes import load_urdf
-from bridges_hip.vec_env import RandomBridges, VecAssemblyGym
+from bridges_hip.vec_env import RandomBridges, RandomTargets, VecAssemblyGym
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
-                                                exploration_from_args, make_nets, priority_from_args)
+                                                exploration_from_args, make_nets, priority_from_args,
+                                                add_hindsight_arguments, hindsight_from_args)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 add_curriculum_arguments(ap)
 add_n_step_argument(ap)
 add_double_q_argument(ap)
 add_priority_arguments(ap, prioritized_flag=True)
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
+add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 a = ap.parse_args()
 sizes = tuple(int(v) for v in a.random_bridge_length.split(":")) if a.random_bridge_length else None
 check_curriculum(vars(a), sizes)
@@ -46,12 +50,14 @@ H = 0.8
 obstacles, targets = [(0.5, 0., i * H + H / 2) for i in range(4)], [(0.5, 0, 4 * H + H / 2)]
 if sizes:
     obstacles, targets = [], RandomBridges("span", sizes=sizes, weights=vars(a).get("family_weights"))
+elif a.random_targets:
+    obstacles, targets = [], RandomTargets(a.random_targets)
 env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, targets, max_steps=15, seed=0, device=dev,
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=False)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
-               "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes), per_env_obstacles=bool(sizes),
+               "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes or a.random_targets), per_env_obstacles=bool(sizes),
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)))
+               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)))
 
 
 def lockstep():

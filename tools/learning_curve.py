@@ -15,7 +15,8 @@ import numpy as np
 import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
-                                                exploration_from_args, make_nets, priority_from_args)
+                                                exploration_from_args, make_nets, priority_from_args,
+                                                add_hindsight_arguments, hindsight_from_args)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
@@ -51,6 +52,7 @@ add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_
 add_double_q_argument(ap)                # --double_q: double Q-learning targets (VecDQN(double_q=True))
 add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
+add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -85,7 +87,7 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True)
                eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)))
+               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)))
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
@@ -124,6 +126,8 @@ for it in range(1, a.locksteps + 1):
                     mean_loss=round(float(np.mean(losses)), 5) if losses else None)
         if agent.exploration == "boltzmann":                    # the block's last lock-step: its share of draws off the arg-max
             line.update(temperature=round(agent.temperature, 4), explored_fraction=r4(agent.explored_fraction))
+        if agent.hindsight is not None:                         # the block's last lock-step: the relabelled rows it pushed
+            line.update(hindsight_rows=agent.hindsight_rows)
         if family:                                              # success per span / height n = LO..HI, and the episodes behind it
             line.update(success_by_class={n: r4(c["success_rate"]) for n, c in enumerate(ep["by_class"]) if n >= family[1]},
                         episodes_by_class={n: c["episodes"] for n, c in enumerate(ep["by_class"]) if n >= family[1]})

@@ -143,8 +143,7 @@ class CapturedTrainStep:
         self.block, self.action = (None, None) if self.conv_rows else (z(N, 1, *S), z(N, 1, *S))
         self.x_all = z(N, 4, *S) if self.conv_rows else None
         self.sf = z(N, px) if self.use_sf else None
-        if self.weights:
-            self.w = z(N)
+        self.w = z(N) if self.weights else None
         self.counter, self.losses = torch.zeros((), dtype=torch.int64, device=dev), z(n)
         self.lane, self.iota = torch.arange(B, device=dev), torch.arange(n, device=dev)
         if self.conv_rows:                                 # read from the caller's tensors by the one launch of a call
@@ -176,10 +175,7 @@ class CapturedTrainStep:
                 pass                                       # another optimiser, or one with options the launch does not cover
 
     def _fused_body(self, block, action, binary, reward, obstacle, q, sf, w=None):
-        if w is not None:
-            self.step.launch(self.counter, block, action, binary, reward, obstacle, q, sf, self.losses, weight_all=w)
-        else:
-            self.step.launch(self.counter, block, action, binary, reward, obstacle, q, sf, self.losses)
+        self.step.launch(self.counter, block, action, binary, reward, obstacle, q, sf, self.losses, weight_all=w)
         if not self.step.fused_adam:                       # else the Adam update is the last launch of the sequence
             self.opt.step()
 
@@ -234,7 +230,7 @@ class CapturedTrainStep:
                     if self.fused:
                         N = self.n_max * self.B
                         self._fused_body(self.block.view(N, -1), self.action.view(N, -1), self.binary, self.reward, self.obstacle,
-                                         self.q, self.sf, self.w if self.weights else None)
+                                         self.q, self.sf, self.w)
                     else:
                         self._autograd_body()
         finally:

@@ -37,6 +37,7 @@ in one pass (the target net is constant meanwhile); the optimiser steps themselv
 """
 import os
 import time
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -55,7 +56,25 @@ from robotoddler.training import train_step as T
 OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
 
 
+class TargetBatch(NamedTuple):
+    """What VecDQN._targets hands to train_steps for n transitions: the five fields of a plain agent's batch in the order they
+    always had, then what only some modes fill or read.  Every tensor is the first n rows of one of the scratch env's."""
+    block_f: Optional[torch.Tensor]                          # [n, 1, S, S] f32 raster of s; None with task_channels
+    binary: torch.Tensor                                     # [n, 6] f32 binary features
+    action_f: Optional[torch.Tensor]                         # [n, 1, S, S] f32 raster of the action block; None with task_channels
+    q_target: torch.Tensor                                   # [n] f32 TD targets
+    sf_target: Optional[torch.Tensor]                        # [n, px] f32 successor-feature targets; None without mse_block_features
+    reward_maps: Optional[torch.Tensor] = None               # [n, px] f32 map of every transition (per_env_tasks, else None)
+    obstacle_bits: Optional[torch.Tensor] = None             # [n, 64] int64 obstacle bit raster of every transition (per_env_obstacles)
+    state_bits: Optional[torch.Tensor] = None                # [n, 64] int64 bit rasters of s and of the action block, filled in every
+    action_bits: Optional[torch.Tensor] = None               # mode: with task_channels the train step builds its rows from them
+
+
 class VecDQN:
+    # an instance that __init__ has not filled (tests build such stand-ins with __new__) reads the loop as it was
+    exploration, n_step, rows_fed = "epsilon_greedy", 1, 0
+    hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = None
+
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
@@ -263,11 +282,11 @@ class VecDQN:
         self._eager_reduce = None                            # dqn_ops.ReduceTables of the eager optimiser steps
         self.episodes_done = 0
         self.env_steps = 0
-        # (env-steps, finished episodes) of a lock-step; n-step returns on one rank: and the emitted rows
-        # Boltzmann exploration: and, last, the envs whose draw left the first maximum
-        # hindsight relabelling: and, after those, the relabelled rows
-        self._counts_host = torch.zeros((3 if self.n_step > 1 else 2) + (self.exploration == "boltzmann") + (self.hindsight is not None),
-                                        dtype=torch.int64).pin_memory()
+        # the counts of a lock-step (_count): env-steps and finished episodes; n-step returns: the emitted rows (one rank);
+        # Boltzmann exploration: the envs whose draw left the first maximum; hindsight relabelling: the relabelled rows
+        self._count_names = (("valid", "done") + (("emitted",) if self.n_step > 1 else ())
+                             + (("explored",) if self.exploration == "boltzmann" else ()) + (("hindsight",) if self.hindsight is not None else ()))
+        self._counts_host = torch.zeros(len(self._count_names), dtype=torch.int64).pin_memory()
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
         # (a task family -- RandomBridges -- keeps them per class as well: one row per span / height n = 0..hi)
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
@@ -324,13 +343,12 @@ class VecDQN:
         env._dqn_rows = (env._cand_version, out)
         if self.TRACK_ROWS:
             seen = env.n_valid[:env.E].sum()
-            self._rows_seen_dev = seen if getattr(self, "_rows_seen_dev", None) is None else self._rows_seen_dev + seen
+            self._rows_seen_dev = seen if self._rows_seen_dev is None else self._rows_seen_dev + seen
         return out
 
     @property
     def rows_seen(self):
-        dev = getattr(self, "_rows_seen_dev", None)
-        return int(dev) if dev is not None else 0
+        return int(self._rows_seen_dev) if self._rows_seen_dev is not None else 0
 
     def _distinct_rows(self, env, idx, row_env, stable_flag):
         """Candidate rows whose network input is the same tensor, bit for bit: the input of a row is (state raster of its env,
@@ -346,7 +364,7 @@ class VecDQN:
         n = idx.numel()
         if not self.DEDUP_ROWS or n < 2:
             return None
-        m = getattr(self, "_hash_mult", None)
+        m = self._hash_mult
         if m is None:
             g = torch.Generator().manual_seed(0x5eed5)
             m = self._hash_mult = (torch.randint(-2 ** 62, 2 ** 62, (2, 64), generator=g, dtype=torch.int64) | 1).to(self.device)
@@ -387,7 +405,7 @@ class VecDQN:
         return words.contiguous().view(torch.int64)
 
     def _task_hash_mult(self, w):
-        m = getattr(self, "_task_mult", None)
+        m = self._task_mult
         if m is None or m.numel() != w:
             g = torch.Generator().manual_seed(0x7a5c)
             m = self._task_mult = (torch.randint(-2 ** 62, 2 ** 62, (w,), generator=g, dtype=torch.int64) | 1).to(self.device)
@@ -407,7 +425,7 @@ class VecDQN:
             rep, inverse = groups
             idx, row_env = idx.index_select(0, rep), row_env.index_select(0, rep)
         n, C = idx.numel(), self.ROW_CHUNK
-        self.rows_fed = getattr(self, "rows_fed", 0) + n
+        self.rows_fed += n
         pad = (-n) % C
         if pad:
             idx = torch.cat([idx, idx[:1].expand(pad)])
@@ -487,7 +505,7 @@ class VecDQN:
         # the first layer consumes the BIT-PACKED rasters (bridges_bits_linear): a raster times a weight slice is the
         # sum of the ~35 weight rows of its set pixels, so neither f32 images nor a [n, 4096] GEMM
         px = 64 * 64
-        self.rows_fed = getattr(self, "rows_fed", 0) + idx.numel()
+        self.rows_fed += idx.numel()
         W1 = net.first_layer().weight
         if getattr(env, "per_env_tasks", False):
             # every env owns its reward map: the image-independent part of the first layer is a [E, 2, hidden] table (one
@@ -555,7 +573,7 @@ class VecDQN:
         stable = self._stable_flags(env)
         idx, row_env, seg, rep = self._rows(env, stable)
         q_sel = torch.zeros(E, dtype=torch.float32, device=self.device)
-        if idx.numel() and getattr(self, "exploration", "epsilon_greedy") == "boltzmann":
+        if idx.numel() and self.exploration == "boltzmann":
             # every env draws its row from softmax(q / temperature) with its own uniform, in ONE launch (bridges_boltzmann_select;
             # greedy: the first maximum, as below); no overlap with the count images is computed and none is added to them.  Envs
             # in the same state still share their representative's rows, but stop acting alike sooner than under a greedy choice
@@ -597,7 +615,7 @@ class VecDQN:
                               if self.per_env_obstacles else env.env_targets.reshape(E, -1).clone())
         if getattr(env, "task_family", None) is not None:
             env._task_class = env.task_class.clone()            # likewise the class: the step that ends an episode redraws it
-        if getattr(self, "hindsight", None) is not None and env is self.env:
+        if self.hindsight is not None and env is self.env:
             env._task_episode = env.task_episode.clone()        # and the episode counter, which keys the hindsight draw
         env.step(sel_index)
         valid = R.pack_result(env, rec)
@@ -625,7 +643,7 @@ class VecDQN:
         (the eval env's seed, env, episode 0): a fixed held-out task set, not fresh tasks per evaluation."""
         if eval_env is self.env:
             raise ValueError("evaluate() needs an env of its own: the training env's episodes would be cut short")
-        if float(epsilon) > 0.0 and getattr(self, "exploration", "epsilon_greedy") == "boltzmann":
+        if float(epsilon) > 0.0 and self.exploration == "boltzmann":
             raise ValueError("evaluate(epsilon > 0) explores with the epsilon-greedy rule on count images; an agent built with "
                              "exploration='boltzmann' evaluates greedily only (epsilon=0)")
         if bool(getattr(eval_env, "stable_actions_only", False)) != self.stable_actions_only:
@@ -697,14 +715,12 @@ class VecDQN:
         double_q: a second forward, the policy net's as it stands now, over the same rows behind the first, and the target launch
         selects every transition's row by its q (k_td_target_select); the conv nets' distinct rows are found once for both.
         Per-env tasks: the records' tails (their targets) go to the scratch env first, which rebuilds every transition's reward
-        map from them (bridges_env_load_targets; envs beyond n repeat record 0's task, as their states do); a sixth value is
-        returned then, the [n, px] maps of the transitions (a view of the scratch env's reward_maps: valid until the next call).
+        map from them (bridges_env_load_targets; envs beyond n repeat record 0's task, as their states do).
         Per-env obstacles: the tails' obstacles go in beside the targets (load_task: one bridges_env_load_targets), so the
-        rasteriser filters every next state's candidates against its transition's own obstacles; a seventh value is returned,
-        the bit-packed obstacle rasters of the transitions [n, 64] int64 (a view of the scratch env's env_obstacle_bits).
-        task_channels: the target net's rows come from _row_features on the scratch env (one ops.conv_input per chunk), block_f
-        and action_f are None -- no f32 image of a transition is built -- and two more values follow the task's: the bit
-        rasters of s and of the action block, [n, 64] int64 each, from which the train step builds its rows."""
+        rasteriser filters every next state's candidates against its transition's own obstacles.
+        task_channels: the target net's rows come from _row_features on the scratch env (one ops.conv_input per chunk) and no
+        f32 image of a transition is built.
+        -> a TargetBatch (the fields are listed there) of views: valid until the next call."""
         n = rec.shape[0]
         renv = self._replay_env(n)
         E = renv.E
@@ -784,13 +800,10 @@ class VecDQN:
         binary[:, 0] = stable_s
         if self.priority_refresh:                            # (s_t, a_t) of every transition, for _transition_q
             self._transitions = (renv, bits_s, action_bits, stable_s, block_f, action_f)
-        if self.task_channels:
-            out = (None, binary[:n], None, q_target[:n], (sf_target[:n] if use_sf else None), renv.reward_maps_img[:n].reshape(n, -1))
-            return out + ((renv.env_obstacle_bits[:n],) if self.per_env_obstacles else ()) + (bits_s[:n], action_bits[:n])
-        out = (block_f[:n], binary[:n], action_f[:n], q_target[:n], (sf_target[:n] if use_sf else None))
-        if self.per_env_obstacles:
-            return out + (renv.reward_maps_img[:n].reshape(n, -1), renv.env_obstacle_bits[:n])
-        return out + (renv.reward_maps_img[:n].reshape(n, -1),) if self.per_env_tasks else out
+        return TargetBatch(None if self.task_channels else block_f[:n], binary[:n], None if self.task_channels else action_f[:n],
+                           q_target[:n], sf_target[:n] if use_sf else None, state_bits=bits_s[:n], action_bits=action_bits[:n],
+                           reward_maps=renv.reward_maps_img[:n].reshape(n, -1) if self.per_env_tasks else None,
+                           obstacle_bits=renv.env_obstacle_bits[:n] if self.per_env_obstacles else None)
 
     @torch.no_grad()
     def _transition_q(self, n):
@@ -880,39 +893,33 @@ class VecDQN:
         # n_steps independent batches = ONE draw of n_steps * B records: both sampling rules draw with replacement, so
         # the batches are i.i.d. either way (25 separate draws cost ~100 launches of host time per lock-step)
         drawn = weights = None
-        if self.priority_beta is not None:
-            # importance-sampling weights: always the sampler kernel (they need the draws' rows and the masses), and the weights
-            # directly behind the draw -- they describe the distribution it was made from, before any refresh
+        if self.priority_beta is not None or self.priority_refresh or self.priority_alpha != 1.0:
+            # the sampler kernel: the exponent, and the ring rows of the draws for the refresh and the weights
             rec, drawn = self.ring.sample_prioritized(n_steps * B, self.sample_gen, self.priority_alpha)
-            weights = self.ring.sample_weights(drawn, B, self.beta_now())
-            self.priority_beta_calls += 1
-        elif self.priority_refresh or self.priority_alpha != 1.0:
-            # the sampler kernel: the exponent, and the ring rows of the draws for the refresh
-            rec, drawn = self.ring.sample_prioritized(n_steps * B, self.sample_gen, self.priority_alpha)
+            if self.priority_beta is not None:
+                # importance-sampling weights (they need the draws' rows and the masses) directly behind the draw: they describe
+                # the distribution it was made from, before any refresh
+                weights = self.ring.sample_weights(drawn, B, self.beta_now())
+                self.priority_beta_calls += 1
         else:
             rec = self.ring.sample(n_steps * B, self.sample_gen, self.prioritized)
-        block_f, binary, action_f, q_target, sf_target, *task = self._targets(rec)
+        batch = self._targets(rec)
+        binary, q_target, sf_target, maps, obst_bits = batch.binary, batch.q_target, batch.sf_target, batch.reward_maps, batch.obstacle_bits
         if self.priority_refresh:
             # |q(s_t, a_t) - q_target| of the policy net as it stands now, back to the sampled rows in one launch (once per
             # lock-step for all n_steps batches, the approximation double_q makes); q_target is what _targets returned, whatever
             # the loss parts are
             self.ring.update_priorities(drawn, self._transition_q(n_steps * B), q_target)
-        if self.task_channels:                               # the transitions' bit rasters stand in for their f32 images
-            block_f, action_f = task[-2:]
-            task = task[:-2]
-        maps = task[0] if task else None                     # per-env tasks: the reward map of every transition [n_steps * B, px]
-        obst_bits = task[1] if len(task) > 1 else None       # per-env obstacles: its bit-packed obstacle raster [n_steps * B, 64]
+        # task_channels: the transitions' bit rasters stand in for their f32 images
+        block, action = (batch.state_bits, batch.action_bits) if self.task_channels else (batch.block_f, batch.action_f)
         drv = self._train_step(n_steps)
-        if weights is not None:
-            out = drv.run(n_steps, block_f, action_f, binary, maps, obst_bits, q_target, sf_target, weights=weights)
-        else:
-            out = drv.run(n_steps, block_f, action_f, binary, maps, obst_bits, q_target, sf_target)
+        out = drv.run(n_steps, block, action, binary, maps, obst_bits, q_target, sf_target, weights=weights)
         if out is None:
             drv = None
             S = self.env.img
             if self.task_channels:
                 # the rows of all n_steps * B transitions as the captured step builds them: one launch from bits and maps
-                x = ops.conv_input(block_f, action_f, maps, obst_bits if obst_bits is not None else self.env.obstacle_bits.reshape(1, 64))
+                x = ops.conv_input(block, action, maps, obst_bits if obst_bits is not None else self.env.obstacle_bits.reshape(1, 64))
             else:
                 reward = self.env.reward_features.unsqueeze(0).expand(B, -1, -1, -1) if maps is None else None
                 obstacle = self.env.obstacle_raster.unsqueeze(0).expand(B, -1, -1, -1) if obst_bits is None else None
@@ -928,11 +935,8 @@ class VecDQN:
                         reward = maps[sl].reshape(B, 1, S, S)
                     if obst_bits is not None:
                         obstacle = ops.bits_to_f32(obst_bits[sl]).reshape(B, 1, S, S)
-                    q, sf, _ = self.policy_net(block_f[sl], binary[sl], action_f[sl], reward, obstacle)
-                if weights is not None:
-                    loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None, weights[sl])
-                else:
-                    loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None)
+                    q, sf, _ = self.policy_net(block[sl], binary[sl], action[sl], reward, obstacle)
+                loss = self._loss(q, sf, q_target[sl], sf_target[sl] if sf_target is not None else None, weights[sl] if weights is not None else None)
                 self.opt.zero_grad()
                 if self._eager_reduce is None:
                     self._eager_reduce = dqn_ops.ReduceTables(self.device)
@@ -963,14 +967,14 @@ class VecDQN:
         blob = dict(epsilon=float(self.epsilon), episodes_done=int(self.episodes_done), env_steps=int(self.env_steps),
                     step_images=self.step_images.cpu(), sample_gen=self.sample_gen.get_state().cpu(),
                     explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()},
-                    task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)), n_step=int(getattr(self, "n_step", 1)))
-        if getattr(self, "curriculum", None) is not None:    # one more key: (ema, seen), weights, sums and accumulator
+                    task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)), n_step=int(self.n_step))
+        if self.curriculum is not None:                      # one more key: (ema, seen), weights, sums and accumulator
             blob["curriculum"] = self.curriculum.state_dict()
-        if getattr(self, "priority_beta", None) is not None:  # one more key: the annealing clock of the weights' exponent
+        if self.priority_beta is not None:                   # one more key: the annealing clock of the weights' exponent
             blob["priority_beta_calls"] = int(self.priority_beta_calls)
-        if getattr(self, "exploration", "epsilon_greedy") == "boltzmann":      # one more key: where the schedule stands
+        if self.exploration == "boltzmann":                  # one more key: where the schedule stands
             blob["temperature"] = float(self.temperature)
-        if getattr(self, "hindsight", None) is not None:      # two more keys: the setting and the running episodes
+        if self.hindsight is not None:                       # two more keys: the setting and the running episodes
             blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
             blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
         torch.save(blob, path)
@@ -991,13 +995,13 @@ class VecDQN:
                              f"agent's end in {want[0]} targets and {want[1]} obstacles: the tails do not mean the same task")
         # (a file written before the loop had n-step returns carries no entry: its rows are one-step records)
         got_n = int(blob.get("n_step", 1))
-        want_n = int(getattr(self, "n_step", 1))
+        want_n = int(self.n_step)
         if got_n != want_n:
             raise ValueError(f"{path} was written by a run with n_step = {got_n}, this agent folds n_step = {want_n}: the rows "
                              "of the ring do not mean the same returns")
         # (a file of a run without hindsight relabelling carries no entry)
         got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
-        want_h = (str(self.hindsight), int(self.hindsight_goals)) if getattr(self, "hindsight", None) is not None else None
+        want_h = (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None
         if got_h != want_h:
             raise ValueError(f"{path} was written by a run with (hindsight, hindsight_goals) = {got_h}, this agent has {want_h}: the "
                              "ring does not hold the same mix of rolled-out and relabelled rows")
@@ -1010,11 +1014,11 @@ class VecDQN:
             self.explore_gen.set_state(blob["explore_gen"])
         else:
             self.explore_gen.manual_seed(7654321 + self.seed * 1000 + self.rank + 7919 * (int(blob["counters"].get("lockstep", 0)) + 1))
-        if getattr(self, "curriculum", None) is not None and "curriculum" in blob:     # continue with the same table
+        if self.curriculum is not None and "curriculum" in blob:     # continue with the same table
             self.curriculum.load_state_dict(blob["curriculum"])
-        if getattr(self, "priority_beta", None) is not None:  # (a file of a run without the option carries no entry: 0)
+        if self.priority_beta is not None:                   # (a file of a run without the option carries no entry: 0)
             self.priority_beta_calls = int(blob.get("priority_beta_calls", 0))
-        if getattr(self, "exploration", "epsilon_greedy") == "boltzmann":      # (a file of a run without the option: temp_start)
+        if self.exploration == "boltzmann":                  # (a file of a run without the option: temp_start)
             self.temperature = float(blob.get("temperature", self.temp_start))
         return blob["counters"]
 
@@ -1025,7 +1029,7 @@ class VecDQN:
         into the next one; the pending starts (up to n - 1 transitions per env) are dropped, they never reach the ring."""
         if self._window is not None:
             self._window[0].zero_()
-        if getattr(self, "hindsight_buffer", None) is not None:      # hindsight relabelling: the running episodes go with them
+        if self.hindsight_buffer is not None:                # hindsight relabelling: the running episodes go with them
             self.hindsight_buffer.clear()
 
     def _fold(self, rec, valid):
@@ -1035,6 +1039,10 @@ class VecDQN:
             self._window = (torch.zeros(rows, dtype=torch.int32, device=self.device),
                             *(torch.zeros((rows, n), dtype=torch.float64, device=self.device) for _ in range(4)))
         return dqn_ops.nstep_fold(rec.contiguous(), valid, self.gamma, self.n_step, *self._window)
+
+    def _count(self, name):
+        """One of the last lock-step's counts, as it arrived in pinned memory."""
+        return int(self._counts_host[self._count_names.index(name)])
 
     def lockstep(self, n_train_steps, defer_losses=False):
         """act -> all-gather -> replay push -> n optimiser steps -> soft update.  defer_losses=True returns the losses as
@@ -1055,48 +1063,43 @@ class VecDQN:
         # ONE wait per lock-step on this side: the two counts ride to pinned memory in front of the next act's candidate rows,
         # whose row count the host has to wait for anyway (bridges_valid_rows)
         done_rec = valid & (rec[:, R.O_DONE] > 0.5)
-        counts = [valid.sum(), done_rec.sum()]
-        folded = None
-        if self.n_step > 1 and not D.active():
+        counts = dict(valid=valid.sum(), done=done_rec.sum())
+        if self.n_step > 1:
             # one rank: the fold runs here, and the number of emitted rows rides with the two counts -- no wait of its own
-            folded = self._fold(self.with_task(rec), valid)
-            counts.append(folded[1].sum())
-        elif self.n_step > 1:
-            counts.append(torch.zeros_like(counts[0]))
+            folded = self._fold(self.with_task(rec), valid) if not D.active() else None
+            counts["emitted"] = folded[1].sum() if folded is not None else torch.zeros_like(counts["valid"])
         boltzmann = self.exploration == "boltzmann"
         if boltzmann:                                   # the envs that left the arg-max ride with the counts: no wait of their own
-            counts.append((self._ex_w * valid).sum().to(torch.int64) if self._ex_w is not None else torch.zeros_like(counts[0]))
+            counts["explored"] = (self._ex_w * valid).sum().to(torch.int64) if self._ex_w is not None else torch.zeros_like(counts["valid"])
         hind = None
         if self.hindsight is not None:
             # the lock-step joins every env's running episode; the episodes that end are relabelled at once (three launches) and
             # the number of rows that came out rides with the counts: no wait of its own
-            hb = self.hindsight_buffer
-            hb.write(self.with_task(rec), self.env.step_flags, valid, self.env._task_episode)
-            hind = hb.relabel(self.env, done_rec)
-            counts.append(hind[1][0].to(torch.int64))
-        self._counts_host.copy_(torch.stack(counts), non_blocking=True)
+            self.hindsight_buffer.write(self.with_task(rec), self.env.step_flags, valid, self.env._task_episode)
+            hind = self.hindsight_buffer.relabel(self.env, done_rec)
+            counts["hindsight"] = hind[1][0].to(torch.int64)
+        self._counts_host.copy_(torch.stack([counts[k] for k in self._count_names]), non_blocking=True)
         arrived = torch.cuda.Event()
         arrived.record()
         self._rows(self.env, self._stable_flags(self.env))
         arrived.synchronize()                           # passed already unless the rows came out of the env's cache
-        n_valid, n_done = int(self._counts_host[0]), int(self._counts_host[1])
+        n_valid, n_done = self._count("valid"), self._count("done")
         self.env_steps += n_valid
         if boltzmann:
-            self.explored_fraction = int(self._counts_host[-1 - (hind is not None)]) / n_valid if n_valid else None
-        if self.n_step > 1:
-            if folded is None:
-                # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
-                # windows and pushes the same rows; the collective carries what it carries for n_step = 1
-                out, out_valid = self._fold(*D.all_gather_rows(self.with_task(rec), valid))
-                allrec = out[out_valid]
-            else:
-                out, out_valid = folded
-                allrec = out.index_select(0, torch.nonzero_static(out_valid, size=int(self._counts_host[2])).squeeze(1))
+            self.explored_fraction = self._count("explored") / n_valid if n_valid else None
+        if self.n_step > 1 and folded is None:
+            # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
+            # windows and pushes the same rows; the collective carries what it carries for n_step = 1
+            out, out_valid = self._fold(*D.all_gather_rows(self.with_task(rec), valid))
+            allrec = out[out_valid]
+        elif self.n_step > 1:
+            out, out_valid = folded
+            allrec = out.index_select(0, torch.nonzero_static(out_valid, size=self._count("emitted")).squeeze(1))
         else:
             allrec = D.all_gather_records(self.with_task(rec), valid, n_valid=n_valid)
         self.ring.push(allrec)
         if hind is not None:                            # behind the lock-step's own records
-            self.hindsight_rows = int(self._counts_host[-1])
+            self.hindsight_rows = self._count("hindsight")
             self.ring.push(hind[0][:self.hindsight_rows])
         if not D.active():
             self.episodes_done += n_done

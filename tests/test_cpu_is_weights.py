@@ -178,7 +178,8 @@ def test_loop_without_the_option_never_reaches_the_weights(monkeypatch):
         asked.append(config.get("weights"))
         raise _Reached
     monkeypatch.setattr(T.CapturedTrainStep, "of", classmethod(of))
-    blank = tuple(torch.zeros(1) for _ in range(5))
+    from robotoddler.training.vec_dqn import TargetBatch
+    blank = TargetBatch(*(torch.zeros(1) for _ in range(5)))
     for kw in ({}, dict(priority_beta=None, priority_beta_anneal=0), dict(priority_alpha=0.5, priority_beta=None)):
         a = host_agent(monkeypatch, stand_in_env(), prioritized=True, **kw)
         seen = []
@@ -207,7 +208,8 @@ def test_loop_with_the_option_draws_through_the_kernel_and_hands_the_weights_on(
             raise _Reached
     monkeypatch.setattr(T.CapturedTrainStep, "of", classmethod(lambda cls, *a, **config: events.append(("of", config["weights"])) or Driver()))
     a = host_agent(monkeypatch, stand_in_env(), prioritized=True, priority_beta=0.25, priority_beta_anneal=3)
-    _loaded(a, lambda rec: events.append(("targets",)) or tuple(torch.zeros(1) for _ in range(5)))
+    from robotoddler.training.vec_dqn import TargetBatch
+    _loaded(a, lambda rec: events.append(("targets",)) or TargetBatch(*(torch.zeros(1) for _ in range(5))))
     idx, w = torch.arange(8), torch.linspace(0.1, 1.0, 8)
     a.ring.sample_prioritized = lambda n, gen, alpha: (events.append(("draw", n, alpha)) or a.ring.data[:n], idx)
     a.ring.sample_weights = lambda i, batch, beta: events.append(("weights", i is idx, batch, beta)) or w

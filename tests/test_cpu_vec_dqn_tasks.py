@@ -128,3 +128,18 @@ def test_replay_ring_width(tmp_path):
     assert len(wide) == 8                                                 # a refused load leaves the ring as it was
     ring.load(narrow)
     assert len(ring) == 3
+
+
+def test_target_batch_fields_and_class_defaults():
+    """The batch _targets returns keeps a plain agent's five values in front and fills the rest only where a mode has them; an
+    agent that __init__ has not filled reads every option as switched off."""
+    from robotoddler.training.vec_dqn import TargetBatch, VecDQN
+    assert TargetBatch._fields[:5] == ("block_f", "binary", "action_f", "q_target", "sf_target")
+    assert TargetBatch._fields[5:] == ("reward_maps", "obstacle_bits", "state_bits", "action_bits")
+    five = tuple(torch.zeros(1) for _ in range(5))
+    batch = TargetBatch(*five)
+    assert all(a is b for a, b in zip(batch[:5], five)) and batch[5:] == (None, None, None, None)
+    a = VecDQN.__new__(VecDQN)
+    assert a.exploration == "epsilon_greedy" and a.n_step == 1 and a.rows_fed == 0 and a.rows_seen == 0
+    for name in ("hindsight", "hindsight_buffer", "curriculum", "priority_beta", "_rows_seen_dev", "_hash_mult", "_task_mult"):
+        assert getattr(a, name) is None and name not in vars(a), name

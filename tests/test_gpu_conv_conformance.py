@@ -921,7 +921,7 @@ def test_captured_step_with_a_nan_pixel_reports_it_and_is_undone(model, loss, mo
     drv = pol._fused_trainer
     assert agent._graph_state is not None and not drv.fused and drv._graphs and "guard" in drv.state, "the step was not captured"
     rec = agent.ring.sample(n * B, agent.sample_gen)
-    block, binary, action, q_t, sf_t = agent._targets(rec)
+    block, binary, action, q_t, sf_t = agent._targets(rec)[:5]
     good = drv.run(n, block, action, binary, None, None, q_t, sf_t).clone()
     assert bool(torch.isfinite(good).all()) and bool((good >= 0).all())
     tensors = drv._guard_tensors()

@@ -292,7 +292,8 @@ def check_targets(multi, multi_rows, single, log, emitted):
         assert len(windows[-1]) == h
     taus = torch.tensor([w[-1] for w in windows], device=DEV)
     last = [o.clone() if torch.is_tensor(o) else o for o in single._targets(valid_recs[taus])]
-    one = [o.clone() if torch.is_tensor(o) else o for o in single._targets(valid_recs)]
+    one = single._targets(valid_recs)
+    one = type(one)(*(o.clone() if torch.is_tensor(o) else o for o in one))
     many = multi._targets(multi_rows)
     torch.cuda.synchronize()
     use_sf = one[4] is not None
@@ -303,8 +304,9 @@ def check_targets(multi, multi_rows, single, log, emitted):
         for k in (0, 1, 2):                                                            # block_f, binary, action_f of step t
             if one[k] is not None:
                 assert torch.equal(many[k][i], one[k][t]), (i, k)
-        for k in range(5, len(one)):                                                   # the task: map (and obstacle bits)
-            assert torch.equal(many[k][i], one[k][t]), (i, k)
+        for k in one._fields[5:]:                                                      # the task's map and obstacle bits, the bit rasters
+            if getattr(one, k) is not None:
+                assert torch.equal(getattr(many, k)[i], getattr(one, k)[t]), (i, k)
         G = float(multi_rows[i, R.O_LIN])
         gh1 = GAMMA ** (h - 1)
         X = gh1 * (float(last[3][i]) - float(lin1[tau]))

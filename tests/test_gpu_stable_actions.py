@@ -246,7 +246,7 @@ def test_vec_dqn_acts_and_targets_over_stable_candidates(model):
     # TD targets: a masked max over the replay env's stable next candidates, in plain torch
     n = 64
     rec = agent.ring.sample(n, agent.sample_gen)
-    _b, _bin, _a, q_target, _sf = agent._targets(rec)
+    q_target = agent._targets(rec).q_target
     renv = agent.replay_env
     total = renv.total_candidates()
     full = renv.cand_mask[:total].bool()

@@ -198,9 +198,9 @@ def plain_steps(agent, n_steps):
     from bridges_hip import dqn_ops, ops
     B = agent.B
     rec = agent.ring.sample(n_steps * B, agent.sample_gen, agent.prioritized)
-    _none, binary, _none2, q_target, sf_target, maps, *rest = agent._targets(rec)
-    obst_bits, (bits_s, bits_a) = (rest[0] if agent.per_env_obstacles else None), rest[-2:]
-    block_f, action_f = ops.bits_to_f32(bits_s).unsqueeze(1), ops.bits_to_f32(bits_a).unsqueeze(1)
+    batch = agent._targets(rec)
+    binary, q_target, sf_target, maps, obst_bits = batch.binary, batch.q_target, batch.sf_target, batch.reward_maps, batch.obstacle_bits
+    block_f, action_f = ops.bits_to_f32(batch.state_bits).unsqueeze(1), ops.bits_to_f32(batch.action_bits).unsqueeze(1)
     reward_f = maps.reshape(-1, 1, 64, 64).clone()
     obst_f = (ops.bits_to_f32(obst_bits) if obst_bits is not None
               else ops.bits_to_f32(agent.env.obstacle_bits.reshape(1, 64)).expand(n_steps * B, -1, -1).contiguous()).unsqueeze(1)

@@ -304,7 +304,8 @@ def test_replay_rebuilds_every_transitions_obstacles(n):
     gamma = agent.gamma
     rec = agent.ring.sample(n, agent.sample_gen)
     assert rec.shape[1] == 126
-    block_f, binary, action_f, q_target, sf_target, maps, obst_bits = agent._targets(rec)
+    batch = agent._targets(rec)
+    action_f, q_target, sf_target, maps, obst_bits = batch.action_f, batch.q_target, batch.sf_target, batch.reward_maps, batch.obstacle_bits
     renv = agent.replay_env
     assert renv.E >= n and renv.per_env_tasks and renv.per_env_obstacles and renv.random_obstacles is None and renv.random_targets is None
     assert tuple(maps.shape) == (n, 4096) and tuple(obst_bits.shape) == (n, 64) and obst_bits.dtype == torch.int64
@@ -645,7 +646,8 @@ def test_a_targets_only_agent_is_what_it_was():
         drv = pol._fused_trainer
         assert drv.task_rows and not drv.obstacle_rows and drv._graphs
         assert drv.obstacle.dtype == torch.float32 and tuple(drv.obstacle.shape) == (4096,) and not drv.obstacle.any()
-        assert len(agent._targets(agent.ring.sample(16, agent.sample_gen))) == 6
+        batch = agent._targets(agent.ring.sample(16, agent.sample_gen))
+        assert batch.reward_maps is not None and batch.obstacle_bits is None
         out.append((losses, torch.cat([p.detach().flatten() for p in pol.parameters()]).clone()))
     assert out[0][0] == out[1][0] and all(len(l) == 2 for l in out[0][0][1:]) and torch.equal(out[0][1], out[1][1])
     # refusals on real envs

@@ -422,7 +422,8 @@ def test_replay_rebuilds_every_transitions_task(n):
     gamma = agent.gamma
     rec = agent.ring.sample(n, agent.sample_gen)
     assert rec.shape[1] == 120
-    block_f, binary, action_f, q_target, sf_target, maps = agent._targets(rec)
+    batch = agent._targets(rec)
+    action_f, q_target, sf_target, maps = batch.action_f, batch.q_target, batch.sf_target, batch.reward_maps
     renv = agent.replay_env
     Er = renv.E
     assert Er >= n and renv.per_env_tasks and tuple(maps.shape) == (n, 4096)
@@ -464,6 +465,51 @@ def test_replay_rebuilds_every_transitions_task(n):
     assert torch.allclose(sf_target, want_sf, rtol=1e-5, atol=1e-5), float((sf_target - want_sf).abs().max())
     with pytest.raises(ValueError, match="120"):
         agent._targets(rec[:, :R.RECORD_WIDTH])
+
+
+def batch_agent(mode, E=16, B=8):
+    """An agent of every mode that fills other fields of the batch, on E envs (two obstacles per env where the mode has them)."""
+    from bridges_hip.shapes import load_urdf
+    from bridges_hip.vec_env import RandomObstacles, RandomTargets, VecAssemblyGym
+    from robotoddler.training.successor_dqn import build_parser, make_nets
+    from robotoddler.training.vec_dqn import VecDQN
+    tasks, obstacles, conv = mode != "plain", mode.endswith("obstacles"), mode.startswith("conv")
+    env = VecAssemblyGym(E, [load_urdf("shapes/trapezoid.urdf")], RandomObstacles([((-3.0, 3.0), (0.3, 2.5))] * 2) if obstacles else [],
+                         RandomTargets() if tasks else [tuple(t) for t in TASKS4[0]], max_steps=6, seed=11, f32_rasters=not tasks)
+    if not conv:
+        return make_agent(env, per_env_tasks=tasks, B=B, per_env_obstacles=obstacles)
+    torch.manual_seed(5)
+    pol, tgt = make_nets(vars(build_parser().parse_args(["--model", "ConvNet"])), torch.device(DEV))
+    return VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 8192, B, 0.95, 0.01, "mse_q_values", seed=3,
+                  per_env_tasks=True, per_env_obstacles=obstacles, task_channels=True)
+
+
+@pytest.mark.parametrize("mode", ["plain", "tasks", "tasks+obstacles", "conv", "conv+obstacles"])
+def test_target_batch_fields_by_mode(mode):
+    """Which fields of _targets' batch a mode fills, their shapes and dtypes, the bit rasters against the f32 images where both
+    exist, and one optimiser step on what train_steps picks from the batch by name."""
+    from bridges_hip import ops
+    from robotoddler.training.vec_dqn import TargetBatch
+    agent = batch_agent(mode)
+    for _ in range(5):
+        rec, valid = agent.act()
+        agent.ring.push(agent.with_task(rec)[valid])
+    n, px = 16, 4096
+    batch = agent._targets(agent.ring.sample(n, agent.sample_gen))
+    assert isinstance(batch, TargetBatch)
+    is_f32 = lambda t, *shape: torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == shape
+    is_bits = lambda t: torch.is_tensor(t) and t.dtype == torch.int64 and tuple(t.shape) == (n, 64)
+    assert is_f32(batch.binary, n, 6) and is_f32(batch.q_target, n) and is_bits(batch.state_bits) and is_bits(batch.action_bits)
+    if mode.startswith("conv"):                              # (mse_q_values alone: no successor-feature target either)
+        assert batch.block_f is None and batch.action_f is None and batch.sf_target is None
+    else:
+        assert is_f32(batch.block_f, n, 1, 64, 64) and is_f32(batch.action_f, n, 1, 64, 64) and is_f32(batch.sf_target, n, px)
+        assert torch.equal(ops.bits_to_f32(batch.state_bits), batch.block_f.squeeze(1))
+        assert torch.equal(ops.bits_to_f32(batch.action_bits), batch.action_f.squeeze(1))
+    assert batch.reward_maps is None if mode == "plain" else is_f32(batch.reward_maps, n, px)
+    assert is_bits(batch.obstacle_bits) if mode.endswith("obstacles") else batch.obstacle_bits is None
+    losses = agent.train_steps(1)
+    assert len(losses) == 1 and np.isfinite(losses[0])
 
 
 # ------------------------------------------------------------------------------------------------------------ 7: optimiser step

@@ -203,6 +203,24 @@ class TaskFamily(C.Structure):
                 ("size", C.c_double), ("x", C.c_double), ("task_class", C.c_void_p)]
 
 
+# bridges_env_fork (the table fork_table() of csrc/api.hip, in its order): the per-env STATE arrays a fork copies -- fields of
+# bridges_env_buffers, then of bridges_task_buffers, then of bridges_task_family -- and the per-env buffers it deliberately
+# leaves alone, each with its reason.  A per-env buffer that stands in neither list fails tests/test_cpu_beam.py.
+FORK_ENV_FIELDS = ("n_blocks", "blk_shape", "blk_pose", "blk_verts", "blk_occ", "targets_left", "state_bits", "n_if", "if_body",
+                   "if_geom", "draw_counter", "needs_reset", "step_flags", "reward", "lin_reward", "n_reached", "n_cand", "lp_ws",
+                   "lp_snap")
+FORK_TASK_FIELDS = ("env_targets", "target_bits", "reward_map", "reward_prefix", "task_episode", "env_obstacles", "env_obstacle_bits")
+FORK_FAMILY_FIELDS = ("task_class",)
+FORK_EXCLUDED = {
+    "sel_index": "an input of the next step, written by its caller",
+    "n_valid": "candidate array: recounted by the refresh after the fork",
+    "cand_offset": "candidate array: the prefix sum of the refresh",
+    "state_raster": "rewritten from state_bits by the refresh",
+    "state_raster_nz": "describes the buffer slot (what the sparse update left in it), not the env",
+}
+BEAM_MAX_WIDTH = 16                            # bridges_beam_select: 1 <= B <= 16
+
+
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)
 assert [f[0] for f in EnvBuffers._fields_][-10:-7] == ["lp_ws", "lp_ws_stride", "stats"]
 
@@ -219,6 +237,8 @@ SIGNATURES = {
     "bridges_env_candidate_stability": [vp, vp],
     "bridges_env_restrict_to_stable": [vp, vp],
     "bridges_env_rebuild_contacts": [vp, vp],
+    "bridges_env_fork_scratch": [vp, C.POINTER(i64)],
+    "bridges_env_fork": [vp, vp, vp, i64, vp],
     "bridges_env_set_task_buffers": [vp, C.POINTER(TaskBuffers)],
     "bridges_env_set_task_family": [vp, C.POINTER(TaskFamily)],
     "bridges_env_set_family_thresholds": [vp, vp],
@@ -256,6 +276,7 @@ SIGNATURES = {
     "bridges_mlp_mid_backward": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
     "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_boltzmann_select": [i32, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_beam_select": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups_keyed": [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp],

@@ -508,6 +508,40 @@ def boltzmann_select(seg, q, u, temperature, greedy, idx, cand_offset, rep=None)
     return sel_compact, sel_index, q_sel, explore_w, p_sel
 
 
+def beam_select(seg, q, width, live, ret, disc, idx, cand_offset, rep=None, out=None):
+    """The top-``width`` candidates of every group of ``width`` beams in one launch (bridges_beam_select; the rule stands in
+    include/bridges_hip.h): E = G * width envs, seg / q / idx / cand_offset / rep as for eps_greedy_select, live uint8 [E], ret and
+    disc float64 [E].  A candidate (live env e, row j with q neither NaN nor -inf) scores ret[e] + disc[e] * q[j] in float64;
+    slot i of a group takes its i-th candidate by (score desc, q desc, env asc, row asc).
+    -> dict(src int32 [E] -- what VecAssemblyGym.fork takes --, sel_compact int64 [E], sel_index int32 [E], q_sel float32 [E],
+    score float64 [E], live uint8 [E]); ``out``: such a dict to write into (no allocation)."""
+    L = abi.require_gpu()
+    if isinstance(seg, (tuple, list)):
+        seg_lo, seg_hi = seg
+        E = seg_lo.numel()
+    else:
+        E = seg.numel() - 1
+        seg_lo, seg_hi = seg[:E], seg[1:]
+    n = q.numel()
+    assert seg_lo.dtype == torch.int32 and seg_hi.dtype == torch.int32 and seg_lo.is_contiguous() and seg_hi.is_contiguous()
+    assert seg_hi.numel() == E and idx.dtype == torch.int64 and cand_offset.dtype == torch.int32
+    assert rep is None or (rep.dtype == torch.int32 and rep.numel() == E and rep.is_contiguous())
+    assert live.dtype == torch.uint8 and ret.dtype == torch.float64 and disc.dtype == torch.float64
+    assert live.numel() == E and ret.numel() == E and disc.numel() == E
+    q = q.to(torch.float32).contiguous()
+    idx, cand_offset, live, ret, disc = idx.contiguous(), cand_offset.contiguous(), live.contiguous(), ret.contiguous(), disc.contiguous()
+    assert idx.numel() == n and cand_offset.numel() >= E
+    dev = q.device
+    if out is None:
+        out = dict(src=torch.empty(E, dtype=torch.int32, device=dev), sel_compact=torch.empty(E, dtype=torch.int64, device=dev),
+                   sel_index=torch.empty(E, dtype=torch.int32, device=dev), q_sel=torch.empty(E, dtype=torch.float32, device=dev),
+                   score=torch.empty(E, dtype=torch.float64, device=dev), live=torch.empty(E, dtype=torch.uint8, device=dev))
+    abi.check(L.bridges_beam_select(E, int(width), n, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), _ptr(idx), _ptr(cand_offset), _ptr(rep),
+                                    _ptr(live), _ptr(ret), _ptr(disc), _ptr(out["src"]), _ptr(out["sel_compact"]), _ptr(out["sel_index"]),
+                                    _ptr(out["q_sel"]), _ptr(out["score"]), _ptr(out["live"]), _stream()), "bridges_beam_select")
+    return out
+
+
 def episode_stats_(out, rec, valid, gpow, n_targets, run, counted, count_first_only=False):
     """Folds one lock-step's records rec float64 [E, W] / valid bool [E] into the per-episode sums ``out`` float64 [8] in place
     (bridges_episode_stats): run float32 [E, 2] and counted int32 [E] carry the episodes that span calls, gpow float32 [K] =

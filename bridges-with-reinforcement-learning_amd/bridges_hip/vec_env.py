@@ -740,6 +740,26 @@ class VecAssemblyGym:
             self.restrict_to_stable()
         self._cand_version += 1
 
+    def fork(self, src):
+        """Env e continues from the state of env src[e] (bridges_env_fork; src: int32 [E] on the device, any pattern --
+        permutation, duplicates, broadcast, swap; an entry outside [0, E) keeps env e as it is): every per-env state array,
+        the contact list, the persisted tableaux and, on per-env tasks, the env's task are copied bit for bit through a
+        scratch allocated on first use (bridges_env_fork_scratch bytes); then the candidate sets are rebuilt as refresh()
+        rebuilds them, narrowed to the stable placements under stable_actions_only.  The copied contacts and snapshots are as
+        current as their sources', so nothing has to be rebuilt.  No host wait."""
+        src = torch.as_tensor(src)
+        if src.numel() != self.E:
+            raise ValueError(f"fork: src must hold one source env per env ({self.E}), got {tuple(src.shape)}")
+        src = src.to(device=self.device, dtype=torch.int32).contiguous()
+        n = C.c_int64(0)                                     # (a host-side sum; it grows when task buffers are attached later)
+        abi.check(self.L.bridges_env_fork_scratch(self._env, C.byref(n)), "bridges_env_fork_scratch")
+        if getattr(self, "_fork_scratch", None) is None or self._fork_scratch.numel() < n.value:
+            self._fork_scratch = torch.empty(max(int(n.value), 16), dtype=torch.uint8, device=self.device)
+        abi.check(self.L.bridges_env_fork(self._env, _ptr(src), _ptr(self._fork_scratch), self._fork_scratch.numel(), _stream()),
+                  "bridges_env_fork")
+        self._fork_src = src                                 # alive until the stream has consumed it
+        self.refresh()                                       # bumps _cand_version: the row caches of the old sets are stale
+
     def restrict_to_stable(self):
         """Narrow the candidate set to the stable placements (bridges_env_restrict_to_stable): is_action_stable_rbe of every
         valid candidate (candidate_stability_mask), then cand_mask &= (cand_stable == 1) and n_valid recounted; an env left

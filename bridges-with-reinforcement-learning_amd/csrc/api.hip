@@ -14,6 +14,8 @@
 #include "conv_train_kernels.hip"
 #include "replay_kernels.hip"
 #include "hindsight_kernels.hip"
+#include "fork_kernels.hip"
+#include "beam_kernels.hip"
 
 using namespace bridges;
 
@@ -468,6 +470,101 @@ int bridges_env_rebuild_contacts(bridges_env* env, void* stream) {
     return launch("k_rebuild_contacts", k_rebuild_contacts, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx);
 }
 
+// ---- bridges_env_fork ------------------------------------------------------------------------------------------------
+// THE list of per-env state arrays a fork copies: (pointer, bytes per env).  A buffer added to bridges_env_buffers /
+// bridges_task_buffers later is forked by adding one line here (and to FORK_* in bridges_hip/abi.py, which
+// tests/test_cpu_beam.py holds against this list and against the buffer tables: a per-env buffer that is neither forked nor
+// listed as excluded fails there).  A NULL pointer is an optional buffer that is not there: skipped.
+static int fork_table(const bridges_env* env, ForkTable* T) {
+    const DevCtx& c = env->ctx;
+    const bridges_env_buffers& b = c.b;
+    const bridges_task_buffers& t = env->tasks;              // all-zero (every pointer NULL) without per-env tasks
+    const bridges_task_family& f = env->family;              // likewise without a family
+    const int64_t K = c.K, NT = c.n_targets, NO = t.n_obstacles;
+    struct Row { const void* p; int64_t bytes; };
+#define FORK_ROW(ptr, bytes) {(const void*)(ptr), (int64_t)(bytes)}
+    const Row rows[] = {
+        FORK_ROW(b.n_blocks, 4),
+        FORK_ROW(b.blk_shape, 4 * K),
+        FORK_ROW(b.blk_pose, 8 * K * 4),
+        FORK_ROW(b.blk_verts, 8 * K * MAXV * 2),
+        FORK_ROW(b.blk_occ, K),
+        FORK_ROW(b.targets_left, 4),
+        FORK_ROW(b.state_bits, 8 * IMG),
+        FORK_ROW(b.n_if, 4),
+        FORK_ROW(b.if_body, 4 * MAXIF * 2),
+        FORK_ROW(b.if_geom, 8 * MAXIF * 8),
+        FORK_ROW(b.draw_counter, 8),
+        FORK_ROW(b.needs_reset, 1),
+        FORK_ROW(b.step_flags, 8),
+        FORK_ROW(b.reward, 4),
+        FORK_ROW(b.lin_reward, 4),
+        FORK_ROW(b.n_reached, 4),
+        FORK_ROW(b.n_cand, 4),
+        FORK_ROW(b.lp_ws, 8 * b.lp_ws_stride),
+        FORK_ROW(b.lp_snap, 8 * b.lp_snap_stride),
+        FORK_ROW(t.env_targets, 8 * NT * 3),
+        FORK_ROW(t.target_bits, 8 * IMG),
+        FORK_ROW(t.reward_map, 4 * IMG * IMG),
+        FORK_ROW(t.reward_prefix, 8 * IMG * (IMG + 1)),
+        FORK_ROW(t.task_episode, 4),
+        FORK_ROW(t.env_obstacles, 8 * NO * 3),
+        FORK_ROW(t.env_obstacle_bits, 8 * IMG),
+        FORK_ROW(f.task_class, 4),
+    };
+#undef FORK_ROW
+    static_assert(sizeof(rows) / sizeof(rows[0]) <= FORK_MAX_ARRAYS, "fork table too long");
+    memset(T, 0, sizeof(*T));
+    T->E = c.E;
+    int64_t off = 0, blocks = 0;
+    for (const Row& r : rows) {
+        if (!r.p || r.bytes <= 0) continue;
+        ForkArray& a = T->a[T->n++];
+        a.base = (char*)r.p;
+        a.row_bytes = r.bytes;
+        a.scratch_off = off;
+        int unit = 16;
+        while (unit > 1 && ((((uintptr_t)r.p) | (uintptr_t)r.bytes) & (uintptr_t)(unit - 1))) unit >>= 1;
+        a.unit = unit;
+        if (r.bytes >= FORK_PIECE / 4) {                     // a long row: pieces of one env's row
+            a.rows_per_block = 1;
+            a.pieces_per_row = (int32_t)ceil_div(r.bytes, FORK_PIECE);
+        } else {                                             // short rows: several envs per workgroup
+            a.rows_per_block = (int32_t)(FORK_PIECE / 4 / r.bytes);
+            a.pieces_per_row = 1;
+        }
+        a.block0 = (int32_t)blocks;
+        blocks += a.rows_per_block == 1 ? (int64_t)c.E * a.pieces_per_row : ceil_div(c.E, a.rows_per_block);
+        off += ceil_div((int64_t)c.E * r.bytes, 16) * 16;
+        if (blocks > (int64_t)0x7fffffff) return fail_arg("bridges_env_fork: too many workgroups");
+    }
+    T->scratch_bytes = off;
+    T->n_blocks = (int32_t)blocks;
+    return BRIDGES_OK;
+}
+
+int bridges_env_fork_scratch(const bridges_env* env, int64_t* bytes) {
+    if (!env || !bytes) return fail_arg("bridges_env_fork_scratch: null");
+    ForkTable T;
+    if (int rc = fork_table(env, &T)) return rc;
+    *bytes = T.scratch_bytes;
+    return BRIDGES_OK;
+}
+
+int bridges_env_fork(bridges_env* env, const int32_t* src, void* scratch, int64_t scratch_bytes, void* stream) {
+    if (!env || !src || !scratch) return fail_arg("bridges_env_fork: null env, src or scratch");
+    if (!aligned(4, src) || !aligned(16, (const char*)scratch)) return fail_arg("bridges_env_fork: src must be 4-byte, scratch 16-byte aligned");
+    ForkTable T;
+    if (int rc = fork_table(env, &T)) return rc;
+    if (scratch_bytes < T.scratch_bytes) return fail_arg("bridges_env_fork: scratch_bytes below bridges_env_fork_scratch's answer");
+    if (T.n_blocks == 0) return BRIDGES_OK;
+    if (int rc = launch("k_fork_rows (gather)", k_fork_rows<true>, dim3((unsigned)T.n_blocks), dim3(FORK_THREADS), 0, stream, T, src,
+                        (char*)scratch))
+        return rc;
+    return launch("k_fork_rows (write back)", k_fork_rows<false>, dim3((unsigned)T.n_blocks), dim3(FORK_THREADS), 0, stream, T, src,
+                  (char*)scratch);
+}
+
 int bridges_env_select_random(bridges_env* env, void* stream) {
     if (!env) return fail_arg("null env");
     return launch("k_select", k_select, dim3(env->ctx.E), dim3(WAVE), 0, stream, env->ctx, 1);
@@ -871,6 +968,26 @@ int bridges_boltzmann_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, c
     // one wave per env, four envs per workgroup
     return launch("k_boltzmann_select", k_boltzmann_select, dim3((unsigned)ceil_div(E, 4)), dim3(256), 0, stream, E, n_rows, seg_lo,
                   seg_hi, q, u, temperature, (int)greedy, idx, cand_offset, rep, sel_compact, sel_index, q_sel, explore_w, p_sel);
+}
+
+int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q,
+                        const int64_t* idx, const int32_t* cand_offset, const int32_t* rep, const uint8_t* live, const double* ret,
+                        const double* disc, int32_t* src, int64_t* sel_compact, int32_t* sel_index, float* q_sel, double* score,
+                        uint8_t* live_out, void* stream) {
+    if (E < 0) return fail_arg("bridges_beam_select: negative count");
+    if (B < 1 || B > BEAM_MAX_WIDTH) return fail_arg("bridges_beam_select: the width must be 1..16");
+    if (E % B != 0) return fail_arg("bridges_beam_select: E must be a multiple of the width");
+    if (E == 0) return BRIDGES_OK;
+    if (n_rows < 1) return fail_arg("bridges_beam_select: n_rows must be >= 1");
+    if (!seg_lo || !seg_hi || !q || !idx || !cand_offset || !live || !ret || !disc || !src || !sel_compact || !sel_index || !q_sel ||
+        !score || !live_out)
+        return fail_arg("bridges_beam_select: null pointer");
+    if (!aligned(4, seg_lo, seg_hi, cand_offset, rep, src, sel_index) || !aligned(4, q, q_sel) || !aligned(8, idx, sel_compact) ||
+        !aligned(8, ret, disc, score))
+        return fail_arg("bridges_beam_select: misaligned pointer");
+    // one workgroup per group of B beams
+    return launch("k_beam_select", k_beam_select, dim3((unsigned)(E / B)), dim3(BEAM_THREADS), 0, stream, E, B, n_rows, seg_lo, seg_hi, q,
+                  idx, cand_offset, rep, live, ret, disc, src, sel_compact, sel_index, q_sel, score, live_out);
 }
 
 int bridges_record_state(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,

@@ -587,6 +587,7 @@ def build_parser():
     add_priority_arguments(p)
     add_exploration_arguments(p)
     add_hindsight_arguments(p)
+    add_eval_beam_argument(p)
     return p
 
 
@@ -728,6 +729,28 @@ def check_double_q(args):
     if args.get('double_q') and args['num_envs'] <= 1:
         raise SystemExit("--double_q needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
                          "reference's target, where the target net both chooses and values the next action")
+
+
+def add_eval_beam_argument(p):
+    """--eval_beam: shared with the tools that evaluate through the vectorised loop."""
+    p.add_argument("--eval_beam", type=int, default=argparse.SUPPRESS, metavar="B",
+                   help="Vectorised loop with --eval_envs M: every evaluation also runs a beam search of width B (1..16) on the same "
+                        "M tasks, with the policy net's q as the heuristic (VecDQN.beam_search: B envs per task, forked on the "
+                        "device), and logs beam_success_rate / beam_reward / beam_lin_reward / beam_width beside the greedy keys.")
+
+
+def check_eval_beam(args):
+    """--eval_beam B: refused in words (SystemExit) where the loop cannot run it, before anything touches the GPU."""
+    B = args.get('eval_beam')
+    if B is None:
+        return
+    from bridges_hip import abi
+    if not 1 <= B <= abi.BEAM_MAX_WIDTH:
+        raise SystemExit(f"--eval_beam must be 1..{abi.BEAM_MAX_WIDTH} (the widest beam bridges_beam_select orders)")
+    if args.get('num_envs', 1) <= 1:
+        raise SystemExit("--eval_beam needs the vectorised loop (--num_envs N, N > 1): the search forks lock-step envs on the device")
+    if args.get('eval_envs', EVAL_DEFAULTS['eval_envs']) <= 0:
+        raise SystemExit("--eval_beam searches the tasks of the evaluation env: it needs --eval_envs M, M > 0")
 
 
 def add_hindsight_arguments(p):
@@ -948,6 +971,7 @@ def main(argv=None):
     check_priority(args)
     check_exploration(args)
     check_hindsight(args)
+    check_eval_beam(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

@@ -681,6 +681,109 @@ class VecDQN:
             out["episodes_by_class"] = [c["episodes"] for c in vals["by_class"]]
         return out
 
+    # ------------------------------------------------------------------ beam-search evaluation
+    @torch.no_grad()
+    def beam_search(self, beam_env, width):
+        """Beam search of width B = ``width`` over every task of ``beam_env`` (beam_env_like(eval_env, B): M * B envs, the B envs
+        of a group share one task), the policy net's q as the heuristic: how much the learned Q is worth when the simulator is
+        allowed to look ahead.  Per depth, for all groups at once and without a host decision: the candidate rows and their q
+        through the paths acting uses (_rows, _policy_q); bridges_beam_select keeps the B candidates of every group with the
+        best  return so far + discount * q  ("Beam search"); beam_env.fork(src) makes slot i continue from
+        the env that owns its candidate; beam_env.step places it; the returns are advanced in float64 on the device
+        (ret += disc * lin_reward, disc *= gamma).  A live beam whose step ends its episode (done, or no next action) is held
+        against its group's best finished beam -- success (reward == n_targets, evaluate()'s statistic) first, then the higher
+        return, then the earlier depth, then the lower slot -- and dies; a dead slot spends its lock-steps resetting.  Runs
+        beam_env.K depths and reads the results back once; per depth the host waits only where acting waits (the row count of
+        valid_rows).  Touches no training state.  width = 1 is the greedy episode of evaluate().
+        -> evaluate()'s keys as means over the M tasks (success_rate, reward, lin_reward, num_steps, episodes; reward and
+        lin_reward are the best beam's discounted sums, in float64), beam_width, and structures: per task a dict of the best
+        beam's placed blocks (shape ids, poses (x, z, cos, sin)), its actions (the candidate index placed at every depth),
+        success, reward, lin_reward, num_steps and final_reward.  On a beam env of a task family also success_by_class and
+        episodes_by_class, indexed by the class n = 0..hi of every task."""
+        B, env = int(width), beam_env
+        if env is self.env:
+            raise ValueError("beam_search() needs an env of its own: the training env's episodes would be cut short")
+        if not 1 <= B <= abi.BEAM_MAX_WIDTH:
+            raise ValueError(f"beam_search(width={width!r}): 1..{abi.BEAM_MAX_WIDTH}")
+        if not isinstance(env, VecAssemblyGym) or env.E % B != 0:
+            raise ValueError(f"beam_search(width={B}) needs a VecAssemblyGym of M * {B} envs (beam_env_like(eval_env, {B}))")
+        if env.random_targets is not None or env.random_obstacles is not None or env.task_family is not None:
+            raise ValueError("beam_search(): the beam env draws tasks per episode, so the envs of a group would not share one; build "
+                             "it with beam_env_like(eval_env, width)")
+        if bool(env.stable_actions_only) != self.stable_actions_only:
+            raise ValueError("the beam env's stable_actions_only must match the training env's")
+        if bool(env.per_env_tasks) != self.per_env_tasks or bool(env.per_env_obstacles) != self.per_env_obstacles:
+            raise ValueError("the beam env must have per-env tasks / obstacles exactly when the agent was built with them")
+        E, K, dev = env.E, env.K, self.device
+        M = E // B
+        slots = torch.arange(E, device=dev) % B
+        first = torch.arange(M, device=dev) * B
+        live = (slots == 0).to(torch.uint8)                  # only slot 0 of every group is open
+        ret = torch.zeros(E, dtype=torch.float64, device=dev)       # discounted lin_reward so far: what the search scores
+        ret_r = torch.zeros(E, dtype=torch.float64, device=dev)     # discounted reward so far: what evaluate() reports
+        disc = torch.ones(E, dtype=torch.float64, device=dev)
+        hist = torch.zeros((E, K, 6), dtype=torch.float64, device=dev)    # per depth: shape id, pose[4], candidate index
+        # per group: has, success, lin return, reward return, steps, final reward, then the beam's history
+        best = torch.zeros((M, 6 + 6 * K), dtype=torch.float64, device=dev)
+        one, ninf = torch.ones(M, dtype=torch.float64, device=dev), torch.full((), -float("inf"), dtype=torch.float64, device=dev)
+        env.reset()
+        for d in range(K):
+            stable = self._stable_flags(env)
+            idx, row_env, seg, rep = self._rows(env, stable)
+            if not idx.numel():                              # no env holds a valid candidate: every beam is closed
+                break
+            q = self._policy_q(env, idx, row_env, stable)
+            sel = ops.beam_select(seg, q, B, live, ret, disc, idx, env.cand_offset[:E], rep=rep)
+            src, sc = sel["src"].long(), sel["sel_compact"]
+            placed = torch.cat([env.cand_desc[sc, 2:3].double(), env.cand_pose[sc], sel["sel_index"].double().unsqueeze(1)], dim=1)
+            ret, ret_r, disc, hist = ret[src], ret_r[src], disc[src], hist[src]
+            hist[:, d] = placed
+            live = sel["live"].bool()
+            env.fork(sel["src"])
+            env.needs_reset.masked_fill_(~live, 1)           # a closed slot places nothing: its lock-step is a reset
+            env.step(sel["sel_index"])
+            f = env.step_flags
+            live &= f[:, 0].bool()
+            lin, rew = env.lin_reward.double(), env.reward.double()
+            ret = torch.where(live, ret + disc * lin, ret)   # two roundings each, as the score of bridges_beam_select
+            ret_r = torch.where(live, ret_r + disc * rew, ret_r)
+            disc = disc * self.gamma
+            fin = live & (f[:, 5].bool() | f[:, 6].bool())   # done | no next action: the episode's last record (REC_DONE)
+            succ = fin & (env.reward == float(env.n_targets))
+            fin_g, succ_g, ret_g = fin.view(M, B), succ.view(M, B), ret.view(M, B)
+            elig = fin_g & (succ_g | ~succ_g.any(dim=1, keepdim=True))
+            top = torch.where(elig, ret_g, ninf).max(dim=1, keepdim=True).values
+            pick_slot = torch.where(elig & (ret_g == top), slots.view(M, B), B).min(dim=1).values      # B: nothing finished
+            has_new = pick_slot < B
+            pick = first + pick_slot.clamp(max=B - 1)
+            new = torch.cat([torch.stack([one, succ[pick].double(), ret[pick], ret_r[pick], one * (d + 1), rew[pick]], dim=1),
+                             hist[pick].reshape(M, -1)], dim=1)
+            better = has_new & ((best[:, 0] == 0) | (new[:, 1] > best[:, 1]) | ((new[:, 1] == best[:, 1]) & (new[:, 2] > best[:, 2])))
+            best = torch.where(better.unsqueeze(1), new, best)
+            live = (live & ~fin).to(torch.uint8)
+        host = best.cpu()                                    # the one wait of the search
+        if int(host[:, 0].sum()) != M:
+            raise RuntimeError(f"beam search: {int(host[:, 0].sum())} of {M} tasks ended an episode within {K} depths "
+                               "(a task whose fresh state has no valid candidate never starts one)")
+        succ_h, steps_h = host[:, 1].tolist(), [int(v) for v in host[:, 4].tolist()]
+        hist_h = host[:, 6:].reshape(M, K, 6)
+        structures = []
+        for m in range(M):
+            n = steps_h[m]
+            structures.append(dict(shape=[int(v) for v in hist_h[m, :n, 0].tolist()], pose=hist_h[m, :n, 1:5].tolist(),
+                                   actions=[int(v) for v in hist_h[m, :n, 5].tolist()], success=bool(succ_h[m]),
+                                   lin_reward=float(host[m, 2]), reward=float(host[m, 3]), num_steps=n, final_reward=float(host[m, 5])))
+        out = dict(reward=float(host[:, 3].mean()), lin_reward=float(host[:, 2].mean()), avg_loss=None,
+                   num_steps=float(host[:, 4].mean()), success_rate=float(host[:, 1].mean()), episodes=M, beam_width=B,
+                   structures=structures)
+        classes = getattr(env, "beam_task_class", None)
+        if classes is not None:                              # the tasks of a family: per span / height n = 0..hi
+            n_classes = env.beam_n_classes
+            per = [[s for s, c in zip(succ_h, classes) if c == n] for n in range(n_classes)]
+            out["success_by_class"] = [sum(p) / len(p) if p else None for p in per]
+            out["episodes_by_class"] = [len(p) for p in per]
+        return out
+
     # ------------------------------------------------------------------ gradient steps on sampled batches
     def _make_replay_env(self, n_states):
         """A scratch env of n_states envs of the rollout env's task; on per-env tasks with per-env targets of its own (zeros
@@ -1192,6 +1295,44 @@ def curriculum_from_args(args):
                       min_episodes=args.get('curriculum_min_episodes', defaults.min_episodes))
 
 
+class _ShapeOf:
+    """A shape as VecAssemblyGym's constructor takes it: the geometry and the faces blocks may be placed on."""
+
+    def __init__(self, geometry, target_faces_2d):
+        self.geometry, self.target_faces_2d = geometry, list(target_faces_2d)
+
+
+def beam_env_like(eval_env, width):
+    """The env VecDQN.beam_search runs on: M * width envs, M = eval_env.E, in which envs m * width .. (m + 1) * width - 1 hold the
+    task evaluate() plays in env m of ``eval_env`` -- same shapes, limits, options and seed.  A fixed task is passed through.
+    Per-env tasks: eval_env is reset, the targets (and obstacles) of its episode 0 are taken once and repeated ``width`` times as
+    explicit [E, T, 3] / [E, O, 3] arrays, which no episode redraws: a finished beam's auto-reset changes no task.  A task family
+    goes in the same way, as the coordinates of every env's drawn class (parked obstacle slots included); the classes are kept
+    on the env (beam_task_class, a host list) for the statistics by class."""
+    B = int(width)
+    if not 1 <= B <= abi.BEAM_MAX_WIDTH:
+        raise ValueError(f"beam_env_like(width={width!r}): 1..{abi.BEAM_MAX_WIDTH}")
+    if not isinstance(eval_env, VecAssemblyGym):
+        raise ValueError(f"beam_env_like() takes a VecAssemblyGym; a {type(eval_env).__name__} (env groups on streams of their own) "
+                         "cannot be forked across its groups")
+    ev = eval_env
+    if ev.per_env_tasks:
+        ev.reset()                                           # task_episode 0: the tasks every evaluate() plays
+        targets = ev.env_targets.repeat_interleave(B, dim=0)
+        obstacles = ev.env_obstacles.repeat_interleave(B, dim=0) if ev.per_env_obstacles else list(ev.obstacles)
+    else:
+        targets, obstacles = list(ev.targets), list(ev.obstacles)
+    shapes = [_ShapeOf(g, faces) for g, faces in zip(ev.shapes, ev.shape_target_faces)]
+    env = VecAssemblyGym(ev.E * B, shapes, obstacles, targets, max_steps=ev.max_steps or None, mu=ev.mu, density=ev.density,
+                         bounds=ev.bounds, xlim=ev.xlim, ylim=ev.ylim, x_discr_ground=ev.x_discr_ground, offset_values=ev.offset_values,
+                         seed=ev.seed, device=ev.device, f32_rasters=ev.f32_rasters, a_max=ev.a_max, img_size=(ev.img, ev.img),
+                         sparse_raster_update=ev.sparse_raster_update, candidate_snapshots=ev.candidate_snapshots,
+                         stable_actions_only=ev.stable_actions_only)
+    if ev.task_family is not None:
+        env.beam_task_class, env.beam_n_classes = ev.task_class.tolist(), ev.task_family.n_classes
+    return env
+
+
 def next_multiple(n, every):
     """The first multiple of ``every`` above ``n`` finished episodes: the next checkpoint / evaluation threshold of the vectorised
     loop, from 0 at the start and from the restored episode count on resume."""
@@ -1262,6 +1403,9 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         eval_env = VecAssemblyGym(eval_envs, geoms, eval_obstacles, eval_targets, max_steps=args['max_steps'], seed=seed * 1000003 + 999983,
                                   device=device, f32_rasters=VecDQN.acting_needs_f32_rasters(policy_net) and not task_channels,
                                   img_size=args.get('image_size') or (64, 64), stable_actions_only=args.get('stable_actions_only', False))
+    # --eval_beam B: every evaluation also searches the same tasks with a beam of width B (B envs per task, forked on the device)
+    eval_beam = args.get('eval_beam')
+    beam_env = beam_env_like(eval_env, eval_beam) if eval_beam and eval_env is not None else None
     history, t0, it = [], time.time(), 0
     next_ckpt = next_multiple(0, args['checkpoint_every'])
     next_eval = next_multiple(0, args['evaluate_every'])
@@ -1340,6 +1484,10 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         if eval_envs > 0 and agent.episodes_done >= next_eval:
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)
+                if beam_env is not None:                     # the same tasks under the beam search, beside the greedy keys
+                    bs = agent.beam_search(beam_env, eval_beam)
+                    ev.update(beam_success_rate=bs['success_rate'], beam_reward=bs['reward'], beam_lin_reward=bs['lin_reward'],
+                              beam_width=eval_beam)
                 if aim_run is not None or wandb_run is not None:
                     if family:                               # the sinks take scalars: success_rate_n{k} for the lists by class
                         by_class = ev['success_by_class']

@@ -217,6 +217,27 @@ int bridges_env_restrict_to_stable(bridges_env* env, void* stream);
  * states the host wrote (bridges_replay_unpack / load_states).  Invalidates the env's persisted tableaux (lp_ws, lp_snap):
  * bridges_env_candidate_stability then solves the candidates of these states from scratch.  No host wait. */
 int bridges_env_rebuild_contacts(bridges_env* env, void* stream);
+/* Fork: env e continues from the state of env src[e] (src int32 [E], device) -- the primitive of beam search, best-of-N with
+ * resampling, MCTS and restart distributions.
+ * THE RULE: after the call, every per-env row of every STATE array of env e holds the bits that row of env src[e] held before
+ * the call, for any src: permutations, duplicates, broadcasts, swaps, chains.  An entry src[e] outside [0, E) means e: the env
+ * keeps its own state, and nothing outside the buffers is read.
+ * State arrays (the list is the table fork_table() of csrc/api.hip): n_blocks, blk_shape, blk_pose, blk_verts, blk_occ,
+ * targets_left, state_bits; n_if, if_body, if_geom; draw_counter, needs_reset; step_flags, reward, lin_reward, n_reached; n_cand;
+ * the env's lp_ws row and, when given, its lp_snap row (whole rows: a clone's warm header must never match a tableau of another
+ * geometry); with task buffers attached the env's task as well -- env_targets, target_bits, reward_map, reward_prefix,
+ * task_episode, env_obstacles / env_obstacle_bits where present, task_class with a family set.  A fork is the whole env.
+ * NOT copied: sel_index (an input), the candidate arrays (n_valid, cand_offset, cand_*, state_raster and the *_nz masks, which
+ * describe buffer slots) -- the caller refreshes them (bridges_env_refresh, then bridges_env_restrict_to_stable where it
+ * narrows the sets) --, stats, and everything all envs share.  The copied contact lists and tableaux are as current as the
+ * sources' were.
+ * Two launches through the caller's scratch (bridges_env_fork_scratch bytes, 16-byte aligned; about 0.37 MB per env with
+ * lp_snap, 0.25 MB without): gather the rows of src into the scratch, then write them back.  No kernel both reads and writes a
+ * state array, no atomics, no host wait, the same bits on every call.
+ * Refused (BRIDGES_E_ARG, nothing launched): a NULL env, src or scratch, src not 4-byte or scratch not 16-byte aligned,
+ * scratch_bytes below the sizing call's answer. */
+int bridges_env_fork_scratch(const bridges_env* env, int64_t* bytes);
+int bridges_env_fork(bridges_env* env, const int32_t* src /* [E] device */, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* --- per-env tasks ------------------------------------------------------------
  * tower_setup draws three fresh targets each time an episode starts (assembly_gym/assembly_gym/envs/gym_env.py:64-79,
@@ -529,6 +550,26 @@ int bridges_eps_greedy_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, 
 int bridges_boltzmann_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, const float* u,
                              float temperature, int32_t greedy, const int64_t* idx, const int32_t* cand_offset, const int32_t* rep,
                              int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w, float* p_sel, void* stream);
+
+/* Beam search: the top-B candidates of every group of B beams.  E = G * B envs, group g owns envs gB .. gB + B - 1; rows
+ * seg_lo[e] .. seg_hi[e] of q / idx belong to env e exactly as for bridges_eps_greedy_select (rep may be NULL).  Inputs per env:
+ * live[e] u8 (the beam is still open), ret[e] f64 (its discounted return so far), disc[e] f64 (the discount of its next reward).
+ *   - SCORE of row j of a live env e: S = ret[e] + disc[e] * (double)q[j] -- two binary64 operations, no contraction;
+ *   - a row whose q is NaN or -inf is not a candidate (nor is one whose S is NaN); a dead env has no candidates;
+ *   - ORDER: S descending, then q descending, then env ascending, then row ascending (with one live beam and B = 1: the first
+ *     maximum of q, the choice of bridges_eps_greedy_select(greedy = 1));
+ *   - slot i < B of group g takes the i-th candidate of the group in that order: src[gB + i] = its env, sel_compact = idx[row],
+ *     sel_index = max(sel_compact - cand_offset[rep ? rep[env] : env], 0), q_sel = q[row], score = S, live_out = 1;
+ *   - a slot beyond the group's number of candidates: src = the slot's own env, sel_compact 0, sel_index 0, q_sel 0, score -inf,
+ *     live_out 0.
+ * src is what bridges_env_fork takes, sel_index what the step after it places.  One workgroup per group, B rounds of an arg-max
+ * in a strict total order: no atomics, the same bits on every call.  Rows outside [0, n_rows) are not read.
+ * 1 <= B <= 16.  Refused: B outside that, E % B != 0, n_rows < 1, a NULL array other than rep, a misaligned pointer.  E == 0
+ * returns 0 and launches nothing. */
+int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q,
+                        const int64_t* idx, const int32_t* cand_offset, const int32_t* rep, const uint8_t* live, const double* ret,
+                        const double* disc, int32_t* src, int64_t* sel_compact, int32_t* sel_index, float* q_sel, double* score,
+                        uint8_t* live_out, void* stream);
 
 /* --- transition records of the vectorised loop ------------------------------------------------------------------
  * One float64 row per transition: the compact form of the reference's Transition (successor_dqn.py:27-44) -- the block

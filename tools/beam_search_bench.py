@@ -1,0 +1,206 @@
+"""What beam-search evaluation costs, part by part, on identical inputs in one process:
+  fork      bridges_env_fork alone (the two copy launches, no candidate refresh) against the torch formulation
+            t.copy_(t.index_select(0, src)) over the same state arrays, at --fork_envs envs of a tower env advanced a few random
+            lock-steps; bytes moved = 4 x the scratch (read the source rows, write the scratch, read it, write the rows)
+  select    ops.beam_select (bridges_beam_select: one launch) against a torch top-k formulation (scores in float64, scattered into a
+            padded [G, rows] matrix, torch.topk, gathers) at --groups groups of --width beams
+  search    one VecDQN.beam_search(width) call for every --widths next to one VecDQN.evaluate() call on --tasks held-out tasks
+            (wall clock around the whole call, its host waits included)
+HIP events around single calls (fork, select), the legs alternating, warm-up first; one JSON line per shape with medians and spread.
+--syncs lists the host waits of one evaluate() and one beam_search() call instead (tools/find_syncs.py's counting, plus explicit
+stream / event / device synchronisations): per depth the search must wait only where acting waits.
+    python tools/beam_search_bench.py [--fork_envs 512 4096] [--groups 64 512] [--width 8] [--tasks 64] [--widths 1 4 8] [--syncs]"""
+import argparse, ctypes as C, json, os, sys, time, warnings
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
+import numpy as np
+import torch
+from bridges_hip import abi, ops
+from bridges_hip.shapes import load_urdf
+from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
+from robotoddler.training.successor_dqn import build_parser, make_nets
+from robotoddler.training.vec_dqn import VecDQN, beam_env_like
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--fork_envs", type=int, nargs="*", default=[512, 4096])
+ap.add_argument("--groups", type=int, nargs="*", default=[64, 512])
+ap.add_argument("--width", type=int, default=8, help="beams per group of the select legs")
+ap.add_argument("--rows_per_env", type=int, default=40)
+ap.add_argument("--tasks", type=int, default=64, help="held-out tasks of the search legs (0: skip them)")
+ap.add_argument("--widths", type=int, nargs="*", default=[1, 4, 8])
+ap.add_argument("--max_steps", type=int, default=10)
+ap.add_argument("--reps", type=int, default=40)
+ap.add_argument("--search_reps", type=int, default=7)
+ap.add_argument("--warmup", type=int, default=10)
+ap.add_argument("--syncs", action="store_true")
+a = ap.parse_args()
+assert a.reps >= 20 and a.search_reps >= 5
+dev = torch.device("cuda:0")
+HBM_PEAK = 8.0e12                                             # bytes / s, the card's specification
+
+
+def summarise(times):
+    out = {}
+    for name, t in times.items():
+        t = np.array(t)
+        q1, med, q3 = np.percentile(t, [25, 50, 75])
+        out[name] = dict(median_us=float(med), min_us=float(t.min()), max_us=float(t.max()), iqr_us=float(q3 - q1), calls=len(t))
+    return out
+
+
+def alternate(legs, reps, warmup, wall=False):
+    for _ in range(warmup):
+        for _name, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in legs}
+    for _ in range(reps):
+        for name, fn in legs:
+            if wall:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e6)
+            else:
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                out = fn()
+                stop.record()
+                stop.synchronize()
+                times[name].append(start.elapsed_time(stop) * 1e3)
+            del out
+    return summarise(times)
+
+
+def tower_env(E, **kw):
+    H = 0.8
+    return VecAssemblyGym(E, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(2)], [(0.5, 0, 2 * H + H / 2)],
+                          max_steps=a.max_steps, seed=1, device=dev, f32_rasters=False, **kw)
+
+
+def waits(fn):
+    seen = []
+    saved = (torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize, torch.cuda.synchronize)
+
+    def counting(name, inner):
+        def f(*args, **kw):
+            seen.append(name)
+            return inner(*args, **kw)
+        return f
+    torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize = counting("stream", saved[0]), counting("event", saved[1])
+    torch.cuda.synchronize = counting("device", saved[2])
+    try:
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            torch.cuda.set_sync_debug_mode("warn")
+            try:
+                fn()
+            finally:
+                torch.cuda.set_sync_debug_mode("default")
+        seen += ["op"] * sum("synchroniz" in str(x.message) for x in w)
+    finally:
+        torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize, torch.cuda.synchronize = saved
+    return seen
+
+
+# ---- fork ---------------------------------------------------------------------------------------------------------------------
+for E in ([] if a.syncs else a.fork_envs):
+    env = tower_env(E)
+    for _ in range(4):
+        env.select_random()
+        env.step()
+    arrays = [t for t in ([env.buf[n] for n in abi.FORK_ENV_FIELDS if n != "lp_snap"] + [env.lp_snap]) if t is not None]
+    n = C.c_int64(0)
+    abi.check(env.L.bridges_env_fork_scratch(env._env, C.byref(n)), "bridges_env_fork_scratch")
+    scratch = torch.empty(n.value, dtype=torch.uint8, device=dev)
+    src = torch.randint(0, E, (E,), generator=torch.Generator().manual_seed(E), dtype=torch.int32).to(dev)
+    src_l = src.long()
+
+    def fork_op():
+        abi.check(env.L.bridges_env_fork(env._env, src.data_ptr(), scratch.data_ptr(), n.value, abi.current_stream()), "bridges_env_fork")
+
+    def formulation():
+        for t in arrays:
+            t.copy_(t.index_select(0, src_l))
+    s = alternate((("fork", fork_op), ("torch", formulation)), a.reps, a.warmup)
+    moved = 4 * n.value
+    bw = moved / (s["fork"]["median_us"] * 1e-6)
+    print(json.dumps(dict(part="fork", envs=E, scratch_bytes=n.value, scratch_bytes_per_env=n.value / E, bytes_moved=moved,
+                          bandwidth_TB_s=bw / 1e12, share_of_hbm_peak=bw / HBM_PEAK, **s,
+                          torch_over_fork=s["torch"]["median_us"] / s["fork"]["median_us"],
+                          note="the two copy launches alone (no candidate refresh); HIP events around single calls, legs alternating")),
+          flush=True)
+    del env, arrays, scratch
+
+# ---- select -------------------------------------------------------------------------------------------------------------------
+for G in ([] if a.syncs else a.groups):
+    B = a.width
+    E = G * B
+    g = torch.Generator().manual_seed(G)
+    lengths = torch.randint(1, 2 * a.rows_per_env + 1, (E,), generator=g)
+    seg = torch.cat([torch.zeros(1, dtype=torch.int64), lengths.cumsum(0)]).to(torch.int32).to(dev)
+    nrows = int(seg[-1])
+    row_env = torch.repeat_interleave(torch.arange(E), lengths).to(dev)
+    q = torch.randn(nrows, generator=g).to(dev)
+    idx = torch.arange(nrows, device=dev)
+    cand_offset = seg[:-1].contiguous()
+    live = (torch.rand(E, generator=g) < 0.9).to(torch.uint8).to(dev)
+    ret, disc = torch.randn(E, generator=g, dtype=torch.float64).to(dev), (0.95 ** torch.randint(0, 8, (E,), generator=g).double()).to(dev)
+    # the torch formulation's static part: every row's group and its position among the group's rows
+    row_group = row_env // B
+    group_start = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    group_start[1:] = torch.bincount(row_group, minlength=G).cumsum(0)
+    pos = idx - group_start[row_group]
+    width = int((group_start[1:] - group_start[:-1]).max())
+    own = torch.arange(E, device=dev, dtype=torch.int32)
+
+    def select():
+        return ops.beam_select(seg, q, B, live, ret, disc, idx, cand_offset)
+
+    def formulation():
+        S = ret[row_env] + disc[row_env] * q.double()
+        S = torch.where(live[row_env].bool() & ~torch.isnan(q) & (q != -torch.inf), S, -torch.inf)
+        pad = torch.full((G, width), -torch.inf, dtype=torch.float64, device=dev)
+        pad[row_group, pos] = S
+        top, col = torch.topk(pad, B, dim=1)
+        row = (group_start[:-1, None] + col).clamp(max=nrows - 1).reshape(-1)
+        ok = (top > -torch.inf).reshape(-1)
+        e = row_env[row]
+        return (torch.where(ok, e.to(torch.int32), own), torch.where(ok, idx[row], 0),
+                torch.where(ok, (idx[row] - cand_offset[e]).to(torch.int32), 0), torch.where(ok, q[row], 0.0), top.reshape(-1), ok)
+    k, f = select(), formulation()
+    same = (k["sel_compact"] == f[1]).float().mean().item()   # topk breaks exact ties its own way: random q has none to speak of
+    assert same > 0.999, same
+    s = alternate((("select", select), ("torch", formulation)), a.reps, a.warmup)
+    print(json.dumps(dict(part="select", groups=G, width=B, rows=nrows, same_rows_as_torch=same, **s,
+                          torch_over_select=s["torch"]["median_us"] / s["select"]["median_us"],
+                          note="HIP events around single calls (host launch gaps included), legs alternating")), flush=True)
+
+# ---- search -------------------------------------------------------------------------------------------------------------------
+if a.tasks > 0:
+    args = vars(build_parser().parse_args(["--model", "SuccessorMLP"]))
+    torch.manual_seed(0)
+    pol, tgt = make_nets(args, dev)
+    mk = lambda E, seed: VecAssemblyGym(E, [load_urdf("shapes/trapezoid.urdf")], [], RandomTargets(3), max_steps=a.max_steps, seed=seed,
+                                        device=dev, f32_rasters=False)
+    agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), mk(256, 0), 20000, 32, 0.95, 0.01,
+                   "mse_q_values+mse_block_features", per_env_tasks=True)
+    eval_env = mk(a.tasks, 1)
+    beams = {B: beam_env_like(eval_env, B) for B in a.widths}
+    legs = [("evaluate", lambda: agent.evaluate(eval_env))] + [(f"beam_{B}", (lambda B=B: agent.beam_search(beams[B], B))) for B in a.widths]
+    if a.syncs:
+        for name, fn in legs:
+            fn()
+        for name, fn in legs:
+            w = waits(fn)
+            print(json.dumps(dict(part="syncs", call=name, depths=eval_env.K, waits=len(w), kinds={k: w.count(k) for k in sorted(set(w))})),
+                  flush=True)
+    else:
+        s = alternate(legs, a.search_reps, 2, wall=True)
+        res = {name: fn() for name, fn in legs}
+        print(json.dumps(dict(part="search", tasks=a.tasks, max_steps=a.max_steps, **s,
+                              over_evaluate={name: s[name]["median_us"] / s["evaluate"]["median_us"] for name, _ in legs[1:]},
+                              success_rate={name: r["success_rate"] for name, r in res.items()},
+                              lin_reward={name: r["lin_reward"] for name, r in res.items()},
+                              note="wall clock around whole calls on an UNTRAINED net (cost only), legs alternating")), flush=True)

@@ -7,7 +7,9 @@ at the end of the block (VecDQN.evaluate: one episode in each of N envs, --eval_
 With --eval_envs the line also holds eval_q_first, the mean over the evaluation envs of the policy net's q of the row chosen in
 the FIRST step of the episode: the net's own forecast of eval_lin_reward, the discounted lin_reward the same episodes then
 realise -- their difference is the over-estimation that --double_q is meant to reduce.
-    python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values] [--eval_envs 64]"""
+With --eval_beam B beside --eval_envs the line also holds beam_success_rate / beam_reward / beam_lin_reward: the same tasks under a
+beam search of width B with the policy net's q as the heuristic (VecDQN.beam_search).
+    python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values] [--eval_envs 64 [--eval_beam 8]]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -16,8 +18,8 @@ import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
-                                                add_hindsight_arguments, hindsight_from_args)
-from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
+                                                add_hindsight_arguments, hindsight_from_args, add_eval_beam_argument)
+from robotoddler.training.vec_dqn import VecDQN, beam_env_like, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
@@ -53,7 +55,11 @@ add_double_q_argument(ap)                # --double_q: double Q-learning targets
 add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
+add_eval_beam_argument(ap)               # --eval_beam B: beam search of width B on the evaluation tasks (VecDQN.beam_search)
 a = ap.parse_args()
+eval_beam = vars(a).get("eval_beam")
+if eval_beam is not None and not (1 <= eval_beam <= 16 and a.eval_envs > 0):
+    ap.error("--eval_beam B needs 1 <= B <= 16 and --eval_envs M, M > 0")
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
 family = None
@@ -93,6 +99,7 @@ if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
                               f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels,
                               stable_actions_only=a.stable_actions_only)
+beam_env = beam_env_like(eval_env, eval_beam) if eval_beam else None
 r4 = lambda v: None if v is None else round(v, 4)
 
 
@@ -137,6 +144,10 @@ for it in range(1, a.locksteps + 1):
             ev, q_first = evaluate_with_first_q(agent, eval_env, a.eval_epsilon)
             line.update(eval_success_rate=r4(ev["success_rate"]), eval_reward=r4(ev["reward"]), eval_num_steps=r4(ev["num_steps"]),
                         eval_lin_reward=r4(ev["lin_reward"]), eval_q_first=r4(q_first))
+            if beam_env is not None:                            # the same tasks under a beam of width B
+                bs = agent.beam_search(beam_env, eval_beam)
+                line.update(beam_width=eval_beam, beam_success_rate=r4(bs["success_rate"]), beam_reward=r4(bs["reward"]),
+                            beam_lin_reward=r4(bs["lin_reward"]), beam_num_steps=r4(bs["num_steps"]))
             if family:
                 line.update(eval_success_by_class={n: r4(s) for n, s in enumerate(ev["success_by_class"]) if n >= family[1]})
         print(json.dumps(line), flush=True)

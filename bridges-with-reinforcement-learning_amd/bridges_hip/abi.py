@@ -218,7 +218,8 @@ FORK_EXCLUDED = {
     "state_raster": "rewritten from state_bits by the refresh",
     "state_raster_nz": "describes the buffer slot (what the sparse update left in it), not the env",
 }
-BEAM_MAX_WIDTH = 16                            # bridges_beam_select: 1 <= B <= 16
+BEAM_MAX_WIDTH = 16                            # bridges_beam_select, bridges_beam_merge: 1 <= B <= 16
+BEAM_MAX_SLOTS = 64                            # bridges_beam_merge: 1 <= K <= 64
 
 
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)
@@ -277,6 +278,7 @@ SIGNATURES = {
     "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_boltzmann_select": [i32, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_beam_select": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_beam_merge": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups_keyed": [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp],

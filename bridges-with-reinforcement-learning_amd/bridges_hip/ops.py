@@ -542,6 +542,34 @@ def beam_select(seg, q, width, live, ret, disc, idx, cand_offset, rep=None, out=
     return out
 
 
+def beam_merge(n_blocks, blk_shape, blk_pose, blk_occ, targets_left, width, live, ret, key_last=True, out=None):
+    """The beams of every group of ``width`` that hold the same structure, in one launch (bridges_beam_merge; the rule stands in
+    include/bridges_hip.h): E = G * width envs whose state arrays are n_blocks int32 [E], blk_shape int32 [E, K], blk_pose float64
+    [E, K, 4], blk_occ uint8 [E, K] and targets_left int32 [E] (a VecAssemblyGym's own); live uint8 [E], ret float64 [E].  Two live
+    envs of a group are equivalent iff they hold the same multiset of (shape, occupancy, pose bits) blocks, the same targets_left
+    and -- with key_last -- the same last block; the first of a class by (ret desc, env asc) represents it.
+    -> dict(rep int32 [E], live uint8 [E] = live & (rep == env), n_merged int32 [G] = the live envs closed per group); ``out``: such
+    a dict to write into (no allocation)."""
+    L = abi.require_gpu()
+    E, B = n_blocks.numel(), int(width)
+    assert blk_shape.dim() == 2 and blk_shape.shape[0] == E
+    K = blk_shape.shape[1]
+    assert n_blocks.dtype == torch.int32 and blk_shape.dtype == torch.int32 and blk_pose.dtype == torch.float64
+    assert blk_occ.dtype == torch.uint8 and targets_left.dtype == torch.int32 and live.dtype == torch.uint8 and ret.dtype == torch.float64
+    assert tuple(blk_pose.shape) == (E, K, 4) and tuple(blk_occ.shape) == (E, K)
+    assert targets_left.numel() == E and live.numel() == E and ret.numel() == E
+    for t in (n_blocks, blk_shape, blk_pose, blk_occ, targets_left, live, ret):
+        assert t.is_contiguous()
+    if out is None:
+        dev = n_blocks.device
+        out = dict(rep=torch.empty(E, dtype=torch.int32, device=dev), live=torch.empty(E, dtype=torch.uint8, device=dev),
+                   n_merged=torch.empty(E // B if B > 0 else 0, dtype=torch.int32, device=dev))
+    abi.check(L.bridges_beam_merge(E, B, K, _ptr(n_blocks), _ptr(blk_shape), _ptr(blk_pose), _ptr(blk_occ), _ptr(targets_left), _ptr(live),
+                                   _ptr(ret), int(bool(key_last)), _ptr(out["rep"]), _ptr(out["live"]), _ptr(out["n_merged"]), _stream()),
+              "bridges_beam_merge")
+    return out
+
+
 def episode_stats_(out, rec, valid, gpow, n_targets, run, counted, count_first_only=False):
     """Folds one lock-step's records rec float64 [E, W] / valid bool [E] into the per-episode sums ``out`` float64 [8] in place
     (bridges_episode_stats): run float32 [E, 2] and counted int32 [E] carry the episodes that span calls, gpow float32 [K] =

@@ -990,6 +990,23 @@ int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg
                   idx, cand_offset, rep, live, ret, disc, src, sel_compact, sel_index, q_sel, score, live_out);
 }
 
+int bridges_beam_merge(int32_t E, int32_t B, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
+                       const uint8_t* blk_occ, const int32_t* targets_left, const uint8_t* live, const double* ret, int32_t key_last,
+                       int32_t* rep, uint8_t* live_out, int32_t* n_merged, void* stream) {
+    if (E < 0) return fail_arg("bridges_beam_merge: negative count");
+    if (B < 1 || B > BEAM_MAX_WIDTH) return fail_arg("bridges_beam_merge: the width must be 1..16");
+    if (E % B != 0) return fail_arg("bridges_beam_merge: E must be a multiple of the width");
+    if (K < 1 || K > BEAM_MAX_SLOTS) return fail_arg("bridges_beam_merge: K must be 1..64");
+    if (E == 0) return BRIDGES_OK;
+    if (!n_blocks || !blk_shape || !blk_pose || !blk_occ || !targets_left || !live || !ret || !rep || !live_out || !n_merged)
+        return fail_arg("bridges_beam_merge: null pointer");
+    if (!aligned(4, n_blocks, blk_shape, targets_left, rep, n_merged) || !aligned(8, blk_pose, ret))
+        return fail_arg("bridges_beam_merge: misaligned pointer");
+    // one workgroup per group of B beams
+    return launch("k_beam_merge", k_beam_merge, dim3((unsigned)(E / B)), dim3(BEAM_THREADS), 0, stream, E, B, K, n_blocks, blk_shape,
+                  blk_pose, blk_occ, targets_left, live, ret, (int)key_last, rep, live_out, n_merged);
+}
+
 int bridges_record_state(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
                          const uint8_t* blk_occ, const uint8_t* step_flags, const int64_t* sel_row, const int32_t* cand_desc,
                          const double* cand_pose, double* rec, void* stream) {

@@ -109,4 +109,115 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_select(int E, int B, int 
     }
 }
 
+// bridges_beam_merge: the beams of a group that hold the same structure, placed in whatever order (include/bridges_hip.h has the
+// rule).  A live slot is a tuple of five 64-bit words -- shape id | occupancy << 32, then the four pose bit patterns --, an env's
+// key is (nb, targets_left, [the tuple of slot nb - 1], the sorted multiset of its tuples), and two live envs of a group are
+// equivalent iff their keys agree word for word.
+//
+// One workgroup per group, a wave per env (the waves take the group's envs in turn).  Pass 1: lane i < nb holds slot i's tuple and
+// counts the slots that come before it in the lexicographic order of the words, ties by slot index -- a total order, so the counts
+// are a permutation --, and writes its tuple to that place of the env's sorted row in LDS (K <= 64: one lane per slot; rows of 40
+// bytes per lane: no bank conflicts).  Pass 2, after the barrier: the env's wave holds its sorted row against that of every other
+// live env of the group, one lane per slot and one ballot per pair, and keeps the first equivalent env by (ret descending, env
+// ascending).  Nothing is accepted on a hash; no atomics, no scratch, every output written once.
+#define BEAM_TUPLE_WORDS 5
+#define BEAM_MAX_SLOTS 64
+
+struct BeamTuple {
+    uint64_t w[BEAM_TUPLE_WORDS];
+};
+
+__device__ __forceinline__ bool beam_tuple_less(const BeamTuple& a, const BeamTuple& b) {
+#pragma unroll
+    for (int k = 0; k < BEAM_TUPLE_WORDS; ++k)
+        if (a.w[k] != b.w[k]) return a.w[k] < b.w[k];
+    return false;
+}
+
+__device__ __forceinline__ bool beam_tuple_equal(const BeamTuple& a, const BeamTuple& b) {
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < BEAM_TUPLE_WORDS; ++k) same = same && a.w[k] == b.w[k];
+    return same;
+}
+
+// ret a ranks strictly above ret b: a binary64 >, a NaN below every number (two NaNs tie)
+__device__ __forceinline__ bool beam_ret_above(double a, double b) {
+    if (a != a) return false;
+    if (b != b) return true;
+    return a > b;
+}
+
+__global__ __launch_bounds__(BEAM_THREADS) void k_beam_merge(int E, int B, int K, const int32_t* __restrict__ n_blocks,
+                                                             const int32_t* __restrict__ blk_shape, const double* __restrict__ blk_pose,
+                                                             const uint8_t* __restrict__ blk_occ, const int32_t* __restrict__ targets_left,
+                                                             const uint8_t* __restrict__ live, const double* __restrict__ ret, int key_last,
+                                                             int32_t* __restrict__ rep, uint8_t* __restrict__ live_out,
+                                                             int32_t* __restrict__ n_merged) {
+    __shared__ BeamTuple sorted_s[BEAM_MAX_WIDTH][BEAM_MAX_SLOTS];
+    __shared__ BeamTuple last_s[BEAM_MAX_WIDTH];
+    __shared__ int nb_s[BEAM_MAX_WIDTH], tl_s[BEAM_MAX_WIDTH], live_s[BEAM_MAX_WIDTH], closed_s[BEAM_MAX_WIDTH];
+    __shared__ double ret_s[BEAM_MAX_WIDTH];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int e0 = blockIdx.x * B;
+    if (e0 + B > E) return;
+    for (int b = wv; b < B; b += BEAM_THREADS / WAVE) {      // pass 1: env e0 + b's tuples, sorted, into LDS
+        const int e = e0 + b;
+        const int alive = live[e] != 0;
+        int nb = n_blocks[e];
+        nb = nb < 0 ? 0 : (nb > K ? K : nb);
+        if (lane == 0) { nb_s[b] = nb; tl_s[b] = targets_left[e]; live_s[b] = alive; ret_s[b] = ret[e]; }
+        if (!alive) continue;                                // (wave-uniform) a dead env matches nothing
+        BeamTuple mine;
+#pragma unroll
+        for (int k = 0; k < BEAM_TUPLE_WORDS; ++k) mine.w[k] = 0ull;
+        if (lane < nb) {
+            const size_t s = (size_t)e * K + lane;
+            const uint64_t* p = reinterpret_cast<const uint64_t*>(blk_pose + s * 4);
+            mine.w[0] = (uint64_t)(uint32_t)blk_shape[s] | ((uint64_t)blk_occ[s] << 32);
+            mine.w[1] = p[0]; mine.w[2] = p[1]; mine.w[3] = p[2]; mine.w[4] = p[3];
+        }
+        int before = 0;
+        for (int j = 0; j < nb; ++j) {                       // (nb is wave-uniform: every lane takes part in the shuffles)
+            BeamTuple o;
+#pragma unroll
+            for (int k = 0; k < BEAM_TUPLE_WORDS; ++k) o.w[k] = __shfl(mine.w[k], j);
+            before += (beam_tuple_less(o, mine) || (j < lane && beam_tuple_equal(o, mine))) ? 1 : 0;
+        }
+        if (lane < nb) {
+            sorted_s[b][before] = mine;                      // before < nb: it counts slots other than this one
+            if (lane == nb - 1) last_s[b] = mine;
+        }
+    }
+    __syncthreads();
+    for (int b = wv; b < B; b += BEAM_THREADS / WAVE) {      // pass 2: the representative of env e0 + b
+        const int nb = nb_s[b];
+        int best = b;
+        if (live_s[b]) {
+            BeamTuple mine;
+            if (lane < nb) mine = sorted_s[b][lane];
+            for (int o = 0; o < B; ++o) {
+                if (o == b || !live_s[o] || nb_s[o] != nb || tl_s[o] != tl_s[b]) continue;           // (wave-uniform)
+                bool differs = lane < nb && !beam_tuple_equal(mine, sorted_s[o][lane]);
+                if (key_last && nb > 0 && lane == 0) differs = differs || !beam_tuple_equal(last_s[b], last_s[o]);
+                if (__ballot(differs) != 0ull) continue;
+                // o is of b's class: it takes the place of best if it comes before it by (ret descending, env ascending)
+                if (beam_ret_above(ret_s[o], ret_s[best]) || (!beam_ret_above(ret_s[best], ret_s[o]) && o < best)) best = o;
+            }
+        }
+        if (lane == 0) {
+            const int e = e0 + b;
+            rep[e] = e0 + best;
+            live_out[e] = (live_s[b] && best == b) ? 1 : 0;
+            closed_s[b] = (live_s[b] && best != b) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        int n = 0;
+        for (int b = 0; b < B; ++b) n += closed_s[b];
+        n_merged[blockIdx.x] = n;
+    }
+}
+
 }  // namespace bridges

@@ -737,12 +737,20 @@ def add_eval_beam_argument(p):
                    help="Vectorised loop with --eval_envs M: every evaluation also runs a beam search of width B (1..16) on the same "
                         "M tasks, with the policy net's q as the heuristic (VecDQN.beam_search: B envs per task, forked on the "
                         "device), and logs beam_success_rate / beam_reward / beam_lin_reward / beam_width beside the greedy keys.")
+    p.add_argument("--eval_beam_merge", action="store_true", default=argparse.SUPPRESS,
+                   help="With --eval_beam B: after every depth the search closes the beams that hold the same structure as another "
+                        "beam of their task -- the same blocks placed in another order, the same last block -- and keeps the one with "
+                        "the best return (bridges_beam_merge), so the width is not spent on permutations; logs eval_merged_beams, "
+                        "the beams closed that way.")
 
 
 def check_eval_beam(args):
-    """--eval_beam B: refused in words (SystemExit) where the loop cannot run it, before anything touches the GPU."""
+    """--eval_beam B / --eval_beam_merge: refused in words (SystemExit) where the loop cannot run it, before anything touches the
+    GPU."""
     B = args.get('eval_beam')
     if B is None:
+        if args.get('eval_beam_merge'):
+            raise SystemExit("--eval_beam_merge merges the beams of the search --eval_beam B runs: it needs --eval_beam B")
         return
     from bridges_hip import abi
     if not 1 <= B <= abi.BEAM_MAX_WIDTH:

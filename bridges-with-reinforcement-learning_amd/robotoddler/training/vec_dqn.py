@@ -683,7 +683,7 @@ class VecDQN:
 
     # ------------------------------------------------------------------ beam-search evaluation
     @torch.no_grad()
-    def beam_search(self, beam_env, width):
+    def beam_search(self, beam_env, width, merge=False, on_depth=None):
         """Beam search of width B = ``width`` over every task of ``beam_env`` (beam_env_like(eval_env, B): M * B envs, the B envs
         of a group share one task), the policy net's q as the heuristic: how much the learned Q is worth when the simulator is
         allowed to look ahead.  Per depth, for all groups at once and without a host decision: the candidate rows and their q
@@ -695,11 +695,19 @@ class VecDQN:
         return, then the earlier depth, then the lower slot -- and dies; a dead slot spends its lock-steps resetting.  Runs
         beam_env.K depths and reads the results back once; per depth the host waits only where acting waits (the row count of
         valid_rows).  Touches no training state.  width = 1 is the greedy episode of evaluate().
+        merge: after a depth's finished beams are recorded and closed, one bridges_beam_merge launch closes every live beam that
+        holds the same structure as another live beam of its group with a return at least as high -- the same multiset of blocks,
+        the same targets_left and the same last block (key_last = 1: the frozen block, on which the candidate set can depend), so
+        "same key, same future" holds and the next depth's select refills the group from the survivors' candidates.  merge=False
+        launches nothing of it.  on_depth(d, live): called after depth d's bookkeeping with the live flags (uint8 [E], on the
+        device) -- for tests and tools, which read the env's state then; None costs nothing.
         -> evaluate()'s keys as means over the M tasks (success_rate, reward, lin_reward, num_steps, episodes; reward and
         lin_reward are the best beam's discounted sums, in float64), beam_width, and structures: per task a dict of the best
         beam's placed blocks (shape ids, poses (x, z, cos, sin)), its actions (the candidate index placed at every depth),
-        success, reward, lin_reward, num_steps and final_reward.  On a beam env of a task family also success_by_class and
-        episodes_by_class, indexed by the class n = 0..hi of every task."""
+        success, reward, lin_reward, num_steps and final_reward, and merged_beams: per task the beams that merging closed over the
+        search (zeros without merge); with merge also merged_by_depth and live_by_depth: per depth, over all tasks, the beams
+        closed and the live beams the merge looked at.  On a beam env of a task family also success_by_class and episodes_by_class, indexed by the
+        class n = 0..hi of every task."""
         B, env = int(width), beam_env
         if env is self.env:
             raise ValueError("beam_search() needs an env of its own: the training env's episodes would be cut short")
@@ -716,6 +724,11 @@ class VecDQN:
             raise ValueError("the beam env must have per-env tasks / obstacles exactly when the agent was built with them")
         E, K, dev = env.E, env.K, self.device
         M = E // B
+        if merge and K > abi.BEAM_MAX_SLOTS:
+            raise ValueError(f"beam_search(merge=True): bridges_beam_merge orders at most {abi.BEAM_MAX_SLOTS} block slots per env, "
+                             f"the beam env has {K}")
+        # per task and depth: the beams merging closed, then the live beams it looked at
+        merged = torch.zeros((M, 2 * K), dtype=torch.int32, device=dev) if merge else None
         slots = torch.arange(E, device=dev) % B
         first = torch.arange(M, device=dev) * B
         live = (slots == 0).to(torch.uint8)                  # only slot 0 of every group is open
@@ -761,12 +774,19 @@ class VecDQN:
             better = has_new & ((best[:, 0] == 0) | (new[:, 1] > best[:, 1]) | ((new[:, 1] == best[:, 1]) & (new[:, 2] > best[:, 2])))
             best = torch.where(better.unsqueeze(1), new, best)
             live = (live & ~fin).to(torch.uint8)
-        host = best.cpu()                                    # the one wait of the search
+            if merge:                                        # beams that hold the same structure: the best return stays open
+                mg = ops.beam_merge(env.n_blocks, env.blk_shape, env.blk_pose, env.blk_occ, env.targets_left, B, live, ret, key_last=True)
+                merged[:, d], merged[:, K + d] = mg["n_merged"], live.view(M, B).sum(dim=1)
+                live = mg["live"]
+            if on_depth is not None:
+                on_depth(d, live)
+        # the one wait of the search (with merge: the merged counts ride along as further columns)
+        host = (torch.cat([best, merged.double()], dim=1) if merge else best).cpu()
         if int(host[:, 0].sum()) != M:
             raise RuntimeError(f"beam search: {int(host[:, 0].sum())} of {M} tasks ended an episode within {K} depths "
                                "(a task whose fresh state has no valid candidate never starts one)")
         succ_h, steps_h = host[:, 1].tolist(), [int(v) for v in host[:, 4].tolist()]
-        hist_h = host[:, 6:].reshape(M, K, 6)
+        hist_h = host[:, 6:6 + 6 * K].reshape(M, K, 6)
         structures = []
         for m in range(M):
             n = steps_h[m]
@@ -775,7 +795,11 @@ class VecDQN:
                                    lin_reward=float(host[m, 2]), reward=float(host[m, 3]), num_steps=n, final_reward=float(host[m, 5])))
         out = dict(reward=float(host[:, 3].mean()), lin_reward=float(host[:, 2].mean()), avg_loss=None,
                    num_steps=float(host[:, 4].mean()), success_rate=float(host[:, 1].mean()), episodes=M, beam_width=B,
-                   structures=structures)
+                   structures=structures, merged_beams=[0] * M)
+        if merge:
+            counts = host[:, 6 + 6 * K:].long()
+            out.update(merged_beams=counts[:, :K].sum(dim=1).tolist(), merged_by_depth=counts[:, :K].sum(dim=0).tolist(),
+                       live_by_depth=counts[:, K:].sum(dim=0).tolist())
         classes = getattr(env, "beam_task_class", None)
         if classes is not None:                              # the tasks of a family: per span / height n = 0..hi
             n_classes = env.beam_n_classes
@@ -1406,6 +1430,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     # --eval_beam B: every evaluation also searches the same tasks with a beam of width B (B envs per task, forked on the device)
     eval_beam = args.get('eval_beam')
     beam_env = beam_env_like(eval_env, eval_beam) if eval_beam and eval_env is not None else None
+    eval_beam_merge = bool(args.get('eval_beam_merge'))      # --eval_beam_merge: that search merges beams of the same structure
     history, t0, it = [], time.time(), 0
     next_ckpt = next_multiple(0, args['checkpoint_every'])
     next_eval = next_multiple(0, args['evaluate_every'])
@@ -1485,9 +1510,11 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)
                 if beam_env is not None:                     # the same tasks under the beam search, beside the greedy keys
-                    bs = agent.beam_search(beam_env, eval_beam)
+                    bs = agent.beam_search(beam_env, eval_beam, merge=eval_beam_merge)
                     ev.update(beam_success_rate=bs['success_rate'], beam_reward=bs['reward'], beam_lin_reward=bs['lin_reward'],
                               beam_width=eval_beam)
+                    if eval_beam_merge:                      # the beams closed as duplicates, over all tasks and depths
+                        ev.update(eval_merged_beams=sum(bs['merged_beams']))
                 if aim_run is not None or wandb_run is not None:
                     if family:                               # the sinks take scalars: success_rate_n{k} for the lists by class
                         by_class = ev['success_by_class']

@@ -571,6 +571,29 @@ int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg
                         const double* disc, int32_t* src, int64_t* sel_compact, int32_t* sel_index, float* q_sel, double* score,
                         uint8_t* live_out, void* stream);
 
+/* Beam search: the beams of a group that hold the same structure, reached by whatever order of placements.  E = G * B envs, group
+ * g owns envs gB .. gB + B - 1 as for bridges_beam_select; the caller guarantees that the envs of a group share one task.  The
+ * state arrays are the env's own (n_blocks [E], blk_shape [E, K], blk_pose [E, K, 4], blk_occ [E, K], targets_left [E]: the env's
+ * 4-byte word, as the fork table copies it); live u8 [E], ret f64 [E] as for bridges_beam_select.
+ *   - BLOCK TUPLE of live slot i < nb of env e, nb = n_blocks[e] clamped to [0, K]: the shape id as u32, the occupancy byte, and
+ *     the four pose words as 64-bit BIT PATTERNS -- no float comparison, so -0.0 != 0.0 (that costs a merge, never correctness);
+ *   - KEY of env e: nb; targets_left[e] (the order of placements can change which targets count as reached); with key_last != 0
+ *     the tuple of slot nb - 1 (absent when nb = 0); and the SORTED MULTISET of the tuples of slots 0 .. nb - 1 -- equal tuples
+ *     inside one env count with their multiplicity;
+ *   - EQUIVALENCE: two LIVE envs of the SAME group are equivalent iff their keys are equal word for word (nothing is accepted on
+ *     a hash); a dead env and envs of other groups never match;
+ *   - REPRESENTATIVE of a class: its first env by ret descending (a binary64 >; a NaN ret ranks below every number), then env
+ *     index ascending;
+ *   - rep[e] = the representative of e's class (e itself for a dead env), live_out[e] = live[e] && rep[e] == e, n_merged[g] = the
+ *     number of live envs of group g that were closed (live[e] && rep[e] != e).
+ * One workgroup per group: every env's tuples are sorted into LDS (ties by slot index, so the order is total), then every env is
+ * held against the other live envs of its group.  No atomics, no scratch, every output written exactly once, the same bits on
+ * every call; no output may alias an input.  1 <= B <= 16, 1 <= K <= 64.  Refused (-1, nothing launched): E < 0, B or K outside
+ * those, E % B != 0, a NULL array, a misaligned pointer.  E == 0 returns 0 and launches nothing. */
+int bridges_beam_merge(int32_t E, int32_t B, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
+                       const uint8_t* blk_occ, const int32_t* targets_left, const uint8_t* live, const double* ret, int32_t key_last,
+                       int32_t* rep, uint8_t* live_out, int32_t* n_merged, void* stream);
+
 /* --- transition records of the vectorised loop ------------------------------------------------------------------
  * One float64 row per transition: the compact form of the reference's Transition (successor_dqn.py:27-44) -- the block
  * list of s, the placed block and the scalars; rasters and candidate sets are re-generated when a record is sampled.

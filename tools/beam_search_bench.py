@@ -7,9 +7,16 @@
   search    one VecDQN.beam_search(width) call for every --widths next to one VecDQN.evaluate() call on --tasks held-out tasks
             (wall clock around the whole call, its host waits included)
 HIP events around single calls (fork, select), the legs alternating, warm-up first; one JSON line per shape with medians and spread.
+--merge times beam merging instead of the parts above:
+  merge     ops.beam_merge (bridges_beam_merge: one launch) alone at --tasks groups of --width beams whose envs hold permutations of
+            a few structures, HIP events around single calls after warm-up
+  search    one VecDQN.beam_search(--width) call without and with merge=True on the same --tasks held-out tasks, alternating (wall
+            clock around the whole call), and the beams merging closed
 --syncs lists the host waits of one evaluate() and one beam_search() call instead (tools/find_syncs.py's counting, plus explicit
-stream / event / device synchronisations): per depth the search must wait only where acting waits.
-    python tools/beam_search_bench.py [--fork_envs 512 4096] [--groups 64 512] [--width 8] [--tasks 64] [--widths 1 4 8] [--syncs]"""
+stream / event / device synchronisations): per depth the search must wait only where acting waits
+(with --merge: of the search with and without merging -- merging must add none).
+    python tools/beam_search_bench.py [--fork_envs 512 4096] [--groups 64 512] [--width 8] [--tasks 64] [--widths 1 4 8] [--syncs]
+    python tools/beam_search_bench.py --merge [--tasks 64] [--width 8] [--syncs]"""
 import argparse, ctypes as C, json, os, sys, time, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -33,6 +40,7 @@ ap.add_argument("--reps", type=int, default=40)
 ap.add_argument("--search_reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--syncs", action="store_true")
+ap.add_argument("--merge", action="store_true", help="time bridges_beam_merge and a search with / without merging at --tasks x --width")
 a = ap.parse_args()
 assert a.reps >= 20 and a.search_reps >= 5
 dev = torch.device("cuda:0")
@@ -105,7 +113,7 @@ def waits(fn):
 
 
 # ---- fork ---------------------------------------------------------------------------------------------------------------------
-for E in ([] if a.syncs else a.fork_envs):
+for E in ([] if a.syncs or a.merge else a.fork_envs):
     env = tower_env(E)
     for _ in range(4):
         env.select_random()
@@ -134,7 +142,7 @@ for E in ([] if a.syncs else a.fork_envs):
     del env, arrays, scratch
 
 # ---- select -------------------------------------------------------------------------------------------------------------------
-for G in ([] if a.syncs else a.groups):
+for G in ([] if a.syncs or a.merge else a.groups):
     B = a.width
     E = G * B
     g = torch.Generator().manual_seed(G)
@@ -177,6 +185,33 @@ for G in ([] if a.syncs else a.groups):
                           torch_over_select=s["torch"]["median_us"] / s["select"]["median_us"],
                           note="HIP events around single calls (host launch gaps included), legs alternating")), flush=True)
 
+# ---- merge --------------------------------------------------------------------------------------------------------------------
+if a.merge and not a.syncs:
+    G, B, K = max(a.tasks, 1), a.width, a.max_steps
+    E = G * B
+    rng = np.random.default_rng(G)
+    pool_shape, pool_occ, pool_pose = rng.integers(0, 2, 12), rng.integers(0, 4, 12), rng.normal(size=(12, 4))
+    n_blocks = np.zeros(E, np.int32)
+    pick = np.zeros((E, K), np.int64)
+    for g in range(G):                                       # a group: permutations of two or three structures of one depth
+        nb = int(rng.integers(1, K + 1))
+        bases = [rng.integers(0, 12, nb) for _ in range(3)]
+        for e in range(g * B, (g + 1) * B):
+            n_blocks[e] = nb
+            pick[e, :nb] = rng.permutation(bases[int(rng.integers(0, 3))])
+    to = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x)).to(dt).to(dev)
+    st = dict(n_blocks=to(n_blocks, torch.int32), blk_shape=to(pool_shape[pick], torch.int32), blk_pose=to(pool_pose[pick], torch.float64),
+              blk_occ=to(pool_occ[pick], torch.uint8), targets_left=torch.full((E,), 3, dtype=torch.int32, device=dev))
+    live = to(rng.random(E) < 0.9, torch.uint8)
+    ret = to(rng.normal(size=E), torch.float64)
+    out = ops.beam_merge(st["n_blocks"], st["blk_shape"], st["blk_pose"], st["blk_occ"], st["targets_left"], B, live, ret)
+
+    def merge_op():
+        return ops.beam_merge(st["n_blocks"], st["blk_shape"], st["blk_pose"], st["blk_occ"], st["targets_left"], B, live, ret, out=out)
+    s = alternate((("merge", merge_op),), a.reps, a.warmup)
+    print(json.dumps(dict(part="merge", groups=G, width=B, slots=K, live=int(live.sum()), closed=int(out["n_merged"].sum()), **s,
+                          note="HIP events around single calls (host launch gap included), after warm-up")), flush=True)
+
 # ---- search -------------------------------------------------------------------------------------------------------------------
 if a.tasks > 0:
     args = vars(build_parser().parse_args(["--model", "SuccessorMLP"]))
@@ -187,8 +222,10 @@ if a.tasks > 0:
     agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), mk(256, 0), 20000, 32, 0.95, 0.01,
                    "mse_q_values+mse_block_features", per_env_tasks=True)
     eval_env = mk(a.tasks, 1)
-    beams = {B: beam_env_like(eval_env, B) for B in a.widths}
-    legs = [("evaluate", lambda: agent.evaluate(eval_env))] + [(f"beam_{B}", (lambda B=B: agent.beam_search(beams[B], B))) for B in a.widths]
+    beams = {B: beam_env_like(eval_env, B) for B in ([a.width] if a.merge else a.widths)}
+    legs = [("evaluate", lambda: agent.evaluate(eval_env))] + [(f"beam_{B}", (lambda B=B: agent.beam_search(beams[B], B))) for B in beams]
+    if a.merge:
+        legs.append((f"beam_{a.width}_merge", lambda: agent.beam_search(beams[a.width], a.width, merge=True)))
     if a.syncs:
         for name, fn in legs:
             fn()
@@ -203,4 +240,7 @@ if a.tasks > 0:
                               over_evaluate={name: s[name]["median_us"] / s["evaluate"]["median_us"] for name, _ in legs[1:]},
                               success_rate={name: r["success_rate"] for name, r in res.items()},
                               lin_reward={name: r["lin_reward"] for name, r in res.items()},
+                              merged_beams={name: sum(r["merged_beams"]) for name, r in res.items() if "merged_beams" in r},
+                              **(dict(merge_minus_plain_us=s[f"beam_{a.width}_merge"]["median_us"] - s[f"beam_{a.width}"]["median_us"])
+                                 if a.merge else {}),
                               note="wall clock around whole calls on an UNTRAINED net (cost only), legs alternating")), flush=True)

@@ -8,8 +8,11 @@ With --eval_envs the line also holds eval_q_first, the mean over the evaluation 
 the FIRST step of the episode: the net's own forecast of eval_lin_reward, the discounted lin_reward the same episodes then
 realise -- their difference is the over-estimation that --double_q is meant to reduce.
 With --eval_beam B beside --eval_envs the line also holds beam_success_rate / beam_reward / beam_lin_reward: the same tasks under a
-beam search of width B with the policy net's q as the heuristic (VecDQN.beam_search).
-    python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values] [--eval_envs 64 [--eval_beam 8]]"""
+beam search of width B with the policy net's q as the heuristic (VecDQN.beam_search).  With --eval_beam_merge beside it the same
+search runs once more with merge=True (beams that hold the same structure are closed after every depth): merge_success_rate /
+merge_reward / merge_lin_reward, eval_merged_beams, and per depth merged_by_depth / live_by_depth (closed / looked at).
+    python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values]
+                                   [--eval_envs 64 [--eval_beam 8 [--eval_beam_merge]]]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -60,6 +63,9 @@ a = ap.parse_args()
 eval_beam = vars(a).get("eval_beam")
 if eval_beam is not None and not (1 <= eval_beam <= 16 and a.eval_envs > 0):
     ap.error("--eval_beam B needs 1 <= B <= 16 and --eval_envs M, M > 0")
+eval_beam_merge = bool(vars(a).get("eval_beam_merge"))
+if eval_beam_merge and eval_beam is None:
+    ap.error("--eval_beam_merge merges the beams of the search --eval_beam B runs: it needs --eval_beam B")
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
 family = None
@@ -148,6 +154,12 @@ for it in range(1, a.locksteps + 1):
                 bs = agent.beam_search(beam_env, eval_beam)
                 line.update(beam_width=eval_beam, beam_success_rate=r4(bs["success_rate"]), beam_reward=r4(bs["reward"]),
                             beam_lin_reward=r4(bs["lin_reward"]), beam_num_steps=r4(bs["num_steps"]))
+                if eval_beam_merge:                             # ... and under the same beam with merging, beside it
+                    bm = agent.beam_search(beam_env, eval_beam, merge=True)
+                    line.update(merge_success_rate=r4(bm["success_rate"]), merge_reward=r4(bm["reward"]),
+                                merge_lin_reward=r4(bm["lin_reward"]), merge_num_steps=r4(bm["num_steps"]),
+                                eval_merged_beams=sum(bm["merged_beams"]), merged_by_depth=bm["merged_by_depth"],
+                                live_by_depth=bm["live_by_depth"])
             if family:
                 line.update(eval_success_by_class={n: r4(s) for n, s in enumerate(ev["success_by_class"]) if n >= family[1]})
         print(json.dumps(line), flush=True)

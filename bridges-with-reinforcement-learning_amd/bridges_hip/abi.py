@@ -220,6 +220,8 @@ FORK_EXCLUDED = {
 }
 BEAM_MAX_WIDTH = 16                            # bridges_beam_select, bridges_beam_merge: 1 <= B <= 16
 BEAM_MAX_SLOTS = 64                            # bridges_beam_merge: 1 <= K <= 64
+REC_WIDTH = 111                                # BRIDGES_REC_WIDTH: the doubles of a transition record
+BEAM_TRACE_MAX_DEPTH = 16                      # bridges_beam_trace: 1 <= D <= BRIDGES_REC_K
 
 
 # put lp_ws_stride right after lp_ws as in the header (fields above are already in header order)
@@ -279,6 +281,7 @@ SIGNATURES = {
     "bridges_boltzmann_select": [i32, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_beam_select": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_beam_merge": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "bridges_beam_trace": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp, vp, vp],
     "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_env_groups_keyed": [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp],

@@ -570,6 +570,72 @@ def beam_merge(n_blocks, blk_shape, blk_pose, blk_occ, targets_left, width, live
     return out
 
 
+def beam_trace_args(rec, valid, parent, end_env, end_depth, B, gamma, n_step=1, tail=None):
+    """The argument checks of beam_trace that need no device -> (E, B, D, n_step, n_tail, W_out).  ValueError in words."""
+    import math
+    B, n_step = int(B), int(n_step)
+    if not 1 <= B <= abi.BEAM_MAX_WIDTH:
+        raise ValueError(f"beam_trace: the width must be 1..{abi.BEAM_MAX_WIDTH}, got {B}")
+    if not 1 <= n_step <= abi.NSTEP_MAX:
+        raise ValueError(f"beam_trace: n_step must be 1..{abi.NSTEP_MAX}, got {n_step}")
+    if not math.isfinite(float(gamma)):
+        raise ValueError(f"beam_trace: gamma must be finite, got {gamma!r}")
+    if rec.dim() != 3 or rec.shape[2] != abi.REC_WIDTH or rec.dtype != torch.float64:
+        raise ValueError(f"beam_trace: rec must be float64 [D, E, {abi.REC_WIDTH}], got {rec.dtype} {tuple(rec.shape)}")
+    D, E = int(rec.shape[0]), int(rec.shape[1])
+    if not 1 <= D <= abi.BEAM_TRACE_MAX_DEPTH:
+        raise ValueError(f"beam_trace: 1..{abi.BEAM_TRACE_MAX_DEPTH} depths, got {D}")
+    if E % B != 0:
+        raise ValueError(f"beam_trace: E = {E} envs is no multiple of the width {B}")
+    G = E // B
+    if valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != (D, E):
+        raise ValueError(f"beam_trace: valid must be uint8 or bool [{D}, {E}], got {valid.dtype} {tuple(valid.shape)}")
+    if parent.dtype != torch.int32 or tuple(parent.shape) != (D, E):
+        raise ValueError(f"beam_trace: parent must be int32 [{D}, {E}], got {parent.dtype} {tuple(parent.shape)}")
+    for name, t in (("end_env", end_env), ("end_depth", end_depth)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (G,):
+            raise ValueError(f"beam_trace: {name} must be int32 [{G}], got {t.dtype} {tuple(t.shape)}")
+    n_tail = 0
+    if tail is not None:
+        if tail.dtype != torch.float64 or tail.dim() != 2 or tail.shape[0] != E:
+            raise ValueError(f"beam_trace: tail must be float64 [{E}, n_tail], got {tail.dtype} {tuple(tail.shape)}")
+        n_tail = int(tail.shape[1])
+    for name, t in (("rec", rec), ("valid", valid), ("parent", parent), ("end_env", end_env), ("end_depth", end_depth), ("tail", tail)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"beam_trace: {name} must be contiguous")
+    return E, B, D, n_step, n_tail, abi.REC_WIDTH + n_tail + (1 if n_step > 1 else 0)
+
+
+def beam_trace(rec, valid, parent, end_env, end_depth, B, gamma, n_step=1, tail=None, priority=0.0, out=None, offset=None, status=None):
+    """The transition records of one finished beam per group of ``B`` beams, traced back through the slots it occupied
+    (bridges_beam_trace; the rule stands in include/bridges_hip.h).  rec float64 [D, E, 111], valid uint8 [D, E] and parent int32
+    [D, E] are what a search kept per depth (the step's record, whether the env made one, the src of that depth's beam_select);
+    end_env, end_depth int32 [G] name the end of one episode per group (end_depth < 0: none).  An intact chain of L = end_depth + 1
+    steps emits L rows in the width a replay ring stores: the record of the last of h = min(n_step, L - t) steps with the start's
+    STABLE_S, ``priority`` as TD and, for h > 1, the h-step return as LIN; then tail[end_env] (float64 [E, n_tail]: the task), then
+    h when n_step > 1.
+    -> dict(rows float64 [G * D, W_out] -- group g's rows are rows[offset[g] : offset[g + 1]], rows from offset[G] on are not
+    written --, offset int32 [G + 1], status int32 [G]: 1 where the chain is broken); ``out`` / ``offset`` / ``status``: tensors to
+    write into (no allocation).  Nothing here waits for the GPU."""
+    E, B, D, n_step, n_tail, Wo = beam_trace_args(rec, valid, parent, end_env, end_depth, B, gamma, n_step, tail)
+    L = abi.require_gpu()
+    G, dev = E // B, rec.device
+    if out is None:
+        out = torch.empty((G * D, Wo), dtype=torch.float64, device=dev)
+    if offset is None:
+        offset = torch.empty(G + 1, dtype=torch.int32, device=dev) if E else torch.zeros(1, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty(G, dtype=torch.int32, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (G * D, Wo) and out.is_contiguous()
+    assert offset.dtype == torch.int32 and offset.numel() == G + 1 and offset.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == G and status.is_contiguous()
+    if E:
+        abi.check(L.bridges_beam_trace(E, B, D, n_step, n_tail, _ptr(rec), _ptr(valid), _ptr(parent), _ptr(end_env), _ptr(end_depth),
+                                       _ptr(tail), float(gamma), float(priority), _ptr(out), _ptr(offset), _ptr(status), _stream()),
+                  "bridges_beam_trace")
+    return dict(rows=out, offset=offset, status=status)
+
+
 def episode_stats_(out, rec, valid, gpow, n_targets, run, counted, count_first_only=False):
     """Folds one lock-step's records rec float64 [E, W] / valid bool [E] into the per-episode sums ``out`` float64 [8] in place
     (bridges_episode_stats): run float32 [E, 2] and counted int32 [E] carry the episodes that span calls, gpow float32 [K] =

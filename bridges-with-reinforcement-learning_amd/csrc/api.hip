@@ -1007,6 +1007,30 @@ int bridges_beam_merge(int32_t E, int32_t B, int32_t K, const int32_t* n_blocks,
                   blk_pose, blk_occ, targets_left, live, ret, (int)key_last, rep, live_out, n_merged);
 }
 
+int bridges_beam_trace(int32_t E, int32_t B, int32_t D, int32_t n_step, int32_t n_tail, const double* rec, const uint8_t* valid,
+                       const int32_t* parent, const int32_t* end_env, const int32_t* end_depth, const double* tail, double gamma,
+                       double priority, double* out, int32_t* offset, int32_t* status, void* stream) {
+    if (E < 0) return fail_arg("bridges_beam_trace: negative count");
+    if (B < 1 || B > BEAM_MAX_WIDTH) return fail_arg("bridges_beam_trace: the width must be 1..16");
+    if (E % B != 0) return fail_arg("bridges_beam_trace: E must be a multiple of the width");
+    if (D < 1 || D > BRIDGES_REC_K) return fail_arg("bridges_beam_trace: D must be 1..BRIDGES_REC_K");
+    if (n_step < 1 || n_step > BRIDGES_NSTEP_MAX) return fail_arg("bridges_beam_trace: n_step must be 1..BRIDGES_NSTEP_MAX");
+    if (n_tail < 0) return fail_arg("bridges_beam_trace: negative tail width");
+    if (!(gamma - gamma == 0.0)) return fail_arg("bridges_beam_trace: gamma must be finite");
+    if (!rec || !valid || !parent || !end_env || !end_depth || !out || !offset || !status || (n_tail > 0 && !tail))
+        return fail_arg("bridges_beam_trace: null pointer");
+    if (!aligned(8, rec, tail, out) || !aligned(4, parent, end_env, end_depth, offset, status))
+        return fail_arg("bridges_beam_trace: misaligned pointer");
+    if (E == 0) return BRIDGES_OK;
+    BeamTraceArgs a;
+    a.rec = rec; a.valid = valid; a.parent = parent; a.end_env = end_env; a.end_depth = end_depth; a.tail = n_tail > 0 ? tail : nullptr;
+    a.gamma = gamma; a.priority = priority; a.E = E; a.B = B; a.D = D; a.n_step = n_step; a.n_tail = n_tail;
+    // one workgroup per group of B beams, twice: the chains are checked, then the rows of the intact ones are written
+    const dim3 grid((unsigned)(E / B));
+    if (int rc = launch("k_beam_trace_check", k_beam_trace_check, grid, dim3(BEAM_THREADS), 0, stream, a, status)) return rc;
+    return launch("k_beam_trace_rows", k_beam_trace_rows, grid, dim3(BEAM_THREADS), 0, stream, a, (const int32_t*)status, out, offset);
+}
+
 int bridges_record_state(int32_t E, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
                          const uint8_t* blk_occ, const uint8_t* step_flags, const int64_t* sel_row, const int32_t* cand_desc,
                          const double* cand_pose, double* rec, void* stream) {

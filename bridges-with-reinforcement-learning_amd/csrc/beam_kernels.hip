@@ -220,4 +220,155 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_merge(int E, int B, int K
     }
 }
 
+// bridges_beam_trace: the transition records of one finished beam per group, read back along the parent pointers of the search
+// (include/bridges_hip.h has the rule).  Per depth t the search keeps rec [D, E, REC_WIDTH], valid [D, E] and parent [D, E] (the src
+// of that depth's select); a group names the end (end_env, end_depth) of one episode, whose chain is e_{L-1} = end_env,
+// e_{t-1} = parent[t][e_t].
+//
+// Two launches, one workgroup per group in both, no scratch:
+//   k_beam_trace_check   the group's [D, B] slices of parent and valid go to LDS in parallel (at most 256 words each), one lane
+//                        walks the chain there, status[g] = 1 for a broken chain.
+//   k_beam_trace_rows    the same load and walk (a few dozen LDS reads: cheaper than a trip through memory for the chain); the
+//                        group's row offset is the sum of the rows of the groups in front of it -- L of every group with an end and
+//                        status 0, integers, so the order of the sum cannot matter --; lanes t < L fetch lin_t and stable_t of their
+//                        chain member; lane t sums the return of start t in the fixed order of bridges_nstep_fold; then a wave per
+//                        row, the lanes on consecutive doubles of it.
+// The offsets cost G reads per workgroup (G is a number of tasks: tens to hundreds) and save the scan launch and its scratch.
+// No atomics; every output word is written at most once; the same bits on every call.
+static_assert(BRIDGES_REC_K * BEAM_MAX_WIDTH <= BEAM_THREADS, "a group's [D, B] slice is loaded by one lane per word");
+
+struct BeamTraceArgs {
+    const double* rec;
+    const uint8_t* valid;
+    const int32_t* parent;
+    const int32_t* end_env;
+    const int32_t* end_depth;
+    const double* tail;
+    double gamma, priority;
+    int E, B, D, n_step, n_tail;
+};
+
+// The walk of group g in LDS: par_s / val_s [D * B] hold the group's slices (parent as given, row 0 unused), chain_s [D] receives
+// e_t - gB.  -> L (0: nothing ended, or the chain is broken), broken set accordingly.  Called by one lane.
+__device__ __forceinline__ int beam_trace_walk(const BeamTraceArgs& a, int g, const int* par_s, const uint8_t* val_s, int* chain_s,
+                                               bool& broken) {
+    const int B = a.B, e0 = g * B;
+    const int ed = a.end_depth[g];
+    broken = false;
+    if (ed < 0) return 0;
+    broken = true;
+    if (ed >= a.D) return 0;
+    const int ee = a.end_env[g];
+    int b = (ee < e0 || ee >= e0 + B) ? -1 : ee - e0;
+    for (int t = ed; t >= 0; --t) {
+        if (b < 0 || b >= B || !val_s[t * B + b]) return 0;
+        chain_s[t] = b;
+        if (t > 0) {
+            const int p = par_s[t * B + b];
+            b = (p < e0 || p >= e0 + B) ? -1 : p - e0;
+        }
+    }
+    broken = false;
+    return ed + 1;
+}
+
+__device__ __forceinline__ void beam_trace_load(const BeamTraceArgs& a, int g, int* par_s, uint8_t* val_s) {
+    const int i = threadIdx.x;                              // D * B <= BRIDGES_REC_K * BEAM_MAX_WIDTH = BEAM_THREADS
+    if (i < a.D * a.B) {
+        const int t = i / a.B, b = i % a.B;
+        const size_t at = (size_t)t * a.E + (size_t)g * a.B + b;
+        par_s[i] = t > 0 ? a.parent[at] : 0;                // row 0 of parent is never read
+        val_s[i] = a.valid[at];
+    }
+}
+
+__global__ __launch_bounds__(BEAM_THREADS) void k_beam_trace_check(BeamTraceArgs a, int32_t* __restrict__ status) {
+    __shared__ int par_s[BEAM_THREADS];
+    __shared__ uint8_t val_s[BEAM_THREADS];
+    __shared__ int chain_s[BRIDGES_REC_K];
+    const int g = blockIdx.x;
+    beam_trace_load(a, g, par_s, val_s);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bool broken;
+        beam_trace_walk(a, g, par_s, val_s, chain_s, broken);
+        status[g] = broken ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(BEAM_THREADS) void k_beam_trace_rows(BeamTraceArgs a, const int32_t* __restrict__ status,
+                                                                  double* __restrict__ out, int32_t* __restrict__ offset) {
+    __shared__ int par_s[BEAM_THREADS];
+    __shared__ uint8_t val_s[BEAM_THREADS];
+    __shared__ int chain_s[BRIDGES_REC_K];
+    __shared__ double lin_s[BRIDGES_REC_K], stable_s[BRIDGES_REC_K], g_s[BRIDGES_REC_K];
+    __shared__ int part_s[BEAM_THREADS / WAVE];
+    __shared__ int len_s;
+    const int g = blockIdx.x, G = gridDim.x, t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
+    beam_trace_load(a, g, par_s, val_s);
+    // the rows of the groups in front of this one (of all groups, for the last: the total)
+    const int upto = g == G - 1 ? G : g;
+    int mine = 0, own = 0;
+    for (int j = t; j < upto; j += BEAM_THREADS) {
+        const int ed = a.end_depth[j];
+        const int n = (ed >= 0 && status[j] == 0) ? ed + 1 : 0;
+        if (j < g) mine += n; else own = n;
+    }
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) mine += __shfl_xor(mine, m);
+    if (lane == 0) part_s[wv] = mine;
+    __syncthreads();
+    if (t == 0) {
+        bool broken;
+        len_s = beam_trace_walk(a, g, par_s, val_s, chain_s, broken);
+    }
+    __syncthreads();
+    int off = 0;
+    for (int k = 0; k < BEAM_THREADS / WAVE; ++k) off += part_s[k];
+    const int L = len_s;
+    if (t == 0) offset[g] = off;
+    if (g == G - 1 && (G - 1) % BEAM_THREADS == t) offset[G] = off + own;       // (the lane that read the last group's count)
+    if (L == 0) return;
+    const int e0 = g * a.B;
+    constexpr int RW = BRIDGES_REC_WIDTH;
+    if (t < L) {
+        const double* r = a.rec + ((size_t)t * a.E + e0 + chain_s[t]) * RW;
+        lin_s[t] = r[BRIDGES_REC_LIN];
+        stable_s[t] = r[BRIDGES_REC_STABLE_S];
+    }
+    __syncthreads();
+    if (t < L) {                                            // the return of start t, by one lane, in the order of the fold
+        const int h = a.n_step < L - t ? a.n_step : L - t;
+        double acc = 0.0, disc = 1.0;
+        for (int k = 0; k < h; ++k) {
+            acc += disc * lin_s[t + k];
+            disc *= a.gamma;
+        }
+        g_s[t] = acc;
+    }
+    __syncthreads();
+    const int Wo = RW + a.n_tail + (a.n_step > 1 ? 1 : 0);
+    const uint64_t* tail = reinterpret_cast<const uint64_t*>(a.tail) + (size_t)a.end_env[g] * a.n_tail;   // (end_env lies in the group)
+    for (int s = wv; s < L; s += BEAM_THREADS / WAVE) {     // a wave per row, its lanes on consecutive doubles
+        const int h = a.n_step < L - s ? a.n_step : L - s;
+        const int last = s + h - 1;
+        const uint64_t* src = reinterpret_cast<const uint64_t*>(a.rec + ((size_t)last * a.E + e0 + chain_s[last]) * RW);
+        uint64_t* dst = reinterpret_cast<uint64_t*>(out + ((size_t)off + s) * Wo);
+        for (int col = lane; col < Wo; col += WAVE) {
+            uint64_t v;
+            if (col < RW) {
+                v = src[col];
+                if (col == BRIDGES_REC_STABLE_S) v = (uint64_t)__double_as_longlong(stable_s[s]);
+                if (col == BRIDGES_REC_TD) v = (uint64_t)__double_as_longlong(a.priority);
+                if (col == BRIDGES_REC_LIN && h > 1) v = (uint64_t)__double_as_longlong(g_s[s]);
+            } else if (col < RW + a.n_tail) {
+                v = tail[col - RW];
+            } else {
+                v = (uint64_t)__double_as_longlong((double)h);
+            }
+            dst[col] = v;
+        }
+    }
+}
+
 }  // namespace bridges

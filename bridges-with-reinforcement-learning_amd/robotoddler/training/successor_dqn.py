@@ -587,6 +587,7 @@ def build_parser():
     add_priority_arguments(p)
     add_exploration_arguments(p)
     add_hindsight_arguments(p)
+    add_search_arguments(p)
     add_eval_beam_argument(p)
     return p
 
@@ -799,6 +800,54 @@ def hindsight_from_args(args):
     return dict(hindsight=args['hindsight'], hindsight_goals=args.get('hindsight_goals', 1))
 
 
+def add_search_arguments(p):
+    """--search_every / --search_tasks / --search_width / --search_merge: shared with the tools that train through the vectorised
+    loop."""
+    p.add_argument("--search_every", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="With --num_envs N > 1: search in training -- every N-th lock-step a beam search with the policy net's q as "
+                        "the heuristic runs on the tasks the first --search_tasks rollout envs are playing, and the transitions of "
+                        "every task's best finished beam are pushed into the replay buffer behind the lock-step's own (as h-step "
+                        "rows with --n_step). The log gains search_rows, search_success_rate and search_lin_reward.")
+    p.add_argument("--search_tasks", type=int, default=argparse.SUPPRESS, metavar="M",
+                   help="With --search_every: tasks searched, those of rollout envs 0..M-1 (min(num_envs, 64); a fixed task: 1).")
+    p.add_argument("--search_width", type=int, default=argparse.SUPPRESS, metavar="B",
+                   help="With --search_every: width of the beam, 1..16 (8).")
+    p.add_argument("--search_merge", action="store_true", default=argparse.SUPPRESS,
+                   help="With --search_every: the search merges beams that hold the same structure (as --eval_beam_merge).")
+
+
+def check_search(args):
+    """--search_every and its companions: refused in words (SystemExit) where the loop cannot run them, before anything touches
+    the GPU."""
+    if 'search_every' not in args:
+        for k in ('search_tasks', 'search_width', 'search_merge'):
+            if k in args:
+                raise SystemExit(f"--{k} shapes the search in training: it needs --search_every N")
+        return
+    from bridges_hip import abi
+    if args['search_every'] < 1:
+        raise SystemExit("--search_every must be >= 1 (lock-steps between two searches)")
+    if args.get('num_envs', 1) <= 1:
+        raise SystemExit("--search_every needs the vectorised loop (--num_envs N, N > 1): the search forks lock-step envs on the device")
+    if not 1 <= args.get('search_width', 8) <= abi.BEAM_MAX_WIDTH:
+        raise SystemExit(f"--search_width must be 1..{abi.BEAM_MAX_WIDTH} (the widest beam bridges_beam_select orders)")
+    if 'search_tasks' in args and not 1 <= args['search_tasks'] <= args['num_envs']:
+        raise SystemExit(f"--search_tasks must be 1..--num_envs ({args['num_envs']}): the tasks are those of the first rollout envs")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--search_every runs on one rank only: the rows a search finds are not part of the all-gather")
+
+
+def search_from_args(args):
+    """The search arguments of VecDQN from parsed options; refuses what check_search refuses."""
+    check_search(args)
+    if 'search_every' not in args:
+        return {}
+    out = dict(search_every=args['search_every'], search_width=args.get('search_width', 8), search_merge=bool(args.get('search_merge')))
+    if 'search_tasks' in args:
+        out['search_tasks'] = args['search_tasks']
+    return out
+
+
 def add_curriculum_arguments(p):
     """--family_weights and --curriculum*: how a task family (--random_bridge_length / --random_tower_height) draws its classes;
     shared with the tools that take the family options."""
@@ -979,6 +1028,7 @@ def main(argv=None):
     check_priority(args)
     check_exploration(args)
     check_hindsight(args)
+    check_search(args)
     check_eval_beam(args)
     from bridges_hip import abi
     abi.require_gpu()

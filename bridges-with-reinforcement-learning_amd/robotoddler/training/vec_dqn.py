@@ -72,14 +72,15 @@ class TargetBatch(NamedTuple):
 
 class VecDQN:
     # an instance that __init__ has not filled (tests build such stand-ins with __new__) reads the loop as it was
-    exploration, n_step, rows_fed = "epsilon_greedy", 1, 0
-    hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = None
+    exploration, n_step, rows_fed, search_every = "epsilon_greedy", 1, 0, 0
+    hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = last_search = None
 
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
                  n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0,
-                 exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1):
+                 exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1,
+                 search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -144,7 +145,22 @@ class VecDQN:
         env's running episode on the device (records.HindsightBuffer); the relabelled rows follow the lock-step's own records
         into the ring, their number rides to the host with the lock-step's counts: no wait of its own.  The training step does
         not change.  It composes with per-env obstacles, task_channels, double_q, prioritised replay (a relabelled row carries
-        the priority of the transition it restates) and Boltzmann exploration.  None is the loop as it was: no launch of this."""
+        the priority of the transition it restates) and Boltzmann exploration.  None is the loop as it was: no launch of this.
+        ``search_every=N`` (N >= 1; one rank; an extension: search in training): every N-th lockstep(), after
+        the lock-step's own rows are pushed and before train_steps, a beam search of width ``search_width`` = B (1..16, default
+        8) with the policy net's q as the heuristic runs on the tasks the rollout envs 0 .. ``search_tasks`` - 1 (M, at most the
+        env's E; default min(E, 64)) are playing at that moment, in a search env of M * B envs the agent owns
+        (search_env_like), and the records of every task's best finished beam follow into the ring: one-step rows, or
+        n_step-step rows as the fold would have emitted them (beam_search(trace=True), bridges_beam_trace).  A row nobody has
+        scored carries ``search_priority`` in O_TD under prioritized=True (default 1.0; priority_refresh corrects it once the row
+        is drawn) and 0.0 otherwise, as the loop's own rows do.  ``search_merge=True`` merges equal structures in the search.  On
+        a fixed task (per_env_tasks=False) every group would find the same episode: M is forced to 1.  The search reads the nets
+        and the rollout env's tasks and writes the ring; the rollout env, the count images, the exploration stream, epsilon and
+        the temperature, the n-step windows, the hindsight buffer, the episode statistics, the curriculum, env_steps and
+        episodes_done stay as they are.  search_env_steps, search_rows and search_success_rate count what it did; last_search
+        holds the numbers of the lock-step that searched (None for one that did not).  0 is the loop as it was: no launch of
+        this."""
+        self._init_search(env, search_every, search_tasks, search_width, search_merge, search_priority, per_env_tasks, prioritized)
         self.exploration = str(exploration)
         if self.exploration not in ("epsilon_greedy", "boltzmann"):
             raise ValueError(f"VecDQN(exploration={exploration!r}): one of 'epsilon_greedy', 'boltzmann'")
@@ -292,9 +308,67 @@ class VecDQN:
         self.episode_stats = (EpisodeStats(env.E, env.K, gamma, env.n_targets, self.device, n_classes=self._n_classes(env))
                               if episode_stats else None)
         self._eval_state = {}                                # evaluate(): (random stream, EpisodeStats, count images) per env shape
+        self._trace_state = {}                               # beam_search(trace=True): the per-depth buffers per (E, K)
         # the curriculum keeps an accumulator of its own: whether and when the logging statistics above are taken is not its business
         self.curriculum = CurriculumRun(curriculum, env, gamma) if curriculum is not None else None
         self.curriculum_weights_host = None                  # pinned copy of the weights as of the last lock-step
+
+    def _init_search(self, env, every, tasks, width, merge, priority, per_env_tasks, prioritized):
+        """The conditions of search_every=N, decided from the arguments alone; the search env is built by the first search."""
+        self.search_every = int(every)
+        self.search_env = self.last_search = None
+        self.search_calls = 0                                # lockstep() calls since the last search: the phase, checkpointed
+        self.search_env_steps = self.search_rows = 0
+        self.search_success_rate = None
+        if self.search_every < 0:
+            raise ValueError(f"VecDQN(search_every={every!r}): a number of lock-steps, >= 0 (0: no search)")
+        if not self.search_every:
+            if tasks is not None or width is not None or merge or priority is not None:
+                raise ValueError("VecDQN(search_tasks=..., search_width=..., search_merge=..., search_priority=...) shape the search in "
+                                 "training: they need search_every=N")
+            return
+        if D.active():
+            raise ValueError("VecDQN(search_every=N) runs on one rank only: the rows a search finds are not part of the all-gather")
+        if not isinstance(env, VecAssemblyGym):
+            raise ValueError(f"VecDQN(search_every=N) needs a VecAssemblyGym rollout env; a {type(env).__name__} (env groups on streams "
+                             "of their own) is not what the fork of the search env serves")
+        self.search_width = 8 if width is None else int(width)
+        if not 1 <= self.search_width <= abi.BEAM_MAX_WIDTH:
+            raise ValueError(f"VecDQN(search_width={width!r}): 1..{abi.BEAM_MAX_WIDTH}")
+        self.search_tasks = min(env.E, 64) if tasks is None else int(tasks)
+        if not 1 <= self.search_tasks <= env.E:
+            raise ValueError(f"VecDQN(search_tasks={tasks!r}): the tasks are those of the rollout envs 0 .. M - 1, 1 <= M <= {env.E}")
+        if not per_env_tasks:
+            self.search_tasks = 1                            # one task: every group would find the same episode
+        self.search_merge = bool(merge)
+        if self.search_merge and env.K > abi.BEAM_MAX_SLOTS:
+            raise ValueError(f"VecDQN(search_merge=True): bridges_beam_merge orders at most {abi.BEAM_MAX_SLOTS} block slots per env, "
+                             f"the env has {env.K}")
+        if priority is not None and not prioritized:
+            raise ValueError("VecDQN(search_priority=...) is the priority of a row nobody has scored: it needs prioritized=True")
+        self.search_priority = (1.0 if priority is None else float(priority)) if prioritized else 0.0
+        if not self.search_priority >= 0.0:                  # (a NaN fails the comparison)
+            raise ValueError(f"VecDQN(search_priority={priority!r}): a priority, >= 0")
+
+    def _search(self):
+        """One search in training: the tasks of rollout envs 0 .. M - 1 as they stand, repeated B times, into the search env; a
+        traced beam search on it; the rows into the ring.  No host wait but the search's own."""
+        env, M, B = self.env, self.search_tasks, self.search_width
+        if self.search_env is None:
+            self.search_env = search_env_like(env, M, B)
+        senv = self.search_env
+        if self.per_env_tasks:
+            targets = env.env_targets[:M].repeat_interleave(B, dim=0)
+            if self.per_env_obstacles:
+                senv.load_task(targets, env.env_obstacles[:M].repeat_interleave(B, dim=0))
+            else:
+                senv.load_targets(targets)
+        res = self.beam_search(senv, B, merge=self.search_merge, trace=True, trace_n_step=self.n_step, trace_priority=self.search_priority)
+        self.ring.push(res["trace_rows"])
+        self.search_env_steps += senv.E * senv.K
+        self.search_rows += res["trace_count"]
+        self.search_success_rate = res["success_rate"]
+        self.last_search = dict(search_rows=res["trace_count"], search_success_rate=res["success_rate"], search_lin_reward=res["lin_reward"])
 
     @staticmethod
     def _n_classes(env):
@@ -683,7 +757,7 @@ class VecDQN:
 
     # ------------------------------------------------------------------ beam-search evaluation
     @torch.no_grad()
-    def beam_search(self, beam_env, width, merge=False, on_depth=None):
+    def beam_search(self, beam_env, width, merge=False, on_depth=None, trace=False, trace_n_step=1, trace_priority=0.0):
         """Beam search of width B = ``width`` over every task of ``beam_env`` (beam_env_like(eval_env, B): M * B envs, the B envs
         of a group share one task), the policy net's q as the heuristic: how much the learned Q is worth when the simulator is
         allowed to look ahead.  Per depth, for all groups at once and without a host decision: the candidate rows and their q
@@ -707,7 +781,18 @@ class VecDQN:
         success, reward, lin_reward, num_steps and final_reward, and merged_beams: per task the beams that merging closed over the
         search (zeros without merge); with merge also merged_by_depth and live_by_depth: per depth, over all tasks, the beams
         closed and the live beams the merge looked at.  On a beam env of a task family also success_by_class and episodes_by_class, indexed by the
-        class n = 0..hi of every task."""
+        class n = 0..hi of every task.
+        trace: the transition records of every task's best beam as rows a replay ring stores ("Search in
+        training").  Per depth the record of the step is taken with the two launches acting uses (R.pack_state after the fork
+        and before the step, R.pack_result after it) into slice d of a [K, E, RECORD_WIDTH] buffer kept per (E, K), beside the
+        depth's src and live & step_flags[0]; where ``best`` is updated, so are the env and depth its episode ended in; after the
+        last depth ONE bridges_beam_trace call walks every best beam back through the slots it occupied and writes its episode
+        as ``trace_n_step``-step rows (the record of the horizon's last step, the start's stable flag, the h-step return, the
+        task tail with_task joins on, and h when trace_n_step > 1) with ``trace_priority`` in O_TD.  The result gains trace_rows
+        (device, [trace_count, W_out]), trace_count (host: the sum of num_steps, from the read-back the search makes anyway),
+        trace_offset, trace_status and trace_end_env (device: row offsets per task, 1 where a chain was broken -- never, by
+        construction --, the env every task's best episode ended in).
+        Tracing adds no host wait.  trace=False launches nothing of it and returns what the search always returned."""
         B, env = int(width), beam_env
         if env is self.env:
             raise ValueError("beam_search() needs an env of its own: the training env's episodes would be cut short")
@@ -727,6 +812,17 @@ class VecDQN:
         if merge and K > abi.BEAM_MAX_SLOTS:
             raise ValueError(f"beam_search(merge=True): bridges_beam_merge orders at most {abi.BEAM_MAX_SLOTS} block slots per env, "
                              f"the beam env has {K}")
+        if trace:
+            if K > R.K:
+                raise ValueError(f"beam_search(trace=True): a record holds {R.K} block slots, the beam env has {K}")
+            if not 1 <= int(trace_n_step) <= abi.NSTEP_MAX:
+                raise ValueError(f"beam_search(trace_n_step={trace_n_step!r}): 1..{abi.NSTEP_MAX}")
+            tr_rec, tr_valid, tr_parent = self._trace_buffers(E, K)
+            # the task every record of a group is taken under: explicit arrays that no episode of a beam env redraws
+            tr_tail = None
+            if self.per_env_tasks:
+                tr_tail = (torch.cat([env.env_targets.reshape(E, -1), env.env_obstacles.reshape(E, -1)], dim=1)
+                           if self.per_env_obstacles else env.env_targets.reshape(E, -1))
         # per task and depth: the beams merging closed, then the live beams it looked at
         merged = torch.zeros((M, 2 * K), dtype=torch.int32, device=dev) if merge else None
         slots = torch.arange(E, device=dev) % B
@@ -739,6 +835,8 @@ class VecDQN:
         # per group: has, success, lin return, reward return, steps, final reward, then the beam's history
         best = torch.zeros((M, 6 + 6 * K), dtype=torch.float64, device=dev)
         one, ninf = torch.ones(M, dtype=torch.float64, device=dev), torch.full((), -float("inf"), dtype=torch.float64, device=dev)
+        if trace:                                            # per task: where the episode of ``best`` ended
+            end_env, end_depth = first.to(torch.int32), torch.full((M,), -1, dtype=torch.int32, device=dev)
         env.reset()
         for d in range(K):
             stable = self._stable_flags(env)
@@ -754,9 +852,16 @@ class VecDQN:
             live = sel["live"].bool()
             env.fork(sel["src"])
             env.needs_reset.masked_fill_(~live, 1)           # a closed slot places nothing: its lock-step is a reset
+            if trace:
+                # (sel_compact indexes the candidate arrays of BEFORE the fork; the fork's refresh has laid them out anew)
+                R.pack_state(env, env.cand_offset[:E].long() + sel["sel_index"].long(), out=tr_rec[d])
             env.step(sel["sel_index"])
             f = env.step_flags
             live &= f[:, 0].bool()
+            if trace:
+                R.pack_result(env, tr_rec[d])
+                tr_parent[d].copy_(sel["src"])
+                tr_valid[d].copy_(live)
             lin, rew = env.lin_reward.double(), env.reward.double()
             ret = torch.where(live, ret + disc * lin, ret)   # two roundings each, as the score of bridges_beam_select
             ret_r = torch.where(live, ret_r + disc * rew, ret_r)
@@ -773,6 +878,9 @@ class VecDQN:
                              hist[pick].reshape(M, -1)], dim=1)
             better = has_new & ((best[:, 0] == 0) | (new[:, 1] > best[:, 1]) | ((new[:, 1] == best[:, 1]) & (new[:, 2] > best[:, 2])))
             best = torch.where(better.unsqueeze(1), new, best)
+            if trace:
+                end_env = torch.where(better, pick.to(torch.int32), end_env)
+                end_depth = torch.where(better, d, end_depth)
             live = (live & ~fin).to(torch.uint8)
             if merge:                                        # beams that hold the same structure: the best return stays open
                 mg = ops.beam_merge(env.n_blocks, env.blk_shape, env.blk_pose, env.blk_occ, env.targets_left, B, live, ret, key_last=True)
@@ -780,6 +888,9 @@ class VecDQN:
                 live = mg["live"]
             if on_depth is not None:
                 on_depth(d, live)
+        if trace:                                            # (depths a search that broke off early left unwritten lie beyond every end)
+            tr = ops.beam_trace(tr_rec, tr_valid, tr_parent, end_env, end_depth, B, self.gamma, n_step=int(trace_n_step), tail=tr_tail,
+                                priority=float(trace_priority))
         # the one wait of the search (with merge: the merged counts ride along as further columns)
         host = (torch.cat([best, merged.double()], dim=1) if merge else best).cpu()
         if int(host[:, 0].sum()) != M:
@@ -800,6 +911,10 @@ class VecDQN:
             counts = host[:, 6 + 6 * K:].long()
             out.update(merged_beams=counts[:, :K].sum(dim=1).tolist(), merged_by_depth=counts[:, :K].sum(dim=0).tolist(),
                        live_by_depth=counts[:, K:].sum(dim=0).tolist())
+        if trace:
+            n_rows = sum(steps_h)
+            out.update(trace_rows=tr["rows"][:n_rows], trace_count=n_rows, trace_offset=tr["offset"], trace_status=tr["status"],
+                       trace_end_env=end_env)
         classes = getattr(env, "beam_task_class", None)
         if classes is not None:                              # the tasks of a family: per span / height n = 0..hi
             n_classes = env.beam_n_classes
@@ -807,6 +922,17 @@ class VecDQN:
             out["success_by_class"] = [sum(p) / len(p) if p else None for p in per]
             out["episodes_by_class"] = [len(p) for p in per]
         return out
+
+    def _trace_buffers(self, E, K):
+        """beam_search(trace=True): what a search keeps per depth -- records [K, E, RECORD_WIDTH], valid uint8 [K, E], parent
+        int32 [K, E] -- made once per (E, K) and kept, like _eval_state."""
+        kept = self.__dict__.setdefault("_trace_state", {})
+        st = kept.get((E, K))
+        if st is None:
+            st = kept[(E, K)] = (torch.zeros((K, E, R.RECORD_WIDTH), dtype=torch.float64, device=self.device),
+                                              torch.zeros((K, E), dtype=torch.uint8, device=self.device),
+                                              torch.zeros((K, E), dtype=torch.int32, device=self.device))
+        return st
 
     # ------------------------------------------------------------------ gradient steps on sampled batches
     def _make_replay_env(self, n_states):
@@ -1101,6 +1227,8 @@ class VecDQN:
             blob["priority_beta_calls"] = int(self.priority_beta_calls)
         if self.exploration == "boltzmann":                  # one more key: where the schedule stands
             blob["temperature"] = float(self.temperature)
+        if self.search_every:                                # one more key: the lock-steps since the last search
+            blob["search_phase"] = int(self.search_calls)
         if self.hindsight is not None:                       # two more keys: the setting and the running episodes
             blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
             blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
@@ -1147,6 +1275,8 @@ class VecDQN:
             self.priority_beta_calls = int(blob.get("priority_beta_calls", 0))
         if self.exploration == "boltzmann":                  # (a file of a run without the option: temp_start)
             self.temperature = float(blob.get("temperature", self.temp_start))
+        if self.search_every:                                # (a file of a run without the option: phase 0)
+            self.search_calls = int(blob.get("search_phase", 0)) % self.search_every
         return blob["counters"]
 
     # ------------------------------------------------------------------ driver
@@ -1235,6 +1365,12 @@ class VecDQN:
             self.episodes_done += int(((allrec[:, R.O_DONE] > 0.5) & (allrec[:, -1] == 1.0)).sum().item())
         else:
             self.episodes_done += int((allrec[:, R.O_DONE] > 0.5).sum().item())
+        if self.search_every:                           # search in training: every N-th lock-step, behind the rows pushed above
+            self.search_calls += 1
+            self.last_search = None
+            if self.search_calls >= self.search_every:
+                self.search_calls = 0
+                self._search()
         losses = self.train_steps(n_train_steps, defer=defer_losses)
         self.update_target()
         if boltzmann:                                   # (epsilon is left alone: nothing reads it in this mode)
@@ -1295,6 +1431,8 @@ def lockstep_log_values(info):
         vals.update(temperature=info['temperature'], explored_fraction=info.get('explored_fraction'))
     if 'hindsight_rows' in info:                             # hindsight relabelling only
         vals.update(hindsight_rows=info['hindsight_rows'])
+    if 'search_rows' in info:                                # search in training: the lock-steps that searched
+        vals.update({k: info[k] for k in ('search_rows', 'search_success_rate', 'search_lin_reward')})
     by_class = info.get('success_by_class')
     if by_class is not None:
         lo = info.get('class_lo', 0)
@@ -1326,6 +1464,37 @@ class _ShapeOf:
         self.geometry, self.target_faces_2d = geometry, list(target_faces_2d)
 
 
+def _env_like(ev, n_envs, targets, obstacles):
+    """A VecAssemblyGym of ``n_envs`` envs on the given task with the shapes, limits, options and seed of ``ev``."""
+    shapes = [_ShapeOf(g, faces) for g, faces in zip(ev.shapes, ev.shape_target_faces)]
+    return VecAssemblyGym(n_envs, shapes, obstacles, targets, max_steps=ev.max_steps or None, mu=ev.mu, density=ev.density,
+                          bounds=ev.bounds, xlim=ev.xlim, ylim=ev.ylim, x_discr_ground=ev.x_discr_ground, offset_values=ev.offset_values,
+                          seed=ev.seed, device=ev.device, f32_rasters=ev.f32_rasters, a_max=ev.a_max, img_size=(ev.img, ev.img),
+                          sparse_raster_update=ev.sparse_raster_update, candidate_snapshots=ev.candidate_snapshots,
+                          stable_actions_only=ev.stable_actions_only)
+
+
+def search_env_like(env, tasks, width):
+    """The env VecDQN's search in training runs on: tasks * width envs with the shapes, limits and options of the rollout env
+    ``env``, whose tasks are loaded before every search (load_targets / load_task: explicit per-env arrays that no episode
+    redraws, zeros until then; a task family goes in the same way, as the coordinates of the rollout envs' drawn classes).  A
+    fixed task is passed through."""
+    M, B = int(tasks), int(width)
+    if not 1 <= B <= abi.BEAM_MAX_WIDTH:
+        raise ValueError(f"search_env_like(width={width!r}): 1..{abi.BEAM_MAX_WIDTH}")
+    if not isinstance(env, VecAssemblyGym):
+        raise ValueError(f"search_env_like() takes a VecAssemblyGym; a {type(env).__name__} (env groups on streams of their own) "
+                         "cannot be forked across its groups")
+    if not 1 <= M <= env.E:
+        raise ValueError(f"search_env_like(tasks={tasks!r}): 1..{env.E}")
+    if env.per_env_tasks:
+        targets = torch.zeros((M * B, env.n_targets, 3), dtype=torch.float64)
+        obstacles = torch.zeros((M * B, env.n_obstacles, 3), dtype=torch.float64) if env.per_env_obstacles else list(env.obstacles)
+    else:
+        targets, obstacles = list(env.targets), list(env.obstacles)
+    return _env_like(env, M * B, targets, obstacles)
+
+
 def beam_env_like(eval_env, width):
     """The env VecDQN.beam_search runs on: M * width envs, M = eval_env.E, in which envs m * width .. (m + 1) * width - 1 hold the
     task evaluate() plays in env m of ``eval_env`` -- same shapes, limits, options and seed.  A fixed task is passed through.
@@ -1346,12 +1515,7 @@ def beam_env_like(eval_env, width):
         obstacles = ev.env_obstacles.repeat_interleave(B, dim=0) if ev.per_env_obstacles else list(ev.obstacles)
     else:
         targets, obstacles = list(ev.targets), list(ev.obstacles)
-    shapes = [_ShapeOf(g, faces) for g, faces in zip(ev.shapes, ev.shape_target_faces)]
-    env = VecAssemblyGym(ev.E * B, shapes, obstacles, targets, max_steps=ev.max_steps or None, mu=ev.mu, density=ev.density,
-                         bounds=ev.bounds, xlim=ev.xlim, ylim=ev.ylim, x_discr_ground=ev.x_discr_ground, offset_values=ev.offset_values,
-                         seed=ev.seed, device=ev.device, f32_rasters=ev.f32_rasters, a_max=ev.a_max, img_size=(ev.img, ev.img),
-                         sparse_raster_update=ev.sparse_raster_update, candidate_snapshots=ev.candidate_snapshots,
-                         stable_actions_only=ev.stable_actions_only)
+    env = _env_like(ev, ev.E * B, targets, obstacles)
     if ev.task_family is not None:
         env.beam_task_class, env.beam_n_classes = ev.task_class.tolist(), ev.task_family.n_classes
     return env
@@ -1364,7 +1528,8 @@ def next_multiple(n, every):
 
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
-    from robotoddler.training.successor_dqn import EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets, track_run_sinks
+    from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets,
+                                                    search_from_args, track_run_sinks)
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
@@ -1413,7 +1578,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
                    priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
                    priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args),
-                   **hindsight_from_args(args))
+                   **hindsight_from_args(args), **search_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -1506,6 +1671,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
             info.update(temperature=agent.temperature, explored_fraction=agent.explored_fraction)
         if agent.hindsight is not None:                      # the relabelled rows this lock-step pushed behind its own records
             info.update(hindsight_rows=agent.hindsight_rows)
+        if agent.last_search is not None:                    # search in training: a lock-step that searched
+            info.update(agent.last_search)
         if eval_envs > 0 and agent.episodes_done >= next_eval:
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)

@@ -741,6 +741,33 @@ int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32
 #define BRIDGES_NSTEP_MAX 8
 int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
                        double* acc, double* disc, double* stable_s, double* td, double* out, uint8_t* out_valid, void* stream);
+/* Beam search: the transition records of one finished beam per group, traced back through the slots it occupied (it stands here
+ * because its rows are the records above, in the h-step form of bridges_nstep_fold).  E = G * B envs, group g owns envs
+ * gB .. gB + B - 1 as for bridges_beam_select.  The search keeps per depth t < D and env e: rec [D, E, BRIDGES_REC_WIDTH] f64, the
+ * one-step record of the transition e made at depth t; valid [D, E] u8, whether it made one; parent [D, E] i32, the slot it was
+ * forked from (the src of that depth's bridges_beam_select; row 0 is never read).  Per group the caller names the end of one
+ * episode: end_env [G], end_depth [G] i32.
+ *   - end_depth[g] < 0: nothing ended; the group emits no rows, status[g] = 0.
+ *   - CHAIN: L = end_depth + 1, e_{L-1} = end_env[g], e_{t-1} = parent[t][e_t] for t = L-1 .. 1.
+ *   - BROKEN CHAIN: end_depth >= D, or some e_t outside [gB, gB + B), or some valid[t][e_t] == 0: no rows, status[g] = 1.  No
+ *     index outside the given arrays is ever read, whatever they hold.
+ *   - ROWS: an intact chain (status[g] = 0) emits L rows, one per start t = 0 .. L-1, ascending.  h = min(n_step, L - t),
+ *     last = t + h - 1.  The row is rec[last][e_last], all BRIDGES_REC_WIDTH columns copied as bits; then REC_STABLE_S is that of
+ *     rec[t][e_t], REC_TD is `priority`, and for h > 1 REC_LIN is the return  acc = 0, disc = 1; for k = 0 .. h-1:
+ *     acc += disc * lin_{t+k}; disc *= gamma  (binary64, in this order: steps 1-2 of bridges_nstep_fold; the same bits on every
+ *     call); for h == 1 the column keeps the record's own bits.  The n_tail doubles of tail[end_env[g]] follow (tail [E, n_tail],
+ *     or NULL with n_tail = 0; the envs of a group share one task), and with n_step > 1 h as a double in a last column:
+ *     out [G * D, W_out], W_out = BRIDGES_REC_WIDTH + n_tail + (n_step > 1).
+ *   - OFFSETS: offset [G + 1] i32, the exclusive prefix sum of the groups' row counts: group g's rows are out[offset[g] + t],
+ *     offset[G] is the total; rows of out at or beyond the total are not written.
+ * A child's block list extends its parent's, so the start state of a row is the first REC_NB - (h - 1) blocks of its block list,
+ * as for the rows of bridges_nstep_fold.  Two launches, one workgroup per group, no scratch, no atomics; every output word is
+ * written at most once; no output may alias an input.  1 <= B <= 16, 1 <= D <= BRIDGES_REC_K, 1 <= n_step <= BRIDGES_NSTEP_MAX.
+ * Refused (-1, nothing launched): E < 0, B, D or n_step outside those, E % B != 0, n_tail < 0, a NULL array (tail excepted when
+ * n_tail = 0), a misaligned pointer, a gamma that is not finite.  E == 0 returns 0 and launches nothing. */
+int bridges_beam_trace(int32_t E, int32_t B, int32_t D, int32_t n_step, int32_t n_tail, const double* rec, const uint8_t* valid,
+                       const int32_t* parent, const int32_t* end_env, const int32_t* end_depth, const double* tail, double gamma,
+                       double priority, double* out, int32_t* offset, int32_t* status, void* stream);
 /* The discounted sum of consecutive block rasters (the action part of an h-step successor-feature target): bits [n_rows, 64] u64,
  * per transition i a first row first[i] (i64) and a count h[i] (i32, 1..BRIDGES_NSTEP_MAX) ->
  *   sum [n, 64, 64] f32:  sum[i] = sum_{k < h[i]} d_k * image(bits[first[i] + k]),    disc [n] f32:  disc[i] = d_{h[i]},

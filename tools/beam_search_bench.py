@@ -15,8 +15,16 @@ HIP events around single calls (fork, select), the legs alternating, warm-up fir
 --syncs lists the host waits of one evaluate() and one beam_search() call instead (tools/find_syncs.py's counting, plus explicit
 stream / event / device synchronisations): per depth the search must wait only where acting waits
 (with --merge: of the search with and without merging -- merging must add none).
+--trace times the tracing of the best beams' records instead:
+  trace     ops.beam_trace (bridges_beam_trace: two launches) alone at --groups groups of --width beams and --max_steps depths,
+            n_step 1 and 3, against a torch formulation of the same rows -- a [E, K, W] path buffer gathered by the depth's parents
+            at every depth, the episodes picked and cut to their lengths by a masked select --, HIP events around single calls that
+            write into given outputs, the legs alternating
+  search    one VecDQN.beam_search(--width) call without and with trace=True on the same --tasks held-out tasks, alternating
+(--trace --syncs: the host waits of both searches -- tracing must add none).
     python tools/beam_search_bench.py [--fork_envs 512 4096] [--groups 64 512] [--width 8] [--tasks 64] [--widths 1 4 8] [--syncs]
-    python tools/beam_search_bench.py --merge [--tasks 64] [--width 8] [--syncs]"""
+    python tools/beam_search_bench.py --merge [--tasks 64] [--width 8] [--syncs]
+    python tools/beam_search_bench.py --trace [--groups 64 512] [--tasks 64] [--width 8] [--syncs]"""
 import argparse, ctypes as C, json, os, sys, time, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -41,7 +49,9 @@ ap.add_argument("--search_reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--syncs", action="store_true")
 ap.add_argument("--merge", action="store_true", help="time bridges_beam_merge and a search with / without merging at --tasks x --width")
+ap.add_argument("--trace", action="store_true", help="time bridges_beam_trace and a search with / without tracing at --tasks x --width")
 a = ap.parse_args()
+assert not (a.merge and a.trace), "--merge and --trace are two modes"
 assert a.reps >= 20 and a.search_reps >= 5
 dev = torch.device("cuda:0")
 HBM_PEAK = 8.0e12                                             # bytes / s, the card's specification
@@ -113,7 +123,7 @@ def waits(fn):
 
 
 # ---- fork ---------------------------------------------------------------------------------------------------------------------
-for E in ([] if a.syncs or a.merge else a.fork_envs):
+for E in ([] if a.syncs or a.merge or a.trace else a.fork_envs):
     env = tower_env(E)
     for _ in range(4):
         env.select_random()
@@ -142,7 +152,7 @@ for E in ([] if a.syncs or a.merge else a.fork_envs):
     del env, arrays, scratch
 
 # ---- select -------------------------------------------------------------------------------------------------------------------
-for G in ([] if a.syncs or a.merge else a.groups):
+for G in ([] if a.syncs or a.merge or a.trace else a.groups):
     B = a.width
     E = G * B
     g = torch.Generator().manual_seed(G)
@@ -212,6 +222,64 @@ if a.merge and not a.syncs:
     print(json.dumps(dict(part="merge", groups=G, width=B, slots=K, live=int(live.sum()), closed=int(out["n_merged"].sum()), **s,
                           note="HIP events around single calls (host launch gap included), after warm-up")), flush=True)
 
+# ---- trace --------------------------------------------------------------------------------------------------------------------
+for G, n_step in ([(G, n) for G in a.groups for n in (1, 3)] if a.trace and not a.syncs else []):
+    from robotoddler.training import records as R
+    B, D, W, n_tail, gamma, priority = a.width, a.max_steps, R.RECORD_WIDTH, 9, 0.95, 1.0
+    E = G * B
+    g = torch.Generator().manual_seed(G + n_step)
+    rec = torch.randn((D, E, W), generator=g, dtype=torch.float64).to(dev)
+    valid = torch.ones((D, E), dtype=torch.uint8, device=dev)
+    # every depth permutes the slots of every group
+    parent = (torch.rand((D, G, B), generator=g).argsort(dim=2) + torch.arange(G)[None, :, None] * B).reshape(D, E).to(torch.int32).to(dev)
+    end_depth = torch.where(torch.rand(G, generator=g) < 0.1, -1, torch.randint(0, D, (G,), generator=g)).to(torch.int32).to(dev)
+    end_env = (torch.arange(G) * B + torch.randint(0, B, (G,), generator=g)).to(torch.int32).to(dev)
+    tail = torch.randn((E, n_tail), generator=g, dtype=torch.float64).to(dev)
+    out = ops.beam_trace(rec, valid, parent, end_env, end_depth, B, gamma, n_step=n_step, tail=tail, priority=priority)
+    parent_l, end_env_l, L = parent.long(), end_env.long(), (end_depth + 1).long()
+    steps = torch.arange(D, device=dev)
+    ends_at = (end_depth[None] == steps[:, None])[:, :, None, None]        # [D, G, 1, 1]
+
+    def trace_op():
+        return ops.beam_trace(rec, valid, parent, end_env, end_depth, B, gamma, n_step=n_step, tail=tail, priority=priority,
+                              out=out["rows"], offset=out["offset"], status=out["status"])
+
+    def formulation():
+        path = torch.zeros((E, D, W), dtype=torch.float64, device=dev)
+        for d in range(D):                                   # what the search would do per depth: the history follows the fork
+            if d:
+                path = path[parent_l[d]]
+            path[:, d] = rec[d]
+            # ... and the group's best episode is kept where it ends (the slot is forked over at the next depth)
+            ep = torch.where(ends_at[d], path[end_env_l], ep) if d else path[end_env_l]
+        task = tail[end_env_l][:, None].expand(-1, D, -1)
+        if n_step > 1:
+            h = torch.minimum(torch.full((), n_step, device=dev), L[:, None] - steps[None]).clamp(min=1)
+            last = (steps[None] + h - 1).clamp(max=D - 1)
+            rows = torch.gather(ep, 1, last[..., None].expand(-1, -1, W)).clone()
+            rows[..., R.O_STABLE_S] = ep[..., R.O_STABLE_S]
+            lin = torch.nn.functional.pad(ep[..., R.O_LIN], (0, n_step - 1))
+            acc, disc = torch.zeros_like(ep[..., 0]), 1.0
+            for k in range(n_step):
+                acc = acc + torch.where(k < h, disc * lin[:, k:k + D], 0.0)
+                disc *= gamma
+            rows[..., R.O_LIN] = torch.where(h > 1, acc, rows[..., R.O_LIN])
+            rows = torch.cat([rows, task, h.double()[..., None]], dim=2)
+        else:
+            rows = torch.cat([ep, task], dim=2)
+        rows[..., R.O_TD] = priority
+        return rows[steps[None] < L[:, None]]                # the masked select: the one host wait of the formulation
+    f = formulation()
+    torch.cuda.synchronize()
+    n = int(out["offset"][-1])
+    assert f.shape[0] == n and int(out["status"].sum()) == 0
+    assert torch.equal(out["rows"][:n], f) if n_step == 1 else torch.allclose(out["rows"][:n], f, rtol=1e-12, atol=1e-12)
+    s = alternate((("trace", trace_op), ("torch", formulation)), a.reps, a.warmup)
+    print(json.dumps(dict(part="trace", groups=G, width=B, depths=D, n_step=n_step, n_tail=n_tail, rows=n, bytes_written=n * out["rows"].shape[1] * 8,
+                          **s, torch_over_trace=s["torch"]["median_us"] / s["trace"]["median_us"],
+                          note="HIP events around single calls (host launch gaps included), legs alternating; the torch leg ends in a "
+                               "masked select, which waits for the device")), flush=True)
+
 # ---- search -------------------------------------------------------------------------------------------------------------------
 if a.tasks > 0:
     args = vars(build_parser().parse_args(["--model", "SuccessorMLP"]))
@@ -222,10 +290,13 @@ if a.tasks > 0:
     agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), mk(256, 0), 20000, 32, 0.95, 0.01,
                    "mse_q_values+mse_block_features", per_env_tasks=True)
     eval_env = mk(a.tasks, 1)
-    beams = {B: beam_env_like(eval_env, B) for B in ([a.width] if a.merge else a.widths)}
+    beams = {B: beam_env_like(eval_env, B) for B in ([a.width] if a.merge or a.trace else a.widths)}
     legs = [("evaluate", lambda: agent.evaluate(eval_env))] + [(f"beam_{B}", (lambda B=B: agent.beam_search(beams[B], B))) for B in beams]
     if a.merge:
         legs.append((f"beam_{a.width}_merge", lambda: agent.beam_search(beams[a.width], a.width, merge=True)))
+    if a.trace:
+        legs.append((f"beam_{a.width}_trace", lambda: agent.beam_search(beams[a.width], a.width, trace=True)))
+        legs.append((f"beam_{a.width}_trace3", lambda: agent.beam_search(beams[a.width], a.width, trace=True, trace_n_step=3)))
     if a.syncs:
         for name, fn in legs:
             fn()
@@ -235,7 +306,7 @@ if a.tasks > 0:
                   flush=True)
     else:
         s = alternate(legs, a.search_reps, 2, wall=True)
-        res = {name: fn() for name, fn in legs}
+        res = {name: {k: v for k, v in fn().items() if not torch.is_tensor(v)} for name, fn in legs}
         print(json.dumps(dict(part="search", tasks=a.tasks, max_steps=a.max_steps, **s,
                               over_evaluate={name: s[name]["median_us"] / s["evaluate"]["median_us"] for name, _ in legs[1:]},
                               success_rate={name: r["success_rate"] for name, r in res.items()},
@@ -243,4 +314,7 @@ if a.tasks > 0:
                               merged_beams={name: sum(r["merged_beams"]) for name, r in res.items() if "merged_beams" in r},
                               **(dict(merge_minus_plain_us=s[f"beam_{a.width}_merge"]["median_us"] - s[f"beam_{a.width}"]["median_us"])
                                  if a.merge else {}),
+                              **(dict(trace_minus_plain_us=s[f"beam_{a.width}_trace"]["median_us"] - s[f"beam_{a.width}"]["median_us"],
+                                      plain_spread_us=s[f"beam_{a.width}"]["max_us"] - s[f"beam_{a.width}"]["min_us"],
+                                      trace_rows=res[f"beam_{a.width}_trace"]["trace_count"]) if a.trace else {}),
                               note="wall clock around whole calls on an UNTRAINED net (cost only), legs alternating")), flush=True)

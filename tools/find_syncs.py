@@ -31,7 +31,7 @@ from bridges_hip.vec_env import RandomBridges, RandomTargets, VecAssemblyGym
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
-                                                add_hindsight_arguments, hindsight_from_args)
+                                                add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 add_curriculum_arguments(ap)
 add_n_step_argument(ap)
@@ -39,6 +39,7 @@ add_double_q_argument(ap)
 add_priority_arguments(ap, prioritized_flag=True)
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
+add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
 a = ap.parse_args()
 sizes = tuple(int(v) for v in a.random_bridge_length.split(":")) if a.random_bridge_length else None
 check_curriculum(vars(a), sizes)
@@ -57,7 +58,8 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, ta
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
                "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes or a.random_targets), per_env_obstacles=bool(sizes),
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)))
+               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
+               **search_from_args(dict(vars(a), num_envs=a.envs)))
 
 
 def lockstep():

@@ -21,7 +21,8 @@ import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
-                                                add_hindsight_arguments, hindsight_from_args, add_eval_beam_argument)
+                                                add_hindsight_arguments, hindsight_from_args, add_eval_beam_argument, add_search_arguments,
+                                                search_from_args)
 from robotoddler.training.vec_dqn import VecDQN, beam_env_like, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
@@ -59,6 +60,7 @@ add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--pr
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_eval_beam_argument(ap)               # --eval_beam B: beam search of width B on the evaluation tasks (VecDQN.beam_search)
+add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
 a = ap.parse_args()
 eval_beam = vars(a).get("eval_beam")
 if eval_beam is not None and not (1 <= eval_beam <= 16 and a.eval_envs > 0):
@@ -99,7 +101,8 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True)
                eps_decay=0.997, stable_actions_only=a.stable_actions_only, episode_stats=True, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)))
+               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
+               **search_from_args(dict(vars(a), num_envs=a.envs)))
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
@@ -127,9 +130,11 @@ def evaluate_with_first_q(agent, eval_env, epsilon):
 
 
 t0 = time.time()
-deferred = []
+deferred, searches = [], []
 for it in range(1, a.locksteps + 1):
     deferred.append(agent.lockstep(a.train_steps, defer_losses=True)[0])
+    if agent.last_search is not None:                           # search in training: the lock-steps of the block that searched
+        searches.append(agent.last_search)
     if it % a.block == 0:
         ep = agent.episode_stats.take().get()                   # the episodes that ended in the block: one read per block
         losses = [l for d in deferred for l in d.get()]
@@ -141,6 +146,11 @@ for it in range(1, a.locksteps + 1):
             line.update(temperature=round(agent.temperature, 4), explored_fraction=r4(agent.explored_fraction))
         if agent.hindsight is not None:                         # the block's last lock-step: the relabelled rows it pushed
             line.update(hindsight_rows=agent.hindsight_rows)
+        if agent.search_every:                                  # means over the block's searches, and the rows they pushed
+            line.update(searches=len(searches), search_rows=sum(s["search_rows"] for s in searches),
+                        search_success_rate=r4(float(np.mean([s["search_success_rate"] for s in searches])) if searches else None),
+                        search_lin_reward=r4(float(np.mean([s["search_lin_reward"] for s in searches])) if searches else None))
+            searches = []
         if family:                                              # success per span / height n = LO..HI, and the episodes behind it
             line.update(success_by_class={n: r4(c["success_rate"]) for n, c in enumerate(ep["by_class"]) if n >= family[1]},
                         episodes_by_class={n: c["episodes"] for n, c in enumerate(ep["by_class"]) if n >= family[1]})

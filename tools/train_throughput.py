@@ -8,7 +8,7 @@ import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
-                                                add_hindsight_arguments, hindsight_from_args)
+                                                add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
 from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
@@ -58,6 +58,7 @@ add_double_q_argument(ap)                # --double_q: double Q-learning targets
 add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
+add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -113,7 +114,8 @@ agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_a
                episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)))
+               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
+               **search_from_args(dict(vars(a), num_envs=a.envs)))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False
@@ -125,9 +127,14 @@ agent._rows_seen_dev, agent.rows_fed = None, 0
 torch.cuda.synchronize(); s0 = agent.env_steps; t0 = time.perf_counter()
 pending, per_step, tp = None, [], t0
 hindsight_rows = 0
+searched, search_rows, search_success = [], 0, []
 for _ in range(a.locksteps):
     deferred, _rec = agent.lockstep(a.train_steps, defer_losses=True)
     hindsight_rows += agent.hindsight_rows
+    searched.append(agent.last_search is not None)
+    if agent.last_search is not None:
+        search_rows += agent.last_search["search_rows"]
+        search_success.append(agent.last_search["search_success_rate"])
     stats = agent.episode_stats.take() if agent.episode_stats is not None else None
     if pending is not None:
         pending[0].get()
@@ -140,6 +147,10 @@ torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 steps_done = agent.env_steps - s0
 rows_seen, rows_fed = getattr(agent, "rows_seen", 0), getattr(agent, "rows_fed", 0)
+# search in training: the host time of the lock-steps that searched beside that of the others (medians)
+_med = lambda v: sorted(v)[len(v) // 2] * 1e3 if v else None
+ms_searching = _med([t for t, s in zip(per_step, searched) if s])
+ms_not_searching = _med([t for t, s in zip(per_step, searched) if not s])
 per_step.sort()
 median = per_step[len(per_step) // 2]
 # 2) the same lock-steps with a device synchronisation between the phases, for the per-phase times only
@@ -180,5 +191,8 @@ print(json.dumps(dict(config=vars(a), family_weights=env.family_weights.tolist()
                       ms_act=t_act / n_phase * 1e3, ms_targets=t_targets[0] / n_phase * 1e3, ms_train=t_train / n_phase * 1e3,
                       ms_per_train_step=(t_train - t_targets[0]) / n_phase / a.train_steps * 1e3, last_loss=losses[-1] if losses else None,
                       hindsight_rows_per_lockstep=(hindsight_rows / a.locksteps) if agent.hindsight is not None else None,
+                      searches=sum(searched), ms_median_lockstep_searching=ms_searching, ms_median_lockstep_not_searching=ms_not_searching,
+                      search_rows_per_search=(search_rows / sum(searched)) if sum(searched) else None,
+                      search_success_rates=search_success if agent.search_every else None,
                       note="env_steps_per_s: pipelined loop (VecDQN.lockstep, deferred loss readback); ms_act / ms_targets / "
                            "ms_train: separate pass with a device synchronisation between the phases (they overlap in the loop)")))

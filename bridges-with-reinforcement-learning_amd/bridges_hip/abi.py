@@ -329,6 +329,7 @@ SIGNATURES = {
     "bridges_td_target": [i32, vp, vp, vp, vp, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp],
     "bridges_td_target_rows": [i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_td_target_select": [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp],
+    "bridges_soft_expect": [i32, vp, vp, vp, vp, f32, vp, i64, vp, i32, vp, vp, vp, vp, vp],
     "bridges_nstep_fold": [i32, i32, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_discounted_sum": [i32, vp, i64, vp, vp, f32, vp, vp, vp],
     "bridges_priority_sample_scratch": [i64, C.POINTER(i64)],

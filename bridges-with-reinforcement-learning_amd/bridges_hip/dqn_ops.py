@@ -73,7 +73,45 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
     return q_target, sf_target, argmax_row
 
 
-def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None, select_q=None):
+def soft_expect(seg_offset, select_q, next_q, temperature, feat=None, feat_row=None, want_entropy=True):
+    """The expectation of next_q and of a feature row under the Boltzmann policy of select_q at ``temperature``, per segment
+    (bridges_soft_expect; the rule stands in include/bridges_hip.h).  seg_offset as td_target takes it; select_q, next_q f32 [R],
+    contiguous (the same tensor: the plain target); feat f32 [F, D] whose rows are contiguous (the row stride may exceed D);
+    feat_row int64 [R]: the row of feat that stands for row j (None: row j itself).
+    -> (value f32 [B], feat_mean f32 [B, D] or None, entropy f32 [B] or None, argmax_row int32 [B])."""
+    L = abi.require_gpu()
+    dev = next_q.device
+    for t in (select_q, next_q):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+    assert select_q.numel() == next_q.numel()
+    if isinstance(seg_offset, (tuple, list)):
+        seg_lo, seg_hi = (t.to(device=dev, dtype=torch.int32).contiguous() for t in seg_offset)
+        B = seg_lo.numel()
+        assert seg_hi.numel() == B
+    else:
+        seg_offset = seg_offset.to(device=dev, dtype=torch.int32).contiguous()
+        B = seg_offset.numel() - 1
+        seg_lo, seg_hi = seg_offset[:B], seg_offset[1:]
+    value = torch.empty(B, dtype=torch.float32, device=dev)
+    argmax_row = torch.empty(B, dtype=torch.int32, device=dev)
+    entropy = torch.empty(B, dtype=torch.float32, device=dev) if want_entropy else None
+    dim, stride, feat_mean = 0, 0, None
+    if feat is not None:
+        assert feat.dtype == torch.float32 and feat.dim() == 2 and feat.device == dev and (feat.shape[1] <= 1 or feat.stride(1) == 1)
+        dim, stride = int(feat.shape[1]), int(feat.stride(0))
+        feat_mean = torch.empty((B, dim), dtype=torch.float32, device=dev)
+        if feat_row is not None:
+            assert feat_row.dtype == torch.int64 and feat_row.is_contiguous() and feat_row.numel() == next_q.numel()
+        else:
+            assert feat.shape[0] >= next_q.numel()
+    abi.check(L.bridges_soft_expect(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(select_q), _ptr(next_q), float(temperature), _ptr(feat), stride,
+                                    _ptr(feat_row if feat is not None else None), dim, _ptr(value), _ptr(feat_mean), _ptr(entropy),
+                                    _ptr(argmax_row), _stream()), "bridges_soft_expect")
+    return value, feat_mean, entropy, argmax_row
+
+
+def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None, select_q=None,
+                 temperature=None, next_feat=None, feat_row=None, feat_head=None, stats=None):
     """The TD targets of transitions whose next-state rows are the segments ``seg`` of ``next_q`` (td_target's seg_offset).
     -> (q [B], sf [B, D] or None).  With ``lin``: q = lin + gamma q' of each segment's arg-max row, sf = lin + gamma psi' of
     that row + the action raster.  lin=None is the single-env reference form: q is the done-masked q' of the arg-max row (lin 0,
@@ -82,7 +120,28 @@ def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin
     ``discount`` f32 [B] (with ``lin``): a discount per transition in place of gamma, in both targets (td_target's).
     ``select_q`` f32 [R] (with ``lin``): double Q-learning -- the arg-max row of a segment is select_q's first maximum, the values
     are next_q's and next_sf's at that row (td_target's).  It goes to the call that finds the rows; the second call of the
-    callable-next_sf form has one row per segment and nothing to select (with psi' of every row it selects again)."""
+    callable-next_sf form has one row per segment and nothing to select (with psi' of every row it selects again).
+    ``temperature`` T (with ``lin``): expected-value targets under the Boltzmann policy of select_q (next_q when select_q is
+    None) at T, in two launches.  Stage one is soft_expect over the segments: value = sum_j p_j q'_j and, with ``next_feat``
+    f32 [F, D] (and ``feat_row``, soft_expect's), the p-weighted mean of the feature rows; ``feat_head`` maps that mean [B, D] to
+    the expected psi' [B, sf_dim] (None: the mean is the expected psi').  Stage two is bridges_td_target_select on one-row
+    segments, value standing in for next_q and the expected psi' for next_sf: q = lin + d * (done ? 0 : value), sf =
+    action_raster + d * (done ? 0 : expected psi'), so done, discount, gamma and the -inf marking of an empty segment that is
+    not done are that kernel's.  next_sf is not used then.  ``stats`` (a dict) receives stage one's value, entropy and
+    argmax_row.  temperature=None: every line below the block is the path as it was."""
+    if temperature is not None:
+        if lin is None:
+            raise ValueError("next_targets(temperature=...) is the vectorised form: it needs lin")
+        nq = next_q.contiguous().float()
+        sel = nq if select_q is None else select_q.contiguous().float()
+        value, mean, entropy, arg = soft_expect(seg, sel, nq, temperature, feat=next_feat, feat_row=feat_row)
+        if stats is not None:
+            stats.update(value=value, entropy=entropy, argmax_row=arg, feat_mean=mean)
+        sf_soft = None if mean is None else (feat_head(mean) if feat_head is not None else mean)
+        one = torch.arange(done.numel() + 1, dtype=torch.int32, device=nq.device)
+        q, sf, _ = td_target(one, value, lin, done, gamma, next_sf=sf_soft, action_raster=action_raster, discount=discount,
+                             select_q=value)
+        return q, sf
     nq = next_q.contiguous().float()
     zeros = torch.zeros(done.numel(), dtype=torch.float32, device=nq.device) if lin is None else lin
     if discount is not None and lin is None:

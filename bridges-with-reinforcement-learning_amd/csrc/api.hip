@@ -16,6 +16,7 @@
 #include "hindsight_kernels.hip"
 #include "fork_kernels.hip"
 #include "beam_kernels.hip"
+#include "soft_target_kernels.hip"
 
 using namespace bridges;
 
@@ -796,6 +797,24 @@ int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32
     // (sf rows that are not 16-byte aligned, or an sf_dim that is no multiple of 4, take the kernel's element-wise epilogue)
     return td_target_launch(n_trans, seg_lo, seg_hi, select_q, next_q, next_sf, next_sf_row_stride, action_raster, lin_reward, done,
                             discount, gamma, sf_dim, q_target, sf_target, argmax_row, stream);
+}
+
+int bridges_soft_expect(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                        float temperature, const float* feat, int64_t feat_row_stride, const int64_t* feat_row, int32_t dim,
+                        float* value, float* feat_mean, float* entropy, int32_t* argmax_row, void* stream) {
+    if (n_trans < 0 || dim < 0) return fail_arg("bridges_soft_expect: negative count");
+    if (!(temperature > 0.f && temperature < INFINITY))                           // (a NaN fails the comparison)
+        return fail_arg("bridges_soft_expect: the temperature must be finite and > 0");
+    if (feat_row_stride < 0) return fail_arg("bridges_soft_expect: negative row stride");
+    if (!aligned(4, seg_lo, seg_hi, argmax_row) || !aligned(4, select_q, next_q, feat, value, feat_mean, entropy) || !aligned(8, feat_row))
+        return fail_arg("bridges_soft_expect: misaligned pointer");
+    if (n_trans == 0) return BRIDGES_OK;
+    if (!seg_lo || !seg_hi || !select_q || !next_q || !value || !argmax_row) return fail_arg("bridges_soft_expect: null pointer");
+    if (dim > 0 && (!feat || !feat_mean)) return fail_arg("bridges_soft_expect: dim > 0 needs feat and feat_mean");
+    // one workgroup per (transition, tile of SOFT_TILE columns); dim == 0 still needs tile 0 for value / entropy / argmax_row
+    const unsigned tiles = dim > 0 ? (unsigned)ceil_div(dim, SOFT_TILE) : 1u;
+    return launch("k_soft_expect", k_soft_expect, dim3((unsigned)n_trans, tiles), dim3(256), 0, stream, n_trans, seg_lo, seg_hi,
+                  select_q, next_q, temperature, feat, feat_row_stride, feat_row, (int)dim, value, feat_mean, entropy, argmax_row);
 }
 
 int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,

@@ -584,6 +584,7 @@ def build_parser():
     add_curriculum_arguments(p)
     add_n_step_argument(p)
     add_double_q_argument(p)
+    add_target_temperature_argument(p)
     add_priority_arguments(p)
     add_exploration_arguments(p)
     add_hindsight_arguments(p)
@@ -730,6 +731,33 @@ def check_double_q(args):
     if args.get('double_q') and args['num_envs'] <= 1:
         raise SystemExit("--double_q needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
                          "reference's target, where the target net both chooses and values the next action")
+
+
+def add_target_temperature_argument(p):
+    """--target_temperature: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--target_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
+                   help="Vectorised loop: expected-value targets under the Boltzmann policy at temperature T (finite, > 0) -- the "
+                        "bootstrap is sum_a' pi(a'|s') q'(s', a') with pi ~ exp(q' / T) instead of max_a' q'(s', a'), and the "
+                        "successor-feature target takes the same expectation of the features (with --double_q the policy net's "
+                        "q weighs the actions). T is constant; it is not the exploration temperature. Logs target_entropy and "
+                        "soft_value_gap. Composes with --n_step, --double_q and --prioritized_replay.")
+
+
+def check_target_temperature(args):
+    """--target_temperature T: refused in words (SystemExit) where the loop cannot run it, before anything touches the GPU."""
+    T = args.get('target_temperature')
+    if T is None:
+        return
+    if not (0.0 < T < float("inf")):                         # (a NaN fails the comparison)
+        raise SystemExit(f"--target_temperature must be a finite number > 0, got {T}")
+    if args['num_envs'] <= 1:
+        raise SystemExit("--target_temperature needs the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
+                         "reference's target, the maximum over the next actions")
+
+
+def target_temperature_from_args(args):
+    """--target_temperature T -> VecDQN's keyword, nothing without the flag."""
+    return dict(target_temperature=args['target_temperature']) if args.get('target_temperature') is not None else {}
 
 
 def add_eval_beam_argument(p):
@@ -1025,6 +1053,7 @@ def main(argv=None):
     check_random_targets(args)
     check_n_step(args)
     check_double_q(args)
+    check_target_temperature(args)
     check_priority(args)
     check_exploration(args)
     check_hindsight(args)

@@ -74,13 +74,15 @@ class VecDQN:
     # an instance that __init__ has not filled (tests build such stand-ins with __new__) reads the loop as it was
     exploration, n_step, rows_fed, search_every = "epsilon_greedy", 1, 0, 0
     hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = last_search = None
+    target_temperature = _soft_stats = target_entropy = soft_value_gap = None
 
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
                  episode_stats=False, per_env_tasks=False, per_env_obstacles=False, task_channels=False, curriculum=None,
                  n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0,
                  exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1,
-                 search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None):
+                 search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None,
+                 target_temperature=None):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -159,7 +161,27 @@ class VecDQN:
         the temperature, the n-step windows, the hindsight buffer, the episode statistics, the curriculum, env_steps and
         episodes_done stay as they are.  search_env_steps, search_rows and search_success_rate count what it did; last_search
         holds the numbers of the lock-step that searched (None for one that did not).  0 is the loop as it was: no launch of
-        this."""
+        this.
+        ``target_temperature=T`` (a finite number > 0; an extension: the Boltzmann softmax backup, Expected SARSA for the policy
+        Boltzmann exploration draws from; DESIGN.md section 7, "Soft targets"): the bootstrap of every target is the expectation
+        under pi(a'|s') ~ exp(q'(s', a') / T) over the next state's candidates instead of the maximum -- q = G + gamma^h sum_a'
+        pi(a') q'(s', a'), and the successor-feature target takes sum_a' pi(a') psi'(s', a') (bridges_soft_expect, then the
+        existing target kernel on one-row segments).  The factored SuccessorMLP runs its middle layers over ALL next-state rows
+        and applies the linear psi' head to the pi-weighted mean of the last hidden rows; the other nets average channel 0 of
+        their distinct rows' outputs.  double_q=True: the policy net's q weighs the rows, values and features stay the target
+        net's.  It composes with n_step, prioritised replay (refresh, weights), per-env tasks and obstacles, task_channels,
+        stable_actions_only and several ranks (every rank forms its own targets, as ever).  The rollout's td_errors stay the
+        max-operator error, evaluation and beam search stay greedy, T is constant.  target_entropy and soft_value_gap hold the
+        last train_steps call's means over the transitions that are not done (they ride to the host with the losses).  None is
+        the loop as it was: no launch of this."""
+        if target_temperature is not None:
+            ok = isinstance(target_temperature, (int, float)) and not isinstance(target_temperature, bool)
+            if not ok or not (0.0 < float(target_temperature) < float("inf")):       # (a NaN fails the comparison)
+                raise ValueError(f"VecDQN(target_temperature={target_temperature!r}): a finite number > 0 (None: the max-operator target)")
+            target_temperature = float(target_temperature)
+        self.target_temperature = target_temperature
+        self._soft_stats = None                              # [2] on the device: what the last _targets call left for the log
+        self.target_entropy = self.soft_value_gap = None
         self._init_search(env, search_every, search_tasks, search_width, search_merge, search_priority, per_env_tasks, prioritized)
         self.exploration = str(exploration)
         if self.exploration not in ("epsilon_greedy", "boltzmann"):
@@ -973,6 +995,9 @@ class VecDQN:
         rasteriser filters every next state's candidates against its transition's own obstacles.
         task_channels: the target net's rows come from _row_features on the scratch env (one ops.conv_input per chunk) and no
         f32 image of a transition is built.
+        target_temperature: the bootstrap is the expectation under the Boltzmann policy of the rows' q (double_q: of the policy
+        net's q) instead of the arg-max row's -- bridges_soft_expect over the segments, then the target kernel on one-row
+        segments; the factored net's middle layers then run over ALL next-state rows and its psi' head over their weighted mean.
         -> a TargetBatch (the fields are listed there) of views: valid until the next call."""
         n = rec.shape[0]
         renv = self._replay_env(n)
@@ -1025,6 +1050,9 @@ class VecDQN:
         idx, row_env, seg, _rep = self._rows(renv, stable_n)      # transitions with the same next state share its rows
         done = done_rec.bool() | (renv.n_valid[:E] == 0)
         select_q, double_q = None, self.double_q
+        soft = self.target_temperature is not None
+        soft_feat = soft_row = soft_head = None
+        self._soft_stats = None
         if idx.numel() and self._factored(self.target_net):
             # q of every next candidate through the factored forward on the bit-packed rasters; the 8204-wide output
             # (successor features) is only needed for the arg-max row of each transition: its channel 0 from the first-layer
@@ -1033,6 +1061,13 @@ class VecDQN:
             nsf0 = lambda best: self.target_net.sf0_from_first_layer(h_pre.index_select(0, best)).contiguous()
             if double_q:                                # (h_pre stays the target net's: the selected row's psi' is its)
                 select_q = self._net_q(self.policy_net, renv, idx, row_env, stable_n)
+            if soft and use_sf:
+                # the psi' head is linear in the last hidden activation, so its expectation is the head of the expected hidden
+                # row: the middle layers over ALL next-state rows, the head GEMM over E rows as ever
+                lin_layers = [m for m in self.target_net.mlp.layers if isinstance(m, torch.nn.Linear)]
+                px = self.target_net.img_size[0] * self.target_net.img_size[1]
+                soft_feat = self.target_net._middle_layers(h_pre, lin_layers)
+                soft_head = lambda mean: torch.addmm(lin_layers[-1].bias[:px], mean, lin_layers[-1].weight[:px].T)
         elif idx.numel():
             groups = self._distinct_rows(renv, idx, row_env, stable_n)
             nq, nsf, _, inverse = self._forward_rows(self.target_net, renv, idx, row_env, stable_n, groups=groups)
@@ -1042,7 +1077,19 @@ class VecDQN:
                 raise ValueError("No successor block features available from the chosen policy net.")
             # (nsf holds the DISTINCT rows' outputs)
             nsf0 = lambda best: nsf[:, 0].index_select(0, best if inverse is None else inverse.index_select(0, best)).reshape(E, -1).contiguous()
-        if idx.numel():
+            if soft and use_sf:                         # channel 0 of the distinct rows' outputs; row j stands at inverse[j]
+                soft_feat, soft_row = nsf[:, 0].reshape(nsf.shape[0], -1), inverse
+        if idx.numel() and soft:
+            stats = {}
+            q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, action_raster=sf_action.squeeze(1) if use_sf else None,
+                                                       lin=lin, discount=discount, select_q=select_q, temperature=self.target_temperature,
+                                                       next_feat=soft_feat, feat_row=soft_row, feat_head=soft_head, stats=stats)
+            # the log's two means over the transitions that are not done; they wait on the device for the losses' copy
+            # (of the n sampled ones: the scratch env's envs beyond n repeat record 0)
+            at_max = nq.contiguous().float().index_select(0, stats["argmax_row"].long().clamp_(0, nq.numel() - 1))
+            both = torch.stack([stats["entropy"], at_max - stats["value"]])[:, :n]
+            self._soft_stats = torch.where(done[:n], torch.zeros_like(both), both).sum(dim=1) / (~done[:n]).sum().clamp_(min=1)
+        elif idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
                                                        action_raster=sf_action.squeeze(1) if use_sf else None, lin=lin,
                                                        discount=discount, select_q=select_q)
@@ -1198,13 +1245,18 @@ class VecDQN:
                 self.opt.step()
                 losses.append(loss.detach())
             out = torch.stack(losses)
+        soft = self._soft_stats
+        if soft is not None:                                 # soft targets: the log's two means ride behind the losses
+            out = torch.cat([out.to(torch.float32).reshape(-1), soft.to(torch.float32)])
         if defer:
-            host = torch.empty(n_steps, dtype=torch.float32, pin_memory=True)
+            host = torch.empty(out.numel(), dtype=torch.float32, pin_memory=True)
             host.copy_(out, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
-            return DeferredLosses(host, done, drv)
+            return DeferredLosses(host, done, drv, owner=self if soft is not None else None)
         losses = out.tolist()                                # the one host sync of the call
+        if soft is not None:
+            losses, (self.target_entropy, self.soft_value_gap) = losses[:-2], losses[-2:]
         return drv.check_losses(losses) if drv is not None else losses
 
     def train_step(self):
@@ -1229,6 +1281,8 @@ class VecDQN:
             blob["temperature"] = float(self.temperature)
         if self.search_every:                                # one more key: the lock-steps since the last search
             blob["search_phase"] = int(self.search_calls)
+        if self.target_temperature is not None:              # one more key: the temperature of the soft targets
+            blob["target_temperature"] = float(self.target_temperature)
         if self.hindsight is not None:                       # two more keys: the setting and the running episodes
             blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
             blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
@@ -1254,6 +1308,12 @@ class VecDQN:
         if got_n != want_n:
             raise ValueError(f"{path} was written by a run with n_step = {got_n}, this agent folds n_step = {want_n}: the rows "
                              "of the ring do not mean the same returns")
+        # (a file of a run without soft targets carries no entry)
+        got_t = blob.get("target_temperature")
+        got_t = None if got_t is None else float(got_t)
+        if got_t != self.target_temperature:
+            raise ValueError(f"{path} was written by a run with target_temperature = {got_t}, this agent has "
+                             f"{self.target_temperature}: the nets were trained towards another backup operator")
         # (a file of a run without hindsight relabelling carries no entry)
         got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
         want_h = (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None
@@ -1400,8 +1460,10 @@ class _TransitionRows:
 class DeferredLosses:
     """Losses of one train_steps call on their way to the host (pinned buffer + event)."""
 
-    def __init__(self, host, done, driver):
+    def __init__(self, host, done, driver, owner=None):
         self._host, self._done, self._driver, self._list = host, done, driver, None
+        self._owner = owner                                  # soft targets: the agent whose two log means follow the losses
+        self.soft = None                                     # ... and, after get(), those means under their log keys
 
     def get(self):
         if self._list is None:
@@ -1410,6 +1472,10 @@ class DeferredLosses:
             else:
                 self._done.synchronize()
                 self._list = self._host.tolist()
+                if self._owner is not None:
+                    self._list, tail = self._list[:-2], self._list[-2:]
+                    self.soft = dict(target_entropy=tail[0], soft_value_gap=tail[1])
+                    self._owner.target_entropy, self._owner.soft_value_gap = tail
                 if self._driver is not None:
                     self._driver.check_losses(self._list)
         return self._list
@@ -1429,6 +1495,8 @@ def lockstep_log_values(info):
                 steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
     if 'temperature' in info:                                # Boltzmann exploration only
         vals.update(temperature=info['temperature'], explored_fraction=info.get('explored_fraction'))
+    if 'target_entropy' in info:                             # soft targets only
+        vals.update(target_entropy=info['target_entropy'], soft_value_gap=info['soft_value_gap'])
     if 'hindsight_rows' in info:                             # hindsight relabelling only
         vals.update(hindsight_rows=info['hindsight_rows'])
     if 'search_rows' in info:                                # search in training: the lock-steps that searched
@@ -1529,6 +1597,7 @@ def next_multiple(n, every):
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
     from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets,
+                                                    target_temperature_from_args,
                                                     search_from_args, track_run_sinks)
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
@@ -1578,7 +1647,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
                    priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
                    priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args),
-                   **hindsight_from_args(args), **search_from_args(args))
+                   **hindsight_from_args(args), **search_from_args(args), **target_temperature_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -1616,6 +1685,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         info, deferred, stats_host, done, episodes, weights_host = entry
         ls = deferred.get()
         info['avg_loss'] = float(np.mean(ls)) if ls else None
+        if deferred.soft is not None:                        # soft targets: the two means that rode with the losses
+            info.update(deferred.soft)
         if stats_host is not None:
             done.synchronize()
             info['mean_reward'], info['mean_lin_reward'] = float(stats_host[0]), float(stats_host[1])

@@ -724,6 +724,37 @@ int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32
                              const uint8_t* done, const float* discount, float gamma, int32_t sf_dim, float* q_target,
                              float* sf_target, int32_t* argmax_row, void* stream);
 
+/* Expected-value targets under the Boltzmann policy (the softmax backup, Expected SARSA for the policy
+ * bridges_boltzmann_select draws from): the expectation of next_q and of a feature row over every transition's next rows.
+ * select_q, next_q [R] f32 hold a value per row (the same pointer is allowed: the plain, non-double target); feat f32 holds
+ * dim floats per row, feat_row_stride floats apart; feat_row [R] i64 (may be NULL) names the row of feat that stands for row j.
+ * The rule, for transition i with the rows lo = seg_lo[i] .. seg_hi[i] - 1 and T = (double)temperature, all in float64:
+ *   - WEIGHTS: those of bridges_boltzmann_select on select_q, word for word -- a row is ELIGIBLE if its select_q is neither NaN
+ *     nor -inf; m = the largest eligible value; w_j = exp(((double)select_q_j - m) / T) for an eligible row, 0 for any other; if
+ *     m is +inf: 1 for the +inf rows, else 0.  Z = sum_j w_j, p_j = w_j / Z.
+ *   - VALUE: value[i] = (float) sum_j p_j (double)next_q[j].
+ *   - FEATURE MEAN: feat_mean[i, c] = (float) sum_j p_j (double)feat[r_j * feat_row_stride + c] for c < dim, r_j = feat_row ?
+ *     feat_row[j] : j; the sum over j is taken in ascending row order in float64 (product and sum rounded separately), then
+ *     rounded once.
+ *   - ENTROPY (entropy may be NULL): entropy[i] = (float)(log Z - sum_j p_j x_j), x_j = ((double)select_q_j - m) / T (taken as 0
+ *     on the +inf rows when m is +inf, so the entropy there is the log of their number).
+ *   - ARG-MAX ROW: argmax_row[i] = the first maximum of select_q among the eligible rows (for finite inputs the row of
+ *     bridges_td_target_select).
+ *   - a row whose weight is exactly 0 contributes nothing and is not read in next_q or feat, whatever they hold there;
+ *   - NOTHING ELIGIBLE (an empty segment, hi <= lo, or a segment without an eligible row): value[i] = -inf, feat_mean[i, :] = 0,
+ *     entropy[i] = 0, argmax_row[i] = 0x7fffffff, and nothing of next_q or feat is read.
+ * Both segment forms of bridges_td_target are taken (a prefix-sum array as seg, seg + 1; separate lo / hi arrays); transitions
+ * may share or overlap ranges.  dim == 0: feat, feat_row and feat_mean may be NULL.  The caller keeps every r_j * feat_row_stride
+ * + c inside feat.  No atomics, every output word is written exactly once, the order of every sum is fixed (value and entropy:
+ * lane-strided partial sums combined by a fixed tree): the same inputs give the same bits on every call.
+ * Returns -1 and launches nothing for: n_trans < 0 or dim < 0; a temperature that is not finite or not > 0; a negative
+ * feat_row_stride; a float / int32 pointer that is not 4-byte aligned or a feat_row that is not 8-byte aligned; with n_trans > 0
+ * a NULL seg_lo, seg_hi, select_q, next_q, value or argmax_row, or dim > 0 with a NULL feat or feat_mean.  n_trans == 0 returns 0
+ * and launches nothing. */
+int bridges_soft_expect(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                        float temperature, const float* feat, int64_t feat_row_stride, const int64_t* feat_row, int32_t dim,
+                        float* value, float* feat_mean, float* entropy, int32_t* argmax_row, void* stream);
+
 /* --- n-step returns of the vectorised loop ------------------------------------------------------------------------
  * The fold of one lock-step's one-step records rec [E, W] f64 (W >= BRIDGES_REC_WIDTH: the record plus its task tail) / valid [E]
  * into h-step records.  Per-env window state that persists between calls: count [E] i32 (pending starts, 0 .. n - 1) and

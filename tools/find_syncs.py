@@ -6,6 +6,7 @@ family (RandomBridges), --curriculum [--curriculum_every N ...] with its curricu
 lock-step holds the fold AND the update, and the count should be that of the same line without --curriculum.  --n_step N runs the
 lock-step with n-step returns (the fold and the compaction of its rows): the count should be that of the same line without it.
 --double_q runs it with double Q-learning targets (a second forward over the next-state rows): the count should not change either.
+--target_temperature T runs it with expected-value targets (bridges_soft_expect; its two log means ride with the losses): nor here.
 --prioritized_replay [--priority_alpha A] [--priority_refresh] runs it on prioritised replay; the sampler kernel and the refresh add
 launches, and the count should be that of plain --prioritized_replay; --priority_beta B [--priority_beta_anneal N] adds the
 importance-sampling weights (one more launch, no wait)."""
@@ -29,6 +30,7 @@ ap.add_argument("--random_targets", type=int, default=0, metavar="T",
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomTargets, VecAssemblyGym
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
+                                                add_target_temperature_argument, target_temperature_from_args,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
@@ -36,6 +38,7 @@ from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
 add_curriculum_arguments(ap)
 add_n_step_argument(ap)
 add_double_q_argument(ap)
+add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
 add_priority_arguments(ap, prioritized_flag=True)
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
@@ -59,7 +62,7 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True)
                "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes or a.random_targets), per_env_obstacles=bool(sizes),
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
                **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
-               **search_from_args(dict(vars(a), num_envs=a.envs)))
+               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)))
 
 
 def lockstep():

@@ -1,0 +1,105 @@
+"""bridges_soft_expect alone against a torch formulation, on the segments the vectorised loop really feeds it.
+
+A VecDQN(target_temperature=T) on the tower task rolls out a few lock-steps, samples --transitions records (800 = 25 batches of
+32, the loop's default) and runs its target pass once; the segments, q vectors and last-hidden rows that pass handed to
+next_targets are kept.  Then the operator is timed alone with HIP events on those very inputs, for dim = the hidden width (the
+factored SuccessorMLP's feature rows) and for dim = 4096 (channel 0 of a module-forward net's output; random rows of the same
+count), alternating with the torch formulation: scatter_reduce(amax) and index_add_ over (transition, row) pairs for m, Z, the
+value and the entropy in float64, and one index_add_ of p * feat[row] in float32 for the feature mean (float64 there would cost
+torch a [pairs, dim] float64 temporary; the kernel sums in float64).  Prints one JSON line per dim: medians with min-max in
+microseconds."""
+import argparse, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
+import torch
+from bridges_hip import dqn_ops
+from bridges_hip.shapes import load_urdf
+from bridges_hip.vec_env import VecAssemblyGym
+from robotoddler.training.successor_dqn import build_parser, make_nets
+from robotoddler.training.vec_dqn import VecDQN
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=1024)
+ap.add_argument("--tower", type=int, default=4)
+ap.add_argument("--max_steps", type=int, default=15)
+ap.add_argument("--locksteps", type=int, default=12, help="rollout lock-steps before the sample")
+ap.add_argument("--transitions", type=int, default=800)
+ap.add_argument("--temperature", type=float, default=1.0)
+ap.add_argument("--reps", type=int, default=30)
+a = ap.parse_args()
+dev = torch.device("cuda:0")
+torch.manual_seed(0)
+pol, tgt = make_nets(vars(build_parser().parse_args(["--model", "SuccessorMLP", "--loss_function", "mse_block_features"])), dev)
+H = 0.8
+env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], [(0.5, 0., i * H + H / 2) for i in range(a.tower)],
+                     [(0.5, 0, a.tower * H + H / 2)], max_steps=a.max_steps, seed=0, device=dev, f32_rasters=False)
+agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01, "mse_block_features",
+               target_temperature=a.temperature)
+for _ in range(a.locksteps):
+    agent.lockstep(0)
+seen, inner = {}, dqn_ops.next_targets
+
+
+def keep(seg, next_q, done, gamma, **kw):
+    seen.update(seg=seg, next_q=next_q, feat=kw["next_feat"])
+    return inner(seg, next_q, done, gamma, **kw)
+
+
+dqn_ops.next_targets = keep
+agent._targets(agent.ring.sample(a.transitions, agent.sample_gen, False))
+dqn_ops.next_targets = inner
+lo, hi = (t.to(torch.int64) for t in seen["seg"])
+nq = seen["next_q"].contiguous().float()
+B, R, T = lo.numel(), nq.numel(), a.temperature
+length = (hi - lo).clamp_(min=0)
+ids = torch.repeat_interleave(torch.arange(B, device=dev), length)                 # the transition of every (transition, row) pair
+start = torch.cumsum(length, 0) - length
+rows = lo[ids] + (torch.arange(ids.numel(), device=dev) - start[ids])               # ... and its row
+
+
+def torch_leg(feat):
+    q = nq.double()[rows]
+    m = torch.full((B,), -float("inf"), dtype=torch.float64, device=dev).scatter_reduce(0, ids, q, "amax")
+    x = (q - m[ids]) / T
+    w = torch.exp(x)
+    Z = torch.zeros(B, dtype=torch.float64, device=dev).index_add_(0, ids, w)
+    p = w / Z[ids]
+    value = torch.zeros(B, dtype=torch.float64, device=dev).index_add_(0, ids, p * q)
+    entropy = torch.log(Z) - torch.zeros(B, dtype=torch.float64, device=dev).index_add_(0, ids, p * x)
+    mean = torch.zeros((B, feat.shape[1]), dtype=torch.float32, device=dev).index_add_(0, ids, p.float().unsqueeze(1) * feat[rows])
+    return value.float(), mean, entropy.float()
+
+
+def kernel_leg(feat):
+    return dqn_ops.soft_expect(seen["seg"], nq, nq, T, feat=feat)
+
+
+def timed(fn, feat):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn(feat)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3
+
+
+def stats(xs):
+    xs = sorted(xs)
+    return dict(median_us=round(xs[len(xs) // 2], 1), min_us=round(xs[0], 1), max_us=round(xs[-1], 1))
+
+
+for name, feat in (("hidden", seen["feat"]), ("4096", torch.randn((R, 4096), device=dev))):
+    v_t, m_t, e_t = torch_leg(feat)
+    v_k, m_k, e_k, _ = kernel_leg(feat)
+    live = length > 0
+    agree = dict(value=float((v_t - v_k)[live].abs().max()), feat_mean=float((m_t - m_k)[live].abs().max()),
+                 entropy=float((e_t - e_k)[live].abs().max()))
+    for _ in range(3):                                                              # warm both legs
+        timed(torch_leg, feat), timed(kernel_leg, feat)
+    t_torch, t_kernel = [], []
+    for _ in range(a.reps):                                                         # legs alternating
+        t_torch.append(timed(torch_leg, feat))
+        t_kernel.append(timed(kernel_leg, feat))
+    print(json.dumps(dict(bench="soft_expect", dim=int(feat.shape[1]), transitions=B, rows=R, pairs=int(ids.numel()),
+                          longest_segment=int(length.max()), temperature=T, kernel=stats(t_kernel), torch=stats(t_torch),
+                          max_abs_difference=agree)), flush=True)

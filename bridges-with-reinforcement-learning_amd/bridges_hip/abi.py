@@ -279,6 +279,7 @@ SIGNATURES = {
     "bridges_mlp_mid_backward": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, vp],
     "bridges_eps_greedy_select": [i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_boltzmann_select": [i32, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_boltzmann_select_rel": [i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_beam_select": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_beam_merge": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_beam_trace": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp, vp, vp],
@@ -330,6 +331,7 @@ SIGNATURES = {
     "bridges_td_target_rows": [i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_td_target_select": [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp],
     "bridges_soft_expect": [i32, vp, vp, vp, vp, f32, vp, i64, vp, i32, vp, vp, vp, vp, vp],
+    "bridges_soft_expect_rel": [i32, vp, vp, vp, vp, f32, f32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp],
     "bridges_nstep_fold": [i32, i32, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_discounted_sum": [i32, vp, i64, vp, vp, f32, vp, vp, vp],
     "bridges_priority_sample_scratch": [i64, C.POINTER(i64)],

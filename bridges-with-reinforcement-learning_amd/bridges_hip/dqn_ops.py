@@ -73,12 +73,16 @@ def td_target(seg_offset, next_q, lin_reward, done, gamma, next_sf=None, action_
     return q_target, sf_target, argmax_row
 
 
-def soft_expect(seg_offset, select_q, next_q, temperature, feat=None, feat_row=None, want_entropy=True):
+def soft_expect(seg_offset, select_q, next_q, temperature, feat=None, feat_row=None, want_entropy=True, relative=False,
+                spread_floor=1e-3):
     """The expectation of next_q and of a feature row under the Boltzmann policy of select_q at ``temperature``, per segment
     (bridges_soft_expect; the rule stands in include/bridges_hip.h).  seg_offset as td_target takes it; select_q, next_q f32 [R],
     contiguous (the same tensor: the plain target); feat f32 [F, D] whose rows are contiguous (the row stride may exceed D);
     feat_row int64 [R]: the row of feat that stands for row j (None: row j itself).
-    -> (value f32 [B], feat_mean f32 [B, D] or None, entropy f32 [B] or None, argmax_row int32 [B])."""
+    -> (value f32 [B], feat_mean f32 [B, D] or None, entropy f32 [B] or None, argmax_row int32 [B]).
+    ``relative`` (bridges_soft_expect_rel): segment i is weighed at temperature * max(the standard deviation of its finite
+    select_q, spread_floor), formed on the device in the same launch; that effective temperature is a further result, temp_out
+    float64 [B]."""
     L = abi.require_gpu()
     dev = next_q.device
     for t in (select_q, next_q):
@@ -104,6 +108,13 @@ def soft_expect(seg_offset, select_q, next_q, temperature, feat=None, feat_row=N
             assert feat_row.dtype == torch.int64 and feat_row.is_contiguous() and feat_row.numel() == next_q.numel()
         else:
             assert feat.shape[0] >= next_q.numel()
+    if relative:
+        temp_out = torch.empty(B, dtype=torch.float64, device=dev)
+        abi.check(L.bridges_soft_expect_rel(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(select_q), _ptr(next_q), float(temperature),
+                                            float(spread_floor), _ptr(feat), stride, _ptr(feat_row if feat is not None else None), dim,
+                                            _ptr(value), _ptr(feat_mean), _ptr(entropy), _ptr(argmax_row), _ptr(temp_out), _stream()),
+                  "bridges_soft_expect_rel")
+        return value, feat_mean, entropy, argmax_row, temp_out
     abi.check(L.bridges_soft_expect(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(select_q), _ptr(next_q), float(temperature), _ptr(feat), stride,
                                     _ptr(feat_row if feat is not None else None), dim, _ptr(value), _ptr(feat_mean), _ptr(entropy),
                                     _ptr(argmax_row), _stream()), "bridges_soft_expect")
@@ -111,7 +122,7 @@ def soft_expect(seg_offset, select_q, next_q, temperature, feat=None, feat_row=N
 
 
 def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None, select_q=None,
-                 temperature=None, next_feat=None, feat_row=None, feat_head=None, stats=None):
+                 temperature=None, next_feat=None, feat_row=None, feat_head=None, stats=None, relative=False, spread_floor=1e-3):
     """The TD targets of transitions whose next-state rows are the segments ``seg`` of ``next_q`` (td_target's seg_offset).
     -> (q [B], sf [B, D] or None).  With ``lin``: q = lin + gamma q' of each segment's arg-max row, sf = lin + gamma psi' of
     that row + the action raster.  lin=None is the single-env reference form: q is the done-masked q' of the arg-max row (lin 0,
@@ -128,15 +139,22 @@ def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin
     segments, value standing in for next_q and the expected psi' for next_sf: q = lin + d * (done ? 0 : value), sf =
     action_raster + d * (done ? 0 : expected psi'), so done, discount, gamma and the -inf marking of an empty segment that is
     not done are that kernel's.  next_sf is not used then.  ``stats`` (a dict) receives stage one's value, entropy and
-    argmax_row.  temperature=None: every line below the block is the path as it was."""
+    argmax_row.  ``relative`` / ``spread_floor`` go to stage one (soft_expect's; ``stats`` then receives temp_out too); stage two
+    is unchanged.  temperature=None: every line below the block is the path as it was."""
     if temperature is not None:
         if lin is None:
             raise ValueError("next_targets(temperature=...) is the vectorised form: it needs lin")
         nq = next_q.contiguous().float()
         sel = nq if select_q is None else select_q.contiguous().float()
-        value, mean, entropy, arg = soft_expect(seg, sel, nq, temperature, feat=next_feat, feat_row=feat_row)
+        if relative:
+            value, mean, entropy, arg, temp_out = soft_expect(seg, sel, nq, temperature, feat=next_feat, feat_row=feat_row,
+                                                              relative=True, spread_floor=spread_floor)
+        else:
+            value, mean, entropy, arg = soft_expect(seg, sel, nq, temperature, feat=next_feat, feat_row=feat_row)
         if stats is not None:
             stats.update(value=value, entropy=entropy, argmax_row=arg, feat_mean=mean)
+            if relative:
+                stats["temp_out"] = temp_out
         sf_soft = None if mean is None else (feat_head(mean) if feat_head is not None else mean)
         one = torch.arange(done.numel() + 1, dtype=torch.int32, device=nq.device)
         q, sf, _ = td_target(one, value, lin, done, gamma, next_sf=sf_soft, action_raster=action_raster, discount=discount,

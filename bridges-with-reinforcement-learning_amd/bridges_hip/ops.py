@@ -477,13 +477,16 @@ def eps_greedy_select(seg, q, join, u, eps, greedy, idx, cand_offset, rep=None):
     return sel_compact, sel_index, q_sel, explore_w
 
 
-def boltzmann_select(seg, q, u, temperature, greedy, idx, cand_offset, rep=None):
+def boltzmann_select(seg, q, u, temperature, greedy, idx, cand_offset, rep=None, relative=False, spread_floor=1e-3):
     """Boltzmann exploration for every env in one launch (bridges_boltzmann_select): env e draws one of its rows with probability
     proportional to exp(q / temperature) by the inverse CDF at u[e] (the rule stands in include/bridges_hip.h; float64 on the
     device).  seg, q, u, idx, cand_offset and rep as for eps_greedy_select; temperature > 0 and finite (the library refuses any
     other, and an empty q).
     -> (sel_compact int64 [E], sel_index int32 [E], q_sel float32 [E], explore_w float32 [E] = 1 where the drawn row is not the
-    first maximum, p_sel float32 [E] = the probability the drawn row had)."""
+    first maximum, p_sel float32 [E] = the probability the drawn row had).
+    ``relative`` (bridges_boltzmann_select_rel): env e draws at temperature * max(the standard deviation of its finite q,
+    spread_floor), formed on the device in the same launch; that effective temperature is a further result, temp_out float64 [E]
+    (0 where greedy)."""
     L = abi.require_gpu()
     if isinstance(seg, (tuple, list)):
         seg_lo, seg_hi = seg
@@ -502,6 +505,13 @@ def boltzmann_select(seg, q, u, temperature, greedy, idx, cand_offset, rep=None)
     sel_compact = torch.empty(E, dtype=torch.int64, device=dev)
     sel_index = torch.empty(E, dtype=torch.int32, device=dev)
     q_sel, explore_w, p_sel = (torch.empty(E, dtype=torch.float32, device=dev) for _ in range(3))
+    if relative:
+        temp_out = torch.empty(E, dtype=torch.float64, device=dev)
+        abi.check(L.bridges_boltzmann_select_rel(E, n, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), _ptr(u), float(temperature),
+                                                 float(spread_floor), int(bool(greedy)), _ptr(idx), _ptr(cand_offset), _ptr(rep),
+                                                 _ptr(sel_compact), _ptr(sel_index), _ptr(q_sel), _ptr(explore_w), _ptr(p_sel),
+                                                 _ptr(temp_out), _stream()), "bridges_boltzmann_select_rel")
+        return sel_compact, sel_index, q_sel, explore_w, p_sel, temp_out
     abi.check(L.bridges_boltzmann_select(E, n, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), _ptr(u), float(temperature), int(bool(greedy)),
                                          _ptr(idx), _ptr(cand_offset), _ptr(rep), _ptr(sel_compact), _ptr(sel_index), _ptr(q_sel),
                                          _ptr(explore_w), _ptr(p_sel), _stream()), "bridges_boltzmann_select")

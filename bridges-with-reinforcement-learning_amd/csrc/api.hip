@@ -817,6 +817,29 @@ int bridges_soft_expect(int32_t n_trans, const int32_t* seg_lo, const int32_t* s
                   select_q, next_q, temperature, feat, feat_row_stride, feat_row, (int)dim, value, feat_mean, entropy, argmax_row);
 }
 
+int bridges_soft_expect_rel(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                            float temperature, float spread_floor, const float* feat, int64_t feat_row_stride, const int64_t* feat_row,
+                            int32_t dim, float* value, float* feat_mean, float* entropy, int32_t* argmax_row, double* temp_out,
+                            void* stream) {
+    if (n_trans < 0 || dim < 0) return fail_arg("bridges_soft_expect_rel: negative count");
+    if (!(temperature > 0.f && temperature < INFINITY))                           // (a NaN fails the comparison)
+        return fail_arg("bridges_soft_expect_rel: the temperature must be finite and > 0");
+    if (!(spread_floor > 0.f && spread_floor < INFINITY))
+        return fail_arg("bridges_soft_expect_rel: the spread floor must be finite and > 0");
+    if (feat_row_stride < 0) return fail_arg("bridges_soft_expect_rel: negative row stride");
+    if (!aligned(4, seg_lo, seg_hi, argmax_row) || !aligned(4, select_q, next_q, feat, value, feat_mean, entropy) || !aligned(8, feat_row))
+        return fail_arg("bridges_soft_expect_rel: misaligned pointer");
+    if (!aligned(8, temp_out)) return fail_arg("bridges_soft_expect_rel: temp_out must be 8-byte aligned");
+    if (n_trans == 0) return BRIDGES_OK;
+    if (!seg_lo || !seg_hi || !select_q || !next_q || !value || !argmax_row || !temp_out) return fail_arg("bridges_soft_expect_rel: null pointer");
+    if (dim > 0 && (!feat || !feat_mean)) return fail_arg("bridges_soft_expect_rel: dim > 0 needs feat and feat_mean");
+    // bridges_soft_expect's grid
+    const unsigned tiles = dim > 0 ? (unsigned)ceil_div(dim, SOFT_TILE) : 1u;
+    return launch("k_soft_expect_rel", k_soft_expect_rel, dim3((unsigned)n_trans, tiles), dim3(256), 0, stream, n_trans, seg_lo, seg_hi,
+                  select_q, next_q, temperature, spread_floor, feat, feat_row_stride, feat_row, (int)dim, value, feat_mean, entropy,
+                  argmax_row, temp_out);
+}
+
 int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
                        double* acc, double* disc, double* stable_s, double* td, double* out, uint8_t* out_valid, void* stream) {
     if (E < 0 || n < 1 || n > BRIDGES_NSTEP_MAX) return fail_arg("bridges_nstep_fold: n must be 1..BRIDGES_NSTEP_MAX");
@@ -987,6 +1010,26 @@ int bridges_boltzmann_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, c
     // one wave per env, four envs per workgroup
     return launch("k_boltzmann_select", k_boltzmann_select, dim3((unsigned)ceil_div(E, 4)), dim3(256), 0, stream, E, n_rows, seg_lo,
                   seg_hi, q, u, temperature, (int)greedy, idx, cand_offset, rep, sel_compact, sel_index, q_sel, explore_w, p_sel);
+}
+
+int bridges_boltzmann_select_rel(int32_t E, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, const float* u,
+                                 float temperature, float spread_floor, int32_t greedy, const int64_t* idx, const int32_t* cand_offset,
+                                 const int32_t* rep, int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w,
+                                 float* p_sel, double* temp_out, void* stream) {
+    if (E < 0) return fail_arg("bridges_boltzmann_select_rel: negative count");
+    if (E == 0) return BRIDGES_OK;
+    if (n_rows < 1) return fail_arg("bridges_boltzmann_select_rel: n_rows must be >= 1");
+    if (!(temperature > 0.f && temperature < INFINITY))                           // (a NaN fails the comparison)
+        return fail_arg("bridges_boltzmann_select_rel: the temperature must be finite and > 0");
+    if (!(spread_floor > 0.f && spread_floor < INFINITY))
+        return fail_arg("bridges_boltzmann_select_rel: the spread floor must be finite and > 0");
+    if (!seg_lo || !seg_hi || !q || !u || !idx || !cand_offset || !sel_compact || !sel_index || !q_sel || !explore_w || !p_sel)
+        return fail_arg("bridges_boltzmann_select_rel: null pointer");
+    if (!temp_out || !aligned(8, temp_out)) return fail_arg("bridges_boltzmann_select_rel: temp_out must be an 8-byte aligned array");
+    // bridges_boltzmann_select's grid
+    return launch("k_boltzmann_select_rel", k_boltzmann_select_rel, dim3((unsigned)ceil_div(E, 4)), dim3(256), 0, stream, E, n_rows,
+                  seg_lo, seg_hi, q, u, temperature, spread_floor, (int)greedy, idx, cand_offset, rep, sel_compact, sel_index, q_sel,
+                  explore_w, p_sel, temp_out);
 }
 
 int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q,

@@ -524,13 +524,47 @@ __device__ __forceinline__ double boltzmann_weight(float qv, double m, double T)
     return exp(((double)qv - m) / T);
 }
 
-__global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, const int32_t* __restrict__ seg_lo,
-                                                          const int32_t* __restrict__ seg_hi, const float* __restrict__ q,
-                                                          const float* __restrict__ u, float temperature, int greedy,
-                                                          const int64_t* __restrict__ idx, const int32_t* __restrict__ cand_offset,
-                                                          const int32_t* __restrict__ rep, int64_t* __restrict__ sel_compact,
-                                                          int32_t* __restrict__ sel_index, float* __restrict__ q_sel,
-                                                          float* __restrict__ explore_w, float* __restrict__ p_sel) {
+// The spread of a segment (the relative-temperature operators; the rule stands in include/bridges_hip.h): the population standard
+// deviation of the rows lo .. hi - 1 of q that are neither NaN nor +-inf, 0 if fewer than two are.  Two passes -- the mean, then the
+// squared deviations from it, never E[x^2] - mean^2 --, float64 throughout.  The lane `first` of STRIDE takes the rows lo + first,
+// lo + first + STRIDE, ..; `combine` makes the segment's sum of a wave's (wave_sum_d's DPP tree): the identity where one wave owns
+// the segment (k_boltzmann_select), the LDS wave-combine of phase A in k_soft_expect, a fresh slot per call.  Every lane that
+// `combine` joins must call this, and all of them get the same bits back.
+template <int STRIDE, class Combine>
+__device__ __forceinline__ double segment_spread(const float* q, int lo, int hi, int first, Combine combine) {
+    double sum = 0.0, cnt = 0.0;
+    for (int j = lo + first; j < hi; j += STRIDE) {
+        const float v = q[j];
+        if (isfinite(v)) { sum += (double)v; cnt += 1.0; }
+    }
+    sum = combine(wave_sum_d(sum), 0);
+    const double n_f = combine(wave_sum_d(cnt), 1);      // (a count below 2^53: exact in any order)
+    if (n_f < 2.0) return 0.0;                           // uniform over the lanes `combine` joins
+    const double mean = sum / n_f;
+    double dev = 0.0;
+    for (int j = lo + first; j < hi; j += STRIDE) {
+        const float v = q[j];
+        if (isfinite(v)) { const double d = (double)v - mean; dev += d * d; }
+    }
+    return sqrt(combine(wave_sum_d(dev), 2) / n_f);
+}
+// T_e = temperature * max(spread, floor); both factors are > 0 and finite, so is the product unless it overflows a double's range
+__device__ __forceinline__ double relative_temperature(float temperature, double spread, float spread_floor) {
+    return (double)temperature * fmax(spread, (double)spread_floor);
+}
+
+// One body for k_boltzmann_select and k_boltzmann_select_rel.  REL: the temperature of env e is relative_temperature() of the
+// spread of its rows, taken between pass 1 and pass 2 and written to temp_out[e] (greedy: 0; no rows or no eligible row: no row
+// is finite either, so temperature * spread_floor without a pass).
+template <bool REL>
+__device__ __forceinline__ void boltzmann_select_body(int E, int n_rows, const int32_t* __restrict__ seg_lo,
+                                                      const int32_t* __restrict__ seg_hi, const float* __restrict__ q,
+                                                      const float* __restrict__ u, float temperature, float spread_floor, int greedy,
+                                                      const int64_t* __restrict__ idx, const int32_t* __restrict__ cand_offset,
+                                                      const int32_t* __restrict__ rep, int64_t* __restrict__ sel_compact,
+                                                      int32_t* __restrict__ sel_index, float* __restrict__ q_sel,
+                                                      float* __restrict__ explore_w, float* __restrict__ p_sel,
+                                                      double* __restrict__ temp_out) {
     constexpr int NONE = 0x7fffffff;
     const int lane = threadIdx.x & (WAVE - 1);
     const int e = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
@@ -539,6 +573,7 @@ __global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, con
     const bool has = hi > lo;
     int row = NONE, first_max = NONE;
     double p = 0.0;
+    double t_e = REL ? (greedy ? 0.0 : relative_temperature(temperature, 0.0, spread_floor)) : 0.0;
     if (greedy) {
         // k_eps_greedy_select's search, operand for operand (it decides what a NaN row does to the choice)
         float best = -INFINITY;
@@ -556,7 +591,7 @@ __global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, con
         row = first_max = bi;
         p = has ? 1.0 : 0.0;
     } else if (has) {
-        const double T = (double)temperature;
+        double T = (double)temperature;
         // pass 1: the largest eligible q (-inf: no row is eligible)
         double mx = -INFINITY;
         for (int j = lo + lane; j < hi; j += 64) {
@@ -567,6 +602,10 @@ __global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, con
         if (m == -(double)INFINITY) {
             row = first_max = lo;
         } else {
+            if (REL) {
+                T = t_e = relative_temperature(temperature, segment_spread<WAVE>(q, lo, hi, lane, [](double v, int) { return v; }),
+                                               spread_floor);
+            }
             // pass 2: the total, and the first row that holds the maximum
             double total = 0.0;
             int fm = NONE;
@@ -612,7 +651,31 @@ __global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, con
         q_sel[e] = has ? q[row] : 0.f;
         explore_w[e] = explored ? 1.f : 0.f;
         p_sel[e] = (float)p;
+        if (REL) temp_out[e] = t_e;
     }
+}
+
+__global__ __launch_bounds__(256) void k_boltzmann_select(int E, int n_rows, const int32_t* __restrict__ seg_lo,
+                                                          const int32_t* __restrict__ seg_hi, const float* __restrict__ q,
+                                                          const float* __restrict__ u, float temperature, int greedy,
+                                                          const int64_t* __restrict__ idx, const int32_t* __restrict__ cand_offset,
+                                                          const int32_t* __restrict__ rep, int64_t* __restrict__ sel_compact,
+                                                          int32_t* __restrict__ sel_index, float* __restrict__ q_sel,
+                                                          float* __restrict__ explore_w, float* __restrict__ p_sel) {
+    boltzmann_select_body<false>(E, n_rows, seg_lo, seg_hi, q, u, temperature, 0.f, greedy, idx, cand_offset, rep, sel_compact, sel_index,
+                                 q_sel, explore_w, p_sel, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_boltzmann_select_rel(int E, int n_rows, const int32_t* __restrict__ seg_lo,
+                                                              const int32_t* __restrict__ seg_hi, const float* __restrict__ q,
+                                                              const float* __restrict__ u, float temperature, float spread_floor,
+                                                              int greedy, const int64_t* __restrict__ idx,
+                                                              const int32_t* __restrict__ cand_offset, const int32_t* __restrict__ rep,
+                                                              int64_t* __restrict__ sel_compact, int32_t* __restrict__ sel_index,
+                                                              float* __restrict__ q_sel, float* __restrict__ explore_w,
+                                                              float* __restrict__ p_sel, double* __restrict__ temp_out) {
+    boltzmann_select_body<true>(E, n_rows, seg_lo, seg_hi, q, u, temperature, spread_floor, greedy, idx, cand_offset, rep, sel_compact,
+                                sel_index, q_sel, explore_w, p_sel, temp_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -30,13 +30,19 @@ __device__ __forceinline__ double soft_block_sum(double wave_value, double* slot
     return ((slot[0] + slot[1]) + slot[2]) + slot[3];
 }
 
-__global__ __launch_bounds__(256) void k_soft_expect(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
-                                                     const float* select_q, const float* next_q, float temperature,
-                                                     const float* __restrict__ feat, int64_t feat_row_stride,
-                                                     const int64_t* __restrict__ feat_row, int dim, float* __restrict__ value,
-                                                     float* __restrict__ feat_mean, float* __restrict__ entropy,
-                                                     int32_t* __restrict__ argmax_row) {
+// One body for k_soft_expect and k_soft_expect_rel.  REL: the temperature of transition i is relative_temperature() of the spread
+// of its rows of select_q (segment_spread of dqn_kernels.hip through the LDS wave-combine, three slots of its own), taken in phase
+// A between pass 1 and the Z pass by every tile; tile 0 writes it to temp_out[i] (nothing eligible: no row is finite either, so
+// temperature * spread_floor without a pass).
+template <bool REL>
+__device__ __forceinline__ void soft_expect_body(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
+                                                 const float* select_q, const float* next_q, float temperature, float spread_floor,
+                                                 const float* __restrict__ feat, int64_t feat_row_stride,
+                                                 const int64_t* __restrict__ feat_row, int dim, float* __restrict__ value,
+                                                 float* __restrict__ feat_mean, float* __restrict__ entropy,
+                                                 int32_t* __restrict__ argmax_row, double* __restrict__ temp_out) {
     constexpr int NONE = 0x7fffffff;
+    __shared__ double s_spread[REL ? 3 : 1][4];          // (never referenced without REL: the compiler drops it)
     __shared__ double s_p[SOFT_CHUNK];
     __shared__ int64_t s_off[SOFT_CHUNK];
     __shared__ double s_m[4], s_z[4], s_v[4], s_e[4];
@@ -44,7 +50,7 @@ __global__ __launch_bounds__(256) void k_soft_expect(int n_trans, const int32_t*
     const int i = blockIdx.x, tile = blockIdx.y, t = threadIdx.x;
     if (i >= n_trans) return;                            // (uniform per workgroup: the grid is n_trans x tiles)
     const int lo = seg_lo[i], hi = seg_hi[i];
-    const double T = (double)temperature;
+    double T = (double)temperature;
     const bool first_tile = tile == 0;
 
     // phase A, pass 1: the largest eligible q (-inf: nothing is eligible; that includes the empty segment)
@@ -62,6 +68,12 @@ __global__ __launch_bounds__(256) void k_soft_expect(int n_trans, const int32_t*
     const int c0 = tile * SOFT_TILE + 4 * t;             // this lane's first column
     const int nc = dim - c0 < 4 ? dim - c0 : 4;          // how many of its four exist (<= 0: none)
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (REL) {
+        double spread = 0.0;
+        if (any) spread = segment_spread<256>(select_q, lo, hi, t, [&](double v, int k) { return soft_block_sum(v, s_spread[k], t); });
+        T = relative_temperature(temperature, spread, spread_floor);
+        if (first_tile && t == 0) temp_out[i] = T;
+    }
     if (any) {
         // pass 2: Z and the first row that holds the maximum
         double z = 0.0;
@@ -152,6 +164,27 @@ __global__ __launch_bounds__(256) void k_soft_expect(int n_trans, const int32_t*
             if (nc > 3) dst[3] = (float)a3;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_soft_expect(int n_trans, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
+                                                     const float* select_q, const float* next_q, float temperature,
+                                                     const float* __restrict__ feat, int64_t feat_row_stride,
+                                                     const int64_t* __restrict__ feat_row, int dim, float* __restrict__ value,
+                                                     float* __restrict__ feat_mean, float* __restrict__ entropy,
+                                                     int32_t* __restrict__ argmax_row) {
+    soft_expect_body<false>(n_trans, seg_lo, seg_hi, select_q, next_q, temperature, 0.f, feat, feat_row_stride, feat_row, dim, value,
+                            feat_mean, entropy, argmax_row, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_soft_expect_rel(int n_trans, const int32_t* __restrict__ seg_lo,
+                                                         const int32_t* __restrict__ seg_hi, const float* select_q, const float* next_q,
+                                                         float temperature, float spread_floor, const float* __restrict__ feat,
+                                                         int64_t feat_row_stride, const int64_t* __restrict__ feat_row, int dim,
+                                                         float* __restrict__ value, float* __restrict__ feat_mean,
+                                                         float* __restrict__ entropy, int32_t* __restrict__ argmax_row,
+                                                         double* __restrict__ temp_out) {
+    soft_expect_body<true>(n_trans, seg_lo, seg_hi, select_q, next_q, temperature, spread_floor, feat, feat_row_stride, feat_row, dim,
+                           value, feat_mean, entropy, argmax_row, temp_out);
 }
 
 }  // namespace bridges

@@ -585,6 +585,7 @@ def build_parser():
     add_n_step_argument(p)
     add_double_q_argument(p)
     add_target_temperature_argument(p)
+    add_relative_temperature_arguments(p)
     add_priority_arguments(p)
     add_exploration_arguments(p)
     add_hindsight_arguments(p)
@@ -758,6 +759,55 @@ def check_target_temperature(args):
 def target_temperature_from_args(args):
     """--target_temperature T -> VecDQN's keyword, nothing without the flag."""
     return dict(target_temperature=args['target_temperature']) if args.get('target_temperature') is not None else {}
+
+
+def add_relative_temperature_arguments(p):
+    """--temp_relative / --target_temp_relative / --spread_floor: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--temp_relative", action="store_true", default=argparse.SUPPRESS,
+                   help="Vectorised loop with --exploration boltzmann: the temperature is a multiple of each state's own spread of q -- "
+                        "an env draws at temperature * max(s, F), s the standard deviation of q among its candidates, formed on the "
+                        "device in the draw's own launch (bridges_boltzmann_select_rel). Logs temperature_effective.")
+    p.add_argument("--target_temp_relative", action="store_true", default=argparse.SUPPRESS,
+                   help="Vectorised loop with --target_temperature T: every transition is backed up at T * max(s, F), s the standard "
+                        "deviation of q' among its next state's candidates (bridges_soft_expect_rel; with --double_q the policy "
+                        "net's values). Logs target_temperature_effective.")
+    p.add_argument("--spread_floor", type=float, default=argparse.SUPPRESS, metavar="F",
+                   help="With --temp_relative / --target_temp_relative: the least spread a temperature multiplies (finite, > 0; 1e-3), "
+                        "which keeps the temperature positive where a state's candidates tie.")
+
+
+def relative_temperature_from_args(args):
+    """--temp_relative / --target_temp_relative / --spread_floor F -> VecDQN's keywords, nothing without the flags; refused in
+    words (SystemExit) without the option whose temperature they make relative."""
+    rel, trel = bool(args.get('temp_relative')), bool(args.get('target_temp_relative'))
+    if rel and args.get('exploration', EXPLORATIONS[0]) != "boltzmann":
+        raise SystemExit("--temp_relative makes the temperature of Boltzmann exploration relative to each state's spread of q: it "
+                         "needs --exploration boltzmann")
+    if trel and args.get('target_temperature') is None:
+        raise SystemExit("--target_temp_relative makes the temperature of the soft targets relative to each state's spread of q: it "
+                         "needs --target_temperature T")
+    out = {}
+    if 'spread_floor' in args:
+        if not (rel or trel):
+            raise SystemExit("--spread_floor is the floor of the spread a relative temperature multiplies: it needs --temp_relative "
+                             "or --target_temp_relative")
+        if not (0.0 < args['spread_floor'] < float("inf")):  # (a NaN fails the comparison)
+            raise SystemExit(f"--spread_floor must be a finite number > 0, got {args['spread_floor']}")
+        out['spread_floor'] = args['spread_floor']
+    if rel:
+        out['temp_relative'] = True
+    if trel:
+        out['target_temp_relative'] = True
+    return out
+
+
+def check_relative_temperature(args):
+    """The three flags: refused in words (SystemExit) where the loop cannot run them, before anything touches the GPU."""
+    given = [f"--{k}" for k in ('temp_relative', 'target_temp_relative', 'spread_floor') if k in args]
+    if given and args['num_envs'] <= 1:
+        raise SystemExit(f"{' / '.join(given)} need the vectorised loop (--num_envs N, N > 1): the single-env loop draws and backs "
+                         "up at one temperature for every state")
+    relative_temperature_from_args(args)
 
 
 def add_eval_beam_argument(p):
@@ -1054,6 +1104,7 @@ def main(argv=None):
     check_n_step(args)
     check_double_q(args)
     check_target_temperature(args)
+    check_relative_temperature(args)
     check_priority(args)
     check_exploration(args)
     check_hindsight(args)

@@ -75,6 +75,8 @@ class VecDQN:
     exploration, n_step, rows_fed, search_every = "epsilon_greedy", 1, 0, 0
     hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = last_search = None
     target_temperature = _soft_stats = target_entropy = soft_value_gap = None
+    temp_relative = target_temp_relative = False
+    spread_floor, temperature_effective, target_temperature_effective, _temp_out = 1e-3, None, None, None
 
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
@@ -82,7 +84,7 @@ class VecDQN:
                  n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0,
                  exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1,
                  search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None,
-                 target_temperature=None):
+                 target_temperature=None, temp_relative=False, target_temp_relative=False, spread_floor=1e-3):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -173,7 +175,33 @@ class VecDQN:
         stable_actions_only and several ranks (every rank forms its own targets, as ever).  The rollout's td_errors stay the
         max-operator error, evaluation and beam search stay greedy, T is constant.  target_entropy and soft_value_gap hold the
         last train_steps call's means over the transitions that are not done (they ride to the host with the losses).  None is
-        the loop as it was: no launch of this."""
+        the loop as it was: no launch of this.
+        ``temp_relative=True`` (with exploration="boltzmann" only) / ``target_temp_relative=True`` (with target_temperature
+        only): the temperature is a MULTIPLE of each state's own spread of q -- env e draws at temperature * max(s_e,
+        ``spread_floor``), transition i is backed up at target_temperature * max(s_i, spread_floor), s the population standard
+        deviation of the finite q among the state's candidate rows (double_q: of the policy net's q, the values that weigh the
+        rows), formed on the device inside the operator's own launch (bridges_boltzmann_select_rel / bridges_soft_expect_rel,
+        the rule in include/bridges_hip.h; DESIGN.md section 7, "Relative temperatures").  ``temperature`` keeps its schedule
+        and target_temperature its value; each is now the multiple.  temperature_effective holds the mean effective temperature
+        over the last lock-step's valid envs (it rides with the counts), target_temperature_effective the mean over the last
+        train_steps call's transitions that are not done (it rides with the losses): no host wait of their own.  Both compose
+        with whatever their parent option composes with; evaluation and beam search stay greedy.  ``spread_floor`` (finite,
+        > 0; default 1e-3) is refused unless one of the two is set.  False is the loop as it was: no launch of this."""
+        self.temp_relative, self.target_temp_relative = bool(temp_relative), bool(target_temp_relative)
+        if self.temp_relative and str(exploration) != "boltzmann":
+            raise ValueError("VecDQN(temp_relative=True) makes the temperature of Boltzmann exploration relative to each state's "
+                             "spread of q: it needs exploration='boltzmann'")
+        if self.target_temp_relative and target_temperature is None:
+            raise ValueError("VecDQN(target_temp_relative=True) makes the temperature of the soft targets relative to each state's "
+                             "spread of q: it needs target_temperature")
+        ok = isinstance(spread_floor, (int, float)) and not isinstance(spread_floor, bool)
+        if not ok or not (0.0 < float(spread_floor) < float("inf")):                 # (a NaN fails the comparison)
+            raise ValueError(f"VecDQN(spread_floor={spread_floor!r}): a finite number > 0")
+        if float(spread_floor) != 1e-3 and not (self.temp_relative or self.target_temp_relative):
+            raise ValueError("VecDQN(spread_floor=...) is the floor of the spread a relative temperature multiplies: it needs "
+                             "temp_relative=True or target_temp_relative=True")
+        self.spread_floor = float(spread_floor)
+        self.temperature_effective = self.target_temperature_effective = self._temp_out = None
         if target_temperature is not None:
             ok = isinstance(target_temperature, (int, float)) and not isinstance(target_temperature, bool)
             if not ok or not (0.0 < float(target_temperature) < float("inf")):       # (a NaN fails the comparison)
@@ -323,7 +351,8 @@ class VecDQN:
         # the counts of a lock-step (_count): env-steps and finished episodes; n-step returns: the emitted rows (one rank);
         # Boltzmann exploration: the envs whose draw left the first maximum; hindsight relabelling: the relabelled rows
         self._count_names = (("valid", "done") + (("emitted",) if self.n_step > 1 else ())
-                             + (("explored",) if self.exploration == "boltzmann" else ()) + (("hindsight",) if self.hindsight is not None else ()))
+                             + (("explored",) if self.exploration == "boltzmann" else ()) + (("hindsight",) if self.hindsight is not None else ())
+                             + (("temp_sum",) if self.temp_relative else ()))
         self._counts_host = torch.zeros(len(self._count_names), dtype=torch.int64).pin_memory()
         # per-episode statistics of the rollout envs (log_episode's numbers), folded on the device after every act()
         # (a task family -- RandomBridges -- keeps them per class as well: one row per span / height n = 0..hi)
@@ -675,8 +704,12 @@ class VecDQN:
             # in the same state still share their representative's rows, but stop acting alike sooner than under a greedy choice
             q = self._policy_q(env, idx, row_env, stable)
             u = torch.rand(E, generator=explore_gen, device=self.device)
-            sel_compact, sel_index, q_sel, self._ex_w, _p = ops.boltzmann_select(seg, q, u, self.temperature, greedy, idx,
-                                                                                 env.cand_offset[:E], rep=rep)
+            if self.temp_relative:                      # (the same launch grid; the effective temperatures are one more result)
+                sel_compact, sel_index, q_sel, self._ex_w, _p, self._temp_out = ops.boltzmann_select(
+                    seg, q, u, self.temperature, greedy, idx, env.cand_offset[:E], rep=rep, relative=True, spread_floor=self.spread_floor)
+            else:
+                sel_compact, sel_index, q_sel, self._ex_w, _p = ops.boltzmann_select(seg, q, u, self.temperature, greedy, idx,
+                                                                                     env.cand_offset[:E], rep=rep)
         elif idx.numel():
             step_of_row = env.n_blocks[row_env].long()
             q = self._policy_q(env, idx, row_env, stable)
@@ -1081,13 +1114,15 @@ class VecDQN:
                 soft_feat, soft_row = nsf[:, 0].reshape(nsf.shape[0], -1), inverse
         if idx.numel() and soft:
             stats = {}
+            relative = dict(relative=True, spread_floor=self.spread_floor) if self.target_temp_relative else {}
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, action_raster=sf_action.squeeze(1) if use_sf else None,
                                                        lin=lin, discount=discount, select_q=select_q, temperature=self.target_temperature,
-                                                       next_feat=soft_feat, feat_row=soft_row, feat_head=soft_head, stats=stats)
+                                                       next_feat=soft_feat, feat_row=soft_row, feat_head=soft_head, stats=stats, **relative)
             # the log's two means over the transitions that are not done; they wait on the device for the losses' copy
             # (of the n sampled ones: the scratch env's envs beyond n repeat record 0)
             at_max = nq.contiguous().float().index_select(0, stats["argmax_row"].long().clamp_(0, nq.numel() - 1))
-            both = torch.stack([stats["entropy"], at_max - stats["value"]])[:, :n]
+            both = torch.stack([stats["entropy"], at_max - stats["value"]]
+                               + ([stats["temp_out"].float()] if self.target_temp_relative else []))[:, :n]
             self._soft_stats = torch.where(done[:n], torch.zeros_like(both), both).sum(dim=1) / (~done[:n]).sum().clamp_(min=1)
         elif idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
@@ -1246,7 +1281,7 @@ class VecDQN:
                 losses.append(loss.detach())
             out = torch.stack(losses)
         soft = self._soft_stats
-        if soft is not None:                                 # soft targets: the log's two means ride behind the losses
+        if soft is not None:                                 # soft targets: the log's two (relative: three) means ride behind the losses
             out = torch.cat([out.to(torch.float32).reshape(-1), soft.to(torch.float32)])
         if defer:
             host = torch.empty(out.numel(), dtype=torch.float32, pin_memory=True)
@@ -1256,7 +1291,11 @@ class VecDQN:
             return DeferredLosses(host, done, drv, owner=self if soft is not None else None)
         losses = out.tolist()                                # the one host sync of the call
         if soft is not None:
-            losses, (self.target_entropy, self.soft_value_gap) = losses[:-2], losses[-2:]
+            k = soft.numel()
+            losses, tail = losses[:-k], losses[-k:]
+            self.target_entropy, self.soft_value_gap = tail[:2]
+            if self.target_temp_relative:
+                self.target_temperature_effective = tail[2]
         return drv.check_losses(losses) if drv is not None else losses
 
     def train_step(self):
@@ -1283,6 +1322,10 @@ class VecDQN:
             blob["search_phase"] = int(self.search_calls)
         if self.target_temperature is not None:              # one more key: the temperature of the soft targets
             blob["target_temperature"] = float(self.target_temperature)
+        if self.target_temp_relative:                        # one more key: ... and that it multiplies the spread, above which floor
+            blob["target_temp_relative"] = float(self.spread_floor)
+        if self.temp_relative:                               # one more key: what the schedule's temperature multiplies
+            blob["temp_relative"] = float(self.spread_floor)
         if self.hindsight is not None:                       # two more keys: the setting and the running episodes
             blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
             blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
@@ -1314,6 +1357,12 @@ class VecDQN:
         if got_t != self.target_temperature:
             raise ValueError(f"{path} was written by a run with target_temperature = {got_t}, this agent has "
                              f"{self.target_temperature}: the nets were trained towards another backup operator")
+        # (a file of a run whose soft targets took the scalar temperature carries no entry)
+        got_r = (True, float(blob["target_temp_relative"])) if "target_temp_relative" in blob else None
+        want_r = (True, float(self.spread_floor)) if self.target_temp_relative else None
+        if got_r != want_r:
+            raise ValueError(f"{path} was written by a run with (target_temp_relative, spread_floor) = {got_r}, this agent has "
+                             f"{want_r}: the nets were trained towards another backup operator")
         # (a file of a run without hindsight relabelling carries no entry)
         got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
         want_h = (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None
@@ -1388,6 +1437,9 @@ class VecDQN:
         boltzmann = self.exploration == "boltzmann"
         if boltzmann:                                   # the envs that left the arg-max ride with the counts: no wait of their own
             counts["explored"] = (self._ex_w * valid).sum().to(torch.int64) if self._ex_w is not None else torch.zeros_like(counts["valid"])
+        if self.temp_relative:                          # the sum of the valid envs' effective temperatures: a float64's bits among the counts
+            counts["temp_sum"] = ((self._temp_out * valid).sum().view(torch.int64) if self._temp_out is not None
+                                  else torch.zeros_like(counts["valid"]))
         hind = None
         if self.hindsight is not None:
             # the lock-step joins every env's running episode; the episodes that end are relabelled at once (three launches) and
@@ -1404,6 +1456,9 @@ class VecDQN:
         self.env_steps += n_valid
         if boltzmann:
             self.explored_fraction = self._count("explored") / n_valid if n_valid else None
+        if self.temp_relative:
+            at = self._count_names.index("temp_sum")
+            self.temperature_effective = float(self._counts_host[at:at + 1].view(torch.float64)) / n_valid if n_valid else None
         if self.n_step > 1 and folded is None:
             # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
             # windows and pushes the same rows; the collective carries what it carries for n_step = 1
@@ -1473,9 +1528,12 @@ class DeferredLosses:
                 self._done.synchronize()
                 self._list = self._host.tolist()
                 if self._owner is not None:
-                    self._list, tail = self._list[:-2], self._list[-2:]
+                    k = 3 if getattr(self._owner, "target_temp_relative", False) else 2      # relative: the mean T_e behind them
+                    self._list, tail = self._list[:-k], self._list[-k:]
                     self.soft = dict(target_entropy=tail[0], soft_value_gap=tail[1])
-                    self._owner.target_entropy, self._owner.soft_value_gap = tail
+                    self._owner.target_entropy, self._owner.soft_value_gap = tail[:2]
+                    if k == 3:
+                        self.soft["target_temperature_effective"] = self._owner.target_temperature_effective = tail[2]
                 if self._driver is not None:
                     self._driver.check_losses(self._list)
         return self._list
@@ -1497,6 +1555,9 @@ def lockstep_log_values(info):
         vals.update(temperature=info['temperature'], explored_fraction=info.get('explored_fraction'))
     if 'target_entropy' in info:                             # soft targets only
         vals.update(target_entropy=info['target_entropy'], soft_value_gap=info['soft_value_gap'])
+    for key in ('temperature_effective', 'target_temperature_effective'):         # relative temperatures only
+        if key in info:
+            vals[key] = info[key]
     if 'hindsight_rows' in info:                             # hindsight relabelling only
         vals.update(hindsight_rows=info['hindsight_rows'])
     if 'search_rows' in info:                                # search in training: the lock-steps that searched
@@ -1597,7 +1658,7 @@ def next_multiple(n, every):
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
     from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets,
-                                                    target_temperature_from_args,
+                                                    relative_temperature_from_args, target_temperature_from_args,
                                                     search_from_args, track_run_sinks)
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
@@ -1647,7 +1708,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
                    priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
                    priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args),
-                   **hindsight_from_args(args), **search_from_args(args), **target_temperature_from_args(args))
+                   **hindsight_from_args(args), **search_from_args(args), **target_temperature_from_args(args),
+                   **relative_temperature_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)
@@ -1740,6 +1802,8 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                     **{k: None for k in EPISODE_KEYS})
         if agent.exploration == "boltzmann":                 # (the temperature the NEXT lock-step draws at, as epsilon above)
             info.update(temperature=agent.temperature, explored_fraction=agent.explored_fraction)
+        if agent.temp_relative:                              # the mean effective temperature THIS lock-step's envs drew at
+            info.update(temperature_effective=agent.temperature_effective)
         if agent.hindsight is not None:                      # the relabelled rows this lock-step pushed behind its own records
             info.update(hindsight_rows=agent.hindsight_rows)
         if agent.last_search is not None:                    # search in training: a lock-step that searched

@@ -551,6 +551,29 @@ int bridges_boltzmann_select(int32_t E, int32_t n_rows, const int32_t* seg_lo, c
                              float temperature, int32_t greedy, const int64_t* idx, const int32_t* cand_offset, const int32_t* rep,
                              int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w, float* p_sel, void* stream);
 
+/* RELATIVE TEMPERATURE: bridges_boltzmann_select and bridges_soft_expect at a temperature that is a multiple of each segment's own
+ * standard deviation of q, formed on the device in the same launch.  The rule, stated once for both operators; select_q is the
+ * array that weighs the rows (q for the select), segment e has its rows lo .. hi - 1:
+ *   - SPREAD: the FINITE rows are those whose select_q is neither NaN nor +-inf, n_f their number.  n_f < 2: s = 0.  Otherwise
+ *     mean = (sum (double)q_j) / n_f over the finite rows and s = sqrt(sum ((double)q_j - mean)^2 / n_f): the population standard
+ *     deviation, in two passes (the mean first, then the squared deviations; never E[x^2] - mean^2), float64 throughout, every sum
+ *     in a fixed order of the kernel's own (lane-strided partial sums combined by a fixed tree), so equal inputs give equal bits.
+ *   - EFFECTIVE TEMPERATURE: T_e = (double)temperature * fmax(s, (double)spread_floor), written as a double to temp_out[e]; the
+ *     floor keeps T_e > 0 where a segment's rows tie.  An empty segment, or one without finite rows, still writes
+ *     (double)temperature * (double)spread_floor.
+ *   - everything else is the scalar operator's rule at T = T_e, word for word: eligibility, m, the weights and the m = +inf case,
+ *     the strict inverse CDF with its fall-back row, p_sel and explore_w; value, feat_mean, entropy, argmax_row and the
+ *     nothing-eligible outputs.
+ *   - bridges_boltzmann_select_rel with greedy != 0 is bridges_boltzmann_select(greedy = 1) operand for operand; it writes
+ *     temp_out[e] = 0 and takes no spread.
+ * The argument lists are the scalar siblings' with spread_floor behind temperature and temp_out [E] / [n_trans] f64 before the
+ * stream; one launch, no atomics, no scratch, every output word written once.  Refused: whatever the sibling refuses; a
+ * spread_floor that is not finite or not > 0; a temp_out that is NULL or not 8-byte aligned. */
+int bridges_boltzmann_select_rel(int32_t E, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, const float* u,
+                                 float temperature, float spread_floor, int32_t greedy, const int64_t* idx, const int32_t* cand_offset,
+                                 const int32_t* rep, int64_t* sel_compact, int32_t* sel_index, float* q_sel, float* explore_w,
+                                 float* p_sel, double* temp_out, void* stream);
+
 /* Beam search: the top-B candidates of every group of B beams.  E = G * B envs, group g owns envs gB .. gB + B - 1; rows
  * seg_lo[e] .. seg_hi[e] of q / idx belong to env e exactly as for bridges_eps_greedy_select (rep may be NULL).  Inputs per env:
  * live[e] u8 (the beam is still open), ret[e] f64 (its discounted return so far), disc[e] f64 (the discount of its next reward).
@@ -754,6 +777,14 @@ int bridges_td_target_select(int32_t n_trans, const int32_t* seg_lo, const int32
 int bridges_soft_expect(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
                         float temperature, const float* feat, int64_t feat_row_stride, const int64_t* feat_row, int32_t dim,
                         float* value, float* feat_mean, float* entropy, int32_t* argmax_row, void* stream);
+
+/* bridges_soft_expect at the RELATIVE TEMPERATURE of every transition (the rule stands at bridges_boltzmann_select_rel): the
+ * spread is that of the transition's rows of select_q -- under double Q-learning the policy net's values, the array that weighs
+ * the rows, never next_q --, T_e goes to temp_out[i] as a double, and every other output is bridges_soft_expect's at T = T_e. */
+int bridges_soft_expect_rel(int32_t n_trans, const int32_t* seg_lo, const int32_t* seg_hi, const float* select_q, const float* next_q,
+                            float temperature, float spread_floor, const float* feat, int64_t feat_row_stride, const int64_t* feat_row,
+                            int32_t dim, float* value, float* feat_mean, float* entropy, int32_t* argmax_row, double* temp_out,
+                            void* stream);
 
 /* --- n-step returns of the vectorised loop ------------------------------------------------------------------------
  * The fold of one lock-step's one-step records rec [E, W] f64 (W >= BRIDGES_REC_WIDTH: the record plus its task tail) / valid [E]

@@ -5,8 +5,11 @@ inputs in one process and at the loop's launch shape (one wave per env over its 
                its step), ops.eps_greedy_select and ops.bits_accumulate_ (the count images of the explored choices)
   torch        the segmented softmax draw in torch: segment maxima by scatter_reduce, exp in float64, one cumsum over all rows,
                per-env targets, searchsorted, clamp, the gathers
-HIP events around single calls, the three legs alternating, warm-up first; one JSON line per shape with medians and spread.
-    python tools/boltzmann_select_bench.py [--envs 1024 4096] [--rows_per_env 40] [--temperature 1.0] [--reps 40]"""
+  relative     (--relative) ops.boltzmann_select(relative=True) (bridges_boltzmann_select_rel: the same launch shape with the
+               spread pass and temp_out), alternating with the scalar operator; the JSON line says whether its median lies
+               inside the scalar operator's own max - min spread
+HIP events around single calls, the legs alternating, warm-up first; one JSON line per shape with medians and spread.
+    python tools/boltzmann_select_bench.py [--envs 1024 4096] [--rows_per_env 40] [--temperature 1.0] [--reps 40] [--relative]"""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -21,6 +24,8 @@ ap.add_argument("--temperature", type=float, default=1.0)
 ap.add_argument("--steps", type=int, default=10, help="count images (episode steps)")
 ap.add_argument("--reps", type=int, default=40)
 ap.add_argument("--warmup", type=int, default=10)
+ap.add_argument("--relative", action="store_true", help="one more leg: the relative-temperature operator")
+ap.add_argument("--spread_floor", type=float, default=1e-3)
 a = ap.parse_args()
 assert a.reps >= 20
 dev = torch.device("cuda:0")
@@ -44,6 +49,9 @@ for E in a.envs:
     def boltzmann():
         return ops.boltzmann_select(seg, q, u, T, False, idx, cand_offset)
 
+    def relative():
+        return ops.boltzmann_select(seg, q, u, T, False, idx, cand_offset, relative=True, spread_floor=a.spread_floor)
+
     def eps_greedy():
         join = ops.bits_dot(cand_bits, images, step_of_row, bits_row=idx)
         out = ops.eps_greedy_select(seg, q, join, u, 0.5, False, idx, cand_offset)
@@ -64,7 +72,7 @@ for E in a.envs:
     k, f = boltzmann(), formulation()
     same = (k[0] == f[0]).float().mean().item()          # one global cumsum is another order of additions: near-ties may differ
     assert same > 0.999, same
-    legs = (("boltzmann", boltzmann), ("eps_greedy", eps_greedy), ("torch", formulation))
+    legs = (("boltzmann", boltzmann), ("eps_greedy", eps_greedy), ("torch", formulation)) + ((("relative", relative),) if a.relative else ())
     for _ in range(a.warmup):
         for _name, fn in legs:
             fn()
@@ -91,5 +99,8 @@ for E in a.envs:
                           inside_the_spread={name: bool(abs(summary[name]["median_us"] - b["median_us"])
                                                         <= max(summary[name]["max_us"] - summary[name]["min_us"], b["max_us"] - b["min_us"]))
                                              for name in ("eps_greedy", "torch")},
+                          **(dict(relative_over_boltzmann=summary["relative"]["median_us"] / b["median_us"],
+                                  relative_inside_boltzmanns_own_spread=bool(abs(summary["relative"]["median_us"] - b["median_us"])
+                                                                             <= b["max_us"] - b["min_us"])) if a.relative else {}),
                           note="HIP events around single calls (host launch gaps included), the legs alternating in one process; "
                                "spread = max - min of the timed calls")), flush=True)

@@ -7,6 +7,9 @@ lock-step holds the fold AND the update, and the count should be that of the sam
 lock-step with n-step returns (the fold and the compaction of its rows): the count should be that of the same line without it.
 --double_q runs it with double Q-learning targets (a second forward over the next-state rows): the count should not change either.
 --target_temperature T runs it with expected-value targets (bridges_soft_expect; its two log means ride with the losses): nor here.
+--temp_relative (with --exploration boltzmann) / --target_temp_relative (with --target_temperature T) [--spread_floor F] make those
+temperatures multiples of each state's spread of q (the sum of the effective temperatures rides with the counts, their mean over
+the sampled transitions with the losses): nor here.
 --prioritized_replay [--priority_alpha A] [--priority_refresh] runs it on prioritised replay; the sampler kernel and the refresh add
 launches, and the count should be that of plain --prioritized_replay; --priority_beta B [--priority_beta_anneal N] adds the
 importance-sampling weights (one more launch, no wait)."""
@@ -31,6 +34,7 @@ from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomTargets, VecAssemblyGym
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_target_temperature_argument, target_temperature_from_args,
+                                                add_relative_temperature_arguments, relative_temperature_from_args,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
@@ -40,6 +44,7 @@ add_n_step_argument(ap)
 add_double_q_argument(ap)
 add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
 add_priority_arguments(ap, prioritized_flag=True)
+add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
@@ -62,7 +67,8 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True)
                "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes or a.random_targets), per_env_obstacles=bool(sizes),
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
                **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
-               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)))
+               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
+               **relative_temperature_from_args(vars(a)))
 
 
 def lockstep():

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_target_temperature_argument, target_temperature_from_args,
+                                                add_relative_temperature_arguments, relative_temperature_from_args,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_eval_beam_argument, add_search_arguments,
@@ -59,6 +60,7 @@ add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_
 add_double_q_argument(ap)                # --double_q: double Q-learning targets (VecDQN(double_q=True))
 add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
 add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
+add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_eval_beam_argument(ap)               # --eval_beam B: beam search of width B on the evaluation tasks (VecDQN.beam_search)
@@ -104,7 +106,8 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True)
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
                **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
-               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)))
+               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
+               **relative_temperature_from_args(vars(a)))
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
@@ -150,6 +153,10 @@ for it in range(1, a.locksteps + 1):
             soft = [d.soft for d in deferred if d.soft is not None]
             line.update(target_entropy=r4(float(np.mean([s["target_entropy"] for s in soft])) if soft else None),
                         soft_value_gap=r4(float(np.mean([s["soft_value_gap"] for s in soft])) if soft else None))
+            if agent.target_temp_relative:                      # ... and of the mean effective temperature of the backups
+                line.update(target_temperature_effective=r4(float(np.mean([s["target_temperature_effective"] for s in soft])) if soft else None))
+        if agent.temp_relative:                                 # the block's last lock-step: the mean temperature its envs drew at
+            line.update(temperature_effective=r4(agent.temperature_effective))
         if agent.hindsight is not None:                         # the block's last lock-step: the relabelled rows it pushed
             line.update(hindsight_rows=agent.hindsight_rows)
         if agent.search_every:                                  # means over the block's searches, and the rows they pushed

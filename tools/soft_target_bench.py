@@ -6,7 +6,9 @@ next_targets are kept.  Then the operator is timed alone with HIP events on thos
 factored SuccessorMLP's feature rows) and for dim = 4096 (channel 0 of a module-forward net's output; random rows of the same
 count), alternating with the torch formulation: scatter_reduce(amax) and index_add_ over (transition, row) pairs for m, Z, the
 value and the entropy in float64, and one index_add_ of p * feat[row] in float32 for the feature mean (float64 there would cost
-torch a [pairs, dim] float64 temporary; the kernel sums in float64).  Prints one JSON line per dim: medians with min-max in
+torch a [pairs, dim] float64 temporary; the kernel sums in float64).  --relative adds a third leg, alternating with the two:
+dqn_ops.soft_expect(relative=True) (bridges_soft_expect_rel: the same grid with the spread pass and temp_out), and says whether
+its median lies inside the scalar operator's own max - min spread.  Prints one JSON line per dim: medians with min-max in
 microseconds."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +28,8 @@ ap.add_argument("--locksteps", type=int, default=12, help="rollout lock-steps be
 ap.add_argument("--transitions", type=int, default=800)
 ap.add_argument("--temperature", type=float, default=1.0)
 ap.add_argument("--reps", type=int, default=30)
+ap.add_argument("--relative", action="store_true", help="one more leg: the relative-temperature operator")
+ap.add_argument("--spread_floor", type=float, default=1e-3)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -74,6 +78,10 @@ def kernel_leg(feat):
     return dqn_ops.soft_expect(seen["seg"], nq, nq, T, feat=feat)
 
 
+def relative_leg(feat):
+    return dqn_ops.soft_expect(seen["seg"], nq, nq, T, feat=feat, relative=True, spread_floor=a.spread_floor)
+
+
 def timed(fn, feat):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -96,10 +104,19 @@ for name, feat in (("hidden", seen["feat"]), ("4096", torch.randn((R, 4096), dev
                  entropy=float((e_t - e_k)[live].abs().max()))
     for _ in range(3):                                                              # warm both legs
         timed(torch_leg, feat), timed(kernel_leg, feat)
-    t_torch, t_kernel = [], []
+        if a.relative:
+            timed(relative_leg, feat)
+    t_torch, t_kernel, t_rel = [], [], []
     for _ in range(a.reps):                                                         # legs alternating
         t_torch.append(timed(torch_leg, feat))
         t_kernel.append(timed(kernel_leg, feat))
+        if a.relative:
+            t_rel.append(timed(relative_leg, feat))
+    rel = {}
+    if a.relative:
+        k, r = stats(t_kernel), stats(t_rel)
+        rel = dict(relative=r, relative_over_kernel=round(r["median_us"] / k["median_us"], 3),
+                   relative_inside_kernels_own_spread=bool(abs(r["median_us"] - k["median_us"]) <= k["max_us"] - k["min_us"]))
     print(json.dumps(dict(bench="soft_expect", dim=int(feat.shape[1]), transitions=B, rows=R, pairs=int(ids.numel()),
                           longest_segment=int(length.max()), temperature=T, kernel=stats(t_kernel), torch=stats(t_torch),
-                          max_abs_difference=agree)), flush=True)
+                          max_abs_difference=agree, **rel)), flush=True)

@@ -294,6 +294,7 @@ SIGNATURES = {
     "bridges_family_draw": [C.c_uint64, i32, i32, vp, i32, i32, vp, vp, vp],
     "bridges_family_curriculum": [vp, i32, vp, i32, i32, f64, C.c_uint32, i32, vp, vp, vp],
     "bridges_replay_unpack": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_replay_unpack_prev": [i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_accumulate": [i32, vp, vp, vp, vp, vp, vp],
     "bridges_stability": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, vp, i64, vp],
     "bridges_stability_penalty": [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, vp, vp, vp, vp, i64, vp],
@@ -332,6 +333,9 @@ SIGNATURES = {
     "bridges_td_target_select": [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp],
     "bridges_soft_expect": [i32, vp, vp, vp, vp, f32, vp, i64, vp, i32, vp, vp, vp, vp, vp],
     "bridges_soft_expect_rel": [i32, vp, vp, vp, vp, f32, f32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp],
+    "bridges_soft_value": [i32, vp, vp, vp, f32, vp, f32, f32, vp, vp, vp, vp, vp],
+    "bridges_soft_value_rel": [i32, vp, vp, vp, f32, f32, vp, f32, f32, vp, vp, vp, vp, vp, vp],
+    "bridges_action_row": [i32, vp, vp, vp, vp, vp, vp, i64, vp, vp],
     "bridges_nstep_fold": [i32, i32, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_bits_discounted_sum": [i32, vp, i64, vp, vp, f32, vp, vp, vp],
     "bridges_priority_sample_scratch": [i64, C.POINTER(i64)],

@@ -121,8 +121,68 @@ def soft_expect(seg_offset, select_q, next_q, temperature, feat=None, feat_row=N
     return value, feat_mean, entropy, argmax_row
 
 
+def _segments(seg_offset, dev):
+    """td_target's two segment forms -> (seg_lo, seg_hi, B), int32 on ``dev``."""
+    if isinstance(seg_offset, (tuple, list)):
+        seg_lo, seg_hi = (t.to(device=dev, dtype=torch.int32).contiguous() for t in seg_offset)
+        assert seg_hi.numel() == seg_lo.numel()
+        return seg_lo, seg_hi, seg_lo.numel()
+    seg_offset = seg_offset.to(device=dev, dtype=torch.int32).contiguous()
+    B = seg_offset.numel() - 1
+    return seg_offset[:B], seg_offset[1:], B
+
+
+def soft_value(seg, q, temperature, taken_row=None, alpha=0.0, clip_lo=-1.0, relative=False, spread_floor=1e-3):
+    """The log-sum-exp value of every segment of q at ``temperature`` and, with ``taken_row`` int32 [B] (a row of q per segment;
+    0x7fffffff: none), the scaled log-policy of that row and the Munchausen bonus (bridges_soft_value; the rule stands in
+    include/bridges_hip.h).  seg as td_target takes it; q f32 [R], contiguous.
+    -> (value f32 [B], tlogp f32 [B], bonus f32 [B], miss uint8 [B]); the last three are None without taken_row.
+    tlogp = T ln pi(row) <= 0, bonus = alpha * max(tlogp, clip_lo), miss = 1 where the row is not an eligible row of the segment
+    (tlogp and bonus are 0 there).  ``relative`` (bridges_soft_value_rel): segment i is weighed at temperature * max(the standard
+    deviation of its finite q, spread_floor); that effective temperature is a further result, temp_out float64 [B]."""
+    L = abi.require_gpu()
+    dev = q.device
+    assert q.dtype == torch.float32 and q.is_contiguous()
+    seg_lo, seg_hi, B = _segments(seg, dev)
+    value = torch.empty(B, dtype=torch.float32, device=dev)
+    tlogp = bonus = miss = None
+    if taken_row is not None:
+        assert taken_row.dtype == torch.int32 and taken_row.is_contiguous() and taken_row.numel() == B and taken_row.device == dev
+        tlogp, bonus = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+        miss = torch.empty(B, dtype=torch.uint8, device=dev)
+    if relative:
+        temp_out = torch.empty(B, dtype=torch.float64, device=dev)
+        abi.check(L.bridges_soft_value_rel(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), float(temperature), float(spread_floor),
+                                           _ptr(taken_row), float(alpha), float(clip_lo), _ptr(value), _ptr(tlogp), _ptr(bonus),
+                                           _ptr(miss), _ptr(temp_out), _stream()), "bridges_soft_value_rel")
+        return value, tlogp, bonus, miss, temp_out
+    abi.check(L.bridges_soft_value(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), float(temperature), _ptr(taken_row), float(alpha),
+                                   float(clip_lo), _ptr(value), _ptr(tlogp), _ptr(bonus), _ptr(miss), _stream()), "bridges_soft_value")
+    return value, tlogp, bonus, miss
+
+
+def action_row(env, seg, idx, rec):
+    """The row of ``idx`` (the compact candidate rows of ``env``, valid_rows) that holds the action every record took
+    (bridges_action_row): row[i] = the first row of segment i whose candidate has the descriptor and the pose BITS of record i,
+    0x7fffffff if none.  seg as td_target takes it, one segment per record; rec float64 [B, W >= RECORD_WIDTH] whose rows are
+    contiguous (a row stride above W is taken).  -> int32 [B].  No host wait."""
+    L = abi.require_gpu()
+    dev = idx.device
+    assert idx.dtype == torch.int64 and idx.is_contiguous()
+    assert rec.dtype == torch.float64 and rec.dim() == 2 and rec.device == dev and (rec.shape[1] <= 1 or rec.stride(1) == 1)
+    seg_lo, seg_hi, B = _segments(seg, dev)
+    assert rec.shape[0] >= B
+    b = env.buf
+    row = torch.empty(B, dtype=torch.int32, device=dev)
+    abi.check(L.bridges_action_row(B, _ptr(seg_lo), _ptr(seg_hi), _ptr(idx), _ptr(b["cand_desc"]), _ptr(b["cand_pose"]), _ptr(rec),
+                                   int(rec.stride(0)) if rec.shape[0] > 1 else int(rec.shape[1]), _ptr(row), _stream()),
+              "bridges_action_row")
+    return row
+
+
 def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin=None, discount=None, select_q=None,
-                 temperature=None, next_feat=None, feat_row=None, feat_head=None, stats=None, relative=False, spread_floor=1e-3):
+                 temperature=None, next_feat=None, feat_row=None, feat_head=None, stats=None, relative=False, spread_floor=1e-3,
+                 munchausen=None, cur_seg=None, cur_q=None, taken_row=None):
     """The TD targets of transitions whose next-state rows are the segments ``seg`` of ``next_q`` (td_target's seg_offset).
     -> (q [B], sf [B, D] or None).  With ``lin``: q = lin + gamma q' of each segment's arg-max row, sf = lin + gamma psi' of
     that row + the action raster.  lin=None is the single-env reference form: q is the done-masked q' of the arg-max row (lin 0,
@@ -140,7 +200,17 @@ def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin
     action_raster + d * (done ? 0 : expected psi'), so done, discount, gamma and the -inf marking of an empty segment that is
     not done are that kernel's.  next_sf is not used then.  ``stats`` (a dict) receives stage one's value, entropy and
     argmax_row.  ``relative`` / ``spread_floor`` go to stage one (soft_expect's; ``stats`` then receives temp_out too); stage two
-    is unchanged.  temperature=None: every line below the block is the path as it was."""
+    is unchanged.  temperature=None: every line below the block is the path as it was.
+    ``munchausen`` = (alpha, clip_lo) (with ``temperature``): Munchausen targets.  Stage one is unchanged, so the expected psi',
+    the entropy and the statistics -- and with them sf -- stay the soft target's.  Stage one-b is soft_value twice: over the next
+    segments of select_q (next_q when select_q is None) for the log-sum-exp value V', and over the segments ``cur_seg`` of
+    ``cur_q`` f32 (the same net's q over the candidates of the state each transition was taken in) with ``taken_row`` int32 [B]
+    (action_row's) for the bonus alpha * max(T ln pi(a|s), clip_lo); ``relative`` gives each call its own segments' spread.
+    Stage two then runs twice on the one-row segments: with V' for next_q and lin + bonus for lin it gives q, with stage one's
+    value and the expected psi' it gives sf as ever.  ``stats`` receives soft_value=V', tlogp, bonus and miss as well.
+    None: nothing of this is launched."""
+    if munchausen is not None and temperature is None:
+        raise ValueError("next_targets(munchausen=...) is formed under the Boltzmann policy: it needs temperature")
     if temperature is not None:
         if lin is None:
             raise ValueError("next_targets(temperature=...) is the vectorised form: it needs lin")
@@ -159,6 +229,16 @@ def next_targets(seg, next_q, done, gamma, next_sf=None, action_raster=None, lin
         one = torch.arange(done.numel() + 1, dtype=torch.int32, device=nq.device)
         q, sf, _ = td_target(one, value, lin, done, gamma, next_sf=sf_soft, action_raster=action_raster, discount=discount,
                              select_q=value)
+        if munchausen is not None:
+            alpha, clip_lo = munchausen
+            rel = dict(relative=True, spread_floor=spread_floor) if relative else {}
+            v_next = soft_value(seg, sel, temperature, **rel)[0]
+            cur = soft_value(cur_seg, cur_q.contiguous().float(), temperature, taken_row=taken_row, alpha=alpha, clip_lo=clip_lo, **rel)
+            tlogp, bonus, miss = cur[1], cur[2], cur[3]
+            if stats is not None:
+                stats.update(soft_value=v_next, tlogp=tlogp, bonus=bonus, miss=miss)
+            lin_m = lin.to(device=nq.device, dtype=torch.float32).reshape(-1) + bonus
+            q, _, _ = td_target(one, v_next, lin_m, done, gamma, discount=discount, select_q=v_next)
         return q, sf
     nq = next_q.contiguous().float()
     zeros = torch.zeros(done.numel(), dtype=torch.float32, device=nq.device) if lin is None else lin

@@ -818,11 +818,13 @@ class VecAssemblyGym:
             self.rebuild_contacts()
         self.refresh()
 
-    def load_records(self, rec):
+    def load_records(self, rec, prev=False):
         """load_states for the next states s' of sampled transition records ([n <= E, RECORD_WIDTH] float64,
         robotoddler/training/records.py): ONE launch (bridges_replay_unpack) writes the block lists, the candidate
         counts and the block ranges instead of the ~60 slice / cast / index launches of unpack_states + load_states;
-        envs beyond n repeat record 0.  Returns (bits of s, lin_reward f32, stable(s) f32, done u8, stable(s') u8), [E] each."""
+        envs beyond n repeat record 0.  Returns (bits of s, lin_reward f32, stable(s) f32, done u8, stable(s') u8), [E] each.
+        ``prev=True`` (bridges_replay_unpack_prev): the env is loaded with the states s the transitions were taken IN -- the
+        block lists as stored, their candidate counts -- and everything else is as above (the returned bits are the env's own)."""
         E, K, dev = self.E, self.K, self.device
         assert rec.dtype == torch.float64 and rec.is_contiguous() and 1 <= rec.shape[0] <= E
         if getattr(self, "_nv_dev", None) is None:
@@ -831,11 +833,13 @@ class VecAssemblyGym:
         lin, stable_s = torch.empty(E, dtype=torch.float32, device=dev), torch.empty(E, dtype=torch.float32, device=dev)
         done, stable_n = torch.empty(E, dtype=torch.uint8, device=dev), torch.empty(E, dtype=torch.uint8, device=dev)
         b = self.buf
-        abi.check(self.L.bridges_replay_unpack(E, rec.shape[0], K, _ptr(rec), _ptr(self._nv_dev), self._nv_dev.numel(),
-                                               len(self.groups), len(self.x_discr_ground), len(self.offset_values),
-                                               _ptr(b["n_blocks"]), _ptr(b["blk_shape"]), _ptr(b["blk_pose"]), _ptr(b["blk_occ"]),
-                                               _ptr(b["n_cand"]), _ptr(ranges[0]), _ptr(ranges[1]), _ptr(lin), _ptr(stable_s),
-                                               _ptr(done), _ptr(stable_n), _stream()), "bridges_replay_unpack")
+        unpack, name = ((self.L.bridges_replay_unpack_prev, "bridges_replay_unpack_prev") if prev
+                        else (self.L.bridges_replay_unpack, "bridges_replay_unpack"))
+        abi.check(unpack(E, rec.shape[0], K, _ptr(rec), _ptr(self._nv_dev), self._nv_dev.numel(),
+                         len(self.groups), len(self.x_discr_ground), len(self.offset_values),
+                         _ptr(b["n_blocks"]), _ptr(b["blk_shape"]), _ptr(b["blk_pose"]), _ptr(b["blk_occ"]),
+                         _ptr(b["n_cand"]), _ptr(ranges[0]), _ptr(ranges[1]), _ptr(lin), _ptr(stable_s),
+                         _ptr(done), _ptr(stable_n), _stream()), name)
         b["needs_reset"].zero_()
         b["n_if"].zero_()                             # interfaces: rebuild_contacts() (stable_actions_only) or none
         self._contacts_current = False

@@ -17,6 +17,7 @@
 #include "fork_kernels.hip"
 #include "beam_kernels.hip"
 #include "soft_target_kernels.hip"
+#include "munchausen_kernels.hip"
 
 using namespace bridges;
 
@@ -840,6 +841,63 @@ int bridges_soft_expect_rel(int32_t n_trans, const int32_t* seg_lo, const int32_
                   argmax_row, temp_out);
 }
 
+// What bridges_soft_value and bridges_soft_value_rel refuse alike (bridges_soft_expect's refusals, then their own).
+static int soft_value_check(const char* who, int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, float temperature,
+                            const int32_t* taken_row, float alpha, float clip_lo, const float* value, const float* tlogp,
+                            const float* bonus, const uint8_t* miss) {
+    if (n < 0) return fail_arg(who, "negative count");
+    if (!(temperature > 0.f && temperature < INFINITY))                           // (a NaN fails the comparison)
+        return fail_arg(who, "the temperature must be finite and > 0");
+    if (!(alpha >= 0.f && alpha <= 1.f)) return fail_arg(who, "alpha must lie in [0, 1]");
+    if (!(clip_lo <= 0.f && clip_lo > -INFINITY)) return fail_arg(who, "clip_lo must be finite and <= 0");
+    if (!aligned(4, seg_lo, seg_hi, taken_row) || !aligned(4, q, value, tlogp, bonus)) return fail_arg(who, "misaligned pointer");
+    if (n == 0) return BRIDGES_OK;
+    if (!seg_lo || !seg_hi || !q || !value) return fail_arg(who, "null pointer");
+    if (taken_row && (!tlogp || !bonus || !miss)) return fail_arg(who, "taken_row needs tlogp, bonus and miss");
+    return BRIDGES_OK;
+}
+
+int bridges_soft_value(int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, float temperature,
+                       const int32_t* taken_row, float alpha, float clip_lo, float* value, float* tlogp, float* bonus, uint8_t* miss,
+                       void* stream) {
+    if (int rc = soft_value_check("bridges_soft_value", n, seg_lo, seg_hi, q, temperature, taken_row, alpha, clip_lo, value, tlogp,
+                                  bonus, miss))
+        return rc;
+    if (n == 0) return BRIDGES_OK;
+    // one wave per segment, four segments per workgroup
+    return launch("k_soft_value", k_soft_value, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, (int)n, seg_lo, seg_hi, q,
+                  temperature, taken_row, alpha, clip_lo, value, tlogp, bonus, miss);
+}
+
+int bridges_soft_value_rel(int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, float temperature,
+                           float spread_floor, const int32_t* taken_row, float alpha, float clip_lo, float* value, float* tlogp,
+                           float* bonus, uint8_t* miss, double* temp_out, void* stream) {
+    if (int rc = soft_value_check("bridges_soft_value_rel", n, seg_lo, seg_hi, q, temperature, taken_row, alpha, clip_lo, value,
+                                  tlogp, bonus, miss))
+        return rc;
+    if (!(spread_floor > 0.f && spread_floor < INFINITY))
+        return fail_arg("bridges_soft_value_rel: the spread floor must be finite and > 0");
+    if (!aligned(8, temp_out)) return fail_arg("bridges_soft_value_rel: temp_out must be 8-byte aligned");
+    if (n == 0) return BRIDGES_OK;
+    if (!temp_out) return fail_arg("bridges_soft_value_rel: null pointer");
+    // bridges_soft_value's grid
+    return launch("k_soft_value_rel", k_soft_value_rel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, (int)n, seg_lo, seg_hi,
+                  q, temperature, spread_floor, taken_row, alpha, clip_lo, value, tlogp, bonus, miss, temp_out);
+}
+
+int bridges_action_row(int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const int64_t* idx, const int32_t* cand_desc,
+                       const double* cand_pose, const double* rec, int64_t rec_stride, int32_t* row, void* stream) {
+    if (n < 0) return fail_arg("bridges_action_row: negative count");
+    if (rec_stride < BRIDGES_REC_WIDTH) return fail_arg("bridges_action_row: a record has at least BRIDGES_REC_WIDTH columns");
+    if (!seg_lo || !seg_hi || !idx || !cand_desc || !cand_pose || !rec || !row) return fail_arg("bridges_action_row: null pointer");
+    if (!aligned(4, seg_lo, seg_hi, row) || !aligned(8, idx) || !aligned(8, cand_pose, rec) || !aligned(16, cand_desc))
+        return fail_arg("bridges_action_row: misaligned pointer");
+    if (n == 0) return BRIDGES_OK;
+    // one wave per transition, four per workgroup
+    return launch("k_action_row", k_action_row, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, (int)n, seg_lo, seg_hi, idx,
+                  cand_desc, cand_pose, rec, rec_stride, row);
+}
+
 int bridges_nstep_fold(int32_t E, int32_t W, int32_t n, const double* rec, const uint8_t* valid, double gamma, int32_t* count,
                        double* acc, double* disc, double* stable_s, double* td, double* out, uint8_t* out_valid, void* stream) {
     if (E < 0 || n < 1 || n > BRIDGES_NSTEP_MAX) return fail_arg("bridges_nstep_fold: n must be 1..BRIDGES_NSTEP_MAX");
@@ -1170,6 +1228,19 @@ int bridges_replay_unpack(int32_t E, int32_t n_rec, int32_t K, const double* rec
         !ranges_prev || !lin || !stable_s || !done || !stable_n)
         return fail_arg("bridges_replay_unpack");
     return launch("k_replay_unpack", k_replay_unpack, dim3((unsigned)E), dim3(64), 0, stream, E, n_rec, K, rec, shape_faces, n_shapes,
+                  n_groups, n_ground, n_off, n_blocks, blk_shape, blk_pose, blk_occ, n_cand, ranges_next, ranges_prev, lin, stable_s,
+                  done, stable_n);
+}
+
+int bridges_replay_unpack_prev(int32_t E, int32_t n_rec, int32_t K, const double* rec, const int32_t* shape_faces, int32_t n_shapes,
+                          int32_t n_groups, int32_t n_ground, int32_t n_off, int32_t* n_blocks, int32_t* blk_shape,
+                          double* blk_pose, uint8_t* blk_occ, int32_t* n_cand, int32_t* ranges_next, int32_t* ranges_prev,
+                          float* lin, float* stable_s, uint8_t* done, uint8_t* stable_n, void* stream) {
+    if (E < 0 || n_rec < 1 || n_rec > E || K < 1 || K > BRIDGES_REC_K || !rec || !shape_faces || n_shapes < 1 || n_groups < 0 ||
+        n_ground < 0 || n_off < 0 || !n_blocks || !blk_shape || !blk_pose || !blk_occ || !n_cand || !ranges_next ||
+        !ranges_prev || !lin || !stable_s || !done || !stable_n)
+        return fail_arg("bridges_replay_unpack_prev");
+    return launch("k_replay_unpack_prev", k_replay_unpack_prev, dim3((unsigned)E), dim3(64), 0, stream, E, n_rec, K, rec, shape_faces, n_shapes,
                   n_groups, n_ground, n_off, n_blocks, blk_shape, blk_pose, blk_occ, n_cand, ranges_next, ranges_prev, lin, stable_s,
                   done, stable_n);
 }

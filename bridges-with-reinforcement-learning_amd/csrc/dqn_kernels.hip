@@ -811,14 +811,18 @@ __global__ __launch_bounds__(EPISODE_STATS_THREADS) void k_episode_stats(
     }
 }
 
-__global__ __launch_bounds__(64) void k_replay_unpack(int E, int n_rec, int K, const double* __restrict__ rec,
-                                                      const int32_t* __restrict__ shape_faces, int n_shapes, int n_groups, int n_ground, int n_off,
-                                                      int32_t* __restrict__ n_blocks, int32_t* __restrict__ blk_shape,
-                                                      double* __restrict__ blk_pose, uint8_t* __restrict__ blk_occ,
-                                                      int32_t* __restrict__ n_cand, int32_t* __restrict__ ranges_next,
-                                                      int32_t* __restrict__ ranges_prev, float* __restrict__ lin,
-                                                      float* __restrict__ stable_s, uint8_t* __restrict__ done,
-                                                      uint8_t* __restrict__ stable_n) {
+// One body for k_replay_unpack and k_replay_unpack_prev.  PREV loads the state s the transition was taken IN: the block list as
+// stored (no action block, no occupancy update), n_blocks = NB, the candidate count of the free faces of s, and both ranges cover
+// s; the scalar outputs are the same.
+template <bool PREV>
+__device__ __forceinline__ void replay_unpack_body(int E, int n_rec, int K, const double* __restrict__ rec,
+                                                   const int32_t* __restrict__ shape_faces, int n_shapes, int n_groups, int n_ground, int n_off,
+                                                   int32_t* __restrict__ n_blocks, int32_t* __restrict__ blk_shape,
+                                                   double* __restrict__ blk_pose, uint8_t* __restrict__ blk_occ,
+                                                   int32_t* __restrict__ n_cand, int32_t* __restrict__ ranges_next,
+                                                   int32_t* __restrict__ ranges_prev, float* __restrict__ lin,
+                                                   float* __restrict__ stable_s, uint8_t* __restrict__ done,
+                                                   uint8_t* __restrict__ stable_n) {
     const int e = blockIdx.x, k = threadIdx.x;
     if (e >= E) return;
     const double* r = rec + (size_t)(e < n_rec ? e : 0) * BRIDGES_REC_WIDTH;     // padding envs repeat the first record
@@ -832,27 +836,27 @@ __global__ __launch_bounds__(64) void k_replay_unpack(int E, int n_rec, int K, c
         double p[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) p[j] = r[BRIDGES_REC_POSE + 4 * k + j];
-        if (k == slot) {                                                   // the action block
+        if (!PREV && k == slot) {                                          // the action block
             shape = (int)r[BRIDGES_REC_ASHAPE];
             occ = (1 << (int)r[BRIDGES_REC_AFACE]) & 255;
 #pragma unroll
             for (int j = 0; j < 4; ++j) p[j] = r[BRIDGES_REC_APOSE + j];
         }
-        if (tb >= 0 && k == tb) occ |= (1 << (int)r[BRIDGES_REC_ATF]) & 255;   // the face it was put on
+        if (!PREV && tb >= 0 && k == tb) occ |= (1 << (int)r[BRIDGES_REC_ATF]) & 255;   // the face it was put on
         blk_shape[(size_t)e * K + k] = shape;
         blk_occ[(size_t)e * K + k] = (uint8_t)occ;
 #pragma unroll
         for (int j = 0; j < 4; ++j) blk_pose[((size_t)e * K + k) * 4 + j] = p[j];
-        if (k <= nb && k < K) free_faces = shape_faces[shape < 0 ? 0 : (shape < n_shapes ? shape : n_shapes - 1)] - __builtin_popcount(occ & ((1 << BRIDGES_MAX_VERTS) - 1));
+        if ((PREV ? k < nb : k <= nb) && k < K) free_faces = shape_faces[shape < 0 ? 0 : (shape < n_shapes ? shape : n_shapes - 1)] - __builtin_popcount(occ & ((1 << BRIDGES_MAX_VERTS) - 1));
     }
     int nfree = free_faces;                                                // lanes >= K hold 0
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) nfree += __shfl_xor(nfree, m);
     if (k == 0) {
-        n_blocks[e] = nb + 1;
+        n_blocks[e] = PREV ? nb : nb + 1;
         n_cand[e] = n_groups * (n_ground + nfree * n_off);     // raw count: bridges_env_refresh clamps to the env's a_max and flags it
         ranges_next[2 * e] = e * K;
-        ranges_next[2 * e + 1] = e * K + nb + 1;
+        ranges_next[2 * e + 1] = PREV ? e * K + nb : e * K + nb + 1;
         ranges_prev[2 * e] = e * K;
         ranges_prev[2 * e + 1] = e * K + nb;
         lin[e] = (float)r[BRIDGES_REC_LIN];
@@ -860,6 +864,30 @@ __global__ __launch_bounds__(64) void k_replay_unpack(int E, int n_rec, int K, c
         done[e] = r[BRIDGES_REC_DONE] > 0.5;
         stable_n[e] = r[BRIDGES_REC_STABLE_N] > 0.5;
     }
+}
+
+__global__ __launch_bounds__(64) void k_replay_unpack(int E, int n_rec, int K, const double* __restrict__ rec,
+                                                      const int32_t* __restrict__ shape_faces, int n_shapes, int n_groups, int n_ground, int n_off,
+                                                      int32_t* __restrict__ n_blocks, int32_t* __restrict__ blk_shape,
+                                                      double* __restrict__ blk_pose, uint8_t* __restrict__ blk_occ,
+                                                      int32_t* __restrict__ n_cand, int32_t* __restrict__ ranges_next,
+                                                      int32_t* __restrict__ ranges_prev, float* __restrict__ lin,
+                                                      float* __restrict__ stable_s, uint8_t* __restrict__ done,
+                                                      uint8_t* __restrict__ stable_n) {
+    replay_unpack_body<false>(E, n_rec, K, rec, shape_faces, n_shapes, n_groups, n_ground, n_off, n_blocks, blk_shape, blk_pose, blk_occ, n_cand,
+                              ranges_next, ranges_prev, lin, stable_s, done, stable_n);
+}
+
+__global__ __launch_bounds__(64) void k_replay_unpack_prev(int E, int n_rec, int K, const double* __restrict__ rec,
+                                                           const int32_t* __restrict__ shape_faces, int n_shapes, int n_groups, int n_ground, int n_off,
+                                                           int32_t* __restrict__ n_blocks, int32_t* __restrict__ blk_shape,
+                                                           double* __restrict__ blk_pose, uint8_t* __restrict__ blk_occ,
+                                                           int32_t* __restrict__ n_cand, int32_t* __restrict__ ranges_next,
+                                                           int32_t* __restrict__ ranges_prev, float* __restrict__ lin,
+                                                           float* __restrict__ stable_s, uint8_t* __restrict__ done,
+                                                           uint8_t* __restrict__ stable_n) {
+    replay_unpack_body<true>(E, n_rec, K, rec, shape_faces, n_shapes, n_groups, n_ground, n_off, n_blocks, blk_shape, blk_pose, blk_occ, n_cand,
+                              ranges_next, ranges_prev, lin, stable_s, done, stable_n);
 }
 
 }  // namespace bridges

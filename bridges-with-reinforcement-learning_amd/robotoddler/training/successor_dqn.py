@@ -586,6 +586,7 @@ def build_parser():
     add_double_q_argument(p)
     add_target_temperature_argument(p)
     add_relative_temperature_arguments(p)
+    add_munchausen_arguments(p)
     add_priority_arguments(p)
     add_exploration_arguments(p)
     add_hindsight_arguments(p)
@@ -808,6 +809,51 @@ def check_relative_temperature(args):
         raise SystemExit(f"{' / '.join(given)} need the vectorised loop (--num_envs N, N > 1): the single-env loop draws and backs "
                          "up at one temperature for every state")
     relative_temperature_from_args(args)
+
+
+def add_munchausen_arguments(p):
+    """--munchausen_alpha / --munchausen_clip: shared with the tools that train through the vectorised loop."""
+    p.add_argument("--munchausen_alpha", type=float, default=argparse.SUPPRESS, metavar="A",
+                   help="Vectorised loop with --target_temperature T: Munchausen targets -- q = r + A * max(T ln pi(a|s), L0) + gamma * "
+                        "V_T(s'), pi = softmax(q' / T) of the target net and V_T the log-sum-exp value (bridges_soft_value; the taken "
+                        "action is found among the rebuilt candidates of s by bridges_action_row). A in [0, 1]. Logs "
+                        "munchausen_bonus, munchausen_clipped and munchausen_missed. Not with --double_q or --n_step N > 1.")
+    p.add_argument("--munchausen_clip", type=float, default=argparse.SUPPRESS, metavar="L0",
+                   help="With --munchausen_alpha: the lower clip of T ln pi(a|s) (finite, <= 0; -1.0).")
+
+
+def munchausen_from_args(args):
+    """--munchausen_alpha A [--munchausen_clip L0] -> VecDQN's keywords, nothing without the flags; refused in words (SystemExit)
+    where the loop cannot run them."""
+    given = [f"--{k}" for k in ('munchausen_alpha', 'munchausen_clip') if k in args]
+    if not given:
+        return {}
+    who = ' / '.join(given)
+    if 'munchausen_alpha' not in args:
+        raise SystemExit("--munchausen_clip clips the Munchausen bonus: it needs --munchausen_alpha A")
+    A, L0 = args['munchausen_alpha'], args.get('munchausen_clip', -1.0)
+    if not (0.0 <= A <= 1.0):                                # (a NaN fails both comparisons)
+        raise SystemExit(f"--munchausen_alpha must lie in [0, 1], got {A}")
+    if not (float("-inf") < L0 <= 0.0):
+        raise SystemExit(f"--munchausen_clip must be a finite number <= 0, got {L0}")
+    if args.get('target_temperature') is None:
+        raise SystemExit(f"{who}: the bonus and the bootstrap are formed under the Boltzmann policy of the target net: it needs "
+                         "--target_temperature T")
+    if args.get('double_q'):
+        raise SystemExit(f"{who} does not run with --double_q: the bonus and the bootstrap are one estimator's, the target net's")
+    if args.get('n_step', 1) > 1:
+        raise SystemExit(f"{who} needs --n_step 1: an h-step row does not hold the descriptors of its intermediate actions, and "
+                         "their bonuses would take h forwards")
+    return dict(munchausen_alpha=A, munchausen_clip=L0)
+
+
+def check_munchausen(args):
+    """The two flags: refused in words (SystemExit) where the loop cannot run them, before anything touches the GPU."""
+    given = [f"--{k}" for k in ('munchausen_alpha', 'munchausen_clip') if k in args]
+    if given and args['num_envs'] <= 1:
+        raise SystemExit(f"{' / '.join(given)} need the vectorised loop (--num_envs N, N > 1): the single-env loop trains on the "
+                         "reference's target, the maximum over the next actions")
+    munchausen_from_args(args)
 
 
 def add_eval_beam_argument(p):
@@ -1105,6 +1151,7 @@ def main(argv=None):
     check_double_q(args)
     check_target_temperature(args)
     check_relative_temperature(args)
+    check_munchausen(args)
     check_priority(args)
     check_exploration(args)
     check_hindsight(args)

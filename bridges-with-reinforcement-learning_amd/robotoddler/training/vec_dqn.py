@@ -77,6 +77,7 @@ class VecDQN:
     target_temperature = _soft_stats = target_entropy = soft_value_gap = None
     temp_relative = target_temp_relative = False
     spread_floor, temperature_effective, target_temperature_effective, _temp_out = 1e-3, None, None, None
+    munchausen = replay_env_s = munchausen_bonus = munchausen_clipped = munchausen_missed = None
 
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
@@ -84,7 +85,8 @@ class VecDQN:
                  n_step=1, double_q=False, priority_alpha=1.0, priority_refresh=False, priority_beta=None, priority_beta_anneal=0,
                  exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1,
                  search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None,
-                 target_temperature=None, temp_relative=False, target_temp_relative=False, spread_floor=1e-3):
+                 target_temperature=None, temp_relative=False, target_temp_relative=False, spread_floor=1e-3,
+                 munchausen_alpha=None, munchausen_clip=None):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -186,7 +188,41 @@ class VecDQN:
         over the last lock-step's valid envs (it rides with the counts), target_temperature_effective the mean over the last
         train_steps call's transitions that are not done (it rides with the losses): no host wait of their own.  Both compose
         with whatever their parent option composes with; evaluation and beam search stay greedy.  ``spread_floor`` (finite,
-        > 0; default 1e-3) is refused unless one of the two is set.  False is the loop as it was: no launch of this."""
+        > 0; default 1e-3) is refused unless one of the two is set.  False is the loop as it was: no launch of this.
+        ``munchausen_alpha=A`` (in [0, 1]; with target_temperature only; DESIGN.md section 7, "Munchausen targets"): Munchausen
+        DQN.  With pi = softmax(q' / T) of the target net, q = r + A * max(T ln pi(a|s), ``munchausen_clip``) + gamma * V_T(s'),
+        V_T = T ln sum exp(q' / T) the log-sum-exp value in place of the expectation (bridges_soft_value over the next rows, and
+        over the rows of the state the transition was taken IN with the taken action's row, bridges_action_row).  A second
+        scratch env, replay_env_s, rebuilds the candidates of s (load_records(prev=True)) and the target net runs over them:
+        one more host wait per train_steps call (its valid_rows).  The successor-feature target stays the soft target's.
+        ``munchausen_clip`` (finite, <= 0; default -1.0) is refused without munchausen_alpha.  target_temp_relative gives each
+        of s and s' its own spread.  Refused with double_q (the bonus and the bootstrap are one estimator's) and with n_step > 1
+        (an h-step row does not hold its intermediate actions).  munchausen_bonus (the mean bonus), munchausen_clipped (the
+        share at or below the clip) and munchausen_missed (taken actions not found among the rebuilt candidates; 0) ride with
+        the losses.  None is the loop as it was: no launch of this, no second env."""
+        self.munchausen = None
+        if munchausen_clip is not None and munchausen_alpha is None:
+            raise ValueError("VecDQN(munchausen_clip=...) clips the Munchausen bonus: it needs munchausen_alpha")
+        if munchausen_alpha is not None:
+            clip = -1.0 if munchausen_clip is None else munchausen_clip
+            for name, v in (("munchausen_alpha", munchausen_alpha), ("munchausen_clip", clip)):
+                if not isinstance(v, (int, float)) or isinstance(v, bool):
+                    raise ValueError(f"VecDQN({name}={v!r}): a number")
+            if not 0.0 <= float(munchausen_alpha) <= 1.0:                            # (a NaN fails both comparisons)
+                raise ValueError(f"VecDQN(munchausen_alpha={munchausen_alpha!r}): the weight of the log-policy bonus lies in [0, 1]")
+            if not float("-inf") < float(clip) <= 0.0:
+                raise ValueError(f"VecDQN(munchausen_clip={clip!r}): the lower clip of T ln pi is finite and <= 0")
+            if target_temperature is None:
+                raise ValueError("VecDQN(munchausen_alpha=...) forms its bonus and its bootstrap under the Boltzmann policy of the "
+                                 "target net: it needs target_temperature")
+            if double_q:
+                raise ValueError("VecDQN(munchausen_alpha=...) does not run with double_q=True: the bonus and the bootstrap are one "
+                                 "estimator's, the target net's")
+            if int(n_step) > 1:
+                raise ValueError("VecDQN(munchausen_alpha=...) needs n_step=1: an h-step row does not hold the descriptors of its "
+                                 "intermediate actions, and their bonuses would take h forwards")
+            self.munchausen = (float(munchausen_alpha), float(clip))
+        self.munchausen_bonus = self.munchausen_clipped = self.munchausen_missed = None
         self.temp_relative, self.target_temp_relative = bool(temp_relative), bool(target_temp_relative)
         if self.temp_relative and str(exploration) != "boltzmann":
             raise ValueError("VecDQN(temp_relative=True) makes the temperature of Boltzmann exploration relative to each state's "
@@ -341,6 +377,8 @@ class VecDQN:
         self.step_images = torch.zeros((env.K + 1, env.img, env.img), dtype=torch.float32, device=self.device)
         # scratch env used to rebuild the candidate sets of sampled next states (see _replay_env)
         self.replay_env = self._make_replay_env(batch_size)
+        # Munchausen targets: a second one for the states the transitions were taken in
+        self.replay_env_s = self._make_replay_env(batch_size) if self.munchausen is not None else None
         self.mse = torch.nn.MSELoss()
         for g in optimizer.param_groups:                # step counter on the device: the train step is graph-captured
             if 'capturable' in g:
@@ -1009,6 +1047,12 @@ class VecDQN:
             self.replay_env = self._make_replay_env(n_states)
         return self.replay_env
 
+    def _replay_env_s(self, n_states):
+        """The scratch env of the states s (Munchausen targets), grown as _replay_env grows its own."""
+        if self.replay_env_s.E < n_states:
+            self.replay_env_s = self._make_replay_env(n_states)
+        return self.replay_env_s
+
     def _replay_f32(self):
         """The scratch env writes f32 rasters of every raw candidate only for nets that consume them row by row; the
         factored MLP reads the bit rasters and expands the few rows it needs (the arg-max row of each transition)."""
@@ -1035,6 +1079,9 @@ class VecDQN:
         n = rec.shape[0]
         renv = self._replay_env(n)
         E = renv.E
+        munch = self.munchausen
+        renv_s = self._replay_env_s(n) if munch is not None else None
+        assert renv_s is None or renv_s.E == E
         horizon = None
         if self.n_step > 1:                                  # an h-step row: the record of the window's last step, then its tail, then h
             if rec.shape[1] != self.ring.width:
@@ -1045,11 +1092,12 @@ class VecDQN:
                 raise ValueError(f"per-env tasks: records of {R.RECORD_WIDTH + self.task_width} columns expected, got {rec.shape[1]}")
             tail = rec[:, R.RECORD_WIDTH:]
             tail = tail if n == E else torch.cat([tail, tail[:1].expand(E - n, -1)])
-            if self.per_env_obstacles:
-                nt = 3 * self.n_task_targets
-                renv.load_task(tail[:, :nt].contiguous(), tail[:, nt:].contiguous())
-            else:
-                renv.load_targets(tail)
+            for task_env in (renv,) if renv_s is None else (renv, renv_s):
+                if self.per_env_obstacles:
+                    nt = 3 * self.n_task_targets
+                    task_env.load_task(tail[:, :nt].contiguous(), tail[:, nt:].contiguous())
+                else:
+                    task_env.load_targets(tail)
             rec = rec[:, :R.RECORD_WIDTH]
         # state s' (= s + action block): candidates, masks, rasters by the same kernels as the rollout; s is the
         # prefix of its block list, so its raster comes out of the same per-block bit rasters.  One launch unpacks the
@@ -1112,24 +1160,48 @@ class VecDQN:
             nsf0 = lambda best: nsf[:, 0].index_select(0, best if inverse is None else inverse.index_select(0, best)).reshape(E, -1).contiguous()
             if soft and use_sf:                         # channel 0 of the distinct rows' outputs; row j stands at inverse[j]
                 soft_feat, soft_row = nsf[:, 0].reshape(nsf.shape[0], -1), inverse
+        relative = dict(relative=True, spread_floor=self.spread_floor) if self.target_temp_relative else {}
+        cur = {}
+        if munch is not None:
+            # Munchausen targets: the states s in the second scratch env, the target net's q over their candidates, and the row
+            # of each that holds the action its record took
+            rec_s = rec.contiguous()
+            rec_s = rec_s if n == E else torch.cat([rec_s, rec_s[:1].expand(E - n, -1)])     # envs beyond n repeat record 0
+            renv_s.load_records(rec_s, prev=True)
+            flag_s = stable_s.bool()
+            idx_s, row_env_s, seg_s, _ = self._rows(renv_s, flag_s)                  # transitions taken in the same state share rows
+            cur_q = (self._net_q(self.target_net, renv_s, idx_s, row_env_s, flag_s).contiguous().float() if idx_s.numel()
+                     else torch.zeros(1, dtype=torch.float32, device=self.device))
+            taken = (dqn_ops.action_row(renv_s, seg_s, idx_s, rec_s) if idx_s.numel()
+                     else torch.full((E,), 0x7fffffff, dtype=torch.int32, device=self.device))
+            cur = dict(munchausen=munch, cur_seg=seg_s, cur_q=cur_q, taken_row=taken)
         if idx.numel() and soft:
             stats = {}
-            relative = dict(relative=True, spread_floor=self.spread_floor) if self.target_temp_relative else {}
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, action_raster=sf_action.squeeze(1) if use_sf else None,
                                                        lin=lin, discount=discount, select_q=select_q, temperature=self.target_temperature,
-                                                       next_feat=soft_feat, feat_row=soft_row, feat_head=soft_head, stats=stats, **relative)
+                                                       next_feat=soft_feat, feat_row=soft_row, feat_head=soft_head, stats=stats, **relative,
+                                                       **cur)
             # the log's two means over the transitions that are not done; they wait on the device for the losses' copy
             # (of the n sampled ones: the scratch env's envs beyond n repeat record 0)
             at_max = nq.contiguous().float().index_select(0, stats["argmax_row"].long().clamp_(0, nq.numel() - 1))
             both = torch.stack([stats["entropy"], at_max - stats["value"]]
                                + ([stats["temp_out"].float()] if self.target_temp_relative else []))[:, :n]
             self._soft_stats = torch.where(done[:n], torch.zeros_like(both), both).sum(dim=1) / (~done[:n]).sum().clamp_(min=1)
+            if munch is not None:
+                # the log's three: the mean bonus, the share at or below the clip, the taken actions not found (over the n sampled)
+                found = stats["miss"][:n] == 0
+                extra = torch.stack([stats["bonus"][:n].mean(), ((stats["tlogp"][:n] <= munch[1]) & found).float().mean(),
+                                     stats["miss"][:n].sum().float()])
+                self._soft_stats = torch.cat([self._soft_stats, extra])
         elif idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
                                                        action_raster=sf_action.squeeze(1) if use_sf else None, lin=lin,
                                                        discount=discount, select_q=select_q)
         else:
             q_target = lin
+            if munch is not None:                            # no next candidate anywhere: the bonus is all the target adds
+                q_target = lin + dqn_ops.soft_value(seg_s, cur_q, self.target_temperature, taken_row=taken, alpha=munch[0],
+                                                    clip_lo=munch[1], **relative)[2]
             sf_target = sf_action.reshape(E, -1) if use_sf else None
         binary = torch.zeros((E, 6), dtype=torch.float32, device=self.device)
         binary[:, 0] = stable_s
@@ -1296,6 +1368,8 @@ class VecDQN:
             self.target_entropy, self.soft_value_gap = tail[:2]
             if self.target_temp_relative:
                 self.target_temperature_effective = tail[2]
+            if self.munchausen is not None and k >= 5:
+                self.munchausen_bonus, self.munchausen_clipped, self.munchausen_missed = tail[-3:]
         return drv.check_losses(losses) if drv is not None else losses
 
     def train_step(self):
@@ -1324,6 +1398,8 @@ class VecDQN:
             blob["target_temperature"] = float(self.target_temperature)
         if self.target_temp_relative:                        # one more key: ... and that it multiplies the spread, above which floor
             blob["target_temp_relative"] = float(self.spread_floor)
+        if self.munchausen is not None:                      # one more key: the weight and the clip of the Munchausen bonus
+            blob["munchausen"] = (float(self.munchausen[0]), float(self.munchausen[1]))
         if self.temp_relative:                               # one more key: what the schedule's temperature multiplies
             blob["temp_relative"] = float(self.spread_floor)
         if self.hindsight is not None:                       # two more keys: the setting and the running episodes
@@ -1363,6 +1439,11 @@ class VecDQN:
         if got_r != want_r:
             raise ValueError(f"{path} was written by a run with (target_temp_relative, spread_floor) = {got_r}, this agent has "
                              f"{want_r}: the nets were trained towards another backup operator")
+        # (a file of a run without Munchausen targets carries no entry)
+        got_m = tuple(float(v) for v in blob["munchausen"]) if "munchausen" in blob else None
+        if got_m != self.munchausen:
+            raise ValueError(f"{path} was written by a run with (munchausen_alpha, munchausen_clip) = {got_m}, this agent has "
+                             f"{self.munchausen}: the nets were trained towards another backup operator")
         # (a file of a run without hindsight relabelling carries no entry)
         got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
         want_h = (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None
@@ -1528,12 +1609,18 @@ class DeferredLosses:
                 self._done.synchronize()
                 self._list = self._host.tolist()
                 if self._owner is not None:
-                    k = 3 if getattr(self._owner, "target_temp_relative", False) else 2      # relative: the mean T_e behind them
+                    rel = 1 if getattr(self._owner, "target_temp_relative", False) else 0      # relative: the mean T_e behind them
+                    mun = 3 if getattr(self._owner, "munchausen", None) is not None else 0      # Munchausen: its three behind those
+                    k = 2 + rel + mun
                     self._list, tail = self._list[:-k], self._list[-k:]
                     self.soft = dict(target_entropy=tail[0], soft_value_gap=tail[1])
                     self._owner.target_entropy, self._owner.soft_value_gap = tail[:2]
-                    if k == 3:
+                    if rel:
                         self.soft["target_temperature_effective"] = self._owner.target_temperature_effective = tail[2]
+                    if mun:
+                        for key, v in zip(("munchausen_bonus", "munchausen_clipped", "munchausen_missed"), tail[-3:]):
+                            self.soft[key] = v
+                            setattr(self._owner, key, v)
                 if self._driver is not None:
                     self._driver.check_losses(self._list)
         return self._list
@@ -1556,6 +1643,9 @@ def lockstep_log_values(info):
     if 'target_entropy' in info:                             # soft targets only
         vals.update(target_entropy=info['target_entropy'], soft_value_gap=info['soft_value_gap'])
     for key in ('temperature_effective', 'target_temperature_effective'):         # relative temperatures only
+        if key in info:
+            vals[key] = info[key]
+    for key in ('munchausen_bonus', 'munchausen_clipped', 'munchausen_missed'):    # Munchausen targets only
         if key in info:
             vals[key] = info[key]
     if 'hindsight_rows' in info:                             # hindsight relabelling only
@@ -1658,7 +1748,7 @@ def next_multiple(n, every):
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
     from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets,
-                                                    relative_temperature_from_args, target_temperature_from_args,
+                                                    munchausen_from_args, relative_temperature_from_args, target_temperature_from_args,
                                                     search_from_args, track_run_sinks)
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
@@ -1709,7 +1799,7 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
                    priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
                    priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args),
                    **hindsight_from_args(args), **search_from_args(args), **target_temperature_from_args(args),
-                   **relative_temperature_from_args(args))
+                   **relative_temperature_from_args(args), **munchausen_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)

@@ -696,6 +696,14 @@ int bridges_replay_unpack(int32_t E, int32_t n_rec, int32_t K, const double* rec
                           int32_t n_groups, int32_t n_ground, int32_t n_off, int32_t* n_blocks, int32_t* blk_shape,
                           double* blk_pose, uint8_t* blk_occ, int32_t* n_cand, int32_t* ranges_next, int32_t* ranges_prev,
                           float* lin, float* stable_s, uint8_t* done, uint8_t* stable_n, void* stream);
+/* bridges_replay_unpack for the state s a transition was taken IN (Munchausen targets: the log-policy of the taken action is
+ * formed over the candidates of s): n_blocks = NB, the block list as the record stores it (no action block, no occupancy
+ * update), the raw candidate count of the free faces of s, ranges_next and ranges_prev both [e*K, e*K + NB).  The argument
+ * list, the scalar outputs and the refusals are bridges_replay_unpack's; one kernel body serves both. */
+int bridges_replay_unpack_prev(int32_t E, int32_t n_rec, int32_t K, const double* rec, const int32_t* shape_faces, int32_t n_shapes,
+                               int32_t n_groups, int32_t n_ground, int32_t n_off, int32_t* n_blocks, int32_t* blk_shape,
+                               double* blk_pose, uint8_t* blk_occ, int32_t* n_cand, int32_t* ranges_next, int32_t* ranges_prev,
+                               float* lin, float* stable_s, uint8_t* done, uint8_t* stable_n, void* stream);
 
 /* --- K7: DQN ops (robotoddler/training/successor_dqn.py) --------------------- */
 /* update_target_net (successor_dqn.py:280-288): target = policy*tau + target*one_minus_tau, the two products and the
@@ -785,6 +793,53 @@ int bridges_soft_expect_rel(int32_t n_trans, const int32_t* seg_lo, const int32_
                             float temperature, float spread_floor, const float* feat, int64_t feat_row_stride, const int64_t* feat_row,
                             int32_t dim, float* value, float* feat_mean, float* entropy, int32_t* argmax_row, double* temp_out,
                             void* stream);
+
+/* MUNCHAUSEN TARGETS: the entropy-regularised (log-sum-exp) value of a segment of q and the scaled log-policy T ln pi(a) of one
+ * of its rows, on top of the rule of bridges_boltzmann_select.  With pi = softmax(q / T) the Munchausen target is
+ *   r + alpha * clip(T ln pi(a|s), clip_lo, 0) + gamma * (1 - done) * V_T(s'),   V_T(s) = T ln sum_j exp(q_j / T),
+ * and T ln pi(a|s) = q(s, a) - V_T(s): this one operator serves both halves.  The rule, for segment i with the rows
+ * lo = seg_lo[i] .. seg_hi[i] - 1 of q (f32) and T = (double)temperature, all in float64:
+ *   - ELIGIBILITY, m and the WEIGHTS w_j are those of bridges_boltzmann_select, word for word; Z = sum_j w_j.
+ *   - VALUE: value[i] = (float)(m + T * log Z); m = +inf: +inf.  NOTHING ELIGIBLE (an empty segment included): value[i] = -inf and
+ *     nothing else of q is read.
+ *   - TAKEN ROW (taken_row i32 [n] given, a = taken_row[i]): if a lies in [lo, hi) and is eligible,
+ *       L = fmin(((double)q_a - m) - T * log Z, 0);  m = +inf: L = -(T * log Z) on a +inf row (Z is their number), -inf on any other;
+ *       tlogp[i] = (float)L,  bonus[i] = (float)((double)alpha * fmax(L, (double)clip_lo)), a zero written as +0.0,  miss[i] = 0.
+ *     If a lies outside the segment, is 0x7fffffff (bridges_action_row's no-match), is not eligible, or nothing is eligible:
+ *       tlogp[i] = 0, bonus[i] = +0.0, miss[i] = 1.
+ *     taken_row == NULL: tlogp, bonus and miss may be NULL and are not written.
+ * Both segment forms of bridges_td_target are taken; segments may share or overlap rows.  Every sum has a fixed order
+ * (lane-strided partial sums combined by a fixed tree), there are no atomics and every output word is written once: equal inputs
+ * give equal bits.  One launch, no scratch.
+ * Returns -1 and launches nothing for: what bridges_soft_expect refuses of the arguments they share (n < 0, a temperature that is
+ * not finite or not > 0, a float / int32 pointer that is not 4-byte aligned, with n > 0 a NULL seg_lo, seg_hi, q or value); an
+ * alpha that is not finite or outside [0, 1]; a clip_lo that is not finite or > 0; with taken_row given, a NULL tlogp, bonus or
+ * miss.  n == 0 returns 0 and launches nothing. */
+int bridges_soft_value(int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, float temperature,
+                       const int32_t* taken_row /* i32 [n] or NULL */, float alpha, float clip_lo, float* value, float* tlogp,
+                       float* bonus, uint8_t* miss, void* stream);
+
+/* bridges_soft_value at the RELATIVE TEMPERATURE of every segment (the rule stands at bridges_boltzmann_select_rel): the spread
+ * is that of the segment's own rows of q, T_e goes to temp_out[i] as a double (nothing eligible: temperature * spread_floor), and
+ * every other output is bridges_soft_value's at T = T_e.  Refused: whatever the sibling refuses; a spread_floor that is not
+ * finite or not > 0; a temp_out that is not 8-byte aligned or, with n > 0, NULL. */
+int bridges_soft_value_rel(int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const float* q, float temperature,
+                           float spread_floor, const int32_t* taken_row, float alpha, float clip_lo, float* value, float* tlogp,
+                           float* bonus, uint8_t* miss, double* temp_out /* f64 [n] */, void* stream);
+
+/* The row of a rebuilt candidate set that holds the action a record took.  For transition i with the rows lo = seg_lo[i] ..
+ * seg_hi[i] - 1 of idx (i64: compact candidate rows, bridges_valid_rows) and the record rec + i * rec_stride (doubles):
+ *   row[i] = the first j in [lo, hi) whose candidate c = idx[j] has cand_desc[c] (i32 [C, 4]: target_block, target_face, shape,
+ *   face) equal to the record's (ATB, ATF, ASHAPE, AFACE) and the four words of cand_pose[c] (f64 [C, 4]) equal to the record's
+ *   APOSE words as 64-bit patterns -- no float comparison: -0.0 does not match 0.0, a NaN matches its own bits;
+ *   0x7fffffff if there is none.
+ * The descriptor alone is not unique (ground positions and offsets share it): the pose bits decide.  The caller keeps every
+ * idx[j] inside cand_desc / cand_pose.  No atomics, each output written once.  Returns -1 and launches nothing for: n < 0,
+ * rec_stride < BRIDGES_REC_WIDTH, a NULL array, an int32 pointer that is not 4-byte, an idx / cand_pose / rec that is not 8-byte
+ * or a cand_desc that is not 16-byte aligned.  n == 0 returns 0 and launches nothing. */
+int bridges_action_row(int32_t n, const int32_t* seg_lo, const int32_t* seg_hi, const int64_t* idx /* i64 [R] */,
+                       const int32_t* cand_desc /* i32 [C,4] */, const double* cand_pose /* f64 [C,4] */, const double* rec,
+                       int64_t rec_stride /* doubles */, int32_t* row /* i32 [n] */, void* stream);
 
 /* --- n-step returns of the vectorised loop ------------------------------------------------------------------------
  * The fold of one lock-step's one-step records rec [E, W] f64 (W >= BRIDGES_REC_WIDTH: the record plus its task tail) / valid [E]

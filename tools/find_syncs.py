@@ -10,6 +10,8 @@ lock-step with n-step returns (the fold and the compaction of its rows): the cou
 --temp_relative (with --exploration boltzmann) / --target_temp_relative (with --target_temperature T) [--spread_floor F] make those
 temperatures multiples of each state's spread of q (the sum of the effective temperatures rides with the counts, their mean over
 the sampled transitions with the losses): nor here.
+--munchausen_alpha A [--munchausen_clip L0] (with --target_temperature T) runs it with Munchausen targets: the second scratch env's
+valid_rows is ONE more wait per lock-step (the conv nets: their distinct-row search over the rows of s adds its two as well).
 --prioritized_replay [--priority_alpha A] [--priority_refresh] runs it on prioritised replay; the sampler kernel and the refresh add
 launches, and the count should be that of plain --prioritized_replay; --priority_beta B [--priority_beta_anneal N] adds the
 importance-sampling weights (one more launch, no wait)."""
@@ -35,6 +37,7 @@ from bridges_hip.vec_env import RandomBridges, RandomTargets, VecAssemblyGym
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_target_temperature_argument, target_temperature_from_args,
                                                 add_relative_temperature_arguments, relative_temperature_from_args,
+                                                add_munchausen_arguments, munchausen_from_args,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
@@ -45,6 +48,7 @@ add_double_q_argument(ap)
 add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
 add_priority_arguments(ap, prioritized_flag=True)
 add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
+add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_clip L0]: Munchausen targets (VecDQN(munchausen_alpha=A, munchausen_clip=L0))
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
@@ -68,7 +72,7 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True)
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
                **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
                **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
-               **relative_temperature_from_args(vars(a)))
+               **relative_temperature_from_args(vars(a)), **munchausen_from_args(vars(a)))
 
 
 def lockstep():

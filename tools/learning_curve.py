@@ -21,6 +21,7 @@ import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_target_temperature_argument, target_temperature_from_args,
                                                 add_relative_temperature_arguments, relative_temperature_from_args,
+                                                add_munchausen_arguments, munchausen_from_args,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_eval_beam_argument, add_search_arguments,
@@ -61,6 +62,7 @@ add_double_q_argument(ap)                # --double_q: double Q-learning targets
 add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
 add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
 add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
+add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_clip L0]: Munchausen targets (VecDQN(munchausen_alpha=A, munchausen_clip=L0))
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_eval_beam_argument(ap)               # --eval_beam B: beam search of width B on the evaluation tasks (VecDQN.beam_search)
@@ -107,7 +109,7 @@ agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=a.lr, fused=True)
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
                **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
                **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
-               **relative_temperature_from_args(vars(a)))
+               **relative_temperature_from_args(vars(a)), **munchausen_from_args(vars(a)))
 eval_env = None
 if a.eval_envs > 0:
     eval_env = VecAssemblyGym(a.eval_envs, [load_urdf("shapes/trapezoid.urdf")], obstacles(), targets(), max_steps=a.max_steps, seed=1, device=dev,
@@ -155,6 +157,10 @@ for it in range(1, a.locksteps + 1):
                         soft_value_gap=r4(float(np.mean([s["soft_value_gap"] for s in soft])) if soft else None))
             if agent.target_temp_relative:                      # ... and of the mean effective temperature of the backups
                 line.update(target_temperature_effective=r4(float(np.mean([s["target_temperature_effective"] for s in soft])) if soft else None))
+            if agent.munchausen is not None:                    # ... and of the three Munchausen keys (missed: the block's sum)
+                line.update(munchausen_bonus=r4(float(np.mean([s["munchausen_bonus"] for s in soft])) if soft else None),
+                            munchausen_clipped=r4(float(np.mean([s["munchausen_clipped"] for s in soft])) if soft else None),
+                            munchausen_missed=float(np.sum([s["munchausen_missed"] for s in soft])) if soft else None)
         if agent.temp_relative:                                 # the block's last lock-step: the mean temperature its envs drew at
             line.update(temperature_effective=r4(agent.temperature_effective))
         if agent.hindsight is not None:                         # the block's last lock-step: the relabelled rows it pushed

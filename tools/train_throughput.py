@@ -8,6 +8,7 @@ import torch
 from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
                                                 add_target_temperature_argument, target_temperature_from_args,
                                                 add_relative_temperature_arguments, relative_temperature_from_args,
+                                                add_munchausen_arguments, munchausen_from_args,
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
@@ -60,6 +61,7 @@ add_double_q_argument(ap)                # --double_q: double Q-learning targets
 add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
 add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
 add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
+add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_clip L0]: Munchausen targets (VecDQN(munchausen_alpha=A, munchausen_clip=L0))
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
@@ -120,7 +122,7 @@ agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_a
                curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
                **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
                **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
-               **relative_temperature_from_args(vars(a)))
+               **relative_temperature_from_args(vars(a)), **munchausen_from_args(vars(a)))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False

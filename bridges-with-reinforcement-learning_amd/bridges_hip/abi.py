@@ -281,6 +281,8 @@ SIGNATURES = {
     "bridges_boltzmann_select": [i32, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_boltzmann_select_rel": [i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "bridges_beam_select": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bridges_particle_select": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                vp],
     "bridges_beam_merge": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "bridges_beam_trace": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp, vp, vp],
     "bridges_valid_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],

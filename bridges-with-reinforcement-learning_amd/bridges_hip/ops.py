@@ -552,6 +552,80 @@ def beam_select(seg, q, width, live, ret, disc, idx, cand_offset, rep=None, out=
     return out
 
 
+def particle_select_args(seg, q, width, live, ret, disc, idx, cand_offset, u_act, u_res, temperature, resample_temperature, rep=None,
+                         out=None):
+    """The argument checks of particle_select that need no device -> (seg_lo, seg_hi, E, B, G, n).  ValueError in words."""
+    import math
+    B = int(width)
+    if not 1 <= B <= abi.BEAM_MAX_WIDTH:
+        raise ValueError(f"particle_select: the width must be 1..{abi.BEAM_MAX_WIDTH}, got {B}")
+    T, Tr = float(temperature), float(resample_temperature)
+    if not (math.isfinite(T) and T > 0.0):
+        raise ValueError(f"particle_select: the temperature must be finite and > 0, got {temperature!r}")
+    if not Tr > 0.0:                                         # (a NaN fails the comparison; +inf passes)
+        raise ValueError(f"particle_select: the resampling temperature must be > 0 (inf allowed), got {resample_temperature!r}")
+    if isinstance(seg, (tuple, list)):
+        seg_lo, seg_hi = seg
+        E = seg_lo.numel()
+    else:
+        E = seg.numel() - 1
+        seg_lo, seg_hi = seg[:E], seg[1:]
+    if E < 0 or E % B != 0:
+        raise ValueError(f"particle_select: E = {E} envs is no multiple of the width {B}")
+    G, n = E // B, q.numel()
+    if E and n < 1:
+        raise ValueError("particle_select: q holds no rows")
+    want = (("seg_lo", seg_lo, torch.int32, E), ("seg_hi", seg_hi, torch.int32, E), ("q", q, torch.float32, n),
+            ("idx", idx, torch.int64, n), ("live", live, torch.uint8, E), ("ret", ret, torch.float64, E),
+            ("disc", disc, torch.float64, E), ("u_act", u_act, torch.float32, E), ("u_res", u_res, torch.float32, G),
+            ("rep", rep, torch.int32, E))
+    for name, t, dt, count in want:
+        if t is None and name == "rep":
+            continue
+        if t.dtype != dt or t.numel() != count:
+            raise ValueError(f"particle_select: {name} must be {dt} [{count}], got {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"particle_select: {name} must be contiguous")
+    if cand_offset.dtype != torch.int32 or cand_offset.numel() < E or not cand_offset.is_contiguous():
+        raise ValueError(f"particle_select: cand_offset must be contiguous int32 [>= {E}], got {cand_offset.dtype} "
+                         f"{tuple(cand_offset.shape)}")
+    if out is not None:
+        for name, dt, count in (("src", torch.int32, E), ("sel_compact", torch.int64, E), ("sel_index", torch.int32, E),
+                                ("q_sel", torch.float32, E), ("score", torch.float64, E), ("live", torch.uint8, E),
+                                ("p_sel", torch.float32, E), ("ess", torch.float64, G)):
+            t = out.get(name)
+            if t is None or t.dtype != dt or t.numel() != count or not t.is_contiguous():
+                raise ValueError(f"particle_select: out[{name!r}] must be contiguous {dt} [{count}]")
+    return seg_lo, seg_hi, E, B, G, n
+
+
+def particle_select(seg, q, width, live, ret, disc, idx, cand_offset, u_act, u_res, temperature, resample_temperature, elite=True,
+                    rep=None, out=None):
+    """Best-of-N rollouts with resampling, one launch (bridges_particle_select; the rule stands in include/bridges_hip.h): the
+    sampled sibling of beam_select, same layout and inputs.  A live env with an eligible row is a parent valued ret + disc * (its
+    largest q); slot k of a group takes a parent by systematic resampling at u_res[g] over the weights exp((S - max S) /
+    resample_temperature) -- inf: every particle keeps its place --, then one of that parent's rows by the Boltzmann rule at
+    ``temperature`` with u_act[slot].  ``elite``: slot 0 is the best parent's first maximum instead.  u_act float32 [E], u_res
+    float32 [G], uniform in [0, 1).
+    -> beam_select's dict plus p_sel float32 [E] (the probability the drawn row had; 1 for the elite) and ess float64 [G] (the
+    effective sample size of the group's weights; 0 without parents); ``out``: such a dict to write into (no allocation)."""
+    seg_lo, seg_hi, E, B, G, n = particle_select_args(seg, q, width, live, ret, disc, idx, cand_offset, u_act, u_res, temperature,
+                                                      resample_temperature, rep, out)
+    L = abi.require_gpu()
+    dev = q.device
+    if out is None:
+        out = dict(src=torch.empty(E, dtype=torch.int32, device=dev), sel_compact=torch.empty(E, dtype=torch.int64, device=dev),
+                   sel_index=torch.empty(E, dtype=torch.int32, device=dev), q_sel=torch.empty(E, dtype=torch.float32, device=dev),
+                   score=torch.empty(E, dtype=torch.float64, device=dev), live=torch.empty(E, dtype=torch.uint8, device=dev),
+                   p_sel=torch.empty(E, dtype=torch.float32, device=dev), ess=torch.empty(G, dtype=torch.float64, device=dev))
+    abi.check(L.bridges_particle_select(E, B, n, _ptr(seg_lo), _ptr(seg_hi), _ptr(q), _ptr(idx), _ptr(cand_offset), _ptr(rep), _ptr(live),
+                                        _ptr(ret), _ptr(disc), _ptr(u_act), _ptr(u_res), float(temperature), float(resample_temperature),
+                                        int(bool(elite)), _ptr(out["src"]), _ptr(out["sel_compact"]), _ptr(out["sel_index"]),
+                                        _ptr(out["q_sel"]), _ptr(out["score"]), _ptr(out["live"]), _ptr(out["p_sel"]), _ptr(out["ess"]),
+                                        _stream()), "bridges_particle_select")
+    return out
+
+
 def beam_merge(n_blocks, blk_shape, blk_pose, blk_occ, targets_left, width, live, ret, key_last=True, out=None):
     """The beams of every group of ``width`` that hold the same structure, in one launch (bridges_beam_merge; the rule stands in
     include/bridges_hip.h): E = G * width envs whose state arrays are n_blocks int32 [E], blk_shape int32 [E, K], blk_pose float64

@@ -1110,6 +1110,31 @@ int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg
                   idx, cand_offset, rep, live, ret, disc, src, sel_compact, sel_index, q_sel, score, live_out);
 }
 
+int bridges_particle_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q,
+                            const int64_t* idx, const int32_t* cand_offset, const int32_t* rep, const uint8_t* live, const double* ret,
+                            const double* disc, const float* u_act, const float* u_res, float temperature,
+                            float resample_temperature, int32_t elite, int32_t* src, int64_t* sel_compact, int32_t* sel_index,
+                            float* q_sel, double* score, uint8_t* live_out, float* p_sel, double* ess, void* stream) {
+    if (E < 0) return fail_arg("bridges_particle_select: negative count");
+    if (B < 1 || B > BEAM_MAX_WIDTH) return fail_arg("bridges_particle_select: the width must be 1..16");
+    if (E % B != 0) return fail_arg("bridges_particle_select: E must be a multiple of the width");
+    if (E == 0) return BRIDGES_OK;
+    if (n_rows < 1) return fail_arg("bridges_particle_select: n_rows must be >= 1");
+    if (!(temperature > 0.f && temperature < INFINITY))                           // (a NaN fails the comparison)
+        return fail_arg("bridges_particle_select: the temperature must be finite and > 0");
+    if (!(resample_temperature > 0.f)) return fail_arg("bridges_particle_select: the resampling temperature must be > 0 (+inf allowed)");
+    if (!seg_lo || !seg_hi || !q || !idx || !cand_offset || !live || !ret || !disc || !u_act || !u_res || !src || !sel_compact ||
+        !sel_index || !q_sel || !score || !live_out || !p_sel || !ess)
+        return fail_arg("bridges_particle_select: null pointer");
+    if (!aligned(4, seg_lo, seg_hi, cand_offset, rep, src, sel_index) || !aligned(4, q, q_sel, u_act, u_res, p_sel) ||
+        !aligned(8, idx, sel_compact) || !aligned(8, ret, disc, score, ess))
+        return fail_arg("bridges_particle_select: misaligned pointer");
+    // one workgroup per group of B particles
+    return launch("k_particle_select", k_particle_select, dim3((unsigned)(E / B)), dim3(BEAM_THREADS), 0, stream, E, B, n_rows, seg_lo,
+                  seg_hi, q, idx, cand_offset, rep, live, ret, disc, u_act, u_res, temperature, resample_temperature, (int)elite, src,
+                  sel_compact, sel_index, q_sel, score, live_out, p_sel, ess);
+}
+
 int bridges_beam_merge(int32_t E, int32_t B, int32_t K, const int32_t* n_blocks, const int32_t* blk_shape, const double* blk_pose,
                        const uint8_t* blk_occ, const int32_t* targets_left, const uint8_t* live, const double* ret, int32_t key_last,
                        int32_t* rep, uint8_t* live_out, int32_t* n_merged, void* stream) {

@@ -109,6 +109,152 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_select(int E, int B, int 
     }
 }
 
+// bridges_particle_select: the sampled sibling of bridges_beam_select (include/bridges_hip.h has the rule).  Same layout; a live env
+// with an eligible row (q neither NaN nor -inf) and a value
+//   S_e = ret[e] + disc[e] * (double)(the env's largest eligible q)      (two binary64 operations, as the beam's score)
+// that is neither NaN nor -inf is a PARENT.  The parents of a group weigh W_p = exp((S_p - max S) / T_r); slot k takes, by systematic
+// resampling at (u_res[g] + k) / B of the total, the first parent whose inclusive prefix sum in env order exceeds the target
+// (strictly), and draws one of that PARENT's rows by the rule of bridges_boltzmann_select at `temperature` with u_act[gB + k].  With
+// elite != 0 slot 0 is afterwards given the first best parent and that parent's first maximum of q.
+//
+// One workgroup per group, three phases with a barrier between them.  (1) A wave per env (the four waves take the group's envs in
+// turn): the largest eligible q (lane-strided, DPP tree), S and the clamped row range into LDS.  (2) One lane: the B weights, their
+// prefix sums added one by one in env order -- at most 16 terms, so the order is the rule's own and costs nothing --, ess, and the
+// parent of every slot.  (3) A wave per slot: the total and the scan of k_boltzmann_select (64 rows at a time, chunks in order) over
+// the parent's rows, with boltzmann_weight of dqn_kernels.hip and the maximum of phase 1; the draw's loop is written again here so
+// that k_boltzmann_select's code stays as it is.  No atomics, no scratch, every output word written once, the same bits on every call.
+__global__ __launch_bounds__(BEAM_THREADS) void k_particle_select(
+    int E, int B, int n_rows, const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi, const float* __restrict__ q,
+    const int64_t* __restrict__ idx, const int32_t* __restrict__ cand_offset, const int32_t* __restrict__ rep,
+    const uint8_t* __restrict__ live, const double* __restrict__ ret, const double* __restrict__ disc, const float* __restrict__ u_act,
+    const float* __restrict__ u_res, float temperature, float resample_temperature, int elite, int32_t* __restrict__ src,
+    int64_t* __restrict__ sel_compact, int32_t* __restrict__ sel_index, float* __restrict__ q_sel, double* __restrict__ score,
+    uint8_t* __restrict__ live_out, float* __restrict__ p_sel, double* __restrict__ ess) {
+    constexpr int NONE = 0x7fffffff;
+    __shared__ int lo_s[BEAM_MAX_WIDTH], hi_s[BEAM_MAX_WIDTH], parent_s[BEAM_MAX_WIDTH], slot_parent_s[BEAM_MAX_WIDTH];
+    __shared__ double ret_s[BEAM_MAX_WIDTH], disc_s[BEAM_MAX_WIDTH], max_s[BEAM_MAX_WIDTH], S_s[BEAM_MAX_WIDTH];
+    __shared__ double W_s[BEAM_MAX_WIDTH], C_s[BEAM_MAX_WIDTH];
+    const int t = threadIdx.x, lane = t & (WAVE - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(t / WAVE);
+    const int g = blockIdx.x, e0 = g * B;
+    if (e0 + B > E) return;
+    for (int b = wv; b < B; b += BEAM_THREADS / WAVE) {      // phase 1: env e0 + b's range, largest eligible q and value
+        const int e = e0 + b;
+        int lo = __builtin_amdgcn_readfirstlane(seg_lo[e]), hi = __builtin_amdgcn_readfirstlane(seg_hi[e]);
+        if (lo < 0) lo = 0;
+        if (hi > n_rows) hi = n_rows;
+        double mx = -INFINITY;
+        for (int j = lo + lane; j < hi; j += WAVE) {
+            const float v = q[j];
+            if (v == v && (double)v > mx) mx = (double)v;
+        }
+        const double m = wave_max_d(mx);                     // -inf: no eligible row
+        if (lane == 0) {
+            const double r = ret[e], d = disc[e];
+            const double S = r + d * m;
+            lo_s[b] = lo; hi_s[b] = hi; ret_s[b] = r; disc_s[b] = d; max_s[b] = m; S_s[b] = S;
+            parent_s[b] = (live[e] && m != -(double)INFINITY && S == S && S != -(double)INFINITY) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    if (t == 0) {                                            // phase 2: weights, prefix sums, the parent of every slot
+        const double Tr = (double)resample_temperature;
+        double M = -INFINITY;
+        int n_par = 0, best = -1;
+        for (int b = 0; b < B; ++b) {
+            if (!parent_s[b]) continue;
+            ++n_par;
+            if (best < 0 || S_s[b] > M) { M = S_s[b]; best = b; }               // the first parent of maximal S
+        }
+        double run = 0.0, sq = 0.0;
+        int last_pos = -1;
+        for (int b = 0; b < B; ++b) {
+            double w = 0.0;
+            if (parent_s[b]) {
+                if (Tr == (double)INFINITY) w = 1.0;
+                else if (M == (double)INFINITY) w = S_s[b] == (double)INFINITY ? 1.0 : 0.0;
+                else w = exp((S_s[b] - M) / Tr);
+            }
+            run += w; sq += w * w;
+            W_s[b] = w; C_s[b] = run;
+            if (w > 0.0) last_pos = b;
+        }
+        const double total = run;
+        ess[g] = n_par ? total * total / sq : 0.0;
+        for (int k = 0; k < B; ++k) {
+            int p = -1;
+            if (n_par) {
+                const double target = ((double)u_res[g] + (double)k) / (double)B * total;
+                p = last_pos;
+                for (int b = B - 1; b >= 0; --b)
+                    if (W_s[b] > 0.0 && C_s[b] > target) p = b;                 // ends on the first such b
+                if (elite && k == 0) p = best;
+            }
+            slot_parent_s[k] = p;
+        }
+    }
+    __syncthreads();
+    for (int k = wv; k < B; k += BEAM_THREADS / WAVE) {      // phase 3: slot k's row of its parent
+        const int slot = e0 + k;
+        const int p = slot_parent_s[k];                      // wave-uniform
+        if (p < 0) {
+            if (lane == 0) {
+                src[slot] = slot; sel_compact[slot] = 0; sel_index[slot] = 0;
+                q_sel[slot] = 0.f; score[slot] = -INFINITY; live_out[slot] = 0; p_sel[slot] = 0.f;
+            }
+            continue;
+        }
+        const int lo = lo_s[p], hi = hi_s[p];
+        const double m = max_s[p], T = (double)temperature;
+        int row;
+        double prob;
+        if (elite && k == 0) {
+            int fm = NONE;
+            for (int j = lo + lane; j < hi; j += WAVE)
+                if (fm == NONE && (double)q[j] == m) fm = j;
+            row = wave_min_i(fm);
+            prob = 1.0;
+        } else {
+            // k_boltzmann_select's passes 2 and 3 over the parent's rows
+            double total = 0.0;
+            for (int base = lo; base < hi; base += WAVE) {
+                const int j = base + lane;
+                total += wave_sum_d(boltzmann_weight(j < hi ? q[j] : -INFINITY, m, T));
+            }
+            const double target = (double)u_act[slot] * total;
+            double carry = 0.0;
+            int last_pos = -1, found = NONE;
+            for (int base = lo; base < hi; base += WAVE) {
+                const int j = base + lane;
+                const double w = boltzmann_weight(j < hi ? q[j] : -INFINITY, m, T);
+                double incl = w;
+#pragma unroll
+                for (int s = 1; s < WAVE; s <<= 1) {
+                    const double up = __shfl_up(incl, s, WAVE);
+                    if (lane >= s) incl += up;
+                }
+                if (w > 0.0) last_pos = j;
+                found = wave_min_i((j < hi && carry + incl > target) ? j : NONE);
+                if (found != NONE) break;                    // wave-uniform
+                carry += readlane_d(incl, WAVE - 1);
+            }
+            if (found == NONE) found = -wave_min_i(-last_pos);                 // (a parent has a row of weight 1: last_pos >= lo)
+            row = found;
+            prob = boltzmann_weight(q[row], m, T) / total;
+        }
+        if (lane == 0) {
+            const int pe = e0 + p;
+            const float v = q[row];
+            const int64_t c = idx[row];
+            int owner = rep ? rep[pe] : pe;
+            if (owner < 0 || owner >= E) owner = pe;
+            const int64_t rel = c - (int64_t)cand_offset[owner];
+            src[slot] = pe; sel_compact[slot] = c; sel_index[slot] = rel > 0 ? (int32_t)rel : 0;
+            q_sel[slot] = v; score[slot] = ret_s[p] + disc_s[p] * (double)v; live_out[slot] = 1; p_sel[slot] = (float)prob;
+        }
+    }
+}
+
 // bridges_beam_merge: the beams of a group that hold the same structure, placed in whatever order (include/bridges_hip.h has the
 // rule).  A live slot is a tuple of five 64-bit words -- shape id | occupancy << 32, then the four pose bit patterns --, an env's
 // key is (nb, targets_left, [the tuple of slot nb - 1], the sorted multiset of its tuples), and two live envs of a group are

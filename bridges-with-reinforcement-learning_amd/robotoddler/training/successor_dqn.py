@@ -592,6 +592,7 @@ def build_parser():
     add_hindsight_arguments(p)
     add_search_arguments(p)
     add_eval_beam_argument(p)
+    add_eval_particle_arguments(p)
     return p
 
 
@@ -869,7 +870,7 @@ def add_eval_beam_argument(p):
                         "the beams closed that way.")
 
 
-def check_eval_beam(args):
+def check_eval_beam(args, flag="--eval_beam", operator="the widest beam bridges_beam_select orders"):
     """--eval_beam B / --eval_beam_merge: refused in words (SystemExit) where the loop cannot run it, before anything touches the
     GPU."""
     B = args.get('eval_beam')
@@ -879,11 +880,63 @@ def check_eval_beam(args):
         return
     from bridges_hip import abi
     if not 1 <= B <= abi.BEAM_MAX_WIDTH:
-        raise SystemExit(f"--eval_beam must be 1..{abi.BEAM_MAX_WIDTH} (the widest beam bridges_beam_select orders)")
+        raise SystemExit(f"{flag} must be 1..{abi.BEAM_MAX_WIDTH} ({operator})")
     if args.get('num_envs', 1) <= 1:
-        raise SystemExit("--eval_beam needs the vectorised loop (--num_envs N, N > 1): the search forks lock-step envs on the device")
+        raise SystemExit(f"{flag} needs the vectorised loop (--num_envs N, N > 1): the search forks lock-step envs on the device")
     if args.get('eval_envs', EVAL_DEFAULTS['eval_envs']) <= 0:
-        raise SystemExit("--eval_beam searches the tasks of the evaluation env: it needs --eval_envs M, M > 0")
+        raise SystemExit(f"{flag} searches the tasks of the evaluation env: it needs --eval_envs M, M > 0")
+
+
+def add_eval_particle_arguments(p):
+    """--eval_particles and its companions: shared with the tools that evaluate through the vectorised loop."""
+    p.add_argument("--eval_particles", type=int, default=argparse.SUPPRESS, metavar="B",
+                   help="Vectorised loop with --eval_envs M: every evaluation also runs a particle search of B particles (1..16) on "
+                        "the same M tasks (VecDQN.particle_search: rollouts sampled from the Boltzmann policy at "
+                        "--eval_particle_temperature, resampled every depth by their value), and logs particle_success_rate / "
+                        "particle_reward / particle_lin_reward / particles / particle_ess / particle_p_sel beside the greedy keys.")
+    p.add_argument("--eval_particle_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
+                   help="With --eval_particles B: temperature of the action draws, finite and > 0 (required).")
+    p.add_argument("--eval_particle_resample_temperature", type=float, default=argparse.SUPPRESS, metavar="TR",
+                   help="With --eval_particles B: temperature of the resampling weights, > 0 (the action temperature); inf: no "
+                        "resampling -- with --eval_particle_no_elite plain best-of-B rollouts.")
+    p.add_argument("--eval_particle_no_elite", action="store_true", default=argparse.SUPPRESS,
+                   help="With --eval_particles B: no particle is reserved for the best parent's best candidate.")
+    p.add_argument("--eval_particle_merge", action="store_true", default=argparse.SUPPRESS,
+                   help="With --eval_particles B: merge particles that hold the same structure (as --eval_beam_merge).")
+
+
+def check_eval_particles(args):
+    """--eval_particles B and its companions: refused in words (SystemExit) where the loop cannot run them, before anything touches
+    the GPU."""
+    import math
+    B = args.get('eval_particles')
+    if B is None:
+        for k in ('eval_particle_temperature', 'eval_particle_resample_temperature', 'eval_particle_no_elite', 'eval_particle_merge'):
+            if k in args:
+                raise SystemExit(f"--{k} shapes the search --eval_particles B runs: it needs --eval_particles B")
+        return
+    if 'eval_beam' in args:
+        raise SystemExit("--eval_particles and --eval_beam are two searches of the same tasks: an evaluation runs one of them")
+    if 'eval_particle_temperature' not in args:
+        raise SystemExit("--eval_particles needs --eval_particle_temperature T: the temperature its actions are drawn at")
+    T = args['eval_particle_temperature']
+    if not (math.isfinite(T) and T > 0.0):
+        raise SystemExit("--eval_particle_temperature must be finite and > 0")
+    if not args.get('eval_particle_resample_temperature', T) > 0.0:          # (a NaN fails the comparison)
+        raise SystemExit("--eval_particle_resample_temperature must be > 0 (inf: no resampling)")
+    check_eval_beam(dict(args, eval_beam=B, eval_beam_merge=False), flag="--eval_particles",
+                    operator="the most particles bridges_particle_select resamples")
+
+
+def eval_particles_from_args(args):
+    """The arguments of VecDQN.particle_search from parsed options (None without --eval_particles); refuses what
+    check_eval_particles refuses."""
+    check_eval_particles(args)
+    if 'eval_particles' not in args:
+        return None
+    return dict(width=args['eval_particles'], temperature=args['eval_particle_temperature'],
+                resample_temperature=args.get('eval_particle_resample_temperature'), elite=not args.get('eval_particle_no_elite'),
+                merge=bool(args.get('eval_particle_merge')))
 
 
 def add_hindsight_arguments(p):
@@ -938,13 +991,20 @@ def add_search_arguments(p):
                    help="With --search_every: width of the beam, 1..16 (8).")
     p.add_argument("--search_merge", action="store_true", default=argparse.SUPPRESS,
                    help="With --search_every: the search merges beams that hold the same structure (as --eval_beam_merge).")
+    p.add_argument("--search_particles", action="store_true", default=argparse.SUPPRESS,
+                   help="With --search_every: the search is a particle search (VecDQN.particle_search: --search_width rollouts per "
+                        "task sampled from the Boltzmann policy and resampled every depth by their value) instead of the beam search.")
+    p.add_argument("--search_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
+                   help="With --search_particles: temperature of the action draws, finite and > 0 (required).")
+    p.add_argument("--search_resample_temperature", type=float, default=argparse.SUPPRESS, metavar="TR",
+                   help="With --search_particles: temperature of the resampling weights, > 0 or inf (the action temperature).")
 
 
 def check_search(args):
     """--search_every and its companions: refused in words (SystemExit) where the loop cannot run them, before anything touches
     the GPU."""
     if 'search_every' not in args:
-        for k in ('search_tasks', 'search_width', 'search_merge'):
+        for k in ('search_tasks', 'search_width', 'search_merge', 'search_particles', 'search_temperature', 'search_resample_temperature'):
             if k in args:
                 raise SystemExit(f"--{k} shapes the search in training: it needs --search_every N")
         return
@@ -959,6 +1019,18 @@ def check_search(args):
         raise SystemExit(f"--search_tasks must be 1..--num_envs ({args['num_envs']}): the tasks are those of the first rollout envs")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--search_every runs on one rank only: the rows a search finds are not part of the all-gather")
+    if 'search_particles' not in args:
+        for k in ('search_temperature', 'search_resample_temperature'):
+            if k in args:
+                raise SystemExit(f"--{k} is a temperature of the particle search: it needs --search_particles")
+        return
+    import math
+    if 'search_temperature' not in args:
+        raise SystemExit("--search_particles needs --search_temperature T: the temperature its actions are drawn at")
+    if not (math.isfinite(args['search_temperature']) and args['search_temperature'] > 0.0):
+        raise SystemExit("--search_temperature must be finite and > 0")
+    if not args.get('search_resample_temperature', 1.0) > 0.0:               # (a NaN fails the comparison)
+        raise SystemExit("--search_resample_temperature must be > 0 (inf: no resampling)")
 
 
 def search_from_args(args):
@@ -969,6 +1041,10 @@ def search_from_args(args):
     out = dict(search_every=args['search_every'], search_width=args.get('search_width', 8), search_merge=bool(args.get('search_merge')))
     if 'search_tasks' in args:
         out['search_tasks'] = args['search_tasks']
+    if 'search_particles' in args:
+        out.update(search_sampler="particles", search_temperature=args['search_temperature'])
+        if 'search_resample_temperature' in args:
+            out['search_resample_temperature'] = args['search_resample_temperature']
     return out
 
 
@@ -1157,6 +1233,7 @@ def main(argv=None):
     check_hindsight(args)
     check_search(args)
     check_eval_beam(args)
+    check_eval_particles(args)
     from bridges_hip import abi
     abi.require_gpu()
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)

@@ -54,6 +54,7 @@ from robotoddler.training import train_step as T
 
 # --random_obstacles: every obstacle of every env is drawn from x in [-3, 3), z in [0.3, 2.5) at the start of an episode
 OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
+SEARCH_SEED = 24681357                                   # particle_search: its stream is seeded with SEARCH_SEED + the agent's seed
 
 
 class TargetBatch(NamedTuple):
@@ -78,6 +79,7 @@ class VecDQN:
     temp_relative = target_temp_relative = False
     spread_floor, temperature_effective, target_temperature_effective, _temp_out = 1e-3, None, None, None
     munchausen = replay_env_s = munchausen_bonus = munchausen_clipped = munchausen_missed = None
+    search_sampler = search_gen = search_temperature = search_resample_temperature = None
 
     def __init__(self, policy_net, target_net, optimizer, env, replay_capacity, batch_size, gamma, tau, loss_function,
                  seed=0, rank=0, eps_start=0.5, eps_end=0.05, eps_decay=0.999, prioritized=False, stable_actions_only=False,
@@ -86,7 +88,8 @@ class VecDQN:
                  exploration="epsilon_greedy", temp_start=1.0, temp_end=0.1, temp_decay=0.999, hindsight=None, hindsight_goals=1,
                  search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None,
                  target_temperature=None, temp_relative=False, target_temp_relative=False, spread_floor=1e-3,
-                 munchausen_alpha=None, munchausen_clip=None):
+                 munchausen_alpha=None, munchausen_clip=None, search_sampler=None, search_temperature=None,
+                 search_resample_temperature=None):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -246,7 +249,8 @@ class VecDQN:
         self.target_temperature = target_temperature
         self._soft_stats = None                              # [2] on the device: what the last _targets call left for the log
         self.target_entropy = self.soft_value_gap = None
-        self._init_search(env, search_every, search_tasks, search_width, search_merge, search_priority, per_env_tasks, prioritized)
+        self._init_search(env, search_every, search_tasks, search_width, search_merge, search_priority, per_env_tasks, prioritized,
+                          sampler=search_sampler, temperature=search_temperature, resample_temperature=search_resample_temperature)
         self.exploration = str(exploration)
         if self.exploration not in ("epsilon_greedy", "boltzmann"):
             raise ValueError(f"VecDQN(exploration={exploration!r}): one of 'epsilon_greedy', 'boltzmann'")
@@ -402,7 +406,8 @@ class VecDQN:
         self.curriculum = CurriculumRun(curriculum, env, gamma) if curriculum is not None else None
         self.curriculum_weights_host = None                  # pinned copy of the weights as of the last lock-step
 
-    def _init_search(self, env, every, tasks, width, merge, priority, per_env_tasks, prioritized):
+    def _init_search(self, env, every, tasks, width, merge, priority, per_env_tasks, prioritized, sampler=None, temperature=None,
+                     resample_temperature=None):
         """The conditions of search_every=N, decided from the arguments alone; the search env is built by the first search."""
         self.search_every = int(every)
         self.search_env = self.last_search = None
@@ -415,7 +420,11 @@ class VecDQN:
             if tasks is not None or width is not None or merge or priority is not None:
                 raise ValueError("VecDQN(search_tasks=..., search_width=..., search_merge=..., search_priority=...) shape the search in "
                                  "training: they need search_every=N")
+            if sampler is not None or temperature is not None or resample_temperature is not None:
+                raise ValueError("VecDQN(search_sampler=..., search_temperature=..., search_resample_temperature=...) shape the search "
+                                 "in training: they need search_every=N")
             return
+        self._init_search_sampler(sampler, temperature, resample_temperature)
         if D.active():
             raise ValueError("VecDQN(search_every=N) runs on one rank only: the rows a search finds are not part of the all-gather")
         if not isinstance(env, VecAssemblyGym):
@@ -439,6 +448,24 @@ class VecDQN:
         if not self.search_priority >= 0.0:                  # (a NaN fails the comparison)
             raise ValueError(f"VecDQN(search_priority={priority!r}): a priority, >= 0")
 
+    def _init_search_sampler(self, sampler, temperature, resample_temperature):
+        """search_sampler="particles": the search in training is particle_search at ``search_temperature`` (finite, > 0) and
+        ``search_resample_temperature`` (> 0, inf allowed; None: the temperature).  None: beam_search, as ever."""
+        import math
+        if sampler is None:
+            if temperature is not None or resample_temperature is not None:
+                raise ValueError("VecDQN(search_temperature=..., search_resample_temperature=...) are the temperatures of "
+                                 "search_sampler='particles': they need it")
+            return
+        if sampler != "particles":
+            raise ValueError(f"VecDQN(search_sampler={sampler!r}): 'particles' or None (the beam search)")
+        if temperature is None or not (math.isfinite(float(temperature)) and float(temperature) > 0.0):
+            raise ValueError(f"VecDQN(search_sampler='particles') needs search_temperature, finite and > 0; got {temperature!r}")
+        if resample_temperature is not None and not float(resample_temperature) > 0.0:        # (a NaN fails the comparison)
+            raise ValueError(f"VecDQN(search_resample_temperature={resample_temperature!r}): > 0 (inf: no resampling)")
+        self.search_sampler, self.search_temperature = "particles", float(temperature)
+        self.search_resample_temperature = self.search_temperature if resample_temperature is None else float(resample_temperature)
+
     def _search(self):
         """One search in training: the tasks of rollout envs 0 .. M - 1 as they stand, repeated B times, into the search env; a
         traced beam search on it; the rows into the ring.  No host wait but the search's own."""
@@ -452,7 +479,11 @@ class VecDQN:
                 senv.load_task(targets, env.env_obstacles[:M].repeat_interleave(B, dim=0))
             else:
                 senv.load_targets(targets)
-        res = self.beam_search(senv, B, merge=self.search_merge, trace=True, trace_n_step=self.n_step, trace_priority=self.search_priority)
+        traced = dict(merge=self.search_merge, trace=True, trace_n_step=self.n_step, trace_priority=self.search_priority)
+        if self.search_sampler == "particles":
+            res = self.particle_search(senv, B, self.search_temperature, self.search_resample_temperature, **traced)
+        else:
+            res = self.beam_search(senv, B, **traced)
         self.ring.push(res["trace_rows"])
         self.search_env_steps += senv.E * senv.K
         self.search_rows += res["trace_count"]
@@ -886,15 +917,70 @@ class VecDQN:
         trace_offset, trace_status and trace_end_env (device: row offsets per task, 1 where a chain was broken -- never, by
         construction --, the env every task's best episode ended in).
         Tracing adds no host wait.  trace=False launches nothing of it and returns what the search always returned."""
+        def select(d, seg, q, live, ret, disc, idx, cand_offset, rep):
+            return ops.beam_select(seg, q, int(width), live, ret, disc, idx, cand_offset, rep=rep)
+        return self._depth_search("beam_search", beam_env, width, select, merge, on_depth, trace, trace_n_step, trace_priority)
+
+    @torch.no_grad()
+    def particle_search(self, beam_env, width, temperature, resample_temperature=None, elite=True, merge=False, on_depth=None,
+                        trace=False, trace_n_step=1, trace_priority=0.0, generator=None):
+        """Best-of-N rollouts with resampling over every task of ``beam_env``: beam_search's depth loop with the select swapped for
+        bridges_particle_select ("Particle search").  Per depth every slot of a group takes a parent among
+        the group's live envs by systematic resampling over exp((ret + disc * max q) / ``resample_temperature``) (None: the
+        ``temperature``; inf: no particle moves -- B independent rollouts, the best-of-N control) and places one of the parent's
+        candidates drawn from the Boltzmann policy at ``temperature``; ``elite``: slot 0 follows the best parent's best
+        candidate instead.  The uniforms come per depth from ``generator`` (None: self.search_gen, a stream of the search's own
+        seeded from the agent's seed, so neither the replay draw nor exploration moves).  Everything else -- fork, step, the
+        float64 returns, the best finished beam, merge, trace -- is beam_search's, and so are the arguments and the result, which
+        gains particles (= width), ess_by_depth (per depth the mean effective sample size over the groups that had parents) and
+        p_sel_mean_by_depth (the mean probability of the drawn candidates over the filled slots), read back with the rest.
+        No host wait is added per depth."""
+        import math
+        T = float(temperature)
+        Tr = T if resample_temperature is None else float(resample_temperature)
+        if not (math.isfinite(T) and T > 0.0):
+            raise ValueError(f"particle_search(temperature={temperature!r}): finite and > 0")
+        if not Tr > 0.0:                                     # (a NaN fails the comparison; inf passes)
+            raise ValueError(f"particle_search(resample_temperature={resample_temperature!r}): > 0 (inf: no resampling)")
+        gen = self._search_generator() if generator is None else generator
+        K, dev = beam_env.K, self.device
+        stats = torch.zeros(2 * K, dtype=torch.float64, device=dev)      # per depth: mean ess, mean p_sel
+
+        def select(d, seg, q, live, ret, disc, idx, cand_offset, rep):
+            E = live.numel()
+            u_act = torch.rand(E, generator=gen, device=dev)
+            u_res = torch.rand(E // int(width), generator=gen, device=dev)
+            sel = ops.particle_select(seg, q.float().contiguous(), int(width), live, ret, disc, idx.contiguous(), cand_offset.contiguous(),
+                                      u_act, u_res, T, Tr, elite=elite, rep=rep)
+            ess, filled = sel["ess"], sel["live"].double()
+            stats[d] = ess.sum() / (ess > 0).sum().clamp(min=1)
+            stats[K + d] = (sel["p_sel"].double() * filled).sum() / filled.sum().clamp(min=1)
+            return sel
+        out = self._depth_search("particle_search", beam_env, width, select, merge, on_depth, trace, trace_n_step, trace_priority,
+                                 stats=stats)
+        st, n = out.pop("depth_stats"), out.pop("depths")
+        out.update(particles=int(width), ess_by_depth=st[:n], p_sel_mean_by_depth=st[K:K + n])
+        return out
+
+    def _search_generator(self):
+        """The random stream of particle_search: made by the first search that needs it, seeded from the agent's seed."""
+        if self.search_gen is None:
+            self.search_gen = torch.Generator(device=self.device).manual_seed(SEARCH_SEED + int(self.seed))
+        return self.search_gen
+
+    def _depth_search(self, what, beam_env, width, select, merge, on_depth, trace, trace_n_step, trace_priority, stats=None):
+        """The depth loop of beam_search and particle_search (``what`` names the caller in messages): select(d, seg, q, live, ret,
+        disc, idx, cand_offset, rep) -> the dict of ops.beam_select chooses every slot's parent and candidate; ``stats``: a
+        float64 vector on the device that rides with the one read-back (-> depth_stats, beside depths: the depths that ran)."""
         B, env = int(width), beam_env
         if env is self.env:
-            raise ValueError("beam_search() needs an env of its own: the training env's episodes would be cut short")
+            raise ValueError(f"{what}() needs an env of its own: the training env's episodes would be cut short")
         if not 1 <= B <= abi.BEAM_MAX_WIDTH:
-            raise ValueError(f"beam_search(width={width!r}): 1..{abi.BEAM_MAX_WIDTH}")
+            raise ValueError(f"{what}(width={width!r}): 1..{abi.BEAM_MAX_WIDTH}")
         if not isinstance(env, VecAssemblyGym) or env.E % B != 0:
-            raise ValueError(f"beam_search(width={B}) needs a VecAssemblyGym of M * {B} envs (beam_env_like(eval_env, {B}))")
+            raise ValueError(f"{what}(width={B}) needs a VecAssemblyGym of M * {B} envs (beam_env_like(eval_env, {B}))")
         if env.random_targets is not None or env.random_obstacles is not None or env.task_family is not None:
-            raise ValueError("beam_search(): the beam env draws tasks per episode, so the envs of a group would not share one; build "
+            raise ValueError(f"{what}(): the beam env draws tasks per episode, so the envs of a group would not share one; build "
                              "it with beam_env_like(eval_env, width)")
         if bool(env.stable_actions_only) != self.stable_actions_only:
             raise ValueError("the beam env's stable_actions_only must match the training env's")
@@ -903,13 +989,13 @@ class VecDQN:
         E, K, dev = env.E, env.K, self.device
         M = E // B
         if merge and K > abi.BEAM_MAX_SLOTS:
-            raise ValueError(f"beam_search(merge=True): bridges_beam_merge orders at most {abi.BEAM_MAX_SLOTS} block slots per env, "
+            raise ValueError(f"{what}(merge=True): bridges_beam_merge orders at most {abi.BEAM_MAX_SLOTS} block slots per env, "
                              f"the beam env has {K}")
         if trace:
             if K > R.K:
-                raise ValueError(f"beam_search(trace=True): a record holds {R.K} block slots, the beam env has {K}")
+                raise ValueError(f"{what}(trace=True): a record holds {R.K} block slots, the beam env has {K}")
             if not 1 <= int(trace_n_step) <= abi.NSTEP_MAX:
-                raise ValueError(f"beam_search(trace_n_step={trace_n_step!r}): 1..{abi.NSTEP_MAX}")
+                raise ValueError(f"{what}(trace_n_step={trace_n_step!r}): 1..{abi.NSTEP_MAX}")
             tr_rec, tr_valid, tr_parent = self._trace_buffers(E, K)
             # the task every record of a group is taken under: explicit arrays that no episode of a beam env redraws
             tr_tail = None
@@ -931,13 +1017,14 @@ class VecDQN:
         if trace:                                            # per task: where the episode of ``best`` ended
             end_env, end_depth = first.to(torch.int32), torch.full((M,), -1, dtype=torch.int32, device=dev)
         env.reset()
+        depths = 0
         for d in range(K):
             stable = self._stable_flags(env)
             idx, row_env, seg, rep = self._rows(env, stable)
             if not idx.numel():                              # no env holds a valid candidate: every beam is closed
                 break
             q = self._policy_q(env, idx, row_env, stable)
-            sel = ops.beam_select(seg, q, B, live, ret, disc, idx, env.cand_offset[:E], rep=rep)
+            sel = select(d, seg, q, live, ret, disc, idx, env.cand_offset[:E], rep)
             src, sc = sel["src"].long(), sel["sel_compact"]
             placed = torch.cat([env.cand_desc[sc, 2:3].double(), env.cand_pose[sc], sel["sel_index"].double().unsqueeze(1)], dim=1)
             ret, ret_r, disc, hist = ret[src], ret_r[src], disc[src], hist[src]
@@ -981,13 +1068,15 @@ class VecDQN:
                 live = mg["live"]
             if on_depth is not None:
                 on_depth(d, live)
+            depths = d + 1
         if trace:                                            # (depths a search that broke off early left unwritten lie beyond every end)
             tr = ops.beam_trace(tr_rec, tr_valid, tr_parent, end_env, end_depth, B, self.gamma, n_step=int(trace_n_step), tail=tr_tail,
                                 priority=float(trace_priority))
         # the one wait of the search (with merge: the merged counts ride along as further columns)
-        host = (torch.cat([best, merged.double()], dim=1) if merge else best).cpu()
+        cols = [best] + ([merged.double()] if merge else []) + ([stats.unsqueeze(0).expand(M, -1)] if stats is not None else [])
+        host = (torch.cat(cols, dim=1) if len(cols) > 1 else best).cpu()
         if int(host[:, 0].sum()) != M:
-            raise RuntimeError(f"beam search: {int(host[:, 0].sum())} of {M} tasks ended an episode within {K} depths "
+            raise RuntimeError(f"{what.replace('_', ' ')}: {int(host[:, 0].sum())} of {M} tasks ended an episode within {K} depths "
                                "(a task whose fresh state has no valid candidate never starts one)")
         succ_h, steps_h = host[:, 1].tolist(), [int(v) for v in host[:, 4].tolist()]
         hist_h = host[:, 6:6 + 6 * K].reshape(M, K, 6)
@@ -1001,13 +1090,15 @@ class VecDQN:
                    num_steps=float(host[:, 4].mean()), success_rate=float(host[:, 1].mean()), episodes=M, beam_width=B,
                    structures=structures, merged_beams=[0] * M)
         if merge:
-            counts = host[:, 6 + 6 * K:].long()
+            counts = host[:, 6 + 6 * K:6 + 8 * K].long()
             out.update(merged_beams=counts[:, :K].sum(dim=1).tolist(), merged_by_depth=counts[:, :K].sum(dim=0).tolist(),
                        live_by_depth=counts[:, K:].sum(dim=0).tolist())
         if trace:
             n_rows = sum(steps_h)
             out.update(trace_rows=tr["rows"][:n_rows], trace_count=n_rows, trace_offset=tr["offset"], trace_status=tr["status"],
                        trace_end_env=end_env)
+        if stats is not None:
+            out.update(depth_stats=host[0, host.shape[1] - stats.numel():].tolist(), depths=depths)
         classes = getattr(env, "beam_task_class", None)
         if classes is not None:                              # the tasks of a family: per span / height n = 0..hi
             n_classes = env.beam_n_classes
@@ -1394,6 +1485,9 @@ class VecDQN:
             blob["temperature"] = float(self.temperature)
         if self.search_every:                                # one more key: the lock-steps since the last search
             blob["search_phase"] = int(self.search_calls)
+        if self.search_sampler is not None:                  # two more keys: the sampler's settings and where its stream stands
+            blob["search_sampler"] = (str(self.search_sampler), float(self.search_temperature), float(self.search_resample_temperature))
+            blob["search_gen"] = self._search_generator().get_state().cpu()
         if self.target_temperature is not None:              # one more key: the temperature of the soft targets
             blob["target_temperature"] = float(self.target_temperature)
         if self.target_temp_relative:                        # one more key: ... and that it multiplies the spread, above which floor
@@ -1444,6 +1538,13 @@ class VecDQN:
         if got_m != self.munchausen:
             raise ValueError(f"{path} was written by a run with (munchausen_alpha, munchausen_clip) = {got_m}, this agent has "
                              f"{self.munchausen}: the nets were trained towards another backup operator")
+        # (a file of a run whose search in training is the beam search, or that has none, carries no entry)
+        got_s = (str(blob["search_sampler"][0]), *(float(v) for v in blob["search_sampler"][1:])) if "search_sampler" in blob else None
+        want_s = ((str(self.search_sampler), float(self.search_temperature), float(self.search_resample_temperature))
+                  if self.search_sampler is not None else None)
+        if got_s != want_s:
+            raise ValueError(f"{path} was written by a run with (search_sampler, search_temperature, search_resample_temperature) = "
+                             f"{got_s}, this agent has {want_s}: the ring does not hold the rows of the same search")
         # (a file of a run without hindsight relabelling carries no entry)
         got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
         want_h = (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None
@@ -1467,6 +1568,8 @@ class VecDQN:
             self.temperature = float(blob.get("temperature", self.temp_start))
         if self.search_every:                                # (a file of a run without the option: phase 0)
             self.search_calls = int(blob.get("search_phase", 0)) % self.search_every
+        if want_s is not None:
+            self._search_generator().set_state(blob["search_gen"])
         return blob["counters"]
 
     # ------------------------------------------------------------------ driver
@@ -1749,7 +1852,7 @@ def next_multiple(n, every):
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
     from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets,
                                                     munchausen_from_args, relative_temperature_from_args, target_temperature_from_args,
-                                                    search_from_args, track_run_sinks)
+                                                    search_from_args, track_run_sinks, eval_particles_from_args)
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
@@ -1817,6 +1920,10 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     eval_beam = args.get('eval_beam')
     beam_env = beam_env_like(eval_env, eval_beam) if eval_beam and eval_env is not None else None
     eval_beam_merge = bool(args.get('eval_beam_merge'))      # --eval_beam_merge: that search merges beams of the same structure
+    # --eval_particles B: ... or with B particles per task (particle_search: sampled rollouts, resampled by their value)
+    eval_particles = eval_particles_from_args(args)
+    if eval_particles is not None and eval_env is not None:
+        beam_env = beam_env_like(eval_env, eval_particles['width'])
     history, t0, it = [], time.time(), 0
     next_ckpt = next_multiple(0, args['checkpoint_every'])
     next_eval = next_multiple(0, args['evaluate_every'])
@@ -1901,7 +2008,17 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
         if eval_envs > 0 and agent.episodes_done >= next_eval:
             if rank == 0:
                 ev = info['evaluation'] = agent.evaluate(eval_env, eval_epsilon)
-                if beam_env is not None:                     # the same tasks under the beam search, beside the greedy keys
+                if beam_env is not None and eval_particles is not None:      # the same tasks under the particle search
+                    ps = agent.particle_search(beam_env, **eval_particles)
+                    ev.update(particle_success_rate=ps['success_rate'], particle_reward=ps['reward'], particle_lin_reward=ps['lin_reward'],
+                              particles=ps['particles'])
+                    # means over the depths at which a task was still open (ess 0: every task had ended before that depth)
+                    opened = [d for d, e in enumerate(ps['ess_by_depth']) if e > 0.0]
+                    ev.update(particle_ess=float(np.mean([ps['ess_by_depth'][d] for d in opened])) if opened else None,
+                              particle_p_sel=float(np.mean([ps['p_sel_mean_by_depth'][d] for d in opened])) if opened else None)
+                    if eval_particles['merge']:
+                        ev.update(eval_merged_particles=sum(ps['merged_beams']))
+                elif beam_env is not None:                   # the same tasks under the beam search, beside the greedy keys
                     bs = agent.beam_search(beam_env, eval_beam, merge=eval_beam_merge)
                     ev.update(beam_success_rate=bs['success_rate'], beam_reward=bs['reward'], beam_lin_reward=bs['lin_reward'],
                               beam_width=eval_beam)

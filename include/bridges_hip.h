@@ -594,6 +594,43 @@ int bridges_beam_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg
                         const double* disc, int32_t* src, int64_t* sel_compact, int32_t* sel_index, float* q_sel, double* score,
                         uint8_t* live_out, void* stream);
 
+/* Particle search: best-of-N rollouts with resampling, the sampled sibling of bridges_beam_select.  Layout, seg_lo / seg_hi / q /
+ * idx / cand_offset / rep / live / ret / disc and the outputs src .. live_out exactly as there; u_act f32 [E] holds one uniform
+ * draw in [0, 1) per slot, u_res f32 [G] one per group.  All arithmetic is binary64 without contraction; T = (double)temperature,
+ * T_r = (double)resample_temperature.
+ *   - ELIGIBLE row: its q is neither NaN nor -inf (bridges_boltzmann_select's word);
+ *   - PARENT: a live env with at least one eligible row whose VALUE S_e = ret[e] + disc[e] * (double)v_e, v_e the env's largest
+ *     eligible q, is neither NaN nor -inf (two operations, as bridges_beam_select's score).  A dead env is never a parent;
+ *   - RESAMPLING WEIGHTS over the parents of a group, in env order: M = max S, W_p = exp((S_p - M) / T_r); with T_r = +inf every
+ *     W_p = 1 (whatever M is); otherwise with M = +inf W_p = 1 for the +inf parents and 0 for the others.  C_p = the inclusive
+ *     prefix sum of W in env order, added one by one, total = C_last, ess[g] = total^2 / sum W_p^2 (0 for a group without parents);
+ *   - SYSTEMATIC RESAMPLING: slot k = 0 .. B - 1 has the target t_k = ((double)u_res[g] + k) / B * total and takes the first parent
+ *     p with C_p > t_k (strict); if rounding leaves none, the last parent with W_p > 0;
+ *   - ELITE (elite != 0): slot 0 is overridden after that assignment: its parent is the first parent of maximal S (env
+ *     ascending), its row that parent's first maximum of q, its p_sel 1;
+ *   - ACTION DRAW of every other slot: the rule of bridges_boltzmann_select word for word -- the weights with their m = +inf case,
+ *     the strict inverse CDF, the fall-back row, p_sel -- over the PARENT's rows at T with the draw u_act[gB + k];
+ *   - slot gB + k: src = the parent p, sel_compact = idx[row], sel_index = max(sel_compact - cand_offset[rep ? rep[p] : p], 0),
+ *     q_sel = q[row], score = ret[p] + disc[p] * (double)q[row], live_out = 1, p_sel as drawn (f32, rounded once);
+ *   - a group without parents writes bridges_beam_select's empty slot to every slot (src = the slot's own env, sel_compact 0,
+ *     sel_index 0, q_sel 0, score -inf, live_out 0) with p_sel 0.
+ * Two exact properties.  With T_r = +inf, elite == 0 and all B envs of a group parents, C_p = p + 1 and t_k = (u + k) / B * B lies
+ * in [k, k + 1), so src[gB + k] = gB + k: no particle moves, the group is B independent rollouts (the best-of-N control).  With
+ * B = 1 and elite != 0 the outputs src .. live_out equal bridges_beam_select(B = 1)'s wherever ret is finite and disc > 0 (the
+ * largest q then has the largest score).
+ * One launch, one workgroup per group; no atomics, no scratch; every output word is written exactly once; every sum has a fixed
+ * order, so the same inputs give the same bits.  The parent draw adds its prefix sums in the order above; the action draw adds
+ * them as bridges_boltzmann_select does, so a target within a few ulp of a c_j may fall to the neighbouring row.  Rows outside
+ * [0, n_rows) are never read.  1 <= B <= 16.
+ * Refused (-1, nothing launched): whatever bridges_beam_select refuses; a temperature that is not finite or not > 0; a
+ * resample_temperature that is NaN or not > 0 (+inf is allowed); a NULL array other than rep; a misaligned pointer.  E == 0
+ * returns 0 and launches nothing. */
+int bridges_particle_select(int32_t E, int32_t B, int32_t n_rows, const int32_t* seg_lo, const int32_t* seg_hi, const float* q,
+                            const int64_t* idx, const int32_t* cand_offset, const int32_t* rep, const uint8_t* live, const double* ret,
+                            const double* disc, const float* u_act, const float* u_res, float temperature,
+                            float resample_temperature, int32_t elite, int32_t* src, int64_t* sel_compact, int32_t* sel_index,
+                            float* q_sel, double* score, uint8_t* live_out, float* p_sel, double* ess, void* stream);
+
 /* Beam search: the beams of a group that hold the same structure, reached by whatever order of placements.  E = G * B envs, group
  * g owns envs gB .. gB + B - 1 as for bridges_beam_select; the caller guarantees that the envs of a group share one task.  The
  * state arrays are the env's own (n_blocks [E], blk_shape [E, K], blk_pose [E, K, 4], blk_occ [E, K], targets_left [E]: the env's

@@ -22,9 +22,16 @@ stream / event / device synchronisations): per depth the search must wait only w
             write into given outputs, the legs alternating
   search    one VecDQN.beam_search(--width) call without and with trace=True on the same --tasks held-out tasks, alternating
 (--trace --syncs: the host waits of both searches -- tracing must add none).
+--particles times the particle search against the beam search instead:
+  select    ops.particle_select (bridges_particle_select: one launch) against ops.beam_select on the same rows at --groups groups of
+            --width envs, HIP events around single calls that write into given outputs, the two alternating in one process
+  search    one VecDQN.particle_search(--width, --particle_temperature) against one VecDQN.beam_search(--width) next to one
+            VecDQN.evaluate() on the same --tasks held-out tasks, alternating (wall clock around the whole call)
+(--particles --syncs: the host waits of both searches -- per depth the particle search must wait exactly where the beam search does).
     python tools/beam_search_bench.py [--fork_envs 512 4096] [--groups 64 512] [--width 8] [--tasks 64] [--widths 1 4 8] [--syncs]
     python tools/beam_search_bench.py --merge [--tasks 64] [--width 8] [--syncs]
-    python tools/beam_search_bench.py --trace [--groups 64 512] [--tasks 64] [--width 8] [--syncs]"""
+    python tools/beam_search_bench.py --trace [--groups 64 512] [--tasks 64] [--width 8] [--syncs]
+    python tools/beam_search_bench.py --particles [--groups 64 512] [--tasks 64] [--width 8] [--particle_temperature 1.0] [--syncs]"""
 import argparse, ctypes as C, json, os, sys, time, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -50,8 +57,11 @@ ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--syncs", action="store_true")
 ap.add_argument("--merge", action="store_true", help="time bridges_beam_merge and a search with / without merging at --tasks x --width")
 ap.add_argument("--trace", action="store_true", help="time bridges_beam_trace and a search with / without tracing at --tasks x --width")
+ap.add_argument("--particles", action="store_true",
+                help="time bridges_particle_select against bridges_beam_select and a particle search against a beam search at --tasks x --width")
+ap.add_argument("--particle_temperature", type=float, default=1.0, help="with --particles: the temperature of both draws")
 a = ap.parse_args()
-assert not (a.merge and a.trace), "--merge and --trace are two modes"
+assert a.merge + a.trace + a.particles <= 1, "--merge, --trace and --particles are three modes"
 assert a.reps >= 20 and a.search_reps >= 5
 dev = torch.device("cuda:0")
 HBM_PEAK = 8.0e12                                             # bytes / s, the card's specification
@@ -123,7 +133,7 @@ def waits(fn):
 
 
 # ---- fork ---------------------------------------------------------------------------------------------------------------------
-for E in ([] if a.syncs or a.merge or a.trace else a.fork_envs):
+for E in ([] if a.syncs or a.merge or a.trace or a.particles else a.fork_envs):
     env = tower_env(E)
     for _ in range(4):
         env.select_random()
@@ -152,7 +162,7 @@ for E in ([] if a.syncs or a.merge or a.trace else a.fork_envs):
     del env, arrays, scratch
 
 # ---- select -------------------------------------------------------------------------------------------------------------------
-for G in ([] if a.syncs or a.merge or a.trace else a.groups):
+for G in ([] if a.syncs or a.merge or a.trace else a.groups):   # (--particles: its own legs below)
     B = a.width
     E = G * B
     g = torch.Generator().manual_seed(G)
@@ -187,6 +197,23 @@ for G in ([] if a.syncs or a.merge or a.trace else a.groups):
         e = row_env[row]
         return (torch.where(ok, e.to(torch.int32), own), torch.where(ok, idx[row], 0),
                 torch.where(ok, (idx[row] - cand_offset[e]).to(torch.int32), 0), torch.where(ok, q[row], 0.0), top.reshape(-1), ok)
+    if a.particles:                                          # the sampled sibling against the operator it stands beside
+        gen = torch.Generator(device=dev).manual_seed(G)
+        u_act, u_res = torch.rand(E, generator=gen, device=dev), torch.rand(G, generator=gen, device=dev)
+        q32, idx64 = q.float().contiguous(), idx.contiguous()
+        out_b = ops.beam_select(seg, q32, B, live, ret, disc, idx64, cand_offset)
+        out_p = ops.particle_select(seg, q32, B, live, ret, disc, idx64, cand_offset, u_act, u_res, a.particle_temperature,
+                                    a.particle_temperature)
+        legs = (("particle_select", lambda: ops.particle_select(seg, q32, B, live, ret, disc, idx64, cand_offset, u_act, u_res,
+                                                                a.particle_temperature, a.particle_temperature, out=out_p)),
+                ("beam_select", lambda: ops.beam_select(seg, q32, B, live, ret, disc, idx64, cand_offset, out=out_b)))
+        s = alternate(legs, a.reps, a.warmup)
+        print(json.dumps(dict(part="particle_select", groups=G, width=B, rows=nrows, temperature=a.particle_temperature,
+                              mean_ess=float(out_p["ess"].mean()), moved=float((out_p["src"] != own).float().mean()), **s,
+                              particle_over_beam=s["particle_select"]["median_us"] / s["beam_select"]["median_us"],
+                              note="HIP events around single calls that write into given outputs (host launch gap included), the two "
+                                   "alternating")), flush=True)
+        continue
     k, f = select(), formulation()
     same = (k["sel_compact"] == f[1]).float().mean().item()   # topk breaks exact ties its own way: random q has none to speak of
     assert same > 0.999, same
@@ -290,13 +317,17 @@ if a.tasks > 0:
     agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), mk(256, 0), 20000, 32, 0.95, 0.01,
                    "mse_q_values+mse_block_features", per_env_tasks=True)
     eval_env = mk(a.tasks, 1)
-    beams = {B: beam_env_like(eval_env, B) for B in ([a.width] if a.merge or a.trace else a.widths)}
+    beams = {B: beam_env_like(eval_env, B) for B in ([a.width] if a.merge or a.trace or a.particles else a.widths)}
     legs = [("evaluate", lambda: agent.evaluate(eval_env))] + [(f"beam_{B}", (lambda B=B: agent.beam_search(beams[B], B))) for B in beams]
     if a.merge:
         legs.append((f"beam_{a.width}_merge", lambda: agent.beam_search(beams[a.width], a.width, merge=True)))
     if a.trace:
         legs.append((f"beam_{a.width}_trace", lambda: agent.beam_search(beams[a.width], a.width, trace=True)))
         legs.append((f"beam_{a.width}_trace3", lambda: agent.beam_search(beams[a.width], a.width, trace=True, trace_n_step=3)))
+    if a.particles:
+        T = a.particle_temperature
+        legs.append((f"particle_{a.width}", lambda: agent.particle_search(beams[a.width], a.width, T)))
+        legs.append((f"best_of_{a.width}", lambda: agent.particle_search(beams[a.width], a.width, T, float("inf"), elite=False)))
     if a.syncs:
         for name, fn in legs:
             fn()

@@ -11,8 +11,14 @@ With --eval_beam B beside --eval_envs the line also holds beam_success_rate / be
 beam search of width B with the policy net's q as the heuristic (VecDQN.beam_search).  With --eval_beam_merge beside it the same
 search runs once more with merge=True (beams that hold the same structure are closed after every depth): merge_success_rate /
 merge_reward / merge_lin_reward, eval_merged_beams, and per depth merged_by_depth / live_by_depth (closed / looked at).
+With --eval_particles B --eval_particle_temperature T beside --eval_envs (alone or beside --eval_beam: the searches touch no
+training state and draw from a stream of their own, so one run holds them all on the same tasks) the line also holds
+particle_success_rate / particle_reward / particle_lin_reward / particle_ess / particle_p_sel: the same tasks under
+VecDQN.particle_search; with --eval_particle_control a further leg control_*: the same B rollouts without resampling and without the
+elite (resample temperature inf), the plain best-of-B control.
     python tools/learning_curve.py --locksteps 1500 --envs 1024 [--model ConvNet --loss mse_q_values]
-                                   [--eval_envs 64 [--eval_beam 8 [--eval_beam_merge]]]"""
+                                   [--eval_envs 64 [--eval_beam 8 [--eval_beam_merge]]
+                                    [--eval_particles 8 --eval_particle_temperature T [--eval_particle_control]]]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -25,8 +31,9 @@ from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_do
                                                 add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
                                                 exploration_from_args, make_nets, priority_from_args,
                                                 add_hindsight_arguments, hindsight_from_args, add_eval_beam_argument, add_search_arguments,
-                                                search_from_args)
+                                                search_from_args, add_eval_particle_arguments, eval_particles_from_args)
 from robotoddler.training.vec_dqn import VecDQN, beam_env_like, curriculum_from_args
+from bridges_hip import ops
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
@@ -66,8 +73,15 @@ add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_cl
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
 add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
 add_eval_beam_argument(ap)               # --eval_beam B: beam search of width B on the evaluation tasks (VecDQN.beam_search)
-add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] (VecDQN(search_every=N, ...))
+add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] [--search_particles ...]
+add_eval_particle_arguments(ap)          # --eval_particles B --eval_particle_temperature T [...]: VecDQN.particle_search on the evaluation tasks
+ap.add_argument("--eval_particle_control", action="store_true",
+                help="with --eval_particles: one more leg, the same rollouts without resampling and without the elite (best-of-B)")
 a = ap.parse_args()
+# (here the particle search may stand beside --eval_beam: the legs of one comparison)
+eval_particles = eval_particles_from_args({k: v for k, v in dict(vars(a), num_envs=a.envs).items() if k != "eval_beam"})
+if a.eval_particle_control and eval_particles is None:
+    ap.error("--eval_particle_control is a leg of --eval_particles B: it needs --eval_particles B")
 eval_beam = vars(a).get("eval_beam")
 if eval_beam is not None and not (1 <= eval_beam <= 16 and a.eval_envs > 0):
     ap.error("--eval_beam B needs 1 <= B <= 16 and --eval_envs M, M > 0")
@@ -116,6 +130,9 @@ if a.eval_envs > 0:
                               f32_rasters=VecDQN.acting_needs_f32_rasters(pol) and not a.task_channels,
                               stable_actions_only=a.stable_actions_only)
 beam_env = beam_env_like(eval_env, eval_beam) if eval_beam else None
+particle_env = None
+if eval_particles is not None:
+    particle_env = beam_env if eval_beam == eval_particles["width"] else beam_env_like(eval_env, eval_particles["width"])
 r4 = lambda v: None if v is None else round(v, 4)
 
 
@@ -189,6 +206,25 @@ for it in range(1, a.locksteps + 1):
                                 merge_lin_reward=r4(bm["lin_reward"]), merge_num_steps=r4(bm["num_steps"]),
                                 eval_merged_beams=sum(bm["merged_beams"]), merged_by_depth=bm["merged_by_depth"],
                                 live_by_depth=bm["live_by_depth"])
+            if particle_env is not None:                        # the same tasks under B sampled, resampled rollouts
+                legs = [("particle", eval_particles)]
+                if a.eval_particle_control:                     # ... and under B independent rollouts, the best kept
+                    legs.append(("control", dict(eval_particles, resample_temperature=float("inf"), elite=False)))
+                for name, kw in legs:
+                    ps = agent.particle_search(particle_env, **kw)
+                    line.update({f"{name}_success_rate": r4(ps["success_rate"]), f"{name}_reward": r4(ps["reward"]),
+                                 f"{name}_lin_reward": r4(ps["lin_reward"]), f"{name}_num_steps": r4(ps["num_steps"]),
+                                 f"{name}_ess": [r4(v) for v in ps["ess_by_depth"]], f"{name}_p_sel": [r4(v) for v in ps["p_sel_mean_by_depth"]]})
+                # what the temperature stands against: the mean over the tasks of the spread (population standard deviation) of
+                # q among the candidates of the empty state, from the relative-temperature operator at multiple 1
+                particle_env.reset()                            # (explicit task arrays: a reset redraws nothing)
+                stable = agent._stable_flags(particle_env)
+                idx, row_env, seg, rep = agent._rows(particle_env, stable)
+                spread = ops.boltzmann_select(seg, agent._policy_q(particle_env, idx, row_env, stable),
+                                              torch.zeros(particle_env.E, device=dev), 1.0, False, idx,
+                                              particle_env.cand_offset[:particle_env.E], rep=rep, relative=True, spread_floor=1e-30)[5]
+                line.update(particles=eval_particles["width"], particle_temperature=eval_particles["temperature"],
+                            eval_q_spread_first=r4(float(spread.mean())))
             if family:
                 line.update(eval_success_by_class={n: r4(s) for n, s in enumerate(ev["success_by_class"]) if n >= family[1]})
         print(json.dumps(line), flush=True)

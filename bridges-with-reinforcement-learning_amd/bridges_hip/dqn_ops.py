@@ -1,5 +1,6 @@
 """Host wrappers of the fused DQN ops (K7): TD / successor-feature target construction and Polyak soft update."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -343,7 +344,7 @@ def hindsight_relabel_scratch(E, G):
     return need.value
 
 
-def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, count=None, scratch=None):
+def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, count=None, scratch=None, n_step=1, gamma=None):
     """Hindsight relabelling of the episodes that ended in this lock-step (bridges_hindsight_relabel, "final" strategy): buf
     [E, K, W] float64 the buffered records of every env's running episode (a record and its task tail, the env's T targets
     first), flags [E, K, 8] uint8 their step_flags, length [E] int32, ended [E] bool / uint8, episode [E] the task_episode of
@@ -352,14 +353,25 @@ def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, coun
     -> (out [E * K * G, W] float64, count [1] int32 on the device): the first count rows of out are the relabelled rows, env
     ascending, then slot, then step; the rest of out is not written.  ``out`` / ``count`` / ``scratch`` (uint8,
     hindsight_relabel_scratch(E, G) bytes) may be passed to reuse buffers.  Three launches, no host wait, the same bits on every
-    call."""
+    call.
+    ``n_step`` / ``gamma``: with n_step = 1 and gamma = None the call above.  Otherwise the h-step rows of the relabelled walks
+    (bridges_hindsight_relabel_nstep, 1 <= n_step <= abi.NSTEP_MAX, gamma finite): out [E * K * G, W + 1], one row per start in
+    the form of nstep_fold -- the return over h = min(n_step, steps left) relabelled steps in O_LIN, O_STABLE_S and O_TD of the
+    start, h in the last column; the end of a walk flushes its pending starts whether or not its last step is done."""
     L = abi.require_gpu()
     E, K, W = buf.shape
     G = int(G)
     if not getattr(env, "per_env_tasks", False):
         raise ValueError("hindsight_relabel needs an env with per-env tasks (targets=RandomTargets() / set_targets)")
+    fold = not (int(n_step) == 1 and gamma is None)
+    if fold:
+        if not 1 <= int(n_step) <= abi.NSTEP_MAX:
+            raise ValueError(f"hindsight_relabel(n_step={n_step}): a return spans 1..{abi.NSTEP_MAX} steps (BRIDGES_NSTEP_MAX)")
+        if gamma is None or not math.isfinite(float(gamma)):
+            raise ValueError(f"hindsight_relabel(n_step={n_step}, gamma={gamma}): the fold needs a finite discount")
     T = int(env.n_targets)
     dev = buf.device
+    Wo = W + 1 if fold else W
     assert buf.dtype == torch.float64 and buf.is_contiguous()
     assert flags.dtype == torch.uint8 and flags.is_contiguous() and tuple(flags.shape) == (E, K, 8)
     assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() == E
@@ -368,18 +380,21 @@ def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, coun
     ended_u8 = ended.view(torch.uint8) if ended.dtype == torch.bool else ended.to(torch.uint8)
     assert ended_u8.numel() == E
     if out is None:
-        out = torch.empty((E * K * max(G, 1), W), dtype=torch.float64, device=dev)
+        out = torch.empty((E * K * max(G, 1), Wo), dtype=torch.float64, device=dev)
     if count is None:
         count = torch.zeros(1, dtype=torch.int32, device=dev)
-    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= E * K * G * W
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= E * K * G * Wo
     assert count.dtype == torch.int32 and count.numel() >= 1
     if scratch is None:
         scratch = torch.empty(max(4 * E * max(G, 1), 4), dtype=torch.uint8, device=dev)
-    abi.check(L.bridges_hindsight_relabel(E, K, W, T, G, _ptr(buf), _ptr(flags), _ptr(length), _ptr(ended_u8), _ptr(episode),
-                                          int(env.seed) & (2 ** 64 - 1), int(env.env_id_base), env.table.ptr, len(env.table_geoms),
-                                          len(env.table_geoms) - 1, _ptr(env.grid_x_dev), _ptr(env.grid_y_dev), int(env.img),
-                                          env._gauss_k.data_ptr(), _ptr(out), _ptr(count), _ptr(scratch), scratch.numel(), _stream()),
-              "bridges_hindsight_relabel")
+    head = (E, K, W, T, G, _ptr(buf), _ptr(flags), _ptr(length), _ptr(ended_u8), _ptr(episode), int(env.seed) & (2 ** 64 - 1),
+            int(env.env_id_base), env.table.ptr, len(env.table_geoms), len(env.table_geoms) - 1, _ptr(env.grid_x_dev),
+            _ptr(env.grid_y_dev), int(env.img), env._gauss_k.data_ptr())
+    tail = (_ptr(out), _ptr(count), _ptr(scratch), scratch.numel(), _stream())
+    if fold:
+        abi.check(L.bridges_hindsight_relabel_nstep(*head, int(n_step), float(gamma), *tail), "bridges_hindsight_relabel_nstep")
+    else:
+        abi.check(L.bridges_hindsight_relabel(*head, *tail), "bridges_hindsight_relabel")
     return out, count
 
 

@@ -951,11 +951,12 @@ int bridges_hindsight_relabel_scratch(int32_t E, int32_t G, int64_t* bytes) {
     return BRIDGES_OK;
 }
 
-int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
-                              const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
-                              const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
-                              const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
-                              int64_t scratch_bytes, void* stream) {
+// What both hindsight entries check and launch: fold = false stores the one-step rows [., W], fold = true the h-step rows [., W + 1].
+static int hindsight_relabel(bool fold, int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                             const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
+                             const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
+                             const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step, double gamma, double* out,
+                             int32_t* count, void* scratch, int64_t scratch_bytes, void* stream) {
     if (E < 0) return fail_arg("bridges_hindsight_relabel: negative count");
     if (G < 1 || G > HIND_MAX_GOALS) return fail_arg("bridges_hindsight_relabel: G must be 1..4");
     if (K < 1 || K > BRIDGES_MAX_BLOCKS) return fail_arg("bridges_hindsight_relabel: K must be 1..BRIDGES_MAX_BLOCKS");
@@ -964,6 +965,9 @@ int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_
     if (n_shapes < 1 || n_shapes > 8 || target_shape < 0 || target_shape >= n_shapes) return fail_arg("bridges_hindsight_relabel: shape table");
     if (img < 1 || img > IMG) return fail_arg("bridges_hindsight_relabel: img must be 1..64");
     if ((int64_t)E * G * K > INT32_MAX) return fail_arg("bridges_hindsight_relabel: more rows than an int32 counts");
+    if (fold && (n_step < 1 || n_step > BRIDGES_NSTEP_MAX))
+        return fail_arg("bridges_hindsight_relabel_nstep: n_step must be 1..BRIDGES_NSTEP_MAX");
+    if (fold && !(gamma - gamma == 0.0)) return fail_arg("bridges_hindsight_relabel_nstep: gamma must be finite");
     if (!buf || !flags || !len || !ended || !episode || !shapes_dev || !grid_x || !grid_y || !gauss_k || !out || !count || !scratch)
         return fail_arg("bridges_hindsight_relabel: null pointer");
     if (!aligned(8, buf, shapes_dev, grid_x, grid_y, out) || !aligned(4, len, episode, gauss_k, count, scratch))
@@ -981,8 +985,29 @@ int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_
     // one wave per (env, slot), four per workgroup
     if (int rc = launch("k_hindsight_count", k_hindsight_count, dim3((unsigned)ceil_div(items, 4)), dim3(256), 0, stream, a, cnt)) return rc;
     if (int rc = launch("k_hindsight_scan", k_hindsight_scan, dim3(1), dim3(HIND_SCAN_THREADS), 0, stream, items, cnt, count)) return rc;
+    if (fold)
+        return launch("k_hindsight_rows_nstep", k_hindsight_rows_nstep, dim3((unsigned)items), dim3(TASK_THREADS), 0, stream, a,
+                      (const int32_t*)cnt, (const int32_t*)count, out, (int)n_step, gamma);
     return launch("k_hindsight_rows", k_hindsight_rows, dim3((unsigned)items), dim3(TASK_THREADS), 0, stream, a, (const int32_t*)cnt,
                   (const int32_t*)count, out);
+}
+
+int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                              const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
+                              const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
+                              const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
+                              int64_t scratch_bytes, void* stream) {
+    return hindsight_relabel(false, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes, target_shape,
+                                    grid_x, grid_y, img, gauss_k, 1, 0.0, out, count, scratch, scratch_bytes, stream);
+}
+
+int bridges_hindsight_relabel_nstep(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                                    const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed,
+                                    int32_t env_id_base, const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape,
+                                    const double* grid_x, const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step,
+                                    double gamma, double* out, int32_t* count, void* scratch, int64_t scratch_bytes, void* stream) {
+    return hindsight_relabel(true, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes, target_shape,
+                                   grid_x, grid_y, img, gauss_k, n_step, gamma, out, count, scratch, scratch_bytes, stream);
 }
 
 int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, int64_t n, const int64_t* idx, const float* q_sa,

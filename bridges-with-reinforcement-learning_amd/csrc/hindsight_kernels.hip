@@ -12,6 +12,9 @@
 //   k_hindsight_rows    four waves per (env, slot) with rows: the goals again (same draw, same bits), the raster of the T target
 //                       cubes, map and prefix tables in LDS (51 KB, as k_task_features: three workgroups per CU), then wave 0 walks
 //                       the episode and stores row offset[slot] + t.  The order of the output is (env, slot, t) by construction.
+//   k_hindsight_rows_nstep  the same body for a loop on n-step returns (bridges_hindsight_relabel_nstep): wave 0 keeps the relabelled
+//                       lin of every step in LDS and stores, per start t of the walk, the h-step row offset[slot] + t -- when step
+//                       t + n_step - 1 is reached, or at the walk's end.  Counts and offsets are the same: one row per walk step.
 // The work per finished (env, slot) is that of one k_task_features workgroup -- which the lock-step runs for every finished env
 // anyway -- plus K rasters of ~250 wave instructions; envs in mid-episode leave at once.
 #include "bridges_device.h"
@@ -182,12 +185,51 @@ __device__ __forceinline__ uint64_t hind_raster(double vx, double vz, const brid
     return raster_rows_nv(cx, cz, nx, nz, s.nv, a.img, a.grid_x[gi], a.grid_y[gi], lane);
 }
 
-__global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows(HindArgs a, const int32_t* __restrict__ off, const int32_t* __restrict__ total,
-                                                                double* __restrict__ out) {
+// The h-step return of a start from the relabelled lin of its h steps: steps 1-2 of bridges_nstep_fold (binary64, this order, no
+// fused multiply-add: the build has -ffp-contract=off).
+__device__ __forceinline__ double hind_return(const double* lin, int h, double gamma) {
+    double acc = 0.0, disc = 1.0;
+    for (int k = 0; k < h; ++k) {
+        acc += disc * lin[k];
+        disc *= gamma;
+    }
+    return acc;
+}
+
+// One relabelled row: the lane-strided copy of `row` with REWARD, LIN, DONE and the targets of the tail replaced.  FOLD: the h-step
+// row of a start (bridges_hindsight_relabel_nstep) -- `lin` is the return, STABLE_S and TD are read from the start's record
+// `start`, and h goes into one more column, W.
+template <bool FOLD>
+__device__ __forceinline__ void hind_store_row(const HindArgs& a, const double* row, const double* start, double reward, double lin,
+                                               double done, double h, double tgv, int lane, double* o) {
+    const int wout = FOLD ? a.W + 1 : a.W;
+    for (int c0 = 0; c0 < wout; c0 += WAVE) {       // (every lane stays for the shuffle)
+        const int c = c0 + lane;
+        double v = c < a.W ? row[c] : 0.0;
+        if (FOLD && (c == BRIDGES_REC_STABLE_S || c == BRIDGES_REC_TD)) v = start[c];
+        if (c == BRIDGES_REC_REWARD) v = reward;
+        if (c == BRIDGES_REC_LIN) v = lin;
+        if (c == BRIDGES_REC_DONE) v = done;
+        const int k = c - BRIDGES_REC_WIDTH;
+        const bool tail = k >= 0 && k < 3 * a.T;
+        const double tk = shfl_d(tgv, tail ? k : 0);
+        if (tail) v = tk;
+        if (FOLD && c == a.W) v = h;
+        if (c < wout) o[c] = v;
+    }
+}
+
+// FOLD = false: bridges_hindsight_relabel's rows.  FOLD = true: bridges_hindsight_relabel_nstep's -- the same walk, with the
+// relabelled lin of every step kept in LDS (K doubles); start t is stored when step t + n_step - 1 is reached, the return folded
+// again from the kept values in ascending k, and the end of the walk stores the starts still pending.
+template <bool FOLD>
+__device__ __forceinline__ void hind_rows(const HindArgs& a, const int32_t* __restrict__ off, const int32_t* __restrict__ total,
+                                          double* __restrict__ out, int n_step, double gamma) {
     __shared__ float kz[TASK_KZ];
     __shared__ uint64_t tb_l[IMG];
     __shared__ float map_l[IMG * TASK_ROW];
     __shared__ double pre_l[IMG * TASK_ROW];
+    __shared__ double lin_l[FOLD ? BRIDGES_MAX_BLOCKS : 1];
     const int item = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     const int e = item / a.G, g = item % a.G;
     const int m = hind_len(a, e);
@@ -217,6 +259,8 @@ __global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows(HindArgs a, con
     const double* rows = a.buf + (size_t)e * a.K * a.W;
     const uint8_t* fl = a.flags + (size_t)e * a.K * 8;
     uint32_t left = (1u << a.T) - 1u;
+    const int wout = FOLD ? a.W + 1 : a.W;
+    double reward_d = 0.0, done_d = 0.0;            // of the last step walked (FOLD: the rows stored at the end are that step's)
     for (int t = 0; t < n; ++t) {
         const double* row = rows + (size_t)t * a.W;
         double vx, vz;
@@ -234,20 +278,36 @@ __global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows(HindArgs a, con
         const float reward = !st_frozen ? -1.f : (all_reached ? (float)n_reached : (float)(-1 + n_reached));
         const float lin = st_free ? base : (st_frozen ? base / 100.f : 0.f);
         const bool done = !st_frozen || all_reached || truncated || no_actions;
-        double* o = out + (size_t)(first + t) * a.W;
-        for (int c0 = 0; c0 < a.W; c0 += WAVE) {    // (every lane stays for the shuffle)
-            const int c = c0 + lane;
-            double v = c < a.W ? row[c] : 0.0;
-            if (c == BRIDGES_REC_REWARD) v = (double)reward;
-            if (c == BRIDGES_REC_LIN) v = (double)lin;
-            if (c == BRIDGES_REC_DONE) v = done ? 1.0 : 0.0;
-            const int k = c - BRIDGES_REC_WIDTH;
-            const bool tail = k >= 0 && k < 3 * a.T;
-            const double tk = shfl_d(tgv, tail ? k : 0);
-            if (tail) v = tk;
-            if (c < a.W) o[c] = v;
+        reward_d = (double)reward; done_d = done ? 1.0 : 0.0;
+        if (!FOLD) {
+            hind_store_row<false>(a, row, row, reward_d, (double)lin, done_d, 1.0, tgv, lane, out + (size_t)(first + t) * wout);
+            continue;
+        }
+        lin_l[t] = (double)lin;                     // every lane the same value: each reads back what it wrote itself
+        if (t + 1 >= n_step) {
+            const int st = t + 1 - n_step;
+            hind_store_row<true>(a, row, rows + (size_t)st * a.W, reward_d, hind_return(lin_l + st, n_step, gamma), done_d,
+                                 (double)n_step, tgv, lane, out + (size_t)(first + st) * wout);
         }
     }
+    if (FOLD) {
+        // the end of the walk: the starts that never saw n_step steps, with the last step's record -- whether or not it is done
+        const double* row = rows + (size_t)(n - 1) * a.W;
+        for (int st = n - n_step + 1 > 0 ? n - n_step + 1 : 0; st < n; ++st)
+            hind_store_row<true>(a, row, rows + (size_t)st * a.W, reward_d, hind_return(lin_l + st, n - st, gamma), done_d,
+                                 (double)(n - st), tgv, lane, out + (size_t)(first + st) * wout);
+    }
+}
+
+__global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows(HindArgs a, const int32_t* __restrict__ off, const int32_t* __restrict__ total,
+                                                                double* __restrict__ out) {
+    hind_rows<false>(a, off, total, out, 1, 0.0);
+}
+
+__global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows_nstep(HindArgs a, const int32_t* __restrict__ off,
+                                                                      const int32_t* __restrict__ total, double* __restrict__ out,
+                                                                      int n_step, double gamma) {
+    hind_rows<true>(a, off, total, out, n_step, gamma);
 }
 
 }  // namespace bridges

@@ -940,13 +940,17 @@ def eval_particles_from_args(args):
 
 
 def add_hindsight_arguments(p):
-    """--hindsight / --hindsight_goals: shared with the tools that train through the vectorised loop."""
+    """--hindsight / --hindsight_goals / --hindsight_fold: shared with the tools that train through the vectorised loop."""
     p.add_argument("--hindsight", choices=("final",), default=argparse.SUPPRESS,
                    help="With --random_targets T only: hindsight goal relabelling -- every episode that ends is stored a second "
                         "time under T targets its own final structure reached (the centres of the bounding boxes of blocks drawn "
                         "from it), with the rewards the env would have given under them. The log gains hindsight_rows.")
     p.add_argument("--hindsight_goals", type=int, default=argparse.SUPPRESS, metavar="G",
                    help="With --hindsight final: relabelled copies of every finished episode, 1..4 (1).")
+    p.add_argument("--hindsight_fold", action="store_true", default=argparse.SUPPRESS,
+                   help="With --hindsight final: run it beside --n_step n > 1 -- the relabelled episode is folded on the device into "
+                        "h-step rows, the return taken over the relabelled linear rewards; an episode whose last relabelled step is "
+                        "not terminal still stores its last n - 1 starts, which bootstrap from the final state.")
 
 
 def check_hindsight(args):
@@ -954,6 +958,8 @@ def check_hindsight(args):
     if 'hindsight' not in args:
         if 'hindsight_goals' in args:
             raise SystemExit("--hindsight_goals counts the relabelled copies of an episode: it needs --hindsight final")
+        if args.get('hindsight_fold'):
+            raise SystemExit("--hindsight_fold folds the relabelled rows into n-step returns: it needs --hindsight final")
         return
     if not 1 <= args.get('hindsight_goals', 1) <= 4:
         raise SystemExit("--hindsight_goals must be 1..4")
@@ -963,8 +969,9 @@ def check_hindsight(args):
     if args.get('random_bridge_length') is not None or args.get('random_tower_height') is not None or args.get('curriculum'):
         raise SystemExit("--hindsight final does not run on a task family (--random_bridge_length / --random_tower_height) or "
                          "with --curriculum: a family's task is its class, and a box centre names none")
-    if args.get('n_step', 1) > 1:
-        raise SystemExit("--hindsight final needs --n_step 1: an h-step row's return would have to be folded again under the new targets")
+    if args.get('n_step', 1) > 1 and not args.get('hindsight_fold'):
+        raise SystemExit("--hindsight final needs --n_step 1 or --hindsight_fold: an h-step row's return has to be folded again under "
+                         "the new targets")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--hindsight final runs on one rank only: the relabelled rows are not part of the all-gather")
 
@@ -974,7 +981,8 @@ def hindsight_from_args(args):
     check_hindsight(args)
     if 'hindsight' not in args:
         return {}
-    return dict(hindsight=args['hindsight'], hindsight_goals=args.get('hindsight_goals', 1))
+    return dict(hindsight=args['hindsight'], hindsight_goals=args.get('hindsight_goals', 1),
+                **(dict(hindsight_fold=True) if args.get('hindsight_fold') else {}))
 
 
 def add_search_arguments(p):

@@ -76,7 +76,7 @@ class VecDQN:
     exploration, n_step, rows_fed, search_every = "epsilon_greedy", 1, 0, 0
     hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = last_search = None
     target_temperature = _soft_stats = target_entropy = soft_value_gap = None
-    temp_relative = target_temp_relative = False
+    temp_relative = target_temp_relative = hindsight_fold = False
     spread_floor, temperature_effective, target_temperature_effective, _temp_out = 1e-3, None, None, None
     munchausen = replay_env_s = munchausen_bonus = munchausen_clipped = munchausen_missed = None
     search_sampler = search_gen = search_temperature = search_resample_temperature = None
@@ -89,7 +89,7 @@ class VecDQN:
                  search_every=0, search_tasks=None, search_width=None, search_merge=False, search_priority=None,
                  target_temperature=None, temp_relative=False, target_temp_relative=False, spread_floor=1e-3,
                  munchausen_alpha=None, munchausen_clip=None, search_sampler=None, search_temperature=None,
-                 search_resample_temperature=None):
+                 search_resample_temperature=None, hindsight_fold=False):
         """``per_env_tasks=True``: train on a rollout env whose envs own their tasks (VecAssemblyGym(targets=RandomTargets())
         or set_targets).  Rows are then shared by (state, task), acting and the target forward weigh every row with the reward
         map of its env, a record ends in the targets its transition was taken under and replay rebuilds the map from them,
@@ -146,7 +146,7 @@ class VecDQN:
         ``temp_decay`` 0.999: the reference's form, per lock-step as epsilon's); epsilon is left alone.  It is a function of the
         lock-step count alone, so ranks agree; it is checkpointed.  act(greedy=True) and evaluate() stay greedy.  The temp_*
         arguments are refused without the option.  "epsilon_greedy" is the loop as it was: no launch of this.
-        ``hindsight="final"`` (with per_env_tasks=True only, one-step returns, one rank; an extension: hindsight experience replay,
+        ``hindsight="final"`` (with per_env_tasks=True only, one rank, one-step returns unless hindsight_fold=True; an extension: hindsight experience replay,
         Andrychowicz et al., strategy "final"): every episode that ends is pushed a second time, ``hindsight_goals`` = G times
         (1..4), under T targets its own final structure reached -- the centres of the bounding boxes of blocks drawn from it on a
         stream of its own -- with the reward, linear reward and done flag the env would have recorded under those targets
@@ -155,6 +155,12 @@ class VecDQN:
         into the ring, their number rides to the host with the lock-step's counts: no wait of its own.  The training step does
         not change.  It composes with per-env obstacles, task_channels, double_q, prioritised replay (a relabelled row carries
         the priority of the transition it restates) and Boltzmann exploration.  None is the loop as it was: no launch of this.
+        ``hindsight_fold=True`` (with hindsight="final" only): the relabelling under n-step returns.  The buffer keeps the one-step
+        records, and the relabelled walk of a finished episode is folded on the device into the ring's h-step rows
+        (bridges_hindsight_relabel_nstep: the return over the RELABELLED linear rewards, O_STABLE_S and O_TD of the start, h in the
+        last column; the end of a walk flushes its pending starts whether or not its last step is done -- under hindsight targets
+        a final step that is not terminal bootstraps like any other).  With n_step = 1 it is hindsight="final" bit for bit.
+        Without it hindsight="final" with n_step > 1 stays refused.
         ``search_every=N`` (N >= 1; one rank; an extension: search in training): every N-th lockstep(), after
         the lock-step's own rows are pushed and before train_steps, a beam search of width ``search_width`` = B (1..16, default
         8) with the policy net's q as the heuristic runs on the tasks the rollout envs 0 .. ``search_tasks`` - 1 (M, at most the
@@ -298,11 +304,13 @@ class VecDQN:
                              "no window would ever fill")
         self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
         self.task_channels = bool(task_channels)
-        self.hindsight, self.hindsight_goals = hindsight, int(hindsight_goals)
+        self.hindsight, self.hindsight_goals, self.hindsight_fold = hindsight, int(hindsight_goals), bool(hindsight_fold)
         if self.hindsight not in (None, "final"):
             raise ValueError(f"VecDQN(hindsight={hindsight!r}): None or 'final'")
         if self.hindsight is None and self.hindsight_goals != 1:
             raise ValueError("VecDQN(hindsight_goals=...) counts the relabelled copies of an episode: it needs hindsight='final'")
+        if self.hindsight is None and self.hindsight_fold:
+            raise ValueError("VecDQN(hindsight_fold=True) folds the relabelled rows into n-step returns: it needs hindsight='final'")
         if self.hindsight is not None:
             if not 1 <= self.hindsight_goals <= 4:
                 raise ValueError(f"VecDQN(hindsight_goals={hindsight_goals}): an episode is relabelled 1..4 times")
@@ -310,8 +318,9 @@ class VecDQN:
                 raise ValueError("VecDQN(hindsight='final') needs per_env_tasks=True: only a record that ends in its own targets can be given others")
             if getattr(env, "task_family", None) is not None or curriculum is not None:
                 raise ValueError("VecDQN(hindsight='final') does not run on a task family (RandomBridges) or under a curriculum: a family's task is its class, and a box centre names none")
-            if self.n_step > 1:
-                raise ValueError("VecDQN(hindsight='final') needs n_step=1: an h-step row's return would have to be folded again under the new targets")
+            if self.n_step > 1 and not self.hindsight_fold:
+                raise ValueError("VecDQN(hindsight='final') needs n_step=1 or hindsight_fold=True: an h-step row's return has to be "
+                                 "folded again under the new targets")
             if D.active():
                 raise ValueError("VecDQN(hindsight='final') runs on one rank only: the relabelled rows are not part of the all-gather")
         if self.task_channels:
@@ -369,8 +378,10 @@ class VecDQN:
         # n-step returns: one more column, the horizon h of the row
         self.ring = R.ReplayRing(replay_capacity, self.device, width=R.RECORD_WIDTH + self.task_width + (self.n_step > 1))
         self._window = None                                  # the n-step windows of the envs of all ranks, made by the first fold
-        # hindsight relabelling: the running episode of every env, in the ring's width
-        self.hindsight_buffer = (R.HindsightBuffer(env.E, self.ring.width, self.device, goals=self.hindsight_goals, n_blocks=env.K)
+        # hindsight relabelling: the running episode of every env, in the ring's width (n-step returns: one-step records, one
+        # column narrower, folded as they are relabelled)
+        self.hindsight_buffer = (R.HindsightBuffer(env.E, self.ring.width, self.device, goals=self.hindsight_goals, n_blocks=env.K,
+                                                   **(dict(n_step=self.n_step, gamma=self.gamma) if self.n_step > 1 else {}))
                                  if self.hindsight is not None else None)
         self.hindsight_rows = 0                              # relabelled rows the last lock-step pushed
         # replay sampling must be identical on every rank (replicated rings) -> shared seed; exploration differs
@@ -1499,6 +1510,8 @@ class VecDQN:
         if self.hindsight is not None:                       # two more keys: the setting and the running episodes
             blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
             blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
+            if self.hindsight_fold:                          # one more key: the relabelled rows are folded as the loop's own are
+                blob["hindsight_fold"] = True
         torch.save(blob, path)
 
     def load_extra(self, path):
@@ -1551,6 +1564,9 @@ class VecDQN:
         if got_h != want_h:
             raise ValueError(f"{path} was written by a run with (hindsight, hindsight_goals) = {got_h}, this agent has {want_h}: the "
                              "ring does not hold the same mix of rolled-out and relabelled rows")
+        if bool(blob.get("hindsight_fold", False)) != self.hindsight_fold:
+            raise ValueError(f"{path} was written by a run with hindsight_fold = {bool(blob.get('hindsight_fold', False))}, this agent "
+                             f"has hindsight_fold = {self.hindsight_fold}: the two runs do not agree on the option")
         if want_h is not None:
             self.hindsight_buffer.load_state_dict(blob["hindsight_buffer"])
         self.epsilon, self.episodes_done, self.env_steps = blob["epsilon"], blob["episodes_done"], blob["env_steps"]

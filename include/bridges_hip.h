@@ -1007,6 +1007,29 @@ int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_
                               const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
                               const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
                               int64_t scratch_bytes, void* stream);
+/* The same relabelling for a loop on n-step returns: the h-step rows of the relabelled walk, in the form of bridges_nstep_fold.
+ * Per ended env e and slot g the eligible blocks, the choice, the targets and the walk are bridges_hindsight_relabel's; let the
+ * walk have the L one-step rows r_0 .. r_{L-1} (exactly the rows that entry writes for (e, g)).  The slot emits L rows, one per
+ * start t = 0 .. L-1, ascending: h = min(n_step, L - t), last = t + h - 1, and the row is r_last with
+ *   REC_LIN = the return  acc = 0, disc = 1; for k = 0 .. h-1: acc += disc * lin(r_{t+k}); disc *= gamma  (binary64, in this order,
+ *     no fused multiply-add: steps 1-2 of bridges_nstep_fold on the RELABELLED lin),
+ *   REC_STABLE_S and REC_TD = those of r_t, the start's,  and h as an exact double in one more column, W;
+ * block list, action, REWARD, DONE, STABLE_N and the whole relabelled tail stay r_last's.  The end of the walk flushes every pending
+ * start whether or not r_{L-1} has DONE: under hindsight targets a final step that is not terminal bootstraps like any other, and
+ * its tail rows are h-step rows with h < n_step that bootstrap from s_L.  (This is where the rule differs from bridges_nstep_fold,
+ * in which only DONE flushes.)  n_step = 1 gives bridges_hindsight_relabel's rows with a column of 1.0 appended, bit for bit: the
+ * relabelled lin is a non-negative finite float, so 0 + 1 * lin keeps its bits.
+ * out [E * K * G, W + 1] f64: env ascending, then g, then start t; *count the number of rows -- the number the one-step entry
+ * reports for the same inputs; rows at or beyond it are not written.  Three launches (the count and the scan are the sibling's),
+ * no atomics, no host wait: the same bits on every call.  scratch: bridges_hindsight_relabel_scratch(E, G) bytes, as there.
+ * Returns -1 and launches nothing for: whatever bridges_hindsight_relabel refuses (W is the width of the input); n_step outside
+ * 1..BRIDGES_NSTEP_MAX; a gamma that is not finite; an out that is not 8-byte aligned.  E == 0 returns 0 and launches nothing. */
+int bridges_hindsight_relabel_nstep(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                                    const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed,
+                                    int32_t env_id_base, const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape,
+                                    const double* grid_x, const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step,
+                                    double gamma, double* out /* [E*K*G, W+1] */, int32_t* count, void* scratch,
+                                    int64_t scratch_bytes, void* stream);
 
 /* Inference epilogues of the conv Q-networks (robotoddler/models/cv.py:5-17, 41-73, 108-170: Conv2d -> ReLU
  * [-> MaxPool2d(2)]), one pass instead of torch's three; bit-identical to relu(conv + bias) / maxpool(relu(conv + bias)).

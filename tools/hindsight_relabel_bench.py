@@ -4,7 +4,9 @@ random targets under the synthetic random policy, the loop's buffer written ever
 call with nothing ended (three launches that leave at once: the floor a lock-step without finished episodes pays).  The buffer
 write (two indexed copies) is timed beside them.  Warm-up first; prints one JSON line with the medians and the spread.
     python tools/hindsight_relabel_bench.py [--envs 4096] [--random_targets 3] [--hindsight_goals 1] [--max_steps 15] [--reps 40]
-The work of a call grows with the episodes that ended: ended_per_call and rows_per_call are printed beside the times."""
+The work of a call grows with the episodes that ended: ended_per_call and rows_per_call are printed beside the times.
+--n_step n: in front of those calls, on the same buffers (the operator only reads them), the folding entry
+(bridges_hindsight_relabel_nstep, gamma 0.95) and the one-step entry, alternating likewise: nstep_fold and one_step in the line."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -12,6 +14,7 @@ import numpy as np
 import torch
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomTargets, VecAssemblyGym
+from bridges_hip import dqn_ops
 from robotoddler.training import records as R
 
 ap = argparse.ArgumentParser()
@@ -20,6 +23,7 @@ ap.add_argument("--random_targets", type=int, default=3, metavar="T")
 ap.add_argument("--hindsight_goals", type=int, default=1, metavar="G")
 ap.add_argument("--max_steps", type=int, default=15)
 ap.add_argument("--reps", type=int, default=40)
+ap.add_argument("--n_step", type=int, default=0, metavar="n", help="also time the folding entry at this n against the one-step entry")
 ap.add_argument("--warmup", type=int, default=20, help="lock-steps before the timed ones (episodes of every length are then in flight)")
 a = ap.parse_args()
 assert a.reps >= 20
@@ -30,6 +34,15 @@ env = VecAssemblyGym(E, [load_urdf("shapes/trapezoid.urdf")], [], RandomTargets(
 env.reset()
 hb = R.HindsightBuffer(E, R.RECORD_WIDTH + 3 * T, dev, goals=a.hindsight_goals, n_blocks=env.K)
 nothing = torch.zeros(E, dtype=torch.bool, device=dev)
+if a.n_step:
+    out_n = torch.empty((hb.out.shape[0], hb.out.shape[1] + 1), dtype=torch.float64, device=dev)
+    count_n = torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def entry(ended, fold):
+    """One of the two entries on the buffer as it stands (nothing is emptied)."""
+    kw = dict(out=out_n, count=count_n, n_step=a.n_step, gamma=0.95) if fold else dict(out=hb.out, count=hb.count)
+    return dqn_ops.hindsight_relabel(env, hb.rows, hb.flags, hb.length, ended, hb.episode, hb.goals, scratch=hb._scratch, **kw)
 
 
 def timed(fn):
@@ -41,7 +54,7 @@ def timed(fn):
     return start.elapsed_time(stop) * 1e3, out                      # us
 
 
-times = dict(relabel=[], nothing_ended=[], buffer_write=[])
+times = dict(relabel=[], nothing_ended=[], buffer_write=[], **(dict(nstep_fold=[], one_step=[]) if a.n_step else {}))
 ended_n, rows_n = [], []
 for it in range(a.warmup + a.reps):
     env.select_random()
@@ -55,6 +68,8 @@ for it in range(a.warmup + a.reps):
     t_write, _ = timed(lambda: hb.write(full, env.step_flags, valid, episode))
     order = ("nothing_ended", "relabel") if it % 2 else ("relabel", "nothing_ended")
     got = {}
+    for name in (("nstep_fold", "one_step") if it % 2 else ("one_step", "nstep_fold")) if a.n_step else ():
+        got[name], _ = timed(lambda: entry(ended, name == "nstep_fold"))
     for name in order:                                               # (the call with nothing ended leaves the buffer as it is)
         got[name], out = timed(lambda: hb.relabel(env, ended if name == "relabel" else nothing))
         if name == "relabel":
@@ -70,6 +85,8 @@ for name, t in times.items():
     t = np.array(t)
     q1, med, q3 = np.percentile(t, [25, 50, 75])
     summary[name] = dict(median_us=float(med), min_us=float(t.min()), max_us=float(t.max()), iqr_us=float(q3 - q1), calls=len(t))
+if a.n_step:
+    summary["nstep_minus_one_step_us"] = summary["nstep_fold"]["median_us"] - summary["one_step"]["median_us"]
 print(json.dumps(dict(config=vars(a), **summary, ended_per_call=float(np.mean(ended_n)), rows_per_call=float(np.mean(rows_n)),
                       us_per_ended_episode=(summary["relabel"]["median_us"] - summary["nothing_ended"]["median_us"]) / max(np.mean(ended_n), 1e-9),
                       note="HIP events around single calls (host launch gaps included), the two calls alternating in one process; "

@@ -63,7 +63,7 @@ add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--pr
 add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
 add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_clip L0]: Munchausen targets (VecDQN(munchausen_alpha=A, munchausen_clip=L0))
 add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
-add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] (VecDQN(hindsight=..., hindsight_goals=G))
+add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] [--hindsight_fold] (VecDQN(hindsight=..., ...))
 add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] [--search_particles --search_temperature T
                                          #  [--search_resample_temperature TR]] (VecDQN(search_every=N, ..., search_sampler="particles", ...))
 a = ap.parse_args()

@@ -581,19 +581,39 @@ def build_parser():
     p.add_argument("--random_tower_height", type=parse_size_range, default=argparse.SUPPRESS, metavar="LO:HI",
                    help="Vectorised loop: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI, as "
                         "--random_bridge_length draws the span.")
+    add_training_arguments(p)
+    add_eval_beam_argument(p)
+    add_eval_particle_arguments(p)
+    return p
+
+
+def add_training_arguments(p, prioritized_flag=False):
+    """Every option group of the vectorised loop's training, in the order --help lists them: the one list build_parser and the
+    tools that train through VecDQN share (``prioritized_flag``: see add_priority_arguments)."""
     add_curriculum_arguments(p)
     add_n_step_argument(p)
     add_double_q_argument(p)
     add_target_temperature_argument(p)
     add_relative_temperature_arguments(p)
     add_munchausen_arguments(p)
-    add_priority_arguments(p)
+    add_priority_arguments(p, prioritized_flag=prioritized_flag)
     add_exploration_arguments(p)
     add_hindsight_arguments(p)
     add_search_arguments(p)
-    add_eval_beam_argument(p)
-    add_eval_particle_arguments(p)
-    return p
+
+
+def agent_options_from_args(args, num_envs=None):
+    """VecDQN's keyword arguments for the groups of add_training_arguments, from parsed options (``num_envs``: for a parser whose
+    flag has another name).  The groups are asked in the order main() checks them, so a line with two faults is refused in the
+    words main() would use."""
+    from robotoddler.training.vec_dqn import curriculum_from_args
+    if num_envs is not None:
+        args = dict(args, num_envs=num_envs)
+    out = dict(curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1), double_q=bool(args.get('double_q', False)))
+    for group in (target_temperature_from_args, relative_temperature_from_args, munchausen_from_args, priority_from_args,
+                  exploration_from_args, hindsight_from_args, search_from_args):
+        out.update(group(args))
+    return out
 
 
 EXPLORATIONS = ("epsilon_greedy", "boltzmann")

@@ -55,6 +55,11 @@ from robotoddler.training import train_step as T
 # --random_obstacles: every obstacle of every env is drawn from x in [-3, 3), z in [0.3, 2.5) at the start of an episode
 OBSTACLE_RANGE = ((-3.0, 3.0), (0.3, 2.5))
 SEARCH_SEED = 24681357                                   # particle_search: its stream is seeded with SEARCH_SEED + the agent's seed
+# the means that ride to the host behind a train_steps call's losses, under their log keys (and attribute names) in the order
+# _targets stacks them: soft targets, a relative target temperature, Munchausen targets
+SOFT_TARGET_KEYS = ("target_entropy", "soft_value_gap")
+RELATIVE_TARGET_KEYS = ("target_temperature_effective",)
+MUNCHAUSEN_KEYS = ("munchausen_bonus", "munchausen_clipped", "munchausen_missed")
 
 
 class TargetBatch(NamedTuple):
@@ -77,7 +82,7 @@ class VecDQN:
     hindsight = hindsight_buffer = curriculum = priority_beta = _rows_seen_dev = _hash_mult = _task_mult = last_search = None
     target_temperature = _soft_stats = target_entropy = soft_value_gap = None
     temp_relative = target_temp_relative = hindsight_fold = False
-    spread_floor, temperature_effective, target_temperature_effective, _temp_out = 1e-3, None, None, None
+    spread_floor, temperature_effective, target_temperature_effective, _temp_out, _soft_names = 1e-3, None, None, None, ()
     munchausen = replay_env_s = munchausen_bonus = munchausen_clipped = munchausen_missed = None
     search_sampler = search_gen = search_temperature = search_resample_temperature = None
 
@@ -253,7 +258,7 @@ class VecDQN:
                 raise ValueError(f"VecDQN(target_temperature={target_temperature!r}): a finite number > 0 (None: the max-operator target)")
             target_temperature = float(target_temperature)
         self.target_temperature = target_temperature
-        self._soft_stats = None                              # [2] on the device: what the last _targets call left for the log
+        self._soft_stats, self._soft_names = None, ()        # on the device: what the last _targets call left for the log, and its keys
         self.target_entropy = self.soft_value_gap = None
         self._init_search(env, search_every, search_tasks, search_width, search_merge, search_priority, per_env_tasks, prioritized,
                           sampler=search_sampler, temperature=search_temperature, resample_temperature=search_resample_temperature)
@@ -1235,7 +1240,7 @@ class VecDQN:
         select_q, double_q = None, self.double_q
         soft = self.target_temperature is not None
         soft_feat = soft_row = soft_head = None
-        self._soft_stats = None
+        self._soft_stats, self._soft_names = None, ()
         if idx.numel() and self._factored(self.target_net):
             # q of every next candidate through the factored forward on the bit-packed rasters; the 8204-wide output
             # (successor features) is only needed for the arg-max row of each transition: its channel 0 from the first-layer
@@ -1289,12 +1294,13 @@ class VecDQN:
             both = torch.stack([stats["entropy"], at_max - stats["value"]]
                                + ([stats["temp_out"].float()] if self.target_temp_relative else []))[:, :n]
             self._soft_stats = torch.where(done[:n], torch.zeros_like(both), both).sum(dim=1) / (~done[:n]).sum().clamp_(min=1)
+            self._soft_names = SOFT_TARGET_KEYS + (RELATIVE_TARGET_KEYS if self.target_temp_relative else ())
             if munch is not None:
                 # the log's three: the mean bonus, the share at or below the clip, the taken actions not found (over the n sampled)
                 found = stats["miss"][:n] == 0
                 extra = torch.stack([stats["bonus"][:n].mean(), ((stats["tlogp"][:n] <= munch[1]) & found).float().mean(),
                                      stats["miss"][:n].sum().float()])
-                self._soft_stats = torch.cat([self._soft_stats, extra])
+                self._soft_stats, self._soft_names = torch.cat([self._soft_stats, extra]), self._soft_names + MUNCHAUSEN_KEYS
         elif idx.numel():
             q_target, sf_target = dqn_ops.next_targets(seg, nq, done, self.gamma, next_sf=nsf0 if use_sf else None,
                                                        action_raster=sf_action.squeeze(1) if use_sf else None, lin=lin,
@@ -1454,25 +1460,15 @@ class VecDQN:
                 self.opt.step()
                 losses.append(loss.detach())
             out = torch.stack(losses)
-        soft = self._soft_stats
-        if soft is not None:                                 # soft targets: the log's two (relative: three) means ride behind the losses
-            out = torch.cat([out.to(torch.float32).reshape(-1), soft.to(torch.float32)])
+        if self._soft_stats is not None:                     # soft targets: the means named in _soft_names ride behind the losses
+            out = torch.cat([out.to(torch.float32).reshape(-1), self._soft_stats.to(torch.float32)])
         if defer:
             host = torch.empty(out.numel(), dtype=torch.float32, pin_memory=True)
             host.copy_(out, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
-            return DeferredLosses(host, done, drv, owner=self if soft is not None else None)
-        losses = out.tolist()                                # the one host sync of the call
-        if soft is not None:
-            k = soft.numel()
-            losses, tail = losses[:-k], losses[-k:]
-            self.target_entropy, self.soft_value_gap = tail[:2]
-            if self.target_temp_relative:
-                self.target_temperature_effective = tail[2]
-            if self.munchausen is not None and k >= 5:
-                self.munchausen_bonus, self.munchausen_clipped, self.munchausen_missed = tail[-3:]
-        return drv.check_losses(losses) if drv is not None else losses
+            return DeferredLosses(host, done, drv, names=self._soft_names, owner=self)
+        return DeferredLosses(out, None, drv, names=self._soft_names, owner=self).get()     # the one host sync of the call
 
     def train_step(self):
         out = self.train_steps(1)
@@ -1483,11 +1479,38 @@ class VecDQN:
         update_target_net(self.policy_net, self.target_net, self.tau)
 
     # ------------------------------------------------------------------ checkpoint of what the nets / ring do not hold
+    def _recorded_options(self):
+        """What a checkpoint records about the options, one row each: the key in the file; what its value names, for a refusal;
+        this agent's value (None without the option: save_extra then writes no key); what a file without the key means; and why
+        a run under another value cannot go on from the file (None: recorded only, load_extra does not compare it)."""
+        T, O = int(self.n_task_targets), int(self.n_task_obstacles)
+        backup, rows = "the nets were trained towards another backup operator", "the ring does not hold the "
+        return (
+            # (T, O) of the records' tails: the width alone cannot tell T = 3, O = 0 from T = 2, O = 1 (a file written before the
+            # tails held obstacles holds targets only, whose number the ring's width check has pinned)
+            ("task_shape", "(targets, obstacles)", (T, O), (T, 0), "the tails do not mean the same task"),
+            ("n_step", "n_step", int(self.n_step), 1, "the rows of the ring do not mean the same returns"),
+            ("target_temperature", "target_temperature", None if self.target_temperature is None else float(self.target_temperature),
+             None, backup),
+            ("target_temp_relative", "target_temp_relative, spread_floor", float(self.spread_floor) if self.target_temp_relative else None,
+             None, backup),
+            ("munchausen", "(munchausen_alpha, munchausen_clip)", None if self.munchausen is None else tuple(map(float, self.munchausen)),
+             None, backup),
+            ("search_sampler", "(search_sampler, search_temperature, search_resample_temperature)",
+             (str(self.search_sampler), float(self.search_temperature), float(self.search_resample_temperature))
+             if self.search_sampler is not None else None, None, rows + "rows of the same search"),
+            ("hindsight", "(hindsight, hindsight_goals)", (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None,
+             None, rows + "same mix of rolled-out and relabelled rows"),
+            ("hindsight_fold", "hindsight_fold", True if self.hindsight_fold else None, False, "the two runs do not agree on the option"),
+            # what the schedule's temperature multiplies goes the way of the exploration setting itself
+            ("temp_relative", "temp_relative, spread_floor", float(self.spread_floor) if self.temp_relative else None, None, None),
+        )
+
     def save_extra(self, path, **counters):
         blob = dict(epsilon=float(self.epsilon), episodes_done=int(self.episodes_done), env_steps=int(self.env_steps),
                     step_images=self.step_images.cpu(), sample_gen=self.sample_gen.get_state().cpu(),
-                    explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()},
-                    task_shape=(int(self.n_task_targets), int(self.n_task_obstacles)), n_step=int(self.n_step))
+                    explore_gen=self.explore_gen.get_state().cpu(), counters={k: int(v) for k, v in counters.items()})
+        blob.update({key: value for key, _, value, _, _ in self._recorded_options() if value is not None})
         if self.curriculum is not None:                      # one more key: (ema, seen), weights, sums and accumulator
             blob["curriculum"] = self.curriculum.state_dict()
         if self.priority_beta is not None:                   # one more key: the annealing clock of the weights' exponent
@@ -1496,22 +1519,10 @@ class VecDQN:
             blob["temperature"] = float(self.temperature)
         if self.search_every:                                # one more key: the lock-steps since the last search
             blob["search_phase"] = int(self.search_calls)
-        if self.search_sampler is not None:                  # two more keys: the sampler's settings and where its stream stands
-            blob["search_sampler"] = (str(self.search_sampler), float(self.search_temperature), float(self.search_resample_temperature))
+        if self.search_sampler is not None:                  # one more key: where the particle search's stream stands
             blob["search_gen"] = self._search_generator().get_state().cpu()
-        if self.target_temperature is not None:              # one more key: the temperature of the soft targets
-            blob["target_temperature"] = float(self.target_temperature)
-        if self.target_temp_relative:                        # one more key: ... and that it multiplies the spread, above which floor
-            blob["target_temp_relative"] = float(self.spread_floor)
-        if self.munchausen is not None:                      # one more key: the weight and the clip of the Munchausen bonus
-            blob["munchausen"] = (float(self.munchausen[0]), float(self.munchausen[1]))
-        if self.temp_relative:                               # one more key: what the schedule's temperature multiplies
-            blob["temp_relative"] = float(self.spread_floor)
-        if self.hindsight is not None:                       # two more keys: the setting and the running episodes
-            blob["hindsight"] = (str(self.hindsight), int(self.hindsight_goals))
+        if self.hindsight is not None:                       # one more key: the running episodes
             blob["hindsight_buffer"] = self.hindsight_buffer.state_dict()
-            if self.hindsight_fold:                          # one more key: the relabelled rows are folded as the loop's own are
-                blob["hindsight_fold"] = True
         torch.save(blob, path)
 
     def load_extra(self, path):
@@ -1521,53 +1532,17 @@ class VecDQN:
         env-step count were never saved -- re-seeds its exploration stream from (seed, rank, lock-step) so that the
         ranks keep drawing different uniforms, and starts its local env-step count from rank 0's."""
         blob = torch.load(path, weights_only=True)
-        # (T, O) of the records' tails: the width alone cannot tell T = 3, O = 0 from T = 2, O = 1 (a file written before the
-        # tails held obstacles carries no entry: it holds targets only, whose number the ring's width check has pinned)
-        want = (int(self.n_task_targets), int(self.n_task_obstacles))
-        got = tuple(int(v) for v in blob.get("task_shape", (want[0], 0)))
-        if got != want:
-            raise ValueError(f"{path} was written by a run whose records end in {got[0]} targets and {got[1]} obstacles, this "
-                             f"agent's end in {want[0]} targets and {want[1]} obstacles: the tails do not mean the same task")
-        # (a file written before the loop had n-step returns carries no entry: its rows are one-step records)
-        got_n = int(blob.get("n_step", 1))
-        want_n = int(self.n_step)
-        if got_n != want_n:
-            raise ValueError(f"{path} was written by a run with n_step = {got_n}, this agent folds n_step = {want_n}: the rows "
-                             "of the ring do not mean the same returns")
-        # (a file of a run without soft targets carries no entry)
-        got_t = blob.get("target_temperature")
-        got_t = None if got_t is None else float(got_t)
-        if got_t != self.target_temperature:
-            raise ValueError(f"{path} was written by a run with target_temperature = {got_t}, this agent has "
-                             f"{self.target_temperature}: the nets were trained towards another backup operator")
-        # (a file of a run whose soft targets took the scalar temperature carries no entry)
-        got_r = (True, float(blob["target_temp_relative"])) if "target_temp_relative" in blob else None
-        want_r = (True, float(self.spread_floor)) if self.target_temp_relative else None
-        if got_r != want_r:
-            raise ValueError(f"{path} was written by a run with (target_temp_relative, spread_floor) = {got_r}, this agent has "
-                             f"{want_r}: the nets were trained towards another backup operator")
-        # (a file of a run without Munchausen targets carries no entry)
-        got_m = tuple(float(v) for v in blob["munchausen"]) if "munchausen" in blob else None
-        if got_m != self.munchausen:
-            raise ValueError(f"{path} was written by a run with (munchausen_alpha, munchausen_clip) = {got_m}, this agent has "
-                             f"{self.munchausen}: the nets were trained towards another backup operator")
-        # (a file of a run whose search in training is the beam search, or that has none, carries no entry)
-        got_s = (str(blob["search_sampler"][0]), *(float(v) for v in blob["search_sampler"][1:])) if "search_sampler" in blob else None
-        want_s = ((str(self.search_sampler), float(self.search_temperature), float(self.search_resample_temperature))
-                  if self.search_sampler is not None else None)
-        if got_s != want_s:
-            raise ValueError(f"{path} was written by a run with (search_sampler, search_temperature, search_resample_temperature) = "
-                             f"{got_s}, this agent has {want_s}: the ring does not hold the rows of the same search")
-        # (a file of a run without hindsight relabelling carries no entry)
-        got_h = tuple(blob["hindsight"]) if "hindsight" in blob else None
-        want_h = (str(self.hindsight), int(self.hindsight_goals)) if self.hindsight is not None else None
-        if got_h != want_h:
-            raise ValueError(f"{path} was written by a run with (hindsight, hindsight_goals) = {got_h}, this agent has {want_h}: the "
-                             "ring does not hold the same mix of rolled-out and relabelled rows")
-        if bool(blob.get("hindsight_fold", False)) != self.hindsight_fold:
-            raise ValueError(f"{path} was written by a run with hindsight_fold = {bool(blob.get('hindsight_fold', False))}, this agent "
-                             f"has hindsight_fold = {self.hindsight_fold}: the two runs do not agree on the option")
-        if want_h is not None:
+        for key, what, want, absent, why in self._recorded_options():
+            got = blob.get(key, absent)
+            got = tuple(got) if isinstance(got, (tuple, list)) else got
+            want = absent if want is None else want
+            if why is None or got == want:
+                continue
+            if key == "task_shape":
+                raise ValueError(f"{path} was written by a run whose records end in {got[0]} targets and {got[1]} obstacles, this "
+                                 f"agent's end in {want[0]} targets and {want[1]} obstacles: {why}")
+            raise ValueError(f"{path} was written by a run with {what} = {got}, this agent has {what} = {want}: {why}")
+        if self.hindsight is not None:
             self.hindsight_buffer.load_state_dict(blob["hindsight_buffer"])
         self.epsilon, self.episodes_done, self.env_steps = blob["epsilon"], blob["episodes_done"], blob["env_steps"]
         self.step_images.copy_(blob["step_images"])
@@ -1584,7 +1559,7 @@ class VecDQN:
             self.temperature = float(blob.get("temperature", self.temp_start))
         if self.search_every:                                # (a file of a run without the option: phase 0)
             self.search_calls = int(blob.get("search_phase", 0)) % self.search_every
-        if want_s is not None:
+        if self.search_sampler is not None:
             self._search_generator().set_state(blob["search_gen"])
         return blob["counters"]
 
@@ -1606,9 +1581,10 @@ class VecDQN:
                             *(torch.zeros((rows, n), dtype=torch.float64, device=self.device) for _ in range(4)))
         return dqn_ops.nstep_fold(rec.contiguous(), valid, self.gamma, self.n_step, *self._window)
 
-    def _count(self, name):
-        """One of the last lock-step's counts, as it arrived in pinned memory."""
-        return int(self._counts_host[self._count_names.index(name)])
+    def _count(self, name, float64=False):
+        """One of the last lock-step's counts, as it arrived in pinned memory (float64: the slot holds a float64's bits)."""
+        at = self._count_names.index(name)
+        return float(self._counts_host[at:at + 1].view(torch.float64)) if float64 else int(self._counts_host[at])
 
     def lockstep(self, n_train_steps, defer_losses=False):
         """act -> all-gather -> replay push -> n optimiser steps -> soft update.  defer_losses=True returns the losses as
@@ -1657,8 +1633,7 @@ class VecDQN:
         if boltzmann:
             self.explored_fraction = self._count("explored") / n_valid if n_valid else None
         if self.temp_relative:
-            at = self._count_names.index("temp_sum")
-            self.temperature_effective = float(self._counts_host[at:at + 1].view(torch.float64)) / n_valid if n_valid else None
+            self.temperature_effective = self._count("temp_sum", float64=True) / n_valid if n_valid else None
         if self.n_step > 1 and folded is None:
             # several ranks: the fold runs AFTER the gather, on the uncompacted rows of all ranks, so every rank holds the same
             # windows and pushes the same rows; the collective carries what it carries for n_step = 1
@@ -1713,33 +1688,28 @@ class _TransitionRows:
 
 
 class DeferredLosses:
-    """Losses of one train_steps call on their way to the host (pinned buffer + event)."""
+    """Losses of one train_steps call on their way to the host (pinned buffer + event; no event: a tensor read where it lies).
+    ``names``: the log keys of the means that follow the losses in the buffer, one value each (VecDQN._soft_names)."""
 
-    def __init__(self, host, done, driver, owner=None):
+    def __init__(self, host, done, driver, names=(), owner=None):
         self._host, self._done, self._driver, self._list = host, done, driver, None
-        self._owner = owner                                  # soft targets: the agent whose two log means follow the losses
-        self.soft = None                                     # ... and, after get(), those means under their log keys
+        self._names, self._owner = tuple(names), owner       # the agent that keeps the means as attributes of the same names
+        self.soft = None                                     # after get(): the means under their log keys (None: there are none)
 
     def get(self):
         if self._list is None:
             if self._host is None:
                 self._list = []
             else:
-                self._done.synchronize()
+                if self._done is not None:
+                    self._done.synchronize()
                 self._list = self._host.tolist()
-                if self._owner is not None:
-                    rel = 1 if getattr(self._owner, "target_temp_relative", False) else 0      # relative: the mean T_e behind them
-                    mun = 3 if getattr(self._owner, "munchausen", None) is not None else 0      # Munchausen: its three behind those
-                    k = 2 + rel + mun
+                if self._names:
+                    k = len(self._names)
                     self._list, tail = self._list[:-k], self._list[-k:]
-                    self.soft = dict(target_entropy=tail[0], soft_value_gap=tail[1])
-                    self._owner.target_entropy, self._owner.soft_value_gap = tail[:2]
-                    if rel:
-                        self.soft["target_temperature_effective"] = self._owner.target_temperature_effective = tail[2]
-                    if mun:
-                        for key, v in zip(("munchausen_bonus", "munchausen_clipped", "munchausen_missed"), tail[-3:]):
-                            self.soft[key] = v
-                            setattr(self._owner, key, v)
+                    self.soft = dict(zip(self._names, tail))
+                    for key, v in self.soft.items():
+                        setattr(self._owner, key, v)
                 if self._driver is not None:
                     self._driver.check_losses(self._list)
         return self._list
@@ -1759,12 +1729,8 @@ def lockstep_log_values(info):
                 steps_per_s=info['steps_per_s'], **{k: info.get(k) for k in EPISODE_KEYS})
     if 'temperature' in info:                                # Boltzmann exploration only
         vals.update(temperature=info['temperature'], explored_fraction=info.get('explored_fraction'))
-    if 'target_entropy' in info:                             # soft targets only
-        vals.update(target_entropy=info['target_entropy'], soft_value_gap=info['soft_value_gap'])
-    for key in ('temperature_effective', 'target_temperature_effective'):         # relative temperatures only
-        if key in info:
-            vals[key] = info[key]
-    for key in ('munchausen_bonus', 'munchausen_clipped', 'munchausen_missed'):    # Munchausen targets only
+    # what rode behind the losses, each only with its option; between them the relative exploration temperature's mean
+    for key in SOFT_TARGET_KEYS + ('temperature_effective',) + RELATIVE_TARGET_KEYS + MUNCHAUSEN_KEYS:
         if key in info:
             vals[key] = info[key]
     if 'hindsight_rows' in info:                             # hindsight relabelling only
@@ -1866,9 +1832,8 @@ def next_multiple(n, every):
 
 
 def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=False):
-    from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, exploration_from_args, hindsight_from_args, make_nets,
-                                                    munchausen_from_args, relative_temperature_from_args, target_temperature_from_args,
-                                                    search_from_args, track_run_sinks, eval_particles_from_args)
+    from robotoddler.training.successor_dqn import (EVAL_DEFAULTS, agent_options_from_args, make_nets, track_run_sinks,
+                                                    eval_particles_from_args)
     backend = os.environ.get("BRIDGES_DIST_BACKEND")          # 'gloo' = rehearsal with several ranks on one card
     rank, world = D.init(backend=backend, device=device)
     names = dict(trapezoid=["trapezoid"], hexagon=["hexagon"], both=["trapezoid", "hexagon"])[args['shapes']]
@@ -1910,15 +1875,9 @@ def run_vectorised(args, device, aim_run=None, wandb_run=None, return_agent=Fals
     opt = torch.optim.Adam(policy_net.parameters(), lr=args['learning_rate'], fused=True)    # one launch for all tensors
     capacity = max(args['replay_buffer_capacity'], 4 * args['num_envs'] * world)
     agent = VecDQN(policy_net, target_net, opt, env, capacity, args['batch_size'], args['gamma'], args['tau'],
-                   args['loss_function'], seed=seed, rank=rank, prioritized=args.get('prioritized_replay', False),
-                   stable_actions_only=args.get('stable_actions_only', False), episode_stats=True,
-                   per_env_tasks=bool(random_targets or family), per_env_obstacles=bool(random_obstacles or family),
-                   task_channels=task_channels, curriculum=curriculum_from_args(args), n_step=args.get('n_step', 1),
-                   double_q=bool(args.get('double_q', False)), priority_alpha=args.get('priority_alpha', 1.0),
-                   priority_refresh=bool(args.get('priority_refresh', False)), priority_beta=args.get('priority_beta'),
-                   priority_beta_anneal=args.get('priority_beta_anneal', 0), **exploration_from_args(args),
-                   **hindsight_from_args(args), **search_from_args(args), **target_temperature_from_args(args),
-                   **relative_temperature_from_args(args), **munchausen_from_args(args))
+                   args['loss_function'], seed=seed, rank=rank, stable_actions_only=args.get('stable_actions_only', False),
+                   episode_stats=True, per_env_tasks=bool(random_targets or family),
+                   per_env_obstacles=bool(random_obstacles or family), task_channels=task_channels, **agent_options_from_args(args))
     # greedy evaluation (successor_dqn.py:749-781 of the reference): rank 0 runs one episode in each of --eval_envs envs of the
     # training task every --evaluate_every finished episodes (--random_targets: a sampler of its own for the evaluation env,
     # whose seed gives it other tasks than any rollout env's; evaluate() resets it, so every evaluation sees the same tasks)

@@ -252,7 +252,15 @@ def test_tools_take_the_flags():
     for tool in ("train_throughput.py", "learning_curve.py", "find_syncs.py"):
         with open(os.path.join(ROOT, "tools", tool)) as fh:
             text = fh.read()
-        assert "add_munchausen_arguments(ap)" in text and "**munchausen_from_args(vars(a))" in text, tool
+        # the tools take every training option through the two shared functions, whose Munchausen group is checked below
+        assert "add_training_arguments(ap" in text and "**agent_options_from_args(vars(a)" in text, tool
+    import argparse
+    from robotoddler.training.successor_dqn import add_training_arguments, agent_options_from_args
+    ap = argparse.ArgumentParser()
+    add_training_arguments(ap, prioritized_flag=True)
+    a = ap.parse_args(["--target_temperature", "1.0", "--munchausen_alpha", "0.9", "--munchausen_clip", "-0.5"])
+    kw = agent_options_from_args(vars(a), num_envs=64)
+    assert (kw["munchausen_alpha"], kw["munchausen_clip"], kw["target_temperature"]) == (0.9, -0.5, 1.0)
     with open(os.path.join(ROOT, "tools", "soft_target_bench.py")) as fh:
         assert "--munchausen" in fh.read()
 
@@ -298,10 +306,12 @@ def test_log_values_carry_the_keys_only_with_the_option():
             pass
     owner = type("A", (), {})()
     owner.munchausen = (0.9, -1.0)
-    d = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125, -0.75, 0.25, 0.0]), Ready(), None, owner=owner)
+    soft, munch = ("target_entropy", "soft_value_gap"), ("munchausen_bonus", "munchausen_clipped", "munchausen_missed")
+    d = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125, -0.75, 0.25, 0.0]), Ready(), None, names=soft + munch, owner=owner)
     assert d.get() == [1.0, 2.0]
     assert d.soft == dict(target_entropy=0.5, soft_value_gap=0.125, munchausen_bonus=-0.75, munchausen_clipped=0.25, munchausen_missed=0.0)
     assert owner.munchausen_bonus == -0.75 and owner.munchausen_missed == 0.0
     owner.target_temp_relative = True
-    d = DeferredLosses(torch.tensor([1.0, 0.5, 0.125, 3.0, -0.75, 0.25, 0.0]), Ready(), None, owner=owner)
+    d = DeferredLosses(torch.tensor([1.0, 0.5, 0.125, 3.0, -0.75, 0.25, 0.0]), Ready(), None,
+                       names=soft + ("target_temperature_effective",) + munch, owner=owner)
     assert d.get() == [1.0] and d.soft["target_temperature_effective"] == 3.0 and d.soft["munchausen_bonus"] == -0.75

@@ -332,7 +332,8 @@ def test_log_values_carry_the_keys_only_with_the_options():
         def synchronize(self):
             pass
     owner = type("A", (), dict(target_temp_relative=True))()
-    d = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125, 3.0]), Ready(), None, owner=owner)
+    d = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125, 3.0]), Ready(), None,
+                       names=("target_entropy", "soft_value_gap", "target_temperature_effective"), owner=owner)
     assert d.get() == [1.0, 2.0] and d.soft == dict(target_entropy=0.5, soft_value_gap=0.125, target_temperature_effective=3.0)
     assert owner.target_temperature_effective == 3.0 and owner.soft_value_gap == 0.125
     # the float64 sum of the effective temperatures rides among the int64 counts as its bits

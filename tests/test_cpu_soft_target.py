@@ -214,7 +214,10 @@ def test_log_values_carry_the_keys_only_with_the_option():
         def synchronize(self):
             pass
     owner = type("A", (), {})()
-    d = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125]), Ready(), None, owner=owner)
+    d = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125]), Ready(), None, names=("target_entropy", "soft_value_gap"), owner=owner)
     assert d.get() == [1.0, 2.0] and d.soft == dict(target_entropy=0.5, soft_value_gap=0.125) and owner.soft_value_gap == 0.125
     plain = DeferredLosses(torch.tensor([1.0, 2.0]), Ready(), None)
     assert plain.get() == [1.0, 2.0] and plain.soft is None
+    # no riders named: nothing is split off, whatever the values and with no owner to write to
+    unsplit = DeferredLosses(torch.tensor([1.0, 2.0, 0.5, 0.125]), Ready(), None, names=())
+    assert unsplit.get() == [1.0, 2.0, 0.5, 0.125] and unsplit.soft is None

@@ -155,6 +155,22 @@ def test_the_loop_trains_and_logs_its_three_keys():
     assert set(deferred.soft) == {"target_entropy", "soft_value_gap", "munchausen_bonus", "munchausen_clipped", "munchausen_missed"}
 
 
+def test_deferred_and_immediate_losses_decode_the_longest_tail_alike():
+    """Two agents of one seed side by side, the losses of one deferred: the same losses and the same six means behind them."""
+    from robotoddler.training.vec_dqn import MUNCHAUSEN_KEYS, RELATIVE_TARGET_KEYS, SOFT_TARGET_KEYS
+    keys = SOFT_TARGET_KEYS + RELATIVE_TARGET_KEYS + MUNCHAUSEN_KEYS
+    now, later = (mlp_agent(tower_env(f32_rasters=False), target_temp_relative=True, **OPTION) for _ in range(2))
+    losses = {now: [], later: []}
+    for _ in range(LOCKSTEPS):
+        losses[now] += now.lockstep(TRAIN_STEPS)[0]
+        deferred = later.lockstep(TRAIN_STEPS, defer_losses=True)[0]
+        losses[later] += deferred.get()
+        assert deferred.soft is None or tuple(deferred.soft) == keys
+        assert [getattr(now, k) for k in keys] == [getattr(later, k) for k in keys]
+    assert len(losses[now]) >= 2 * TRAIN_STEPS and losses[now] == losses[later]
+    assert len(keys) == 6 and all(isinstance(getattr(now, k), float) for k in keys) and later.soft_value_gap == deferred.soft["soft_value_gap"]
+
+
 # ------------------------------------------------------------------------------------------------------------ option off
 def test_the_options_unset_are_the_loop_it_was(monkeypatch):
     from bridges_hip import dqn_ops

@@ -34,25 +34,10 @@ ap.add_argument("--random_targets", type=int, default=0, metavar="T",
                 help="> 0: per-env random tasks (RandomTargets(T), no obstacles; VecDQN(per_env_tasks=True)) instead of the fixed tower")
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomTargets, VecAssemblyGym
-from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
-                                                add_target_temperature_argument, target_temperature_from_args,
-                                                add_relative_temperature_arguments, relative_temperature_from_args,
-                                                add_munchausen_arguments, munchausen_from_args,
-                                                add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
-                                                exploration_from_args, make_nets, priority_from_args,
-                                                add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
-from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
-add_curriculum_arguments(ap)
-add_n_step_argument(ap)
-add_double_q_argument(ap)
-add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
-add_priority_arguments(ap, prioritized_flag=True)
-add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
-add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_clip L0]: Munchausen targets (VecDQN(munchausen_alpha=A, munchausen_clip=L0))
-add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
-add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] [--hindsight_fold] (VecDQN(hindsight=..., ...))
-add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] [--search_particles --search_temperature T
-                                         #  [--search_resample_temperature TR]] (VecDQN(search_every=N, ..., search_sampler="particles", ...))
+from robotoddler.training.successor_dqn import (add_training_arguments, agent_options_from_args, build_parser, check_curriculum,
+                                                make_nets)
+from robotoddler.training.vec_dqn import VecDQN
+add_training_arguments(ap, prioritized_flag=True)    # the training options of the vectorised loop, as successor_dqn.py takes them
 a = ap.parse_args()
 sizes = tuple(int(v) for v in a.random_bridge_length.split(":")) if a.random_bridge_length else None
 check_curriculum(vars(a), sizes)
@@ -70,10 +55,7 @@ env = VecAssemblyGym(a.envs, [load_urdf("shapes/trapezoid.urdf")], obstacles, ta
                      f32_rasters=VecDQN.acting_needs_f32_rasters(pol), candidate_snapshots=False)
 agent = VecDQN(pol, tgt, torch.optim.Adam(pol.parameters(), lr=1e-4, fused=True), env, 200000, 32, 0.95, 0.01,
                "mse_block_features", episode_stats=a.episode_stats, per_env_tasks=bool(sizes or a.random_targets), per_env_obstacles=bool(sizes),
-               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
-               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
-               **relative_temperature_from_args(vars(a)), **munchausen_from_args(vars(a)))
+               **agent_options_from_args(vars(a), num_envs=a.envs))
 
 
 def lockstep():

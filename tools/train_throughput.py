@@ -5,14 +5,9 @@ if "--miopen_search" not in sys.argv:
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
 import torch
-from robotoddler.training.successor_dqn import (add_curriculum_arguments, add_double_q_argument, add_n_step_argument,
-                                                add_target_temperature_argument, target_temperature_from_args,
-                                                add_relative_temperature_arguments, relative_temperature_from_args,
-                                                add_munchausen_arguments, munchausen_from_args,
-                                                add_exploration_arguments, add_priority_arguments, build_parser, check_curriculum,
-                                                exploration_from_args, make_nets, priority_from_args,
-                                                add_hindsight_arguments, hindsight_from_args, add_search_arguments, search_from_args)
-from robotoddler.training.vec_dqn import VecDQN, curriculum_from_args
+from robotoddler.training.successor_dqn import (add_training_arguments, agent_options_from_args, build_parser, check_curriculum,
+                                                make_nets)
+from robotoddler.training.vec_dqn import VecDQN
 from bridges_hip.shapes import load_urdf
 from bridges_hip.vec_env import RandomBridges, RandomObstacles, RandomTargets, VecAssemblyGym
 
@@ -55,17 +50,7 @@ ap.add_argument("--random_bridge_length", default=None, metavar="LO:HI",
                      "(RandomBridges; SuccessorMLP, or ConvNet / UNet with --task_channels)")
 ap.add_argument("--random_tower_height", default=None, metavar="LO:HI",
                 help="a task family instead: bridge_setup(num_stories=n) per env and episode, n drawn from LO..HI")
-add_curriculum_arguments(ap)             # --family_weights W,W,... | --curriculum [--curriculum_every / _beta / _floor]
-add_n_step_argument(ap)                  # --n_step N: n-step returns (VecDQN(n_step=N))
-add_double_q_argument(ap)                # --double_q: double Q-learning targets (VecDQN(double_q=True)); rows_fed counts both passes
-add_target_temperature_argument(ap)      # --target_temperature T: expected-value targets under the Boltzmann policy (VecDQN(target_temperature=T))
-add_priority_arguments(ap, prioritized_flag=True)   # --prioritized_replay [--priority_alpha A] [--priority_refresh] [--priority_beta B [--priority_beta_anneal N]]
-add_relative_temperature_arguments(ap)   # --temp_relative / --target_temp_relative [--spread_floor F]: temperatures as multiples of each state's spread of q
-add_munchausen_arguments(ap)             # --munchausen_alpha A [--munchausen_clip L0]: Munchausen targets (VecDQN(munchausen_alpha=A, munchausen_clip=L0))
-add_exploration_arguments(ap)            # --exploration boltzmann [--temp_start T --temp_end T --temp_decay D] (VecDQN(exploration=...))
-add_hindsight_arguments(ap)              # --hindsight final [--hindsight_goals G] [--hindsight_fold] (VecDQN(hindsight=..., ...))
-add_search_arguments(ap)                 # --search_every N [--search_tasks M] [--search_width B] [--search_merge] [--search_particles --search_temperature T
-                                         #  [--search_resample_temperature TR]] (VecDQN(search_every=N, ..., search_sampler="particles", ...))
+add_training_arguments(ap, prioritized_flag=True)    # the training options of the vectorised loop, as successor_dqn.py takes them
 a = ap.parse_args()
 if a.random_bridge_length and a.random_tower_height:
     ap.error("--random_bridge_length and --random_tower_height name two task families: give one")
@@ -120,10 +105,7 @@ opt = torch.optim.Adam(pol.parameters(), lr=1e-4, fused=not a.no_fused_adam)
 agent = VecDQN(pol, tgt, opt, env, 200000, a.batch, 0.95, 0.01, a.loss, stable_actions_only=a.stable_actions_only,
                episode_stats=a.episode_stats, per_env_tasks=bool(a.random_targets or family),
                per_env_obstacles=bool(a.random_obstacles or family), task_channels=a.task_channels,
-               curriculum=curriculum_from_args(vars(a)), n_step=vars(a).get("n_step", 1), double_q=vars(a).get("double_q", False),
-               **priority_from_args(vars(a)), **exploration_from_args(vars(a)), **hindsight_from_args(vars(a)),
-               **search_from_args(dict(vars(a), num_envs=a.envs)), **target_temperature_from_args(vars(a)),
-               **relative_temperature_from_args(vars(a)), **munchausen_from_args(vars(a)))
+               **agent_options_from_args(vars(a), num_envs=a.envs))
 VecDQN.TRACK_ROWS = True
 if a.no_dedup:
     VecDQN.DEDUP_ROWS = VecDQN.DEDUP_STATES = False

@@ -349,6 +349,11 @@ SIGNATURES = {
                                   i64, vp],
     "bridges_hindsight_relabel_nstep": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, i32, i32, vp, vp, i32, vp, i32,
                                         f64, vp, vp, vp, i64, vp],
+    "bridges_hindsight_per_step_scratch": [i32, i32, C.POINTER(i64)],
+    "bridges_hindsight_per_step": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp,
+                                   i64, vp],
+    "bridges_hindsight_per_step_nstep": [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, i32, i32, vp, vp, i32, vp, i32,
+                                         f64, vp, vp, vp, i64, vp],
     "bridges_successor_loss_weighted": [i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
 }
 

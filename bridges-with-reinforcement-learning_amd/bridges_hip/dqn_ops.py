@@ -337,14 +337,22 @@ def priority_weights(idx, n_rec, batch, beta, scratch):
     return weight
 
 
-def hindsight_relabel_scratch(E, G):
-    """Bytes of scratch bridges_hindsight_relabel needs for E envs and G slots (no GPU needed)."""
+HINDSIGHT_STRATEGIES = ("final", "per_step")
+
+
+def hindsight_relabel_scratch(E, G, strategy="final"):
+    """Bytes of scratch bridges_hindsight_relabel (strategy "final") or bridges_hindsight_per_step ("per_step") needs for E envs
+    and G slots (no GPU needed)."""
+    if strategy not in HINDSIGHT_STRATEGIES:
+        raise ValueError(f"hindsight_relabel_scratch(strategy={strategy!r}): one of {HINDSIGHT_STRATEGIES}")
+    name = "bridges_hindsight_relabel_scratch" if strategy == "final" else "bridges_hindsight_per_step_scratch"
     need = C.c_int64(0)
-    abi.check(abi.lib().bridges_hindsight_relabel_scratch(int(E), int(G), C.byref(need)), "bridges_hindsight_relabel_scratch")
+    abi.check(getattr(abi.lib(), name)(int(E), int(G), C.byref(need)), name)
     return need.value
 
 
-def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, count=None, scratch=None, n_step=1, gamma=None):
+def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, count=None, scratch=None, n_step=1, gamma=None,
+                      strategy="final"):
     """Hindsight relabelling of the episodes that ended in this lock-step (bridges_hindsight_relabel, "final" strategy): buf
     [E, K, W] float64 the buffered records of every env's running episode (a record and its task tail, the env's T targets
     first), flags [E, K, 8] uint8 their step_flags, length [E] int32, ended [E] bool / uint8, episode [E] the task_episode of
@@ -357,10 +365,16 @@ def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, coun
     ``n_step`` / ``gamma``: with n_step = 1 and gamma = None the call above.  Otherwise the h-step rows of the relabelled walks
     (bridges_hindsight_relabel_nstep, 1 <= n_step <= abi.NSTEP_MAX, gamma finite): out [E * K * G, W + 1], one row per start in
     the form of nstep_fold -- the return over h = min(n_step, steps left) relabelled steps in O_LIN, O_STABLE_S and O_TD of the
-    start, h in the last column; the end of a walk flushes its pending starts whether or not its last step is done."""
+    start, h in the last column; the end of a walk flushes its pending starts whether or not its last step is done.
+    ``strategy="per_step"`` (hindsight experience replay's "future"; bridges_hindsight_per_step / _nstep, the rule in
+    include/bridges_hip.h): every transition t gets goals of its own -- a block f >= t of the episode drawn per (slot, t), the
+    others from the structure after step f -- and is emitted once per slot unless the episode was over before t under them.  The
+    same shapes, the same bound of E * K * G rows, the order env, slot, t; scratch: hindsight_relabel_scratch(E, G, "per_step")."""
     L = abi.require_gpu()
     E, K, W = buf.shape
     G = int(G)
+    if strategy not in HINDSIGHT_STRATEGIES:
+        raise ValueError(f"hindsight_relabel(strategy={strategy!r}): one of {HINDSIGHT_STRATEGIES}")
     if not getattr(env, "per_env_tasks", False):
         raise ValueError("hindsight_relabel needs an env with per-env tasks (targets=RandomTargets() / set_targets)")
     fold = not (int(n_step) == 1 and gamma is None)
@@ -386,15 +400,16 @@ def hindsight_relabel(env, buf, flags, length, ended, episode, G, out=None, coun
     assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= E * K * G * Wo
     assert count.dtype == torch.int32 and count.numel() >= 1
     if scratch is None:
-        scratch = torch.empty(max(4 * E * max(G, 1), 4), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(max(4 * E * max(G, 1), 4) * (2 if strategy == "per_step" else 1), dtype=torch.uint8, device=dev)
     head = (E, K, W, T, G, _ptr(buf), _ptr(flags), _ptr(length), _ptr(ended_u8), _ptr(episode), int(env.seed) & (2 ** 64 - 1),
             int(env.env_id_base), env.table.ptr, len(env.table_geoms), len(env.table_geoms) - 1, _ptr(env.grid_x_dev),
             _ptr(env.grid_y_dev), int(env.img), env._gauss_k.data_ptr())
     tail = (_ptr(out), _ptr(count), _ptr(scratch), scratch.numel(), _stream())
+    entry = "bridges_hindsight_relabel" if strategy == "final" else "bridges_hindsight_per_step"
     if fold:
-        abi.check(L.bridges_hindsight_relabel_nstep(*head, int(n_step), float(gamma), *tail), "bridges_hindsight_relabel_nstep")
+        abi.check(getattr(L, entry + "_nstep")(*head, int(n_step), float(gamma), *tail), entry + "_nstep")
     else:
-        abi.check(L.bridges_hindsight_relabel(*head, *tail), "bridges_hindsight_relabel")
+        abi.check(getattr(L, entry)(*head, *tail), entry)
     return out, count
 
 

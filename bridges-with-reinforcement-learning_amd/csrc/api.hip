@@ -951,8 +951,15 @@ int bridges_hindsight_relabel_scratch(int32_t E, int32_t G, int64_t* bytes) {
     return BRIDGES_OK;
 }
 
-// What both hindsight entries check and launch: fold = false stores the one-step rows [., W], fold = true the h-step rows [., W + 1].
-static int hindsight_relabel(bool fold, int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+int bridges_hindsight_per_step_scratch(int32_t E, int32_t G, int64_t* bytes) {
+    if (!bytes || E < 0 || G < 1 || G > HIND_MAX_GOALS) return fail_arg("bridges_hindsight_per_step_scratch");
+    *bytes = 2 * (int64_t)sizeof(int32_t) * (E > 0 ? (int64_t)E * G : 1);     // the rows of every (env, slot) (then their offsets), the masks
+    return BRIDGES_OK;
+}
+
+// What the four hindsight entries check and launch: fold = false stores the one-step rows [., W], fold = true the h-step rows
+// [., W + 1]; per_step = false the goals of the final structure, one set per slot, per_step = true one set per step.
+static int hindsight_relabel(bool per_step, bool fold, int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
                              const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
                              const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
                              const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step, double gamma, double* out,
@@ -973,8 +980,10 @@ static int hindsight_relabel(bool fold, int32_t E, int32_t K, int32_t W, int32_t
     if (!aligned(8, buf, shapes_dev, grid_x, grid_y, out) || !aligned(4, len, episode, gauss_k, count, scratch))
         return fail_arg("bridges_hindsight_relabel: misaligned pointer");
     int64_t need = 0;
-    if (int rc = bridges_hindsight_relabel_scratch(E, G, &need)) return rc;
-    if (scratch_bytes < need) return fail_arg("bridges_hindsight_relabel: scratch too small (bridges_hindsight_relabel_scratch)");
+    if (int rc = per_step ? bridges_hindsight_per_step_scratch(E, G, &need) : bridges_hindsight_relabel_scratch(E, G, &need)) return rc;
+    if (scratch_bytes < need)
+        return fail_arg(per_step ? "bridges_hindsight_per_step: scratch too small (bridges_hindsight_per_step_scratch)"
+                                 : "bridges_hindsight_relabel: scratch too small (bridges_hindsight_relabel_scratch)");
     if (E == 0) return BRIDGES_OK;
     HindArgs a;
     a.buf = buf; a.flags = flags; a.len = len; a.ended = ended; a.episode = episode; a.shapes = shapes_dev; a.grid_x = grid_x;
@@ -982,6 +991,21 @@ static int hindsight_relabel(bool fold, int32_t E, int32_t K, int32_t W, int32_t
     a.n_shapes = n_shapes; a.target_shape = target_shape; a.img = img;
     int32_t* cnt = (int32_t*)scratch;
     const int items = E * G;
+    if (per_step) {
+        // the count and the step mask of every (env, slot): one wave each, four per workgroup; the rows: one workgroup per
+        // (env, slot, step), E * G * K <= INT32_MAX of them
+        uint32_t* mask = (uint32_t*)(cnt + items);
+        const unsigned wgs = (unsigned)items * (unsigned)K;
+        if (int rc = launch("k_hindsight_step_count", k_hindsight_step_count, dim3((unsigned)ceil_div(items, 4)), dim3(256), 0, stream, a, cnt,
+                            mask))
+            return rc;
+        if (int rc = launch("k_hindsight_scan", k_hindsight_scan, dim3(1), dim3(HIND_SCAN_THREADS), 0, stream, items, cnt, count)) return rc;
+        if (fold)
+            return launch("k_hindsight_step_rows_nstep", k_hindsight_step_rows_nstep, dim3(wgs), dim3(TASK_THREADS), 0, stream, a,
+                          (const int32_t*)cnt, (const uint32_t*)mask, out, (int)n_step, gamma);
+        return launch("k_hindsight_step_rows", k_hindsight_step_rows, dim3(wgs), dim3(TASK_THREADS), 0, stream, a, (const int32_t*)cnt,
+                      (const uint32_t*)mask, out);
+    }
     // one wave per (env, slot), four per workgroup
     if (int rc = launch("k_hindsight_count", k_hindsight_count, dim3((unsigned)ceil_div(items, 4)), dim3(256), 0, stream, a, cnt)) return rc;
     if (int rc = launch("k_hindsight_scan", k_hindsight_scan, dim3(1), dim3(HIND_SCAN_THREADS), 0, stream, items, cnt, count)) return rc;
@@ -997,7 +1021,7 @@ int bridges_hindsight_relabel(int32_t E, int32_t K, int32_t W, int32_t T, int32_
                               const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
                               const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
                               int64_t scratch_bytes, void* stream) {
-    return hindsight_relabel(false, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes, target_shape,
+    return hindsight_relabel(false, false, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes, target_shape,
                                     grid_x, grid_y, img, gauss_k, 1, 0.0, out, count, scratch, scratch_bytes, stream);
 }
 
@@ -1006,8 +1030,26 @@ int bridges_hindsight_relabel_nstep(int32_t E, int32_t K, int32_t W, int32_t T, 
                                     int32_t env_id_base, const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape,
                                     const double* grid_x, const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step,
                                     double gamma, double* out, int32_t* count, void* scratch, int64_t scratch_bytes, void* stream) {
-    return hindsight_relabel(true, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes, target_shape,
+    return hindsight_relabel(false, true, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes, target_shape,
                                    grid_x, grid_y, img, gauss_k, n_step, gamma, out, count, scratch, scratch_bytes, stream);
+}
+
+int bridges_hindsight_per_step(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                               const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
+                               const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
+                               const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
+                               int64_t scratch_bytes, void* stream) {
+    return hindsight_relabel(true, false, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes,
+                             target_shape, grid_x, grid_y, img, gauss_k, 1, 0.0, out, count, scratch, scratch_bytes, stream);
+}
+
+int bridges_hindsight_per_step_nstep(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                                     const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed,
+                                     int32_t env_id_base, const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape,
+                                     const double* grid_x, const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step,
+                                     double gamma, double* out, int32_t* count, void* scratch, int64_t scratch_bytes, void* stream) {
+    return hindsight_relabel(true, true, E, K, W, T, G, buf, flags, len, ended, episode, seed, env_id_base, shapes_dev, n_shapes,
+                             target_shape, grid_x, grid_y, img, gauss_k, n_step, gamma, out, count, scratch, scratch_bytes, stream);
 }
 
 int bridges_priority_update(int64_t n_rec, int32_t W, int32_t col, double* rec, int64_t n, const int64_t* idx, const float* q_sa,

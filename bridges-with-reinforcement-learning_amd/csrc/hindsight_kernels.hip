@@ -310,4 +310,190 @@ __global__ __launch_bounds__(TASK_THREADS) void k_hindsight_rows_nstep(HindArgs 
     hind_rows<true>(a, off, total, out, n_step, gamma);
 }
 
+// ---- per-step goals (strategy "per_step", hindsight experience replay's "future"; header comment of bridges_hindsight_per_step) ----
+// One work item is (env, slot, step t < m'): its own draw, its own T targets -- block f >= t first, the others from the structure
+// after step f -- and at most one row.  Three launches again:
+//   k_hindsight_step_count  one wave per (env, slot): the boxes of the K blocks once, one per lane; then for every t the draw, the
+//                           targets (lane reads of the boxes) and the reached-test of steps < t -> the rows of the slot and the
+//                           32-bit mask of the steps that have one
+//   k_hindsight_scan        as above, on the counts
+//   k_hindsight_step_rows   four waves per (env, slot, t), a grid of E * G * K of which all but the set bits of the masks leave
+//                           after two loads: one pass of the k_hindsight_rows body -- the draw again, the T cube rasters, map and
+//                           prefix tables in LDS -- then wave 0 walks steps < t with the reached-test alone, relabels step t
+//                           (FOLD: steps t .. last, their lin kept in LDS) and stores row offset[slot] + popcount(mask below t).
+//                           (One workgroup per (env, slot) looping over its mask was measured too and was no faster; the loop
+//                           around the map build costs SGPR spills: DESIGN.md, "Per-step goals".)
+
+// Lane b < m: box and depth of the block that record b placed (hind_box on hind_block_verts: the bits of the walk of "final").
+struct HindLaneBoxes { double cx, cz, hx, hz, depth; };
+__device__ __forceinline__ HindLaneBoxes hind_lane_boxes(const HindArgs& a, const double* rows, int m, int lane) {
+    HindLaneBoxes lb = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < m; ++b) {
+        double vx, vz;
+        const int sh = hind_block_verts(a, rows + (size_t)b * a.W, lane, vx, vz);
+        const HindBox bx = hind_box(vx, vz, lane < a.shapes[sh].nv);
+        if (lane == b) { lb.cx = bx.cx; lb.cz = bx.cz; lb.hx = bx.hx; lb.hz = bx.hz; lb.depth = a.shapes[sh].depth; }
+    }
+    return lb;
+}
+__device__ __forceinline__ HindBox hind_box_of(const HindLaneBoxes& lb, int b) {
+    HindBox bx;
+    bx.cx = readlane_d(lb.cx, b); bx.cz = readlane_d(lb.cz, b); bx.hx = readlane_d(lb.hx, b); bx.hz = readlane_d(lb.hz, b);
+    return bx;
+}
+
+__device__ __forceinline__ int hind_eligible(const HindArgs& a, const double* rows, int m) {
+    return (m > 0 && !(rows[(size_t)(m - 1) * a.W + BRIDGES_REC_STABLE_N] > 0.5)) ? m - 1 : m;
+}
+
+__device__ __forceinline__ uint64_t hind_slot_key(const HindArgs& a, int e, int g) {
+    const uint64_t h0 = splitmix64((((a.seed & 0xFFFFFFFFull) << 32) | (uint32_t)(a.env_id_base + e)) ^ HIND_SALT);
+    const uint64_t h1 = splitmix64(h0 ^ (uint64_t)a.episode[e]);
+    return splitmix64(h1 ^ (uint64_t)g);
+}
+
+// The targets of work item (slot key h2, step t < mp): h3 = splitmix64(h2 ^ ((t + 1) << 8)), r_i = splitmix64(h3 ^ i), u_i = r_i >> 32;
+// f = t + ((u_0 * (mp - t)) >> 32); n = f + 1, idx = 0 .. n - 1, swap(idx[0], idx[f]), for i = 1 .. min(T, n) - 1:
+// swap(idx[i], idx[i + ((u_i * (n - i)) >> 32)]); target q = centre of block idx[q mod n] in lanes 3 q, 3 q + 2.  Integers only.
+__device__ __forceinline__ void hind_step_goals(const HindArgs& a, uint64_t h2, int t, int mp, int lane, const HindLaneBoxes& lb,
+                                                double& tgv) {
+    const uint64_t h3 = splitmix64(h2 ^ ((uint64_t)(t + 1) << 8));
+    const uint64_t u0 = splitmix64(h3) >> 32;
+    const int f = __builtin_amdgcn_readfirstlane(t + (int)((u0 * (uint64_t)(mp - t)) >> 32));
+    const int n = f + 1;
+    int idx = lane == 0 ? f : (lane == f ? 0 : lane);
+    const int nd = a.T < n ? a.T : n;
+    for (int i = 1; i < nd; ++i) {
+        const uint64_t u = splitmix64(h3 ^ (uint64_t)i) >> 32;
+        const int j = __builtin_amdgcn_readfirstlane(i + (int)((u * (uint64_t)(n - i)) >> 32));
+        const int vi = __builtin_amdgcn_readlane(idx, i), vj = __builtin_amdgcn_readlane(idx, j);
+        idx = lane == i ? vj : (lane == j ? vi : idx);
+    }
+    tgv = 0.0;
+    for (int q = 0; q < a.T; ++q) {
+        const int b = __builtin_amdgcn_readlane(idx, q % n);
+        const double cx = readlane_d(lb.cx, b), cz = readlane_d(lb.cz, b);
+        tgv = lane == 3 * q ? cx : (lane == 3 * q + 2 ? cz : tgv);
+    }
+}
+
+// The open targets in front of step t under the targets tgv: the reached-test of steps 0 .. t - 1 (0: the episode was over).
+__device__ __forceinline__ uint32_t hind_step_prefix(const HindArgs& a, int t, double tgv, const HindLaneBoxes& lb) {
+    uint32_t left = (1u << a.T) - 1u;
+    for (int s = 0; s < t && left != 0u; ++s) left = hind_reach(a, left, tgv, hind_box_of(lb, s), readlane_d(lb.depth, s));
+    return left;
+}
+
+__global__ __launch_bounds__(256) void k_hindsight_step_count(HindArgs a, int32_t* __restrict__ cnt, uint32_t* __restrict__ mask) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int item = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE));
+    if (item >= a.E * a.G) return;
+    const int e = item / a.G, g = item % a.G;
+    const int m = hind_len(a, e);
+    int n = 0;
+    uint32_t has = 0u;
+    if (m > 0) {
+        const double* rows = a.buf + (size_t)e * a.K * a.W;
+        const int mp = hind_eligible(a, rows, m);   // t < m': a collapsed last step has no later block to be a goal
+        if (mp > 0) {
+            const HindLaneBoxes lb = hind_lane_boxes(a, rows, mp, lane);
+            const uint64_t h2 = hind_slot_key(a, e, g);
+            for (int t = 0; t < mp; ++t) {
+                double tgv;
+                hind_step_goals(a, h2, t, mp, lane, lb, tgv);
+                if (hind_step_prefix(a, t, tgv, lb) != 0u) { has |= 1u << t; ++n; }     // else: over before t, no transition
+            }
+        }
+    }
+    if (lane == 0) { cnt[item] = n; mask[item] = has; }
+}
+
+template <bool FOLD>
+__device__ __forceinline__ void hind_step_rows(const HindArgs& a, const int32_t* __restrict__ off, const uint32_t* __restrict__ mask,
+                                               double* __restrict__ out, int n_step, double gamma) {
+    __shared__ float kz[TASK_KZ];
+    __shared__ uint64_t tb_l[IMG];
+    __shared__ float map_l[IMG * TASK_ROW];
+    __shared__ double pre_l[IMG * TASK_ROW];
+    __shared__ double lin_l[FOLD ? BRIDGES_NSTEP_MAX : 1];
+    const int item = blockIdx.x / a.K, t = blockIdx.x % a.K, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    const int e = item / a.G, g = item % a.G;
+    const int m = hind_len(a, e);
+    if (m == 0) return;                             // mid-episode (the whole workgroup leaves)
+    const uint32_t has = mask[item];
+    if (!((has >> t) & 1u)) return;                 // no row of this step
+    const int first = off[item];
+    for (int i = tid; i < TASK_KZ; i += TASK_THREADS) {
+        const int tap = i - TASK_KZ_PAD;
+        kz[i] = (tap >= 0 && tap < BRIDGES_GAUSS_TAPS) ? a.gauss_k[tap] : 0.f;
+    }
+    const double* rows = a.buf + (size_t)e * a.K * a.W;
+    const uint8_t* fl = a.flags + (size_t)e * a.K * 8;
+    const int mp = hind_eligible(a, rows, m);
+    const HindLaneBoxes lb = hind_lane_boxes(a, rows, mp, lane);
+    const uint64_t h2 = hind_slot_key(a, e, g);
+    const bridges_shape& cube = a.shapes[a.target_shape];
+    const int wout = FOLD ? a.W + 1 : a.W;
+    {
+        double tgv;
+        hind_step_goals(a, h2, t, mp, lane, lb, tgv);
+        // raster of the T target cubes at identity rotation, every wave (as k_hindsight_rows)
+        uint64_t bits = 0ull;
+        for (int q = 0; q < a.T; ++q) {
+            const double px = readlane_d(tgv, 3 * q), pz = readlane_d(tgv, 3 * q + 2);
+            const int v = lane < cube.nv ? lane : 0;
+            bits |= hind_raster(px + cube.vx[v], pz + cube.vz[v], cube, a, lane);
+        }
+        if (wv == 0) tb_l[lane] = bits;
+        __syncthreads();
+        task_map_prefix<false>(bits, tb_l, kz, map_l, pre_l, a.img, lane, wv, nullptr);
+        if (wv == 0) {
+            // ---- wave 0: steps t .. last under the targets of step t ----
+            uint32_t left = hind_step_prefix(a, t, tgv, lb);
+            double* o = out + (size_t)(first + __popc(has & ((1u << t) - 1u))) * wout;
+            const int hmax = FOLD ? n_step : 1;
+            double reward_d = 0.0, done_d = 0.0, lin_d = 0.0;
+            int h = 0;
+            for (int s = t; s < m && h < hmax; ++s) {
+                const double* row = rows + (size_t)s * a.W;
+                double vx, vz;
+                const int sh = hind_block_verts(a, row, lane, vx, vz);
+                const bridges_shape& sp = a.shapes[sh];
+                left = hind_reach(a, left, tgv, hind_box(vx, vz, lane < sp.nv), sp.depth);
+                const uint64_t rb = hind_raster(vx, vz, sp, a, lane);
+                double p_hi, p_lo;
+                raster_reward_fetch(rb, pre_l, lane, p_hi, p_lo);
+                const float base = (float)raster_reward_sum(p_hi, p_lo);             // k_raster's cand_lin
+                const bool st_frozen = fl[s * 8 + F_STABLE_FROZEN], st_free = fl[s * 8 + F_STABLE_UNFROZEN];
+                const bool truncated = fl[s * 8 + F_TRUNCATED], no_actions = fl[s * 8 + F_NO_ACTIONS];
+                const int n_reached = a.T - __popc(left);
+                const bool all_reached = left == 0u;
+                const float reward = !st_frozen ? -1.f : (all_reached ? (float)n_reached : (float)(-1 + n_reached));
+                const float lin = st_free ? base : (st_frozen ? base / 100.f : 0.f);
+                const bool done = !st_frozen || all_reached || truncated || no_actions;
+                reward_d = (double)reward; done_d = done ? 1.0 : 0.0; lin_d = (double)lin;
+                if (FOLD) lin_l[h] = lin_d;         // every lane the same value: each reads back what it wrote itself
+                ++h;
+                if (all_reached) break;             // the walk under these targets ends here
+            }
+            const double* last = rows + (size_t)(t + h - 1) * a.W;
+            if (FOLD)
+                hind_store_row<true>(a, last, rows + (size_t)t * a.W, reward_d, hind_return(lin_l, h, gamma), done_d, (double)h, tgv, lane, o);
+            else
+                hind_store_row<false>(a, last, last, reward_d, lin_d, done_d, 1.0, tgv, lane, o);
+        }
+    }
+}
+
+__global__ __launch_bounds__(TASK_THREADS) void k_hindsight_step_rows(HindArgs a, const int32_t* __restrict__ off,
+                                                                     const uint32_t* __restrict__ mask, double* __restrict__ out) {
+    hind_step_rows<false>(a, off, mask, out, 1, 0.0);
+}
+
+__global__ __launch_bounds__(TASK_THREADS) void k_hindsight_step_rows_nstep(HindArgs a, const int32_t* __restrict__ off,
+                                                                           const uint32_t* __restrict__ mask, double* __restrict__ out,
+                                                                           int n_step, double gamma) {
+    hind_step_rows<true>(a, off, mask, out, n_step, gamma);
+}
+
 }  // namespace bridges

@@ -961,14 +961,17 @@ def eval_particles_from_args(args):
 
 def add_hindsight_arguments(p):
     """--hindsight / --hindsight_goals / --hindsight_fold: shared with the tools that train through the vectorised loop."""
-    p.add_argument("--hindsight", choices=("final",), default=argparse.SUPPRESS,
+    p.add_argument("--hindsight", choices=("final", "per_step"), default=argparse.SUPPRESS,
                    help="With --random_targets T only: hindsight goal relabelling -- every episode that ends is stored a second "
                         "time under T targets its own final structure reached (the centres of the bounding boxes of blocks drawn "
-                        "from it), with the rewards the env would have given under them. The log gains hindsight_rows.")
+                        "from it), with the rewards the env would have given under them. per_step (hindsight experience replay's 'future' "
+                        "strategy): every transition gets goals of its own instead -- a block the episode places at that step or "
+                        "later, and others from the structure as it then stands. The log gains hindsight_rows.")
     p.add_argument("--hindsight_goals", type=int, default=argparse.SUPPRESS, metavar="G",
-                   help="With --hindsight final: relabelled copies of every finished episode, 1..4 (1).")
+                   help="With --hindsight final: relabelled copies of every finished episode, 1..4 (1); with --hindsight per_step: "
+                        "relabelled rows per transition.")
     p.add_argument("--hindsight_fold", action="store_true", default=argparse.SUPPRESS,
-                   help="With --hindsight final: run it beside --n_step n > 1 -- the relabelled episode is folded on the device into "
+                   help="With --hindsight final or per_step: run it beside --n_step n > 1 -- the relabelled episode is folded on the device into "
                         "h-step rows, the return taken over the relabelled linear rewards; an episode whose last relabelled step is "
                         "not terminal still stores its last n - 1 starts, which bootstrap from the final state.")
 
@@ -977,23 +980,24 @@ def check_hindsight(args):
     """--hindsight / --hindsight_goals: refused in words (SystemExit) where the loop cannot run them, before anything touches the GPU."""
     if 'hindsight' not in args:
         if 'hindsight_goals' in args:
-            raise SystemExit("--hindsight_goals counts the relabelled copies of an episode: it needs --hindsight final")
+            raise SystemExit("--hindsight_goals counts the relabelled copies of an episode: it needs --hindsight final or per_step")
         if args.get('hindsight_fold'):
-            raise SystemExit("--hindsight_fold folds the relabelled rows into n-step returns: it needs --hindsight final")
+            raise SystemExit("--hindsight_fold folds the relabelled rows into n-step returns: it needs --hindsight final or per_step")
         return
     if not 1 <= args.get('hindsight_goals', 1) <= 4:
         raise SystemExit("--hindsight_goals must be 1..4")
+    opt = f"--hindsight {args['hindsight']}"
     if not args.get('random_targets'):
-        raise SystemExit("--hindsight final needs --random_targets T (and with it --num_envs N, N > 1): only a record that ends "
+        raise SystemExit(f"{opt} needs --random_targets T (and with it --num_envs N, N > 1): only a record that ends "
                          "in its own targets can be given others")
     if args.get('random_bridge_length') is not None or args.get('random_tower_height') is not None or args.get('curriculum'):
-        raise SystemExit("--hindsight final does not run on a task family (--random_bridge_length / --random_tower_height) or "
+        raise SystemExit(f"{opt} does not run on a task family (--random_bridge_length / --random_tower_height) or "
                          "with --curriculum: a family's task is its class, and a box centre names none")
     if args.get('n_step', 1) > 1 and not args.get('hindsight_fold'):
-        raise SystemExit("--hindsight final needs --n_step 1 or --hindsight_fold: an h-step row's return has to be folded again under "
+        raise SystemExit(f"{opt} needs --n_step 1 or --hindsight_fold: an h-step row's return has to be folded again under "
                          "the new targets")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("--hindsight final runs on one rank only: the relabelled rows are not part of the all-gather")
+        raise SystemExit(f"{opt} runs on one rank only: the relabelled rows are not part of the all-gather")
 
 
 def hindsight_from_args(args):

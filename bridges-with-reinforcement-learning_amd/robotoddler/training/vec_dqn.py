@@ -166,6 +166,15 @@ class VecDQN:
         last column; the end of a walk flushes its pending starts whether or not its last step is done -- under hindsight targets
         a final step that is not terminal bootstraps like any other).  With n_step = 1 it is hindsight="final" bit for bit.
         Without it hindsight="final" with n_step > 1 stays refused.
+        ``hindsight="per_step"`` (every condition and refusal of "final", hindsight_fold included): hindsight experience replay's
+        strategy "future".  It is not called "future" here because that value was refused by name before the strategy existed and
+        stays refused: the option names what the loop does -- goals per step.  Every transition t of an episode that ends gets,
+        per slot g < ``hindsight_goals``, T goals of its own: the box centre of a block f >= t of the episode, drawn per (g, t),
+        and T - 1 more from the structure as it stands after step f; the transition is pushed once per slot under them, unless
+        the episode would have been over before step t (bridges_hindsight_per_step / _nstep, the rule in include/bridges_hip.h).
+        So early transitions no longer see goals that only blocks placed much later reach by chance, and G counts relabelled rows
+        per transition.  Buffer, counts, host waits, checkpoint keys and the training step are those of "final"; a checkpoint of
+        one strategy is refused by the other ((hindsight, hindsight_goals) is recorded).
         ``search_every=N`` (N >= 1; one rank; an extension: search in training): every N-th lockstep(), after
         the lock-step's own rows are pushed and before train_steps, a beam search of width ``search_width`` = B (1..16, default
         8) with the policy net's q as the heuristic runs on the tasks the rollout envs 0 .. ``search_tasks`` - 1 (M, at most the
@@ -310,24 +319,25 @@ class VecDQN:
         self.per_env_tasks, self.per_env_obstacles = bool(per_env_tasks), bool(per_env_obstacles)
         self.task_channels = bool(task_channels)
         self.hindsight, self.hindsight_goals, self.hindsight_fold = hindsight, int(hindsight_goals), bool(hindsight_fold)
-        if self.hindsight not in (None, "final"):
-            raise ValueError(f"VecDQN(hindsight={hindsight!r}): None or 'final'")
+        if self.hindsight not in (None, "final", "per_step"):
+            raise ValueError(f"VecDQN(hindsight={hindsight!r}): None, 'final' or 'per_step'")
         if self.hindsight is None and self.hindsight_goals != 1:
-            raise ValueError("VecDQN(hindsight_goals=...) counts the relabelled copies of an episode: it needs hindsight='final'")
+            raise ValueError("VecDQN(hindsight_goals=...) counts the relabelled copies of an episode: it needs hindsight='final' or 'per_step'")
         if self.hindsight is None and self.hindsight_fold:
-            raise ValueError("VecDQN(hindsight_fold=True) folds the relabelled rows into n-step returns: it needs hindsight='final'")
+            raise ValueError("VecDQN(hindsight_fold=True) folds the relabelled rows into n-step returns: it needs hindsight='final' or 'per_step'")
         if self.hindsight is not None:
+            opt = f"VecDQN(hindsight={self.hindsight!r})"
             if not 1 <= self.hindsight_goals <= 4:
                 raise ValueError(f"VecDQN(hindsight_goals={hindsight_goals}): an episode is relabelled 1..4 times")
             if not self.per_env_tasks:
-                raise ValueError("VecDQN(hindsight='final') needs per_env_tasks=True: only a record that ends in its own targets can be given others")
+                raise ValueError(f"{opt} needs per_env_tasks=True: only a record that ends in its own targets can be given others")
             if getattr(env, "task_family", None) is not None or curriculum is not None:
-                raise ValueError("VecDQN(hindsight='final') does not run on a task family (RandomBridges) or under a curriculum: a family's task is its class, and a box centre names none")
+                raise ValueError(f"{opt} does not run on a task family (RandomBridges) or under a curriculum: a family's task is its class, and a box centre names none")
             if self.n_step > 1 and not self.hindsight_fold:
-                raise ValueError("VecDQN(hindsight='final') needs n_step=1 or hindsight_fold=True: an h-step row's return has to be "
+                raise ValueError(f"{opt} needs n_step=1 or hindsight_fold=True: an h-step row's return has to be "
                                  "folded again under the new targets")
             if D.active():
-                raise ValueError("VecDQN(hindsight='final') runs on one rank only: the relabelled rows are not part of the all-gather")
+                raise ValueError(f"{opt} runs on one rank only: the relabelled rows are not part of the all-gather")
         if self.task_channels:
             self._check_task_channels(policy_net, target_net, env)
         if getattr(env, "per_env_obstacles", False) and not self.per_env_obstacles:
@@ -386,6 +396,7 @@ class VecDQN:
         # hindsight relabelling: the running episode of every env, in the ring's width (n-step returns: one-step records, one
         # column narrower, folded as they are relabelled)
         self.hindsight_buffer = (R.HindsightBuffer(env.E, self.ring.width, self.device, goals=self.hindsight_goals, n_blocks=env.K,
+                                                   strategy=self.hindsight or "final",
                                                    **(dict(n_step=self.n_step, gamma=self.gamma) if self.n_step > 1 else {}))
                                  if self.hindsight is not None else None)
         self.hindsight_rows = 0                              # relabelled rows the last lock-step pushed

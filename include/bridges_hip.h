@@ -1030,6 +1030,47 @@ int bridges_hindsight_relabel_nstep(int32_t E, int32_t K, int32_t W, int32_t T, 
                                     const double* grid_x, const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step,
                                     double gamma, double* out /* [E*K*G, W+1] */, int32_t* count, void* scratch,
                                     int64_t scratch_bytes, void* stream);
+/* --- hindsight relabelling with per-step goals ("per_step" strategy: hindsight experience replay's "future") ---------
+ * Every transition of an episode that ended in this lock-step is written again, G times, under T targets that the episode
+ * achieves from that transition onward.  Inputs, shape table, grids and kernel taps are bridges_hindsight_relabel's, and so are
+ * m, the eligible blocks m' and the reading of a record.  One work item is (ended env e, slot g < G, step t < m'); it emits at
+ * most one row.  (With m' = m - 1 the collapsed last step m - 1 has no later block to be a goal: it emits nothing, the rollout's
+ * own record carries the collapse.)
+ *   draw: the "hind_rng" stream with one more key -- h2 as there (seed, env_id_base + e, episode[e], g);
+ *     h3 = splitmix64(h2 ^ ((t + 1) << 8));  r_i = splitmix64(h3 ^ i);  u_i = r_i >> 32                 -- integer arithmetic only
+ *   future block: f = t + ((u_0 * (m' - t)) >> 32), in [t, m' - 1].
+ *   goals, from the structure as it stands after step f: n = f + 1, idx = 0 .. n - 1; swap(idx[0], idx[f]); for i = 1 ..
+ *     min(T, n) - 1: swap(idx[i], idx[j]), j = i + ((u_i * (n - i)) >> 32).  Target q = (cx, 0, cz), the bounding-box centre of
+ *     block idx[q mod n], the box taken as bridges_env_step's reached-test takes it.  Target 0 is always block f's own centre.
+ *   existence: bridges_env_step's reached-test (the target after a reached one is skipped) of steps 0 .. t - 1 under these
+ *     targets; if it leaves no target open the episode was over before step t, the transition does not exist, nothing is emitted.
+ *   row (bridges_hindsight_per_step): record t with REWARD, LIN, DONE and the 3 T target values of the tail replaced by what
+ *     bridges_env_step records at step t under these targets -- the expressions of bridges_hindsight_relabel's rows, the open
+ *     targets being those the walk 0 .. t leaves.  Every other column is copied.
+ *   h-step row (bridges_hindsight_per_step_nstep), in the form of bridges_hindsight_relabel_nstep: the walk under the goals of t
+ *     runs from step t to the first step that leaves no target open, or else to step m - 1 (a collapsed last step included);
+ *     h = min(n_step, walk_end - t + 1), last = t + h - 1; the row is record last relabelled under the goals of t, with
+ *     REC_LIN = acc = 0, disc = 1; for k = 0 .. h-1: acc += disc * lin(step t + k); disc *= gamma (binary64, in this order, no
+ *     fused multiply-add), REC_STABLE_S and REC_TD of record t, and h in one more column, W.  An open end flushes: a start
+ *     whose walk ends before n_step steps is stored with its shorter h whether or not its last step has DONE.  n_step = 1 gives
+ *     the one-step rows with a column of 1.0 appended, bit for bit.
+ * out [E * K * G, W] (nstep: [E * K * G, W + 1]) f64: the rows compacted to the front, env ascending, then g, then t; *count
+ * (device i32) their number; rows beyond it are not written.  Envs in mid-episode emit nothing; the inputs are only read.
+ * Three launches (count with a step mask per (env, slot), scan, rows), no atomics, no host wait: the same bits on every call.
+ * scratch: bridges_hindsight_per_step_scratch(E, G) bytes (a count and a mask per (env, slot)), caller-owned, overwritten.
+ * Returns -1 and launches nothing for whatever the sibling entry of the "final" strategy refuses.  E == 0 returns 0. */
+int bridges_hindsight_per_step_scratch(int32_t E, int32_t G, int64_t* bytes);
+int bridges_hindsight_per_step(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                               const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed, int32_t env_id_base,
+                               const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape, const double* grid_x,
+                               const double* grid_y, int32_t img, const float* gauss_k, double* out, int32_t* count, void* scratch,
+                               int64_t scratch_bytes, void* stream);
+int bridges_hindsight_per_step_nstep(int32_t E, int32_t K, int32_t W, int32_t T, int32_t G, const double* buf, const uint8_t* flags,
+                                     const int32_t* len, const uint8_t* ended, const uint32_t* episode, uint64_t seed,
+                                     int32_t env_id_base, const bridges_shape* shapes_dev, int32_t n_shapes, int32_t target_shape,
+                                     const double* grid_x, const double* grid_y, int32_t img, const float* gauss_k, int32_t n_step,
+                                     double gamma, double* out /* [E*K*G, W+1] */, int32_t* count, void* scratch,
+                                     int64_t scratch_bytes, void* stream);
 
 /* Inference epilogues of the conv Q-networks (robotoddler/models/cv.py:5-17, 41-73, 108-170: Conv2d -> ReLU
  * [-> MaxPool2d(2)]), one pass instead of torch's three; bit-identical to relu(conv + bias) / maxpool(relu(conv + bias)).

@@ -6,7 +6,10 @@ write (two indexed copies) is timed beside them.  Warm-up first; prints one JSON
     python tools/hindsight_relabel_bench.py [--envs 4096] [--random_targets 3] [--hindsight_goals 1] [--max_steps 15] [--reps 40]
 The work of a call grows with the episodes that ended: ended_per_call and rows_per_call are printed beside the times.
 --n_step n: in front of those calls, on the same buffers (the operator only reads them), the folding entry
-(bridges_hindsight_relabel_nstep, gamma 0.95) and the one-step entry, alternating likewise: nstep_fold and one_step in the line."""
+(bridges_hindsight_relabel_nstep, gamma 0.95) and the one-step entry, alternating likewise: nstep_fold and one_step in the line.
+--strategy per_step: on the same buffers again, the per-step entry (bridges_hindsight_per_step; with --n_step n its folding
+sibling) on the envs that ended and with nothing ended, alternating with the "final" calls: per_step and per_step_nothing_ended in
+the line, with the rows it emits per call and the cost per emitted row beside "final"'s cost per (episode, slot)."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bridges-with-reinforcement-learning_amd")]
@@ -24,6 +27,8 @@ ap.add_argument("--hindsight_goals", type=int, default=1, metavar="G")
 ap.add_argument("--max_steps", type=int, default=15)
 ap.add_argument("--reps", type=int, default=40)
 ap.add_argument("--n_step", type=int, default=0, metavar="n", help="also time the folding entry at this n against the one-step entry")
+ap.add_argument("--strategy", choices=("final", "per_step"), default="final",
+                help="per_step: also time the per-step entry, alternating with the 'final' entry on the same buffers")
 ap.add_argument("--warmup", type=int, default=20, help="lock-steps before the timed ones (episodes of every length are then in flight)")
 a = ap.parse_args()
 assert a.reps >= 20
@@ -37,6 +42,17 @@ nothing = torch.zeros(E, dtype=torch.bool, device=dev)
 if a.n_step:
     out_n = torch.empty((hb.out.shape[0], hb.out.shape[1] + 1), dtype=torch.float64, device=dev)
     count_n = torch.zeros(1, dtype=torch.int32, device=dev)
+if a.strategy == "per_step":
+    out_s = torch.empty((hb.out.shape[0], hb.out.shape[1] + bool(a.n_step)), dtype=torch.float64, device=dev)
+    count_s = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch_s = torch.empty(dqn_ops.hindsight_relabel_scratch(E, hb.goals, "per_step"), dtype=torch.uint8, device=dev)
+
+
+def per_step(ended):
+    """The per-step entry on the buffer as it stands (nothing is emptied)."""
+    kw = dict(n_step=a.n_step, gamma=0.95) if a.n_step else {}
+    return dqn_ops.hindsight_relabel(env, hb.rows, hb.flags, hb.length, ended, hb.episode, hb.goals, out=out_s, count=count_s,
+                                     scratch=scratch_s, strategy="per_step", **kw)
 
 
 def entry(ended, fold):
@@ -54,8 +70,9 @@ def timed(fn):
     return start.elapsed_time(stop) * 1e3, out                      # us
 
 
-times = dict(relabel=[], nothing_ended=[], buffer_write=[], **(dict(nstep_fold=[], one_step=[]) if a.n_step else {}))
-ended_n, rows_n = [], []
+times = dict(relabel=[], nothing_ended=[], buffer_write=[], **(dict(nstep_fold=[], one_step=[]) if a.n_step else {}),
+             **(dict(per_step=[], per_step_nothing_ended=[]) if a.strategy == "per_step" else {}))
+ended_n, rows_n, rows_s = [], [], []
 for it in range(a.warmup + a.reps):
     env.select_random()
     rec = R.pack_state(env, env.cand_offset[:E].long() + env.buf["sel_index"].long())
@@ -70,6 +87,10 @@ for it in range(a.warmup + a.reps):
     got = {}
     for name in (("nstep_fold", "one_step") if it % 2 else ("one_step", "nstep_fold")) if a.n_step else ():
         got[name], _ = timed(lambda: entry(ended, name == "nstep_fold"))
+    for name in (("per_step_nothing_ended", "per_step") if it % 2 else ("per_step", "per_step_nothing_ended")) if a.strategy == "per_step" else ():
+        got[name], out = timed(lambda: per_step(ended if name == "per_step" else nothing))
+        if name == "per_step":
+            rows_step = int(out[1].item())
     for name in order:                                               # (the call with nothing ended leaves the buffer as it is)
         got[name], out = timed(lambda: hb.relabel(env, ended if name == "relabel" else nothing))
         if name == "relabel":
@@ -80,11 +101,18 @@ for it in range(a.warmup + a.reps):
             times[name].append(t)
         ended_n.append(int(ended.sum().item()))
         rows_n.append(rows)
+        if a.strategy == "per_step":
+            rows_s.append(rows_step)
 summary = {}
 for name, t in times.items():
     t = np.array(t)
     q1, med, q3 = np.percentile(t, [25, 50, 75])
     summary[name] = dict(median_us=float(med), min_us=float(t.min()), max_us=float(t.max()), iqr_us=float(q3 - q1), calls=len(t))
+if a.strategy == "per_step":
+    work = summary["per_step"]["median_us"] - summary["per_step_nothing_ended"]["median_us"]
+    final = summary["relabel"]["median_us"] - summary["nothing_ended"]["median_us"]
+    summary.update(rows_per_call_per_step=float(np.mean(rows_s)), us_per_row_per_step=work / max(np.mean(rows_s), 1e-9),
+                   us_per_episode_slot_final=final / max(np.mean(ended_n) * hb.goals, 1e-9))
 if a.n_step:
     summary["nstep_minus_one_step_us"] = summary["nstep_fold"]["median_us"] - summary["one_step"]["median_us"]
 print(json.dumps(dict(config=vars(a), **summary, ended_per_call=float(np.mean(ended_n)), rows_per_call=float(np.mean(rows_n)),
